@@ -8,10 +8,15 @@ GPU, inputs and outputs resident in HBM.  A "step" is one serviceFunction() body
 so there is no data-path collective; torch.distributed is used only for the barrier
 and the max-over-ranks of the elapsed time.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 prints ONE JSON line on rank 0, with `roofline` (HBM read roofline of the wave-scan
-kernel) and `cpu_baseline` (the CPU oracle timed on this node's host cores, N=1 only).
+kernel, from the HIP events of the timed steps).  A plain run sets up, warms up, times the K
+steps and reports them, nothing else.  --full adds what else the line has carried: the
+empirical read ceiling (a probe kernel of its own), the oracle check of two channels,
+`cpu_baseline` (the CPU oracle timed on this node's host cores, N=1 only), `few_channels`
+and, for the headline configuration, the other configurations measured beside it.
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 
 N > 1: one process per GPU.  Under a launcher (torchrun: WORLD_SIZE / RANK / LOCAL_RANK / MASTER_* in the
 environment) this process is one rank.  Started plainly with --gpus N > 1 it is the launcher itself: before
@@ -50,15 +55,21 @@ def parse():
                     help="carrier offset bound of the stimulus: M*dphi per symbol uniform in [-cfo, cfo] rad (section 8(d): 1e-3)")
     ap.add_argument("--sigma", type=float, default=0.01, help="noise per component of the stimulus (section 8(d): 0.01)")
     ap.add_argument("--scale", type=float, default=1.0, help="amplitude factor applied to the whole stimulus")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line carries: the empirical read ceiling, the oracle check, the CPU "
+                         "baseline, `few_channels` and the other configurations (the --no-* / --check options below select among them)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (soft, bits, phase, sampleIndex of a fixed, seeded sample of channels, "
+                         "at most 64 MB) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=1.5, help="wall seconds of the CPU baseline sample")
     ap.add_argument("--check", dest="check", action="store_true", default=True,
-                    help="replay two channels of the run through the oracle afterwards and compare all four streams (default)")
+                    help="--full: replay two channels of the run through the oracle afterwards and compare all four streams (default)")
     ap.add_argument("--no-check", dest="check", action="store_false")
     ap.add_argument("--no-few", dest="no_few", action="store_true",
-                    help="skip the one-channel measurement (BASELINE configs[1]) that the default run appends as `few_channels`")
+                    help="--full: skip the one-channel measurement (BASELINE configs[1]) appended as `few_channels`")
     ap.add_argument("--no-extra", dest="no_extra", action="store_true",
-                    help="skip the other configurations the default single-GPU run appends to its line (`configs3_per_gpu`, `mixed`, "
+                    help="--full: skip the other configurations a single-GPU run appends to its line (`configs3_per_gpu`, `mixed`, "
                          "`worst_case`, `few_channels_64` / `_512` / `_1024`, `end_to_end`), each measured like the headline with its own oracle check")
     ap.add_argument("--strong", type=int, default=0, metavar="TOTAL_CHANNELS",
                     help="strong scaling: TOTAL_CHANNELS channels shared by the ranks (BASELINE configs[3]: "
@@ -71,7 +82,10 @@ def parse():
                          "the data-dependent worst case of the wave-scan kernel")
     ap.add_argument("--stamps", default="", metavar="FILE.npy",
                     help="(diagnostic builds, -DPSK_DIAG_STAMP) save every wave's start / end tick of the last step")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def cpu_baseline(iq_host, M, S, A, n, wall_budget):
@@ -430,6 +444,47 @@ def end_to_end(pl, torch, dev, dev_index, C=4096, N=32768, M=4, S=8, calls=3):
     return res
 
 
+DUMP_BYTES = 64 << 20
+DUMP_SEED = 0x5EED4000
+
+
+def dump_outputs(path, out, soft, bits, phase, sidx):
+    """--dump-outputs DIR: what the last timed step handed its caller, for a fixed, seeded sample of channels (0 and C-1
+    first, then a seeded permutation) that fits in DUMP_BYTES.  The four output ports of the sampled channels, each one's
+    rows concatenated in channel order, as float32 (the int16 streams widen exactly): soft.npy, bits.npy, phase.npy,
+    sample_index.npy; counts.npy (float64) has one row per sampled channel: channel, n_symbols, n_bits, n_sampleIndex.
+    A single channel larger than DUMP_BYTES is cut to a prefix of its symbols."""
+    import numpy as np
+    import torch
+
+    C = len(out)
+    counts = np.array([(c, out[c].n_symbols, out[c].n_bits, out[c].n_sampleIndex) for c in range(C)], np.int64)
+    per_channel = 4 * (3 * counts[:, 1] + counts[:, 2] + counts[:, 3]) + 32  # soft 2n, phase n, bits, sampleIndex; counts row
+    budget = DUMP_BYTES - 1024  # (.npy headers)
+    rng = np.random.default_rng(DUMP_SEED)
+    order = [0] + ([C - 1] if C > 1 else []) + [c for c in rng.permutation(C).tolist() if c not in (0, C - 1)]
+    take, total = [], 0
+    for c in order:
+        if total + per_channel[c] > budget:
+            break
+        take.append(c)
+        total += per_channel[c]
+    if not take:  # one channel over the budget: a prefix of its symbols
+        c, n, nb, ni = (int(v) for v in counts[0])
+        m = (budget - 32) // (4 * (3 + -(-nb // max(n, 1)) + 1))
+        counts[0, 1:] = (m, nb * m // n, ni * m // n)
+        take = [0]
+    take.sort()
+    sel = counts[take]
+    idx = torch.tensor(take, device=soft.device)
+    rows = {"soft": (soft, 2 * sel[:, 1]), "bits": (bits, sel[:, 2]), "phase": (phase, sel[:, 1]), "sample_index": (sidx, sel[:, 3])}
+    os.makedirs(path, exist_ok=True)
+    for name, (t, n) in rows.items():
+        host = t.index_select(0, idx).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.concatenate([host[i, : n[i]] for i in range(len(take))]).astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), sel.astype(np.float64))
+
+
 def cpu_model():
     try:
         for l in open("/proc/cpuinfo"):
@@ -643,9 +698,11 @@ def main():
     # HIP events on the stream the kernels run on
     dev_ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
     dev_ms_avg = sum(dev_ms) / len(dev_ms)
-    # the box's empirical read ceiling over the same input buffer: 16-byte
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, soft, bits, phase, sidx)
+    # (--full) the box's empirical read ceiling over the same input buffer: 16-byte
     # loads and nothing else, so that "% of peak" and "% of achievable" can both be stated
-    probe_ms = h.probe_read_ms(iq.data_ptr(), iq.numel() * 4, reps=5)
+    probe_ms = h.probe_read_ms(iq.data_ptr(), iq.numel() * 4, reps=5) if a.full else None
     st = h.stats()
     n_out = int(out[0].n_symbols)
     if a.chain_hist and rank == 0:
@@ -727,20 +784,20 @@ def main():
             "algorithmic_write_bytes_per_launch": alg_write_bytes,
             "launch_ms_avg": dev_ms_avg,
             "launch_ms_min": dev_ms[0],
-            "empirical_read_ceiling": alg_read_bytes / (probe_ms * 1e-3) / 1e9,
-            "frac_of_empirical_read_ceiling": probe_ms / dev_ms_avg,
+            "empirical_read_ceiling": alg_read_bytes / (probe_ms * 1e-3) / 1e9 if a.full else None,
+            "frac_of_empirical_read_ceiling": probe_ms / dev_ms_avg if a.full else None,
         },
         "kernel_stats": st,
     }
 
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         n_host = min(C, 64)
         iq_host = iq[:n_host].cpu().numpy()
         res["cpu_baseline"] = cpu_baseline(iq_host, M, S, a.numAvg, a.phaseAvg, a.cpu_seconds)
         res["cpu_baseline"]["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
         res["cpu_baseline"]["cpu_model"] = cpu_model()
 
-    if a.check and rank == 0:
+    if a.full and a.check and rank == 0:
         from oracle import pyoracle as po
 
         # replay channel 0 and C-1 through the oracle with the same packetisation
@@ -766,10 +823,10 @@ def main():
         res["check"] = {"channels": [0, C - 1], "calls_replayed": a.warmup + a.steps, "bits_index_exact": True,
                         "soft_max_rel_err": worst, "soft_phase_bit_identical": bool(same)}
 
-    if rank == 0 and world == 1 and not a.mixed and not a.no_few:
+    if a.full and rank == 0 and world == 1 and not a.mixed and not a.no_few:
         res["few_channels"] = few_channels(pl, torch, dev, dev_index, M, S, a.numAvg, a.phaseAvg, a.check)
 
-    if rank == 0 and world == 1 and headline and not a.phase0 and not a.no_extra:
+    if a.full and rank == 0 and world == 1 and headline and not a.phase0 and not a.no_extra:
         # the other BASELINE configurations and the two ends of SURVEY section 8(d), measured beside the headline in the same run
         h.close()
         del iq, soft, phase, sidx, bits

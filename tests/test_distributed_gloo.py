@@ -110,7 +110,7 @@ def test_bench_launcher_refuses_more_ranks_than_devices():
 def test_bench_two_ranks_share_the_gpu():
     """The real rank path (HIP handles, kernels, events, the oracle check of --check) under the launcher, two
     ranks on the one GPU of the test box (gloo for the barrier and the reductions: RCCL wants a GPU per rank)."""
-    r = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--channels", "256", "--nsamp", "16384", "--check",
+    r = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--channels", "256", "--nsamp", "16384", "--full", "--check",
                     "--no-cpu-baseline"], {"PSK_BENCH_BACKEND": "gloo", "PSK_BENCH_SHARE_GPU": "1"}, timeout=600)
     assert r["n_gpus"] == 2 and r["check"]["bits_index_exact"] and r["check"]["soft_max_rel_err"] == 0.0
     assert r["config"]["channels_per_gpu"] == 256
@@ -126,7 +126,7 @@ def test_bench_rank_through_rccl():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    r = _run_bench(["--steps", "3", "--warmup", "2", "--channels", "256", "--nsamp", "16384", "--no-cpu-baseline"],
+    r = _run_bench(["--steps", "3", "--warmup", "2", "--channels", "256", "--nsamp", "16384", "--full", "--no-cpu-baseline"],
                    {"PSK_BENCH_FORCE_DIST": "1", "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1",
                     "MASTER_PORT": str(port), "HSA_ENABLE_IPC_MODE_LEGACY": "0"}, timeout=600, keep_world=True)
     assert r["n_gpus"] == 1 and r["check"]["soft_phase_bit_identical"]

@@ -22,7 +22,7 @@ cd $R
 for r in $(seq 1 $reps); do
   for i in $(seq 0 $((n-1))); do
     cp /tmp/lib_variant_$i.so psk_soft_amd/libpsk_soft_hip.so
-    python bench.py --steps 20 --warmup 10 --no-cpu-baseline --no-few $bargs --stamps $out/stamps_$i.npy 2>/dev/null | tail -1 | python -c "
+    python bench.py --steps 20 --warmup 10 --full --no-cpu-baseline --no-few $bargs --stamps $out/stamps_$i.npy 2>/dev/null | tail -1 | python -c "
 import sys,json,numpy as np
 d=json.loads(sys.stdin.read())
 a=np.load('$out/stamps_$i.npy'); t0,t1=a[:,0],a[:,1]

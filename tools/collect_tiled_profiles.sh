@@ -8,7 +8,7 @@ mkdir -p $out
 cd $R
 tools/tiled_sweep.sh "1 16 64 256 512" 1048576 > $out/sweep_channels.txt 2>&1
 tools/tiled_sweep2.sh "1 64 512" "16384 131072" > $out/sweep_short_calls.txt 2>&1
-python3 bench.py > $out/bench.json 2> $out/bench.err
+python3 bench.py --full > $out/bench.json 2> $out/bench.err
 tools/prof_tiled.sh "1 64 256" 1048576 $tag/prof > $out/kernel_stats.txt 2>&1
 for c in 1 64 256; do
   f=$(find $out/prof/c$c -name "*kernel_stats.csv" | head -1)

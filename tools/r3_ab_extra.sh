@@ -16,7 +16,7 @@ cd $R
 for r in 1 2 3; do
   for i in $(seq 0 $((n-1))); do
     cp /tmp/lib_variant_$i.so psk_soft_amd/libpsk_soft_hip.so
-    python bench.py --steps 200 --warmup 50 --no-cpu-baseline --no-few --no-extra $bargs 2>/dev/null | tail -1 | python -c "
+    python bench.py --steps 200 --warmup 50 --full --no-cpu-baseline --no-few --no-extra $bargs 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 print('RUN $i ms_per_step %.4f launch %.4f check %s' % (d['ms_per_step'], d['roofline']['launch_ms_avg'], d.get('check',{}).get('soft_phase_bit_identical')))"

@@ -8,13 +8,13 @@ cd $R
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o /tmp/chain_probe tools/micro/mfma_lds_chain_probe.hip > $out/chain_probe.txt 2>&1 \
   && timeout -k 10 120 /tmp/chain_probe >> $out/chain_probe.txt 2>&1
 echo "chain probe done: $(tail -1 $out/chain_probe.txt | cut -c1-200)"
-timeout -k 10 300 python bench.py > $out/bench_base.json 2> $out/bench_base.err || { echo "baseline bench failed"; tail -5 $out/bench_base.err; exit 1; }
+timeout -k 10 300 python bench.py --full > $out/bench_base.json 2> $out/bench_base.err || { echo "baseline bench failed"; tail -5 $out/bench_base.err; exit 1; }
 python - <<PY
 import json
 d = json.load(open("$out/bench_base.json"))
 print("baseline: ms_per_step %.4f launch_ms_avg %.4f frac %.4f chain_blocks %d check %s" % (d["ms_per_step"], d["roofline"]["launch_ms_avg"], d["roofline"]["frac"], d["kernel_stats"]["fit_chain_blocks"], d.get("check")))
 PY
-timeout -k 10 300 python bench.py --phase0 --no-cpu-baseline --no-few > $out/bench_phase0.json 2> $out/bench_phase0.err || { echo "phase0 bench failed"; tail -5 $out/bench_phase0.err; }
+timeout -k 10 300 python bench.py --phase0 --full --no-cpu-baseline --no-few > $out/bench_phase0.json 2> $out/bench_phase0.err || { echo "phase0 bench failed"; tail -5 $out/bench_phase0.err; }
 python - <<PY
 import json
 try:

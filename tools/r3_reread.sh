@@ -5,9 +5,9 @@ out=$R/gpurun_out/${1:-reread}
 mkdir -p $out
 cd $R
 for v in 0 1; do
-  PSK_SOFT_REREAD=$v python3 bench.py --mixed --check --no-cpu-baseline --no-few --no-extra --steps 20 --warmup 10 > $out/mixed_$v.json 2> $out/mixed_$v.err
-  PSK_SOFT_REREAD=$v python3 bench.py --numAvg 400 --check --no-cpu-baseline --no-few --no-extra --steps 20 --warmup 10 > $out/a400_$v.json 2> $out/a400_$v.err
-  PSK_SOFT_REREAD=$v python3 bench.py --numAvg 200 --check --no-cpu-baseline --no-few --no-extra --steps 20 --warmup 10 > $out/a200_$v.json 2> $out/a200_$v.err
+  PSK_SOFT_REREAD=$v python3 bench.py --mixed --full --check --no-cpu-baseline --no-few --no-extra --steps 20 --warmup 10 > $out/mixed_$v.json 2> $out/mixed_$v.err
+  PSK_SOFT_REREAD=$v python3 bench.py --numAvg 400 --full --check --no-cpu-baseline --no-few --no-extra --steps 20 --warmup 10 > $out/a400_$v.json 2> $out/a400_$v.err
+  PSK_SOFT_REREAD=$v python3 bench.py --numAvg 200 --full --check --no-cpu-baseline --no-few --no-extra --steps 20 --warmup 10 > $out/a200_$v.json 2> $out/a200_$v.err
 done
 python3 - <<PY
 import json,glob
