@@ -67,20 +67,32 @@ typedef struct psk_soft_props {
 typedef struct psk_soft_limits {
     uint32_t max_window_samples;   /* >= samplesPerBaud*numAvg of every channel (the `samples` deque) */
     uint32_t max_phase_avg;        /* >= phaseAvg of every channel (LinearFit::yvals)                 */
-    uint32_t max_packet_complex;   /* >= complex samples of one packet of one channel (host-buffer path) */
+    uint32_t max_packet_complex;   /* >= complex samples of one packet of one channel (host-buffer path), either format */
 } psk_soft_limits_t;
 
-/* One bulkio::InFloatPort::dataTransfer as serviceFunction() reads it
+/* Sample format of a packet (psk_soft_packet_t::format), per packet: one call may mix formats and a channel may change
+ * format from one call to the next (the carried window holds converted samples).
+ *   PSK_SOFT_FORMAT_CF32  interleaved float32 I,Q (bulkio::InFloatPort); `data` 8-byte aligned.
+ *   PSK_SOFT_FORMAT_CS16  interleaved int16 I,Q (sc16, bulkio::InShortPort); `data` 4-byte aligned.  Every call gives
+ *                         bit for bit what the CF32 packet of the values (float)v gives (the cast is exact); the
+ *                         library converts on the GPU, the packet crosses the link and sits in memory at half the size.
+ * Any other value is refused with PSK_SOFT_ERR_INVALID_ARG before anything is enqueued.  (ABI version 2 before this
+ * field had a name called it `reserved` and ignored it: callers that left garbage there must zero it.) */
+enum { PSK_SOFT_FORMAT_CF32 = 0, PSK_SOFT_FORMAT_CS16 = 1 };
+
+/* One bulkio::InFloatPort (or InShortPort) ::dataTransfer as serviceFunction() reads it
  * (reference cpp/psk_soft.cpp:349-359, 394, 428). */
 typedef struct psk_soft_packet {
-    const float *data;          /* dataBuffer: interleaved I,Q (device or host pointer, per entry point) */
-    uint64_t n_floats;          /* dataBuffer.size()                                                      */
+    const float *data;          /* dataBuffer: interleaved I,Q (device or host pointer, per entry point); for
+                                   PSK_SOFT_FORMAT_CS16 it points at int16 elements (cast the pointer)          */
+    uint64_t n_floats;          /* dataBuffer.size(): ELEMENTS of the packet's format (floats or int16s); the
+                                   packet holds n_floats / 2 complex samples, an odd last element is ignored   */
     double sri_xdelta;          /* SRI.xdelta                                                             */
     int32_t sri_mode;           /* SRI.mode; anything but 1 is dropped with a warning (:359-363)          */
     uint8_t sriChanged;
     uint8_t inputQueueFlushed;  /* forces resetState (:353-357)                                           */
     uint8_t present;            /* 0 = getPacket() returned NULL for this channel: NOOP (:350-352)        */
-    uint8_t reserved;
+    uint8_t format;             /* PSK_SOFT_FORMAT_CF32 / PSK_SOFT_FORMAT_CS16 (checked on present packets)  */
 } psk_soft_packet_t;
 
 /* Where one channel's four output streams go, and what the call produced.

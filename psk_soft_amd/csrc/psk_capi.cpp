@@ -31,6 +31,15 @@ hipError_t launch_fast(int S, int H, int exact, const ChanPlan *plans, const uin
 hipError_t launch_seq(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
                       uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
 hipError_t launch_read_probe(const void *src, uint64_t bytes, float *sink, hipStream_t stream);
+// complex int16 packets (psk_cs16.hip): the conversion pre-pass
+hipError_t launch_cs16_convert(const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
+// ... and the wave-scan and reference-order kernels that read them in place (psk_fast_inst.hip / psk_kernels.hip built with
+// PSK_INST_CS16=1): numAvg <= 128, samplesPerBaud 2 .. 16, screened and exact tier
+bool fast_cs16_has(int S);
+hipError_t launch_fast_cs16(int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
+                            float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
+hipError_t launch_seq_cs16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
 // time-tiled kernels (psk_tile.hip)
 bool tile_front_has(int S, int H);
 hipError_t launch_tile_front(int S, int H, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles,
@@ -80,6 +89,18 @@ psk_soft_status fail(psk_soft_status st, const std::string &msg)
 constexpr int kPlanSlots = 4;
 constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that mixes window classes (see psk_soft_process_device)
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
+constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 packets, one per stream that uses them (see CvtScratch)
+// bytes of a packet's element and the alignment its data needs
+inline size_t elem_bytes(const psk_soft_packet_t &k) { return k.format == PSK_SOFT_FORMAT_CS16 ? sizeof(int16_t) : sizeof(float); }
+// bytes of the upload slot of a call of n channels: header, plans, compact lists, CS16 conversion descriptors (psk_plan.h)
+inline size_t slot_cvt_offset(size_t n)
+{
+    return (psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * n + 15u) & ~(size_t)15u;
+}
+// ... then two more channel lists for the reference-order kernel when a call has CS16 channels on the in-place kernels: the channels
+// of the float build, the channels of the CS16 build
+inline size_t slot_seq_offset(size_t n) { return slot_cvt_offset(n) + sizeof(psk::CvtDesc) * n; }
+inline size_t slot_bytes(size_t n) { return slot_seq_offset(n) + sizeof(uint32_t) * n; }
 
 // Minimal fork-join pool for the host-buffer path: packing packets into pinned memory and
 // unpacking results are plain memcpy work that one thread cannot do at PCIe rate.
@@ -167,7 +188,7 @@ private:
 struct PlanSummary {
     psk_soft_status st = PSK_SOFT_OK;
     uint32_t bad = 0;  // first refused channel (index into the batch)
-    int why = 0;       // 0: status of plan_call, 1: samplesPerBaud > 1024, 2: alignment
+    int why = 0;       // 0: status of plan_call, 1: samplesPerBaud > 1024, 2: alignment, 3: packet format
     bool any = false, any_emit = false, any_seq = false, any_quiet = false;
     bool long_call = false;  // some channel's call is planned for the reference-order kernel only because of its length
     bool need_SH[33][17] = {};
@@ -207,14 +228,29 @@ inline size_t region_bits(size_t in_cap) { return in_cap + in_cap + in_cap / 2; 
 inline size_t region_sidx(size_t in_cap) { return in_cap + in_cap + in_cap / 2 + in_cap; }
 inline size_t region_total(size_t in_cap) { return in_cap + in_cap + in_cap / 2 + in_cap + in_cap / 4; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Where the CS16 packets of a call are converted to (psk_cs16.hip): float2 rows, 128-byte aligned, grown on demand.  One buffer
+// per stream that calls with CS16 packets -- the chunks of psk_soft_process_host run on streams of their own and would
+// otherwise wait for each other --; a buffer taken over from another stream is used behind the event that ends its last call.
+struct CvtScratch {
+    hipStream_t stream = nullptr;
+    float *buf = nullptr;
+    size_t cap = 0;  // bytes
+    hipEvent_t ev = nullptr;
+    bool ev_used = false;
+    uint64_t last_use = 0;
+};
+
 // Largest phaseAvg of the wave-scan kernels: their LDS ring of unwrapped phases holds phaseAvg + 128 values in a power
 // of two; 32768 floats (128 KiB) leave room for the energy ring next to it.  Channels with phaseAvg > kDeepFit are
 // launched apart from the others of their window class ("deep" classes, index H + 8): a ring that size allows one wave
 // per CU, and sized for the whole launch it would take the residency of thousands of ordinary channels with it.
 constexpr uint32_t kFastFitMax = 32768 - 128;
 constexpr uint32_t kDeepFit = 2048 - 128;
-const int kClassH[] = {1, 2, 4, 8, 9, 10, 12, 16};  // second index of the per-class tables: history blocks (+ 8: deep fit window)
-inline int class_H(int Hi) { return Hi > 8 ? Hi - 8 : Hi; }
+// second index of the per-class tables: history blocks (+ 8: deep fit window); 3: one block, CS16 packets read in place
+const int kClassH[] = {1, 3, 2, 4, 8, 9, 10, 12, 16};
+constexpr int kClassCs16 = 3;
+inline int class_H(int Hi) { return Hi == kClassCs16 ? 1 : Hi > 8 ? Hi - 8 : Hi; }
+constexpr int kNumClassH = (int)(sizeof(kClassH) / sizeof(kClassH[0]));
 // time-tiled kernels, automatic choice (measured, tools/tiled_sweep2.sh: QPSK, samplesPerBaud 8): a class of at most 64
 // channels whose longest call has at least 16 blocks of 128 symbols, or of at most 512 channels and 192 blocks (at 128
 // blocks the two paths are level there; above 512 channels the wave-scan kernels fill the machine by themselves);
@@ -322,6 +358,9 @@ struct psk_soft_handle {
     hipStream_t tile_stream = nullptr;  // stream of the last call that used the scratch
     bool tile_ev_used = false;
     bool poisoned = false;  // a HIP call failed after kernels of a call were enqueued: host mirror and device state may disagree
+    // CS16 packets: conversion scratch (CvtScratch)
+    CvtScratch cvt[kCvtScratch];
+    uint64_t cvt_calls = 0;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -499,11 +538,11 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
             // (a slot = the plans of a call followed by the compact channel lists of its launches: one upload)
             // (... behind the header the kernels find in front of the plans: psk_plan.h)
             char *hb = nullptr, *db = nullptr;
-            if ((e2 = hipHostMalloc((void **)&hb, psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * n_channels)) != hipSuccess)
+            if ((e2 = hipHostMalloc((void **)&hb, slot_bytes(n_channels))) != hipSuccess)
                 return bail("hipHostMalloc plans", e2);
             std::memset(hb, 0, psk::kPlanHeaderBytes);
             h->h_plans[s] = reinterpret_cast<psk::ChanPlan *>(hb + psk::kPlanHeaderBytes);
-            if ((e2 = hipMalloc((void **)&db, psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * n_channels)) != hipSuccess)
+            if ((e2 = hipMalloc((void **)&db, slot_bytes(n_channels))) != hipSuccess)
                 return bail("hipMalloc plans", e2);
             h->d_plans[s] = reinterpret_cast<psk::ChanPlan *>(db + psk::kPlanHeaderBytes);
             if ((e2 = hipEventCreateWithFlags(&h->ev[s], hipEventDisableTiming)) != hipSuccess)
@@ -546,6 +585,10 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
             if (q) (void)hipFree(q);
         if (h->pf.hint) (void)hipHostFree(h->pf.hint);
         if (h->tile_ev) (void)hipEventDestroy(h->tile_ev);
+        for (auto &cv : h->cvt) {
+            if (cv.ev) (void)hipEventSynchronize(cv.ev), (void)hipEventDestroy(cv.ev);
+            if (cv.buf) (void)hipFree(cv.buf);
+        }
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
             if (sl.h_buf) (void)hipHostFree(sl.h_buf);
@@ -666,7 +709,13 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                                  (h->opt_ties_in_place ? 0u : (uint32_t)psk::PLAN_TIES_HANDOVER);
     const psk::Limits lim = h->lim;
     // what a planned channel asks of the launches (`mult` channels with this very plan)
-    auto account = [&](const psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
+    // CS16 channels of the window classes with in-place instantiations (psk_fast_inst.hip, PSK_INST_CS16): their own class, no
+    // conversion.  (What would go through the time-tiled kernels is moved back to the float class and the pre-pass below.)
+    auto cs16_in_place = [&](const psk::ChanPlan &p) {
+        return (p.lf_flags & psk::PLAN_CS16) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
+               p.lf_n <= kDeepFit && psk::fast_cs16_has((int)p.S);
+    };
+    auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
         r.any = true;
         if (p.mode == psk::PLAN_FAST) {
             if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
@@ -680,7 +729,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (p.S > r.max_S_any) r.max_S_any = p.S;
             } else if (p.n_out) {
                 r.any_emit = true;
-                const int Hh = psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+                if (cs16_in_place(p))
+                    p.lf_flags |= psk::PLAN_CS16_IN_PLACE;
+                const int Hh = (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16 : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
                 r.need_SH[p.S][Hh] = true;
                 r.cnt_SH[p.S][Hh] += mult;
                 if (p.lf_n > r.max_n[p.S][Hh]) r.max_n[p.S][Hh] = p.lf_n;
@@ -701,8 +752,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         }
     };
     uint32_t *const handed_over = dry ? nullptr : psk::plan_header(h->d_plans[slot]);  // (psk_plan.h)
+    // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 pairs)
     auto misaligned = [&](const psk::ChanPlan &p) {
-        return !dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & 7u) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
+        const uintptr_t in_mask = (p.lf_flags & psk::PLAN_CS16) ? 3u : 7u;
+        return !dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & in_mask) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
                         ((uintptr_t)p.phase & 3u) || ((uintptr_t)p.sidx & 3u));
     };
 
@@ -769,7 +822,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 for (; i < nch; i++) {
                     const psk_soft_packet_t &k = pkts[i];
                     psk_soft_output_t &o = outs[i];
-                    if (k.n_floats != k0.n_floats || k.present != k0.present || k.sri_mode != k0.sri_mode || k.sriChanged != k0.sriChanged ||
+                    if (k.n_floats != k0.n_floats || k.format != k0.format || k.present != k0.present || k.sri_mode != k0.sri_mode ||
+                        k.sriChanged != k0.sriChanged ||
                         k.inputQueueFlushed != k0.inputQueueFlushed || std::memcmp(&k.sri_xdelta, &k0.sri_xdelta, sizeof(double)) != 0)
                         break;
                     if (n_out > o.cap_symbols && (o.soft || o.phase))
@@ -804,7 +858,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             psk::ChanPlan &p = plans[i];
             psk_soft_status st = psk::plan_call(next[i], lim, pkts[i], outs[i], p, cont && (cont[i] & 1u));
             if (st != PSK_SOFT_OK) {
-                r.st = st, r.bad = i, r.why = 0;
+                r.st = st, r.bad = i, r.why = st == PSK_SOFT_ERR_INVALID_ARG ? 3 : 0;
                 return;
             }
             if (p.mode == psk::PLAN_SKIP)
@@ -837,7 +891,13 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             return fail(PSK_SOFT_ERR_LIMIT, "samplesPerBaud > 1024");
         if (res.why == 2)
             return fail(PSK_SOFT_ERR_INVALID_ARG,
-                        "psk_soft_process: packet data must be 8-byte aligned, soft 8, bits 4, phase 4, sampleIndex 4");
+                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
+        if (res.why == 3) {
+            char buf[160];
+            std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1)",
+                          ch0 + res.bad, (unsigned)pkts[res.bad].format);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
         char buf[160];
         std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u refused (status %d)", ch0 + res.bad, (int)res.st);
         return fail(res.st, buf);
@@ -878,6 +938,36 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (h->slot_aux_used[k][a])
                     PSK_HIP(hipStreamWaitEvent(stream, h->slot_aux_ev[k][a], 0));
         }
+    // CS16 channels read in place have a class of their own (kClassCs16), which has no time-tiled kernels: where the float class
+    // would go through those (the same choice as below, on the two classes together), its channels go back to the float class and
+    // to the conversion pre-pass
+    if (!stamped || (plans[0].lf_flags & psk::PLAN_CS16_IN_PLACE))
+        for (int S = 2; S <= 16; S++) {
+            if (!res.need_SH[S][kClassCs16] || !h->opt_tiled || !psk::tile_front_has(S, 1))
+                continue;
+            const uint32_t cnt = res.cnt_SH[S][1] + res.cnt_SH[S][kClassCs16];
+            const uint32_t mb = res.max_blocks_SH[S][1] > res.max_blocks_SH[S][kClassCs16] ? res.max_blocks_SH[S][1] : res.max_blocks_SH[S][kClassCs16];
+            const uint32_t mn = res.max_n[S][1] > res.max_n[S][kClassCs16] ? res.max_n[S][1] : res.max_n[S][kClassCs16];
+            const bool pipe = h->opt_pipe == 2 ? mb >= 4u
+                                               : h->opt_pipe && h->opt_tiled == 1 && cnt >= kPipeMinChannels && cnt <= kPipeMaxChannels &&
+                                                     mb >= kPipeMinBlocks && !cont && mn + 128u <= kPipeMaxYLen;
+            const bool tiled = h->opt_tiled == 2 || pipe || (cnt <= kTiledFewChannels && mb >= kTiledMinBlocksFew) ||
+                               (cnt <= kTiledMaxChannels && mb >= kTiledMinBlocks);
+            if (!tiled)
+                continue;
+            res.need_SH[S][1] = true;
+            res.cnt_SH[S][1] = cnt;
+            res.max_blocks_SH[S][1] = mb;
+            res.max_n[S][1] = mn;
+            res.max_A[S][1] = res.max_A[S][1] > res.max_A[S][kClassCs16] ? res.max_A[S][1] : res.max_A[S][kClassCs16];
+            res.blocks_SH[S][1] += res.blocks_SH[S][kClassCs16];
+            res.need_SH[S][kClassCs16] = false;
+            res.cnt_SH[S][kClassCs16] = res.max_blocks_SH[S][kClassCs16] = res.max_n[S][kClassCs16] = res.max_A[S][kClassCs16] = 0;
+            res.blocks_SH[S][kClassCs16] = 0;
+            for (uint32_t i = 0; i < nch; i++)
+                if (plans[i].S == (uint32_t)S)
+                    plans[i].lf_flags &= ~(uint32_t)psk::PLAN_CS16_IN_PLACE;
+        }
     // compact lists, one per launch, behind the plans: first the channels that emit nothing, then every (S, H)
     // class in launch order
     uint32_t *const h_list = reinterpret_cast<uint32_t *>(h->h_plans[slot] + nch);
@@ -892,7 +982,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 run += res.cnt_SH[S][H];
             }
         uint32_t fill_SH[33][17] = {}, fill_quiet = 0, fill_any = 0;
-        if (stamped)  // (one class holds every channel, in order; the offsets of the others are equal to its end)
+        // (one class holds every channel, in order; the offsets of the others are equal to its end -- unless the stamped class was just
+        // moved back to the float class: its offsets are that class's then, the lists the same)
+        if (stamped)
             for (uint32_t i = 0; i < nch; i++) h_list[i] = i;
         for (uint32_t i = 0; i < nch && !stamped; i++) {
             const psk::ChanPlan &p = plans[i];
@@ -901,7 +993,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
                 h_list[off_any + fill_any++] = i;
             } else if (p.n_out) {
-                const int Hh = psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+                const int Hh = (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16 : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
                 h_list[off_SH[p.S][Hh] + fill_SH[p.S][Hh]++] = i;
             } else {
                 h_list[off_quiet + fill_quiet++] = i;
@@ -952,7 +1044,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     for (int pass = 0; pass < (h->opt_tiled ? 2 : 0); pass++) {
         for (int S : kFastS)
             for (int H : kClassH) {
-                if (!res.need_SH[S][H] || !psk::tile_front_has(S, class_H(H)))
+                if (!res.need_SH[S][H] || H == kClassCs16 || !psk::tile_front_has(S, class_H(H)))
                     continue;
                 // pipelined: the serial fit of a range under the front stage of the next (see kPipeMinChannels)
                 // (PSK_SOFT_PIPELINED=2, tests: wherever the kernels allow it, a few blocks to a range)
@@ -1099,6 +1191,73 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
         }
     }
+    // CS16 packets (psk_cs16.hip): converted into float2 rows of the conversion scratch by one pre-pass in front of the call's first
+    // kernel; their plans point at the rows from here on.  The descriptors travel behind the plans, in the same upload.
+    uint32_t n_cvt = 0;
+    uint64_t cvt_max_n = 0;
+    CvtScratch *cv = nullptr;
+    {
+        size_t need = 0;
+        for (uint32_t i = 0; i < nch; i++) {
+            const psk::ChanPlan &p = plans[i];
+            if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.mode != psk::PLAN_SKIP && p.n_in) {
+                need += align_up(sizeof(float2) * p.n_in, 128);
+                n_cvt++;
+            }
+        }
+        if (n_cvt) {
+            for (auto &c : h->cvt)  // (the stream's own buffer, else the one used longest ago)
+                if (c.buf && c.stream == stream) {
+                    cv = &c;
+                    break;
+                }
+            if (!cv) {
+                cv = &h->cvt[0];
+                for (auto &c : h->cvt)
+                    if (c.last_use < cv->last_use)
+                        cv = &c;
+            }
+            if (!cv->ev)
+                PSK_HIP(hipEventCreateWithFlags(&cv->ev, hipEventDisableTiming));
+            if (cv->ev_used && cv->stream != stream)
+                PSK_HIP(hipStreamWaitEvent(stream, cv->ev, 0));
+            if (need > cv->cap) {  // (rare: grows to the largest call seen, plus a quarter)
+                PSK_HIP(hipDeviceSynchronize());
+                if (cv->buf) (void)hipFree(cv->buf);
+                cv->buf = nullptr;
+                cv->cap = 0;
+                const size_t cap = align_up(need + need / 4, 4096);
+                PSK_HIP(hipMalloc((void **)&cv->buf, cap));
+                cv->cap = cap;
+            }
+            cv->stream = stream;
+            cv->last_use = ++h->cvt_calls;
+            psk::CvtDesc *const desc =
+                reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_cvt_offset(nch));
+            size_t off = 0;
+            uint32_t k = 0;
+            for (uint32_t i = 0; i < nch; i++) {
+                psk::ChanPlan &p = plans[i];
+                if (!((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.mode != psk::PLAN_SKIP && p.n_in))
+                    continue;
+                desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
+                desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
+                desc[k].n = p.n_in;
+                p.in = desc[k].dst;
+                off += align_up(sizeof(float2) * p.n_in, 128);
+                cvt_max_n = p.n_in > cvt_max_n ? p.n_in : cvt_max_n;
+                k++;
+            }
+        }
+    }
+    // the reference-order kernel's two lists when CS16 channels are read in place: float-build channels first, then the others
+    uint32_t n_in_place = 0;
+    for (uint32_t i = 0; i < nch; i++) n_in_place += (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? 1u : 0u;
+    if (n_in_place) {
+        uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_seq_offset(nch));
+        uint32_t a = 0, b = nch - n_in_place;
+        for (uint32_t i = 0; i < nch; i++) seq[(plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? b++ : a++] = i;
+    }
     // PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call
     // reads exist, what it leaves behind fits the rings, its place in the scratch of the time-tiled kernels lies inside it -- is
     // checked here, on the host, in front of the first launch; a violation refuses the call (nothing enqueued, nothing committed)
@@ -1135,6 +1294,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 why = "window class without a wave-scan instantiation planned for one";
             else if (p.mode == psk::PLAN_FAST && p.n_out > psk::kResyncCount)
                 why = "a piece longer than 2^20 symbols on the wave-scan kernels";
+            else if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.n_in &&
+                     (!cv || (const char *)p.in < (const char *)cv->buf ||
+                      (const char *)p.in + sizeof(float2) * p.n_in > (const char *)cv->buf + cv->cap))
+                why = "converted CS16 packet outside the conversion scratch";
         }
         if (why) {
             char buf[200];
@@ -1147,16 +1310,19 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     struct Cls {
         int S, H;
     };
-    Cls cls[33 * 8];
+    Cls cls[33 * kNumClassH];
     int n_cls = 0;
-    for (int k = 7; k >= 0; k--)
+    for (int k = kNumClassH - 1; k >= 0; k--)
         for (int S : kFastS)
             if (need_SH[S][kClassH[k]])
                 cls[n_cls++] = Cls{S, kClassH[k]};
     const bool fork = n_cls > 1 && h->opt_fork;
     // deferred join (see psk_soft_handle::opt_deferred): only calls whose every channel runs on wave-scan launches
-    bool deferred = fork && (h->opt_deferred || g_split_mode) && (!cont || g_split_mode) && !tile_syms && !res.cnt_any && !res.any_seq;
-    if (fork && !cont && !h->opt_deferred && h->opt_split > 1 && !tile_syms && !res.cnt_any && !res.any_seq) {
+    // (nor calls with CS16 packets: the conversion scratch is one per stream, and the next call's pre-pass must not overwrite it
+    // under the side streams of this one)
+    bool deferred = fork && (h->opt_deferred || g_split_mode) && (!cont || g_split_mode) && !tile_syms && !res.cnt_any && !res.any_seq &&
+                    !n_cvt;
+    if (fork && !cont && !h->opt_deferred && h->opt_split > 1 && !tile_syms && !res.cnt_any && !res.any_seq && !n_cvt) {
         // Classes that cannot be resident together (a SIMD's registers hold four waves of the short windows or two of the long
         // ones) take two rounds of waves, and a wave that starts late still needs the whole call's time at the lone-wave rate.
         // Cut in time, the pieces of the short class that start late are short too, and the class runs its last pieces with the
@@ -1198,7 +1364,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         hdr[0] = 0u;                       // channels handed over: counted by the kernels
         hdr[1] = res.any_seq ? 1u : 0u;    // channels planned for the reference-order kernel
     }
-    const size_t up_bytes = psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
+    const size_t up_bytes = n_in_place ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
+                            : n_cvt    ? slot_cvt_offset(nch) + sizeof(psk::CvtDesc) * n_cvt
+                                       : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
     if (h->opt_up_stream) {
         // (the slot's previous user has finished -- waited for above --, nothing else reads or writes d_plans[slot])
         PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[slot]), psk::plan_header(h->h_plans[slot]), up_bytes,
@@ -1242,6 +1410,12 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     // left out, which is wrong as soon as a call is handed over; what the two launches cost a small call is measured that way)
     static const bool diag_no_tail = std::getenv("PSK_SOFT_DIAG_NO_TAIL") && std::atoi(std::getenv("PSK_SOFT_DIAG_NO_TAIL")) != 0;
     auto enqueue = [&]() -> psk_soft_status {
+        if (n_cvt) {
+            PSK_HIP(mark("cs16_convert", 0, 0, ~0u, 0, n_cvt, 0, 0));
+            PSK_HIP(psk::launch_cs16_convert(
+                reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)),
+                n_cvt, cvt_max_n, stream));
+        }
         if (any_quiet)
             PSK_HIP(mark("fast<0,1> (calls that emit nothing)", 0, 1, off_quiet, res.cnt_quiet, 0, ring_floats(res.max_n_quiet, 512u), 0));
         if (any_quiet)
@@ -1367,10 +1541,17 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (exact && diag_no_tail)
                     break;
                 PSK_HIP(mark(exact ? "fast (exact tier)" : "fast (screened tier)", S, H, off_SH[S][H], res.cnt_SH[S][H], 0, y_len, r_len));
-                PSK_HIP(psk::launch_fast(S, class_H(H), exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
-                                         h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
+                if (H == kClassCs16)
+                    PSK_HIP(psk::launch_fast_cs16(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
+                                                  h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
+                else
+                    PSK_HIP(psk::launch_fast(S, class_H(H), exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
+                                             h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
             }
-            if (deferred)  // (the class's hand-overs are redone on its own stream, in front of its next call)
+            if (deferred && H == kClassCs16)  // (the class's hand-overs are redone on its own stream, in front of its next call)
+                PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
+                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+            else if (deferred)
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring, h->lim.ring_cap,
                                         h->d_yv, h->lim.fit_cap, st));
         }
@@ -1391,12 +1572,24 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             if (any_seq || any_emit)
                 PSK_HIP(mark("seq (reference order)", 0, 0, ~0u, nch, 0, 0, 0));
-            if ((any_seq || any_emit) && !diag_no_tail)  // any_emit: the exactness guard may hand calls over at run time
+            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place)  // any_emit: the exactness guard may hand calls over at run time
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], nullptr, ch0, nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
+            if ((any_seq || any_emit) && !diag_no_tail && n_in_place) {  // (CS16 read in place: each build on its own channels)
+                const uint32_t *const d_seq = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) +
+                                                                                 slot_seq_offset(nch));
+                PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, nch - n_in_place, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                        h->lim.fit_cap, stream));
+                PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_seq + (nch - n_in_place), ch0, n_in_place, h->d_state, h->d_ring,
+                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
+            }
         }
         if (tile_syms)
             PSK_HIP(hipEventRecord(h->tile_ev, stream));
+        if (n_cvt) {
+            PSK_HIP(hipEventRecord(cv->ev, stream));
+            cv->ev_used = true;
+        }
         PSK_HIP(hipEventRecord(h->ev[slot], stream));
         return PSK_SOFT_OK;
     };
@@ -1532,7 +1725,9 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
             // the next piece reads and writes behind this one
             if (pk[i].present) {
                 mode_of[i] = h->last_mode[ch0 + i];
-                pk[i].data = pk[i].data ? pk[i].data + pk[i].n_floats : nullptr;
+                pk[i].data = pk[i].data ? reinterpret_cast<const float *>(reinterpret_cast<const char *>(pk[i].data) +
+                                                                          elem_bytes(pk[i]) * pk[i].n_floats)
+                                        : nullptr;
                 pk[i].n_floats = left[i];
                 if (ou[i].soft) ou[i].soft += 2 * o.n_symbols;
                 if (ou[i].bits) ou[i].bits += o.n_bits;
@@ -1651,7 +1846,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
             return fail(PSK_SOFT_ERR_CAPACITY, "psk_soft_process_host: output buffer too small");
         // every channel's rows start on a cache line: rows that straddle lines cost 6-8 % of the
         // kernel's streaming rate (tools/micro/placement_probe.hip)
-        need[i].in = pkts[i].present ? align_up(sizeof(float) * (pkts[i].n_floats & ~1ull), 128) : 0;
+        need[i].in = pkts[i].present ? align_up(elem_bytes(pkts[i]) * (pkts[i].n_floats & ~1ull), 128) : 0;  // (CS16 staged as CS16)
         need[i].soft = align_up(sizeof(float) * 2 * o.n_symbols, 128);
         need[i].phase = align_up(sizeof(float) * o.n_symbols, 128);
         need[i].bits = align_up(sizeof(int16_t) * o.n_bits, 128);
@@ -1732,7 +1927,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
         uint8_t *h_in = sl.h_buf;
         h->pool->run(n, [&](uint32_t i) {
             if (pk0[i].present && pk0[i].n_floats)
-                std::memcpy(h_in + off_in[i], pk0[i].data, sizeof(float) * (pk0[i].n_floats & ~1ull));
+                std::memcpy(h_in + off_in[i], pk0[i].data, elem_bytes(pk0[i]) * (pk0[i].n_floats & ~1ull));
         });
         if (oi)
             PSK_HIP(hipMemcpyAsync(d_in, h_in, oi, hipMemcpyHostToDevice, sl.stream));

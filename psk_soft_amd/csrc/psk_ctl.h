@@ -158,6 +158,8 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
         out.ret = PSK_SOFT_NOOP;
         return PSK_SOFT_OK;
     }
+    if (pkt.format != PSK_SOFT_FORMAT_CF32 && pkt.format != PSK_SOFT_FORMAT_CS16)
+        return PSK_SOFT_ERR_INVALID_ARG;  // (the only status plan_call returns it for)
     if (pkt.inputQueueFlushed && !cont) {  // :353-357
         out.n_warn++;
         c.props.resetState = 1;
@@ -222,7 +224,7 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
         c.resetPhaseAvg = false;
     }
 
-    const uint64_t N = pkt.n_floats / 2;  // :428
+    const uint64_t N = pkt.n_floats / 2;  // :428 (elements of either format: floats or int16s)
     const uint64_t dev_ring0 = c.ring_len < lim.ring_cap ? c.ring_len : lim.ring_cap;
 
     plan.in = pkt.data;
@@ -301,7 +303,7 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
     plan.lf_len0 = (uint32_t)c.lf_len;
     plan.lf_count0 = (uint32_t)c.lf_count;
     plan.lf_xdelta = c.lf_xdelta;
-    plan.lf_flags = 0;
+    plan.lf_flags = pkt.format == PSK_SOFT_FORMAT_CS16 ? (uint32_t)PLAN_CS16 : 0u;
     plan.n_out = n_out;
     if (plan.mode == PLAN_FAST && n_out && any_front)
         plan.lf_flags |= PLAN_ANYFRONT;

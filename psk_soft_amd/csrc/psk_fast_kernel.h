@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64, ((HV == 0 && SV <= 5 && !EXACT) ? 4 : (HV == 0 
 
     XView X;
     X.ring = reinterpret_cast<const f2g *>(ring_src);
-    X.in = reinterpret_cast<const f2g *>(p.in);
+    X.in = reinterpret_cast<const pkt_t *>(p.in);
     X.L0 = p.ring_len0;
 
     FastCarry cy;

@@ -229,8 +229,12 @@ PSK_DEV void load_symbol_any(const XView &X, uint64_t tau, bool wanted, float2 (
 #pragma unroll
     for (int k = 0; k < S; k++) {
         const uint64_t j = j0 + (uint64_t)k;
+#if PSK_INST_CS16
+        const f2g v = x_load<S>(X, j);
+#else
         const f2g *p = j < X.L0 ? X.ring + j : X.in + (j - X.L0);  // (a select of two addresses)
         const f2g v = *mem_ptr<packet_global(S)>(p);
+#endif
         x[k] = make_float2(wanted ? v.x : 0.0f, wanted ? v.y : 0.0f);
     }
 }
@@ -245,6 +249,22 @@ PSK_DEV void load_block(const XView &X, long long cblk, uint32_t A, long long ta
         // steady: one wave-uniform base address plus a per-lane offset that does not change from block to block; a lane's
         // two symbols are contiguous and 16*S bytes long: S 16-byte loads (at 8-byte alignment, which gfx950 global
         // loads allow), whatever the parity of S
+#if PSK_INST_CS16
+        // (complex int16: the lane's two symbols are 8*S bytes -- S 8-byte loads of two samples each, at the 4-byte alignment
+        // the ABI asks of CS16 packets, converted as they arrive)
+        typedef uint32_t u2g __attribute__((ext_vector_type(2), aligned(4)));
+        const typename MemPtr<packet_global(S), const u2g>::type q =
+            (typename MemPtr<packet_global(S), const u2g>::type)(X.in + ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0)) +
+            (uint32_t)lane * (uint32_t)S;
+#pragma unroll
+        for (int k = 0; k < S; k++) {
+            const u2g t = q[k];
+            const f2g a = cs16_f2(t.x), b = cs16_f2(t.y);
+            x[(2 * k) / S][(2 * k) % S] = make_float2(a.x, a.y);
+            x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
+        }
+        return;
+#else
         const f2g *base = X.in + ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0);
         const typename F4Ptr<packet_global(S)>::type q =
             (typename F4Ptr<packet_global(S)>::type)base + (uint32_t)lane * (uint32_t)S;
@@ -259,6 +279,7 @@ PSK_DEV void load_block(const XView &X, long long cblk, uint32_t A, long long ta
             x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(t.z, t.w);
         }
         return;
+#endif
     }
 #pragma unroll
     for (int r = 0; r < kR; r++) {
@@ -1498,8 +1519,12 @@ PSK_DEV void fast_main_loop(const ChanPlan &p, const XView &X, float *yring, uin
 #pragma unroll
             for (int r = 0; r < kR; r++) {
                 const uint64_t j = (uint64_t)(c * kB + 2 * lane + r) * S + (uint64_t)kpred[r];  // (exists: A > kB)
+#if PSK_INST_CS16
+                const f2g g = x_load<S>(X, j);
+#else
                 const f2g *q = j < X.L0 ? X.ring + j : X.in + (j - X.L0);
                 const f2g g = *mem_ptr<packet_global(S)>(q);
+#endif
                 px[r] = g.x;
                 py[r] = g.y;
                 pkk[r] = kpred[r];
@@ -1758,8 +1783,12 @@ PSK_DEV void fast_main_loop(const ChanPlan &p, const XView &X, float *yring, uin
             const bool miss = valid[r] && (pkk[r] != bestK[r]);
             if (vote_any(miss)) {  // (wave-uniform, like every branch around loads here: see load_block)
                 const uint64_t j = miss ? (uint64_t)(i0 + r) * S + (uint64_t)bestK[r] : 0ull;  // (sample 0 exists)
+#if PSK_INST_CS16
+                const f2g g = x_load<S>(X, j);
+#else
                 const f2g *q = j < X.L0 ? X.ring + j : X.in + (j - X.L0);
                 const f2g g = *mem_ptr<packet_global(S)>(q);
+#endif
                 px[r] = miss ? g.x : px[r];
                 py[r] = miss ? g.y : py[r];
             }

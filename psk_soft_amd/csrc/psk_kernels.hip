@@ -27,6 +27,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// -DPSK_INST_CS16=1 (Makefile: psk_seq_cs16.o): the reference-order kernel alone, reading complex int16 packets, in namespace
+// psk_cs16 (see psk_fast_inst.hip), exported as launch_seq_cs16 -- it redoes the calls the CS16 wave-scan kernels hand over
+#if PSK_INST_CS16
+#define psk psk_cs16
+#endif
 #include "psk_fast_kernel.h"
 
 namespace psk {
@@ -185,7 +190,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
     float2 *ring_dst = ring_base + (size_t)(p.ring_src ^ 1u) * ring_cap;
     XView X;
     X.ring = reinterpret_cast<const f2g *>(ring_src);
-    X.in = reinterpret_cast<const f2g *>(p.in);
+    X.in = reinterpret_cast<const pkt_t *>(p.in);
     X.L0 = p.ring_len0;
     const uint32_t S = p.S;
     const uint64_t N = p.n_in;
@@ -316,6 +321,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
 
 }  // namespace psk
 
+#if !PSK_INST_CS16
 // ---------------------------------------------------------------------------------
 // launchers (called from psk_capi.cpp through plain C++ declarations).  Every (samplesPerBaud,
 // history depth, screened / exact) instantiation of the wave-scan kernel is its own translation
@@ -460,6 +466,9 @@ hipError_t launch_fast(int S, int H, int exact, PSK_FAST_ARGS)
     PSK_CASE_S_WIDE(32)
     return hipErrorInvalidValue;
 }
+#else
+namespace psk {
+#endif
 
 hipError_t launch_seq(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
                       uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
@@ -501,3 +510,14 @@ hipError_t launch_read_probe(const void *src, uint64_t bytes, float *sink, hipSt
     return hipGetLastError();
 }
 }  // namespace psk
+#if PSK_INST_CS16
+#undef psk
+namespace psk {
+hipError_t launch_seq_cs16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
+{
+    return psk_cs16::launch_seq(static_cast<const psk_cs16::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cs16::ChanState *>(states),
+                                rings, ring_cap, yvs, fit_cap, stream);
+}
+}  // namespace psk
+#endif

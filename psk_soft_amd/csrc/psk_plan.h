@@ -46,9 +46,24 @@ enum LfFlags : uint32_t {
     // (tests, A/B runs: PSK_SOFT_TIES_IN_PLACE=0) windows longer than a block hand a call with a near-tie to the exact tier, as
     // before round 3, instead of settling the block in place
     PLAN_TIES_HANDOVER = 128u,
+    // the packet is complex int16 (PSK_SOFT_FORMAT_CS16).  Unless PLAN_CS16_IN_PLACE is set too, the kernels never see it as such:
+    // `in` points at the float2 copy the conversion pre-pass of the call (psk_cs16.hip) writes into scratch in front of them
+    PLAN_CS16 = 256u,
+    // (host-side) ... and read in place by the CS16 builds of the wave-scan and reference-order kernels: `in` stays the caller's int16
+    // pairs, no pre-pass (psk_capi.cpp: the window classes with such instantiations)
+    PLAN_CS16_IN_PLACE = 512u,
 };
 
+
 constexpr uint32_t kResyncCount = 1048576u;  // cpp/psk_soft.cpp:51, 582
+
+// One CS16 packet for the conversion pre-pass (psk_cs16.hip): n complex int16 samples at src become n float2 at dst.  They sit
+// behind the compact channel lists in the upload slot of the call, so that they travel with the plans in one copy.
+struct CvtDesc {
+    const uint32_t *src;  // I in the low half, Q in the high half (little-endian int16 pairs); 4-byte aligned
+    float *dst;           // interleaved I,Q floats; 128-byte aligned, in the handle's conversion scratch
+    uint64_t n;
+};
 
 // wave-scan kernel, numAvg <= 128: the instantiations whose LDS energy ring is sized by the host per
 // launch (psk_fast_loop.h) instead of the fixed 256 positions -- the host sizes their phase ring tighter too

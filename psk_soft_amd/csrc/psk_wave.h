@@ -233,17 +233,59 @@ PSK_DEV void store_s2u(int16_t *p, s2u v) { *reinterpret_cast<s2u *>(p) = v; }
 PSK_DEV void store_s2u(PSK_GLOBAL int16_t *p, s2u v) { PSK_ST((PSK_GLOBAL s2u *)p, v); }
 PSK_DEV void store_s4u(int16_t *p, s4u v) { *reinterpret_cast<s4u *>(p) = v; }
 PSK_DEV void store_s4u(PSK_GLOBAL int16_t *p, s4u v) { PSK_ST((PSK_GLOBAL s4u *)p, v); }
+// The packet's sample type is a property of the translation unit: PSK_INST_CS16=1 builds (psk_fast_inst.hip, psk_kernels.hip
+// compiled a second time, Makefile) read complex int16 packets (PSK_SOFT_FORMAT_CS16) straight from the caller's buffer, one 32-bit
+// word per sample, I in the low half; every other build reads float2.  The carried samples (the ring) are float2 in both.
+#ifndef PSK_INST_CS16
+#define PSK_INST_CS16 0
+#endif
+#if PSK_INST_CS16
+typedef uint32_t pkt_t;
+#else
+typedef f2g pkt_t;
+#endif
+// an int16 pair -> float2: sign-extended halves (v_bfe_i32 / v_ashrrev_i32), then v_cvt_f32_i32 -- exact for every int16
+PSK_DEV f2g cs16_f2(uint32_t v)
+{
+    f2g r;
+    r.x = (float)(int32_t)(int16_t)(v & 0xffffu);
+    r.y = (float)((int32_t)v >> 16);
+    return r;
+}
 struct XView {
     const f2g *ring;
-    const f2g *in;
+    const pkt_t *in;
     uint32_t L0;  // samples in the ring
 };
 PSK_DEV float2 x_at(const XView &X, uint64_t j)
 {
+#if PSK_INST_CS16
+    // (both loads, then a select: no lane takes a branch of its own; the index the other buffer gets exists)
+    const bool r = j < X.L0;
+    const f2g a = X.ring[r ? j : 0];
+    const f2g b = cs16_f2(X.in[r ? 0 : j - X.L0]);
+    const f2g v = r ? a : b;
+#else
     const f2g v = j < X.L0 ? X.ring[j] : X.in[j - X.L0];
+#endif
     return make_float2(v.x, v.y);
 }
+// sample j of X through the address space of packet_global(S): what x_at reads, for the wave-scan kernels
+template <int S>
+PSK_DEV f2g x_load(const XView &X, uint64_t j)
+{
+#if PSK_INST_CS16
+    const bool r = j < X.L0;
+    const f2g a = *mem_ptr<packet_global(S)>(X.ring + (r ? j : 0));
+    const uint32_t b = *mem_ptr<packet_global(S)>(X.in + (r ? 0 : j - X.L0));
+    return r ? a : cs16_f2(b);
+#else
+    const f2g *p = j < X.L0 ? X.ring + j : X.in + (j - X.L0);  // (a select of two addresses)
+    return *mem_ptr<packet_global(S)>(p);
+#endif
+}
 
+#if !PSK_INST_CS16
 template <int S>
 PSK_DEV void load_symbol(const XView &X, uint64_t tau, bool valid, float2 (&x)[S])
 {
@@ -280,6 +322,7 @@ PSK_DEV void load_symbol(const XView &X, uint64_t tau, bool valid, float2 (&x)[S
         }
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------------
 // LinearFit pieces shared by both kernels

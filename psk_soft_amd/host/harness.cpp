@@ -20,9 +20,11 @@ struct Time {
     double twsec, tfsec;
 };
 
-struct InFloatPort {
+// dataFloat_in (T = float) or dataShort_in (T = short: complex int16 packets)
+template <class Sample>
+struct InPort {
     struct dataTransfer {
-        std::vector<float> dataBuffer;
+        std::vector<Sample> dataBuffer;
         StreamSRI SRI;
         Time T;
         bool EOS;
@@ -39,7 +41,7 @@ struct InFloatPort {
         q.pop_front();
         return p;
     }
-    ~InFloatPort()
+    ~InPort()
     {
         for (size_t i = 0; i < q.size(); i++) delete q[i];
     }
@@ -70,32 +72,84 @@ struct OutPort {
     }
 };
 
-typedef psk_soft_gpu::component<InFloatPort, OutPort<float>, OutPort<short> > Component;
+typedef psk_soft_gpu::component<InPort<float>, OutPort<float>, OutPort<short> > Component;
+typedef psk_soft_gpu::component<InPort<short>, OutPort<float>, OutPort<short> > ShortComponent;
 
+// one of the two components: float input (psk_harness_create) or short input (psk_harness_create_i16)
 struct Harness {
-    InFloatPort in;
+    InPort<float> in;
+    InPort<short> in_s;
     OutPort<float> soft, phase;
     OutPort<short> bits, sidx;
-    Component comp;
+    Component *comp;
+    ShortComponent *comp_s;
     std::string error;
-    explicit Harness(int device) : comp(device)
+    template <class C>
+    void wire(C &c)
     {
-        comp.dataFloat_in = &in;
-        comp.softDecision_dataFloat_out = &soft;
-        comp.bits_dataShort_out = &bits;
-        comp.phase_dataFloat_out = &phase;
-        comp.sampleIndex_dataShort_out = &sidx;
+        c.softDecision_dataFloat_out = &soft;
+        c.bits_dataShort_out = &bits;
+        c.phase_dataFloat_out = &phase;
+        c.sampleIndex_dataShort_out = &sidx;
+    }
+    Harness(int device, bool short_input) : comp(0), comp_s(0)
+    {
+        if (short_input) {
+            comp_s = new ShortComponent(device);
+            comp_s->dataFloat_in = &in_s;
+            wire(*comp_s);
+        } else {
+            comp = new Component(device);
+            comp->dataFloat_in = &in;
+            wire(*comp);
+        }
+    }
+    ~Harness()
+    {
+        delete comp;
+        delete comp_s;
     }
 };
+
+template <class C>
+void configure_prop(C &c, int id, unsigned value)
+{
+    switch (id) {
+    case 0: { bool ch = c.samplesPerBaud != value; c.samplesPerBaud = (unsigned short)value; if (ch) c.samplesPerBaudChanged("samplesPerBaud"); break; }
+    case 1: c.numAvg = value; break;
+    case 2: { bool ch = c.constelationSize != value; c.constelationSize = (unsigned short)value; if (ch) c.constelationSizeChanged("constelationSize"); break; }
+    case 3: { bool ch = c.phaseAvg != value; c.phaseAvg = (unsigned short)value; if (ch) c.phaseAvgChanged("phaseAvg"); break; }
+    case 4: c.differentialDecoding = value != 0; break;
+    case 5: c.resetState = value != 0; break;
+    }
+}
+
+template <class T>
+void push_packet(InPort<T> &in, const T *data, size_t n, double xdelta, int mode, int sriChanged, int flushed, int eos,
+                 const char *streamID, double twsec)
+{
+    typename InPort<T>::dataTransfer *p = new typename InPort<T>::dataTransfer();
+    p->dataBuffer.assign(data, data + n);
+    p->SRI.xdelta = xdelta;
+    p->SRI.mode = mode;
+    p->SRI.streamID = streamID ? streamID : "";
+    p->T.twsec = twsec;
+    p->T.tfsec = 0;
+    p->EOS = eos != 0;
+    p->streamID = p->SRI.streamID;
+    p->sriChanged = sriChanged != 0;
+    p->inputQueueFlushed = flushed != 0;
+    in.q.push_back(p);
+}
 
 }  // namespace
 
 extern "C" {
 
-void *psk_harness_create(int device, char *err, int errlen)
+static void *create(int device, bool short_input, char *err, int errlen)
 {
     try {
-        return new Harness(device);
+        return new Harness(device, short_input);
     } catch (const std::exception &e) {
         if (err && errlen > 0) {
             std::string m = e.what();
@@ -106,6 +160,9 @@ void *psk_harness_create(int device, char *err, int errlen)
         return 0;
     }
 }
+void *psk_harness_create(int device, char *err, int errlen) { return create(device, false, err, errlen); }
+// a component whose input is a short port (complex int16 packets, PSK_SOFT_FORMAT_CS16)
+void *psk_harness_create_i16(int device, char *err, int errlen) { return create(device, true, err, errlen); }
 void psk_harness_destroy(void *h) { delete (Harness *)h; }
 
 // configure() of one property: stores it and, like REDHAWK's PropertySet, runs the registered
@@ -114,17 +171,13 @@ void psk_harness_destroy(void *h) { delete (Harness *)h; }
 int psk_harness_configure(void *hv, int id, unsigned value)
 {
     Harness *h = (Harness *)hv;
-    Component &c = h->comp;
+    if (id < 0 || id > 5)
+        return -1;
     try {
-        switch (id) {
-        case 0: { bool ch = c.samplesPerBaud != value; c.samplesPerBaud = (unsigned short)value; if (ch) c.samplesPerBaudChanged("samplesPerBaud"); break; }
-        case 1: c.numAvg = value; break;
-        case 2: { bool ch = c.constelationSize != value; c.constelationSize = (unsigned short)value; if (ch) c.constelationSizeChanged("constelationSize"); break; }
-        case 3: { bool ch = c.phaseAvg != value; c.phaseAvg = (unsigned short)value; if (ch) c.phaseAvgChanged("phaseAvg"); break; }
-        case 4: c.differentialDecoding = value != 0; break;
-        case 5: c.resetState = value != 0; break;
-        default: return -1;
-        }
+        if (h->comp)
+            configure_prop(*h->comp, id, value);
+        else
+            configure_prop(*h->comp_s, id, value);
     } catch (const std::exception &e) {
         h->error = e.what();
         return -2;
@@ -135,33 +188,31 @@ int psk_harness_configure(void *hv, int id, unsigned value)
 void psk_harness_push(void *hv, const float *data, size_t n_floats, double xdelta, int mode, int sriChanged,
                       int flushed, int eos, const char *streamID, double twsec)
 {
-    Harness *h = (Harness *)hv;
-    InFloatPort::dataTransfer *p = new InFloatPort::dataTransfer();
-    p->dataBuffer.assign(data, data + n_floats);
-    p->SRI.xdelta = xdelta;
-    p->SRI.mode = mode;
-    p->SRI.streamID = streamID ? streamID : "";
-    p->T.twsec = twsec;
-    p->T.tfsec = 0;
-    p->EOS = eos != 0;
-    p->streamID = p->SRI.streamID;
-    p->sriChanged = sriChanged != 0;
-    p->inputQueueFlushed = flushed != 0;
-    h->in.q.push_back(p);
+    push_packet(((Harness *)hv)->in, data, n_floats, xdelta, mode, sriChanged, flushed, eos, streamID, twsec);
+}
+// (short-input component) n_shorts int16 elements, interleaved I,Q
+void psk_harness_push_i16(void *hv, const short *data, size_t n_shorts, double xdelta, int mode, int sriChanged,
+                          int flushed, int eos, const char *streamID, double twsec)
+{
+    push_packet(((Harness *)hv)->in_s, data, n_shorts, xdelta, mode, sriChanged, flushed, eos, streamID, twsec);
 }
 
 int psk_harness_service(void *hv)
 {
     Harness *h = (Harness *)hv;
     try {
-        return h->comp.serviceFunction();
+        return h->comp ? h->comp->serviceFunction() : h->comp_s->serviceFunction();
     } catch (const std::exception &e) {
         h->error = e.what();
         return -1;
     }
 }
 const char *psk_harness_error(void *hv) { return ((Harness *)hv)->error.c_str(); }
-int psk_harness_warnings(void *hv) { return ((Harness *)hv)->comp.warnings; }
+int psk_harness_warnings(void *hv)
+{
+    Harness *h = (Harness *)hv;
+    return h->comp ? h->comp->warnings : h->comp_s->warnings;
+}
 
 // port: 0 soft 1 bits 2 phase 3 sampleIndex
 static size_t port_size(Harness *h, int port)
@@ -224,6 +275,10 @@ size_t psk_harness_port_sri(void *hv, int port, double *xdelta, int *mode, size_
 }
 int psk_harness_last_eos(void *hv) { return ((Harness *)hv)->soft.last_eos ? 1 : 0; }
 const char *psk_harness_last_stream(void *hv) { return ((Harness *)hv)->soft.last_stream.c_str(); }
-void *psk_harness_handle(void *hv) { return ((Harness *)hv)->comp.handle(); }
+void *psk_harness_handle(void *hv)
+{
+    Harness *h = (Harness *)hv;
+    return h->comp ? h->comp->handle() : h->comp_s->handle();
+}
 
 }  // extern "C"

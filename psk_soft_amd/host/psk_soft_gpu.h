@@ -6,6 +6,10 @@
 //   * inside REDHAWK:  psk_soft_gpu::component<bulkio::InFloatPort, bulkio::OutFloatPort,
 //                                             bulkio::OutShortPort>   (see INTEGRATION.md), and
 //   * in this repository's tests: with the small in-memory ports of harness.cpp.
+// The input port may also be a short port (bulkio::InShortPort: complex int16, sc16, as FEI tuners, VITA-49 and UHD
+// deliver it): the packet format follows the element type of its dataBuffer at compile time (float: PSK_SOFT_FORMAT_CF32,
+// short: PSK_SOFT_FORMAT_CS16), and the library converts on the GPU -- no short-to-float component in front of it, half the
+// bytes through the host-buffer path.  Outputs are the same either way: an sc16 packet gives what its float cast gives.
 // Port surface used (exactly what the reference uses): InPort::dataTransfer with dataBuffer,
 // SRI.{xdelta,mode}, sriChanged, inputQueueFlushed, T, EOS, streamID; getPacket(timeout);
 // OutPort::pushSRI(SRI) and pushPacket(vector&, T, EOS, streamID).
@@ -25,7 +29,13 @@ namespace psk_soft_gpu {
 enum { NOOP = PSK_SOFT_NOOP, NORMAL = PSK_SOFT_NORMAL };
 const float BLOCKING = -1.0f;  // bulkio::Const::BLOCKING
 
-template <class InFloatPort, class OutFloatPort, class OutShortPort>
+// packet format of an input port's sample type: float or short, nothing else compiles
+template <class T> struct sample_format;
+template <> struct sample_format<float> { enum { value = PSK_SOFT_FORMAT_CF32 }; };
+template <> struct sample_format<short> { enum { value = PSK_SOFT_FORMAT_CS16 }; };
+
+// InPort: bulkio::InFloatPort or bulkio::InShortPort (or anything with their dataTransfer)
+template <class InPort, class OutFloatPort, class OutShortPort>
 class component {
   public:
     // properties (cpp/psk_soft_base.h:45-56, defaults cpp/psk_soft_base.cpp:96-148)
@@ -35,8 +45,9 @@ class component {
     unsigned short phaseAvg;
     bool differentialDecoding;
     bool resetState;
-    // ports (cpp/psk_soft_base.h:58-68); owned by the caller / the generated base class
-    InFloatPort *dataFloat_in;
+    // ports (cpp/psk_soft_base.h:58-68); owned by the caller / the generated base class.  (The input keeps the reference's
+    // member name whatever its type; a short-input component's generated base calls its port dataShort_in.)
+    InPort *dataFloat_in;
     OutFloatPort *softDecision_dataFloat_out;
     OutShortPort *bits_dataShort_out;
     OutFloatPort *phase_dataFloat_out;
@@ -68,22 +79,24 @@ class component {
 
     int serviceFunction()
     {
-        typename InFloatPort::dataTransfer *tmp = dataFloat_in->getPacket(BLOCKING);
+        typedef typename InPort::dataTransfer transfer_t;
+        typedef typename decltype(static_cast<transfer_t *>(0)->dataBuffer)::value_type sample_t;
+        transfer_t *tmp = dataFloat_in->getPacket(BLOCKING);
         if (!tmp)  // cpp/psk_soft.cpp:350-352
             return NOOP;
         push_properties();  // numAvg / differentialDecoding / resetState have no listener (:374-378)
 
         psk_soft_packet_t pkt;
-        pkt.data = tmp->dataBuffer.empty() ? 0 : &tmp->dataBuffer[0];
+        pkt.data = tmp->dataBuffer.empty() ? 0 : reinterpret_cast<const float *>(&tmp->dataBuffer[0]);
         pkt.n_floats = tmp->dataBuffer.size();
         pkt.sri_xdelta = tmp->SRI.xdelta;
         pkt.sri_mode = tmp->SRI.mode;
         pkt.sriChanged = tmp->sriChanged ? 1 : 0;
         pkt.inputQueueFlushed = tmp->inputQueueFlushed ? 1 : 0;
         pkt.present = 1;
-        pkt.reserved = 0;
+        pkt.format = (uint8_t)sample_format<sample_t>::value;
 
-        const size_t cap = (size_t)psk_soft_output_capacity(handle_, 0, pkt.n_floats / 2);
+        const size_t cap = (size_t)psk_soft_output_capacity(handle_, 0, pkt.n_floats / 2);  // (n / 2 complex samples either way)
         out_.assign(2 * cap, 0.0f);
         bits_.assign(3 * cap, 0);
         phase_vec_.assign(cap, 0.0f);

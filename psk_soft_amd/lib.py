@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "libpsk_soft_hip.so")
 DEVICE_NONE = -1
 OK = 0
 NOOP, NORMAL = 0, 1
+# Packet.format: interleaved float32 I/Q, or interleaved int16 I/Q (sc16; n_floats then counts int16 elements)
+FORMAT_CF32, FORMAT_CS16 = 0, 1
 
 STATUS_NAMES = {
     0: "PSK_SOFT_OK",
@@ -57,7 +59,7 @@ class Packet(ctypes.Structure):
         ("sriChanged", ctypes.c_uint8),
         ("inputQueueFlushed", ctypes.c_uint8),
         ("present", ctypes.c_uint8),
-        ("reserved", ctypes.c_uint8),
+        ("format", ctypes.c_uint8),  # FORMAT_CF32 / FORMAT_CS16
     ]
 
 
@@ -287,8 +289,8 @@ class Handle:
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with
-        data (float32 interleaved I/Q), xdelta, and optional mode / sriChanged /
-        inputQueueFlushed.  Returns one dict per channel with the four output streams."""
+        data (interleaved I/Q: an int16 array is handed over as it is, FORMAT_CS16, anything else as float32), xdelta,
+        and optional mode / sriChanged / inputQueueFlushed.  Returns one dict per channel with the four output streams."""
         n = len(packets)
         pk = (Packet * n)()
         out = (Output * n)()
@@ -299,10 +301,12 @@ class Handle:
                 pk[i].present = 0
                 bufs.append(None)
                 continue
-            data = np.ascontiguousarray(p["data"], dtype=np.float32)
+            cs16 = isinstance(p["data"], np.ndarray) and p["data"].dtype == np.int16
+            data = np.ascontiguousarray(p["data"], dtype=np.int16 if cs16 else np.float32)
             keep.append(data)
             pk[i].data = data.ctypes.data
             pk[i].n_floats = data.size
+            pk[i].format = FORMAT_CS16 if cs16 else FORMAT_CF32
             pk[i].sri_xdelta = float(p["xdelta"])
             pk[i].sri_mode = int(p.get("mode", 1))
             pk[i].sriChanged = int(bool(p.get("sriChanged", False)))
@@ -349,7 +353,8 @@ class Handle:
         return res
 
     def plan_only(self, ch0, packets):
-        """Control-plane results (counts, SRI) of one call without data (DEVICE_NONE handles)."""
+        """Control-plane results (counts, SRI) of one call without data (DEVICE_NONE handles).  packets: None or dict with
+        n_floats (elements of the format), xdelta, optional mode / sriChanged / inputQueueFlushed / format."""
         n = len(packets)
         pk = (Packet * n)()
         out = (Output * n)()
@@ -361,6 +366,7 @@ class Handle:
             pk[i].sri_mode = int(p.get("mode", 1))
             pk[i].sriChanged = int(bool(p.get("sriChanged", False)))
             pk[i].inputQueueFlushed = int(bool(p.get("inputQueueFlushed", False)))
+            pk[i].format = int(p.get("format", FORMAT_CF32))
             pk[i].present = 1
             out[i].cap_symbols = 1 << 62
         _check(self._L.psk_soft_process_device(self._h, ch0, n, pk, out, None))

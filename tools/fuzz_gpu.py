@@ -25,6 +25,11 @@ XD_CHOICES = [float(v) for v in os.environ["PSK_FUZZ_XD"].split(",")] if os.envi
 # PSK_FUZZ_MORE=1: two more kinds of events in the scripts -- samplesPerBaud changed between two calls, and a new SRI (another
 # xdelta, sriChanged set) in the middle of a stream (off by default: the draws of the seeds quoted in DESIGN.md stay what they were)
 MORE = os.environ.get("PSK_FUZZ_MORE", "0") != "0"
+# PSK_FUZZ_CS16=p: with probability p a channel's stream is complex int16 (PSK_SOFT_FORMAT_CS16; the oracle gets its float cast):
+# half of those send every packet as int16, the other half alternate int16 / float32 packets call by call.  Its signal is the same
+# draw, scaled so that its peak lands between 1 and 32767 LSB (ties of small integers included) and rounded; the NONFINITE and
+# EXTREME draws stay with the float channels.  Drawn from generators of their own: the other draws of a seed stay what they were.
+CS16 = float(os.environ.get("PSK_FUZZ_CS16", "0"))
 TOL = 1e-5
 STRICT = os.environ.get("PSK_FUZZ_STRICT", "1") != "0"  # every float of soft / phase must equal the oracle's
 XD = 0.01
@@ -104,6 +109,8 @@ def main():
         rng = random.Random(seed * 1000 + rnd)
         nrng = np.random.default_rng(seed * 1000 + rnd)
         props, sigs, scripts = [], [], []
+        crng = random.Random(seed * 1000 + rnd + 0x5C16)
+        cs16 = []  # per channel: None (float32), "all" (every packet int16) or "alt" (int16 and float32 packets call by call)
         for c in range(C):
             S = rng.choice(S_CHOICES)
             A = rng.choice(A_CHOICES)
@@ -131,6 +138,13 @@ def main():
                         new_xd = rng.choice([0.01, 0.02, 1e-3, 0.5, 2.5e-7])
                 ev.append(("packet", prev, cut, rng.random() < 0.05, new_xd))
                 prev = cut
+            fmt = None
+            if CS16 and crng.random() < CS16:
+                fmt = crng.choice(["all", "alt"])
+                peak = float(np.abs(sig[np.isfinite(sig)]).max()) if np.isfinite(sig).any() else 0.0
+                scale = 10.0 ** crng.uniform(0.0, np.log10(32767.0)) / peak if peak > 0 else 1.0
+                sig = np.clip(np.rint(np.nan_to_num(sig.astype(np.float64) * scale)), -32768, 32767).astype(np.int16)
+            cs16.append(fmt)
             props.append(p)
             sigs.append(sig)
             scripts.append(ev)
@@ -170,7 +184,13 @@ def main():
                 if len(ev) > 4 and ev[4] is not None:  # (PSK_FUZZ_MORE: a new SRI in front of this packet)
                     xds[c] = ev[4]
                     sri = True
-                pk.append(dict(data=data, xdelta=xds[c], sriChanged=sri, inputQueueFlushed=flushed))
+                if cs16[c] is not None:  # (the oracle, and the float32 packets of an alternating channel, get the exact cast)
+                    f32 = data.astype(np.float32)
+                    send = data if (cs16[c] == "all" or pos[c] % 2 == 0) else f32
+                    data = f32
+                else:
+                    send = data
+                pk.append(dict(data=send, xdelta=xds[c], sriChanged=sri, inputQueueFlushed=flushed))
                 r = oracles[c].service(data, xds[c], sriChanged=sri, inputQueueFlushed=flushed)
                 for k, v in (("soft", r.soft), ("bits", r.bits), ("phase", r.phase), ("index", r.index)):
                     ref[c][k].append(v)
@@ -200,7 +220,8 @@ def main():
                         break
             if why:
                 bad += 1
-                print("MISMATCH round %d channel %d: %s  props=%s script=%s" % (rnd, c, why, props[c], scripts[c]))
+                print("MISMATCH round %d channel %d%s: %s  props=%s script=%s" % (rnd, c, " (CS16 %s)" % cs16[c] if cs16[c] else "", why,
+                                                                              props[c], scripts[c]))
                 if g["phase"].size == r["phase"].size and g["soft"].size == r["soft"].size and g["phase"].size:
                     # where, and what the phase estimate is there: one ulp of a large estimate is the known case
                     dp = np.nonzero(g["phase"] != r["phase"])[0]
@@ -216,7 +237,7 @@ def main():
                         print("   soft differs at symbols %s ... (%d symbols); got %s ref %s" % (
                             sym[:16].tolist(), sym.size, g["soft"][2 * sym[0] : 2 * sym[0] + 2], r["soft"][2 * sym[0] : 2 * sym[0] + 2]))
         bad_total += bad
-        print("round %d: %d channels, %d mismatches, last-call stats %s" % (rnd, C, bad, st))
+        print("round %d: %d channels (%d CS16), %d mismatches, last-call stats %s" % (rnd, C, sum(f is not None for f in cs16), bad, st))
     print("TOTAL mismatches:", bad_total)
     return 1 if bad_total else 0
 

@@ -23,6 +23,10 @@ others() { f=$1; shift; /opt/rocm/bin/hipcc $FL "$@" -o $tmp/$f.s psk_soft_amd/c
   python3 tools/isa_exec_spills.py $tmp/$f.s --sites 0 >> $out; python3 tools/isa_lane_loss.py $tmp/$f.s --sites 3 >> $out.lanes; rm -f $tmp/$f.s; }
 others psk_tile; others psk_kernels
 for s in $(seq 2 16); do others psk_tile_inst@S$s -DPSK_INST_S=$s -DPSK_INST_H=1; done
+# the CS16 builds (PSK_INST_CS16=1): the wave-scan kernel for numAvg <= 128, samplesPerBaud 2 ... 16, both tiers; the reference-order
+# kernel; the conversion pre-pass (psk_cs16.hip)
+for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cs16_S${s}_H1_E$e -DPSK_INST_CS16=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
+others psk_kernels@cs16 -DPSK_INST_CS16=1; others psk_cs16
 echo "instantiations with D sites / with E sites (tools/isa_lane_loss.py):"; grep -c "no covering save) [1-9]" $out.lanes; grep -c "mask restore) [1-9]" $out.lanes
 grep -c . $out; grep -v "C (lane carrier moved under a partial mask) 0" $out | wc -l
 rmdir $tmp
