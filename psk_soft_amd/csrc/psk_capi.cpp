@@ -1499,17 +1499,20 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 e++;
                 for (uint32_t t0 = 0; t0 < T; t0 += tr) {
                     const uint32_t nt = T - t0 < tr ? T - t0 : tr;
+                    PSK_HIP(mark("pipe_front", S, H, off_SH[S][H], cnt, nt, y_len, r_len));
                     PSK_HIP(psk::launch_tile_front(S, class_H(H), h->d_plans[slot], l, ch0, cnt, nt, h->d_state, h->d_ring, h->lim.ring_cap, r_len,
                                                    h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, t0, st));
                     PSK_HIP(hipEventRecord(h->pipe_ev[e], st));
                     PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
                     e++;
+                    PSK_HIP(mark("pipe_fit", S, H, off_SH[S][H], cnt, nt, y_pipe, 0));
                     PSK_HIP(psk::launch_tile_fit_range(h->d_plans[slot], l, ch0, cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                                        h->lim.fit_cap, y_pipe, h->d_tiles, h->d_traw, h->d_ts, h->d_test, carry, carry_y, t0, nt,
                                                        h->pipe_st[0]));
                     PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[0]));
                     PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
                     e++;
+                    PSK_HIP(mark("pipe_back", S, H, off_SH[S][H], cnt, nt, y_pipe, 0));
                     PSK_HIP(psk::launch_tile_back(h->d_plans[slot], l, ch0, cnt, nt, h->d_state, h->d_tiles, h->d_ts, h->d_test, t0, 1u,
                                                   h->pipe_st[1]));
                 }
@@ -1696,6 +1699,10 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
                 n_fl = n_fl > cut ? n_fl - cut : 2ull * S * (A + 2);
                 (void)A;
             }
+            // (a piece that is not the last holds whole complex samples: an odd element at the end of the packet goes with the last
+            // piece, which ignores it -- in an earlier one it would start the next piece one element late, misaligned)
+            if (n_fl < left[i])
+                n_fl &= ~1ull;
             q.n_floats = n_fl;
             left[i] -= n_fl < left[i] ? n_fl : left[i];
             if (left[i])
@@ -2187,6 +2194,8 @@ psk_soft_status psk_soft_import_state(psk_soft_handle_t *h, uint32_t ch, const v
         p += sizeof(float2) * h->lim.ring_cap;
         PSK_HIP(hipMemcpy(h->d_yv + (size_t)ch * h->lim.fit_cap, p, sizeof(float) * h->lim.fit_cap, hipMemcpyHostToDevice));
     }
+    c.pad_flags = 0, c.pad_rate = 0, c.pad_xdelta = 0;  // (a blob of an earlier build may hold indeterminate bytes there)
+    std::memset(c.pad_tail, 0, sizeof c.pad_tail);
     ctl_touch(h);
     h->ctl[ch] = c;  // (last: a failed copy above leaves the host mirror as it was)
     return PSK_SOFT_OK;

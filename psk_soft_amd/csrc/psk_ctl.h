@@ -11,6 +11,7 @@
 #ifndef PSK_CTL_H
 #define PSK_CTL_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "psk_plan.h"
@@ -25,20 +26,26 @@ struct ChanCtl {
     bool resetSamplesPerBaud = true;
     bool resetNumSymbols = true;
     bool resetPhaseAvg = true;
+    // (the padding is spelled out and zero: psk_soft_export_state copies the struct as it is, and an implicit gap would carry
+    // whatever bytes the copy it came from held -- two equal states would export to different blobs)
+    uint8_t pad_flags = 0;
     // mirrored control state
     uint64_t ring_len = 0;        // samples.size() (may exceed the device ring in the stalled state)
     uint64_t symEnergySize = 10;  // symbolEnergy.size(), cpp/psk_soft.cpp:189
     uint64_t index = 0;           // cpp/psk_soft.cpp:190
     uint64_t count = 0;           // cpp/psk_soft.cpp:196
     float sampleRate = 1.0f;      // cpp/psk_soft.cpp:195
+    uint32_t pad_rate = 0;
     uint64_t lf_n = 50;           // LinearFit(phaseAvg, sampleRate), cpp/psk_soft.cpp:197
     float lf_xdelta = 1.0f;       // 1.0/sampleRate, cpp/psk_soft.cpp:41
+    uint32_t pad_xdelta = 0;
     uint64_t lf_len = 0;          // yvals.size()
     uint64_t lf_count = 0;
     // device bookkeeping
     uint32_t lf_head = 0;         // oldest entry of the circular yvals buffer in HBM
     uint32_t ring_src = 0;        // which ping-pong ring buffer is current
     bool lf_recompute_pending = false;  // a LinearFit::reset() was planned while no kernel ran
+    uint8_t pad_tail[7] = {};
 
     ChanCtl()
     {
@@ -65,6 +72,9 @@ struct ChanCtl {
         if (old.phaseAvg != p.phaseAvg) phaseAvgChanged();
     }
 };
+static_assert(sizeof(ChanCtl) == 104 && offsetof(ChanCtl, ring_len) == 16 && offsetof(ChanCtl, lf_n) == 56 &&
+                  offsetof(ChanCtl, lf_len) == 72 && offsetof(ChanCtl, lf_recompute_pending) == 96,
+              "ChanCtl: no implicit padding (the exported state blob holds it byte for byte)");
 
 struct Limits {
     uint32_t ring_cap;  // samples per ring buffer

@@ -1308,21 +1308,29 @@ def test_deferred_join_of_mixed_window_classes(oracle_mod):
         check(c)
 
 
-@pytest.mark.parametrize("pieces", [2, 3, 5])
-def test_mixed_batch_cut_in_time(oracle_mod, monkeypatch, pieces):
+# (ids: the default-options variants keep the ids the test had before it was parametrized over tiling)
+@pytest.mark.parametrize("pieces,tiling", [(2, "tiled"), (3, "tiled"), (5, "tiled"), (2, "untiled"), (3, "untiled"), (5, "untiled")],
+                         ids=["2", "3", "5", "2-untiled", "3-untiled", "5-untiled"])
+def test_mixed_batch_cut_in_time(oracle_mod, monkeypatch, capfd, pieces, tiling):
     """A batch that mixes window classes with calls of 128 blocks or more is cut in time inside the library (psk_capi.cpp:
     PSK_SOFT_SPLIT_CLASSES pieces, each a continuation of the ONE serviceFunction() call, the classes running through them on
     their own streams and joined at the end of the call).  Cut points fall in the middle of the call, where the reference
     neither rebuilds its energy sums nor resets its fit: everything -- timing picks, the unwrap across the cut, LinearFit's
     sums and count, differential decoding's `last`, the end-of-call wrap (once, at the end) -- has to come out as in the uncut
     call.  Two calls in a row, ragged lengths (a channel whose call is too short to cut, one that emits an odd number of
-    symbols), every channel against the oracle."""
+    symbols), every channel against the oracle.
+    "untiled" (PSK_SOFT_TIME_TILED=0): the call is cut, which a traced second run (same outputs) shows -- every class's
+    screened-tier launch once per piece.  "tiled" (default options): the 12 channels of the (S=8, numAvg <= 128) class go to
+    the time-tiled kernels, and a call with a time-tiled class is not cut."""
     from concurrent.futures import ThreadPoolExecutor
 
     from psk_soft_amd import lib as pl
     from psk_soft_amd.stimulus import synth_channel
+    from tests.test_gpu_cs16_schedules import parse_trace, rounds, screened, whats
 
     monkeypatch.setenv("PSK_SOFT_SPLIT_CLASSES", str(pieces))
+    if tiling == "untiled":
+        monkeypatch.setenv("PSK_SOFT_TIME_TILED", "0")
     S, C, calls = 8, 30, 2
     Ms = [(2, 4, 8)[c % 3] for c in range(C)]
     props = [dict(samplesPerBaud=S, constelationSize=Ms[c], numAvg=(25, 100, 200, 400, 1000)[c % 5], phaseAvg=(10, 50, 200)[(c // 5) % 3],
@@ -1331,39 +1339,63 @@ def test_mixed_batch_cut_in_time(oracle_mod, monkeypatch, pieces):
     lens[3], lens[4] = 9000, 70000  # (too short to cut; cut into fewer blocks than pieces x 128)
     with ThreadPoolExecutor(8) as ex:
         host = list(ex.map(lambda c: synth_channel(4200 + c, Ms[c], S, calls * lens[c], cfo=(0.02 if c % 7 == 0 else None)), range(C)))
-    h = pl.Handle(C, device=0, max_window_samples=16384, max_phase_avg=512)
-    h.configure(0, props)
-    cap = [lens[c] // S + 2 for c in range(C)]
-    d_in = [h.device_alloc(2 * lens[c] * 4) for c in range(C)]
-    d_soft, d_phase = [h.device_alloc(cap[c] * 8) for c in range(C)], [h.device_alloc(cap[c] * 4) for c in range(C)]
-    d_sidx, d_bits = [h.device_alloc(cap[c] * 2 + 4) for c in range(C)], [h.device_alloc(cap[c] * 6 + 4) for c in range(C)]
-    got = [dict(soft=[], bits=[], phase=[], index=[]) for _ in range(C)]
-    try:
-        for k in range(calls):
-            pk, out = (pl.Packet * C)(), (pl.Output * C)()
-            for c in range(C):
-                h.upload(d_in[c], host[c][2 * k * lens[c] : 2 * (k + 1) * lens[c]])
-                pk[c].data, pk[c].n_floats, pk[c].sri_xdelta, pk[c].sri_mode, pk[c].sriChanged, pk[c].present = d_in[c], 2 * lens[c], 0.01, 1, int(k == 0), 1
-                out[c].soft, out[c].bits, out[c].phase, out[c].sampleIndex, out[c].cap_symbols = d_soft[c], d_bits[c], d_phase[c], d_sidx[c], cap[c]
-            h.process_device(0, pk, out)
-            h.synchronize()
-            st = h.stats()
-            assert st["channels_fast"] == C and st["channels_sequential"] == 0, st
-            for c in range(C):
-                ns, b = int(out[c].n_symbols), {2: 1, 4: 2, 8: 3}[Ms[c]]
-                assert int(out[c].n_bits) == b * ns and int(out[c].n_sampleIndex) == ns
-                got[c]["soft"].append(h.download(d_soft[c], (2 * ns,), np.float32))
-                got[c]["phase"].append(h.download(d_phase[c], (ns,), np.float32))
-                got[c]["index"].append(h.download(d_sidx[c], (ns,), np.int16))
-                got[c]["bits"].append(h.download(d_bits[c], (b * ns,), np.int16))
-    finally:
-        for lst in (d_in, d_soft, d_phase, d_sidx, d_bits):
-            for q in lst:
-                h.device_free(q)
-        h.close()
+
+    def run(trace):
+        if trace:
+            monkeypatch.setenv("PSK_SOFT_TRACE_LAUNCHES", "2")
+        else:
+            monkeypatch.delenv("PSK_SOFT_TRACE_LAUNCHES", raising=False)
+        h = pl.Handle(C, device=0, max_window_samples=16384, max_phase_avg=512)
+        h.configure(0, props)
+        cap = [lens[c] // S + 2 for c in range(C)]
+        d_in = [h.device_alloc(2 * lens[c] * 4) for c in range(C)]
+        d_soft, d_phase = [h.device_alloc(cap[c] * 8) for c in range(C)], [h.device_alloc(cap[c] * 4) for c in range(C)]
+        d_sidx, d_bits = [h.device_alloc(cap[c] * 2 + 4) for c in range(C)], [h.device_alloc(cap[c] * 6 + 4) for c in range(C)]
+        got = [dict(soft=[], bits=[], phase=[], index=[]) for _ in range(C)]
+        traces = []
+        try:
+            for k in range(calls):
+                pk, out = (pl.Packet * C)(), (pl.Output * C)()
+                for c in range(C):
+                    h.upload(d_in[c], host[c][2 * k * lens[c] : 2 * (k + 1) * lens[c]])
+                    pk[c].data, pk[c].n_floats, pk[c].sri_xdelta, pk[c].sri_mode, pk[c].sriChanged, pk[c].present = d_in[c], 2 * lens[c], 0.01, 1, int(k == 0), 1
+                    out[c].soft, out[c].bits, out[c].phase, out[c].sampleIndex, out[c].cap_symbols = d_soft[c], d_bits[c], d_phase[c], d_sidx[c], cap[c]
+                capfd.readouterr()
+                h.process_device(0, pk, out)
+                traces.append(parse_trace(capfd.readouterr().err))
+                h.synchronize()
+                st = h.stats()
+                assert st["channels_fast"] == C and st["channels_sequential"] == 0, st
+                for c in range(C):
+                    ns, b = int(out[c].n_symbols), {2: 1, 4: 2, 8: 3}[Ms[c]]
+                    assert int(out[c].n_bits) == b * ns and int(out[c].n_sampleIndex) == ns
+                    got[c]["soft"].append(h.download(d_soft[c], (2 * ns,), np.float32))
+                    got[c]["phase"].append(h.download(d_phase[c], (ns,), np.float32))
+                    got[c]["index"].append(h.download(d_sidx[c], (ns,), np.int16))
+                    got[c]["bits"].append(h.download(d_bits[c], (b * ns,), np.int16))
+        finally:
+            for lst in (d_in, d_soft, d_phase, d_sidx, d_bits):
+                for q in lst:
+                    h.device_free(q)
+            h.close()
+        return [{k: np.concatenate(v) for k, v in g.items()} for g in got], traces
+
+    got, _ = run(False)
+    got_traced, traces = run(True)
+    monkeypatch.delenv("PSK_SOFT_TRACE_LAUNCHES", raising=False)
     for c in range(C):
+        for key in ("soft", "bits", "phase", "index"):
+            assert np.array_equal(got[c][key].view(np.uint8), got_traced[c][key].view(np.uint8)), "traced run, channel %d %s" % (c, key)
         ref = oracle_run(oracle_mod, host[c], props[c], packet=lens[c])
-        assert_parity({k: np.concatenate(v) for k, v in got[c].items()}, ref, "cut in %d, channel %d (%s)" % (pieces, c, props[c]))
+        assert_parity(got[c], ref, "cut in %d, channel %d (%s)" % (pieces, c, props[c]))
+    classes = {(S, {25: 1, 100: 1, 200: 2, 400: 4, 1000: 8}[p["numAvg"]]) for p in props}
+    for k, lines in enumerate(traces):
+        if tiling == "untiled":
+            assert rounds(lines) == pieces and screened(lines) == {cl: pieces for cl in classes}, (k, screened(lines))
+            assert "tile_front" not in whats(lines), (k, whats(lines))
+        else:
+            assert rounds(lines) == 1 and screened(lines) == {cl: 1 for cl in classes - {(S, 1)}}, (k, screened(lines))
+            assert [t["H"] for t in lines if t["what"] == "tile_front"] == [1], (k, lines)
 
 
 @pytest.mark.parametrize("scale", [1e-19, 1e-21, 3e-22, 2e-23])
