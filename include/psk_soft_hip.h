@@ -158,7 +158,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h);
 /* configure() of channels [ch0, ch0+nch): stores the properties and runs the change
  * listeners the component registers (cpp/psk_soft.cpp:210-212, 638-651) for every
  * property whose value differs from the stored one.  Takes effect at the next process call
- * (the reference snapshots its properties at the top of serviceFunction, :374-378). */
+ * (the reference snapshots its properties at the top of serviceFunction, :374-378).
+ * Every samplesPerBaud the ushort property holds (1 .. 65535) is accepted; PSK_SOFT_ERR_LIMIT only when
+ * samplesPerBaud*numAvg exceeds max_window_samples or phaseAvg max_phase_avg. */
 psk_soft_status psk_soft_configure(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
                                    const psk_soft_props_t *props /* [nch] */);
 psk_soft_status psk_soft_query(const psk_soft_handle_t *h, uint32_t ch, psk_soft_props_t *props);

@@ -51,6 +51,16 @@ hipError_t launch_tile_front_any(const ChanPlan *plans, const uint32_t *list, ui
 hipError_t launch_tile_fit(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
                            uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, TileInfo *tiles, const float *t_raw,
                            const float2 *t_s, float *t_est, const PfScratch &sc, hipStream_t stream);
+// wide symbols, samplesPerBaud > kSeqMaxS: the front stage of the time-tiled kernels (psk_wide.hip) and the reference-order kernel
+// with symbolEnergy[] in device memory (psk_kernels.hip built with PSK_SEQ_WIDE=1)
+hipError_t launch_wide_front(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles, uint32_t max_S,
+                             const float2 *rings, uint32_t ring_cap, TileInfo *tiles, float *t_raw, float2 *t_s, PfChan *pf_chan, void *rec,
+                             void *wst, hipStream_t stream);
+size_t wide_rec_bytes();
+size_t wide_stat_bytes();
+uint32_t wide_chunks(uint32_t S);
+hipError_t launch_seq_wide(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, double *symE, uint32_t symE_stride, hipStream_t stream);
 hipError_t launch_pfit(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles, ChanState *states,
                        float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, TileInfo *tiles, const float *t_raw,
                        const float2 *t_s, float *t_est, const PfScratch &sc, bool second_round, hipStream_t stream);
@@ -188,7 +198,7 @@ private:
 struct PlanSummary {
     psk_soft_status st = PSK_SOFT_OK;
     uint32_t bad = 0;  // first refused channel (index into the batch)
-    int why = 0;       // 0: status of plan_call, 1: samplesPerBaud > 1024, 2: alignment, 3: packet format
+    int why = 0;       // 0: status of plan_call, 2: alignment, 3: packet format
     bool any = false, any_emit = false, any_seq = false, any_quiet = false;
     bool long_call = false;  // some channel's call is planned for the reference-order kernel only because of its length
     bool need_SH[33][17] = {};
@@ -204,6 +214,9 @@ struct PlanSummary {
     // the window classes without an instantiation (PLAN_ANYFRONT), one launch set for all of them
     uint32_t cnt_any = 0, max_n_any = 0, max_A_any = 0, max_blocks_any = 0, max_S_any = 0;
     uint64_t blocks_any = 0;
+    // ... of them, the wide symbols (samplesPerBaud > kSeqMaxS): a launch set of their own (psk_wide.hip)
+    uint32_t cnt_wide = 0, max_n_wide = 0, max_A_wide = 0, max_blocks_wide = 0, max_S_wide = 0;
+    uint64_t blocks_wide = 0;
 };
 
 // One chunk of channels of the host-buffer path in flight: pinned and device buffers for the packed
@@ -264,7 +277,8 @@ constexpr size_t kPipeMaxSymbols = (size_t)1 << 29;  // (16 bytes of scratch a s
 constexpr int kPipeEvents = 2 * (int)kPipeMaxRanges + 2;
 // a batch of several window classes whose calls are at least this long is cut in time (psk_soft_process_device)
 constexpr uint32_t kSplitMinBlocks = 128;
-constexpr uint32_t kSeqMaxS = 1024;    // symbolEnergy[] of the reference-order kernel lives in LDS
+constexpr uint32_t kSeqMaxS = 1024;    // symbolEnergy[] of the reference-order kernel lives in LDS; wider symbols: psk_wide.hip and
+                                       // the PSK_SEQ_WIDE build of that kernel
 const int kFastS[] = {2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17,
                       18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32};
 
@@ -354,6 +368,12 @@ struct psk_soft_handle {
     void *d_pipe_carry = nullptr;           // per channel of a pipelined launch: the fit state between two ranges (PipeCarry)
     float *d_pipe_y = nullptr;              // ... and its ring of unwrapped phases
     size_t pipe_cap = 0;
+    // wide symbols (samplesPerBaud > kSeqMaxS): the chunk records of the front stage (psk_wide.hip) and the rows of symbolEnergy[] of the
+    // reference-order kernel's wide build, grown on demand like the scratch above and ordered by the same event
+    void *d_wide_rec = nullptr, *d_wide_stat = nullptr;
+    size_t wide_rec_cap = 0, wide_stat_cap = 0;  // bytes
+    double *d_wide_symE = nullptr;
+    size_t wide_symE_cap = 0;  // doubles
     hipEvent_t tile_ev = nullptr;
     hipStream_t tile_stream = nullptr;  // stream of the last call that used the scratch
     bool tile_ev_used = false;
@@ -611,6 +631,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
             if (e) (void)hipEventDestroy(e);
         if (h->d_pipe_carry) (void)hipFree(h->d_pipe_carry);
         if (h->d_pipe_y) (void)hipFree(h->d_pipe_y);
+        if (h->d_wide_rec) (void)hipFree(h->d_wide_rec);
+        if (h->d_wide_stat) (void)hipFree(h->d_wide_stat);
+        if (h->d_wide_symE) (void)hipFree(h->d_wide_symE);
         if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
         for (auto &row : h->slot_aux_ev)
             for (hipEvent_t &e : row)
@@ -631,10 +654,9 @@ psk_soft_status psk_soft_configure(psk_soft_handle_t *h, uint32_t ch0, uint32_t 
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_configure: bad channel range");
     for (uint32_t i = 0; i < nch; i++) {
         const psk_soft_props_t &p = props[i];
-        if ((uint64_t)p.samplesPerBaud * p.numAvg > h->lim.ring_cap || p.phaseAvg >= h->lim.fit_cap ||
-            p.samplesPerBaud > kSeqMaxS)
+        if ((uint64_t)p.samplesPerBaud * p.numAvg > h->lim.ring_cap || p.phaseAvg >= h->lim.fit_cap)
             return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_configure: property exceeds the limits given at create "
-                                            "(samplesPerBaud*numAvg, phaseAvg) or samplesPerBaud > 1024");
+                                            "(samplesPerBaud*numAvg, phaseAvg)");
     }
     ctl_touch(h);
     for (uint32_t i = 0; i < nch; i++) h->ctl[ch0 + i].configure(props[i]);
@@ -718,7 +740,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
         r.any = true;
         if (p.mode == psk::PLAN_FAST) {
-            if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
+            if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
+                r.any_emit = true;
+                r.cnt_wide += mult;
+                const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
+                r.blocks_wide += (uint64_t)nb * mult;
+                if (nb > r.max_blocks_wide) r.max_blocks_wide = nb;
+                if (p.lf_n > r.max_n_wide) r.max_n_wide = p.lf_n;
+                if (p.A > r.max_A_wide) r.max_A_wide = p.A;
+                if (p.S > r.max_S_wide) r.max_S_wide = p.S;
+            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
                 r.any_emit = true;
                 r.cnt_any += mult;
                 const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
@@ -806,8 +837,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             stamp_ctl = run->lazy ? run->ctl : h->ctl[ch0];
             psk::ChanPlan &p0 = plans[0];
             const psk_soft_packet_t &k0 = pkts[0];
-            bool ok = stamp_ctl.props.samplesPerBaud <= kSeqMaxS &&
-                      psk::plan_call(stamp_ctl, lim, k0, outs[0], p0, false) == PSK_SOFT_OK && p0.mode != psk::PLAN_SKIP &&
+            bool ok = psk::plan_call(stamp_ctl, lim, k0, outs[0], p0, false) == PSK_SOFT_OK && p0.mode != psk::PLAN_SKIP &&
                       !misaligned(p0);
             if (ok) {
                 p0.lf_flags |= extra_flags;
@@ -851,10 +881,6 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     auto plan_range = [&](uint32_t lo, uint32_t hi, PlanSummary &r) {
         for (uint32_t i = lo; i < hi; i++) {
             next[i] = cur[i];
-            if (next[i].props.samplesPerBaud > kSeqMaxS) {
-                r.st = PSK_SOFT_ERR_LIMIT, r.bad = i, r.why = 1;
-                return;
-            }
             psk::ChanPlan &p = plans[i];
             psk_soft_status st = psk::plan_call(next[i], lim, pkts[i], outs[i], p, cont && (cont[i] & 1u));
             if (st != PSK_SOFT_OK) {
@@ -887,8 +913,6 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         return PSK_SOFT_OK;
     }
     if (res.st != PSK_SOFT_OK) {
-        if (res.why == 1)
-            return fail(PSK_SOFT_ERR_LIMIT, "samplesPerBaud > 1024");
         if (res.why == 2)
             return fail(PSK_SOFT_ERR_INVALID_ARG,
                         "psk_soft_process: packet data must be 8-byte aligned (CS16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
@@ -973,15 +997,15 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     uint32_t *const h_list = reinterpret_cast<uint32_t *>(h->h_plans[slot] + nch);
     const uint32_t *const d_list = reinterpret_cast<const uint32_t *>(h->d_plans[slot] + nch);
     uint32_t off_SH[33][17] = {}, off_quiet = 0;
-    const uint32_t off_any = res.cnt_quiet;
+    const uint32_t off_any = res.cnt_quiet, off_wide = res.cnt_quiet + res.cnt_any;
     {
-        uint32_t run = res.cnt_quiet + res.cnt_any;
+        uint32_t run = res.cnt_quiet + res.cnt_any + res.cnt_wide;
         for (int S : kFastS)
             for (int H : kClassH) {
                 off_SH[S][H] = run;
                 run += res.cnt_SH[S][H];
             }
-        uint32_t fill_SH[33][17] = {}, fill_quiet = 0, fill_any = 0;
+        uint32_t fill_SH[33][17] = {}, fill_quiet = 0, fill_any = 0, fill_wide = 0;
         // (one class holds every channel, in order; the offsets of the others are equal to its end -- unless the stamped class was just
         // moved back to the float class: its offsets are that class's then, the lists the same)
         if (stamped)
@@ -990,7 +1014,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             const psk::ChanPlan &p = plans[i];
             if (p.mode != psk::PLAN_FAST)
                 continue;
-            if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
+            if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
+                h_list[off_wide + fill_wide++] = i;
+            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
                 h_list[off_any + fill_any++] = i;
             } else if (p.n_out) {
                 const int Hh = (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16 : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
@@ -1005,9 +1031,37 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     // that the class makes a few thousand tiles.
     bool tiled_SH[33][17] = {};
     bool pf_second = false;
-    uint32_t tiles_max_any = 0;
+    uint32_t tiles_max_any = 0, tiles_max_wide = 0;
     uint32_t tiles_max_SH[33][17] = {};
     size_t tile_syms = 0, tile_count = 0;
+    // (wide symbols first: their places in the scratch index the chunk records of psk_wide.hip too, which need not cover the others)
+    const uint32_t wide_z = res.cnt_wide ? psk::wide_chunks(res.max_S_wide) : 0u;
+    if (res.cnt_wide) {
+        // always tiled, like the classes below; a tile is one wave per chunk of 1024 timing phases, and few symbols a call fill
+        // the machine only on short tiles -- as short as one block, unless the window in front of a tile is longer
+        uint64_t K = res.blocks_wide * wide_z / kTiledTargetTiles;
+        K = K < 1 ? 1 : K > 16 ? 16 : K;
+        const uint64_t k_win = (res.max_A_wide + 127u) / 128u;
+        if (K < k_win) {
+            const uint64_t k_fill = res.blocks_wide * wide_z / (kTiledTargetTiles / 2);
+            const uint64_t k_long = k_win > 64 ? 64 : k_win;
+            K = k_fill > k_long ? k_long : k_fill > K ? k_fill : K;
+        }
+        tiles_max_wide = (uint32_t)((res.max_blocks_wide + K - 1) / K);
+        for (uint32_t i = 0; i < res.cnt_wide; i++) {
+            psk::ChanPlan &p = plans[h_list[off_wide + i]];
+            const uint64_t nb = (p.n_out + 127u) / 128u;
+            p.lf_flags |= psk::PLAN_TILED;
+            if (h->opt_pfit && p.lf_len0 == p.lf_n && p.lf_n >= 2)
+                p.lf_flags |= psk::PLAN_PFIT;
+            p.tile_blocks = (uint32_t)K;
+            p.tile_base = (uint32_t)tile_count;
+            p.tile_off = tile_syms;
+            tile_count += (size_t)((nb + K - 1) / K);
+            tile_syms += (size_t)nb * 128u;
+        }
+    }
+    const size_t wide_rec_need = tile_syms * wide_z * psk::wide_rec_bytes(), wide_stat_need = tile_count * wide_z * psk::wide_stat_bytes();
     if (res.cnt_any) {
         // (window classes without a wave-scan instantiation: always tiled, whatever the option says -- the alternative is the
         // reference-order kernel; a tile at least as long as the longest window, so that rebuilding it stays a fraction)
@@ -1133,7 +1187,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                     }
                     plans[i].lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT);
                 }
-                res.cnt_any = 0;
+                res.cnt_any = res.cnt_wide = 0;
                 for (auto &row : tiled_SH)
                     for (bool &t : row) t = false;
                 for (auto &row : piped_SH)
@@ -1146,6 +1200,50 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 h->pf_sym_cap = psyms;
             }
         }
+    }
+    if (res.cnt_wide && (wide_rec_need > h->wide_rec_cap || wide_stat_need > h->wide_stat_cap)) {
+        // the chunk records of the wide front stage: grown to the largest call seen, plus a quarter
+        PSK_HIP(hipDeviceSynchronize());
+        if (h->d_wide_rec) (void)hipFree(h->d_wide_rec);
+        if (h->d_wide_stat) (void)hipFree(h->d_wide_stat);
+        h->d_wide_rec = h->d_wide_stat = nullptr;
+        h->wide_rec_cap = h->wide_stat_cap = 0;
+        const size_t rb = wide_rec_need + wide_rec_need / 4, sb = wide_stat_need + wide_stat_need / 4;
+        if (hipMalloc(&h->d_wide_rec, rb) == hipSuccess && hipMalloc(&h->d_wide_stat, sb) == hipSuccess) {
+            h->wide_rec_cap = rb, h->wide_stat_cap = sb;
+        } else {  // (out of device memory: the reference-order kernel carries these calls)
+            (void)hipGetLastError();
+            for (uint32_t i = 0; i < res.cnt_wide; i++) {
+                psk::ChanPlan &p = plans[h_list[off_wide + i]];
+                p.mode = psk::PLAN_SEQ;
+                p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT);
+            }
+            res.cnt_wide = 0;
+            res.any_seq = true;
+        }
+    }
+    // the reference-order kernel's wide build (samplesPerBaud > kSeqMaxS): a list of its own -- the other build's symbolEnergy[] is
+    // kSeqMaxS long -- and a row of symbolEnergy[] in device memory for each channel of it, as long as the widest
+    uint32_t n_wide_seq = 0, wide_seq_S = 0;
+    for (uint32_t i = 0; i < nch; i++)
+        if (plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) {
+            n_wide_seq++;
+            wide_seq_S = plans[i].S > wide_seq_S ? plans[i].S : wide_seq_S;
+        }
+    if (n_wide_seq && (size_t)n_wide_seq * wide_seq_S > h->wide_symE_cap) {
+        PSK_HIP(hipDeviceSynchronize());
+        if (h->d_wide_symE) (void)hipFree(h->d_wide_symE);
+        h->d_wide_symE = nullptr;
+        h->wide_symE_cap = 0;
+        const size_t need = (size_t)n_wide_seq * wide_seq_S, cap = need + need / 4;
+        PSK_HIP(hipMalloc((void **)&h->d_wide_symE, sizeof(double) * cap));
+        h->wide_symE_cap = cap;
+    }
+    if (n_wide_seq && !tile_syms) {  // (the rows of symbolEnergy[] are ordered like the scratch of the time-tiled kernels)
+        if (!h->tile_ev)
+            PSK_HIP(hipEventCreateWithFlags(&h->tile_ev, hipEventDisableTiming));
+        if (h->tile_ev_used && h->tile_stream != stream)
+            PSK_HIP(hipStreamWaitEvent(stream, h->tile_ev, 0));
     }
     if (tile_syms) {
         if (!h->tile_ev)
@@ -1251,12 +1349,15 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         }
     }
     // the reference-order kernel's two lists when CS16 channels are read in place: float-build channels first, then the others
+    // (and the wide symbols' last)
     uint32_t n_in_place = 0;
     for (uint32_t i = 0; i < nch; i++) n_in_place += (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? 1u : 0u;
-    if (n_in_place) {
+    const uint32_t n_seq_narrow = nch - n_in_place - n_wide_seq;
+    if (n_in_place || n_wide_seq) {
         uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_seq_offset(nch));
-        uint32_t a = 0, b = nch - n_in_place;
-        for (uint32_t i = 0; i < nch; i++) seq[(plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? b++ : a++] = i;
+        uint32_t a = 0, b = n_seq_narrow, c = nch - n_wide_seq;
+        for (uint32_t i = 0; i < nch; i++)
+            seq[(plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) ? c++ : (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? b++ : a++] = i;
     }
     // PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call
     // reads exist, what it leaves behind fits the rings, its place in the scratch of the time-tiled kernels lies inside it -- is
@@ -1294,6 +1395,12 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 why = "window class without a wave-scan instantiation planned for one";
             else if (p.mode == psk::PLAN_FAST && p.n_out > psk::kResyncCount)
                 why = "a piece longer than 2^20 symbols on the wave-scan kernels";
+            else if ((p.lf_flags & psk::PLAN_TILED) && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS && p.mode == psk::PLAN_FAST && p.n_out &&
+                     (psk::wide_chunks(p.S) > wide_z || (p.tile_off + nb * 128u) * wide_z * psk::wide_rec_bytes() > h->wide_rec_cap ||
+                      ((uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks) * wide_z * psk::wide_stat_bytes() > h->wide_stat_cap))
+                why = "place in the wide-symbol scratch outside it";
+            else if (p.S > kSeqMaxS && (p.S > wide_seq_S || !h->d_wide_symE || (size_t)n_wide_seq * wide_seq_S > h->wide_symE_cap))
+                why = "wide symbol without a row of symbolEnergy";
             else if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.n_in &&
                      (!cv || (const char *)p.in < (const char *)cv->buf ||
                       (const char *)p.in + sizeof(float2) * p.n_in > (const char *)cv->buf + cv->cap))
@@ -1321,8 +1428,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     // (nor calls with CS16 packets: the conversion scratch is one per stream, and the next call's pre-pass must not overwrite it
     // under the side streams of this one)
     bool deferred = fork && (h->opt_deferred || g_split_mode) && (!cont || g_split_mode) && !tile_syms && !res.cnt_any && !res.any_seq &&
-                    !n_cvt;
-    if (fork && !cont && !h->opt_deferred && h->opt_split > 1 && !tile_syms && !res.cnt_any && !res.any_seq && !n_cvt) {
+                    !n_cvt && !n_wide_seq;
+    if (fork && !cont && !h->opt_deferred && h->opt_split > 1 && !tile_syms && !res.cnt_any && !res.any_seq && !n_cvt && !n_wide_seq) {
         // Classes that cannot be resident together (a SIMD's registers hold four waves of the short windows or two of the long
         // ones) take two rounds of waves, and a wave that starts late still needs the whole call's time at the lone-wave rate.
         // Cut in time, the pieces of the short class that start late are short too, and the class runs its last pieces with the
@@ -1364,7 +1471,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         hdr[0] = 0u;                       // channels handed over: counted by the kernels
         hdr[1] = res.any_seq ? 1u : 0u;    // channels planned for the reference-order kernel
     }
-    const size_t up_bytes = n_in_place ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
+    const size_t up_bytes = (n_in_place || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
                             : n_cvt    ? slot_cvt_offset(nch) + sizeof(psk::CvtDesc) * n_cvt
                                        : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
     if (h->opt_up_stream) {
@@ -1444,6 +1551,24 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                                          h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf, stream));
             PSK_HIP(mark("tile_back (any)", (int)res.max_S_any, 0, off_any, res.cnt_any, tiles_max_any, y_len, 0));
             PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_any, ch0, res.cnt_any, tiles_max_any, h->d_state, h->d_tiles,
+                                          h->d_ts, h->d_test, 0u, 0u, stream));
+        }
+        if (res.cnt_wide) {  // (wide symbols: the chunk and pick launches of psk_wide.hip in place of the front stage above)
+            const uint32_t y_len = ring_floats(res.max_n_wide, 512u);
+            PSK_HIP(mark("wide_front (chunk, pick)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, wide_z));
+            PSK_HIP(psk::launch_wide_front(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, res.max_S_wide, h->d_ring,
+                                           h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, h->d_wide_rec, h->d_wide_stat, stream));
+            if (h->opt_pfit)
+                PSK_HIP(mark("pfit (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, pf_second));
+            if (h->opt_pfit)
+                PSK_HIP(psk::launch_pfit(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, h->d_state, h->d_ring,
+                                         h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf,
+                                         pf_second, stream));
+            PSK_HIP(mark("tile_fit (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, 0));
+            PSK_HIP(psk::launch_tile_fit(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, h->d_state, h->d_ring, h->lim.ring_cap,
+                                         h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf, stream));
+            PSK_HIP(mark("tile_back (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, 0));
+            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, h->d_state, h->d_tiles,
                                           h->d_ts, h->d_test, 0u, 0u, stream));
         }
         if (any_quiet && deferred)  // (every launch set ends its own calls: the quiet channels' on the caller's stream)
@@ -1575,19 +1700,23 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             if (any_seq || any_emit)
                 PSK_HIP(mark("seq (reference order)", 0, 0, ~0u, nch, 0, 0, 0));
-            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place)  // any_emit: the exactness guard may hand calls over at run time
+            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], nullptr, ch0, nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
-            if ((any_seq || any_emit) && !diag_no_tail && n_in_place) {  // (CS16 read in place: each build on its own channels)
+            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_wide_seq)) {  // (CS16 read in place, wide symbols: each build on its own channels)
                 const uint32_t *const d_seq = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) +
                                                                                  slot_seq_offset(nch));
-                PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, nch - n_in_place, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, n_seq_narrow, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
-                PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_seq + (nch - n_in_place), ch0, n_in_place, h->d_state, h->d_ring,
+                PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_seq + n_seq_narrow, ch0, n_in_place, h->d_state, h->d_ring,
                                              h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
+                if (n_wide_seq)
+                    PSK_HIP(mark("seq_wide (reference order, samplesPerBaud > 1024)", (int)wide_seq_S, 0, ~0u, 0, 0, 0, 0));
+                PSK_HIP(psk::launch_seq_wide(h->d_plans[slot], d_seq + (nch - n_wide_seq), ch0, n_wide_seq, h->d_state, h->d_ring,
+                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, h->d_wide_symE, wide_seq_S, stream));
             }
         }
-        if (tile_syms)
+        if (tile_syms || n_wide_seq)
             PSK_HIP(hipEventRecord(h->tile_ev, stream));
         if (n_cvt) {
             PSK_HIP(hipEventRecord(cv->ev, stream));
@@ -1602,7 +1731,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         return est;
     }
     commit();
-    if (tile_syms) {
+    if (tile_syms || n_wide_seq) {
         h->tile_ev_used = true;
         h->tile_stream = stream;
     }

@@ -94,8 +94,9 @@ inline bool fast_kernel_has(uint32_t S, uint32_t A)
     return A <= (S <= 16 ? 1024u : 512u);
 }
 // window classes without an instantiation go through the time-tiled kernels behind a front stage that takes samplesPerBaud
-// and numAvg at run time (psk_tile.hip: psk_tile_front_any_kernel; up to 16 timing phases per lane)
-inline bool any_front_has(uint32_t S) { return S >= 2 && S <= 1024; }
+// and numAvg at run time (psk_tile.hip: psk_tile_front_any_kernel, up to 16 timing phases per lane, samplesPerBaud <= 1024; wider
+// symbols psk_wide.hip, 1024 phases a wave)
+inline bool any_front_has(uint32_t S) { return S >= 2; }
 // history blocks of the instantiation that takes a window of numAvg symbols
 inline int fast_hist_blocks(uint32_t A) { return A <= 128u ? 1 : A <= 256u ? 2 : A <= 512u ? 4 : 8; }
 

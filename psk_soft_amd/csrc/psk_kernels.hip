@@ -32,6 +32,13 @@
 #if PSK_INST_CS16
 #define psk psk_cs16
 #endif
+// -DPSK_SEQ_WIDE=1 (Makefile: psk_seq_wide.o): the reference-order kernel alone for samplesPerBaud > kSeqMaxS, in namespace psk_seqw,
+// exported as launch_seq_wide: symbolEnergy[] lives in a row of device memory per channel of the launch (psk_capi.cpp sizes the
+// rows by the launch's widest channel), and the loops over it are spread over the wave's lanes -- element k always in lane
+// k mod 64, so that no lane reads a sum another lane has written
+#if PSK_SEQ_WIDE
+#define psk psk_seqw
+#endif
 #include "psk_fast_kernel.h"
 
 namespace psk {
@@ -163,9 +170,17 @@ __device__ void seq_emit_symbol(SeqEmit &E, cf32 sample, int sampleIndex, bool h
 
 __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict__ plans, const uint32_t *__restrict__ list, uint32_t ch0,
                                                      ChanState *__restrict__ states, float2 *__restrict__ rings,
-                                                     uint32_t ring_cap, float *__restrict__ yvs, uint32_t fit_cap)
+                                                     uint32_t ring_cap, float *__restrict__ yvs, uint32_t fit_cap
+#if PSK_SEQ_WIDE
+                                                     , double *__restrict__ symE_rows, uint32_t symE_stride
+#endif
+                                                     )
 {
+#if PSK_SEQ_WIDE
+    double *const symE = symE_rows + (size_t)blockIdx.x * symE_stride;
+#else
     __shared__ double symE[kSeqMaxS];
+#endif
     __shared__ float2 chunk[kSeqChunk];
     __shared__ uint64_t sh_head;
     const int lane = threadIdx.x & 63;
@@ -220,6 +235,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
         E.n_emit = 0;
         if (p.lf_flags & LF_RECOMPUTE)
             E.fit.reset_sums();
+#if !PSK_SEQ_WIDE
         if (!s1) {  // resyncEnergy ran in this call's prologue, :619-636
             for (uint32_t k = 0; k < S; k++) symE[k] = 0.0;
             for (uint64_t j = 0; j < X.L0; j++) {
@@ -231,7 +247,93 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
             }
             count = 0;
         }
+#endif
     }
+#if PSK_SEQ_WIDE
+    // resyncEnergy ran in this call's prologue, :619-636: element k sums samples k, k + S, ... in order
+    auto resync = [&](uint64_t from, uint64_t n) {
+        for (uint32_t k = lane; k < S; k += kWave) {
+            double acc = 0.0;
+            for (uint64_t j = k; j < n; j += S) {
+                const float2 v = x_at(X, from + j);
+                acc += (double)norm_f(v.x, v.y);
+            }
+            symE[k] = acc;
+        }
+    };
+    if (!s1) {
+        resync(0, X.L0);
+        idx = (uint32_t)(X.L0 % S);
+        count = 0;
+    }
+    for (uint64_t base = 0; base < N; base += kSeqChunk) {
+        const uint32_t cnt = (N - base) < (uint64_t)kSeqChunk ? (uint32_t)(N - base) : (uint32_t)kSeqChunk;
+        __syncthreads();
+        for (uint32_t j = lane; j < cnt; j += kWave) chunk[j] = x_at(X, X.L0 + base + j);
+        __syncthreads();
+        if (s1) {  // samplesPerBaud == 1, :468-469
+            if (lane == 0)
+                for (uint32_t jj = 0; jj < cnt; jj++) {
+                    cf32 cur;
+                    cur.re = chunk[jj].x;
+                    cur.im = chunk[jj].y;
+                    seq_emit_symbol(E, cur, 0, false);
+                }
+            continue;
+        }
+        // the samples up to the next symbol boundary: each adds to its own element, :447-451
+        for (uint32_t jj = 0; jj < cnt;) {
+            const uint32_t run = S - idx < cnt - jj ? S - idx : cnt - jj;
+            for (uint32_t k = idx + ((uint32_t)(lane - (int)idx) & (kWave - 1)); k < idx + run; k += kWave) {
+                const float2 v = chunk[jj + (k - idx)];
+                symE[k] += (double)norm_f(v.x, v.y);
+            }
+            size += run;
+            jj += run;
+            idx += run;
+            if (idx < S)
+                continue;
+            idx = 0;  // :587
+            if (size != D)  // :457
+                continue;
+            // std::max_element with `<` (:462): the running best moves on a strictly larger sum only, so a NaN never wins and
+            // holds phase 0 if it stands there -- the first maximum among the sums that are not NaN, else 0
+            double bv = 0.0;
+            uint32_t bk = 0xFFFFFFFFu;
+            for (uint32_t k = lane; k < S; k += kWave) {
+                const double v = symE[k];
+                if (v == v && (bk == 0xFFFFFFFFu || bv < v))
+                    bv = v, bk = k;
+            }
+            for (int d = 1; d < kWave; d <<= 1) {
+                const double ov = __shfl_xor(bv, d);
+                const uint32_t ok = (uint32_t)__shfl_xor((int)bk, d);
+                if (ok != 0xFFFFFFFFu && (bk == 0xFFFFFFFFu || bv < ov || (ov == bv && ok < bk)))
+                    bv = ov, bk = ok;
+            }
+            const bool nan0 = lane == 0 && !(symE[0] == symE[0]);
+            const uint32_t best = (__any(nan0) || bk >= S) ? 0u : bk;
+            if (lane == 0) {
+                float2 pk = x_at(X, head + best);
+                cf32 smp;
+                smp.re = pk.x;
+                smp.im = pk.y;
+                seq_emit_symbol(E, smp, (int)best, true);
+            }
+            for (uint32_t k = lane; k < S; k += kWave) {  // :572-577
+                float2 o = x_at(X, head + k);
+                symE[k] -= (double)norm_f(o.x, o.y);
+            }
+            head += S;  // :579-580
+            size -= S;
+            count++;
+            if (count == kResyncCount) {  // :582-583
+                resync(head, size);
+                count = 0;
+            }
+        }
+    }
+#else
     for (uint64_t base = 0; base < N; base += kSeqChunk) {
         const uint32_t cnt = (N - base) < (uint64_t)kSeqChunk ? (uint32_t)(N - base) : (uint32_t)kSeqChunk;
         __syncthreads();
@@ -287,6 +389,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
             }
         }
     }
+#endif
     if (lane == 0) {
         // end-of-call wrap, cpp/psk_soft.cpp:592-603
         const float wrapValue = (float)(kTwoPi * (double)p.M);
@@ -321,7 +424,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
 
 }  // namespace psk
 
-#if !PSK_INST_CS16
+#if !PSK_INST_CS16 && !PSK_SEQ_WIDE
 // ---------------------------------------------------------------------------------
 // launchers (called from psk_capi.cpp through plain C++ declarations).  Every (samplesPerBaud,
 // history depth, screened / exact) instantiation of the wave-scan kernel is its own translation
@@ -470,6 +573,18 @@ hipError_t launch_fast(int S, int H, int exact, PSK_FAST_ARGS)
 namespace psk {
 #endif
 
+#if PSK_SEQ_WIDE
+// (symE: a row of symE_stride doubles for each of the nch channels of the list)
+hipError_t launch_seq(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
+                      uint32_t ring_cap, float *yvs, uint32_t fit_cap, double *symE, uint32_t symE_stride, hipStream_t stream)
+{
+    if (!nch)
+        return hipSuccess;
+    hipLaunchKernelGGL(psk_seq_kernel, dim3(nch), dim3(kWave), 0, stream, plans, list, ch0, states, rings, ring_cap, yvs,
+                       fit_cap, symE, symE_stride);
+    return hipGetLastError();
+}
+#else
 hipError_t launch_seq(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
                       uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
 {
@@ -479,6 +594,7 @@ hipError_t launch_seq(const ChanPlan *plans, const uint32_t *list, uint32_t ch0,
                        fit_cap);
     return hipGetLastError();
 }
+#endif
 // Measurement support: the empirical read ceiling -- 16-byte loads over a
 // buffer, summed, nothing written (the sum only reaches memory if it is NaN-free and equals a value
 // it cannot have).  4 independent loads per thread in flight, grid-stride, 2048 workgroups of 256.
@@ -518,6 +634,17 @@ hipError_t launch_seq_cs16(const void *plans, const uint32_t *list, uint32_t ch0
 {
     return psk_cs16::launch_seq(static_cast<const psk_cs16::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cs16::ChanState *>(states),
                                 rings, ring_cap, yvs, fit_cap, stream);
+}
+}  // namespace psk
+#endif
+#if PSK_SEQ_WIDE
+#undef psk
+namespace psk {
+hipError_t launch_seq_wide(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, double *symE, uint32_t symE_stride, hipStream_t stream)
+{
+    return psk_seqw::launch_seq(static_cast<const psk_seqw::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_seqw::ChanState *>(states),
+                                rings, ring_cap, yvs, fit_cap, symE, symE_stride, stream);
 }
 }  // namespace psk
 #endif

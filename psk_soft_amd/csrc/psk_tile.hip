@@ -2,6 +2,7 @@
 // samplesPerBaud, and the dispatch to the per-samplesPerBaud instantiations of the front kernel (psk_tile_inst.hip).
 #include "psk_tile_kernel.h"
 #include "psk_pfit.h"
+#include "psk_tile_any.h"
 
 namespace psk {
 
@@ -67,98 +68,6 @@ PSK_DEV bool tile_fold(const ChanPlan &p, const TileInfo *ti, int n_tiles, int l
 // the fit kernel's fold decides as for the instantiated front kernel.  ~25 us per block of 128 symbols and tile
 // (the reference-order kernel: 600).
 constexpr int kAnyPhases = 16;  // phases per lane: samplesPerBaud <= 1024
-struct AnyTop {
-    double best, second;
-    int k;
-};
-PSK_DEV AnyTop any_merge(const AnyTop &a, const AnyTop &b)  // first maximum: the larger sum, the lower phase on a tie
-{
-    const bool b_wins = b.best > a.best || (b.best == a.best && b.k < a.k);
-    AnyTop r;
-    r.best = b_wins ? b.best : a.best;
-    r.k = b_wins ? b.k : a.k;
-    const double loser = b_wins ? a.best : b.best;
-    const double s2 = a.second > b.second ? a.second : b.second;
-    r.second = loser > s2 ? loser : s2;
-    return r;
-}
-// wave-wide maximum of a double / minimum of an unsigned: the scan pattern of wave_scan_f64 (row_shr 1, 2, 4, 8, row_bcast 15
-// and 31) with the extremum in place of the addition, lanes without a source taking the identity; the result sits in lane 63
-template <int CTRL, int ROW_MASK>
-PSK_DEV double any_f64_from(double v)
-{
-    return __hiloint2double(__builtin_amdgcn_update_dpp((int)0xFFF00000u, __double2hiint(v), CTRL, ROW_MASK, 0xF, false),
-                            __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xF, false));
-}
-PSK_DEV double any_max_f64(double v)
-{
-    v = __builtin_fmax(v, any_f64_from<0x111, 0xF>(v));
-    v = __builtin_fmax(v, any_f64_from<0x112, 0xF>(v));
-    v = __builtin_fmax(v, any_f64_from<0x114, 0xF>(v));
-    v = __builtin_fmax(v, any_f64_from<0x118, 0xF>(v));
-    v = __builtin_fmax(v, any_f64_from<0x142, 0xA>(v));
-    v = __builtin_fmax(v, any_f64_from<0x143, 0xC>(v));
-    return read_lane(v, 63);
-}
-// the same for U independent values, level by level: U chains that do not wait for one another
-template <int CTRL, int ROW_MASK, int U>
-PSK_DEV void any_max_f64_level(double (&v)[U])
-{
-    double o[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) o[u] = any_f64_from<CTRL, ROW_MASK>(v[u]);
-#pragma unroll
-    for (int u = 0; u < U; u++) v[u] = __builtin_fmax(v[u], o[u]);
-}
-template <int U>
-PSK_DEV void any_max_f64_multi(double (&v)[U])
-{
-    any_max_f64_level<0x111, 0xF>(v);
-    any_max_f64_level<0x112, 0xF>(v);
-    any_max_f64_level<0x114, 0xF>(v);
-    any_max_f64_level<0x118, 0xF>(v);
-    any_max_f64_level<0x142, 0xA>(v);
-    any_max_f64_level<0x143, 0xC>(v);
-#pragma unroll
-    for (int u = 0; u < U; u++) v[u] = read_lane(v[u], 63);
-}
-template <int CTRL, int ROW_MASK>
-PSK_DEV unsigned any_u32_from(unsigned v)
-{
-    return (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
-PSK_DEV unsigned any_min_u32(unsigned v)
-{
-    unsigned o;
-    o = any_u32_from<0x111, 0xF>(v), v = o < v ? o : v;
-    o = any_u32_from<0x112, 0xF>(v), v = o < v ? o : v;
-    o = any_u32_from<0x114, 0xF>(v), v = o < v ? o : v;
-    o = any_u32_from<0x118, 0xF>(v), v = o < v ? o : v;
-    o = any_u32_from<0x142, 0xA>(v), v = o < v ? o : v;
-    o = any_u32_from<0x143, 0xC>(v), v = o < v ? o : v;
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-template <int CTRL, int ROW_MASK, int U>
-PSK_DEV void any_min_u32_level(unsigned (&v)[U])
-{
-    unsigned o[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) o[u] = any_u32_from<CTRL, ROW_MASK>(v[u]);
-#pragma unroll
-    for (int u = 0; u < U; u++) v[u] = o[u] < v[u] ? o[u] : v[u];
-}
-template <int U>
-PSK_DEV void any_min_u32_multi(unsigned (&v)[U])
-{
-    any_min_u32_level<0x111, 0xF>(v);
-    any_min_u32_level<0x112, 0xF>(v);
-    any_min_u32_level<0x114, 0xF>(v);
-    any_min_u32_level<0x118, 0xF>(v);
-    any_min_u32_level<0x142, 0xA>(v);
-    any_min_u32_level<0x143, 0xC>(v);
-#pragma unroll
-    for (int u = 0; u < U; u++) v[u] = (unsigned)__builtin_amdgcn_readlane((int)v[u], 63);
-}
 // NP: phases a lane holds at most (samplesPerBaud <= 64 * NP for every channel of the launch).  With one phase a lane (NP = 1,
 // samplesPerBaud <= 64) the energies entering and leaving the window are asked for eight symbols at a time: the walk is one
 // dependent step per symbol, and a step that waits for its own two loads is all latency.

@@ -35,7 +35,7 @@ STRICT = os.environ.get("PSK_FUZZ_STRICT", "1") != "0"  # every float of soft / 
 XD = 0.01
 # PSK_FUZZ_S / PSK_FUZZ_A / PSK_FUZZ_N: comma-separated lists that replace the default draws (to aim a run at some instantiations);
 # PSK_FUZZ_WINDOW / PSK_FUZZ_PACKET: the handle's max_window_samples (samplesPerBaud * numAvg; the scripts set numAvg up to 300)
-# and max_packet_complex (a stream is up to 12000 symbols long), for samplesPerBaud beyond 64
+# and max_packet_complex (a stream is up to 12000 symbols long, 150 for samplesPerBaud > 1024), for samplesPerBaud beyond 64
 S_CHOICES = [int(v) for v in os.environ["PSK_FUZZ_S"].split(",")] if os.environ.get("PSK_FUZZ_S") else (
     [2, 4, 5, 8, 8, 8, 10, 10, 16, 3, 7, 1, 6, 9, 11, 12, 13, 14, 15, 33] + list(range(17, 33)))
 A_CHOICES = [int(v) for v in os.environ["PSK_FUZZ_A"].split(",")] if os.environ.get("PSK_FUZZ_A") else (
@@ -117,7 +117,8 @@ def main():
             M = rng.choice(M_CHOICES)
             n = rng.choice(N_CHOICES)
             p = dict(samplesPerBaud=S, constelationSize=M, numAvg=A, phaseAvg=n, differentialDecoding=int(rng.random() < 0.25))
-            N = max(S * rng.choice([50, 300, 1200, 3000, 12000]), 64)
+            # (wide symbols, samplesPerBaud > 1024: a few dozen to a few hundred symbols -- at 65535 that is already ~10^7 samples)
+            N = max(S * rng.choice([50, 300, 1200, 3000, 12000] if S <= 1024 else [20, 60, 150]), 64)
             sig = make_signal(rng, nrng, M, max(S, 1), N)
             # script: a list of events; cuts with occasional tiny / empty packets, property changes, resets
             n_calls = rng.choice([1, 2, 3, 5])
@@ -126,7 +127,7 @@ def main():
             for cut in cuts + [N]:
                 if rng.random() < 0.15:
                     key = rng.choice(["phaseAvg", "numAvg", "constelationSize", "resetState", "differentialDecoding"])
-                    val = {"phaseAvg": rng.choice([5, 50, 300]), "numAvg": rng.choice([10, 100, 300]),
+                    val = {"phaseAvg": rng.choice([5, 50, 300]), "numAvg": rng.choice([10, 100, 300] if S <= 1024 else [1, 2, 5]),
                            "constelationSize": rng.choice([2, 4, 8]), "resetState": 1,
                            "differentialDecoding": rng.choice([0, 1])}[key]
                     ev.append(("set", key, val))
