@@ -40,6 +40,13 @@ hipError_t launch_fast_cs16(int S, int exact, const ChanPlan *plans, const uint3
                             float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
 hipError_t launch_seq_cs16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
                            uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
+// complex int8 packets (psk_cs8.hip): the same four entry points, for the builds with PSK_INST_CS8=1
+hipError_t launch_cs8_convert(const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
+bool fast_cs8_has(int S);
+hipError_t launch_fast_cs8(int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
+                           float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
+hipError_t launch_seq_cs8(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                          uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
 // time-tiled kernels (psk_tile.hip)
 bool tile_front_has(int S, int H);
 hipError_t launch_tile_front(int S, int H, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles,
@@ -99,16 +106,19 @@ psk_soft_status fail(psk_soft_status st, const std::string &msg)
 constexpr int kPlanSlots = 4;
 constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that mixes window classes (see psk_soft_process_device)
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
-constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 packets, one per stream that uses them (see CvtScratch)
-// bytes of a packet's element and the alignment its data needs
-inline size_t elem_bytes(const psk_soft_packet_t &k) { return k.format == PSK_SOFT_FORMAT_CS16 ? sizeof(int16_t) : sizeof(float); }
-// bytes of the upload slot of a call of n channels: header, plans, compact lists, CS16 conversion descriptors (psk_plan.h)
+constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 packets, one per stream that uses them (see CvtScratch)
+// bytes of a packet's element
+inline size_t elem_bytes(const psk_soft_packet_t &k)
+{
+    return k.format == PSK_SOFT_FORMAT_CS16 ? sizeof(int16_t) : k.format == PSK_SOFT_FORMAT_CS8 ? sizeof(int8_t) : sizeof(float);
+}
+// bytes of the upload slot of a call of n channels: header, plans, compact lists, CS16 / CS8 conversion descriptors (psk_plan.h)
 inline size_t slot_cvt_offset(size_t n)
 {
     return (psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * n + 15u) & ~(size_t)15u;
 }
-// ... then two more channel lists for the reference-order kernel when a call has CS16 channels on the in-place kernels: the channels
-// of the float build, the channels of the CS16 build
+// ... then one more channel list for the reference-order kernel when a call has CS16 / CS8 channels on the in-place kernels: the
+// channels of the float build, of the CS16 build, of the CS8 build (and of the wide-symbol build)
 inline size_t slot_seq_offset(size_t n) { return slot_cvt_offset(n) + sizeof(psk::CvtDesc) * n; }
 inline size_t slot_bytes(size_t n) { return slot_seq_offset(n) + sizeof(uint32_t) * n; }
 
@@ -259,10 +269,12 @@ struct CvtScratch {
 // per CU, and sized for the whole launch it would take the residency of thousands of ordinary channels with it.
 constexpr uint32_t kFastFitMax = 32768 - 128;
 constexpr uint32_t kDeepFit = 2048 - 128;
-// second index of the per-class tables: history blocks (+ 8: deep fit window); 3: one block, CS16 packets read in place
-const int kClassH[] = {1, 3, 2, 4, 8, 9, 10, 12, 16};
+// second index of the per-class tables: history blocks (+ 8: deep fit window); 3: one block, CS16 packets read in place; 5: one
+// block, CS8 packets read in place
+const int kClassH[] = {1, 3, 5, 2, 4, 8, 9, 10, 12, 16};
 constexpr int kClassCs16 = 3;
-inline int class_H(int Hi) { return Hi == kClassCs16 ? 1 : Hi > 8 ? Hi - 8 : Hi; }
+constexpr int kClassCs8 = 5;
+inline int class_H(int Hi) { return Hi == kClassCs16 || Hi == kClassCs8 ? 1 : Hi > 8 ? Hi - 8 : Hi; }
 constexpr int kNumClassH = (int)(sizeof(kClassH) / sizeof(kClassH[0]));
 // time-tiled kernels, automatic choice (measured, tools/tiled_sweep2.sh: QPSK, samplesPerBaud 8): a class of at most 64
 // channels whose longest call has at least 16 blocks of 128 symbols, or of at most 512 channels and 192 blocks (at 128
@@ -378,7 +390,7 @@ struct psk_soft_handle {
     hipStream_t tile_stream = nullptr;  // stream of the last call that used the scratch
     bool tile_ev_used = false;
     bool poisoned = false;  // a HIP call failed after kernels of a call were enqueued: host mirror and device state may disagree
-    // CS16 packets: conversion scratch (CvtScratch)
+    // CS16 / CS8 packets: conversion scratch (CvtScratch)
     CvtScratch cvt[kCvtScratch];
     uint64_t cvt_calls = 0;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
@@ -737,6 +749,17 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         return (p.lf_flags & psk::PLAN_CS16) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
                p.lf_n <= kDeepFit && psk::fast_cs16_has((int)p.S);
     };
+    // (CS8: the same classes, PSK_INST_CS8, a class of their own too)
+    auto cs8_in_place = [&](const psk::ChanPlan &p) {
+        return (p.lf_flags & psk::PLAN_CS8) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
+               p.lf_n <= kDeepFit && psk::fast_cs8_has((int)p.S);
+    };
+    // the class of a planned channel that emits on the wave-scan kernels
+    auto class_of = [&](const psk::ChanPlan &p) {
+        return (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16
+               : (p.lf_flags & psk::PLAN_CS8_IN_PLACE) ? kClassCs8
+                                                        : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+    };
     auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
         r.any = true;
         if (p.mode == psk::PLAN_FAST) {
@@ -762,7 +785,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 r.any_emit = true;
                 if (cs16_in_place(p))
                     p.lf_flags |= psk::PLAN_CS16_IN_PLACE;
-                const int Hh = (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16 : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+                if (cs8_in_place(p))
+                    p.lf_flags |= psk::PLAN_CS8_IN_PLACE;
+                const int Hh = class_of(p);
                 r.need_SH[p.S][Hh] = true;
                 r.cnt_SH[p.S][Hh] += mult;
                 if (p.lf_n > r.max_n[p.S][Hh]) r.max_n[p.S][Hh] = p.lf_n;
@@ -783,9 +808,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         }
     };
     uint32_t *const handed_over = dry ? nullptr : psk::plan_header(h->d_plans[slot]);  // (psk_plan.h)
-    // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 pairs)
+    // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 pairs, 2-byte aligned int8 pairs)
     auto misaligned = [&](const psk::ChanPlan &p) {
-        const uintptr_t in_mask = (p.lf_flags & psk::PLAN_CS16) ? 3u : 7u;
+        const uintptr_t in_mask = (p.lf_flags & psk::PLAN_CS16) ? 3u : (p.lf_flags & psk::PLAN_CS8) ? 1u : 7u;
         return !dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & in_mask) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
                         ((uintptr_t)p.phase & 3u) || ((uintptr_t)p.sidx & 3u));
     };
@@ -915,10 +940,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     if (res.st != PSK_SOFT_OK) {
         if (res.why == 2)
             return fail(PSK_SOFT_ERR_INVALID_ARG,
-                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
+                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2), soft 8, bits 4, phase 4, sampleIndex 4");
         if (res.why == 3) {
             char buf[160];
-            std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1)",
+            std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3)",
                           ch0 + res.bad, (unsigned)pkts[res.bad].format);
             return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
         }
@@ -962,16 +987,19 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (h->slot_aux_used[k][a])
                     PSK_HIP(hipStreamWaitEvent(stream, h->slot_aux_ev[k][a], 0));
         }
-    // CS16 channels read in place have a class of their own (kClassCs16), which has no time-tiled kernels: where the float class
-    // would go through those (the same choice as below, on the two classes together), its channels go back to the float class and
-    // to the conversion pre-pass
-    if (!stamped || (plans[0].lf_flags & psk::PLAN_CS16_IN_PLACE))
+    // CS16 and CS8 channels read in place have classes of their own (kClassCs16, kClassCs8), which have no time-tiled kernels: where
+    // the float class would go through those (the same choice as below, on the three classes together), their channels go back to
+    // the float class and to the conversion pre-pass
+    if (!stamped || (plans[0].lf_flags & (psk::PLAN_CS16_IN_PLACE | psk::PLAN_CS8_IN_PLACE)))
         for (int S = 2; S <= 16; S++) {
-            if (!res.need_SH[S][kClassCs16] || !h->opt_tiled || !psk::tile_front_has(S, 1))
+            if ((!res.need_SH[S][kClassCs16] && !res.need_SH[S][kClassCs8]) || !h->opt_tiled || !psk::tile_front_has(S, 1))
                 continue;
-            const uint32_t cnt = res.cnt_SH[S][1] + res.cnt_SH[S][kClassCs16];
-            const uint32_t mb = res.max_blocks_SH[S][1] > res.max_blocks_SH[S][kClassCs16] ? res.max_blocks_SH[S][1] : res.max_blocks_SH[S][kClassCs16];
-            const uint32_t mn = res.max_n[S][1] > res.max_n[S][kClassCs16] ? res.max_n[S][1] : res.max_n[S][kClassCs16];
+            uint32_t cnt = res.cnt_SH[S][1], mb = res.max_blocks_SH[S][1], mn = res.max_n[S][1];
+            for (int Hc : {kClassCs16, kClassCs8}) {
+                cnt += res.cnt_SH[S][Hc];
+                mb = res.max_blocks_SH[S][Hc] > mb ? res.max_blocks_SH[S][Hc] : mb;
+                mn = res.max_n[S][Hc] > mn ? res.max_n[S][Hc] : mn;
+            }
             const bool pipe = h->opt_pipe == 2 ? mb >= 4u
                                                : h->opt_pipe && h->opt_tiled == 1 && cnt >= kPipeMinChannels && cnt <= kPipeMaxChannels &&
                                                      mb >= kPipeMinBlocks && !cont && mn + 128u <= kPipeMaxYLen;
@@ -983,14 +1011,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             res.cnt_SH[S][1] = cnt;
             res.max_blocks_SH[S][1] = mb;
             res.max_n[S][1] = mn;
-            res.max_A[S][1] = res.max_A[S][1] > res.max_A[S][kClassCs16] ? res.max_A[S][1] : res.max_A[S][kClassCs16];
-            res.blocks_SH[S][1] += res.blocks_SH[S][kClassCs16];
-            res.need_SH[S][kClassCs16] = false;
-            res.cnt_SH[S][kClassCs16] = res.max_blocks_SH[S][kClassCs16] = res.max_n[S][kClassCs16] = res.max_A[S][kClassCs16] = 0;
-            res.blocks_SH[S][kClassCs16] = 0;
+            for (int Hc : {kClassCs16, kClassCs8}) {
+                res.max_A[S][1] = res.max_A[S][1] > res.max_A[S][Hc] ? res.max_A[S][1] : res.max_A[S][Hc];
+                res.blocks_SH[S][1] += res.blocks_SH[S][Hc];
+                res.need_SH[S][Hc] = false;
+                res.cnt_SH[S][Hc] = res.max_blocks_SH[S][Hc] = res.max_n[S][Hc] = res.max_A[S][Hc] = 0;
+                res.blocks_SH[S][Hc] = 0;
+            }
             for (uint32_t i = 0; i < nch; i++)
                 if (plans[i].S == (uint32_t)S)
-                    plans[i].lf_flags &= ~(uint32_t)psk::PLAN_CS16_IN_PLACE;
+                    plans[i].lf_flags &= ~(uint32_t)(psk::PLAN_CS16_IN_PLACE | psk::PLAN_CS8_IN_PLACE);
         }
     // compact lists, one per launch, behind the plans: first the channels that emit nothing, then every (S, H)
     // class in launch order
@@ -1019,7 +1049,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
                 h_list[off_any + fill_any++] = i;
             } else if (p.n_out) {
-                const int Hh = (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16 : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+                const int Hh = class_of(p);
                 h_list[off_SH[p.S][Hh] + fill_SH[p.S][Hh]++] = i;
             } else {
                 h_list[off_quiet + fill_quiet++] = i;
@@ -1098,7 +1128,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     for (int pass = 0; pass < (h->opt_tiled ? 2 : 0); pass++) {
         for (int S : kFastS)
             for (int H : kClassH) {
-                if (!res.need_SH[S][H] || H == kClassCs16 || !psk::tile_front_has(S, class_H(H)))
+                if (!res.need_SH[S][H] || H == kClassCs16 || H == kClassCs8 || !psk::tile_front_has(S, class_H(H)))
                     continue;
                 // pipelined: the serial fit of a range under the front stage of the next (see kPipeMinChannels)
                 // (PSK_SOFT_PIPELINED=2, tests: wherever the kernels allow it, a few blocks to a range)
@@ -1289,18 +1319,29 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
         }
     }
-    // CS16 packets (psk_cs16.hip): converted into float2 rows of the conversion scratch by one pre-pass in front of the call's first
-    // kernel; their plans point at the rows from here on.  The descriptors travel behind the plans, in the same upload.
-    uint32_t n_cvt = 0;
-    uint64_t cvt_max_n = 0;
+    // CS16 and CS8 packets (psk_cs16.hip, psk_cs8.hip): converted into float2 rows of the conversion scratch by one pre-pass per
+    // format in front of the call's first kernel; their plans point at the rows from here on.  The descriptors travel behind the
+    // plans, in the same upload: the CS16 packets' first, then the CS8 packets'.
+    auto cvt_flag = [](const psk::ChanPlan &p) -> uint32_t {  // (the format flag of a packet the pre-pass converts, else 0)
+        if (p.mode == psk::PLAN_SKIP || !p.n_in)
+            return 0u;
+        if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE))
+            return psk::PLAN_CS16;
+        if ((p.lf_flags & psk::PLAN_CS8) && !(p.lf_flags & psk::PLAN_CS8_IN_PLACE))
+            return psk::PLAN_CS8;
+        return 0u;
+    };
+    uint32_t n_cvt = 0, n_cvt16 = 0;
+    uint64_t cvt_max_n16 = 0, cvt_max_n8 = 0;
     CvtScratch *cv = nullptr;
     {
         size_t need = 0;
         for (uint32_t i = 0; i < nch; i++) {
             const psk::ChanPlan &p = plans[i];
-            if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.mode != psk::PLAN_SKIP && p.n_in) {
+            if (const uint32_t f = cvt_flag(p)) {
                 need += align_up(sizeof(float2) * p.n_in, 128);
                 n_cvt++;
+                n_cvt16 += f == psk::PLAN_CS16 ? 1u : 0u;
             }
         }
         if (n_cvt) {
@@ -1333,31 +1374,39 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             psk::CvtDesc *const desc =
                 reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_cvt_offset(nch));
             size_t off = 0;
-            uint32_t k = 0;
+            uint32_t k16 = 0, k8 = n_cvt16;
             for (uint32_t i = 0; i < nch; i++) {
                 psk::ChanPlan &p = plans[i];
-                if (!((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.mode != psk::PLAN_SKIP && p.n_in))
+                const uint32_t f = cvt_flag(p);
+                if (!f)
                     continue;
+                const uint32_t k = f == psk::PLAN_CS16 ? k16++ : k8++;
                 desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
                 desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
                 desc[k].n = p.n_in;
                 p.in = desc[k].dst;
                 off += align_up(sizeof(float2) * p.n_in, 128);
-                cvt_max_n = p.n_in > cvt_max_n ? p.n_in : cvt_max_n;
-                k++;
+                uint64_t &mx = f == psk::PLAN_CS16 ? cvt_max_n16 : cvt_max_n8;
+                mx = p.n_in > mx ? p.n_in : mx;
             }
         }
     }
-    // the reference-order kernel's two lists when CS16 channels are read in place: float-build channels first, then the others
-    // (and the wide symbols' last)
-    uint32_t n_in_place = 0;
-    for (uint32_t i = 0; i < nch; i++) n_in_place += (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? 1u : 0u;
-    const uint32_t n_seq_narrow = nch - n_in_place - n_wide_seq;
-    if (n_in_place || n_wide_seq) {
+    // the reference-order kernel's lists when CS16 / CS8 channels are read in place: float-build channels first, then the CS16
+    // build's, then the CS8 build's (and the wide symbols' last)
+    uint32_t n_in_place = 0, n_in_place8 = 0;
+    for (uint32_t i = 0; i < nch; i++) {
+        n_in_place += (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? 1u : 0u;
+        n_in_place8 += (plans[i].lf_flags & psk::PLAN_CS8_IN_PLACE) ? 1u : 0u;
+    }
+    const uint32_t n_seq_narrow = nch - n_in_place - n_in_place8 - n_wide_seq;
+    if (n_in_place || n_in_place8 || n_wide_seq) {
         uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_seq_offset(nch));
-        uint32_t a = 0, b = n_seq_narrow, c = nch - n_wide_seq;
+        uint32_t a = 0, b = n_seq_narrow, b8 = n_seq_narrow + n_in_place, c = nch - n_wide_seq;
         for (uint32_t i = 0; i < nch; i++)
-            seq[(plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) ? c++ : (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? b++ : a++] = i;
+            seq[(plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) ? c++
+                : (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE)              ? b++
+                : (plans[i].lf_flags & psk::PLAN_CS8_IN_PLACE)               ? b8++
+                                                                             : a++] = i;
     }
     // PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call
     // reads exist, what it leaves behind fits the rings, its place in the scratch of the time-tiled kernels lies inside it -- is
@@ -1401,10 +1450,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 why = "place in the wide-symbol scratch outside it";
             else if (p.S > kSeqMaxS && (p.S > wide_seq_S || !h->d_wide_symE || (size_t)n_wide_seq * wide_seq_S > h->wide_symE_cap))
                 why = "wide symbol without a row of symbolEnergy";
-            else if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE) && p.n_in &&
+            else if (cvt_flag(p) &&
                      (!cv || (const char *)p.in < (const char *)cv->buf ||
                       (const char *)p.in + sizeof(float2) * p.n_in > (const char *)cv->buf + cv->cap))
-                why = "converted CS16 packet outside the conversion scratch";
+                why = "converted CS16 / CS8 packet outside the conversion scratch";
         }
         if (why) {
             char buf[200];
@@ -1471,7 +1520,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         hdr[0] = 0u;                       // channels handed over: counted by the kernels
         hdr[1] = res.any_seq ? 1u : 0u;    // channels planned for the reference-order kernel
     }
-    const size_t up_bytes = (n_in_place || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
+    const size_t up_bytes = (n_in_place || n_in_place8 || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
                             : n_cvt    ? slot_cvt_offset(nch) + sizeof(psk::CvtDesc) * n_cvt
                                        : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
     if (h->opt_up_stream) {
@@ -1517,11 +1566,18 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     // left out, which is wrong as soon as a call is handed over; what the two launches cost a small call is measured that way)
     static const bool diag_no_tail = std::getenv("PSK_SOFT_DIAG_NO_TAIL") && std::atoi(std::getenv("PSK_SOFT_DIAG_NO_TAIL")) != 0;
     auto enqueue = [&]() -> psk_soft_status {
-        if (n_cvt) {
-            PSK_HIP(mark("cs16_convert", 0, 0, ~0u, 0, n_cvt, 0, 0));
+        if (n_cvt16) {
+            PSK_HIP(mark("cs16_convert", 0, 0, ~0u, 0, n_cvt16, 0, 0));
             PSK_HIP(psk::launch_cs16_convert(
                 reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)),
-                n_cvt, cvt_max_n, stream));
+                n_cvt16, cvt_max_n16, stream));
+        }
+        if (n_cvt > n_cvt16) {
+            PSK_HIP(mark("cs8_convert", 0, 0, ~0u, 0, n_cvt - n_cvt16, 0, 0));
+            PSK_HIP(psk::launch_cs8_convert(
+                reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)) +
+                    n_cvt16,
+                n_cvt - n_cvt16, cvt_max_n8, stream));
         }
         if (any_quiet)
             PSK_HIP(mark("fast<0,1> (calls that emit nothing)", 0, 1, off_quiet, res.cnt_quiet, 0, ring_floats(res.max_n_quiet, 512u), 0));
@@ -1672,6 +1728,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (H == kClassCs16)
                     PSK_HIP(psk::launch_fast_cs16(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
                                                   h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
+                else if (H == kClassCs8)
+                    PSK_HIP(psk::launch_fast_cs8(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
+                                                 h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
                 else
                     PSK_HIP(psk::launch_fast(S, class_H(H), exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
                                              h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
@@ -1679,6 +1738,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             if (deferred && H == kClassCs16)  // (the class's hand-overs are redone on its own stream, in front of its next call)
                 PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
                                              h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+            else if (deferred && H == kClassCs8)
+                PSK_HIP(psk::launch_seq_cs8(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
+                                            h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
             else if (deferred)
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring, h->lim.ring_cap,
                                         h->d_yv, h->lim.fit_cap, st));
@@ -1700,16 +1762,18 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             if (any_seq || any_emit)
                 PSK_HIP(mark("seq (reference order)", 0, 0, ~0u, nch, 0, 0, 0));
-            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
+            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_in_place8 && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], nullptr, ch0, nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
-            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_wide_seq)) {  // (CS16 read in place, wide symbols: each build on its own channels)
+            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_in_place8 || n_wide_seq)) {  // (CS16 / CS8 read in place, wide symbols: each build on its own channels)
                 const uint32_t *const d_seq = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) +
                                                                                  slot_seq_offset(nch));
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, n_seq_narrow, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
                 PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_seq + n_seq_narrow, ch0, n_in_place, h->d_state, h->d_ring,
                                              h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
+                PSK_HIP(psk::launch_seq_cs8(h->d_plans[slot], d_seq + n_seq_narrow + n_in_place, ch0, n_in_place8, h->d_state, h->d_ring,
+                                            h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
                 if (n_wide_seq)
                     PSK_HIP(mark("seq_wide (reference order, samplesPerBaud > 1024)", (int)wide_seq_S, 0, ~0u, 0, 0, 0, 0));
                 PSK_HIP(psk::launch_seq_wide(h->d_plans[slot], d_seq + (nch - n_wide_seq), ch0, n_wide_seq, h->d_state, h->d_ring,
@@ -1982,7 +2046,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
             return fail(PSK_SOFT_ERR_CAPACITY, "psk_soft_process_host: output buffer too small");
         // every channel's rows start on a cache line: rows that straddle lines cost 6-8 % of the
         // kernel's streaming rate (tools/micro/placement_probe.hip)
-        need[i].in = pkts[i].present ? align_up(elem_bytes(pkts[i]) * (pkts[i].n_floats & ~1ull), 128) : 0;  // (CS16 staged as CS16)
+        need[i].in = pkts[i].present ? align_up(elem_bytes(pkts[i]) * (pkts[i].n_floats & ~1ull), 128) : 0;  // (CS16 / CS8 staged as such)
         need[i].soft = align_up(sizeof(float) * 2 * o.n_symbols, 128);
         need[i].phase = align_up(sizeof(float) * o.n_symbols, 128);
         need[i].bits = align_up(sizeof(int16_t) * o.n_bits, 128);

@@ -229,7 +229,7 @@ PSK_DEV void load_symbol_any(const XView &X, uint64_t tau, bool wanted, float2 (
 #pragma unroll
     for (int k = 0; k < S; k++) {
         const uint64_t j = j0 + (uint64_t)k;
-#if PSK_INST_CS16
+#if PSK_INST_FMT != 0
         const f2g v = x_load<S>(X, j);
 #else
         const f2g *p = j < X.L0 ? X.ring + j : X.in + (j - X.L0);  // (a select of two addresses)
@@ -249,7 +249,30 @@ PSK_DEV void load_block(const XView &X, long long cblk, uint32_t A, long long ta
         // steady: one wave-uniform base address plus a per-lane offset that does not change from block to block; a lane's
         // two symbols are contiguous and 16*S bytes long: S 16-byte loads (at 8-byte alignment, which gfx950 global
         // loads allow), whatever the parity of S
-#if PSK_INST_CS16
+#if PSK_INST_FMT == 3
+        // (complex int8: the lane's two symbols are 4*S bytes, but the wave's base offset, (tau_first*S - L0) samples of 2 bytes,
+        // has an arbitrary parity, so they are only 2-byte aligned.  S + 1 dword loads from the 4-byte boundary at or below the
+        // lane's first byte -- the shift is wave-uniform -- and v_alignbyte_b32 of neighbouring dwords put every pair of samples
+        // in place.  With no shift the last load repeats the one before it: nothing past the lane's 4*S bytes is read; with a
+        // shift it ends two bytes past them, inside the dword that holds the lane's last sample.)
+        const char *const wb =
+            reinterpret_cast<const char *>(X.in) + 2ull * ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0);  // (wave-uniform)
+        const uint32_t sh = (uint32_t)(uintptr_t)wb & 3u;                                                           // 0 or 2
+        const typename MemPtr<packet_global(S), const uint32_t>::type q =
+            (typename MemPtr<packet_global(S), const uint32_t>::type)(wb - sh) + (uint32_t)lane * (uint32_t)S;
+        uint32_t w[S + 1];
+#pragma unroll
+        for (int k = 0; k < S; k++) w[k] = q[k];
+        w[S] = q[sh ? S : S - 1];
+#pragma unroll
+        for (int k = 0; k < S; k++) {
+            const uint32_t t = __builtin_amdgcn_alignbyte(w[k + 1], w[k], sh);
+            const f2g a = cs8_f2<0>(t), b = cs8_f2<2>(t);
+            x[(2 * k) / S][(2 * k) % S] = make_float2(a.x, a.y);
+            x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
+        }
+        return;
+#elif PSK_INST_FMT == 1
         // (complex int16: the lane's two symbols are 8*S bytes -- S 8-byte loads of two samples each, at the 4-byte alignment
         // the ABI asks of CS16 packets, converted as they arrive)
         typedef uint32_t u2g __attribute__((ext_vector_type(2), aligned(4)));
@@ -1519,7 +1542,7 @@ PSK_DEV void fast_main_loop(const ChanPlan &p, const XView &X, float *yring, uin
 #pragma unroll
             for (int r = 0; r < kR; r++) {
                 const uint64_t j = (uint64_t)(c * kB + 2 * lane + r) * S + (uint64_t)kpred[r];  // (exists: A > kB)
-#if PSK_INST_CS16
+#if PSK_INST_FMT != 0
                 const f2g g = x_load<S>(X, j);
 #else
                 const f2g *q = j < X.L0 ? X.ring + j : X.in + (j - X.L0);
@@ -1783,7 +1806,7 @@ PSK_DEV void fast_main_loop(const ChanPlan &p, const XView &X, float *yring, uin
             const bool miss = valid[r] && (pkk[r] != bestK[r]);
             if (vote_any(miss)) {  // (wave-uniform, like every branch around loads here: see load_block)
                 const uint64_t j = miss ? (uint64_t)(i0 + r) * S + (uint64_t)bestK[r] : 0ull;  // (sample 0 exists)
-#if PSK_INST_CS16
+#if PSK_INST_FMT != 0
                 const f2g g = x_load<S>(X, j);
 #else
                 const f2g *q = j < X.L0 ? X.ring + j : X.in + (j - X.L0);

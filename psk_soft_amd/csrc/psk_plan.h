@@ -52,15 +52,19 @@ enum LfFlags : uint32_t {
     // (host-side) ... and read in place by the CS16 builds of the wave-scan and reference-order kernels: `in` stays the caller's int16
     // pairs, no pre-pass (psk_capi.cpp: the window classes with such instantiations)
     PLAN_CS16_IN_PLACE = 512u,
+    // the packet is complex int8 (PSK_SOFT_FORMAT_CS8): the same two flags for it (psk_cs8.hip, the PSK_INST_CS8 builds)
+    PLAN_CS8 = 1024u,
+    PLAN_CS8_IN_PLACE = 2048u,
 };
 
 
 constexpr uint32_t kResyncCount = 1048576u;  // cpp/psk_soft.cpp:51, 582
 
-// One CS16 packet for the conversion pre-pass (psk_cs16.hip): n complex int16 samples at src become n float2 at dst.  They sit
-// behind the compact channel lists in the upload slot of the call, so that they travel with the plans in one copy.
+// One CS16 or CS8 packet for the conversion pre-pass (psk_cs16.hip, psk_cs8.hip): n complex samples at src become n float2 at dst.
+// They sit behind the compact channel lists in the upload slot of the call, so that they travel with the plans in one copy.
 struct CvtDesc {
-    const uint32_t *src;  // I in the low half, Q in the high half (little-endian int16 pairs); 4-byte aligned
+    const uint32_t *src;  // I in the low half, Q in the high half (little-endian int16 pairs); 4-byte aligned -- for a CS8 packet
+                          // the int8 pairs, 2-byte aligned (psk_cs8.hip reads them as uint16)
     float *dst;           // interleaved I,Q floats; 128-byte aligned, in the handle's conversion scratch
     uint64_t n;
 };

@@ -233,13 +233,21 @@ PSK_DEV void store_s2u(int16_t *p, s2u v) { *reinterpret_cast<s2u *>(p) = v; }
 PSK_DEV void store_s2u(PSK_GLOBAL int16_t *p, s2u v) { PSK_ST((PSK_GLOBAL s2u *)p, v); }
 PSK_DEV void store_s4u(int16_t *p, s4u v) { *reinterpret_cast<s4u *>(p) = v; }
 PSK_DEV void store_s4u(PSK_GLOBAL int16_t *p, s4u v) { PSK_ST((PSK_GLOBAL s4u *)p, v); }
-// The packet's sample type is a property of the translation unit: PSK_INST_CS16=1 builds (psk_fast_inst.hip, psk_kernels.hip
-// compiled a second time, Makefile) read complex int16 packets (PSK_SOFT_FORMAT_CS16) straight from the caller's buffer, one 32-bit
-// word per sample, I in the low half; every other build reads float2.  The carried samples (the ring) are float2 in both.
+// The packet's sample type is a property of the translation unit (PSK_INST_FMT, a PSK_SOFT_FORMAT_* value): PSK_INST_CS16=1
+// builds (psk_fast_inst.hip, psk_kernels.hip compiled a second time, Makefile) read complex int16 packets (PSK_SOFT_FORMAT_CS16)
+// straight from the caller's buffer, one 32-bit word per sample, I in the low half; PSK_INST_CS8=1 builds read complex int8
+// packets (PSK_SOFT_FORMAT_CS8), one 16-bit word per sample, I in the low byte; every other build reads float2.  The carried
+// samples (the ring) are float2 in all of them.
 #ifndef PSK_INST_CS16
 #define PSK_INST_CS16 0
 #endif
-#if PSK_INST_CS16
+#ifndef PSK_INST_CS8
+#define PSK_INST_CS8 0
+#endif
+#define PSK_INST_FMT (PSK_INST_CS8 ? 3 : PSK_INST_CS16 ? 1 : 0)
+#if PSK_INST_FMT == 3
+typedef uint16_t pkt_t;
+#elif PSK_INST_FMT == 1
 typedef uint32_t pkt_t;
 #else
 typedef f2g pkt_t;
@@ -252,6 +260,16 @@ PSK_DEV f2g cs16_f2(uint32_t v)
     r.y = (float)((int32_t)v >> 16);
     return r;
 }
+// int8 pairs -> float2: the sample in byte lanes b, b+1 of v, sign-extended (v_bfe_i32 / v_ashrrev_i32), then v_cvt_f32_i32 --
+// exact for every int8
+template <int B>
+PSK_DEV f2g cs8_f2(uint32_t v)
+{
+    f2g r;
+    r.x = (float)(int32_t)(int8_t)(uint8_t)(v >> (8 * B));
+    r.y = (float)(int32_t)(int8_t)(uint8_t)(v >> (8 * B + 8));
+    return r;
+}
 struct XView {
     const f2g *ring;
     const pkt_t *in;
@@ -259,11 +277,15 @@ struct XView {
 };
 PSK_DEV float2 x_at(const XView &X, uint64_t j)
 {
-#if PSK_INST_CS16
+#if PSK_INST_FMT != 0
     // (both loads, then a select: no lane takes a branch of its own; the index the other buffer gets exists)
     const bool r = j < X.L0;
     const f2g a = X.ring[r ? j : 0];
+#if PSK_INST_FMT == 3
+    const f2g b = cs8_f2<0>(X.in[r ? 0 : j - X.L0]);  // (a 2-byte load: CS8 packets are 2-byte aligned)
+#else
     const f2g b = cs16_f2(X.in[r ? 0 : j - X.L0]);
+#endif
     const f2g v = r ? a : b;
 #else
     const f2g v = j < X.L0 ? X.ring[j] : X.in[j - X.L0];
@@ -274,18 +296,22 @@ PSK_DEV float2 x_at(const XView &X, uint64_t j)
 template <int S>
 PSK_DEV f2g x_load(const XView &X, uint64_t j)
 {
-#if PSK_INST_CS16
+#if PSK_INST_FMT != 0
     const bool r = j < X.L0;
     const f2g a = *mem_ptr<packet_global(S)>(X.ring + (r ? j : 0));
-    const uint32_t b = *mem_ptr<packet_global(S)>(X.in + (r ? 0 : j - X.L0));
+    const pkt_t b = *mem_ptr<packet_global(S)>(X.in + (r ? 0 : j - X.L0));
+#if PSK_INST_FMT == 3
+    return r ? a : cs8_f2<0>(b);
+#else
     return r ? a : cs16_f2(b);
+#endif
 #else
     const f2g *p = j < X.L0 ? X.ring + j : X.in + (j - X.L0);  // (a select of two addresses)
     return *mem_ptr<packet_global(S)>(p);
 #endif
 }
 
-#if !PSK_INST_CS16
+#if PSK_INST_FMT == 0
 template <int S>
 PSK_DEV void load_symbol(const XView &X, uint64_t tau, bool valid, float2 (&x)[S])
 {

@@ -20,7 +20,7 @@ struct Time {
     double twsec, tfsec;
 };
 
-// dataFloat_in (T = float) or dataShort_in (T = short: complex int16 packets)
+// dataFloat_in (T = float), dataShort_in (T = short: complex int16 packets) or dataChar_in (T = char: complex int8 packets)
 template <class Sample>
 struct InPort {
     struct dataTransfer {
@@ -74,15 +74,20 @@ struct OutPort {
 
 typedef psk_soft_gpu::component<InPort<float>, OutPort<float>, OutPort<short> > Component;
 typedef psk_soft_gpu::component<InPort<short>, OutPort<float>, OutPort<short> > ShortComponent;
+// (plain char, as some BULKIO releases type dataChar buffers: psk_soft_gpu.h reads it as int8_t)
+typedef psk_soft_gpu::component<InPort<char>, OutPort<float>, OutPort<short> > CharComponent;
 
-// one of the two components: float input (psk_harness_create) or short input (psk_harness_create_i16)
+// one of the three components: float input (psk_harness_create), short input (psk_harness_create_i16) or char input
+// (psk_harness_create_i8)
 struct Harness {
     InPort<float> in;
     InPort<short> in_s;
+    InPort<char> in_c;
     OutPort<float> soft, phase;
     OutPort<short> bits, sidx;
     Component *comp;
     ShortComponent *comp_s;
+    CharComponent *comp_c;
     std::string error;
     template <class C>
     void wire(C &c)
@@ -92,12 +97,17 @@ struct Harness {
         c.phase_dataFloat_out = &phase;
         c.sampleIndex_dataShort_out = &sidx;
     }
-    Harness(int device, bool short_input) : comp(0), comp_s(0)
+    // input: 0 float, 1 short, 2 char
+    Harness(int device, int input) : comp(0), comp_s(0), comp_c(0)
     {
-        if (short_input) {
+        if (input == 1) {
             comp_s = new ShortComponent(device);
             comp_s->dataFloat_in = &in_s;
             wire(*comp_s);
+        } else if (input == 2) {
+            comp_c = new CharComponent(device);
+            comp_c->dataFloat_in = &in_c;
+            wire(*comp_c);
         } else {
             comp = new Component(device);
             comp->dataFloat_in = &in;
@@ -108,6 +118,7 @@ struct Harness {
     {
         delete comp;
         delete comp_s;
+        delete comp_c;
     }
 };
 
@@ -146,10 +157,10 @@ void push_packet(InPort<T> &in, const T *data, size_t n, double xdelta, int mode
 
 extern "C" {
 
-static void *create(int device, bool short_input, char *err, int errlen)
+static void *create(int device, int input, char *err, int errlen)
 {
     try {
-        return new Harness(device, short_input);
+        return new Harness(device, input);
     } catch (const std::exception &e) {
         if (err && errlen > 0) {
             std::string m = e.what();
@@ -160,9 +171,11 @@ static void *create(int device, bool short_input, char *err, int errlen)
         return 0;
     }
 }
-void *psk_harness_create(int device, char *err, int errlen) { return create(device, false, err, errlen); }
+void *psk_harness_create(int device, char *err, int errlen) { return create(device, 0, err, errlen); }
 // a component whose input is a short port (complex int16 packets, PSK_SOFT_FORMAT_CS16)
-void *psk_harness_create_i16(int device, char *err, int errlen) { return create(device, true, err, errlen); }
+void *psk_harness_create_i16(int device, char *err, int errlen) { return create(device, 1, err, errlen); }
+// a component whose input is a char port (complex int8 packets, PSK_SOFT_FORMAT_CS8)
+void *psk_harness_create_i8(int device, char *err, int errlen) { return create(device, 2, err, errlen); }
 void psk_harness_destroy(void *h) { delete (Harness *)h; }
 
 // configure() of one property: stores it and, like REDHAWK's PropertySet, runs the registered
@@ -176,8 +189,10 @@ int psk_harness_configure(void *hv, int id, unsigned value)
     try {
         if (h->comp)
             configure_prop(*h->comp, id, value);
-        else
+        else if (h->comp_s)
             configure_prop(*h->comp_s, id, value);
+        else
+            configure_prop(*h->comp_c, id, value);
     } catch (const std::exception &e) {
         h->error = e.what();
         return -2;
@@ -196,12 +211,19 @@ void psk_harness_push_i16(void *hv, const short *data, size_t n_shorts, double x
 {
     push_packet(((Harness *)hv)->in_s, data, n_shorts, xdelta, mode, sriChanged, flushed, eos, streamID, twsec);
 }
+// (char-input component) n_chars int8 elements, interleaved I,Q
+void psk_harness_push_i8(void *hv, const signed char *data, size_t n_chars, double xdelta, int mode, int sriChanged,
+                         int flushed, int eos, const char *streamID, double twsec)
+{
+    push_packet(((Harness *)hv)->in_c, reinterpret_cast<const char *>(data), n_chars, xdelta, mode, sriChanged, flushed, eos, streamID,
+                twsec);
+}
 
 int psk_harness_service(void *hv)
 {
     Harness *h = (Harness *)hv;
     try {
-        return h->comp ? h->comp->serviceFunction() : h->comp_s->serviceFunction();
+        return h->comp ? h->comp->serviceFunction() : h->comp_s ? h->comp_s->serviceFunction() : h->comp_c->serviceFunction();
     } catch (const std::exception &e) {
         h->error = e.what();
         return -1;
@@ -211,7 +233,7 @@ const char *psk_harness_error(void *hv) { return ((Harness *)hv)->error.c_str();
 int psk_harness_warnings(void *hv)
 {
     Harness *h = (Harness *)hv;
-    return h->comp ? h->comp->warnings : h->comp_s->warnings;
+    return h->comp ? h->comp->warnings : h->comp_s ? h->comp_s->warnings : h->comp_c->warnings;
 }
 
 // port: 0 soft 1 bits 2 phase 3 sampleIndex
@@ -278,7 +300,7 @@ const char *psk_harness_last_stream(void *hv) { return ((Harness *)hv)->soft.las
 void *psk_harness_handle(void *hv)
 {
     Harness *h = (Harness *)hv;
-    return h->comp ? h->comp->handle() : h->comp_s->handle();
+    return h->comp ? h->comp->handle() : h->comp_s ? h->comp_s->handle() : h->comp_c->handle();
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@
 // deliver it): the packet format follows the element type of its dataBuffer at compile time (float: PSK_SOFT_FORMAT_CF32,
 // short: PSK_SOFT_FORMAT_CS16), and the library converts on the GPU -- no short-to-float component in front of it, half the
 // bytes through the host-buffer path.  Outputs are the same either way: an sc16 packet gives what its float cast gives.
+// A char port (bulkio::InCharPort, dataChar: complex int8, sc8) gives PSK_SOFT_FORMAT_CS8 the same way, a quarter of the float
+// bytes; its elements are read as int8_t whether the release types the buffer as signed char or as plain char.
 // Port surface used (exactly what the reference uses): InPort::dataTransfer with dataBuffer,
 // SRI.{xdelta,mode}, sriChanged, inputQueueFlushed, T, EOS, streamID; getPacket(timeout);
 // OutPort::pushSRI(SRI) and pushPacket(vector&, T, EOS, streamID).
@@ -29,12 +31,15 @@ namespace psk_soft_gpu {
 enum { NOOP = PSK_SOFT_NOOP, NORMAL = PSK_SOFT_NORMAL };
 const float BLOCKING = -1.0f;  // bulkio::Const::BLOCKING
 
-// packet format of an input port's sample type: float or short, nothing else compiles
+// packet format of an input port's sample type: float, short, signed char or char, nothing else compiles
 template <class T> struct sample_format;
 template <> struct sample_format<float> { enum { value = PSK_SOFT_FORMAT_CF32 }; };
 template <> struct sample_format<short> { enum { value = PSK_SOFT_FORMAT_CS16 }; };
+template <> struct sample_format<signed char> { enum { value = PSK_SOFT_FORMAT_CS8 }; };
+// (plain char: the library reads the bytes as int8_t, whatever the signedness of char on the host)
+template <> struct sample_format<char> { enum { value = PSK_SOFT_FORMAT_CS8 }; };
 
-// InPort: bulkio::InFloatPort or bulkio::InShortPort (or anything with their dataTransfer)
+// InPort: bulkio::InFloatPort, bulkio::InShortPort or bulkio::InCharPort (or anything with their dataTransfer)
 template <class InPort, class OutFloatPort, class OutShortPort>
 class component {
   public:

@@ -15,8 +15,9 @@ LIB_PATH = os.path.join(_HERE, "libpsk_soft_hip.so")
 DEVICE_NONE = -1
 OK = 0
 NOOP, NORMAL = 0, 1
-# Packet.format: interleaved float32 I/Q, or interleaved int16 I/Q (sc16; n_floats then counts int16 elements)
-FORMAT_CF32, FORMAT_CS16 = 0, 1
+# Packet.format: interleaved float32 I/Q, interleaved int16 I/Q (sc16) or interleaved int8 I/Q (sc8); n_floats counts the
+# elements of the format
+FORMAT_CF32, FORMAT_CS16, FORMAT_CS8 = 0, 1, 3
 
 STATUS_NAMES = {
     0: "PSK_SOFT_OK",
@@ -59,7 +60,7 @@ class Packet(ctypes.Structure):
         ("sriChanged", ctypes.c_uint8),
         ("inputQueueFlushed", ctypes.c_uint8),
         ("present", ctypes.c_uint8),
-        ("format", ctypes.c_uint8),  # FORMAT_CF32 / FORMAT_CS16
+        ("format", ctypes.c_uint8),  # FORMAT_CF32 / FORMAT_CS16 / FORMAT_CS8
     ]
 
 
@@ -289,7 +290,8 @@ class Handle:
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with
-        data (interleaved I/Q: an int16 array is handed over as it is, FORMAT_CS16, anything else as float32), xdelta,
+        data (interleaved I/Q: an int16 array is handed over as it is, FORMAT_CS16, an int8 array too, FORMAT_CS8, anything
+        else as float32), xdelta,
         and optional mode / sriChanged / inputQueueFlushed.  Returns one dict per channel with the four output streams."""
         n = len(packets)
         pk = (Packet * n)()
@@ -301,12 +303,13 @@ class Handle:
                 pk[i].present = 0
                 bufs.append(None)
                 continue
-            cs16 = isinstance(p["data"], np.ndarray) and p["data"].dtype == np.int16
-            data = np.ascontiguousarray(p["data"], dtype=np.int16 if cs16 else np.float32)
+            dt = p["data"].dtype if isinstance(p["data"], np.ndarray) else None
+            fmt = FORMAT_CS16 if dt == np.int16 else FORMAT_CS8 if dt == np.int8 else FORMAT_CF32
+            data = np.ascontiguousarray(p["data"], dtype={FORMAT_CS16: np.int16, FORMAT_CS8: np.int8}.get(fmt, np.float32))
             keep.append(data)
             pk[i].data = data.ctypes.data
             pk[i].n_floats = data.size
-            pk[i].format = FORMAT_CS16 if cs16 else FORMAT_CF32
+            pk[i].format = fmt
             pk[i].sri_xdelta = float(p["xdelta"])
             pk[i].sri_mode = int(p.get("mode", 1))
             pk[i].sriChanged = int(bool(p.get("sriChanged", False)))

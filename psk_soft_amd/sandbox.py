@@ -28,12 +28,16 @@ def _load():
         L.psk_harness_create.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.psk_harness_create_i16.restype = vp
         L.psk_harness_create_i16.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+        L.psk_harness_create_i8.restype = vp
+        L.psk_harness_create_i8.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.psk_harness_destroy.argtypes = [vp]
         L.psk_harness_configure.argtypes = [vp, ctypes.c_int, ctypes.c_uint]
         L.psk_harness_push.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t, ctypes.c_double, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_double]
         L.psk_harness_push_i16.argtypes = [vp, ctypes.POINTER(ctypes.c_short), ctypes.c_size_t, ctypes.c_double, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_double]
+        L.psk_harness_push_i8.argtypes = [vp, ctypes.POINTER(ctypes.c_byte), ctypes.c_size_t, ctypes.c_double, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_double]
         L.psk_harness_service.argtypes = [vp]
         L.psk_harness_error.argtypes = [vp]
         L.psk_harness_error.restype = ctypes.c_char_p
@@ -57,18 +61,21 @@ def _load():
 class Component:
     """comp.samplesPerBaud = 8 ... ; comp.push(...); comp.service(); comp.getData(port).
 
-    input="float": the reference's dataFloat_in; input="short": a dataShort_in port of complex int16 packets."""
+    input="float": the reference's dataFloat_in; input="short": a dataShort_in port of complex int16 packets; input="char": a
+    dataChar_in port of complex int8 packets."""
 
     def __init__(self, device=0, input="float"):
         L = _load()
-        if input not in ("float", "short"):
-            raise ValueError("input must be 'float' or 'short'")
+        if input not in ("float", "short", "char"):
+            raise ValueError("input must be 'float', 'short' or 'char'")
         err = ctypes.create_string_buffer(512)
-        h = (L.psk_harness_create_i16 if input == "short" else L.psk_harness_create)(int(device), err, 512)
+        create = {"float": L.psk_harness_create, "short": L.psk_harness_create_i16, "char": L.psk_harness_create_i8}[input]
+        h = create(int(device), err, 512)
         if not h:
             raise RuntimeError(err.value.decode())
         object.__setattr__(self, "_h", ctypes.c_void_p(h))
         object.__setattr__(self, "_short", input == "short")
+        object.__setattr__(self, "_char", input == "char")
         object.__setattr__(self, "_vals", dict(samplesPerBaud=10, numAvg=100, constelationSize=4, phaseAvg=50,
                                                differentialDecoding=0, resetState=0))
 
@@ -100,11 +107,16 @@ class Component:
     def push(self, data, sampleRate=None, xdelta=None, complexData=True, sriChanged=False, inputQueueFlushed=False,
              EOS=False, streamID="stream", twsec=0.0):
         """Queue one packet on the input port (sb.DataSource.push: sampleRate -> SRI.xdelta = 1/sampleRate); a short-input
-        component takes int16 data (anything else is refused rather than rounded)."""
+        component takes int16 data and a char-input component int8 data (anything else is refused rather than rounded)."""
         xd = (1.0 / sampleRate) if xdelta is None else xdelta
         args = (float(xd), 1 if complexData else 0, int(bool(sriChanged)), int(bool(inputQueueFlushed)), int(bool(EOS)),
                 streamID.encode(), float(twsec))
-        if self._short:
+        if self._char:
+            if np.asarray(data).dtype != np.int8:
+                raise TypeError("a char-input component takes int8 packets")
+            data = np.ascontiguousarray(data, dtype=np.int8)
+            _load().psk_harness_push_i8(self._h, data.ctypes.data_as(ctypes.POINTER(ctypes.c_byte)), data.size, *args)
+        elif self._short:
             if np.asarray(data).dtype != np.int16:
                 raise TypeError("a short-input component takes int16 packets")
             data = np.ascontiguousarray(data, dtype=np.int16)

@@ -2,7 +2,8 @@
 # Is the float path's machine code unchanged?  Compiles every wave-scan instantiation of tools/lint_all.sh's list and the
 # other translation units (psk_tile.hip, psk_kernels.hip, psk_tile_inst.hip S 2 .. 16) to gfx950 assembly twice -- from the
 # working tree and from git ref REF -- and compares the instruction streams with comments, directives, metadata and labels
-# stripped.  CPU only (hipcc -S), 8 compiles at a time.
+# stripped.  The complex int16 units are compared too (PSK_INST_CS16=1: the wave-scan kernel for samplesPerBaud 2 .. 16, both
+# tiers, the reference-order kernel, the conversion pre-pass psk_cs16.hip): 31 more.  CPU only (hipcc -S), 8 compiles at a time.
 # usage: tools/f32_isa_same.sh [REF] [out.txt]     (REF defaults to main)
 ref=${1:-main}
 out=${2:-/tmp/f32_isa_same.txt}
@@ -46,6 +47,9 @@ for s in $(seq 2 16); do list="$list $s,0,0"; done
     echo "tile psk_tile.hip"
     echo "kernels psk_kernels.hip"
     for s in $(seq 2 16); do echo "tile_inst_S$s psk_tile_inst.hip -DPSK_INST_S=$s -DPSK_INST_H=1"; done
+    for s in $(seq 2 16); do for e in 0 1; do echo "cs16_fast_S${s}_H1_E$e psk_fast_inst.hip -DPSK_INST_CS16=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e"; done; done
+    echo "cs16_kernels psk_kernels.hip -DPSK_INST_CS16=1"
+    echo "cs16_convert psk_cs16.hip"
 } | sed "s/ *$//" | xargs -P 8 -L 1 bash -c 'one "$@"' _ | sort > $out
 echo "$(grep -c ': same' $out) same, $(grep -c 'DIFFERENT' $out) different, $(grep -c 'failed' $out) failed of $(grep -c . $out)"
 [ -n "${KEEP:-}" ] || rm -rf $tmp

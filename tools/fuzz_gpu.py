@@ -30,6 +30,10 @@ MORE = os.environ.get("PSK_FUZZ_MORE", "0") != "0"
 # draw, scaled so that its peak lands between 1 and 32767 LSB (ties of small integers included) and rounded; the NONFINITE and
 # EXTREME draws stay with the float channels.  Drawn from generators of their own: the other draws of a seed stay what they were.
 CS16 = float(os.environ.get("PSK_FUZZ_CS16", "0"))
+# PSK_FUZZ_CS8=p: with probability p a channel that is not CS16 is complex int8 (PSK_SOFT_FORMAT_CS8): half of those send every
+# packet as int8, the other half rotate CS8 / CS16 / CF32 packets of the same values call by call.  The signal is scaled so that
+# its peak lands between 1 and 127 LSB and rounded.  Drawn from a generator of its own, like the CS16 draw.
+CS8 = float(os.environ.get("PSK_FUZZ_CS8", "0"))
 TOL = 1e-5
 STRICT = os.environ.get("PSK_FUZZ_STRICT", "1") != "0"  # every float of soft / phase must equal the oracle's
 XD = 0.01
@@ -110,7 +114,9 @@ def main():
         nrng = np.random.default_rng(seed * 1000 + rnd)
         props, sigs, scripts = [], [], []
         crng = random.Random(seed * 1000 + rnd + 0x5C16)
-        cs16 = []  # per channel: None (float32), "all" (every packet int16) or "alt" (int16 and float32 packets call by call)
+        cs16 = []  # per channel: None (float32), "all" (every packet int16) or "alt" (int16 and float32 packets call by call),
+        # "cs8" (every packet int8) or "rot" (int8, int16 and float32 packets in turn)
+        crng8 = random.Random(seed * 1000 + rnd + 0x5C08)
         for c in range(C):
             S = rng.choice(S_CHOICES)
             A = rng.choice(A_CHOICES)
@@ -145,6 +151,11 @@ def main():
                 peak = float(np.abs(sig[np.isfinite(sig)]).max()) if np.isfinite(sig).any() else 0.0
                 scale = 10.0 ** crng.uniform(0.0, np.log10(32767.0)) / peak if peak > 0 else 1.0
                 sig = np.clip(np.rint(np.nan_to_num(sig.astype(np.float64) * scale)), -32768, 32767).astype(np.int16)
+            elif CS8 and crng8.random() < CS8:
+                fmt = crng8.choice(["cs8", "rot"])
+                peak = float(np.abs(sig[np.isfinite(sig)]).max()) if np.isfinite(sig).any() else 0.0
+                scale = 10.0 ** crng8.uniform(0.0, np.log10(127.0)) / peak if peak > 0 else 1.0
+                sig = np.clip(np.rint(np.nan_to_num(sig.astype(np.float64) * scale)), -128, 127).astype(np.int8)
             cs16.append(fmt)
             props.append(p)
             sigs.append(sig)
@@ -187,7 +198,10 @@ def main():
                     sri = True
                 if cs16[c] is not None:  # (the oracle, and the float32 packets of an alternating channel, get the exact cast)
                     f32 = data.astype(np.float32)
-                    send = data if (cs16[c] == "all" or pos[c] % 2 == 0) else f32
+                    if cs16[c] == "rot":
+                        send = (data, data.astype(np.int16), f32)[pos[c] % 3]
+                    else:
+                        send = data if (cs16[c] in ("all", "cs8") or pos[c] % 2 == 0) else f32
                     data = f32
                 else:
                     send = data
@@ -221,7 +235,7 @@ def main():
                         break
             if why:
                 bad += 1
-                print("MISMATCH round %d channel %d%s: %s  props=%s script=%s" % (rnd, c, " (CS16 %s)" % cs16[c] if cs16[c] else "", why,
+                print("MISMATCH round %d channel %d%s: %s  props=%s script=%s" % (rnd, c, " (int %s)" % cs16[c] if cs16[c] else "", why,
                                                                               props[c], scripts[c]))
                 if g["phase"].size == r["phase"].size and g["soft"].size == r["soft"].size and g["phase"].size:
                     # where, and what the phase estimate is there: one ulp of a large estimate is the known case
@@ -238,7 +252,7 @@ def main():
                         print("   soft differs at symbols %s ... (%d symbols); got %s ref %s" % (
                             sym[:16].tolist(), sym.size, g["soft"][2 * sym[0] : 2 * sym[0] + 2], r["soft"][2 * sym[0] : 2 * sym[0] + 2]))
         bad_total += bad
-        print("round %d: %d channels (%d CS16), %d mismatches, last-call stats %s" % (rnd, C, sum(f is not None for f in cs16), bad, st))
+        print("round %d: %d channels (%d CS16 / CS8), %d mismatches, last-call stats %s" % (rnd, C, sum(f is not None for f in cs16), bad, st))
     print("TOTAL mismatches:", bad_total)
     return 1 if bad_total else 0
 
