@@ -227,9 +227,71 @@ enum {
      * calls made so far after psk_soft_join(); psk_soft_synchronize() waits for them on the host.  Results are unchanged.
      * A call whose channels would not all stay on the stream they were on (a property or packet pattern that moves a channel
      * to another window class) joins everything first, by itself. */
-    PSK_SOFT_OPT_DEFERRED_JOIN = 5
+    PSK_SOFT_OPT_DEFERRED_JOIN = 5,
+    /* 1 = every psk_soft_process_* call ends with a reduction pass over the output rows it has just written: one
+     * psk_soft_quality_t per channel of the call, read back with psk_soft_get_quality (see there).  0 (default): nothing
+     * changes -- no launch, no record.  Setting the option to 1 zeroes all records.  Any other value is refused.
+     * Results of the four streams are unchanged.  The pass reads the call's WHOLE rows, so they must be complete on the
+     * caller's stream: with PSK_SOFT_OPT_DEFERRED_JOIN also on, the call joins its side streams before the pass, and the
+     * deferred join has no effect while this option is on (the call is still cut in time and by class as before; the
+     * pass comes behind the join of the last piece).  Outputs in psk_soft_host_alloc memory are read back over the link
+     * by the pass: correct, and the one case where the option costs a second crossing of the soft rows. */
+    PSK_SOFT_OPT_QUALITY = 6
 };
 psk_soft_status psk_soft_set_option(psk_soft_handle_t *h, int option, int value);
+
+/* ---- which channels hold a signal (PSK_SOFT_OPT_QUALITY) ----------------------------------------------------------
+ * The reference answers that question with its two debug ports: `phase` (cpp/psk_soft.cpp:482) and `sampleIndex`
+ * (:466) exist so that a person can watch carrier and timing in a plot.  For thousands of channels the record below
+ * stands in for the plot: sums over the soft symbols of ONE call, taken on the GPU while the rows are still in HBM,
+ * and the two ends of the call's phase and sampleIndex rows.  Sums, not means, and nothing accumulates across calls:
+ * a host that wants a longer average adds the sums and counts of consecutive records.
+ *
+ * Per soft symbol (re, im), in float32, every operation rounded once, no fused multiply-add, denormals kept:
+ *   e = re*re + im*im,  q = e*e.  The symbol is FINITE when re, im and q are finite (the first symbol of a
+ *   differentially decoded stream is inf / NaN -- a quotient by the zero before the stream -- and is left out).
+ *   (pr, pi) = (re, im), then log2(M) times (pr, pi) <- (pr*pr - pi*pi, pr*pi + pi*pr): z^M.
+ *   a = e for M = 2, q for 4, q*q for 8: |z|^M without a square root.  The symbol enters the lock sums when it is
+ *   finite, pr, pi and a are finite and a >= FLT_MIN; its term is the unit phasor c = (pr / a, pi / a) (unit phasors,
+ *   not amplitude-weighted ones: two or three huge quotients of a differential stream would carry a weighted sum).
+ * The sums are doubles, added in a fixed order: the same call on two fresh handles gives byte-identical records. */
+enum { PSK_SOFT_Q_SOFT = 1, PSK_SOFT_Q_PHASE = 2, PSK_SOFT_Q_INDEX = 4, PSK_SOFT_Q_LOCK = 8, PSK_SOFT_Q_PLANNED = 128 };
+
+typedef struct psk_soft_quality {           /* the LAST call that covered the channel with the option on */
+    uint64_t n_symbols;       /* symbols that call emitted for the channel                                   */
+    uint64_t n_finite;        /* of those: soft symbols that enter sum_e / sum_e2                            */
+    uint64_t n_lock;          /* of those: soft symbols that enter sum_lock_*                                */
+    uint64_t index_changes;   /* i >= 1 with sampleIndex[i] != sampleIndex[i-1] (timing picks that moved)    */
+    double sum_e, sum_e2;     /* sums of e_i and of q_i (above)                                              */
+    double sum_lock_re, sum_lock_im;   /* sum of the unit phasors c_i (above)                                */
+    float phase_first, phase_last;     /* phase[0], phase[n-1] of the call, copied                           */
+    int16_t index_first, index_last;   /* sampleIndex[0], sampleIndex[n-1], copied                           */
+    uint16_t constelationSize, samplesPerBaud;   /* the snapshot the call ran with                           */
+    uint8_t differentialDecoding, flags;         /* PSK_SOFT_Q_*: which parts of the record are filled in    */
+    uint8_t pad[6];                              /* zero; the struct is a multiple of 8 bytes                */
+} psk_soft_quality_t;
+/* flags of a data record: Q_SOFT when the call had a soft pointer and emitted symbols (else the four sums, n_finite and
+ * n_lock are zero), Q_PHASE likewise for phase_*, Q_INDEX for index_* / index_changes (a sampleIndex pointer and
+ * n_sampleIndex > 0: not at samplesPerBaud 1), Q_LOCK when Q_SOFT and constelationSize is 2, 4 or 8.  A covered channel
+ * that emits nothing (no packet, real data, a window still filling) gets an all-zero record, written in stream order
+ * by the pass; a channel a call does not cover keeps its record.  A control-plane-only handle fills in n_symbols, the
+ * three snapshot fields and flags = PSK_SOFT_Q_PLANNED, everything else zero. */
+
+/* lock:  |sum of the unit phasors| / n_lock -- 1 for a stream whose M-th power points one way, whatever way; of the order
+ *        of n^-1/2 .. 0.1 for noise.  NaN without Q_LOCK or with n_lock 0.
+ * snr_db: second- and fourth-moment estimator for a constant-modulus signal in complex Gaussian noise: m2 = sum_e / n_finite,
+ *        m4 = sum_e2 / n_finite, d = 2 m2^2 - m4, s = sqrt(d), 10 log10(s / (m2 - s)); NaN when d <= 0, m2 - s <= 0, n_finite is 0
+ *        or differentialDecoding (the soft symbols are quotients of two noisy samples there: heavy-tailed, the moments
+ *        mean nothing; lock stays valid).  An ESTIMATE on the one sample per symbol the timing pick chose, not a
+ *        calibrated measurement.
+ * mean_energy: sum_e / n_finite (NaN with n_finite 0).
+ * index_change_rate: index_changes / (n_symbols - 1); NaN without Q_INDEX or with fewer than two symbols. */
+typedef struct psk_soft_quality_derived { double lock, snr_db, mean_energy, index_change_rate; } psk_soft_quality_derived_t;
+
+uint64_t psk_soft_quality_bytes(void);      /* sizeof(psk_soft_quality_t), for bindings */
+/* waits like psk_soft_get_channel_stats does and copies the records of [ch0, ch0+nch) out */
+psk_soft_status psk_soft_get_quality(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_quality_t *q /* [nch] */);
+psk_soft_status psk_soft_quality_derive(const psk_soft_quality_t *q, psk_soft_quality_derived_t *d);  /* host only, pure */
 
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);

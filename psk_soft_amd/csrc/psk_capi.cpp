@@ -9,6 +9,7 @@
 #include <hip/hip_vector_types.h>
 
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +23,7 @@
 
 #include "psk_ctl.h"
 #include "psk_plan.h"
+#include "psk_quality.h"
 #include "psk_soft_hip.h"
 
 namespace psk {
@@ -106,6 +108,7 @@ psk_soft_status fail(psk_soft_status st, const std::string &msg)
 constexpr int kPlanSlots = 4;
 constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that mixes window classes (see psk_soft_process_device)
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
+constexpr int kQualitySlots = 4;  // calls whose quality pass (PSK_SOFT_OPT_QUALITY) may be in flight: descriptors and partials of each
 constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 packets, one per stream that uses them (see CvtScratch)
 // bytes of a packet's element
 inline size_t elem_bytes(const psk_soft_packet_t &k)
@@ -263,6 +266,19 @@ struct CvtScratch {
     uint64_t last_use = 0;
 };
 
+// PSK_SOFT_OPT_QUALITY: what the pass behind one call owns until its event -- the descriptors (pinned, and their copy in device
+// memory: one per channel of the handle) and the partials of the fold (grown on demand).  The chunks of psk_soft_process_host run
+// on streams of their own and overlap, hence several.
+struct QualitySlot {
+    psk::QualityDesc *h_desc = nullptr, *d_desc = nullptr;
+    psk::QualityPartial *d_part = nullptr;
+    size_t part_cap = 0;  // partials
+    hipEvent_t ev = nullptr;
+    bool used = false;
+    hipStream_t stream = nullptr;
+    uint32_t ch0 = 0, nch = 0;
+};
+
 // Largest phaseAvg of the wave-scan kernels: their LDS ring of unwrapped phases holds phaseAvg + 128 values in a power
 // of two; 32768 floats (128 KiB) leave room for the energy ring next to it.  Channels with phaseAvg > kDeepFit are
 // launched apart from the others of their window class ("deep" classes, index H + 8): a ring that size allows one wave
@@ -393,6 +409,18 @@ struct psk_soft_handle {
     // CS16 / CS8 packets: conversion scratch (CvtScratch)
     CvtScratch cvt[kCvtScratch];
     uint64_t cvt_calls = 0;
+    // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
+    // handle keeps them on the host
+    int opt_quality = 0;
+    psk_soft_quality_t *d_quality = nullptr;
+    std::vector<psk_soft_quality_t> quality_dry;
+    QualitySlot qslot[kQualitySlots];
+    int q_turn = 0;
+    struct QualitySnap {
+        uint16_t M, S;
+        uint8_t diff;
+    };
+    std::vector<QualitySnap> q_snap;  // scratch of one call: the properties it ran with
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -460,6 +488,14 @@ hipError_t deferred_join(psk_soft_handle *h, hipStream_t stream)
     h->deferred_pending = false;
     return hipSuccess;
 }
+// the control state of one channel, wherever it lives at the moment (nothing is brought up to date)
+const psk::ChanCtl &ctl_of(const psk_soft_handle *h, uint32_t c)
+{
+    for (const auto &r : h->uni)
+        if (r.lazy && r.lo <= c && c < r.hi)
+            return r.ctl;
+    return h->ctl[c];
+}
 bool ctl_equal(const psk::ChanCtl &a, const psk::ChanCtl &b)
 {
     return a.props.samplesPerBaud == b.props.samplesPerBaud && a.props.constelationSize == b.props.constelationSize &&
@@ -506,6 +542,8 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
     h->last_mode.assign(n_channels, psk::PLAN_SKIP);
     h->device = device;
     h->dry = (device == PSK_SOFT_DEVICE_NONE);
+    if (h->dry)
+        h->quality_dry.assign(n_channels, psk_soft_quality_t{});
     if (const char *e = std::getenv("PSK_SOFT_TIME_TILED"))
         h->opt_tiled = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
     if (const char *e = std::getenv("PSK_SOFT_TIES_IN_PLACE"))
@@ -566,6 +604,9 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
             return bail("hipMemcpy state", e2);
         if ((e2 = hipMemset(h->d_ring, 0, ring_b)) != hipSuccess) return bail("hipMemset", e2);
         if ((e2 = hipMemset(h->d_yv, 0, yv_b)) != hipSuccess) return bail("hipMemset", e2);
+        if ((e2 = hipMalloc((void **)&h->d_quality, sizeof(psk_soft_quality_t) * (size_t)n_channels)) != hipSuccess)
+            return bail("hipMalloc quality", e2);
+        if ((e2 = hipMemset(h->d_quality, 0, sizeof(psk_soft_quality_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
         for (int s = 0; s < kPlanSlots; s++) {
             // (a slot = the plans of a call followed by the compact channel lists of its launches: one upload)
             // (... behind the header the kernels find in front of the plans: psk_plan.h)
@@ -608,6 +649,13 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_state) (void)hipFree(h->d_state);
         if (h->d_ring) (void)hipFree(h->d_ring);
         if (h->d_yv) (void)hipFree(h->d_yv);
+        for (auto &q : h->qslot) {
+            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
+            if (q.h_desc) (void)hipHostFree(q.h_desc);
+            if (q.d_desc) (void)hipFree(q.d_desc);
+            if (q.d_part) (void)hipFree(q.d_part);
+        }
+        if (h->d_quality) (void)hipFree(h->d_quality);
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
         if (h->d_test) (void)hipFree(h->d_test);
@@ -1807,16 +1855,14 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     return PSK_SOFT_OK;
 }
 
-// The public entry.  A call that would emit more than 2^20 symbols in one channel, or run LinearFit::count past 2^20 in the
+// The call behind the public entry (psk_soft_process_device, below).  A call that would emit more than 2^20 symbols in one channel, or run LinearFit::count past 2^20 in the
 // middle (the reference then rebuilds the fit's sums at that symbol, cpp/psk_soft.cpp:51-52, and its energy sums after it,
 // :582-583), is cut at those boundaries inside the library: the pieces are planned as continuations of ONE serviceFunction() call
 // (no prologue between them) and run on the wave-scan / time-tiled kernels like any other call -- round 2 handed such calls to the
 // reference-order kernel, 4.7 us per symbol on one lane.  Everything else goes straight through.
-psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
-                                        const psk_soft_packet_t *pkts, psk_soft_output_t *outs, void *stream_v)
+static psk_soft_status process_device_call(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                           psk_soft_output_t *outs, void *stream_v)
 {
-    if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
-        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
     // (the ordinary call is planned as it is; the plan pass itself says when a channel's call is too long for one piece --
     // nothing is committed or enqueued then)
     g_long_call = false;
@@ -1949,6 +1995,122 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
         PSK_HIP(deferred_join(h, stream_v ? (hipStream_t)stream_v : h->stream));
     }
     return PSK_SOFT_OK;
+}
+
+// PSK_SOFT_OPT_QUALITY: the reduction pass behind a call (psk_quality.hip) -- fold + join on the caller's stream over the call's
+// WHOLE rows (the pointers and total counts of outs[]: the pass does not care how the call was scheduled), one record per channel
+// of the call.  The descriptors go up from pinned memory of a slot of their own, reused behind its event.
+static psk_soft_status quality_pass(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_output_t *outs, void *stream_v)
+{
+    const psk_soft_handle::QualitySnap *snap = h->q_snap.data();
+    if (h->dry) {
+        for (uint32_t i = 0; i < nch; i++) {
+            psk_soft_quality_t r = {};
+            r.n_symbols = outs[i].n_symbols;
+            r.constelationSize = snap[i].M, r.samplesPerBaud = snap[i].S, r.differentialDecoding = snap[i].diff;
+            r.flags = PSK_SOFT_Q_PLANNED;
+            h->quality_dry[ch0 + i] = r;
+        }
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: the rows must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    QualitySlot &q = h->qslot[h->q_turn];
+    if (q.used)
+        PSK_HIP(hipEventSynchronize(q.ev));
+    if (!q.ev)
+        PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+    if (!q.h_desc)
+        PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(psk::QualityDesc) * (size_t)h->nch));
+    if (!q.d_desc)
+        PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(psk::QualityDesc) * (size_t)h->nch));
+    uint64_t n_seg = 0;
+    uint32_t max_seg = 0;
+    for (uint32_t i = 0; i < nch; i++) {
+        const psk_soft_output_t &o = outs[i];
+        psk::QualityDesc &d = q.h_desc[i];
+        d = psk::QualityDesc{};
+        d.channel = ch0 + i;
+        d.M = snap[i].M, d.S = snap[i].S, d.diff = snap[i].diff;
+        if (!o.n_symbols)
+            continue;  // (its zero record)
+        d.n_symbols = o.n_symbols;
+        d.n_sidx = o.n_sampleIndex;
+        uint32_t f = 0;
+        if (o.soft)
+            f |= PSK_SOFT_Q_SOFT | (d.M == 2 || d.M == 4 || d.M == 8 ? PSK_SOFT_Q_LOCK : 0);
+        if (o.phase)
+            f |= PSK_SOFT_Q_PHASE;
+        if (o.sampleIndex && o.n_sampleIndex)
+            f |= PSK_SOFT_Q_INDEX;
+        d.flags = (uint8_t)f;
+        d.soft = (f & PSK_SOFT_Q_SOFT) ? o.soft : nullptr;
+        d.phase = (f & PSK_SOFT_Q_PHASE) ? o.phase : nullptr;
+        d.sidx = (f & PSK_SOFT_Q_INDEX) ? o.sampleIndex : nullptr;
+        if (f & (PSK_SOFT_Q_SOFT | PSK_SOFT_Q_INDEX)) {
+            const uint64_t segs = (o.n_symbols + psk::kQualitySegSymbols - 1u) / psk::kQualitySegSymbols;
+            if (n_seg + segs > 0x7fffffffull)
+                return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_process: too many symbols in one call for the quality pass");
+            d.seg0 = (uint32_t)n_seg;
+            d.n_seg = (uint32_t)segs;
+            n_seg += segs;
+            max_seg = d.n_seg > max_seg ? d.n_seg : max_seg;
+        }
+    }
+    if (n_seg > q.part_cap) {
+        if (q.d_part) (void)hipFree(q.d_part);
+        q.d_part = nullptr;
+        q.part_cap = 0;
+        const size_t cap = (size_t)n_seg + (size_t)n_seg / 4u + 256u;
+        PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(psk::QualityPartial) * cap));
+        q.part_cap = cap;
+    }
+    // (the record of a channel is written by one call at a time: behind the passes of other streams over the same channels)
+    for (const QualitySlot &k : h->qslot)
+        if (&k != &q && k.used && k.stream != stream && k.ch0 < ch0 + nch && ch0 < k.ch0 + k.nch)
+            PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
+    PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(psk::QualityDesc) * (size_t)nch, hipMemcpyHostToDevice, stream));
+    q.used = true, q.stream = stream, q.ch0 = ch0, q.nch = nch;
+    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; `slot` is the call's last plan slot)
+    auto mark = [&](const char *what) -> hipError_t {
+        if (!h->opt_trace)
+            return hipSuccess;
+        if (const hipError_t e = hipDeviceSynchronize())
+            return e;
+        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%u y_len=%u r_len=%u slot=%d stream=%p\n", what, 0, 0, ch0, nch,
+                     (uint32_t)n_seg, 0u, 0u, (h->slot + kPlanSlots - 1) % kPlanSlots, (void *)stream);
+        std::fflush(stderr);
+        return hipSuccess;
+    };
+    PSK_HIP(mark("quality_fold"));
+    PSK_HIP(psk::launch_quality_fold(q.d_desc, nch, max_seg, q.d_part, stream));
+    PSK_HIP(mark("quality_join"));
+    PSK_HIP(psk::launch_quality_join(q.d_desc, nch, q.d_part, h->d_quality, stream));
+    PSK_HIP(hipEventRecord(q.ev, stream));
+    h->q_turn = (h->q_turn + 1) % kQualitySlots;
+    return PSK_SOFT_OK;
+}
+
+// The public entry: the call, and with PSK_SOFT_OPT_QUALITY the reduction pass behind it.
+psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
+                                        const psk_soft_packet_t *pkts, psk_soft_output_t *outs, void *stream_v)
+{
+    if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
+    if (!h->opt_quality)
+        return process_device_call(h, ch0, nch, pkts, outs, stream_v);
+    // (the properties the call runs with: it snapshots them at its top, reference cpp/psk_soft.cpp:374-378)
+    h->q_snap.resize(nch);
+    for (uint32_t i = 0; i < nch; i++) {
+        const psk_soft_props_t &p = ctl_of(h, ch0 + i).props;
+        h->q_snap[i] = {p.constelationSize, p.samplesPerBaud, (uint8_t)(p.differentialDecoding != 0)};
+    }
+    const psk_soft_status st = process_device_call(h, ch0, nch, pkts, outs, stream_v);
+    if (st != PSK_SOFT_OK)
+        return st;
+    return quality_pass(h, ch0, nch, outs, stream_v);
 }
 
 // ---- host-buffer path: the ingest pipeline --------------------------
@@ -2276,6 +2438,58 @@ psk_soft_status psk_soft_get_channel_stats(psk_soft_handle_t *h, uint32_t ch0, u
     return stats_range(h, ch0, nch, stats, true);
 }
 
+// everything enqueued so far, the quality passes behind the calls included
+static psk_soft_status quality_wait(psk_soft_handle_t *h)
+{
+    const psk_soft_status st = psk_soft_synchronize(h);
+    if (st != PSK_SOFT_OK)
+        return st;
+    for (QualitySlot &q : h->qslot)
+        if (q.used)
+            PSK_HIP(hipEventSynchronize(q.ev));
+    return PSK_SOFT_OK;
+}
+
+uint64_t psk_soft_quality_bytes(void) { return sizeof(psk_soft_quality_t); }
+
+psk_soft_status psk_soft_get_quality(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_quality_t *q)
+{
+    if (!h || !q || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_quality: bad arguments");
+    if (h->dry) {
+        std::memcpy(q, h->quality_dry.data() + ch0, sizeof(psk_soft_quality_t) * nch);
+        return PSK_SOFT_OK;
+    }
+    const psk_soft_status st = quality_wait(h);
+    if (st != PSK_SOFT_OK)
+        return st;
+    PSK_HIP(hipMemcpy(q, h->d_quality + ch0, sizeof(psk_soft_quality_t) * nch, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_quality_derive(const psk_soft_quality_t *q, psk_soft_quality_derived_t *d)
+{
+    if (!q || !d)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_quality_derive: null pointer");
+    const double nan = std::nan("");
+    d->lock = d->snr_db = d->mean_energy = d->index_change_rate = nan;
+    if ((q->flags & PSK_SOFT_Q_LOCK) && q->n_lock)
+        d->lock = std::hypot(q->sum_lock_re, q->sum_lock_im) / (double)q->n_lock;
+    if (q->n_finite) {
+        const double m2 = q->sum_e / (double)q->n_finite, m4 = q->sum_e2 / (double)q->n_finite;
+        d->mean_energy = m2;
+        const double dd = 2.0 * m2 * m2 - m4;
+        if (!q->differentialDecoding && dd > 0.0) {
+            const double s = std::sqrt(dd);
+            if (m2 - s > 0.0)
+                d->snr_db = 10.0 * std::log10(s / (m2 - s));
+        }
+    }
+    if ((q->flags & PSK_SOFT_Q_INDEX) && q->n_symbols >= 2)
+        d->index_change_rate = (double)q->index_changes / (double)(q->n_symbols - 1);
+    return PSK_SOFT_OK;
+}
+
 psk_soft_status psk_soft_set_option(psk_soft_handle_t *h, int option, int value)
 {
     if (!h)
@@ -2300,6 +2514,21 @@ psk_soft_status psk_soft_set_option(psk_soft_handle_t *h, int option, int value)
         if (value < 0 || value > 2)
             return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_set_option: PSK_SOFT_OPT_PARALLEL_FIT takes 0, 1 or 2");
         h->opt_pfit = value;
+        return PSK_SOFT_OK;
+    case PSK_SOFT_OPT_QUALITY:
+        if (value != 0 && value != 1)
+            return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_set_option: PSK_SOFT_OPT_QUALITY takes 0 or 1");
+        if (value) {  // (all records zeroed)
+            if (h->dry) {
+                h->quality_dry.assign(h->nch, psk_soft_quality_t{});
+            } else {
+                const psk_soft_status st = quality_wait(h);
+                if (st != PSK_SOFT_OK)
+                    return st;
+                PSK_HIP(hipMemset(h->d_quality, 0, sizeof(psk_soft_quality_t) * (size_t)h->nch));
+            }
+        }
+        h->opt_quality = value;
         return PSK_SOFT_OK;
     default: return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_set_option: unknown option");
     }

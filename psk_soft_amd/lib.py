@@ -99,8 +99,50 @@ class Stats(ctypes.Structure):
     ]
 
 
+# Quality.flags
+Q_SOFT, Q_PHASE, Q_INDEX, Q_LOCK, Q_PLANNED = 1, 2, 4, 8, 128
+
+
+class Quality(ctypes.Structure):
+    """psk_soft_quality_t: the record of the last call that covered a channel with OPT_QUALITY on."""
+
+    _fields_ = [
+        ("n_symbols", ctypes.c_uint64),
+        ("n_finite", ctypes.c_uint64),
+        ("n_lock", ctypes.c_uint64),
+        ("index_changes", ctypes.c_uint64),
+        ("sum_e", ctypes.c_double),
+        ("sum_e2", ctypes.c_double),
+        ("sum_lock_re", ctypes.c_double),
+        ("sum_lock_im", ctypes.c_double),
+        ("phase_first", ctypes.c_float),
+        ("phase_last", ctypes.c_float),
+        ("index_first", ctypes.c_int16),
+        ("index_last", ctypes.c_int16),
+        ("constelationSize", ctypes.c_uint16),
+        ("samplesPerBaud", ctypes.c_uint16),
+        ("differentialDecoding", ctypes.c_uint8),
+        ("flags", ctypes.c_uint8),
+        ("pad", ctypes.c_uint8 * 6),
+    ]
+
+
+class QualityDerived(ctypes.Structure):
+    _fields_ = [
+        ("lock", ctypes.c_double),
+        ("snr_db", ctypes.c_double),
+        ("mean_energy", ctypes.c_double),
+        ("index_change_rate", ctypes.c_double),
+    ]
+
+
+QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
+
 # every symbol include/psk_soft_hip.h declares
 EXPORTS = (
+    "psk_soft_quality_bytes",
+    "psk_soft_get_quality",
+    "psk_soft_quality_derive",
     "psk_soft_device_alloc",
     "psk_soft_device_free",
     "psk_soft_device_upload",
@@ -183,6 +225,10 @@ def load():
     L.psk_soft_device_upload.argtypes = [vp, vp, vp, ctypes.c_size_t]
     L.psk_soft_device_download.argtypes = [vp, vp, vp, ctypes.c_size_t]
     L.psk_soft_probe_read_ms.argtypes = [vp, vp, u64, i32, ctypes.POINTER(ctypes.c_double)]
+    L.psk_soft_quality_bytes.argtypes = []
+    L.psk_soft_quality_bytes.restype = u64
+    L.psk_soft_get_quality.argtypes = [vp, u32, u32, ctypes.POINTER(Quality)]
+    L.psk_soft_quality_derive.argtypes = [ctypes.POINTER(Quality), ctypes.POINTER(QualityDerived)]
     _lib = L
     return L
 
@@ -208,6 +254,13 @@ def host_free(arr):
 def _check(status):
     if status != OK:
         raise PskSoftError(status, load().psk_soft_last_error().decode("utf-8", "replace"))
+
+
+def quality_derive(q):
+    """psk_soft_quality_derive of one Quality record: dict of lock, snr_db, mean_energy, index_change_rate (NaN where undefined)."""
+    d = QualityDerived()
+    _check(load().psk_soft_quality_derive(ctypes.byref(q), ctypes.byref(d)))
+    return {k: getattr(d, k) for k, _ in QualityDerived._fields_}
 
 
 class Handle:
@@ -268,6 +321,8 @@ class Handle:
     OPT_TIME_TILED = 3  # 0 never, 1 where it pays (default), 2 wherever the kernels exist
     OPT_DEFERRED_JOIN = 5  # mixed window classes: the side streams are joined by join() / synchronize(), not by every call
     OPT_PARALLEL_FIT = 4  # tiled calls: 0 fit block by block, 1 parallel fit with the second round on demand (default), 2 always
+
+    OPT_QUALITY = 6  # 1: every process call ends with the per-channel reduction pass, see quality()
 
     def set_option(self, option, value):
         _check(self._L.psk_soft_set_option(self._h, int(option), int(value)))
@@ -429,6 +484,22 @@ class Handle:
         arr = (Stats * nch)()
         _check(self._L.psk_soft_get_channel_stats(self._h, ch0, nch, arr))
         return [{k: getattr(s, k) for k, _ in Stats._fields_} for s in arr]
+
+    def quality_records(self, ch0=0, nch=None):
+        """The raw Quality records of [ch0, ch0+nch) (psk_soft_get_quality), a ctypes array."""
+        nch = self.n_channels - ch0 if nch is None else nch
+        arr = (Quality * nch)()
+        _check(self._L.psk_soft_get_quality(self._h, ch0, nch, arr))
+        return arr
+
+    def quality(self, ch0=0, nch=None):
+        """One dict per channel: the fields of its Quality record and the derived values (quality_derive)."""
+        res = []
+        for q in self.quality_records(ch0, nch):
+            d = {k: getattr(q, k) for k in QUALITY_FIELDS}
+            d.update(quality_derive(q))
+            res.append(d)
+        return res
 
     def export_state(self, ch):
         n = int(self._L.psk_soft_state_bytes(self._h))

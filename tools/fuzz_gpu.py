@@ -34,6 +34,10 @@ CS16 = float(os.environ.get("PSK_FUZZ_CS16", "0"))
 # packet as int8, the other half rotate CS8 / CS16 / CF32 packets of the same values call by call.  The signal is scaled so that
 # its peak lands between 1 and 127 LSB and rounded.  Drawn from a generator of its own, like the CS16 draw.
 CS8 = float(os.environ.get("PSK_FUZZ_CS8", "0"))
+# PSK_FUZZ_QUALITY=1: PSK_SOFT_OPT_QUALITY is on, and after every call the record of every channel that had a packet is compared
+# with the model (tests/quality_model.py) applied to the rows the call returned: counts, copied values, snapshot and flags equal,
+# the sums within the bound of n doubles added in any order.  The streams themselves are compared as always.
+QUALITY = os.environ.get("PSK_FUZZ_QUALITY", "0") != "0"
 TOL = 1e-5
 STRICT = os.environ.get("PSK_FUZZ_STRICT", "1") != "0"  # every float of soft / phase must equal the oracle's
 XD = 0.01
@@ -166,6 +170,12 @@ def main():
         h = pl.Handle(C, device=0, max_window_samples=int(os.environ.get("PSK_FUZZ_WINDOW", 33 * 1024 + 64)), max_phase_avg=max(2048, max(N_CHOICES)),
                       max_packet_complex=int(os.environ.get("PSK_FUZZ_PACKET", 1 << 20)))
         h.configure(0, props)
+        if QUALITY:
+            from tests import quality_model as qm
+
+            h.set_option(pl.Handle.OPT_QUALITY, 1)
+        cur = [dict(p) for p in props]  # the properties as configured so far (the snapshot of the next call)
+        q_bad = q_seen = 0
         oracles = []
         for c in range(C):
             o = po.OracleComponent()
@@ -187,6 +197,7 @@ def main():
                 ev = scripts[c][pos[c]]
                 while ev[0] == "set":
                     h.configure(c, [{ev[1]: ev[2]}])
+                    cur[c][ev[1]] = ev[2]
                     setattr(oracles[c], ev[1], ev[2])
                     pos[c] += 1
                     ev = scripts[c][pos[c]]
@@ -212,6 +223,18 @@ def main():
                 first[c] = False
                 pos[c] += 1
             res = h.process_host(0, pk)
+            if QUALITY:
+                recs = h.quality_records()
+                for c in range(C):
+                    if pk[c] is None:
+                        continue
+                    q_seen += 1
+                    try:
+                        qm.assert_record(recs[c], qm.model_record(res[c]["soft"], res[c]["phase"], res[c]["index"], cur[c]["constelationSize"],
+                                                                  cur[c]["samplesPerBaud"], cur[c]["differentialDecoding"]), "channel %d" % c)
+                    except AssertionError as e:
+                        q_bad += 1
+                        print("QUALITY MISMATCH round %d %s  props=%s" % (rnd, e, cur[c]))
             for c in range(C):
                 if pk[c] is not None:
                     for k in got[c]:
@@ -252,6 +275,9 @@ def main():
                         print("   soft differs at symbols %s ... (%d symbols); got %s ref %s" % (
                             sym[:16].tolist(), sym.size, g["soft"][2 * sym[0] : 2 * sym[0] + 2], r["soft"][2 * sym[0] : 2 * sym[0] + 2]))
         bad_total += bad
+        if QUALITY:
+            bad_total += q_bad
+            print("round %d: %d quality records compared with the model, %d mismatches" % (rnd, q_seen, q_bad))
         print("round %d: %d channels (%d CS16 / CS8), %d mismatches, last-call stats %s" % (rnd, C, sum(f is not None for f in cs16), bad, st))
     print("TOTAL mismatches:", bad_total)
     return 1 if bad_total else 0

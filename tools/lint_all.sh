@@ -32,6 +32,8 @@ for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cs8_S${s}_H1_E$e 
 others psk_kernels@cs8 -DPSK_INST_CS8=1; others psk_cs8
 # wide symbols (samplesPerBaud > 1024): the chunk and pick kernels (psk_wide.hip), the reference-order kernel's PSK_SEQ_WIDE build
 others psk_wide; others psk_kernels@wide -DPSK_SEQ_WIDE=1
+# the reduction pass of PSK_SOFT_OPT_QUALITY (psk_quality.hip): fold and join
+others psk_quality
 echo "instantiations with D sites / with E sites (tools/isa_lane_loss.py):"; grep -c "no covering save) [1-9]" $out.lanes; grep -c "mask restore) [1-9]" $out.lanes
 grep -c . $out; grep -v "C (lane carrier moved under a partial mask) 0" $out | wc -l
 rmdir $tmp
