@@ -188,6 +188,39 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
                                       const psk_soft_packet_t *pkts, psk_soft_output_t *outs);
 psk_soft_status psk_soft_synchronize(psk_soft_handle_t *h);
 
+/* psk_soft_process_device for packets whose samples are not contiguous: channelizer output, written frame by frame
+ * ([frame][channel]: for each time step one sample of every channel), handed over as it lies.
+ *   sample_stride[i]  distance between consecutive complex samples of packet i, counted in complex samples of that packet's
+ *                     format: sample k is the adjacent I,Q pair at element offset 2*k*sample_stride[i] from `data`.  For
+ *                     channel c of a matrix `width` channels wide: data = base + 2*c elements, sample_stride = width.
+ *   n_floats          as ever the packet's OWN elements (2 per sample, an odd last element ignored).  The library reads exactly
+ *                     those n_floats / 2 pairs, nothing between or behind them, and never writes to the caller's buffer.
+ * A stride of 1 -- or sample_stride == NULL, for the whole call -- is psk_soft_process_device: the same code path, no gather.
+ * One call may mix strided and contiguous packets, and formats.  `data` is aligned as the format asks (8 / 4 / 2 bytes: whole
+ * samples); the caller's buffer lives as long as for psk_soft_process_device (until the call's work on `stream` is done).
+ * Refused with PSK_SOFT_ERR_INVALID_ARG before anything is planned, committed or enqueued: a stride of 0 on a present packet,
+ * and an extent stride x bytes-per-sample x samples that does not fit 64 bits.
+ * Results: every output stream, count, SRI field, warning count, statistic and quality record is bit for bit what
+ * psk_soft_process_device gives for the contiguous packet holding the same samples, under every schedule and option.
+ *
+ * How: the strided packets are first gathered, on `stream`, into contiguous rows of a gather scratch the handle owns, in their
+ * own format (2 / 4 / 8 bytes a sample; rows 128-byte aligned), and the ordinary call runs on the rows.  Runs of at least 8
+ * consecutive packets of one format and stride whose `data` pointers lie exactly one sample apart -- adjacent columns of one
+ * matrix, lengths may differ -- take a tiled transpose that reads whole runs of bytes of every frame; any other strided packet
+ * is gathered sample by sample, each load a memory line of its own: correct and slow.  Keep a matrix's channels consecutive in
+ * the call.
+ * The scratch: one buffer per calling stream (four in all; a fifth stream takes over the one used longest ago, behind the
+ * event that ends its last call), grown to 1.25 x the largest call seen and never shrunk; growing is the one place that waits
+ * for the device.  With PSK_SOFT_OPT_DEFERRED_JOIN a class of an earlier call may still be reading its rows on a side stream
+ * when the next strided call arrives: that call JOINS the side streams into `stream` before it gathers (as psk_soft_join
+ * would), so rows are never overwritten while in use; calls without strided packets keep the deferred join as it is.
+ * A control-plane-only handle checks the strides, then plans and counts like psk_soft_process_device.
+ * There is no host-pointer counterpart: a host with pageable frame-major data gathers while it stages. */
+psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
+                                                const psk_soft_packet_t *pkts /* [nch] */,
+                                                const uint64_t *sample_stride /* [nch], or NULL */,
+                                                psk_soft_output_t *outs /* [nch] */, void *stream);
+
 /* PSK_SOFT_OPT_DEFERRED_JOIN: make `stream` (a hipStream_t; NULL = the handle's own) wait for everything the calls made so
  * far have put on the handle's side streams -- the point in stream order behind which their results may be used.  A no-op
  * without pending deferred calls.  (There is no counterpart in the reference: its serviceFunction() is synchronous.) */

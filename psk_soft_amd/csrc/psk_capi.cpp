@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "psk_ctl.h"
+#include "psk_gather.h"
 #include "psk_plan.h"
 #include "psk_quality.h"
 #include "psk_soft_hip.h"
@@ -110,6 +111,8 @@ constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
 constexpr int kQualitySlots = 4;  // calls whose quality pass (PSK_SOFT_OPT_QUALITY) may be in flight: descriptors and partials of each
 constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 packets, one per stream that uses them (see CvtScratch)
+constexpr int kGatherScratch = 4;  // gather scratch buffers of strided packets, one per stream that uses them (see GatherScratch)
+constexpr int kGatherDescSlots = 4;  // strided calls whose gather descriptors may be in flight
 // bytes of a packet's element
 inline size_t elem_bytes(const psk_soft_packet_t &k)
 {
@@ -266,6 +269,26 @@ struct CvtScratch {
     uint64_t last_use = 0;
 };
 
+// Where the strided packets of a call are gathered to (psk_soft_process_device_strided, psk_gather.hip): rows in the packet's own
+// element type, 128-byte aligned, grown on demand.  As CvtScratch: one buffer per calling stream, a buffer taken over from
+// another stream is used behind the event that ends its last call.
+struct GatherScratch {
+    hipStream_t stream = nullptr;
+    char *buf = nullptr;
+    size_t cap = 0;  // bytes
+    hipEvent_t ev = nullptr;
+    bool ev_used = false;
+    uint64_t last_use = 0;
+};
+// ... and the descriptors of one such call (psk_gather.h): written into page-locked memory, uploaded on the caller's stream in
+// front of the gather, reused behind the event that ends the call
+struct GatherDescSlot {
+    char *h_buf = nullptr, *d_buf = nullptr;
+    size_t cap = 0;  // bytes
+    hipEvent_t ev = nullptr;
+    bool used = false;
+};
+
 // PSK_SOFT_OPT_QUALITY: what the pass behind one call owns until its event -- the descriptors (pinned, and their copy in device
 // memory: one per channel of the handle) and the partials of the fold (grown on demand).  The chunks of psk_soft_process_host run
 // on streams of their own and overlap, hence several.
@@ -409,6 +432,13 @@ struct psk_soft_handle {
     // CS16 / CS8 packets: conversion scratch (CvtScratch)
     CvtScratch cvt[kCvtScratch];
     uint64_t cvt_calls = 0;
+    // strided packets: gather scratch and descriptor slots (GatherScratch, GatherDescSlot)
+    GatherScratch gat[kGatherScratch];
+    GatherDescSlot gdesc[kGatherDescSlots];
+    uint64_t gat_calls = 0;
+    int gdesc_turn = 0;
+    int opt_diag_gather_only = 0;  // PSK_SOFT_DIAG_GATHER_ONLY=1 (environment, timing experiments only -- tools/strided_rates.py): a
+                                   // strided call gathers and returns; the ordinary call behind it is left out, outs[] untouched
     // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
     // handle keeps them on the host
     int opt_quality = 0;
@@ -552,6 +582,8 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
         h->opt_trace = std::atoi(e);
     if (const char *e = std::getenv("PSK_SOFT_VALIDATE"))
         h->opt_validate = std::atoi(e);
+    if (const char *e = std::getenv("PSK_SOFT_DIAG_GATHER_ONLY"))
+        h->opt_diag_gather_only = std::atoi(e) != 0;
     if (const char *e = std::getenv("PSK_SOFT_SPLIT_CLASSES"))
         h->opt_split = std::atoi(e) < 0 ? 0 : std::atoi(e) > 16 ? 16 : std::atoi(e);
     if (const char *e = std::getenv("PSK_SOFT_PIPELINED"))
@@ -668,6 +700,15 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         for (auto &cv : h->cvt) {
             if (cv.ev) (void)hipEventSynchronize(cv.ev), (void)hipEventDestroy(cv.ev);
             if (cv.buf) (void)hipFree(cv.buf);
+        }
+        for (auto &g : h->gat) {
+            if (g.ev) (void)hipEventSynchronize(g.ev), (void)hipEventDestroy(g.ev);
+            if (g.buf) (void)hipFree(g.buf);
+        }
+        for (auto &g : h->gdesc) {
+            if (g.ev) (void)hipEventSynchronize(g.ev), (void)hipEventDestroy(g.ev);
+            if (g.h_buf) (void)hipHostFree(g.h_buf);
+            if (g.d_buf) (void)hipFree(g.d_buf);
         }
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
@@ -2111,6 +2152,234 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
     if (st != PSK_SOFT_OK)
         return st;
     return quality_pass(h, ch0, nch, outs, stream_v);
+}
+
+// Strided packets (include/psk_soft_hip.h): every packet whose samples lie `sample_stride[i]` samples apart is gathered into a
+// contiguous row of the gather scratch, in its own element type, on the caller's stream; a copy of the packet array points at the
+// rows and the ordinary call runs on it.  process_round, the plans, the cut into pieces and every kernel behind it see contiguous
+// packets.  Runs of packets that are adjacent columns of one frame-major matrix (frame groups, psk_gather.h) go through the tile
+// kernel, the rest through the plain strided gather.
+psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                                const uint64_t *sample_stride, psk_soft_output_t *outs, void *stream_v)
+{
+    if (!sample_stride)
+        return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
+    if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
+    // the refusals of this entry, before anything is planned: a stride of 0, an extent that does not fit 64 bits, a strided packet
+    // that does not start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
+    auto known = [](const psk_soft_packet_t &k) {
+        return k.format == PSK_SOFT_FORMAT_CF32 || k.format == PSK_SOFT_FORMAT_CS16 || k.format == PSK_SOFT_FORMAT_CS8;
+    };
+    // (a strided packet the call reads: present, complex data, at least one sample)
+    auto gathered = [&](uint32_t i) {
+        const psk_soft_packet_t &k = pkts[i];
+        return k.present && sample_stride[i] != 1 && k.sri_mode == 1 && k.n_floats >= 2 && k.data;
+    };
+    uint32_t n_gather = 0;
+    bool unknown = false;
+    for (uint32_t i = 0; i < nch; i++) {
+        const psk_soft_packet_t &k = pkts[i];
+        if (!k.present)
+            continue;
+        const uint64_t s = sample_stride[i];
+        char buf[160];
+        if (!s) {
+            std::snprintf(buf, sizeof buf, "psk_soft_process_device_strided: channel %u: a sample stride of 0", ch0 + i);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        if (s == 1)
+            continue;
+        if (!known(k)) {
+            unknown = true;
+            continue;
+        }
+        const uint64_t sb = 2u * elem_bytes(k);
+        uint64_t pitch = 0, extent = 0;
+        if (__builtin_mul_overflow(s, sb, &pitch) || __builtin_mul_overflow(pitch, k.n_floats / 2u, &extent)) {
+            std::snprintf(buf, sizeof buf, "psk_soft_process_device_strided: channel %u: stride x sample size x samples does not fit 64 bits",
+                          ch0 + i);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        if (!gathered(i))
+            continue;
+        if (reinterpret_cast<uintptr_t>(k.data) % sb)
+            return fail(PSK_SOFT_ERR_INVALID_ARG,
+                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2), soft 8, bits 4, phase 4, sampleIndex 4");
+        n_gather++;
+    }
+    // (a control-plane-only handle plans and counts: lengths and formats are all it looks at)
+    if (!n_gather || unknown || h->dry)
+        return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
+
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // ---- frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart ----
+    struct Run {
+        uint32_t first, g, bytes;
+    };
+    std::vector<Run> runs;
+    std::vector<size_t> row_off(nch, 0);
+    size_t need = 0;
+    for (uint32_t i = 0; i < nch;) {
+        if (!gathered(i)) {
+            i++;
+            continue;
+        }
+        const uint32_t sb = 2u * (uint32_t)elem_bytes(pkts[i]);
+        uint32_t j = i + 1;
+        while (j < nch && gathered(j) && pkts[j].format == pkts[i].format && sample_stride[j] == sample_stride[i] &&
+               reinterpret_cast<const char *>(pkts[j].data) == reinterpret_cast<const char *>(pkts[j - 1].data) + sb)
+            j++;
+        runs.push_back({i, j - i, sb});
+        for (uint32_t c = i; c < j; c++) {
+            row_off[c] = need;
+            need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
+        }
+        i = j;
+    }
+    // descriptors, per sample size (2, 4, 8 bytes: one launch of each kernel per size): [groups | their columns | singles]
+    uint32_t n_groups[3] = {}, n_cols[3] = {}, n_singles[3] = {};
+    auto size_idx = [](uint32_t bytes) { return bytes == 2 ? 0 : bytes == 4 ? 1 : 2; };
+    for (const Run &r : runs) {
+        const int b = size_idx(r.bytes);
+        if (r.g >= psk::kGatherMinGroup)
+            n_groups[b]++, n_cols[b] += r.g;
+        else
+            n_singles[b] += r.g;
+    }
+    const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
+    const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
+    const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
+    const size_t desc_bytes = off_singles + sizeof(psk::GatherSingle) * tot_singles;
+
+    // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
+    // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
+    PSK_HIP(deferred_join(h, stream));
+    GatherScratch *sc = nullptr;
+    for (auto &c : h->gat)
+        if (c.buf && c.stream == stream) {
+            sc = &c;
+            break;
+        }
+    if (!sc) {
+        sc = &h->gat[0];
+        for (auto &c : h->gat)
+            if (c.last_use < sc->last_use)
+                sc = &c;
+    }
+    if (!sc->ev)
+        PSK_HIP(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
+    if (sc->ev_used && sc->stream != stream)
+        PSK_HIP(hipStreamWaitEvent(stream, sc->ev, 0));
+    if (need > sc->cap) {  // (rare: grows to the largest call seen, plus a quarter; the one place that waits for the device)
+        PSK_HIP(hipDeviceSynchronize());
+        if (sc->buf) (void)hipFree(sc->buf);
+        sc->buf = nullptr;
+        sc->cap = 0;
+        const size_t cap = align_up(need + need / 4, 4096);
+        PSK_HIP(hipMalloc((void **)&sc->buf, cap));
+        sc->cap = cap;
+    }
+    sc->stream = stream;
+    sc->last_use = ++h->gat_calls;
+    GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
+    h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
+    if (!ds.ev)
+        PSK_HIP(hipEventCreateWithFlags(&ds.ev, hipEventDisableTiming));
+    if (ds.used)
+        PSK_HIP(hipEventSynchronize(ds.ev));
+    ds.used = false;
+    if (desc_bytes > ds.cap) {
+        if (ds.h_buf) (void)hipHostFree(ds.h_buf);
+        if (ds.d_buf) (void)hipFree(ds.d_buf);
+        ds.h_buf = ds.d_buf = nullptr;
+        ds.cap = 0;
+        const size_t cap = align_up(desc_bytes + desc_bytes / 4, 4096);
+        PSK_HIP(hipHostMalloc((void **)&ds.h_buf, cap));
+        PSK_HIP(hipMalloc((void **)&ds.d_buf, cap));
+        ds.cap = cap;
+    }
+    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
+    psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + off_cols);
+    psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
+    uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
+    uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
+    const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
+    uint64_t n_tiles[3] = {}, max_n_single[3] = {};
+    std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
+    for (const Run &r : runs) {
+        const int b = size_idx(r.bytes);
+        for (uint32_t c = r.first; c < r.first + r.g; c++) pk[c].data = reinterpret_cast<const float *>(sc->buf + row_off[c]);
+        if (r.g >= psk::kGatherMinGroup) {
+            psk::GatherGroup &g = hg[g_at[b]++];
+            g = psk::GatherGroup{};
+            g.src = pkts[r.first].data;
+            g.stride = sample_stride[r.first];
+            g.first = c_at[b] - c_lo[b];  // (the launch gets the columns of its sample size)
+            g.g = r.g;
+            g.tiles_c = (r.g + psk::kGatherTile - 1u) / psk::kGatherTile;
+            for (uint32_t c = r.first; c < r.first + r.g; c++) {
+                const uint64_t n = pkts[c].n_floats / 2u;
+                hc[c_at[b]++] = psk::GatherChan{sc->buf + row_off[c], n};
+                g.n_max = n > g.n_max ? n : g.n_max;
+            }
+            g.tile0 = n_tiles[b];
+            n_tiles[b] += (uint64_t)g.tiles_c * ((g.n_max + psk::kGatherTile - 1u) / psk::kGatherTile);
+        } else {
+            for (uint32_t c = r.first; c < r.first + r.g; c++) {
+                const uint64_t n = pkts[c].n_floats / 2u;
+                hs[s_at[b]++] = psk::GatherSingle{pkts[c].data, sc->buf + row_off[c], sample_stride[c], n};
+                max_n_single[b] = n > max_n_single[b] ? n : max_n_single[b];
+            }
+        }
+    }
+    PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
+    ds.used = true;  // (from here on the slot waits for its event, which the end of this function records whatever happens)
+    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; S = bytes of a complex sample, cnt = groups / singles covered)
+    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) -> hipError_t {
+        if (!h->opt_trace)
+            return hipSuccess;
+        if (const hipError_t e = hipDeviceSynchronize())
+            return e;
+        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, bytes, 0, ch0, cnt,
+                     (unsigned long long)tiles, 0u, 0u, h->slot, (void *)stream);
+        std::fflush(stderr);
+        return hipSuccess;
+    };
+    auto enqueue = [&]() -> psk_soft_status {
+        const psk::GatherGroup *const dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
+        const psk::GatherChan *const dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + off_cols);
+        const psk::GatherSingle *const dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + off_singles);
+        for (int b = 0; b < 3; b++) {
+            const int bytes = 2 << b;
+            if (n_groups[b]) {
+                PSK_HIP(mark("gather_tiles", bytes, n_groups[b], n_tiles[b]));
+                PSK_HIP(psk::launch_gather_tiles(bytes, dg + g_lo[b], n_groups[b], dc + c_lo[b], n_tiles[b], stream));
+            }
+            if (n_singles[b]) {
+                PSK_HIP(mark("gather_singles", bytes, n_singles[b], 0));
+                PSK_HIP(psk::launch_gather_singles(bytes, dsg + s_lo[b], n_singles[b], max_n_single[b], stream));
+            }
+        }
+        return PSK_SOFT_OK;
+    };
+    psk_soft_status st = enqueue();
+    if (st == PSK_SOFT_OK && !h->opt_diag_gather_only)
+        st = psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
+    // the rows and the descriptors are free again behind everything this call has put on the stream (without the deferred join
+    // the side streams of the call are joined into it by now; with it, the next strided call joins them first, above)
+    const std::string keep = g_last_error;
+    const hipError_t e1 = hipEventRecord(sc->ev, stream), e2 = hipEventRecord(ds.ev, stream);
+    sc->ev_used = true;
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+        (void)hipStreamSynchronize(stream);
+        ds.used = false;
+        if (st == PSK_SOFT_OK)
+            return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    }
+    g_last_error = keep;
+    return st;
 }
 
 // ---- host-buffer path: the ingest pipeline --------------------------

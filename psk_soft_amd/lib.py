@@ -161,6 +161,7 @@ EXPORTS = (
     "psk_soft_fire_listener",
     "psk_soft_output_capacity",
     "psk_soft_process_device",
+    "psk_soft_process_device_strided",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -204,6 +205,7 @@ def load():
     L.psk_soft_output_capacity.argtypes = [vp, u32, u64]
     L.psk_soft_output_capacity.restype = u64
     L.psk_soft_process_device.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(Output), vp]
+    L.psk_soft_process_device_strided.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Output), vp]
     L.psk_soft_process_host.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(Output)]
     L.psk_soft_synchronize.argtypes = [vp]
     L.psk_soft_join.argtypes = [vp, vp]
@@ -249,6 +251,32 @@ def host_alloc(n, dtype):
 
 def host_free(arr):
     load().psk_soft_host_free(ctypes.c_void_p(arr.ctypes.data))
+
+
+FORMAT_SAMPLE_BYTES = {FORMAT_CF32: 8, FORMAT_CS16: 4, FORMAT_CS8: 2}
+
+
+def frame_major_packets(base, frames, width, first_column, n_channels, fmt=FORMAT_CF32, xdelta=1.0, sriChanged=False):
+    """Packets and strides of `n_channels` adjacent channels of a frame-major matrix (a channelizer's output: `frames` rows
+    of `width` complex samples of format `fmt`, one sample of every channel per row) at the device address `base`: channel i
+    is column first_column + i.  `frames` is a count for all channels or one count per channel (ragged lengths).  Returns
+    (Packet array, uint64 stride array) for Handle.process_device_strided; set the remaining packet fields as needed."""
+    if first_column < 0 or first_column + n_channels > width:
+        raise ValueError("columns %d .. %d are outside a matrix %d wide" % (first_column, first_column + n_channels, width))
+    sb = FORMAT_SAMPLE_BYTES[fmt]
+    pk = (Packet * n_channels)()
+    strides = (ctypes.c_uint64 * n_channels)()
+    for i in range(n_channels):
+        n = int(frames if np.isscalar(frames) else frames[i])
+        pk[i].data = int(base) + sb * (first_column + i)
+        pk[i].n_floats = 2 * n
+        pk[i].sri_xdelta = float(xdelta)
+        pk[i].sri_mode = 1
+        pk[i].sriChanged = int(bool(sriChanged))
+        pk[i].present = 1
+        pk[i].format = fmt
+        strides[i] = width
+    return pk, strides
 
 
 def _check(status):
@@ -342,6 +370,16 @@ class Handle:
     def process_device(self, ch0, pkts, outs, stream=None):
         """pkts / outs: ctypes arrays of Packet / Output holding DEVICE pointers."""
         _check(self._L.psk_soft_process_device(self._h, ch0, len(pkts), pkts, outs, ctypes.c_void_p(stream or 0)))
+
+    def process_device_strided(self, ch0, pkts, strides, outs, stream=None):
+        """process_device for packets whose complex samples lie strides[i] samples apart (frame-major channelizer output, see
+        frame_major_packets): gathered on the GPU, then the ordinary call.  strides: None (all contiguous), a ctypes uint64
+        array or a sequence of ints, one per packet."""
+        if strides is not None and not isinstance(strides, ctypes.Array):
+            strides = (ctypes.c_uint64 * len(pkts))(*[int(s) for s in strides])
+        if strides is not None and len(strides) != len(pkts):
+            raise ValueError("one stride per packet")
+        _check(self._L.psk_soft_process_device_strided(self._h, ch0, len(pkts), pkts, strides, outs, ctypes.c_void_p(stream or 0)))
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with

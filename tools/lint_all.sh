@@ -34,6 +34,8 @@ others psk_kernels@cs8 -DPSK_INST_CS8=1; others psk_cs8
 others psk_wide; others psk_kernels@wide -DPSK_SEQ_WIDE=1
 # the reduction pass of PSK_SOFT_OPT_QUALITY (psk_quality.hip): fold and join
 others psk_quality
+# the gather pre-pass of psk_soft_process_device_strided (psk_gather.hip): the tile kernel and the plain strided gather, three sample sizes each
+others psk_gather
 echo "instantiations with D sites / with E sites (tools/isa_lane_loss.py):"; grep -c "no covering save) [1-9]" $out.lanes; grep -c "mask restore) [1-9]" $out.lanes
 grep -c . $out; grep -v "C (lane carrier moved under a partial mask) 0" $out | wc -l
 rmdir $tmp
