@@ -79,24 +79,30 @@ typedef struct psk_soft_limits {
  *   PSK_SOFT_FORMAT_CS8   interleaved int8 I,Q (sc8, bulkio::InCharPort dataChar); `data` 2-byte aligned (whole complex
  *                         samples).  Bit for bit what the CF32 packet -- and the CS16 packet -- of the values (float)v
  *                         gives; a quarter of the float packet's bytes.
- * Any other value (2 among them) is refused with PSK_SOFT_ERR_INVALID_ARG before anything is enqueued.  (ABI version 2 before this
+ *   PSK_SOFT_FORMAT_CF16  interleaved IEEE binary16 I,Q, little-endian, I first (cf16; torch.complex32 is this layout);
+ *                         `data` 4-byte aligned (whole complex samples).  Bit for bit what the CF32 packet of the widened
+ *                         values gives: binary16 -> binary32 is exact for every finite value and the infinities, half
+ *                         subnormals become normal floats (never flushed), a quiet NaN keeps its sign and its payload
+ *                         shifted left by 13 bits.  Signalling-NaN encodings (exponent 31, mantissa non-zero, bit 9 clear)
+ *                         are outside that contract: the result is that of some NaN.  Half the float packet's bytes.
+ * Any other value (2, 5, 6, 7 among them) is refused with PSK_SOFT_ERR_INVALID_ARG before anything is enqueued.  (ABI version 2 before this
  * field had a name called it `reserved` and ignored it: callers that left garbage there must zero it.) */
-enum { PSK_SOFT_FORMAT_CF32 = 0, PSK_SOFT_FORMAT_CS16 = 1, PSK_SOFT_FORMAT_CS8 = 3 };
+enum { PSK_SOFT_FORMAT_CF32 = 0, PSK_SOFT_FORMAT_CS16 = 1, PSK_SOFT_FORMAT_CS8 = 3, PSK_SOFT_FORMAT_CF16 = 4 };
 
 /* One bulkio::InFloatPort (or InShortPort, InCharPort) ::dataTransfer as serviceFunction() reads it
  * (reference cpp/psk_soft.cpp:349-359, 394, 428). */
 typedef struct psk_soft_packet {
     const float *data;          /* dataBuffer: interleaved I,Q (device or host pointer, per entry point); for
                                    PSK_SOFT_FORMAT_CS16 it points at int16 elements, for PSK_SOFT_FORMAT_CS8 at int8
-                                   elements (cast the pointer)                                                  */
-    uint64_t n_floats;          /* dataBuffer.size(): ELEMENTS of the packet's format (floats, int16s, int8s); the
+                                   elements, for PSK_SOFT_FORMAT_CF16 at binary16 elements (cast the pointer)   */
+    uint64_t n_floats;          /* dataBuffer.size(): ELEMENTS of the packet's format (floats, int16s, int8s, halves); the
                                    packet holds n_floats / 2 complex samples, an odd last element is ignored   */
     double sri_xdelta;          /* SRI.xdelta                                                             */
     int32_t sri_mode;           /* SRI.mode; anything but 1 is dropped with a warning (:359-363)          */
     uint8_t sriChanged;
     uint8_t inputQueueFlushed;  /* forces resetState (:353-357)                                           */
     uint8_t present;            /* 0 = getPacket() returned NULL for this channel: NOOP (:350-352)        */
-    uint8_t format;             /* PSK_SOFT_FORMAT_CF32 / _CS16 / _CS8 (checked on present packets)          */
+    uint8_t format;             /* PSK_SOFT_FORMAT_CF32 / _CS16 / _CS8 / _CF16 (checked on present packets)  */
 } psk_soft_packet_t;
 
 /* Where one channel's four output streams go, and what the call produced.

@@ -50,6 +50,13 @@ hipError_t launch_fast_cs8(int S, int exact, const ChanPlan *plans, const uint32
                            float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
 hipError_t launch_seq_cs8(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
+// complex binary16 packets (psk_cf16.hip): the same four entry points, for the builds with PSK_INST_CF16=1
+hipError_t launch_cf16_convert(const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
+bool fast_cf16_has(int S);
+hipError_t launch_fast_cf16(int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
+                            float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
+hipError_t launch_seq_cf16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
 // time-tiled kernels (psk_tile.hip)
 bool tile_front_has(int S, int H);
 hipError_t launch_tile_front(int S, int H, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles,
@@ -110,21 +117,24 @@ constexpr int kPlanSlots = 4;
 constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that mixes window classes (see psk_soft_process_device)
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
 constexpr int kQualitySlots = 4;  // calls whose quality pass (PSK_SOFT_OPT_QUALITY) may be in flight: descriptors and partials of each
-constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 packets, one per stream that uses them (see CvtScratch)
+constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 / CF16 packets, one per stream that uses them (see CvtScratch)
 constexpr int kGatherScratch = 4;  // gather scratch buffers of strided packets, one per stream that uses them (see GatherScratch)
 constexpr int kGatherDescSlots = 4;  // strided calls whose gather descriptors may be in flight
 // bytes of a packet's element
 inline size_t elem_bytes(const psk_soft_packet_t &k)
 {
-    return k.format == PSK_SOFT_FORMAT_CS16 ? sizeof(int16_t) : k.format == PSK_SOFT_FORMAT_CS8 ? sizeof(int8_t) : sizeof(float);
+    return k.format == PSK_SOFT_FORMAT_CS16   ? sizeof(int16_t)
+           : k.format == PSK_SOFT_FORMAT_CS8  ? sizeof(int8_t)
+           : k.format == PSK_SOFT_FORMAT_CF16 ? sizeof(uint16_t)
+                                              : sizeof(float);
 }
-// bytes of the upload slot of a call of n channels: header, plans, compact lists, CS16 / CS8 conversion descriptors (psk_plan.h)
+// bytes of the upload slot of a call of n channels: header, plans, compact lists, CS16 / CS8 / CF16 conversion descriptors (psk_plan.h)
 inline size_t slot_cvt_offset(size_t n)
 {
     return (psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * n + 15u) & ~(size_t)15u;
 }
-// ... then one more channel list for the reference-order kernel when a call has CS16 / CS8 channels on the in-place kernels: the
-// channels of the float build, of the CS16 build, of the CS8 build (and of the wide-symbol build)
+// ... then one more channel list for the reference-order kernel when a call has CS16 / CS8 / CF16 channels on the in-place kernels:
+// the channels of the float build, of the CS16 build, of the CS8 build, of the CF16 build (and of the wide-symbol build)
 inline size_t slot_seq_offset(size_t n) { return slot_cvt_offset(n) + sizeof(psk::CvtDesc) * n; }
 inline size_t slot_bytes(size_t n) { return slot_seq_offset(n) + sizeof(uint32_t) * n; }
 
@@ -309,11 +319,12 @@ struct QualitySlot {
 constexpr uint32_t kFastFitMax = 32768 - 128;
 constexpr uint32_t kDeepFit = 2048 - 128;
 // second index of the per-class tables: history blocks (+ 8: deep fit window); 3: one block, CS16 packets read in place; 5: one
-// block, CS8 packets read in place
-const int kClassH[] = {1, 3, 5, 2, 4, 8, 9, 10, 12, 16};
+// block, CS8 packets read in place; 6: one block, CF16 packets read in place
+const int kClassH[] = {1, 3, 5, 6, 2, 4, 8, 9, 10, 12, 16};
 constexpr int kClassCs16 = 3;
 constexpr int kClassCs8 = 5;
-inline int class_H(int Hi) { return Hi == kClassCs16 || Hi == kClassCs8 ? 1 : Hi > 8 ? Hi - 8 : Hi; }
+constexpr int kClassCf16 = 6;
+inline int class_H(int Hi) { return Hi == kClassCs16 || Hi == kClassCs8 || Hi == kClassCf16 ? 1 : Hi > 8 ? Hi - 8 : Hi; }
 constexpr int kNumClassH = (int)(sizeof(kClassH) / sizeof(kClassH[0]));
 // time-tiled kernels, automatic choice (measured, tools/tiled_sweep2.sh: QPSK, samplesPerBaud 8): a class of at most 64
 // channels whose longest call has at least 16 blocks of 128 symbols, or of at most 512 channels and 192 blocks (at 128
@@ -429,7 +440,7 @@ struct psk_soft_handle {
     hipStream_t tile_stream = nullptr;  // stream of the last call that used the scratch
     bool tile_ev_used = false;
     bool poisoned = false;  // a HIP call failed after kernels of a call were enqueued: host mirror and device state may disagree
-    // CS16 / CS8 packets: conversion scratch (CvtScratch)
+    // CS16 / CS8 / CF16 packets: conversion scratch (CvtScratch)
     CvtScratch cvt[kCvtScratch];
     uint64_t cvt_calls = 0;
     // strided packets: gather scratch and descriptor slots (GatherScratch, GatherDescSlot)
@@ -843,10 +854,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         return (p.lf_flags & psk::PLAN_CS8) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
                p.lf_n <= kDeepFit && psk::fast_cs8_has((int)p.S);
     };
+    // (CF16: the same classes, PSK_INST_CF16, a class of their own too)
+    auto cf16_in_place = [&](const psk::ChanPlan &p) {
+        return (p.lf_flags & psk::PLAN_CF16) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
+               p.lf_n <= kDeepFit && psk::fast_cf16_has((int)p.S);
+    };
     // the class of a planned channel that emits on the wave-scan kernels
     auto class_of = [&](const psk::ChanPlan &p) {
-        return (p.lf_flags & psk::PLAN_CS16_IN_PLACE) ? kClassCs16
-               : (p.lf_flags & psk::PLAN_CS8_IN_PLACE) ? kClassCs8
+        return (p.lf_flags & psk::PLAN_CS16_IN_PLACE)   ? kClassCs16
+               : (p.lf_flags & psk::PLAN_CS8_IN_PLACE)  ? kClassCs8
+               : (p.lf_flags & psk::PLAN_CF16_IN_PLACE) ? kClassCf16
                                                         : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
     };
     auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
@@ -876,6 +893,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                     p.lf_flags |= psk::PLAN_CS16_IN_PLACE;
                 if (cs8_in_place(p))
                     p.lf_flags |= psk::PLAN_CS8_IN_PLACE;
+                if (cf16_in_place(p))
+                    p.lf_flags |= psk::PLAN_CF16_IN_PLACE;
                 const int Hh = class_of(p);
                 r.need_SH[p.S][Hh] = true;
                 r.cnt_SH[p.S][Hh] += mult;
@@ -897,9 +916,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         }
     };
     uint32_t *const handed_over = dry ? nullptr : psk::plan_header(h->d_plans[slot]);  // (psk_plan.h)
-    // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 pairs, 2-byte aligned int8 pairs)
+    // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 and binary16 pairs, 2-byte aligned int8 pairs)
     auto misaligned = [&](const psk::ChanPlan &p) {
-        const uintptr_t in_mask = (p.lf_flags & psk::PLAN_CS16) ? 3u : (p.lf_flags & psk::PLAN_CS8) ? 1u : 7u;
+        const uintptr_t in_mask = (p.lf_flags & (psk::PLAN_CS16 | psk::PLAN_CF16)) ? 3u : (p.lf_flags & psk::PLAN_CS8) ? 1u : 7u;
         return !dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & in_mask) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
                         ((uintptr_t)p.phase & 3u) || ((uintptr_t)p.sidx & 3u));
     };
@@ -1029,10 +1048,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     if (res.st != PSK_SOFT_OK) {
         if (res.why == 2)
             return fail(PSK_SOFT_ERR_INVALID_ARG,
-                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2), soft 8, bits 4, phase 4, sampleIndex 4");
+                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
         if (res.why == 3) {
             char buf[160];
-            std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3)",
+            std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
                           ch0 + res.bad, (unsigned)pkts[res.bad].format);
             return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
         }
@@ -1076,15 +1095,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (h->slot_aux_used[k][a])
                     PSK_HIP(hipStreamWaitEvent(stream, h->slot_aux_ev[k][a], 0));
         }
-    // CS16 and CS8 channels read in place have classes of their own (kClassCs16, kClassCs8), which have no time-tiled kernels: where
-    // the float class would go through those (the same choice as below, on the three classes together), their channels go back to
-    // the float class and to the conversion pre-pass
-    if (!stamped || (plans[0].lf_flags & (psk::PLAN_CS16_IN_PLACE | psk::PLAN_CS8_IN_PLACE)))
+    // CS16, CS8 and CF16 channels read in place have classes of their own (kClassCs16, kClassCs8, kClassCf16), which have no
+    // time-tiled kernels: where the float class would go through those (the same choice as below, on the four classes together),
+    // their channels go back to the float class and to the conversion pre-pass
+    constexpr uint32_t kInPlaceFlags = psk::PLAN_CS16_IN_PLACE | psk::PLAN_CS8_IN_PLACE | psk::PLAN_CF16_IN_PLACE;
+    if (!stamped || (plans[0].lf_flags & kInPlaceFlags))
         for (int S = 2; S <= 16; S++) {
-            if ((!res.need_SH[S][kClassCs16] && !res.need_SH[S][kClassCs8]) || !h->opt_tiled || !psk::tile_front_has(S, 1))
+            if ((!res.need_SH[S][kClassCs16] && !res.need_SH[S][kClassCs8] && !res.need_SH[S][kClassCf16]) || !h->opt_tiled || !psk::tile_front_has(S, 1))
                 continue;
             uint32_t cnt = res.cnt_SH[S][1], mb = res.max_blocks_SH[S][1], mn = res.max_n[S][1];
-            for (int Hc : {kClassCs16, kClassCs8}) {
+            for (int Hc : {kClassCs16, kClassCs8, kClassCf16}) {
                 cnt += res.cnt_SH[S][Hc];
                 mb = res.max_blocks_SH[S][Hc] > mb ? res.max_blocks_SH[S][Hc] : mb;
                 mn = res.max_n[S][Hc] > mn ? res.max_n[S][Hc] : mn;
@@ -1100,7 +1120,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             res.cnt_SH[S][1] = cnt;
             res.max_blocks_SH[S][1] = mb;
             res.max_n[S][1] = mn;
-            for (int Hc : {kClassCs16, kClassCs8}) {
+            for (int Hc : {kClassCs16, kClassCs8, kClassCf16}) {
                 res.max_A[S][1] = res.max_A[S][1] > res.max_A[S][Hc] ? res.max_A[S][1] : res.max_A[S][Hc];
                 res.blocks_SH[S][1] += res.blocks_SH[S][Hc];
                 res.need_SH[S][Hc] = false;
@@ -1109,7 +1129,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             for (uint32_t i = 0; i < nch; i++)
                 if (plans[i].S == (uint32_t)S)
-                    plans[i].lf_flags &= ~(uint32_t)(psk::PLAN_CS16_IN_PLACE | psk::PLAN_CS8_IN_PLACE);
+                    plans[i].lf_flags &= ~kInPlaceFlags;
         }
     // compact lists, one per launch, behind the plans: first the channels that emit nothing, then every (S, H)
     // class in launch order
@@ -1217,7 +1237,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     for (int pass = 0; pass < (h->opt_tiled ? 2 : 0); pass++) {
         for (int S : kFastS)
             for (int H : kClassH) {
-                if (!res.need_SH[S][H] || H == kClassCs16 || H == kClassCs8 || !psk::tile_front_has(S, class_H(H)))
+                if (!res.need_SH[S][H] || H == kClassCs16 || H == kClassCs8 || H == kClassCf16 || !psk::tile_front_has(S, class_H(H)))
                     continue;
                 // pipelined: the serial fit of a range under the front stage of the next (see kPipeMinChannels)
                 // (PSK_SOFT_PIPELINED=2, tests: wherever the kernels allow it, a few blocks to a range)
@@ -1408,9 +1428,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
         }
     }
-    // CS16 and CS8 packets (psk_cs16.hip, psk_cs8.hip): converted into float2 rows of the conversion scratch by one pre-pass per
+    // CS16, CS8 and CF16 packets (psk_cs16.hip, psk_cs8.hip, psk_cf16.hip): converted into float2 rows of the conversion scratch by one pre-pass per
     // format in front of the call's first kernel; their plans point at the rows from here on.  The descriptors travel behind the
-    // plans, in the same upload: the CS16 packets' first, then the CS8 packets'.
+    // plans, in the same upload: the CS16 packets' first, then the CS8 packets', then the CF16 packets'.
     auto cvt_flag = [](const psk::ChanPlan &p) -> uint32_t {  // (the format flag of a packet the pre-pass converts, else 0)
         if (p.mode == psk::PLAN_SKIP || !p.n_in)
             return 0u;
@@ -1418,10 +1438,12 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             return psk::PLAN_CS16;
         if ((p.lf_flags & psk::PLAN_CS8) && !(p.lf_flags & psk::PLAN_CS8_IN_PLACE))
             return psk::PLAN_CS8;
+        if ((p.lf_flags & psk::PLAN_CF16) && !(p.lf_flags & psk::PLAN_CF16_IN_PLACE))
+            return psk::PLAN_CF16;
         return 0u;
     };
-    uint32_t n_cvt = 0, n_cvt16 = 0;
-    uint64_t cvt_max_n16 = 0, cvt_max_n8 = 0;
+    uint32_t n_cvt = 0, n_cvt16 = 0, n_cvt8 = 0;
+    uint64_t cvt_max_n16 = 0, cvt_max_n8 = 0, cvt_max_nh = 0;
     CvtScratch *cv = nullptr;
     {
         size_t need = 0;
@@ -1431,6 +1453,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 need += align_up(sizeof(float2) * p.n_in, 128);
                 n_cvt++;
                 n_cvt16 += f == psk::PLAN_CS16 ? 1u : 0u;
+                n_cvt8 += f == psk::PLAN_CS8 ? 1u : 0u;
             }
         }
         if (n_cvt) {
@@ -1463,38 +1486,40 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             psk::CvtDesc *const desc =
                 reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_cvt_offset(nch));
             size_t off = 0;
-            uint32_t k16 = 0, k8 = n_cvt16;
+            uint32_t k16 = 0, k8 = n_cvt16, kh = n_cvt16 + n_cvt8;
             for (uint32_t i = 0; i < nch; i++) {
                 psk::ChanPlan &p = plans[i];
                 const uint32_t f = cvt_flag(p);
                 if (!f)
                     continue;
-                const uint32_t k = f == psk::PLAN_CS16 ? k16++ : k8++;
+                const uint32_t k = f == psk::PLAN_CS16 ? k16++ : f == psk::PLAN_CS8 ? k8++ : kh++;
                 desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
                 desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
                 desc[k].n = p.n_in;
                 p.in = desc[k].dst;
                 off += align_up(sizeof(float2) * p.n_in, 128);
-                uint64_t &mx = f == psk::PLAN_CS16 ? cvt_max_n16 : cvt_max_n8;
+                uint64_t &mx = f == psk::PLAN_CS16 ? cvt_max_n16 : f == psk::PLAN_CS8 ? cvt_max_n8 : cvt_max_nh;
                 mx = p.n_in > mx ? p.n_in : mx;
             }
         }
     }
-    // the reference-order kernel's lists when CS16 / CS8 channels are read in place: float-build channels first, then the CS16
-    // build's, then the CS8 build's (and the wide symbols' last)
-    uint32_t n_in_place = 0, n_in_place8 = 0;
+    // the reference-order kernel's lists when CS16 / CS8 / CF16 channels are read in place: float-build channels first, then the
+    // CS16 build's, then the CS8 build's, then the CF16 build's (and the wide symbols' last)
+    uint32_t n_in_place = 0, n_in_place8 = 0, n_in_placeh = 0;
     for (uint32_t i = 0; i < nch; i++) {
         n_in_place += (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? 1u : 0u;
         n_in_place8 += (plans[i].lf_flags & psk::PLAN_CS8_IN_PLACE) ? 1u : 0u;
+        n_in_placeh += (plans[i].lf_flags & psk::PLAN_CF16_IN_PLACE) ? 1u : 0u;
     }
-    const uint32_t n_seq_narrow = nch - n_in_place - n_in_place8 - n_wide_seq;
-    if (n_in_place || n_in_place8 || n_wide_seq) {
+    const uint32_t n_seq_narrow = nch - n_in_place - n_in_place8 - n_in_placeh - n_wide_seq;
+    if (n_in_place || n_in_place8 || n_in_placeh || n_wide_seq) {
         uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_seq_offset(nch));
-        uint32_t a = 0, b = n_seq_narrow, b8 = n_seq_narrow + n_in_place, c = nch - n_wide_seq;
+        uint32_t a = 0, b = n_seq_narrow, b8 = n_seq_narrow + n_in_place, bh = n_seq_narrow + n_in_place + n_in_place8, c = nch - n_wide_seq;
         for (uint32_t i = 0; i < nch; i++)
             seq[(plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) ? c++
                 : (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE)              ? b++
                 : (plans[i].lf_flags & psk::PLAN_CS8_IN_PLACE)               ? b8++
+                : (plans[i].lf_flags & psk::PLAN_CF16_IN_PLACE)              ? bh++
                                                                              : a++] = i;
     }
     // PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call
@@ -1542,7 +1567,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             else if (cvt_flag(p) &&
                      (!cv || (const char *)p.in < (const char *)cv->buf ||
                       (const char *)p.in + sizeof(float2) * p.n_in > (const char *)cv->buf + cv->cap))
-                why = "converted CS16 / CS8 packet outside the conversion scratch";
+                why = "converted CS16 / CS8 / CF16 packet outside the conversion scratch";
         }
         if (why) {
             char buf[200];
@@ -1609,7 +1634,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         hdr[0] = 0u;                       // channels handed over: counted by the kernels
         hdr[1] = res.any_seq ? 1u : 0u;    // channels planned for the reference-order kernel
     }
-    const size_t up_bytes = (n_in_place || n_in_place8 || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
+    const size_t up_bytes = (n_in_place || n_in_place8 || n_in_placeh || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
                             : n_cvt    ? slot_cvt_offset(nch) + sizeof(psk::CvtDesc) * n_cvt
                                        : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
     if (h->opt_up_stream) {
@@ -1631,14 +1656,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     };
     // PSK_SOFT_TRACE_LAUNCHES=1 (debugging a faulting kernel): in front of every launch the host waits for everything enqueued so
     // far and writes one line for the launch and one per channel of its list to stderr -- the last launch named in the log of a
-    // run that died is the one that did it, with the shapes it was given.  (=2: the launch lines only.)
+    // run that died is the one that did it, with the shapes it was given.  (=2: the launch lines only.)  stream= is the stream the
+    // launch goes to (mark_st): the caller's, or the side stream of the launch's class.
+    hipStream_t mark_st = stream;
     auto mark = [&](const char *what, int S, int H, uint32_t off, uint32_t cnt, uint32_t tiles, uint32_t y_len, uint32_t r_len) -> hipError_t {
         if (!h->opt_trace)
             return hipSuccess;
         if (const hipError_t e = hipDeviceSynchronize())
             return e;
         std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%u y_len=%u r_len=%u slot=%d stream=%p\n", what, S, H, ch0, cnt,
-                     tiles, y_len, r_len, slot, (void *)stream);
+                     tiles, y_len, r_len, slot, (void *)mark_st);
         for (uint32_t i = 0; i < cnt && h->opt_trace == 1; i++) {
             const uint32_t bi = stamped || off == ~0u ? i : h_list[off + i];
             const psk::ChanPlan &p = plans[bi];
@@ -1661,12 +1688,19 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)),
                 n_cvt16, cvt_max_n16, stream));
         }
-        if (n_cvt > n_cvt16) {
-            PSK_HIP(mark("cs8_convert", 0, 0, ~0u, 0, n_cvt - n_cvt16, 0, 0));
+        if (n_cvt8) {
+            PSK_HIP(mark("cs8_convert", 0, 0, ~0u, 0, n_cvt8, 0, 0));
             PSK_HIP(psk::launch_cs8_convert(
                 reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)) +
                     n_cvt16,
-                n_cvt - n_cvt16, cvt_max_n8, stream));
+                n_cvt8, cvt_max_n8, stream));
+        }
+        if (n_cvt > n_cvt16 + n_cvt8) {
+            PSK_HIP(mark("cf16_convert", 0, 0, ~0u, 0, n_cvt - n_cvt16 - n_cvt8, 0, 0));
+            PSK_HIP(psk::launch_cf16_convert(
+                reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)) +
+                    n_cvt16 + n_cvt8,
+                n_cvt - n_cvt16 - n_cvt8, cvt_max_nh, stream));
         }
         if (any_quiet)
             PSK_HIP(mark("fast<0,1> (calls that emit nothing)", 0, 1, off_quiet, res.cnt_quiet, 0, ring_floats(res.max_n_quiet, 512u), 0));
@@ -1752,6 +1786,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                     used_aux = i;
                 }
             }
+            mark_st = st;
             const uint32_t y_len = ring_floats(max_n[S][H], psk::ering_dynamic(S) ? 256u : 512u);
             const uint32_t r_len = class_H(H) == 1 ? ((max_A[S][H] + 128u + 1u) & ~1u) : 0u;
             if (tiled_SH[S][H] && piped_SH[S][H]) {
@@ -1769,12 +1804,14 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 e++;
                 for (uint32_t t0 = 0; t0 < T; t0 += tr) {
                     const uint32_t nt = T - t0 < tr ? T - t0 : tr;
+                    mark_st = st;
                     PSK_HIP(mark("pipe_front", S, H, off_SH[S][H], cnt, nt, y_len, r_len));
                     PSK_HIP(psk::launch_tile_front(S, class_H(H), h->d_plans[slot], l, ch0, cnt, nt, h->d_state, h->d_ring, h->lim.ring_cap, r_len,
                                                    h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, t0, st));
                     PSK_HIP(hipEventRecord(h->pipe_ev[e], st));
                     PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
                     e++;
+                    mark_st = h->pipe_st[0];
                     PSK_HIP(mark("pipe_fit", S, H, off_SH[S][H], cnt, nt, y_pipe, 0));
                     PSK_HIP(psk::launch_tile_fit_range(h->d_plans[slot], l, ch0, cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                                        h->lim.fit_cap, y_pipe, h->d_tiles, h->d_traw, h->d_ts, h->d_test, carry, carry_y, t0, nt,
@@ -1782,12 +1819,14 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                     PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[0]));
                     PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
                     e++;
+                    mark_st = h->pipe_st[1];
                     PSK_HIP(mark("pipe_back", S, H, off_SH[S][H], cnt, nt, y_pipe, 0));
                     PSK_HIP(psk::launch_tile_back(h->d_plans[slot], l, ch0, cnt, nt, h->d_state, h->d_tiles, h->d_ts, h->d_test, t0, 1u,
                                                   h->pipe_st[1]));
                 }
                 PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[1]));  // (behind the last fit too: the last back waited for it)
                 PSK_HIP(hipStreamWaitEvent(st, h->pipe_ev[e], 0));
+                mark_st = st;
             } else if (tiled_SH[S][H]) {
                 // (a call these cannot carry comes out with guard 1 and nothing committed: the launches below redo it)
                 PSK_HIP(mark("tile_front", S, H, off_SH[S][H], res.cnt_SH[S][H], tiles_max_SH[S][H], y_len, r_len));
@@ -1820,6 +1859,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 else if (H == kClassCs8)
                     PSK_HIP(psk::launch_fast_cs8(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
                                                  h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
+                else if (H == kClassCf16)
+                    PSK_HIP(psk::launch_fast_cf16(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
+                                                  h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
                 else
                     PSK_HIP(psk::launch_fast(S, class_H(H), exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
                                              h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
@@ -1830,10 +1872,14 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             else if (deferred && H == kClassCs8)
                 PSK_HIP(psk::launch_seq_cs8(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+            else if (deferred && H == kClassCf16)
+                PSK_HIP(psk::launch_seq_cf16(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
+                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
             else if (deferred)
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring, h->lim.ring_cap,
                                         h->d_yv, h->lim.fit_cap, st));
         }
+        mark_st = stream;
         if (deferred) {
             for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
                 if (!h->slot_aux_ev[slot][a])
@@ -1851,10 +1897,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             if (any_seq || any_emit)
                 PSK_HIP(mark("seq (reference order)", 0, 0, ~0u, nch, 0, 0, 0));
-            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_in_place8 && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
+            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_in_place8 && !n_in_placeh && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], nullptr, ch0, nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
-            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_in_place8 || n_wide_seq)) {  // (CS16 / CS8 read in place, wide symbols: each build on its own channels)
+            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_in_place8 || n_in_placeh || n_wide_seq)) {  // (CS16 / CS8 / CF16 read in place, wide symbols: each build on its own channels)
                 const uint32_t *const d_seq = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) +
                                                                                  slot_seq_offset(nch));
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, n_seq_narrow, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
@@ -1863,6 +1909,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                                              h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
                 PSK_HIP(psk::launch_seq_cs8(h->d_plans[slot], d_seq + n_seq_narrow + n_in_place, ch0, n_in_place8, h->d_state, h->d_ring,
                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
+                PSK_HIP(psk::launch_seq_cf16(h->d_plans[slot], d_seq + n_seq_narrow + n_in_place + n_in_place8, ch0, n_in_placeh, h->d_state,
+                                             h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
                 if (n_wide_seq)
                     PSK_HIP(mark("seq_wide (reference order, samplesPerBaud > 1024)", (int)wide_seq_S, 0, ~0u, 0, 0, 0, 0));
                 PSK_HIP(psk::launch_seq_wide(h->d_plans[slot], d_seq + (nch - n_wide_seq), ch0, n_wide_seq, h->d_state, h->d_ring,
@@ -2169,7 +2217,8 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
     // the refusals of this entry, before anything is planned: a stride of 0, an extent that does not fit 64 bits, a strided packet
     // that does not start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
     auto known = [](const psk_soft_packet_t &k) {
-        return k.format == PSK_SOFT_FORMAT_CF32 || k.format == PSK_SOFT_FORMAT_CS16 || k.format == PSK_SOFT_FORMAT_CS8;
+        return k.format == PSK_SOFT_FORMAT_CF32 || k.format == PSK_SOFT_FORMAT_CS16 || k.format == PSK_SOFT_FORMAT_CS8 ||
+               k.format == PSK_SOFT_FORMAT_CF16;
     };
     // (a strided packet the call reads: present, complex data, at least one sample)
     auto gathered = [&](uint32_t i) {
@@ -2205,7 +2254,7 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
             continue;
         if (reinterpret_cast<uintptr_t>(k.data) % sb)
             return fail(PSK_SOFT_ERR_INVALID_ARG,
-                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2), soft 8, bits 4, phase 4, sampleIndex 4");
+                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
         n_gather++;
     }
     // (a control-plane-only handle plans and counts: lengths and formats are all it looks at)
@@ -2477,7 +2526,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
             return fail(PSK_SOFT_ERR_CAPACITY, "psk_soft_process_host: output buffer too small");
         // every channel's rows start on a cache line: rows that straddle lines cost 6-8 % of the
         // kernel's streaming rate (tools/micro/placement_probe.hip)
-        need[i].in = pkts[i].present ? align_up(elem_bytes(pkts[i]) * (pkts[i].n_floats & ~1ull), 128) : 0;  // (CS16 / CS8 staged as such)
+        need[i].in = pkts[i].present ? align_up(elem_bytes(pkts[i]) * (pkts[i].n_floats & ~1ull), 128) : 0;  // (CS16 / CS8 / CF16 staged as such)
         need[i].soft = align_up(sizeof(float) * 2 * o.n_symbols, 128);
         need[i].phase = align_up(sizeof(float) * o.n_symbols, 128);
         need[i].bits = align_up(sizeof(int16_t) * o.n_bits, 128);

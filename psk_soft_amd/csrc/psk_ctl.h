@@ -169,7 +169,8 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
         out.ret = PSK_SOFT_NOOP;
         return PSK_SOFT_OK;
     }
-    if (pkt.format != PSK_SOFT_FORMAT_CF32 && pkt.format != PSK_SOFT_FORMAT_CS16 && pkt.format != PSK_SOFT_FORMAT_CS8)
+    if (pkt.format != PSK_SOFT_FORMAT_CF32 && pkt.format != PSK_SOFT_FORMAT_CS16 && pkt.format != PSK_SOFT_FORMAT_CS8 &&
+        pkt.format != PSK_SOFT_FORMAT_CF16)
         return PSK_SOFT_ERR_INVALID_ARG;  // (the only status plan_call returns it for)
     if (pkt.inputQueueFlushed && !cont) {  // :353-357
         out.n_warn++;
@@ -314,7 +315,10 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
     plan.lf_len0 = (uint32_t)c.lf_len;
     plan.lf_count0 = (uint32_t)c.lf_count;
     plan.lf_xdelta = c.lf_xdelta;
-    plan.lf_flags = pkt.format == PSK_SOFT_FORMAT_CS16 ? (uint32_t)PLAN_CS16 : pkt.format == PSK_SOFT_FORMAT_CS8 ? (uint32_t)PLAN_CS8 : 0u;
+    plan.lf_flags = pkt.format == PSK_SOFT_FORMAT_CS16   ? (uint32_t)PLAN_CS16
+                    : pkt.format == PSK_SOFT_FORMAT_CS8  ? (uint32_t)PLAN_CS8
+                    : pkt.format == PSK_SOFT_FORMAT_CF16 ? (uint32_t)PLAN_CF16
+                                                         : 0u;
     plan.n_out = n_out;
     if (plan.mode == PLAN_FAST && n_out && any_front)
         plan.lf_flags |= PLAN_ANYFRONT;

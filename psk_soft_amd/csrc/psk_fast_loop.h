@@ -287,6 +287,21 @@ PSK_DEV void load_block(const XView &X, long long cblk, uint32_t A, long long ta
             x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
         }
         return;
+#elif PSK_INST_FMT == 4
+        // (complex binary16: CS16's geometry and alignment -- S 8-byte loads of two samples each at 4-byte alignment -- widened
+        // as they arrive)
+        typedef uint32_t u2g __attribute__((ext_vector_type(2), aligned(4)));
+        const typename MemPtr<packet_global(S), const u2g>::type q =
+            (typename MemPtr<packet_global(S), const u2g>::type)(X.in + ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0)) +
+            (uint32_t)lane * (uint32_t)S;
+#pragma unroll
+        for (int k = 0; k < S; k++) {
+            const u2g t = q[k];
+            const f2g a = cf16_f2(t.x), b = cf16_f2(t.y);
+            x[(2 * k) / S][(2 * k) % S] = make_float2(a.x, a.y);
+            x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
+        }
+        return;
 #else
         const f2g *base = X.in + ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0);
         const typename F4Ptr<packet_global(S)>::type q =

@@ -40,7 +40,7 @@ constexpr uint32_t kGatherTile = 64;  // the tile kernel moves 64 columns x 64 f
 // seven eighths of its lanes idle.
 constexpr uint32_t kGatherMinGroup = 8;
 
-// bytes: 2 (CS8), 4 (CS16) or 8 (CF32) per complex sample.  Descriptors in device memory.
+// bytes: 2 (CS8), 4 (CS16, CF16) or 8 (CF32) per complex sample.  Descriptors in device memory.
 hipError_t launch_gather_tiles(int bytes, const GatherGroup *groups, uint32_t n_groups, const GatherChan *chans, uint64_t n_tiles,
                                hipStream_t stream);
 hipError_t launch_gather_singles(int bytes, const GatherSingle *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);

@@ -36,6 +36,10 @@
 #if PSK_INST_CS8
 #define psk psk_cs8
 #endif
+// -DPSK_INST_CF16=1 (Makefile: psk_seq_cf16.o): the same for complex binary16 packets, in namespace psk_cf16, exported as launch_seq_cf16
+#if PSK_INST_CF16
+#define psk psk_cf16
+#endif
 // -DPSK_SEQ_WIDE=1 (Makefile: psk_seq_wide.o): the reference-order kernel alone for samplesPerBaud > kSeqMaxS, in namespace psk_seqw,
 // exported as launch_seq_wide: symbolEnergy[] lives in a row of device memory per channel of the launch (psk_capi.cpp sizes the
 // rows by the launch's widest channel), and the loops over it are spread over the wave's lanes -- element k always in lane
@@ -428,7 +432,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
 
 }  // namespace psk
 
-#if !PSK_INST_CS16 && !PSK_INST_CS8 && !PSK_SEQ_WIDE
+#if !PSK_INST_CS16 && !PSK_INST_CS8 && !PSK_INST_CF16 && !PSK_SEQ_WIDE
 // ---------------------------------------------------------------------------------
 // launchers (called from psk_capi.cpp through plain C++ declarations).  Every (samplesPerBaud,
 // history depth, screened / exact) instantiation of the wave-scan kernel is its own translation
@@ -649,6 +653,17 @@ hipError_t launch_seq_cs8(const void *plans, const uint32_t *list, uint32_t ch0,
 {
     return psk_cs8::launch_seq(static_cast<const psk_cs8::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cs8::ChanState *>(states),
                                rings, ring_cap, yvs, fit_cap, stream);
+}
+}  // namespace psk
+#endif
+#if PSK_INST_CF16
+#undef psk
+namespace psk {
+hipError_t launch_seq_cf16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
+{
+    return psk_cf16::launch_seq(static_cast<const psk_cf16::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cf16::ChanState *>(states),
+                                rings, ring_cap, yvs, fit_cap, stream);
 }
 }  // namespace psk
 #endif

@@ -55,16 +55,21 @@ enum LfFlags : uint32_t {
     // the packet is complex int8 (PSK_SOFT_FORMAT_CS8): the same two flags for it (psk_cs8.hip, the PSK_INST_CS8 builds)
     PLAN_CS8 = 1024u,
     PLAN_CS8_IN_PLACE = 2048u,
+    // the packet is complex binary16 (PSK_SOFT_FORMAT_CF16): the same two flags for it (psk_cf16.hip, the PSK_INST_CF16 builds)
+    PLAN_CF16 = 4096u,
+    PLAN_CF16_IN_PLACE = 8192u,
 };
 
 
 constexpr uint32_t kResyncCount = 1048576u;  // cpp/psk_soft.cpp:51, 582
 
-// One CS16 or CS8 packet for the conversion pre-pass (psk_cs16.hip, psk_cs8.hip): n complex samples at src become n float2 at dst.
+// One CS16, CS8 or CF16 packet for the conversion pre-pass (psk_cs16.hip, psk_cs8.hip, psk_cf16.hip): n complex samples at src become
+// n float2 at dst.
 // They sit behind the compact channel lists in the upload slot of the call, so that they travel with the plans in one copy.
 struct CvtDesc {
     const uint32_t *src;  // I in the low half, Q in the high half (little-endian int16 pairs); 4-byte aligned -- for a CS8 packet
-                          // the int8 pairs, 2-byte aligned (psk_cs8.hip reads them as uint16)
+                          // the int8 pairs, 2-byte aligned (psk_cs8.hip reads them as uint16), for a CF16 packet binary16 pairs
+                          // laid out like the int16 ones
     float *dst;           // interleaved I,Q floats; 128-byte aligned, in the handle's conversion scratch
     uint64_t n;
 };

@@ -236,18 +236,24 @@ PSK_DEV void store_s4u(PSK_GLOBAL int16_t *p, s4u v) { PSK_ST((PSK_GLOBAL s4u *)
 // The packet's sample type is a property of the translation unit (PSK_INST_FMT, a PSK_SOFT_FORMAT_* value): PSK_INST_CS16=1
 // builds (psk_fast_inst.hip, psk_kernels.hip compiled a second time, Makefile) read complex int16 packets (PSK_SOFT_FORMAT_CS16)
 // straight from the caller's buffer, one 32-bit word per sample, I in the low half; PSK_INST_CS8=1 builds read complex int8
-// packets (PSK_SOFT_FORMAT_CS8), one 16-bit word per sample, I in the low byte; every other build reads float2.  The carried
-// samples (the ring) are float2 in all of them.
+// packets (PSK_SOFT_FORMAT_CS8), one 16-bit word per sample, I in the low byte; PSK_INST_CF16=1 builds read complex binary16
+// packets (PSK_SOFT_FORMAT_CF16), one 32-bit word per sample like CS16, I in the low half; every other build reads float2.  The
+// carried samples (the ring) are float2 in all of them.
 #ifndef PSK_INST_CS16
 #define PSK_INST_CS16 0
 #endif
 #ifndef PSK_INST_CS8
 #define PSK_INST_CS8 0
 #endif
-#define PSK_INST_FMT (PSK_INST_CS8 ? 3 : PSK_INST_CS16 ? 1 : 0)
+#ifndef PSK_INST_CF16
+#define PSK_INST_CF16 0
+#endif
+#define PSK_INST_FMT (PSK_INST_CF16 ? 4 : PSK_INST_CS8 ? 3 : PSK_INST_CS16 ? 1 : 0)
 #if PSK_INST_FMT == 3
 typedef uint16_t pkt_t;
 #elif PSK_INST_FMT == 1
+typedef uint32_t pkt_t;
+#elif PSK_INST_FMT == 4
 typedef uint32_t pkt_t;
 #else
 typedef f2g pkt_t;
@@ -270,6 +276,16 @@ PSK_DEV f2g cs8_f2(uint32_t v)
     r.y = (float)(int32_t)(int8_t)(uint8_t)(v >> (8 * B + 8));
     return r;
 }
+// a binary16 pair -> float2: v_cvt_f32_f16 of the low half and of the high half (sub-dword select) -- the IEEE widening, exact
+// for every finite half and the infinities; half subnormals become normal floats (the 16-bit denormal mode of a kernel is never
+// flush), a quiet NaN keeps its sign and its payload, 13 bits further up
+PSK_DEV f2g cf16_f2(uint32_t v)
+{
+    f2g r;
+    r.x = (float)__builtin_bit_cast(_Float16, (uint16_t)(v & 0xffffu));
+    r.y = (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16));
+    return r;
+}
 struct XView {
     const f2g *ring;
     const pkt_t *in;
@@ -283,6 +299,8 @@ PSK_DEV float2 x_at(const XView &X, uint64_t j)
     const f2g a = X.ring[r ? j : 0];
 #if PSK_INST_FMT == 3
     const f2g b = cs8_f2<0>(X.in[r ? 0 : j - X.L0]);  // (a 2-byte load: CS8 packets are 2-byte aligned)
+#elif PSK_INST_FMT == 4
+    const f2g b = cf16_f2(X.in[r ? 0 : j - X.L0]);
 #else
     const f2g b = cs16_f2(X.in[r ? 0 : j - X.L0]);
 #endif
@@ -302,6 +320,8 @@ PSK_DEV f2g x_load(const XView &X, uint64_t j)
     const pkt_t b = *mem_ptr<packet_global(S)>(X.in + (r ? 0 : j - X.L0));
 #if PSK_INST_FMT == 3
     return r ? a : cs8_f2<0>(b);
+#elif PSK_INST_FMT == 4
+    return r ? a : cf16_f2(b);
 #else
     return r ? a : cs16_f2(b);
 #endif

@@ -15,9 +15,9 @@ LIB_PATH = os.path.join(_HERE, "libpsk_soft_hip.so")
 DEVICE_NONE = -1
 OK = 0
 NOOP, NORMAL = 0, 1
-# Packet.format: interleaved float32 I/Q, interleaved int16 I/Q (sc16) or interleaved int8 I/Q (sc8); n_floats counts the
-# elements of the format
-FORMAT_CF32, FORMAT_CS16, FORMAT_CS8 = 0, 1, 3
+# Packet.format: interleaved float32 I/Q, interleaved int16 I/Q (sc16), interleaved int8 I/Q (sc8) or interleaved float16 I/Q
+# (cf16: torch.complex32 is this layout); n_floats counts the elements of the format
+FORMAT_CF32, FORMAT_CS16, FORMAT_CS8, FORMAT_CF16 = 0, 1, 3, 4
 
 STATUS_NAMES = {
     0: "PSK_SOFT_OK",
@@ -60,7 +60,7 @@ class Packet(ctypes.Structure):
         ("sriChanged", ctypes.c_uint8),
         ("inputQueueFlushed", ctypes.c_uint8),
         ("present", ctypes.c_uint8),
-        ("format", ctypes.c_uint8),  # FORMAT_CF32 / FORMAT_CS16 / FORMAT_CS8
+        ("format", ctypes.c_uint8),  # FORMAT_CF32 / FORMAT_CS16 / FORMAT_CS8 / FORMAT_CF16
     ]
 
 
@@ -253,7 +253,7 @@ def host_free(arr):
     load().psk_soft_host_free(ctypes.c_void_p(arr.ctypes.data))
 
 
-FORMAT_SAMPLE_BYTES = {FORMAT_CF32: 8, FORMAT_CS16: 4, FORMAT_CS8: 2}
+FORMAT_SAMPLE_BYTES = {FORMAT_CF32: 8, FORMAT_CS16: 4, FORMAT_CS8: 2, FORMAT_CF16: 4}
 
 
 def frame_major_packets(base, frames, width, first_column, n_channels, fmt=FORMAT_CF32, xdelta=1.0, sriChanged=False):
@@ -383,8 +383,8 @@ class Handle:
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with
-        data (interleaved I/Q: an int16 array is handed over as it is, FORMAT_CS16, an int8 array too, FORMAT_CS8, anything
-        else as float32), xdelta,
+        data (interleaved I/Q: an int16 array is handed over as it is, FORMAT_CS16, an int8 array too, FORMAT_CS8, a float16
+        array too, FORMAT_CF16, anything else as float32), xdelta,
         and optional mode / sriChanged / inputQueueFlushed.  Returns one dict per channel with the four output streams."""
         n = len(packets)
         pk = (Packet * n)()
@@ -397,8 +397,10 @@ class Handle:
                 bufs.append(None)
                 continue
             dt = p["data"].dtype if isinstance(p["data"], np.ndarray) else None
-            fmt = FORMAT_CS16 if dt == np.int16 else FORMAT_CS8 if dt == np.int8 else FORMAT_CF32
-            data = np.ascontiguousarray(p["data"], dtype={FORMAT_CS16: np.int16, FORMAT_CS8: np.int8}.get(fmt, np.float32))
+            fmt = FORMAT_CS16 if dt == np.int16 else FORMAT_CS8 if dt == np.int8 else FORMAT_CF16 if dt == np.float16 else FORMAT_CF32
+            data = np.ascontiguousarray(
+                p["data"], dtype={FORMAT_CS16: np.int16, FORMAT_CS8: np.int8, FORMAT_CF16: np.float16}.get(fmt, np.float32)
+            )
             keep.append(data)
             pk[i].data = data.ctypes.data
             pk[i].n_floats = data.size

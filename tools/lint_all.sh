@@ -30,6 +30,9 @@ others psk_kernels@cs16 -DPSK_INST_CS16=1; others psk_cs16
 # the CS8 builds (PSK_INST_CS8=1): the same classes; the reference-order kernel; the conversion pre-pass (psk_cs8.hip)
 for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cs8_S${s}_H1_E$e -DPSK_INST_CS8=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
 others psk_kernels@cs8 -DPSK_INST_CS8=1; others psk_cs8
+# the CF16 builds (PSK_INST_CF16=1): the same classes; the reference-order kernel; the conversion pre-pass (psk_cf16.hip)
+for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cf16_S${s}_H1_E$e -DPSK_INST_CF16=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
+others psk_kernels@cf16 -DPSK_INST_CF16=1; others psk_cf16
 # wide symbols (samplesPerBaud > 1024): the chunk and pick kernels (psk_wide.hip), the reference-order kernel's PSK_SEQ_WIDE build
 others psk_wide; others psk_kernels@wide -DPSK_SEQ_WIDE=1
 # the reduction pass of PSK_SOFT_OPT_QUALITY (psk_quality.hip): fold and join
