@@ -34,29 +34,15 @@ hipError_t launch_fast(int S, int H, int exact, const ChanPlan *plans, const uin
 hipError_t launch_seq(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
                       uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
 hipError_t launch_read_probe(const void *src, uint64_t bytes, float *sink, hipStream_t stream);
-// complex int16 packets (psk_cs16.hip): the conversion pre-pass
-hipError_t launch_cs16_convert(const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
+// complex int16, complex int8 and complex binary16 packets (psk_pkt.hip; fmt: the PSK_SOFT_FORMAT_* value): the conversion pre-pass
+hipError_t launch_convert(int fmt, const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
 // ... and the wave-scan and reference-order kernels that read them in place (psk_fast_inst.hip / psk_kernels.hip built with
-// PSK_INST_CS16=1): numAvg <= 128, samplesPerBaud 2 .. 16, screened and exact tier
-bool fast_cs16_has(int S);
-hipError_t launch_fast_cs16(int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
-                            float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
-hipError_t launch_seq_cs16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
-                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
-// complex int8 packets (psk_cs8.hip): the same four entry points, for the builds with PSK_INST_CS8=1
-hipError_t launch_cs8_convert(const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
-bool fast_cs8_has(int S);
-hipError_t launch_fast_cs8(int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
+// PSK_INST_PKT): numAvg <= 128, samplesPerBaud 2 .. 16, screened and exact tier
+bool fast_pkt_has(int fmt, int S);
+hipError_t launch_fast_pkt(int fmt, int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
                            float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
-hipError_t launch_seq_cs8(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+hipError_t launch_seq_pkt(int fmt, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
-// complex binary16 packets (psk_cf16.hip): the same four entry points, for the builds with PSK_INST_CF16=1
-hipError_t launch_cf16_convert(const CvtDesc *desc, uint32_t n_desc, uint64_t max_n, hipStream_t stream);
-bool fast_cf16_has(int S);
-hipError_t launch_fast_cf16(int S, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
-                            float2 *rings, uint32_t ring_cap, float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream);
-hipError_t launch_seq_cf16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
-                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream);
 // time-tiled kernels (psk_tile.hip)
 bool tile_front_has(int S, int H);
 hipError_t launch_tile_front(int S, int H, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles,
@@ -123,10 +109,8 @@ constexpr int kGatherDescSlots = 4;  // strided calls whose gather descriptors m
 // bytes of a packet's element
 inline size_t elem_bytes(const psk_soft_packet_t &k)
 {
-    return k.format == PSK_SOFT_FORMAT_CS16   ? sizeof(int16_t)
-           : k.format == PSK_SOFT_FORMAT_CS8  ? sizeof(int8_t)
-           : k.format == PSK_SOFT_FORMAT_CF16 ? sizeof(uint16_t)
-                                              : sizeof(float);
+    const psk::PktFormat *const f = psk::pkt_format(k.format);
+    return f ? f->elem_bytes : sizeof(float);
 }
 // bytes of the upload slot of a call of n channels: header, plans, compact lists, CS16 / CS8 / CF16 conversion descriptors (psk_plan.h)
 inline size_t slot_cvt_offset(size_t n)
@@ -267,7 +251,7 @@ inline size_t region_bits(size_t in_cap) { return in_cap + in_cap + in_cap / 2; 
 inline size_t region_sidx(size_t in_cap) { return in_cap + in_cap + in_cap / 2 + in_cap; }
 inline size_t region_total(size_t in_cap) { return in_cap + in_cap + in_cap / 2 + in_cap + in_cap / 4; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-// Where the CS16 packets of a call are converted to (psk_cs16.hip): float2 rows, 128-byte aligned, grown on demand.  One buffer
+// Where the CS16 packets of a call are converted to (psk_pkt.hip): float2 rows, 128-byte aligned, grown on demand.  One buffer
 // per stream that calls with CS16 packets -- the chunks of psk_soft_process_host run on streams of their own and would
 // otherwise wait for each other --; a buffer taken over from another stream is used behind the event that ends its last call.
 struct CvtScratch {
@@ -319,12 +303,24 @@ struct QualitySlot {
 constexpr uint32_t kFastFitMax = 32768 - 128;
 constexpr uint32_t kDeepFit = 2048 - 128;
 // second index of the per-class tables: history blocks (+ 8: deep fit window); 3: one block, CS16 packets read in place; 5: one
-// block, CS8 packets read in place; 6: one block, CF16 packets read in place
+// block, CS8 packets read in place; 6: one block, CF16 packets read in place (psk_ctl.h: PktFormat::cls)
 const int kClassH[] = {1, 3, 5, 6, 2, 4, 8, 9, 10, 12, 16};
-constexpr int kClassCs16 = 3;
-constexpr int kClassCs8 = 5;
-constexpr int kClassCf16 = 6;
-inline int class_H(int Hi) { return Hi == kClassCs16 || Hi == kClassCs8 || Hi == kClassCf16 ? 1 : Hi > 8 ? Hi - 8 : Hi; }
+// the format whose packets class Hi reads in place; nullptr: a class of the float kernels
+inline const psk::PktFormat *class_pkt(int Hi)
+{
+    for (const psk::PktFormat &f : psk::kPktFormats)
+        if (f.cls == Hi)
+            return &f;
+    return nullptr;
+}
+inline int class_H(int Hi) { return class_pkt(Hi) ? 1 : Hi > 8 ? Hi - 8 : Hi; }
+constexpr uint32_t in_place_flags()
+{
+    uint32_t m = 0;
+    for (const psk::PktFormat &f : psk::kPktFormats) m |= f.in_place;
+    return m;
+}
+constexpr uint32_t kInPlaceFlags = in_place_flags();
 constexpr int kNumClassH = (int)(sizeof(kClassH) / sizeof(kClassH[0]));
 // time-tiled kernels, automatic choice (measured, tools/tiled_sweep2.sh: QPSK, samplesPerBaud 8): a class of at most 64
 // channels whose longest call has at least 16 blocks of 128 symbols, or of at most 512 channels and 192 blocks (at 128
@@ -843,28 +839,19 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                                  (h->opt_ties_in_place ? 0u : (uint32_t)psk::PLAN_TIES_HANDOVER);
     const psk::Limits lim = h->lim;
     // what a planned channel asks of the launches (`mult` channels with this very plan)
-    // CS16 channels of the window classes with in-place instantiations (psk_fast_inst.hip, PSK_INST_CS16): their own class, no
-    // conversion.  (What would go through the time-tiled kernels is moved back to the float class and the pre-pass below.)
-    auto cs16_in_place = [&](const psk::ChanPlan &p) {
-        return (p.lf_flags & psk::PLAN_CS16) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
-               p.lf_n <= kDeepFit && psk::fast_cs16_has((int)p.S);
-    };
-    // (CS8: the same classes, PSK_INST_CS8, a class of their own too)
-    auto cs8_in_place = [&](const psk::ChanPlan &p) {
-        return (p.lf_flags & psk::PLAN_CS8) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
-               p.lf_n <= kDeepFit && psk::fast_cs8_has((int)p.S);
-    };
-    // (CF16: the same classes, PSK_INST_CF16, a class of their own too)
-    auto cf16_in_place = [&](const psk::ChanPlan &p) {
-        return (p.lf_flags & psk::PLAN_CF16) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
-               p.lf_n <= kDeepFit && psk::fast_cf16_has((int)p.S);
+    // CS16, CS8 and CF16 channels of the window classes with in-place instantiations (psk_fast_inst.hip, PSK_INST_PKT): a class of
+    // their own per format, no conversion.  (What would go through the time-tiled kernels is moved back to the float class and the
+    // pre-pass below.)
+    auto in_place = [&](const psk::ChanPlan &p, const psk::PktFormat &f) {
+        return (p.lf_flags & f.flag) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
+               p.lf_n <= kDeepFit && psk::fast_pkt_has((int)f.id, (int)p.S);
     };
     // the class of a planned channel that emits on the wave-scan kernels
     auto class_of = [&](const psk::ChanPlan &p) {
-        return (p.lf_flags & psk::PLAN_CS16_IN_PLACE)   ? kClassCs16
-               : (p.lf_flags & psk::PLAN_CS8_IN_PLACE)  ? kClassCs8
-               : (p.lf_flags & psk::PLAN_CF16_IN_PLACE) ? kClassCf16
-                                                        : psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+        for (const psk::PktFormat &f : psk::kPktFormats)
+            if (p.lf_flags & f.in_place)
+                return f.cls;
+        return psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
     };
     auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
         r.any = true;
@@ -889,12 +876,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (p.S > r.max_S_any) r.max_S_any = p.S;
             } else if (p.n_out) {
                 r.any_emit = true;
-                if (cs16_in_place(p))
-                    p.lf_flags |= psk::PLAN_CS16_IN_PLACE;
-                if (cs8_in_place(p))
-                    p.lf_flags |= psk::PLAN_CS8_IN_PLACE;
-                if (cf16_in_place(p))
-                    p.lf_flags |= psk::PLAN_CF16_IN_PLACE;
+                for (const psk::PktFormat &f : psk::kPktFormats)
+                    if (in_place(p, f))
+                        p.lf_flags |= f.in_place;
                 const int Hh = class_of(p);
                 r.need_SH[p.S][Hh] = true;
                 r.cnt_SH[p.S][Hh] += mult;
@@ -918,7 +902,10 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     uint32_t *const handed_over = dry ? nullptr : psk::plan_header(h->d_plans[slot]);  // (psk_plan.h)
     // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 and binary16 pairs, 2-byte aligned int8 pairs)
     auto misaligned = [&](const psk::ChanPlan &p) {
-        const uintptr_t in_mask = (p.lf_flags & (psk::PLAN_CS16 | psk::PLAN_CF16)) ? 3u : (p.lf_flags & psk::PLAN_CS8) ? 1u : 7u;
+        uintptr_t in_mask = 7u;
+        for (const psk::PktFormat &f : psk::kPktFormats)
+            if (p.lf_flags & f.flag)
+                in_mask = f.align_mask;
         return !dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & in_mask) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
                         ((uintptr_t)p.phase & 3u) || ((uintptr_t)p.sidx & 3u));
     };
@@ -1095,16 +1082,18 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (h->slot_aux_used[k][a])
                     PSK_HIP(hipStreamWaitEvent(stream, h->slot_aux_ev[k][a], 0));
         }
-    // CS16, CS8 and CF16 channels read in place have classes of their own (kClassCs16, kClassCs8, kClassCf16), which have no
+    // CS16, CS8 and CF16 channels read in place have classes of their own (PktFormat::cls), which have no
     // time-tiled kernels: where the float class would go through those (the same choice as below, on the four classes together),
     // their channels go back to the float class and to the conversion pre-pass
-    constexpr uint32_t kInPlaceFlags = psk::PLAN_CS16_IN_PLACE | psk::PLAN_CS8_IN_PLACE | psk::PLAN_CF16_IN_PLACE;
     if (!stamped || (plans[0].lf_flags & kInPlaceFlags))
         for (int S = 2; S <= 16; S++) {
-            if ((!res.need_SH[S][kClassCs16] && !res.need_SH[S][kClassCs8] && !res.need_SH[S][kClassCf16]) || !h->opt_tiled || !psk::tile_front_has(S, 1))
+            bool need = false;
+            for (const psk::PktFormat &f : psk::kPktFormats) need = need || res.need_SH[S][f.cls];
+            if (!need || !h->opt_tiled || !psk::tile_front_has(S, 1))
                 continue;
             uint32_t cnt = res.cnt_SH[S][1], mb = res.max_blocks_SH[S][1], mn = res.max_n[S][1];
-            for (int Hc : {kClassCs16, kClassCs8, kClassCf16}) {
+            for (const psk::PktFormat &f : psk::kPktFormats) {
+                const int Hc = f.cls;
                 cnt += res.cnt_SH[S][Hc];
                 mb = res.max_blocks_SH[S][Hc] > mb ? res.max_blocks_SH[S][Hc] : mb;
                 mn = res.max_n[S][Hc] > mn ? res.max_n[S][Hc] : mn;
@@ -1120,7 +1109,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             res.cnt_SH[S][1] = cnt;
             res.max_blocks_SH[S][1] = mb;
             res.max_n[S][1] = mn;
-            for (int Hc : {kClassCs16, kClassCs8, kClassCf16}) {
+            for (const psk::PktFormat &f : psk::kPktFormats) {
+                const int Hc = f.cls;
                 res.max_A[S][1] = res.max_A[S][1] > res.max_A[S][Hc] ? res.max_A[S][1] : res.max_A[S][Hc];
                 res.blocks_SH[S][1] += res.blocks_SH[S][Hc];
                 res.need_SH[S][Hc] = false;
@@ -1237,7 +1227,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     for (int pass = 0; pass < (h->opt_tiled ? 2 : 0); pass++) {
         for (int S : kFastS)
             for (int H : kClassH) {
-                if (!res.need_SH[S][H] || H == kClassCs16 || H == kClassCs8 || H == kClassCf16 || !psk::tile_front_has(S, class_H(H)))
+                if (!res.need_SH[S][H] || class_pkt(H) || !psk::tile_front_has(S, class_H(H)))
                     continue;
                 // pipelined: the serial fit of a range under the front stage of the next (see kPipeMinChannels)
                 // (PSK_SOFT_PIPELINED=2, tests: wherever the kernels allow it, a few blocks to a range)
@@ -1428,32 +1418,29 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
         }
     }
-    // CS16, CS8 and CF16 packets (psk_cs16.hip, psk_cs8.hip, psk_cf16.hip): converted into float2 rows of the conversion scratch by one pre-pass per
+    // CS16, CS8 and CF16 packets (psk_pkt.hip): converted into float2 rows of the conversion scratch by one pre-pass per
     // format in front of the call's first kernel; their plans point at the rows from here on.  The descriptors travel behind the
-    // plans, in the same upload: the CS16 packets' first, then the CS8 packets', then the CF16 packets'.
-    auto cvt_flag = [](const psk::ChanPlan &p) -> uint32_t {  // (the format flag of a packet the pre-pass converts, else 0)
+    // plans, in the same upload: the CS16 packets' first, then the CS8 packets', then the CF16 packets' (the order of kPktFormats).
+    auto cvt_format = [](const psk::ChanPlan &p) -> int {  // (the row in kPktFormats of a packet the pre-pass converts, else -1)
         if (p.mode == psk::PLAN_SKIP || !p.n_in)
-            return 0u;
-        if ((p.lf_flags & psk::PLAN_CS16) && !(p.lf_flags & psk::PLAN_CS16_IN_PLACE))
-            return psk::PLAN_CS16;
-        if ((p.lf_flags & psk::PLAN_CS8) && !(p.lf_flags & psk::PLAN_CS8_IN_PLACE))
-            return psk::PLAN_CS8;
-        if ((p.lf_flags & psk::PLAN_CF16) && !(p.lf_flags & psk::PLAN_CF16_IN_PLACE))
-            return psk::PLAN_CF16;
-        return 0u;
+            return -1;
+        for (int f = 0; f < psk::kNumPktFormats; f++)
+            if ((p.lf_flags & psk::kPktFormats[f].flag) && !(p.lf_flags & psk::kPktFormats[f].in_place))
+                return f;
+        return -1;
     };
-    uint32_t n_cvt = 0, n_cvt16 = 0, n_cvt8 = 0;
-    uint64_t cvt_max_n16 = 0, cvt_max_n8 = 0, cvt_max_nh = 0;
+    uint32_t n_cvt = 0, n_cvt_f[psk::kNumPktFormats] = {};  // (per format: descriptors)
+    uint64_t cvt_max_n[psk::kNumPktFormats] = {};           // (... and the longest packet)
     CvtScratch *cv = nullptr;
     {
         size_t need = 0;
         for (uint32_t i = 0; i < nch; i++) {
             const psk::ChanPlan &p = plans[i];
-            if (const uint32_t f = cvt_flag(p)) {
+            const int f = cvt_format(p);
+            if (f >= 0) {
                 need += align_up(sizeof(float2) * p.n_in, 128);
                 n_cvt++;
-                n_cvt16 += f == psk::PLAN_CS16 ? 1u : 0u;
-                n_cvt8 += f == psk::PLAN_CS8 ? 1u : 0u;
+                n_cvt_f[f]++;
             }
         }
         if (n_cvt) {
@@ -1486,41 +1473,43 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             psk::CvtDesc *const desc =
                 reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_cvt_offset(nch));
             size_t off = 0;
-            uint32_t k16 = 0, k8 = n_cvt16, kh = n_cvt16 + n_cvt8;
+            uint32_t next[psk::kNumPktFormats] = {};  // (where each format's descriptors go on)
+            for (int f = 1; f < psk::kNumPktFormats; f++) next[f] = next[f - 1] + n_cvt_f[f - 1];
             for (uint32_t i = 0; i < nch; i++) {
                 psk::ChanPlan &p = plans[i];
-                const uint32_t f = cvt_flag(p);
-                if (!f)
+                const int f = cvt_format(p);
+                if (f < 0)
                     continue;
-                const uint32_t k = f == psk::PLAN_CS16 ? k16++ : f == psk::PLAN_CS8 ? k8++ : kh++;
+                const uint32_t k = next[f]++;
                 desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
                 desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
                 desc[k].n = p.n_in;
                 p.in = desc[k].dst;
                 off += align_up(sizeof(float2) * p.n_in, 128);
-                uint64_t &mx = f == psk::PLAN_CS16 ? cvt_max_n16 : f == psk::PLAN_CS8 ? cvt_max_n8 : cvt_max_nh;
-                mx = p.n_in > mx ? p.n_in : mx;
+                cvt_max_n[f] = p.n_in > cvt_max_n[f] ? p.n_in : cvt_max_n[f];
             }
         }
     }
     // the reference-order kernel's lists when CS16 / CS8 / CF16 channels are read in place: float-build channels first, then the
     // CS16 build's, then the CS8 build's, then the CF16 build's (and the wide symbols' last)
-    uint32_t n_in_place = 0, n_in_place8 = 0, n_in_placeh = 0;
-    for (uint32_t i = 0; i < nch; i++) {
-        n_in_place += (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE) ? 1u : 0u;
-        n_in_place8 += (plans[i].lf_flags & psk::PLAN_CS8_IN_PLACE) ? 1u : 0u;
-        n_in_placeh += (plans[i].lf_flags & psk::PLAN_CF16_IN_PLACE) ? 1u : 0u;
-    }
-    const uint32_t n_seq_narrow = nch - n_in_place - n_in_place8 - n_in_placeh - n_wide_seq;
-    if (n_in_place || n_in_place8 || n_in_placeh || n_wide_seq) {
+    uint32_t n_in_place = 0, n_in_place_f[psk::kNumPktFormats] = {};
+    for (uint32_t i = 0; i < nch; i++)
+        for (int f = 0; f < psk::kNumPktFormats; f++) n_in_place_f[f] += (plans[i].lf_flags & psk::kPktFormats[f].in_place) ? 1u : 0u;
+    for (const uint32_t n : n_in_place_f) n_in_place += n;
+    const uint32_t n_seq_narrow = nch - n_in_place - n_wide_seq;
+    if (n_in_place || n_wide_seq) {
         uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_seq_offset(nch));
-        uint32_t a = 0, b = n_seq_narrow, b8 = n_seq_narrow + n_in_place, bh = n_seq_narrow + n_in_place + n_in_place8, c = nch - n_wide_seq;
-        for (uint32_t i = 0; i < nch; i++)
-            seq[(plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) ? c++
-                : (plans[i].lf_flags & psk::PLAN_CS16_IN_PLACE)              ? b++
-                : (plans[i].lf_flags & psk::PLAN_CS8_IN_PLACE)               ? b8++
-                : (plans[i].lf_flags & psk::PLAN_CF16_IN_PLACE)              ? bh++
-                                                                             : a++] = i;
+        uint32_t a = 0, b[psk::kNumPktFormats] = {n_seq_narrow}, c = nch - n_wide_seq;
+        for (int f = 1; f < psk::kNumPktFormats; f++) b[f] = b[f - 1] + n_in_place_f[f - 1];
+        for (uint32_t i = 0; i < nch; i++) {
+            uint32_t *at = &a;
+            for (int f = 0; f < psk::kNumPktFormats; f++)
+                if (plans[i].lf_flags & psk::kPktFormats[f].in_place)
+                    at = &b[f];
+            if (plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS)
+                at = &c;
+            seq[(*at)++] = i;
+        }
     }
     // PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call
     // reads exist, what it leaves behind fits the rings, its place in the scratch of the time-tiled kernels lies inside it -- is
@@ -1564,7 +1553,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 why = "place in the wide-symbol scratch outside it";
             else if (p.S > kSeqMaxS && (p.S > wide_seq_S || !h->d_wide_symE || (size_t)n_wide_seq * wide_seq_S > h->wide_symE_cap))
                 why = "wide symbol without a row of symbolEnergy";
-            else if (cvt_flag(p) &&
+            else if (cvt_format(p) >= 0 &&
                      (!cv || (const char *)p.in < (const char *)cv->buf ||
                       (const char *)p.in + sizeof(float2) * p.n_in > (const char *)cv->buf + cv->cap))
                 why = "converted CS16 / CS8 / CF16 packet outside the conversion scratch";
@@ -1634,7 +1623,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
         hdr[0] = 0u;                       // channels handed over: counted by the kernels
         hdr[1] = res.any_seq ? 1u : 0u;    // channels planned for the reference-order kernel
     }
-    const size_t up_bytes = (n_in_place || n_in_place8 || n_in_placeh || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
+    const size_t up_bytes = (n_in_place || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
                             : n_cvt    ? slot_cvt_offset(nch) + sizeof(psk::CvtDesc) * n_cvt
                                        : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
     if (h->opt_up_stream) {
@@ -1682,25 +1671,13 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     // left out, which is wrong as soon as a call is handed over; what the two launches cost a small call is measured that way)
     static const bool diag_no_tail = std::getenv("PSK_SOFT_DIAG_NO_TAIL") && std::atoi(std::getenv("PSK_SOFT_DIAG_NO_TAIL")) != 0;
     auto enqueue = [&]() -> psk_soft_status {
-        if (n_cvt16) {
-            PSK_HIP(mark("cs16_convert", 0, 0, ~0u, 0, n_cvt16, 0, 0));
-            PSK_HIP(psk::launch_cs16_convert(
-                reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)),
-                n_cvt16, cvt_max_n16, stream));
-        }
-        if (n_cvt8) {
-            PSK_HIP(mark("cs8_convert", 0, 0, ~0u, 0, n_cvt8, 0, 0));
-            PSK_HIP(psk::launch_cs8_convert(
-                reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)) +
-                    n_cvt16,
-                n_cvt8, cvt_max_n8, stream));
-        }
-        if (n_cvt > n_cvt16 + n_cvt8) {
-            PSK_HIP(mark("cf16_convert", 0, 0, ~0u, 0, n_cvt - n_cvt16 - n_cvt8, 0, 0));
-            PSK_HIP(psk::launch_cf16_convert(
-                reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch)) +
-                    n_cvt16 + n_cvt8,
-                n_cvt - n_cvt16 - n_cvt8, cvt_max_nh, stream));
+        const psk::CvtDesc *d_desc =
+            reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch));
+        for (int f = 0; f < psk::kNumPktFormats; d_desc += n_cvt_f[f], f++) {
+            if (!n_cvt_f[f])
+                continue;
+            PSK_HIP(mark(psk::kPktFormats[f].convert, 0, 0, ~0u, 0, n_cvt_f[f], 0, 0));
+            PSK_HIP(psk::launch_convert((int)psk::kPktFormats[f].id, d_desc, n_cvt_f[f], cvt_max_n[f], stream));
         }
         if (any_quiet)
             PSK_HIP(mark("fast<0,1> (calls that emit nothing)", 0, 1, off_quiet, res.cnt_quiet, 0, ring_floats(res.max_n_quiet, 512u), 0));
@@ -1853,28 +1830,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 if (exact && diag_no_tail)
                     break;
                 PSK_HIP(mark(exact ? "fast (exact tier)" : "fast (screened tier)", S, H, off_SH[S][H], res.cnt_SH[S][H], 0, y_len, r_len));
-                if (H == kClassCs16)
-                    PSK_HIP(psk::launch_fast_cs16(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
-                                                  h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
-                else if (H == kClassCs8)
-                    PSK_HIP(psk::launch_fast_cs8(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
+                if (const psk::PktFormat *const f = class_pkt(H))
+                    PSK_HIP(psk::launch_fast_pkt((int)f->id, S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
                                                  h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
-                else if (H == kClassCf16)
-                    PSK_HIP(psk::launch_fast_cf16(S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
-                                                  h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
                 else
                     PSK_HIP(psk::launch_fast(S, class_H(H), exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
                                              h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
             }
-            if (deferred && H == kClassCs16)  // (the class's hand-overs are redone on its own stream, in front of its next call)
-                PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
-                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
-            else if (deferred && H == kClassCs8)
-                PSK_HIP(psk::launch_seq_cs8(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
-                                            h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
-            else if (deferred && H == kClassCf16)
-                PSK_HIP(psk::launch_seq_cf16(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
-                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+            if (deferred && class_pkt(H))  // (the class's hand-overs are redone on its own stream, in front of its next call)
+                PSK_HIP(psk::launch_seq_pkt((int)class_pkt(H)->id, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
+                                            h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
             else if (deferred)
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring, h->lim.ring_cap,
                                         h->d_yv, h->lim.fit_cap, st));
@@ -1897,20 +1862,18 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             if (any_seq || any_emit)
                 PSK_HIP(mark("seq (reference order)", 0, 0, ~0u, nch, 0, 0, 0));
-            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_in_place8 && !n_in_placeh && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
+            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], nullptr, ch0, nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
-            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_in_place8 || n_in_placeh || n_wide_seq)) {  // (CS16 / CS8 / CF16 read in place, wide symbols: each build on its own channels)
+            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_wide_seq)) {  // (CS16 / CS8 / CF16 read in place, wide symbols: each build on its own channels)
                 const uint32_t *const d_seq = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) +
                                                                                  slot_seq_offset(nch));
                 PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, n_seq_narrow, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
                                         h->lim.fit_cap, stream));
-                PSK_HIP(psk::launch_seq_cs16(h->d_plans[slot], d_seq + n_seq_narrow, ch0, n_in_place, h->d_state, h->d_ring,
-                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
-                PSK_HIP(psk::launch_seq_cs8(h->d_plans[slot], d_seq + n_seq_narrow + n_in_place, ch0, n_in_place8, h->d_state, h->d_ring,
-                                            h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
-                PSK_HIP(psk::launch_seq_cf16(h->d_plans[slot], d_seq + n_seq_narrow + n_in_place + n_in_place8, ch0, n_in_placeh, h->d_state,
-                                             h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
+                const uint32_t *d_seq_f = d_seq + n_seq_narrow;
+                for (int f = 0; f < psk::kNumPktFormats; d_seq_f += n_in_place_f[f], f++)
+                    PSK_HIP(psk::launch_seq_pkt((int)psk::kPktFormats[f].id, h->d_plans[slot], d_seq_f, ch0, n_in_place_f[f], h->d_state,
+                                                h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
                 if (n_wide_seq)
                     PSK_HIP(mark("seq_wide (reference order, samplesPerBaud > 1024)", (int)wide_seq_S, 0, ~0u, 0, 0, 0, 0));
                 PSK_HIP(psk::launch_seq_wide(h->d_plans[slot], d_seq + (nch - n_wide_seq), ch0, n_wide_seq, h->d_state, h->d_ring,
@@ -2216,10 +2179,7 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
     // the refusals of this entry, before anything is planned: a stride of 0, an extent that does not fit 64 bits, a strided packet
     // that does not start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
-    auto known = [](const psk_soft_packet_t &k) {
-        return k.format == PSK_SOFT_FORMAT_CF32 || k.format == PSK_SOFT_FORMAT_CS16 || k.format == PSK_SOFT_FORMAT_CS8 ||
-               k.format == PSK_SOFT_FORMAT_CF16;
-    };
+    auto known = [](const psk_soft_packet_t &k) { return psk::pkt_format_known(k.format); };
     // (a strided packet the call reads: present, complex data, at least one sample)
     auto gathered = [&](uint32_t i) {
         const psk_soft_packet_t &k = pkts[i];

@@ -19,6 +19,35 @@
 
 namespace psk {
 
+// The packet formats other than float2 (PSK_SOFT_FORMAT_CF32), one row each.  The order of the rows is the order of the conversion
+// descriptors behind the plans of a call and of the reference-order kernel's channel lists (psk_capi.cpp).
+struct PktFormat {
+    uint32_t id;          // PSK_SOFT_FORMAT_*
+    uint32_t elem_bytes;  // of one I or Q element
+    uint32_t align_mask;  // of the packet's address: one complex sample, a 32-bit word at the most
+    uint32_t flag;        // PLAN_*: the packet has this format
+    uint32_t in_place;    // PLAN_*_IN_PLACE: ... and is read in place by the format's builds of the kernels
+    int cls;              // window class of the channels read in place (psk_capi.cpp: kClassH)
+    const char *convert;  // the conversion pre-pass in the launch trace
+};
+constexpr PktFormat kPktFormats[] = {
+    {PSK_SOFT_FORMAT_CS16, 2u, 3u, PLAN_CS16, PLAN_CS16_IN_PLACE, 3, "cs16_convert"},
+    {PSK_SOFT_FORMAT_CS8, 1u, 1u, PLAN_CS8, PLAN_CS8_IN_PLACE, 5, "cs8_convert"},
+    {PSK_SOFT_FORMAT_CF16, 2u, 3u, PLAN_CF16, PLAN_CF16_IN_PLACE, 6, "cf16_convert"},
+};
+constexpr int kNumPktFormats = (int)(sizeof(kPktFormats) / sizeof(kPktFormats[0]));
+static_assert(PSK_PKT_ID_cs16 == PSK_SOFT_FORMAT_CS16 && PSK_PKT_ID_cs8 == PSK_SOFT_FORMAT_CS8 && PSK_PKT_ID_cf16 == PSK_SOFT_FORMAT_CF16,
+              "the format ids of the device builds (psk_plan.h) are the PSK_SOFT_FORMAT_* values");
+// the row of a PSK_SOFT_FORMAT_* value; nullptr: float2, or no format at all
+inline const PktFormat *pkt_format(uint32_t id)
+{
+    for (const PktFormat &f : kPktFormats)
+        if (f.id == id)
+            return &f;
+    return nullptr;
+}
+inline bool pkt_format_known(uint32_t id) { return id == PSK_SOFT_FORMAT_CF32 || pkt_format(id); }
+
 struct ChanCtl {
     // properties, defaults of cpp/psk_soft_base.cpp:96-148
     psk_soft_props_t props;
@@ -169,8 +198,7 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
         out.ret = PSK_SOFT_NOOP;
         return PSK_SOFT_OK;
     }
-    if (pkt.format != PSK_SOFT_FORMAT_CF32 && pkt.format != PSK_SOFT_FORMAT_CS16 && pkt.format != PSK_SOFT_FORMAT_CS8 &&
-        pkt.format != PSK_SOFT_FORMAT_CF16)
+    if (!pkt_format_known(pkt.format))
         return PSK_SOFT_ERR_INVALID_ARG;  // (the only status plan_call returns it for)
     if (pkt.inputQueueFlushed && !cont) {  // :353-357
         out.n_warn++;
@@ -315,10 +343,8 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
     plan.lf_len0 = (uint32_t)c.lf_len;
     plan.lf_count0 = (uint32_t)c.lf_count;
     plan.lf_xdelta = c.lf_xdelta;
-    plan.lf_flags = pkt.format == PSK_SOFT_FORMAT_CS16   ? (uint32_t)PLAN_CS16
-                    : pkt.format == PSK_SOFT_FORMAT_CS8  ? (uint32_t)PLAN_CS8
-                    : pkt.format == PSK_SOFT_FORMAT_CF16 ? (uint32_t)PLAN_CF16
-                                                         : 0u;
+    const PktFormat *const fmt = pkt_format(pkt.format);
+    plan.lf_flags = fmt ? fmt->flag : 0u;
     plan.n_out = n_out;
     if (plan.mode == PLAN_FAST && n_out && any_front)
         plan.lf_flags |= PLAN_ANYFRONT;

@@ -272,9 +272,9 @@ PSK_DEV void load_block(const XView &X, long long cblk, uint32_t A, long long ta
             x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
         }
         return;
-#elif PSK_INST_FMT == 1
-        // (complex int16: the lane's two symbols are 8*S bytes -- S 8-byte loads of two samples each, at the 4-byte alignment
-        // the ABI asks of CS16 packets, converted as they arrive)
+#elif PSK_INST_FMT != 0
+        // (complex int16 and complex binary16, one 32-bit word a sample: the lane's two symbols are 8*S bytes -- S 8-byte loads of
+        // two samples each, at the 4-byte alignment the ABI asks of such packets, converted as they arrive)
         typedef uint32_t u2g __attribute__((ext_vector_type(2), aligned(4)));
         const typename MemPtr<packet_global(S), const u2g>::type q =
             (typename MemPtr<packet_global(S), const u2g>::type)(X.in + ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0)) +
@@ -282,22 +282,7 @@ PSK_DEV void load_block(const XView &X, long long cblk, uint32_t A, long long ta
 #pragma unroll
         for (int k = 0; k < S; k++) {
             const u2g t = q[k];
-            const f2g a = cs16_f2(t.x), b = cs16_f2(t.y);
-            x[(2 * k) / S][(2 * k) % S] = make_float2(a.x, a.y);
-            x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
-        }
-        return;
-#elif PSK_INST_FMT == 4
-        // (complex binary16: CS16's geometry and alignment -- S 8-byte loads of two samples each at 4-byte alignment -- widened
-        // as they arrive)
-        typedef uint32_t u2g __attribute__((ext_vector_type(2), aligned(4)));
-        const typename MemPtr<packet_global(S), const u2g>::type q =
-            (typename MemPtr<packet_global(S), const u2g>::type)(X.in + ((uint64_t)tau_first * (uint64_t)S - (uint64_t)X.L0)) +
-            (uint32_t)lane * (uint32_t)S;
-#pragma unroll
-        for (int k = 0; k < S; k++) {
-            const u2g t = q[k];
-            const f2g a = cf16_f2(t.x), b = cf16_f2(t.y);
+            const f2g a = pkt_f2(t.x), b = pkt_f2(t.y);
             x[(2 * k) / S][(2 * k) % S] = make_float2(a.x, a.y);
             x[(2 * k + 1) / S][(2 * k + 1) % S] = make_float2(b.x, b.y);
         }

@@ -27,18 +27,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// -DPSK_INST_CS16=1 (Makefile: psk_seq_cs16.o): the reference-order kernel alone, reading complex int16 packets, in namespace
-// psk_cs16 (see psk_fast_inst.hip), exported as launch_seq_cs16 -- it redoes the calls the CS16 wave-scan kernels hand over
-#if PSK_INST_CS16
-#define psk psk_cs16
-#endif
-// -DPSK_INST_CS8=1 (Makefile: psk_seq_cs8.o): the same for complex int8 packets, in namespace psk_cs8, exported as launch_seq_cs8
-#if PSK_INST_CS8
-#define psk psk_cs8
-#endif
-// -DPSK_INST_CF16=1 (Makefile: psk_seq_cf16.o): the same for complex binary16 packets, in namespace psk_cf16, exported as launch_seq_cf16
-#if PSK_INST_CF16
-#define psk psk_cf16
+// -DPSK_INST_PKT=cs16 (cs8, cf16; Makefile: psk_seq_cs16.o ...): the reference-order kernel alone, reading complex int16 (complex
+// int8, complex binary16) packets, in namespace psk_cs16 (psk_cs8, psk_cf16; see psk_fast_inst.hip), exported as launch_seq_cs16
+// (launch_seq_cs8, launch_seq_cf16) -- it redoes the calls the wave-scan kernels of that format hand over
+#define PSK_PASTE_(a, b) a##b
+#define PSK_PASTE(a, b) PSK_PASTE_(a, b)
+#ifdef PSK_INST_PKT
+#define PSK_PKT_NS PSK_PASTE(psk_, PSK_INST_PKT)
+#define psk PSK_PKT_NS
 #endif
 // -DPSK_SEQ_WIDE=1 (Makefile: psk_seq_wide.o): the reference-order kernel alone for samplesPerBaud > kSeqMaxS, in namespace psk_seqw,
 // exported as launch_seq_wide: symbolEnergy[] lives in a row of device memory per channel of the launch (psk_capi.cpp sizes the
@@ -432,7 +428,7 @@ __global__ __launch_bounds__(64) void psk_seq_kernel(const ChanPlan *__restrict_
 
 }  // namespace psk
 
-#if !PSK_INST_CS16 && !PSK_INST_CS8 && !PSK_INST_CF16 && !PSK_SEQ_WIDE
+#if !defined(PSK_INST_PKT) && !PSK_SEQ_WIDE
 // ---------------------------------------------------------------------------------
 // launchers (called from psk_capi.cpp through plain C++ declarations).  Every (samplesPerBaud,
 // history depth, screened / exact) instantiation of the wave-scan kernel is its own translation
@@ -634,36 +630,14 @@ hipError_t launch_read_probe(const void *src, uint64_t bytes, float *sink, hipSt
     return hipGetLastError();
 }
 }  // namespace psk
-#if PSK_INST_CS16
+#ifdef PSK_INST_PKT
 #undef psk
 namespace psk {
-hipError_t launch_seq_cs16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
-                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
+hipError_t PSK_PASTE(launch_seq_, PSK_INST_PKT)(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
+                                                uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
 {
-    return psk_cs16::launch_seq(static_cast<const psk_cs16::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cs16::ChanState *>(states),
-                                rings, ring_cap, yvs, fit_cap, stream);
-}
-}  // namespace psk
-#endif
-#if PSK_INST_CS8
-#undef psk
-namespace psk {
-hipError_t launch_seq_cs8(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
-                          uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
-{
-    return psk_cs8::launch_seq(static_cast<const psk_cs8::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cs8::ChanState *>(states),
-                               rings, ring_cap, yvs, fit_cap, stream);
-}
-}  // namespace psk
-#endif
-#if PSK_INST_CF16
-#undef psk
-namespace psk {
-hipError_t launch_seq_cf16(const void *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, void *states, float2 *rings,
-                           uint32_t ring_cap, float *yvs, uint32_t fit_cap, hipStream_t stream)
-{
-    return psk_cf16::launch_seq(static_cast<const psk_cf16::ChanPlan *>(plans), list, ch0, nch, static_cast<psk_cf16::ChanState *>(states),
-                                rings, ring_cap, yvs, fit_cap, stream);
+    return PSK_PKT_NS::launch_seq(static_cast<const PSK_PKT_NS::ChanPlan *>(plans), list, ch0, nch, static_cast<PSK_PKT_NS::ChanState *>(states),
+                                  rings, ring_cap, yvs, fit_cap, stream);
 }
 }  // namespace psk
 #endif

@@ -10,6 +10,13 @@
 
 #include <stdint.h>
 
+// The packet formats other than float2 by the name their builds carry (-DPSK_INST_PKT=<name>, psk_wave.h), as preprocessor
+// numbers: the PSK_SOFT_FORMAT_* values of include/psk_soft_hip.h, which is an enum and no use in an #if.  psk_ctl.h and
+// psk_pkt.hip assert that the two agree.
+#define PSK_PKT_ID_cs16 1
+#define PSK_PKT_ID_cs8 3
+#define PSK_PKT_ID_cf16 4
+
 namespace psk {
 
 enum PlanMode : uint32_t {
@@ -47,15 +54,15 @@ enum LfFlags : uint32_t {
     // before round 3, instead of settling the block in place
     PLAN_TIES_HANDOVER = 128u,
     // the packet is complex int16 (PSK_SOFT_FORMAT_CS16).  Unless PLAN_CS16_IN_PLACE is set too, the kernels never see it as such:
-    // `in` points at the float2 copy the conversion pre-pass of the call (psk_cs16.hip) writes into scratch in front of them
+    // `in` points at the float2 copy the conversion pre-pass of the call (psk_pkt.hip) writes into scratch in front of them
     PLAN_CS16 = 256u,
     // (host-side) ... and read in place by the CS16 builds of the wave-scan and reference-order kernels: `in` stays the caller's int16
     // pairs, no pre-pass (psk_capi.cpp: the window classes with such instantiations)
     PLAN_CS16_IN_PLACE = 512u,
-    // the packet is complex int8 (PSK_SOFT_FORMAT_CS8): the same two flags for it (psk_cs8.hip, the PSK_INST_CS8 builds)
+    // the packet is complex int8 (PSK_SOFT_FORMAT_CS8): the same two flags for it (the PSK_INST_PKT=cs8 builds)
     PLAN_CS8 = 1024u,
     PLAN_CS8_IN_PLACE = 2048u,
-    // the packet is complex binary16 (PSK_SOFT_FORMAT_CF16): the same two flags for it (psk_cf16.hip, the PSK_INST_CF16 builds)
+    // the packet is complex binary16 (PSK_SOFT_FORMAT_CF16): the same two flags for it (the PSK_INST_PKT=cf16 builds)
     PLAN_CF16 = 4096u,
     PLAN_CF16_IN_PLACE = 8192u,
 };
@@ -63,12 +70,12 @@ enum LfFlags : uint32_t {
 
 constexpr uint32_t kResyncCount = 1048576u;  // cpp/psk_soft.cpp:51, 582
 
-// One CS16, CS8 or CF16 packet for the conversion pre-pass (psk_cs16.hip, psk_cs8.hip, psk_cf16.hip): n complex samples at src become
+// One CS16, CS8 or CF16 packet for the conversion pre-pass (psk_pkt.hip): n complex samples at src become
 // n float2 at dst.
 // They sit behind the compact channel lists in the upload slot of the call, so that they travel with the plans in one copy.
 struct CvtDesc {
     const uint32_t *src;  // I in the low half, Q in the high half (little-endian int16 pairs); 4-byte aligned -- for a CS8 packet
-                          // the int8 pairs, 2-byte aligned (psk_cs8.hip reads them as uint16), for a CF16 packet binary16 pairs
+                          // the int8 pairs, 2-byte aligned (read as uint16), for a CF16 packet binary16 pairs
                           // laid out like the int16 ones
     float *dst;           // interleaved I,Q floats; 128-byte aligned, in the handle's conversion scratch
     uint64_t n;

@@ -233,27 +233,25 @@ PSK_DEV void store_s2u(int16_t *p, s2u v) { *reinterpret_cast<s2u *>(p) = v; }
 PSK_DEV void store_s2u(PSK_GLOBAL int16_t *p, s2u v) { PSK_ST((PSK_GLOBAL s2u *)p, v); }
 PSK_DEV void store_s4u(int16_t *p, s4u v) { *reinterpret_cast<s4u *>(p) = v; }
 PSK_DEV void store_s4u(PSK_GLOBAL int16_t *p, s4u v) { PSK_ST((PSK_GLOBAL s4u *)p, v); }
-// The packet's sample type is a property of the translation unit (PSK_INST_FMT, a PSK_SOFT_FORMAT_* value): PSK_INST_CS16=1
-// builds (psk_fast_inst.hip, psk_kernels.hip compiled a second time, Makefile) read complex int16 packets (PSK_SOFT_FORMAT_CS16)
-// straight from the caller's buffer, one 32-bit word per sample, I in the low half; PSK_INST_CS8=1 builds read complex int8
-// packets (PSK_SOFT_FORMAT_CS8), one 16-bit word per sample, I in the low byte; PSK_INST_CF16=1 builds read complex binary16
-// packets (PSK_SOFT_FORMAT_CF16), one 32-bit word per sample like CS16, I in the low half; every other build reads float2.  The
-// carried samples (the ring) are float2 in all of them.
-#ifndef PSK_INST_CS16
-#define PSK_INST_CS16 0
+// The packet's sample type is a property of the translation unit: -DPSK_INST_PKT=cs16 | cs8 | cf16 builds (psk_fast_inst.hip,
+// psk_kernels.hip compiled once more per format, Makefile PKT_FORMATS) read complex int16 packets (PSK_SOFT_FORMAT_CS16) straight
+// from the caller's buffer, one 32-bit word per sample, I in the low half; complex int8 packets (PSK_SOFT_FORMAT_CS8), one 16-bit
+// word per sample, I in the low byte; complex binary16 packets (PSK_SOFT_FORMAT_CF16), one 32-bit word per sample like CS16, I in
+// the low half.  Every other build reads float2.  The carried samples (the ring) are float2 in all of them.  PSK_INST_FMT is the
+// PSK_SOFT_FORMAT_* value of the build, pkt_t a sample as it lies in the packet, pkt_f2() (below) its float2.
+#define PSK_PASTE_(a, b) a##b
+#define PSK_PASTE(a, b) PSK_PASTE_(a, b)
+#ifdef PSK_INST_PKT
+#define PSK_INST_FMT PSK_PASTE(PSK_PKT_ID_, PSK_INST_PKT)  // (psk_plan.h)
+#if PSK_INST_FMT == 0
+#error "PSK_INST_PKT must be one of cs16, cs8, cf16 (psk_plan.h: PSK_PKT_ID_*)"
 #endif
-#ifndef PSK_INST_CS8
-#define PSK_INST_CS8 0
+#else
+#define PSK_INST_FMT 0
 #endif
-#ifndef PSK_INST_CF16
-#define PSK_INST_CF16 0
-#endif
-#define PSK_INST_FMT (PSK_INST_CF16 ? 4 : PSK_INST_CS8 ? 3 : PSK_INST_CS16 ? 1 : 0)
 #if PSK_INST_FMT == 3
 typedef uint16_t pkt_t;
-#elif PSK_INST_FMT == 1
-typedef uint32_t pkt_t;
-#elif PSK_INST_FMT == 4
+#elif PSK_INST_FMT != 0
 typedef uint32_t pkt_t;
 #else
 typedef f2g pkt_t;
@@ -268,7 +266,7 @@ PSK_DEV f2g cs16_f2(uint32_t v)
 }
 // int8 pairs -> float2: the sample in byte lanes b, b+1 of v, sign-extended (v_bfe_i32 / v_ashrrev_i32), then v_cvt_f32_i32 --
 // exact for every int8
-template <int B>
+template <int B = 0>
 PSK_DEV f2g cs8_f2(uint32_t v)
 {
     f2g r;
@@ -286,6 +284,9 @@ PSK_DEV f2g cf16_f2(uint32_t v)
     r.y = (float)__builtin_bit_cast(_Float16, (uint16_t)(v >> 16));
     return r;
 }
+#ifdef PSK_INST_PKT
+PSK_DEV f2g pkt_f2(pkt_t v) { return PSK_PASTE(PSK_INST_PKT, _f2)(v); }
+#endif
 struct XView {
     const f2g *ring;
     const pkt_t *in;
@@ -297,13 +298,7 @@ PSK_DEV float2 x_at(const XView &X, uint64_t j)
     // (both loads, then a select: no lane takes a branch of its own; the index the other buffer gets exists)
     const bool r = j < X.L0;
     const f2g a = X.ring[r ? j : 0];
-#if PSK_INST_FMT == 3
-    const f2g b = cs8_f2<0>(X.in[r ? 0 : j - X.L0]);  // (a 2-byte load: CS8 packets are 2-byte aligned)
-#elif PSK_INST_FMT == 4
-    const f2g b = cf16_f2(X.in[r ? 0 : j - X.L0]);
-#else
-    const f2g b = cs16_f2(X.in[r ? 0 : j - X.L0]);
-#endif
+    const f2g b = pkt_f2(X.in[r ? 0 : j - X.L0]);  // (CS8: a 2-byte load, the packets are 2-byte aligned)
     const f2g v = r ? a : b;
 #else
     const f2g v = j < X.L0 ? X.ring[j] : X.in[j - X.L0];
@@ -318,13 +313,7 @@ PSK_DEV f2g x_load(const XView &X, uint64_t j)
     const bool r = j < X.L0;
     const f2g a = *mem_ptr<packet_global(S)>(X.ring + (r ? j : 0));
     const pkt_t b = *mem_ptr<packet_global(S)>(X.in + (r ? 0 : j - X.L0));
-#if PSK_INST_FMT == 3
-    return r ? a : cs8_f2<0>(b);
-#elif PSK_INST_FMT == 4
-    return r ? a : cf16_f2(b);
-#else
-    return r ? a : cs16_f2(b);
-#endif
+    return r ? a : pkt_f2(b);
 #else
     const f2g *p = j < X.L0 ? X.ring + j : X.in + (j - X.L0);  // (a select of two addresses)
     return *mem_ptr<packet_global(S)>(p);

@@ -23,7 +23,7 @@ from tests.test_gpu_strided import contiguous, gathers, strided_run
 
 pytestmark = pytest.mark.gpu
 
-H_CF16 = 6  # the window class of CF16 packets read in place (kClassCf16)
+H_CF16 = 6  # the window class of CF16 packets read in place (psk_ctl.h: kPktFormats)
 F16 = np.dtype(np.float16)
 
 
@@ -601,6 +601,63 @@ def test_a_channel_that_alternates_the_four_formats(oracle_mod, monkeypatch, cap
         hs = {t["H"] for t in lines if t["what"].startswith("fast (")}
         assert {1, H_CS16, H_CS8, H_CF16} <= hs, (k, hs)
         assert {"cs16_convert", "cs8_convert", "cf16_convert"} <= whats(lines), (k, whats(lines))  # (numAvg 200, 600)
+
+
+def test_the_in_place_formats_hand_over_in_one_call(oracle_mod, monkeypatch, capfd):
+    """Eight channels, two each of CF32, CS16, CS8 and CF16 (interleaved), PSK_SOFT_TIES_IN_PLACE=0, three calls, time tiling
+    off.  The first of each pair is an int8-valued tie stream.  The second of the CF32, CS16 and CF16 pairs is a stream that
+    trips the exactness guard in every call -- a few LSB of noise around a burst of +-32767 (CF16: +-32768, exact in half), the
+    stream of channel 16 of test_deferred_join_with_a_cs16_class -- so the joined tail's reference-order kernels really redo a
+    channel of the float build, of the CS16 build and of the CF16 build in one call, each from its own part of the channel
+    list: the CF16 part lies behind the CS16 and the CS8 parts.  An int8 packet cannot trip that guard at numAvg <= 128 (its
+    sample energies span 1 .. 2^15, and 24 + 15 + log2(numAvg + 256) stays below 53: the double sums are always exact), so
+    the second CS8 channel is a tie stream too and the CS8 build's launch finds nothing handed over.  Every channel bit for bit
+    the oracle's, call by call."""
+    S, N = 4, 10000
+    cuts = [0, 3001, 7000, N]
+    ts = _tie_streams(N, S)
+    rng = np.random.default_rng(21)
+
+    def guard_stream(full):  # (numpy int16 values; full = the burst's amplitude)
+        x = rng.integers(-2, 3, 2 * N).astype(np.int32)
+        for a in cuts[:-1]:
+            i0 = a + 1000
+            x[2 * i0 : 2 * (i0 + 256)] = rng.choice(np.int32([-full, full]), 512)
+        return x
+
+    k = rng.integers(0, 4, N // S + 1)
+    pulses = (np.repeat(np.stack([(1, 1), (-1, 1), (-1, -1), (1, -1)])[k], S, axis=0)[:N] * 2).reshape(-1)  # (QPSK pulses, no noise)
+    streams = [ts[0], ts[1], ts[2], ts[6], guard_stream(32767), guard_stream(32767), pulses, guard_stream(32768)]
+    conv = (np.float32, np.int16, np.int8, np.float16)
+    C = len(streams)
+    assert C == 8 and all(np.abs(streams[c]).max() <= 127 for c in (0, 1, 2, 3, 6))
+    streams = [np.asarray(x).astype(conv[c % 4]) for c, x in enumerate(streams)]
+    assert all(np.array_equal(x.astype(np.float64), np.asarray(y, np.float64)) for x, y in zip(streams, [ts[0], ts[1], ts[2], ts[6]]))
+    guarded = [4, 5, 7]  # (CF32, CS16, CF16)
+    props = dict(samplesPerBaud=S, constelationSize=4, numAvg=100, phaseAvg=50)
+    data = [[_cut(streams[c], cuts)[k] for c in range(C)] for k in range(3)]
+
+    def run(h, cf):
+        h.configure(0, [props] * C)
+        got, traces, nsym = {c: [] for c in range(C)}, [], []
+        for k in range(3):
+            g, t, n = device_run(h, [data[k]], cf, k0=k)
+            for c in range(C):
+                got[c] += g[c]
+            traces += t
+            nsym += n
+            st = h.stats()
+            per = [h.channel_stats(c, 1)[0]["channels_guard"] for c in range(C)]
+            assert [c for c in range(C) if per[c]] == guarded, (k, per)
+            assert st["channels_sequential"] >= 3 and st["channels_guard"] == 3, (k, st)
+        return got, traces, nsym
+
+    res = untraced_then_traced(monkeypatch, capfd, dict(PSK_SOFT_TIES_IN_PLACE=0, PSK_SOFT_TIME_TILED=0), C, run)
+    check_parity(oracle_mod, res[0][0], lambda c: props, data, "hand-over of four formats")
+    for k, lines in enumerate(res[1][1]):
+        hs = {t["H"] for t in lines if t["what"].startswith("fast (")}
+        assert {1, H_CS16, H_CS8, H_CF16} <= hs, (k, hs)
+        assert "seq (reference order)" in whats(lines), (k, whats(lines))
 
 
 def test_stamp_key_tells_cf16_from_the_other_formats(oracle_mod):

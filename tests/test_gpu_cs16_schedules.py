@@ -24,7 +24,7 @@ from tests.test_gpu_parity import assert_parity
 pytestmark = pytest.mark.gpu
 
 KEYS = ("soft", "bits", "phase", "index")
-H_CS16 = 3  # the window class of CS16 packets read in place (kClassCs16)
+H_CS16 = 3  # the window class of CS16 packets read in place (psk_ctl.h: kPktFormats)
 _LINE = re.compile(r"\[psk_soft\] ok; next: (?P<what>.+?) S=(?P<S>-?\d+) H=(?P<H>-?\d+) ch0=\d+ cnt=(?P<cnt>\d+) .*?"
                    r"slot=(?P<slot>\d+) stream=(?P<stream>\S+)")
 
@@ -256,7 +256,7 @@ def _mixed_cut_batch(C, S, calls, prepass):
 @pytest.mark.parametrize("pieces", [2, 3, 5])
 @pytest.mark.parametrize("variant", ["untiled", "default"])
 def test_cs16_in_place_inside_a_mixed_batch_cut_in_time(oracle_mod, monkeypatch, capfd, pieces, variant):
-    """The CS16 class read in place (kClassCs16) inside a mixed batch that the library cuts into PSK_SOFT_SPLIT_CLASSES pieces:
+    """The CS16 class read in place (H=3) inside a mixed batch that the library cuts into PSK_SOFT_SPLIT_CLASSES pieces:
     each piece of an int16 packet starts elem_bytes(CS16) x the elements before it further on, and the pieces carry the call's
     rounding bounds (PLAN_CARRY_DRIFT).  "untiled": 28 channels with PSK_SOFT_TIME_TILED=0; "default": default options, every
     class of more than 64 channels and under 192 blocks, so that nothing goes to the time-tiled kernels by itself."""

@@ -18,7 +18,7 @@ from tests.test_gpu_parity import assert_parity
 pytestmark = pytest.mark.gpu
 
 SCALE8 = 40.0
-H_CS8 = 5  # the window class of CS8 packets read in place (kClassCs8)
+H_CS8 = 5  # the window class of CS8 packets read in place (psk_ctl.h: kPktFormats)
 
 
 def q8(x, scale=SCALE8):

@@ -23,16 +23,13 @@ others() { f=$1; shift; /opt/rocm/bin/hipcc $FL "$@" -o $tmp/$f.s psk_soft_amd/c
   python3 tools/isa_exec_spills.py $tmp/$f.s --sites 0 >> $out; python3 tools/isa_lane_loss.py $tmp/$f.s --sites 3 >> $out.lanes; rm -f $tmp/$f.s; }
 others psk_tile; others psk_kernels
 for s in $(seq 2 16); do others psk_tile_inst@S$s -DPSK_INST_S=$s -DPSK_INST_H=1; done
-# the CS16 builds (PSK_INST_CS16=1): the wave-scan kernel for numAvg <= 128, samplesPerBaud 2 ... 16, both tiers; the reference-order
-# kernel; the conversion pre-pass (psk_cs16.hip)
-for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cs16_S${s}_H1_E$e -DPSK_INST_CS16=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
-others psk_kernels@cs16 -DPSK_INST_CS16=1; others psk_cs16
-# the CS8 builds (PSK_INST_CS8=1): the same classes; the reference-order kernel; the conversion pre-pass (psk_cs8.hip)
-for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cs8_S${s}_H1_E$e -DPSK_INST_CS8=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
-others psk_kernels@cs8 -DPSK_INST_CS8=1; others psk_cs8
-# the CF16 builds (PSK_INST_CF16=1): the same classes; the reference-order kernel; the conversion pre-pass (psk_cf16.hip)
-for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@cf16_S${s}_H1_E$e -DPSK_INST_CF16=1 -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
-others psk_kernels@cf16 -DPSK_INST_CF16=1; others psk_cf16
+# the builds that read a packet format in place (PSK_INST_PKT=cs16 | cs8 | cf16): the wave-scan kernel for numAvg <= 128, samplesPerBaud
+# 2 ... 16, both tiers; the reference-order kernel; and the conversion pre-passes of the three (psk_pkt.hip)
+for f in cs16 cs8 cf16; do
+  for s in $(seq 2 16); do for e in 0 1; do others psk_fast_inst@${f}_S${s}_H1_E$e -DPSK_INST_PKT=$f -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e; done; done
+  others psk_kernels@$f -DPSK_INST_PKT=$f
+done
+others psk_pkt
 # wide symbols (samplesPerBaud > 1024): the chunk and pick kernels (psk_wide.hip), the reference-order kernel's PSK_SEQ_WIDE build
 others psk_wide; others psk_kernels@wide -DPSK_SEQ_WIDE=1
 # the reduction pass of PSK_SOFT_OPT_QUALITY (psk_quality.hip): fold and join
