@@ -275,7 +275,15 @@ enum {
      * deferred join has no effect while this option is on (the call is still cut in time and by class as before; the
      * pass comes behind the join of the last piece).  Outputs in psk_soft_host_alloc memory are read back over the link
      * by the pass: correct, and the one case where the option costs a second crossing of the soft rows. */
-    PSK_SOFT_OPT_QUALITY = 6
+    PSK_SOFT_OPT_QUALITY = 6,
+    /* phaseAvg 32641 .. 65535 ("far" fit windows, more than any LDS ring holds).  0 (default): a call of such a channel that
+     * emits symbols runs on the reference-order kernel, one lane per channel, and the launch of the whole batch waits for it.
+     * 1 = it runs on the time-tiled kernels, behind the front stage that takes samplesPerBaud and numAvg at run time, with a fit
+     * stage that keeps the fit window in a scratch in device memory: 512 KiB per far channel, owned by the handle, allocated
+     * when the first such call comes and kept.  Any other value is refused.  Takes effect at the next process call; results are
+     * unchanged, bit for bit; psk_soft_set_force_sequential(1) still wins.  Such channels count in channels_fast and
+     * channels_tiled.  The environment variable PSK_SOFT_FAR_FIT (0 / 1) sets the default of new handles. */
+    PSK_SOFT_OPT_FAR_FIT = 7
 };
 psk_soft_status psk_soft_set_option(psk_soft_handle_t *h, int option, int value);
 

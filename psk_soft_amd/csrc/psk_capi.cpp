@@ -72,6 +72,13 @@ hipError_t launch_tile_fit_range(const ChanPlan *plans, const uint32_t *list, ui
                                  const float2 *t_s, float *t_est, void *carry, float *carry_y, uint32_t tile0, uint32_t ntiles,
                                  hipStream_t stream);
 size_t pipe_carry_bytes();
+// PSK_SOFT_OPT_FAR_FIT (psk_farfit.hip): the fit stage for phaseAvg above kFastFitMax, its rings in rows of a scratch in device memory
+hipError_t launch_far_fit(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
+                          uint32_t ring_cap, float *yvs, uint32_t fit_cap, float *far_y, uint32_t far_rows, TileInfo *tiles,
+                          const float *t_raw, const float2 *t_s, float *t_est, hipStream_t stream);
+hipError_t launch_far_quiet(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states, float2 *rings,
+                            uint32_t ring_cap, float *yvs, uint32_t fit_cap, float *far_y, uint32_t far_rows, hipStream_t stream);
+size_t far_ring_bytes();
 hipError_t launch_tile_back(const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, uint32_t max_tiles,
                             const ChanState *states, const TileInfo *tiles, const float2 *t_s, const float *t_est, uint32_t tile0,
                             uint32_t early, hipStream_t stream);
@@ -227,6 +234,13 @@ struct PlanSummary {
     // ... of them, the wide symbols (samplesPerBaud > kSeqMaxS): a launch set of their own (psk_wide.hip)
     uint32_t cnt_wide = 0, max_n_wide = 0, max_A_wide = 0, max_blocks_wide = 0, max_S_wide = 0;
     uint64_t blocks_wide = 0;
+    // ... and of both, the channels of the far fit (PLAN_FARFIT, phaseAvg > kFastFitMax): launch sets of their own, so that the LDS
+    // rings of the two above stay sized for their own channels
+    struct FarSet {
+        uint32_t cnt = 0, max_A = 0, max_blocks = 0, max_S = 0;
+        uint64_t blocks = 0;
+    } anyf, widef;
+    uint32_t cnt_quietf = 0;  // ... and their calls that emit nothing while the window holds values (psk_far_quiet_kernel)
 };
 
 // One chunk of channels of the host-buffer path in flight: pinned and device buffers for the packed
@@ -435,6 +449,14 @@ struct psk_soft_handle {
     hipEvent_t tile_ev = nullptr;
     hipStream_t tile_stream = nullptr;  // stream of the last call that used the scratch
     bool tile_ev_used = false;
+    // PSK_SOFT_OPT_FAR_FIT: phaseAvg above kFastFitMax on the fast path (psk_farfit.hip).  The rings of that fit stage are rows of
+    // d_far_y, one per channel that has ever emitted as a far channel (far_row[channel] = row + 1, 0: none yet) -- by channel, not by
+    // position in the call: calls on disjoint channel ranges run side by side on different streams.  Grown on demand, never shrunk;
+    // a row holds nothing between calls (the prologue of every call copies the carried values in).
+    int opt_far_fit = 0;
+    float *d_far_y = nullptr;
+    uint32_t far_rows_cap = 0, far_rows_used = 0;
+    std::vector<uint32_t> far_row;
     bool poisoned = false;  // a HIP call failed after kernels of a call were enqueued: host mirror and device state may disagree
     // CS16 / CS8 / CF16 packets: conversion scratch (CvtScratch)
     CvtScratch cvt[kCvtScratch];
@@ -574,6 +596,7 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
     h->lim.fit_cap = lim.max_phase_avg + 1;  // circular yvals buffer
     h->lim.fast_fit_max = kFastFitMax;
     h->lim.force_seq = false;
+    h->lim.far_fit = false;
     h->ctl.resize(n_channels);
     h->ctl_next.resize(n_channels);
     h->last_mode.assign(n_channels, psk::PLAN_SKIP);
@@ -583,6 +606,9 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
         h->quality_dry.assign(n_channels, psk_soft_quality_t{});
     if (const char *e = std::getenv("PSK_SOFT_TIME_TILED"))
         h->opt_tiled = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
+    if (const char *e = std::getenv("PSK_SOFT_FAR_FIT"))  // (as psk_soft_set_option(PSK_SOFT_OPT_FAR_FIT))
+        h->opt_far_fit = std::atoi(e) != 0;
+    h->lim.far_fit = h->opt_far_fit != 0;
     if (const char *e = std::getenv("PSK_SOFT_TIES_IN_PLACE"))
         h->opt_ties_in_place = std::atoi(e) != 0;
     if (const char *e = std::getenv("PSK_SOFT_TRACE_LAUNCHES"))
@@ -742,6 +768,7 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_wide_rec) (void)hipFree(h->d_wide_rec);
         if (h->d_wide_stat) (void)hipFree(h->d_wide_stat);
         if (h->d_wide_symE) (void)hipFree(h->d_wide_symE);
+        if (h->d_far_y) (void)hipFree(h->d_far_y);
         if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
         for (auto &row : h->slot_aux_ev)
             for (hipEvent_t &e : row)
@@ -856,7 +883,16 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
         r.any = true;
         if (p.mode == psk::PLAN_FAST) {
-            if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
+            if (p.n_out && (p.lf_flags & psk::PLAN_FARFIT)) {
+                r.any_emit = true;
+                PlanSummary::FarSet &f = p.S > kSeqMaxS ? r.widef : r.anyf;
+                f.cnt += mult;
+                const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
+                f.blocks += (uint64_t)nb * mult;
+                if (nb > f.max_blocks) f.max_blocks = nb;
+                if (p.A > f.max_A) f.max_A = p.A;
+                if (p.S > f.max_S) f.max_S = p.S;
+            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
                 r.any_emit = true;
                 r.cnt_wide += mult;
                 const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
@@ -887,14 +923,17 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
                 r.blocks_SH[p.S][Hh] += (uint64_t)nb * mult;
                 if (nb > r.max_blocks_SH[p.S][Hh]) r.max_blocks_SH[p.S][Hh] = nb;
+            } else if (lim.far_fit && p.lf_n > lim.fast_fit_max && p.lf_len0) {
+                r.cnt_quietf += mult;  // (nothing emitted, but prologue and epilogue go through the window: no LDS holds it)
             } else {
                 r.any_quiet = true;
                 r.cnt_quiet += mult;
-                if (p.lf_n > r.max_n_quiet) r.max_n_quiet = p.lf_n;
+                // (an empty far window needs no room in the launch's LDS ring: nothing is copied in or out)
+                if (p.lf_n > r.max_n_quiet && (p.lf_len0 || p.lf_n <= lim.fast_fit_max)) r.max_n_quiet = p.lf_n;
             }
         } else {
             r.any_seq = true;
-            if (!lim.force_seq && p.lf_n <= lim.fast_fit_max &&
+            if (!lim.force_seq && p.lf_n <= (lim.far_fit ? 65535u : lim.fast_fit_max) &&
                 (p.n_out > psk::kResyncCount || (uint64_t)p.lf_count0 + p.n_out > psk::kResyncCount))
                 r.long_call = true;
         }
@@ -1127,14 +1166,17 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     const uint32_t *const d_list = reinterpret_cast<const uint32_t *>(h->d_plans[slot] + nch);
     uint32_t off_SH[33][17] = {}, off_quiet = 0;
     const uint32_t off_any = res.cnt_quiet, off_wide = res.cnt_quiet + res.cnt_any;
+    const uint32_t off_anyf = off_wide + res.cnt_wide, off_widef = off_anyf + res.anyf.cnt;  // (the far fit's two)
+    const uint32_t off_quietf = off_widef + res.widef.cnt;                                   // (... and its quiet calls)
+    const uint32_t cnt_far_rows = res.anyf.cnt + res.widef.cnt + res.cnt_quietf;            // (the three lists follow one another)
     {
-        uint32_t run = res.cnt_quiet + res.cnt_any + res.cnt_wide;
+        uint32_t run = off_quietf + res.cnt_quietf;
         for (int S : kFastS)
             for (int H : kClassH) {
                 off_SH[S][H] = run;
                 run += res.cnt_SH[S][H];
             }
-        uint32_t fill_SH[33][17] = {}, fill_quiet = 0, fill_any = 0, fill_wide = 0;
+        uint32_t fill_SH[33][17] = {}, fill_quiet = 0, fill_any = 0, fill_wide = 0, fill_anyf = 0, fill_widef = 0, fill_quietf = 0;
         // (one class holds every channel, in order; the offsets of the others are equal to its end -- unless the stamped class was just
         // moved back to the float class: its offsets are that class's then, the lists the same)
         if (stamped)
@@ -1143,13 +1185,20 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             const psk::ChanPlan &p = plans[i];
             if (p.mode != psk::PLAN_FAST)
                 continue;
-            if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
+            if (p.n_out && (p.lf_flags & psk::PLAN_FARFIT)) {
+                if (p.S > kSeqMaxS)
+                    h_list[off_widef + fill_widef++] = i;
+                else
+                    h_list[off_anyf + fill_anyf++] = i;
+            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
                 h_list[off_wide + fill_wide++] = i;
             } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
                 h_list[off_any + fill_any++] = i;
             } else if (p.n_out) {
                 const int Hh = class_of(p);
                 h_list[off_SH[p.S][Hh] + fill_SH[p.S][Hh]++] = i;
+            } else if (lim.far_fit && p.lf_n > lim.fast_fit_max && p.lf_len0) {
+                h_list[off_quietf + fill_quietf++] = i;
             } else {
                 h_list[off_quiet + fill_quiet++] = i;
             }
@@ -1160,11 +1209,34 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
     // that the class makes a few thousand tiles.
     bool tiled_SH[33][17] = {};
     bool pf_second = false;
-    uint32_t tiles_max_any = 0, tiles_max_wide = 0;
+    uint32_t tiles_max_any = 0, tiles_max_wide = 0, tiles_max_anyf = 0, tiles_max_widef = 0;
     uint32_t tiles_max_SH[33][17] = {};
     size_t tile_syms = 0, tile_count = 0;
     // (wide symbols first: their places in the scratch index the chunk records of psk_wide.hip too, which need not cover the others)
-    const uint32_t wide_z = res.cnt_wide ? psk::wide_chunks(res.max_S_wide) : 0u;
+    const uint32_t wide_z = (res.cnt_wide || res.widef.cnt) ? psk::wide_chunks(res.max_S_wide > res.widef.max_S ? res.max_S_wide : res.widef.max_S) : 0u;
+    // the far fit's launch sets get their places the way the two sets they are split off from do (below); never the parallel fit,
+    // whose kernels keep the window in LDS as well
+    auto place_far = [&](const PlanSummary::FarSet &f, uint32_t off, uint64_t blocks_z, uint64_t k_min, uint32_t &tiles_max) {
+        uint64_t K = blocks_z / kTiledTargetTiles;
+        K = K < k_min ? k_min : K > 16 ? 16 : K;
+        const uint64_t k_win = (f.max_A + 127u) / 128u;
+        if (K < k_win) {
+            const uint64_t k_fill = blocks_z / (kTiledTargetTiles / 2);
+            const uint64_t k_long = k_win > 64 ? 64 : k_win;
+            K = k_fill > k_long ? k_long : k_fill > K ? k_fill : K;
+        }
+        tiles_max = (uint32_t)((f.max_blocks + K - 1) / K);
+        for (uint32_t i = 0; i < f.cnt; i++) {
+            psk::ChanPlan &p = plans[h_list[off + i]];
+            const uint64_t nb = (p.n_out + 127u) / 128u;
+            p.lf_flags |= psk::PLAN_TILED;
+            p.tile_blocks = (uint32_t)K;
+            p.tile_base = (uint32_t)tile_count;
+            p.tile_off = tile_syms;
+            tile_count += (size_t)((nb + K - 1) / K);
+            tile_syms += (size_t)nb * 128u;
+        }
+    };
     if (res.cnt_wide) {
         // always tiled, like the classes below; a tile is one wave per chunk of 1024 timing phases, and few symbols a call fill
         // the machine only on short tiles -- as short as one block, unless the window in front of a tile is longer
@@ -1190,6 +1262,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             tile_syms += (size_t)nb * 128u;
         }
     }
+    if (res.widef.cnt)  // (behind the wide symbols, in front of everything else: the chunk records cover the two)
+        place_far(res.widef, off_widef, res.widef.blocks * wide_z, 1, tiles_max_widef);
     const size_t wide_rec_need = tile_syms * wide_z * psk::wide_rec_bytes(), wide_stat_need = tile_count * wide_z * psk::wide_stat_bytes();
     if (res.cnt_any) {
         // (window classes without a wave-scan instantiation: always tiled, whatever the option says -- the alternative is the
@@ -1218,6 +1292,8 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             tile_syms += (size_t)nb * 128u;
         }
     }
+    if (res.anyf.cnt)
+        place_far(res.anyf, off_anyf, res.anyf.blocks, 2, tiles_max_anyf);
     bool piped_SH[33][17] = {};
     uint32_t pipe_tiles_SH[33][17] = {};  // tiles of a range
     size_t pipe_need = 0;
@@ -1314,9 +1390,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                         plans[i].mode = plans[i].S == 1u ? psk::PLAN_SEQ_S1 : psk::PLAN_SEQ;
                         res.any_seq = true;
                     }
-                    plans[i].lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT);
+                    plans[i].lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
                 }
-                res.cnt_any = res.cnt_wide = 0;
+                res.cnt_any = res.cnt_wide = res.anyf.cnt = res.widef.cnt = 0;
                 for (auto &row : tiled_SH)
                     for (bool &t : row) t = false;
                 for (auto &row : piped_SH)
@@ -1330,7 +1406,7 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
         }
     }
-    if (res.cnt_wide && (wide_rec_need > h->wide_rec_cap || wide_stat_need > h->wide_stat_cap)) {
+    if ((res.cnt_wide || res.widef.cnt) && (wide_rec_need > h->wide_rec_cap || wide_stat_need > h->wide_stat_cap)) {
         // the chunk records of the wide front stage: grown to the largest call seen, plus a quarter
         PSK_HIP(hipDeviceSynchronize());
         if (h->d_wide_rec) (void)hipFree(h->d_wide_rec);
@@ -1342,12 +1418,55 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
             h->wide_rec_cap = rb, h->wide_stat_cap = sb;
         } else {  // (out of device memory: the reference-order kernel carries these calls)
             (void)hipGetLastError();
-            for (uint32_t i = 0; i < res.cnt_wide; i++) {
-                psk::ChanPlan &p = plans[h_list[off_wide + i]];
+            for (uint32_t i = 0; i < res.cnt_wide + res.widef.cnt; i++) {
+                psk::ChanPlan &p = plans[h_list[(i < res.cnt_wide ? off_wide : off_widef - res.cnt_wide) + i]];
                 p.mode = psk::PLAN_SEQ;
-                p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT);
+                p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
             }
-            res.cnt_wide = 0;
+            res.cnt_wide = res.widef.cnt = 0;
+            res.any_seq = true;
+        }
+    }
+    // the far fit's rings: a row of the scratch for every channel of its two launch sets (kept from the channel's first such call on)
+    if (cnt_far_rows) {
+        if (h->far_row.empty())
+            h->far_row.assign(h->nch, 0u);
+        uint32_t used = h->far_rows_used;
+        for (uint32_t i = 0; i < cnt_far_rows; i++)
+            if (!h->far_row[ch0 + h_list[off_anyf + i]])
+                used++;
+        bool got = true;
+        if (used > h->far_rows_cap) {
+            // (the one place of this path that waits for the device: no call is in flight on a row that moves, and a row carries
+            // nothing from one call to the next)
+            PSK_HIP(hipDeviceSynchronize());
+            if (h->d_far_y) (void)hipFree(h->d_far_y);
+            h->d_far_y = nullptr;
+            h->far_rows_cap = 0;
+            const uint32_t cap = used + used / 4 < h->nch ? used + used / 4 : h->nch;
+            if (hipMalloc((void **)&h->d_far_y, psk::far_ring_bytes() * cap) == hipSuccess) {
+                h->far_rows_cap = cap;
+            } else {  // (out of device memory: the reference-order kernel carries these calls, as with the option off)
+                (void)hipGetLastError();
+                got = false;
+            }
+        }
+        for (uint32_t i = 0; i < cnt_far_rows; i++) {
+            psk::ChanPlan &p = plans[h_list[off_anyf + i]];
+            if (got) {
+                uint32_t &row = h->far_row[ch0 + h_list[off_anyf + i]];
+                if (!row)
+                    row = ++h->far_rows_used;
+                p.far_row = row - 1u;
+            } else if (p.n_out) {
+                p.mode = p.S == 1u ? psk::PLAN_SEQ_S1 : psk::PLAN_SEQ;
+                p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
+            }
+        }
+        if (!got) {
+            if (res.cnt_quietf)
+                return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the fit window of a far channel (PSK_SOFT_OPT_FAR_FIT)");
+            res.anyf.cnt = res.widef.cnt = 0;
             res.any_seq = true;
         }
     }
@@ -1539,6 +1658,9 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                      (!p.tile_blocks || p.tile_off + nb * 128u > h->tile_sym_cap ||
                       (uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks > h->tile_cap))
                 why = "place in the time-tiled scratch outside it";
+            else if ((p.lf_flags & psk::PLAN_FARFIT) && p.mode == psk::PLAN_FAST && p.n_out &&
+                     (!h->d_far_y || p.far_row >= h->far_rows_cap || (p.lf_flags & psk::PLAN_PFIT) || p.lf_n < 128u))
+                why = "far fit without a row of its scratch";
             else if ((p.lf_flags & psk::PLAN_PFIT) && p.mode == psk::PLAN_FAST && p.n_out &&
                      (p.tile_off + nb * 128u > h->pf_sym_cap || (uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks > h->pf_cap))
                 why = "place in the parallel fit's scratch outside it";
@@ -1725,6 +1847,34 @@ static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_
                                          h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf, stream));
             PSK_HIP(mark("tile_back (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, 0));
             PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, h->d_state, h->d_tiles,
+                                          h->d_ts, h->d_test, 0u, 0u, stream));
+        }
+        if (res.cnt_quietf) {
+            PSK_HIP(mark("far_quiet (calls that emit nothing)", 0, 0, off_quietf, res.cnt_quietf, 0, 0, 0));
+            PSK_HIP(psk::launch_far_quiet(h->d_plans[slot], d_list + off_quietf, ch0, res.cnt_quietf, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                          h->lim.fit_cap, h->d_far_y, h->far_rows_cap, stream));
+        }
+        // the far fit's two launch sets: the same front and back stages around the fit stage with its rings in device memory
+        if (res.anyf.cnt) {
+            PSK_HIP(mark("tile_front_any (far)", (int)res.anyf.max_S, 0, off_anyf, res.anyf.cnt, tiles_max_anyf, 0, 0));
+            PSK_HIP(psk::launch_tile_front_any(h->d_plans[slot], d_list + off_anyf, ch0, res.anyf.cnt, tiles_max_anyf, res.anyf.max_S, h->d_state,
+                                               h->d_ring, h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, stream));
+            PSK_HIP(mark("far_fit (any)", (int)res.anyf.max_S, 0, off_anyf, res.anyf.cnt, tiles_max_anyf, 0, 0));
+            PSK_HIP(psk::launch_far_fit(h->d_plans[slot], d_list + off_anyf, ch0, res.anyf.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                        h->lim.fit_cap, h->d_far_y, h->far_rows_cap, h->d_tiles, h->d_traw, h->d_ts, h->d_test, stream));
+            PSK_HIP(mark("tile_back (any, far)", (int)res.anyf.max_S, 0, off_anyf, res.anyf.cnt, tiles_max_anyf, 0, 0));
+            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_anyf, ch0, res.anyf.cnt, tiles_max_anyf, h->d_state, h->d_tiles,
+                                          h->d_ts, h->d_test, 0u, 0u, stream));
+        }
+        if (res.widef.cnt) {
+            PSK_HIP(mark("wide_front (chunk, pick; far)", (int)res.widef.max_S, 0, off_widef, res.widef.cnt, tiles_max_widef, 0, wide_z));
+            PSK_HIP(psk::launch_wide_front(h->d_plans[slot], d_list + off_widef, ch0, res.widef.cnt, tiles_max_widef, res.widef.max_S, h->d_ring,
+                                           h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, h->d_wide_rec, h->d_wide_stat, stream));
+            PSK_HIP(mark("far_fit (wide)", (int)res.widef.max_S, 0, off_widef, res.widef.cnt, tiles_max_widef, 0, 0));
+            PSK_HIP(psk::launch_far_fit(h->d_plans[slot], d_list + off_widef, ch0, res.widef.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                        h->lim.fit_cap, h->d_far_y, h->far_rows_cap, h->d_tiles, h->d_traw, h->d_ts, h->d_test, stream));
+            PSK_HIP(mark("tile_back (wide, far)", (int)res.widef.max_S, 0, off_widef, res.widef.cnt, tiles_max_widef, 0, 0));
+            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_widef, ch0, res.widef.cnt, tiles_max_widef, h->d_state, h->d_tiles,
                                           h->d_ts, h->d_test, 0u, 0u, stream));
         }
         if (any_quiet && deferred)  // (every launch set ends its own calls: the quiet channels' on the caller's stream)
@@ -2807,6 +2957,12 @@ psk_soft_status psk_soft_set_option(psk_soft_handle_t *h, int option, int value)
             }
         }
         h->opt_quality = value;
+        return PSK_SOFT_OK;
+    case PSK_SOFT_OPT_FAR_FIT:
+        if (value != 0 && value != 1)
+            return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_set_option: PSK_SOFT_OPT_FAR_FIT takes 0 or 1");
+        h->opt_far_fit = value;
+        h->lim.far_fit = value != 0;  // (process_round reads the limits once per call: from the next call on)
         return PSK_SOFT_OK;
     default: return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_set_option: unknown option");
     }

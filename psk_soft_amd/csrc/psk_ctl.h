@@ -109,6 +109,7 @@ struct Limits {
     uint32_t ring_cap;  // samples per ring buffer
     uint32_t fit_cap;   // floats in the circular yvals buffer
     uint32_t fast_fit_max;   // largest phaseAvg the wave-scan kernel holds in LDS
+    bool far_fit;            // PSK_SOFT_OPT_FAR_FIT: larger ones go to the fit stage with its ring in device memory (PLAN_FARFIT)
     bool force_seq;
 };
 
@@ -289,6 +290,7 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
         c.lf_count = 0;
     }
     uint64_t n_out = 0;
+    const uint64_t fit_max = lim.far_fit ? 65535u : lim.fast_fit_max;  // largest phaseAvg a fast path takes
     bool any_front = false;  // (regular window mode) the window class has no wave-scan instantiation
     if (S == 1) {
         // :445 nothing is pushed; :454 index==lastSample needs index==0; :457 size==numDataPts
@@ -297,7 +299,7 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
                 n_out = N;
                 // (a symbol per sample, no timing recovery: the time-tiled kernels behind their run-time front stage, which has
                 // nothing to pick there; the reference-order kernel for what the fit limits exclude)
-                any_front = !lim.force_seq && n_out > 0 && c.lf_n <= lim.fast_fit_max && n_out <= kResyncCount &&
+                any_front = !lim.force_seq && n_out > 0 && c.lf_n <= fit_max && n_out <= kResyncCount &&
                             plan_lf_count0(c) + n_out <= kResyncCount;
                 plan.mode = any_front ? PLAN_FAST : PLAN_SEQ_S1;
             }
@@ -328,8 +330,9 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
         c.index = ctl_mod(c.ring_len, S);
         c.count = (c.count + n_out) % kResyncCount;  // :581-583
         plan.ring_len1 = (uint32_t)c.ring_len;
-        any_front = !fast_kernel_has((uint32_t)S, (uint32_t)A);
-        bool fast_ok = !lim.force_seq && (!any_front || any_front_has((uint32_t)S)) && c.lf_n <= lim.fast_fit_max &&
+        // (a far fit window goes behind the run-time front stage whatever its window class: one fit kernel, not one per instantiation)
+        any_front = !fast_kernel_has((uint32_t)S, (uint32_t)A) || c.lf_n > lim.fast_fit_max;
+        bool fast_ok = !lim.force_seq && (!any_front || any_front_has((uint32_t)S)) && c.lf_n <= fit_max &&
                        n_out <= kResyncCount &&
                        ((plan_lf_count0(c)) + n_out <= kResyncCount);
         plan.mode = (n_out == 0 || fast_ok) ? PLAN_FAST : PLAN_SEQ;
@@ -347,7 +350,7 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
     plan.lf_flags = fmt ? fmt->flag : 0u;
     plan.n_out = n_out;
     if (plan.mode == PLAN_FAST && n_out && any_front)
-        plan.lf_flags |= PLAN_ANYFRONT;
+        plan.lf_flags |= PLAN_ANYFRONT | (c.lf_n > lim.fast_fit_max ? (uint32_t)PLAN_FARFIT : 0u);
     if (plan.mode != PLAN_SKIP && c.lf_recompute_pending) {
         plan.lf_flags |= LF_RECOMPUTE;
         plan.lf_count0 = 0;

@@ -11,13 +11,18 @@ namespace psk {
 PSK_HD int hist_blocks_for(uint32_t A) { return A <= 128u ? 1 : A <= 256u ? 2 : A <= 512u ? 4 : 8; }
 
 // Per-call prologue of a channel (shared with the time-tiled fit kernel, psk_tile_kernel.h): LinearFit history into
-// the LDS ring, the carried state into `cy`; LinearFit::reset() sums if it ran.
+// the LDS ring, the carried state into `cy`; LinearFit::reset() sums if it ran.  (FAR: the ring is the far fit's, in device memory
+// -- psk_fast_loop.h: far_ring_fence.)
+template <bool FAR = false>
 PSK_DEV void call_prologue(const ChanPlan &p, const ChanState *st, const float *yv, uint32_t fit_cap, float *yring, uint32_t ymask,
                            int lane, FastCarry &cy)
 {
     const uint32_t len0 = p.lf_len0;
     for (uint32_t j = lane; j < len0; j += kWave) yring[j & ymask] = yv[(p.lf_head + j) % fit_cap];
-    wave_lds_fence();
+    if constexpr (FAR)
+        far_ring_fence();
+    else
+        wave_lds_fence();
     cy.ySum = st->lf_ySum;
     cy.xySum = st->lf_xySum;
     cy.est = st->phaseEstimate;
@@ -54,6 +59,7 @@ PSK_DEV void call_prologue(const ChanPlan &p, const ChanState *st, const float *
 // End of a call that ran to completion (shared with the time-tiled fit kernel): end-of-call wrap, then the channel
 // state is committed -- LinearFit history and sums, the surviving samples into the other ring buffer, `guard_done` into
 // ChanState::guard.
+template <bool FAR = false>
 PSK_DEV void call_epilogue(const ChanPlan &p, ChanState *st, float *yv, uint32_t fit_cap, float *yring, uint32_t ymask, const XView &X,
                            float2 *ring_dst, int lane, FastCarry &cy, uint32_t guard_done)
 {
@@ -73,7 +79,10 @@ PSK_DEV void call_epilogue(const ChanPlan &p, ChanState *st, float *yv, uint32_t
             float v = yring[(first + j) & ymask];
             yring[(first + j) & ymask] = v - cst;
         }
-        wave_lds_fence();
+        if constexpr (FAR)
+            far_ring_fence();
+        else
+            wave_lds_fence();
         fit_rebuild_sums([&](uint32_t j) { return yring[(first + j) & ymask]; }, len1, p.lf_xdelta, cy.ySum, cy.xySum);
         fit_denominator(p.lf_xdelta, len1, cy.den, cy.xavg);
         if (len1 > 1) {

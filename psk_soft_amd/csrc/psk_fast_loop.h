@@ -85,6 +85,30 @@ struct FastCarry {
                            // thresholds this tile used still exceed what the reference's running sums may have drifted by
 };
 
+// The ring of LinearFit::yvals of a running call (`yring`, `ymask`: position i of the values ever pushed at index i & ymask) is
+// LDS in every kernel but the far fit (psk_farfit.hip, FAR = true below), where it is a row in device memory, for windows no LDS
+// holds (phaseAvg > 32640).  With a window of 128 values or more the values that leave it during a block were all pushed by
+// EARLIER blocks: that kernel reads the block's 128 of them once, in front of the unwrap passes (far_ring_preread), which then
+// work on registers, and the block's own values are stored once their counts are final.  One lane's global store is not visible
+// to another lane's load without a release / acquire at workgroup scope (wave_lds_fence only restrains the compiler, and relies
+// on LDS executing in order): far_ring_fence is one, and waits for the outstanding stores -- once per block, never inside the
+// pass loop.
+PSK_DEV void far_ring_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+// the values leaving the window at the lane's two positions of the block that starts at q0 (0 where the window is still filling)
+PSK_DEV void far_ring_preread(const float *yring, uint32_t ymask, uint32_t q0, uint32_t n, int lane, float (&z)[kR])
+{
+    far_ring_fence();  // (the stores of the blocks before this one)
+#pragma unroll
+    for (int r = 0; r < kR; r++) {
+        const uint32_t before = q0 + (uint32_t)(2 * lane + r);
+        z[r] = before >= n ? yring[(before - n) & ymask] : 0.0f;
+    }
+}
+
 // exactness guard bookkeeping: max of the energy bit patterns and min of (bits - 1); a zero
 // energy gives bits 0 / 0xFFFFFFFF and so constrains neither
 // An energy that is inf or NaN (energies carry no sign) is not a question of exactness: the screened tier leaves
@@ -606,10 +630,11 @@ PSK_DEV int fit_sums_verify(const bool (&valid)[kR], const bool (&steady)[kR], f
 // recomputes the same values).  with_y = false: ySum_l holds verified sums, only xySum is chained.  The two sums
 // are chained one after the other (ySum does not depend on xySum): two short loops of 2 moves + 4 dependent
 // additions a step instead of one long one.
-template <bool WARM>
+// FAR: the ring is the far fit's, `z_far` the block's pre-read leaving values.
+template <bool WARM, bool FAR = false>
 PSK_DEV void fit_sums_chain(bool with_y, int lane, int lane_last, uint32_t q0, uint32_t n, float xd, float sizef_steady,
                             double ySum_c, double xySum_c, const bool (&valid)[kR], const float *yring, uint32_t ymask,
-                            const float (&y)[kR], double (&ySum_l)[kR], double (&xySum_l)[kR])
+                            const float (&y)[kR], double (&ySum_l)[kR], double (&xySum_l)[kR], const float *z_far = nullptr)
 {
     const double xdd = (double)xd;
     // operands rebuilt from what the block left behind (the ring holds every y of the window).  Pops where the
@@ -622,7 +647,7 @@ PSK_DEV void fit_sums_chain(bool with_y, int lane, int lane_last, uint32_t q0, u
         const uint32_t before = q0 + (uint32_t)(2 * lane + r);
         steady[r] = WARM ? before >= n : true;
         const float sizef = WARM ? (float)(steady[r] ? n - 1 : before) : sizef_steady;
-        const float zf = yring[(before - n) & ymask];
+        const float zf = FAR ? z_far[r] : yring[(before - n) & ymask];
         zz[r] = steady[r] ? (double)zf : 0.0;
         yy[r] = (double)y[r];
         float tf = y[r] * sizef;  // :78, size before the push
@@ -673,11 +698,13 @@ PSK_DEV void fit_sums_chain(bool with_y, int lane, int lane_last, uint32_t q0, u
 // the block's last valid symbol.
 // WIDE (the exact tier): numWraps kept as the 64-bit integer the reference has -- an estimate that is NaN or astronomically
 // large (what a non-finite sample leaves behind) unwraps by counts far beyond 2^31, and (long)NaN is LONG_MIN on x86.
-template <bool WARM, bool WIDE>
+// FAR: the ring is the far fit's (see far_ring_fence): `z_far` holds the values leaving the window, the passes touch no memory.
+template <bool WARM, bool WIDE, bool FAR = false>
 PSK_DEV int fit_block(int lane, uint32_t q0, uint32_t n, float xd, float den_s, float xavg_s, const FitKnown &fk,
                       const bool (&valid)[kR], const float (&raw)[kR], const FastCarry &cy,
                       float *yring, uint32_t ymask, float (&y)[kR], float (&est)[kR], double (&ySum_l)[kR], double (&xySum_l)[kR],
-                      int lane_last, int r_last, float &den_last, float &xavg_last, bool cheap, int &rejected, float &m_last)
+                      int lane_last, int r_last, float &den_last, float &xavg_last, bool cheap, int &rejected, float &m_last,
+                      const float *z_far = nullptr)
 {
     uint32_t before[kR];
     bool steady[kR];
@@ -729,15 +756,23 @@ PSK_DEV int fit_block(int lane, uint32_t q0, uint32_t n, float xd, float den_s, 
         for (int r = 0; r < kR; r++) {
             double yd = (double)raw[r] + (double)(long long)w[r] * two_pi;  // cpp/psk_soft.cpp:478 (thisPhase is a float widened, :474)
             y[r] = (float)yd;                                         // next(float yval), :481
-            if (valid[r])
-                yring[before[r] & ymask] = y[r];
+            if constexpr (!FAR) {
+                if (valid[r])
+                    yring[before[r] & ymask] = y[r];
+            }
         }
-        wave_lds_fence();
+        if constexpr (!FAR)
+            wave_lds_fence();
         float z[kR];
 #pragma unroll
-        for (int r = 0; r < kR; r++)
-            z[r] = steady[r] ? yring[(before[r] - n) & ymask] : 0.0f;  // yvals.front(), :70
-        wave_lds_fence();
+        for (int r = 0; r < kR; r++) {
+            if constexpr (FAR)
+                z[r] = steady[r] ? z_far[r] : 0.0f;
+            else
+                z[r] = steady[r] ? yring[(before[r] - n) & ymask] : 0.0f;  // yvals.front(), :70
+        }
+        if constexpr (!FAR)
+            wave_lds_fence();
         // candidate sums, wave-parallel (positions past the end need no masking: a prefix sum never looks ahead)
         double ys_prev, xs_prev;
         {
@@ -827,6 +862,13 @@ PSK_DEV int fit_block(int lane, uint32_t q0, uint32_t n, float xd, float den_s, 
     if (WARM) {
         den_last = read_lane(r_last ? den_l[1] : den_l[0], lane_last);
         xavg_last = read_lane(r_last ? xavg_l[1] : xavg_l[0], lane_last);
+    }
+    if constexpr (FAR) {
+        // the block's values, once, now that their counts are final (what follows changes sums and estimates only)
+#pragma unroll
+        for (int r = 0; r < kR; r++)
+            if (valid[r])
+                yring[before[r] & ymask] = y[r];
     }
     return pass;
 }
@@ -1073,10 +1115,11 @@ PSK_DEV void exact_block_from_ring(const ERingT<ering_dynamic(S)> &er, int base,
 // Feedback unwrap + LinearFit::next over one block of 128 symbols (reference cpp/psk_soft.cpp:476-481, 48-87): the
 // raw phases in, the phase estimates out, the carried sums / estimate / window bookkeeping of `cy` advanced to the
 // block's last valid position.  `c` = index of the block in the call.
-template <bool EXACT>
+// FAR: the ring is the far fit's, in device memory, and `z_far` the block's leaving values (far_ring_preread).
+template <bool EXACT, bool FAR = false>
 PSK_DEV void fit_stage(int c, int lane, uint32_t n, float xd, float den_s, float xavg_s, const FitKnown &fk, const bool (&valid)[kR],
                        const float (&raw)[kR], int nvalid, int lane_last, int r_last, float *yring, uint32_t ymask, FastCarry &cy,
-                       float (&est)[kR])
+                       float (&est)[kR], const float *z_far = nullptr)
 {
     const uint32_t q0 = cy.q;
     float y[kR];
@@ -1090,11 +1133,11 @@ PSK_DEV void fit_stage(int c, int lane, uint32_t n, float xd, float den_s, float
     const bool warm = !__builtin_expect(q0 >= n && n != 1u, 1);
     const bool cheap = cy.chain_run != 0;  // the recurrence ran on the last blocks: do not bother with candidates
     if (!warm) {
-        pass = fit_block<false, EXACT>(lane, q0, n, xd, den_s, xavg_s, fk, valid, raw, cy, yring, ymask, y, est, ySum_l, xySum_l,
-                                lane_last, r_last, den_last, xavg_last, cheap, rejected, m_lane);
+        pass = fit_block<false, EXACT, FAR>(lane, q0, n, xd, den_s, xavg_s, fk, valid, raw, cy, yring, ymask, y, est, ySum_l, xySum_l,
+                                lane_last, r_last, den_last, xavg_last, cheap, rejected, m_lane, z_far);
     } else {
-        pass = fit_block<true, EXACT>(lane, q0, n, xd, den_s, xavg_s, fk, valid, raw, cy, yring, ymask, y, est, ySum_l, xySum_l,
-                               lane_last, r_last, den_last, xavg_last, cheap, rejected, m_lane);
+        pass = fit_block<true, EXACT, FAR>(lane, q0, n, xd, den_s, xavg_s, fk, valid, raw, cy, yring, ymask, y, est, ySum_l, xySum_l,
+                               lane_last, r_last, den_last, xavg_last, cheap, rejected, m_lane, z_far);
     }
 #ifdef PSK_ABL_NOCHAIN  /* (ablation builds only: what the chain costs) */
     rejected = 0;
@@ -1105,9 +1148,9 @@ PSK_DEV void fit_stage(int c, int lane, uint32_t n, float xd, float den_s, float
         // differ from these by an ulp here and there: a count that would change under them (a feedback within
         // an ulp of the half-way point of the unwrap) sends the call to the reference-order kernel.
         if (!warm)
-            fit_sums_chain<false>((rejected & 1) != 0, lane, lane_last, q0, n, xd, fk.sizef, cy.ySum, cy.xySum, valid, yring, ymask, y, ySum_l, xySum_l);
+            fit_sums_chain<false, FAR>((rejected & 1) != 0, lane, lane_last, q0, n, xd, fk.sizef, cy.ySum, cy.xySum, valid, yring, ymask, y, ySum_l, xySum_l, z_far);
         else
-            fit_sums_chain<true>(true, lane, lane_last, q0, n, xd, fk.sizef, cy.ySum, cy.xySum, valid, yring, ymask, y, ySum_l, xySum_l);
+            fit_sums_chain<true, FAR>(true, lane, lane_last, q0, n, xd, fk.sizef, cy.ySum, cy.xySum, valid, yring, ymask, y, ySum_l, xySum_l, z_far);
         float est2[kR];
 #pragma unroll
         for (int r = 0; r < kR; r++) {

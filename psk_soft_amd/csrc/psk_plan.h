@@ -65,6 +65,10 @@ enum LfFlags : uint32_t {
     // the packet is complex binary16 (PSK_SOFT_FORMAT_CF16): the same two flags for it (the PSK_INST_PKT=cf16 builds)
     PLAN_CF16 = 4096u,
     PLAN_CF16_IN_PLACE = 8192u,
+    // a fit window no LDS ring holds (phaseAvg > 32640) with PSK_SOFT_OPT_FAR_FIT on: always PLAN_ANYFRONT, whatever the window
+    // class, and the fit stage behind the front stage is the one with its ring in device memory (psk_farfit.hip), on launch lists
+    // of its own; ChanPlan::far_row is the channel's row of that scratch
+    PLAN_FARFIT = 16384u,
 };
 
 
@@ -115,7 +119,7 @@ struct ChanPlan {
     // time-tiled kernels (PLAN_TILED): where this channel's symbols and tiles sit in the scratch of the call
     uint32_t tile_blocks;  // 128-symbol blocks per tile
     uint32_t tile_base;    // index of the channel's first TileInfo
-    uint32_t tile_pad;
+    uint32_t far_row;      // (PLAN_FARFIT) the channel's row in the scratch of the far fit's rings (psk_farfit.hip)
     uint64_t tile_off;     // offset of its first symbol in the raw-phase / picked-sample / estimate arrays
     // word 0 of the header in front of the call's plans in device memory (plan_header() below): the kernel that hands this
     // channel's call over counts it there.  (In every plan, although every kernel could find the header from its `plans`

@@ -35,6 +35,55 @@ constexpr uint32_t kGridYMax = 65535u;  // channels of one launch of the kernels
 
 PSK_DEV bool tile_plan_mine(const ChanPlan &p) { return p.mode == PLAN_FAST && (p.lf_flags & PLAN_TILED) && p.n_out != 0; }
 
+// What the tiles of the front kernel found, folded over the call: true = the call is not theirs to carry.
+PSK_DEV bool tile_fold(const ChanPlan &p, const TileInfo *ti, int n_tiles, int lane, int &exact_blocks_out, float &emax_out)
+{
+    float emax = 0.0f;
+    unsigned umax = 0u, umin1 = 0xFFFFFFFFu, refuse_b = 0u, gap_b = 0x7F800000u, cap_b = 0x7F800000u, wmax_b = 0u;
+    int exact_blocks = 0;
+    for (int j = lane; j < n_tiles; j += kWave) {
+        const TileInfo t = ti[j];
+        umax = t.umax > umax ? t.umax : umax;
+        umin1 = t.umin1 < umin1 ? t.umin1 : umin1;
+        refuse_b |= t.refuse;
+        const unsigned g = __float_as_uint(t.gap_rel), cp = __float_as_uint(t.cap), w = __float_as_uint(t.wmax);
+        gap_b = g < gap_b ? g : gap_b;
+        cap_b = cp < cap_b ? cp : cap_b;
+        // (a NaN maximum -- bit pattern above inf's -- stays on top and fails both comparisons below)
+        wmax_b = w > wmax_b ? w : wmax_b;
+        exact_blocks += (int)t.stat_exact;
+        emax = __builtin_fmaxf(emax, t.emax);
+    }
+    emax_out = wave_max_f32(__builtin_fmaxf(emax, 0.0f));
+    umax = wave_max_u32(umax);
+    umin1 = wave_min_u32(umin1);
+    gap_b = wave_min_u32(gap_b);
+    cap_b = wave_min_u32(cap_b);
+    wmax_b = wave_max_u32(wmax_b);
+    exact_blocks = __builtin_amdgcn_readlane(wave_scan_i32(exact_blocks), 63);
+    bool refuse = __any(refuse_b != 0u);
+    {
+        const float wmax = __uint_as_float(wmax_b);
+        // the screening thresholds of every tile must cover the drift of the reference's sums at the scale of the call
+        // (a silent call: every window sum is exactly zero, `wmax` is the denormal the phase-index bits of the screening's
+        // argmax leave behind, thresholds and `cap` are zero -- and the first phase wins there as in the reference)
+        if (!(wmax <= __uint_as_float(cap_b)) && !(wmax < 1.0e-37f))
+            refuse = true;
+        // an exact re-decision closer than that drift: only the exactness guard (quirk Q8) can vouch for it
+        const bool ambiguous = !(__uint_as_float(gap_b) > wmax);
+        if (umin1 != 0xFFFFFFFFu && ambiguous) {
+            int emax = (int)(umax >> 23), emin = (int)((umin1 + 1u) >> 23);
+            emax = emax < 1 ? 1 : emax;
+            emin = emin < 1 ? 1 : emin;
+            const int terms_log2 = 32 - __builtin_clz((unsigned)(p.A + 2u * kB));
+            if (24 + (emax - emin) + terms_log2 > 52)
+                refuse = true;
+        }
+    }
+    exact_blocks_out = exact_blocks;
+    return refuse;
+}
+
 // ---- front: grid (tiles, channels of the launch) ----
 template <int SV, int HV>
 __global__ __launch_bounds__(64) void psk_tile_front_kernel(const ChanPlan *__restrict__ plans, const uint32_t *__restrict__ list, uint32_t ch0,

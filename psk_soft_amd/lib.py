@@ -351,6 +351,7 @@ class Handle:
     OPT_PARALLEL_FIT = 4  # tiled calls: 0 fit block by block, 1 parallel fit with the second round on demand (default), 2 always
 
     OPT_QUALITY = 6  # 1: every process call ends with the per-channel reduction pass, see quality()
+    OPT_FAR_FIT = 7  # 1: phaseAvg above 32640 on the fast path, the fit window in device memory (default 0: reference-order kernel)
 
     def set_option(self, option, value):
         _check(self._L.psk_soft_set_option(self._h, int(option), int(value)))

@@ -38,6 +38,11 @@ CS8 = float(os.environ.get("PSK_FUZZ_CS8", "0"))
 # with the model (tests/quality_model.py) applied to the rows the call returned: counts, copied values, snapshot and flags equal,
 # the sums within the bound of n doubles added in any order.  The streams themselves are compared as always.
 QUALITY = os.environ.get("PSK_FUZZ_QUALITY", "0") != "0"
+# PSK_FUZZ_FAR_FIT=p: PSK_SOFT_OPT_FAR_FIT is on, and with probability p a channel's phaseAvg is drawn above 32640 (the fit window in
+# device memory, psk_farfit.hip; symbols enough that the window fills now and then).  The draws come from a generator of their own:
+# 0, the default, leaves every other draw of a seed as it was.
+FAR_FIT = float(os.environ.get("PSK_FUZZ_FAR_FIT", "0"))
+FAR_N = [32641, 32768, 40000, 65535]
 TOL = 1e-5
 STRICT = os.environ.get("PSK_FUZZ_STRICT", "1") != "0"  # every float of soft / phase must equal the oracle's
 XD = 0.01
@@ -121,14 +126,20 @@ def main():
         cs16 = []  # per channel: None (float32), "all" (every packet int16) or "alt" (int16 and float32 packets call by call),
         # "cs8" (every packet int8) or "rot" (int8, int16 and float32 packets in turn)
         crng8 = random.Random(seed * 1000 + rnd + 0x5C08)
+        crngf = random.Random(seed * 1000 + rnd + 0xFA12)
         for c in range(C):
             S = rng.choice(S_CHOICES)
             A = rng.choice(A_CHOICES)
             M = rng.choice(M_CHOICES)
             n = rng.choice(N_CHOICES)
+            far = bool(FAR_FIT) and crngf.random() < FAR_FIT
+            if far:
+                n = crngf.choice(FAR_N)
             p = dict(samplesPerBaud=S, constelationSize=M, numAvg=A, phaseAvg=n, differentialDecoding=int(rng.random() < 0.25))
             # (wide symbols, samplesPerBaud > 1024: a few dozen to a few hundred symbols -- at 65535 that is already ~10^7 samples)
             N = max(S * rng.choice([50, 300, 1200, 3000, 12000] if S <= 1024 else [20, 60, 150]), 64)
+            if far and S <= 32:
+                N = min(S * crngf.choice([12000, 50000, 90000]), int(os.environ.get("PSK_FUZZ_PACKET", 1 << 20)))
             sig = make_signal(rng, nrng, M, max(S, 1), N)
             # script: a list of events; cuts with occasional tiny / empty packets, property changes, resets
             n_calls = rng.choice([1, 2, 3, 5])
@@ -167,9 +178,11 @@ def main():
             if os.environ.get("PSK_FUZZ_DUMP") and int(os.environ["PSK_FUZZ_DUMP"]) == c:  # with a single-round replay: keep this channel's case
                 np.save(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "fuzz_case_sig.npy"), sig)
                 print("DUMPED channel %d: props=%s script=%s" % (c, p, ev))
-        h = pl.Handle(C, device=0, max_window_samples=int(os.environ.get("PSK_FUZZ_WINDOW", 33 * 1024 + 64)), max_phase_avg=max(2048, max(N_CHOICES)),
+        h = pl.Handle(C, device=0, max_window_samples=int(os.environ.get("PSK_FUZZ_WINDOW", 33 * 1024 + 64)), max_phase_avg=max(2048, max(N_CHOICES), max(FAR_N) if FAR_FIT else 0),
                       max_packet_complex=int(os.environ.get("PSK_FUZZ_PACKET", 1 << 20)))
         h.configure(0, props)
+        if FAR_FIT:
+            h.set_option(pl.Handle.OPT_FAR_FIT, 1)
         if QUALITY:
             from tests import quality_model as qm
 
