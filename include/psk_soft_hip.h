@@ -227,6 +227,62 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
                                                 const uint64_t *sample_stride /* [nch], or NULL */,
                                                 psk_soft_output_t *outs /* [nch] */, void *stream);
 
+/* ---- tuned packets: a frequency shift per packet, applied on the GPU in front of the demodulator ------------------------------
+ * A channelizer delivers each signal wherever it falls inside its bin, and the M-th-power phase tracker of serviceFunction()
+ * (reference cpp/psk_soft.cpp:474-482) follows only a small carrier offset: lock (psk_soft_quality_derive) falls from 0.98 at
+ * 0.05 cycles per symbol to 0.1 at 0.10 for QPSK, and is gone at 0.05 for 8-PSK.  A tuned packet is multiplied by a numerically
+ * controlled oscillator before anything else looks at it.
+ *
+ * The definition (host and device alike).  phase and step are in turns x 2^64; all arithmetic on them is mod 2^64.  Sample k
+ * (k = 0 .. n_floats / 2 - 1) of the packet is
+ *   - converted to float exactly, as its format defines (above);
+ *   - multiplied by the phasor W(p_k), p_k = phase + k * step, taken from two tables of 1024 entries with
+ *       h = p_k >> 54,  l = (p_k >> 44) & 1023          (the top 20 bits; the phase word is truncated, as in any DDS)
+ *       C[h] = (cosf(a), sinf(a)),  a = (float)((double)h * 0x1.921fb54442d18p-8)     (pi / 512)
+ *       F[l] = (cosf(b), sinf(b)),  b = (float)((double)l * 0x1.921fb54442d18p-18)    (pi / 2^19)
+ *     cosf and sinf being glibc 2.35's (the library carries them: they do not depend on the libm it runs with),
+ *       W = (Cr*Fr - Ci*Fi,  Cr*Fi + Ci*Fr)
+ *       y = (xr*Wr - xi*Wi,  xr*Wi + xi*Wr)
+ *     every operation float32, rounded once, no fused multiply-add, denormals kept.
+ * W(0) = (1, 0) exactly; | |W| - 1 | <= 1.4e-7; the angle of W is that of the truncated phase to 3.3e-7 rad, on top of the
+ * quantum of 6e-6 rad (2 pi / 2^20).
+ * The result of the call is bit for bit what the contiguous PSK_SOFT_FORMAT_CF32 packet holding the y values gives: all four
+ * streams, counts, SRI fields, warnings, statistics and quality records, under every schedule and option.  That contract covers
+ * samples whose y is finite; with a non-finite sample or product the formula above is still what runs, and which NaN comes out
+ * is unspecified.  A packet whose tune is {0, 0} is not tuned at all: it takes exactly the path it takes without `tune`, the
+ * in-place builds of the integer formats included, and keeps the sign of -0.
+ * The oscillator's state belongs to the caller: the library keeps nothing between calls (state blobs are unchanged); the phase
+ * word of a stream's next packet is psk_soft_tune_advance(). */
+typedef struct psk_soft_tune {
+    uint64_t phase;   /* phase word of the packet's sample 0  */
+    uint64_t step;    /* phase increment per complex sample   */
+} psk_soft_tune_t;
+
+/* psk_soft_process_device_strided with tune[i] applied to packet i.  tune == NULL is psk_soft_process_device_strided: the same
+ * code path.  Strides are checked and refused as there; every phase / step value is valid.  One call may mix tuned and untuned
+ * packets, strides and formats.
+ * How: one more launch on `stream` behind the gathers writes every tuned packet, shifted, as a float2 row (8 bytes a sample,
+ * whatever the packet's format; 128-byte aligned) of the gather scratch, and the ordinary call runs on those rows as on CF32
+ * packets.  A tuned strided packet in a run the tiled transpose takes (at least 8 adjacent columns, see above) is first gathered
+ * into a row of its own format and tuned from there; any other tuned packet, contiguous or strided, is read where it lies.
+ * Scratch, descriptor slots, events and the deferred-join rule are those of psk_soft_process_device_strided.
+ * A control-plane-only handle checks, then plans and counts like psk_soft_process_device.  No host-pointer counterpart. */
+psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
+                                              const psk_soft_packet_t *pkts /* [nch] */,
+                                              const uint64_t *sample_stride /* [nch], or NULL */,
+                                              const psk_soft_tune_t *tune /* [nch], or NULL */,
+                                              psk_soft_output_t *outs /* [nch] */, void *stream);
+
+/* Host only, pure.
+ * psk_soft_tune_step: the step word of a shift by `cycles_per_sample` (negative = downwards): r = f - floor(f), the result
+ *   (uint64_t)(r * 2^64), truncated, mod 2^64; 0 for a non-finite f.  To take a channel's carrier offset of f cycles per
+ *   sample OUT, tune with psk_soft_tune_step(-f).
+ * psk_soft_tune_advance: phase + step * n_complex (mod 2^64): the phase word of the next packet of a continuous stream.
+ * psk_soft_tune_apply: the definition above for n_complex CF32 samples, in to out (in == out allowed). */
+uint64_t psk_soft_tune_step(double cycles_per_sample);
+uint64_t psk_soft_tune_advance(uint64_t phase, uint64_t step, uint64_t n_complex);
+psk_soft_status psk_soft_tune_apply(const psk_soft_tune_t *tune, const float *in, uint64_t n_complex, float *out);
+
 /* PSK_SOFT_OPT_DEFERRED_JOIN: make `stream` (a hipStream_t; NULL = the handle's own) wait for everything the calls made so
  * far have put on the handle's side streams -- the point in stream order behind which their results may be used.  A no-op
  * without pending deferred calls.  (There is no counterpart in the reference: its serviceFunction() is synchronous.) */

@@ -26,6 +26,7 @@
 #include "psk_plan.h"
 #include "psk_quality.h"
 #include "psk_soft_hip.h"
+#include "psk_tune.h"
 
 namespace psk {
 hipError_t launch_fast(int S, int H, int exact, const ChanPlan *plans, const uint32_t *list, uint32_t ch0, uint32_t nch, ChanState *states,
@@ -466,6 +467,7 @@ struct psk_soft_handle {
     GatherDescSlot gdesc[kGatherDescSlots];
     uint64_t gat_calls = 0;
     int gdesc_turn = 0;
+    float *d_tune_tab = nullptr;  // tuned packets: the two phasor tables (psk_tune.h), uploaded when the first tuned packet comes
     int opt_diag_gather_only = 0;  // PSK_SOFT_DIAG_GATHER_ONLY=1 (environment, timing experiments only -- tools/strided_rates.py): a
                                    // strided call gathers and returns; the ordinary call behind it is left out, outs[] untouched
     // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
@@ -743,6 +745,7 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
             if (g.h_buf) (void)hipHostFree(g.h_buf);
             if (g.d_buf) (void)hipFree(g.d_buf);
         }
+        if (h->d_tune_tab) (void)hipFree(h->d_tune_tab);
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
             if (sl.h_buf) (void)hipHostFree(sl.h_buf);
@@ -2320,10 +2323,17 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
 // rows and the ordinary call runs on it.  process_round, the plans, the cut into pieces and every kernel behind it see contiguous
 // packets.  Runs of packets that are adjacent columns of one frame-major matrix (frame groups, psk_gather.h) go through the tile
 // kernel, the rest through the plain strided gather.
-psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                                const uint64_t *sample_stride, psk_soft_output_t *outs, void *stream_v)
+//
+// Tuned packets (`tune` non-NULL and the packet's {phase, step} not {0, 0}; psk_soft_process_device_strided, below, is this
+// entry with tune == NULL) go through the same machinery: behind the gathers one launch of the tune kernel (psk_tune.hip) writes
+// each of them, shifted, as a float2 row of the same scratch, and the packet copy points at that row with format CF32.  The kernel reads a contiguous packet where the caller
+// has it, a column of a frame group of at least kGatherMinGroup columns from the own-format row the tile kernel has just written,
+// and any other strided packet where it lies, at its stride (no gather of its own).
+psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                              const uint64_t *sample_stride, const psk_soft_tune_t *tune, psk_soft_output_t *outs,
+                                              void *stream_v)
 {
-    if (!sample_stride)
+    if (!sample_stride && !tune)
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
     if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
@@ -2331,17 +2341,29 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
     // that does not start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
     auto known = [](const psk_soft_packet_t &k) { return psk::pkt_format_known(k.format); };
     // (a strided packet the call reads: present, complex data, at least one sample)
+    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
     auto gathered = [&](uint32_t i) {
         const psk_soft_packet_t &k = pkts[i];
-        return k.present && sample_stride[i] != 1 && k.sri_mode == 1 && k.n_floats >= 2 && k.data;
+        return k.present && stride_of(i) != 1 && k.sri_mode == 1 && k.n_floats >= 2 && k.data;
     };
-    uint32_t n_gather = 0;
+    // (a packet the tune kernel reads: tuned, present, complex data, at least one sample, of a format the library knows)
+    auto tuned = [&](uint32_t i) {
+        const psk_soft_packet_t &k = pkts[i];
+        return tune && (tune[i].phase | tune[i].step) != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && k.data && known(k);
+    };
+    uint32_t n_gather = 0, n_tune = 0;
     bool unknown = false;
     for (uint32_t i = 0; i < nch; i++) {
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
-        const uint64_t s = sample_stride[i];
+        const uint64_t s = stride_of(i);
+        if (s == 1 && tuned(i)) {
+            if (reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
+                return fail(PSK_SOFT_ERR_INVALID_ARG,
+                            "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
+            n_tune++;
+        }
         char buf[160];
         if (!s) {
             std::snprintf(buf, sizeof buf, "psk_soft_process_device_strided: channel %u: a sample stride of 0", ch0 + i);
@@ -2366,9 +2388,10 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
             return fail(PSK_SOFT_ERR_INVALID_ARG,
                         "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
         n_gather++;
+        n_tune += tuned(i);
     }
     // (a control-plane-only handle plans and counts: lengths and formats are all it looks at)
-    if (!n_gather || unknown || h->dry)
+    if ((!n_gather && !n_tune) || unknown || h->dry)
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
 
     PSK_HIP(hipSetDevice(h->device));
@@ -2378,10 +2401,14 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
         uint32_t first, g, bytes;
     };
     std::vector<Run> runs;
-    std::vector<size_t> row_off(nch, 0);
+    std::vector<size_t> row_off(nch, 0), tune_off(n_tune ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned packet)
     size_t need = 0;
     for (uint32_t i = 0; i < nch;) {
         if (!gathered(i)) {
+            if (tuned(i)) {
+                tune_off[i] = need;
+                need += align_up(sizeof(float2) * (size_t)(pkts[i].n_floats / 2u), 128);
+            }
             i++;
             continue;
         }
@@ -2392,8 +2419,15 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
             j++;
         runs.push_back({i, j - i, sb});
         for (uint32_t c = i; c < j; c++) {
-            row_off[c] = need;
-            need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
+            // (a tuned column outside the tile kernel's groups has no own-format row: the tune kernel reads it where it lies)
+            if (!tuned(c) || j - i >= psk::kGatherMinGroup) {
+                row_off[c] = need;
+                need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
+            }
+            if (tuned(c)) {
+                tune_off[c] = need;
+                need += align_up(sizeof(float2) * (size_t)(pkts[c].n_floats / 2u), 128);
+            }
         }
         i = j;
     }
@@ -2405,12 +2439,13 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
         if (r.g >= psk::kGatherMinGroup)
             n_groups[b]++, n_cols[b] += r.g;
         else
-            n_singles[b] += r.g;
+            for (uint32_t c = r.first; c < r.first + r.g; c++) n_singles[b] += !tuned(c);
     }
     const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
     const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
     const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
-    const size_t desc_bytes = off_singles + sizeof(psk::GatherSingle) * tot_singles;
+    const size_t off_tune = off_singles + sizeof(psk::GatherSingle) * tot_singles;
+    const size_t desc_bytes = off_tune + sizeof(psk::TuneDesc) * n_tune;
 
     // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
     // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
@@ -2442,6 +2477,10 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
     }
     sc->stream = stream;
     sc->last_use = ++h->gat_calls;
+    if (n_tune && !h->d_tune_tab) {  // (once per handle)
+        PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
+        PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
+    }
     GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
     h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
     if (!ds.ev)
@@ -2462,14 +2501,17 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
     psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
     psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + off_cols);
     psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
+    psk::TuneDesc *const ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + off_tune);
     uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
     uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
     const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
-    uint64_t n_tiles[3] = {}, max_n_single[3] = {};
+    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0;
     std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
     for (const Run &r : runs) {
         const int b = size_idx(r.bytes);
-        for (uint32_t c = r.first; c < r.first + r.g; c++) pk[c].data = reinterpret_cast<const float *>(sc->buf + row_off[c]);
+        for (uint32_t c = r.first; c < r.first + r.g; c++)
+            if (!tuned(c))
+                pk[c].data = reinterpret_cast<const float *>(sc->buf + row_off[c]);
         if (r.g >= psk::kGatherMinGroup) {
             psk::GatherGroup &g = hg[g_at[b]++];
             g = psk::GatherGroup{};
@@ -2487,10 +2529,36 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
             n_tiles[b] += (uint64_t)g.tiles_c * ((g.n_max + psk::kGatherTile - 1u) / psk::kGatherTile);
         } else {
             for (uint32_t c = r.first; c < r.first + r.g; c++) {
+                if (tuned(c))
+                    continue;
                 const uint64_t n = pkts[c].n_floats / 2u;
                 hs[s_at[b]++] = psk::GatherSingle{pkts[c].data, sc->buf + row_off[c], sample_stride[c], n};
                 max_n_single[b] = n > max_n_single[b] ? n : max_n_single[b];
             }
+        }
+    }
+    // the tuned packets: from the row the tile kernel writes (its columns), else from where the caller has them, at their stride
+    {
+        std::vector<uint8_t> in_group(n_tune ? nch : 0, 0);
+        for (const Run &r : runs)
+            if (n_tune && r.g >= psk::kGatherMinGroup)
+                std::fill(in_group.begin() + r.first, in_group.begin() + r.first + r.g, (uint8_t)1);
+        uint32_t t_at = 0;
+        for (uint32_t c = 0; c < nch && n_tune; c++) {
+            if (!tuned(c))
+                continue;
+            psk::TuneDesc &d = ht[t_at++];
+            d = psk::TuneDesc{};
+            d.src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
+            d.dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
+            d.stride = in_group[c] ? 1u : stride_of(c);
+            d.n = pkts[c].n_floats / 2u;
+            d.phase = tune[c].phase, d.step = tune[c].step;
+            d.format = pkts[c].format;
+            max_n_tune = d.n > max_n_tune ? d.n : max_n_tune;
+            pk[c].data = d.dst;
+            pk[c].n_floats = 2u * d.n;
+            pk[c].format = PSK_SOFT_FORMAT_CF32;
         }
     }
     PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
@@ -2521,6 +2589,10 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
                 PSK_HIP(psk::launch_gather_singles(bytes, dsg + s_lo[b], n_singles[b], max_n_single[b], stream));
             }
         }
+        if (n_tune) {  // (cnt = tuned packets)
+            PSK_HIP(mark("tune", 8, n_tune, 0));
+            PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + off_tune), n_tune, max_n_tune, h->d_tune_tab, stream));
+        }
         return PSK_SOFT_OK;
     };
     psk_soft_status st = enqueue();
@@ -2539,6 +2611,36 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
     }
     g_last_error = keep;
     return st;
+}
+
+psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                                const uint64_t *sample_stride, psk_soft_output_t *outs, void *stream_v)
+{
+    return psk_soft_process_device_tuned(h, ch0, nch, pkts, sample_stride, nullptr, outs, stream_v);
+}
+
+// ---- tuned packets: the host-side helpers (pure) ----
+uint64_t psk_soft_tune_step(double cycles_per_sample)
+{
+    if (!std::isfinite(cycles_per_sample))
+        return 0;
+    const double r = cycles_per_sample - std::floor(cycles_per_sample);  // [0, 1]; 1 (a tiny negative rate) wraps to 0
+    return r >= 1.0 ? 0 : (uint64_t)(r * 0x1p64);
+}
+
+uint64_t psk_soft_tune_advance(uint64_t phase, uint64_t step, uint64_t n_complex) { return phase + step * n_complex; }
+
+psk_soft_status psk_soft_tune_apply(const psk_soft_tune_t *tune, const float *in, uint64_t n_complex, float *out)
+{
+    if (!tune || (n_complex && (!in || !out)))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_tune_apply: null pointer");
+    const float *const tab = psk::tune_tables();
+    uint64_t p = tune->phase;
+    for (uint64_t k = 0; k < n_complex; k++, p += tune->step) {
+        const float xr = in[2u * k], xi = in[2u * k + 1u];  // (in == out is fine)
+        psk::tune_rotate(tab, p, xr, xi, &out[2u * k], &out[2u * k + 1u]);
+    }
+    return PSK_SOFT_OK;
 }
 
 // ---- host-buffer path: the ingest pipeline --------------------------

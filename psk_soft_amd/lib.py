@@ -136,6 +136,12 @@ class QualityDerived(ctypes.Structure):
     ]
 
 
+class Tune(ctypes.Structure):
+    """psk_soft_tune_t: phase word of a packet's sample 0 and step per complex sample, both in turns x 2^64."""
+
+    _fields_ = [("phase", ctypes.c_uint64), ("step", ctypes.c_uint64)]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_hip.h declares
@@ -162,6 +168,10 @@ EXPORTS = (
     "psk_soft_output_capacity",
     "psk_soft_process_device",
     "psk_soft_process_device_strided",
+    "psk_soft_process_device_tuned",
+    "psk_soft_tune_step",
+    "psk_soft_tune_advance",
+    "psk_soft_tune_apply",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -206,6 +216,14 @@ def load():
     L.psk_soft_output_capacity.restype = u64
     L.psk_soft_process_device.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(Output), vp]
     L.psk_soft_process_device_strided.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Output), vp]
+    L.psk_soft_process_device_tuned.argtypes = [
+        vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Tune), ctypes.POINTER(Output), vp
+    ]
+    L.psk_soft_tune_step.argtypes = [ctypes.c_double]
+    L.psk_soft_tune_step.restype = u64
+    L.psk_soft_tune_advance.argtypes = [u64, u64, u64]
+    L.psk_soft_tune_advance.restype = u64
+    L.psk_soft_tune_apply.argtypes = [ctypes.POINTER(Tune), vp, u64, vp]
     L.psk_soft_process_host.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(Output)]
     L.psk_soft_synchronize.argtypes = [vp]
     L.psk_soft_join.argtypes = [vp, vp]
@@ -289,6 +307,27 @@ def quality_derive(q):
     d = QualityDerived()
     _check(load().psk_soft_quality_derive(ctypes.byref(q), ctypes.byref(d)))
     return {k: getattr(d, k) for k, _ in QualityDerived._fields_}
+
+
+def tune_step(cycles_per_sample):
+    """psk_soft_tune_step: the step word (turns x 2^64) of a shift by `cycles_per_sample`; negate a channel's offset to remove it."""
+    return int(load().psk_soft_tune_step(float(cycles_per_sample)))
+
+
+def tune_advance(phase, step, n_complex):
+    """psk_soft_tune_advance: the phase word of the next packet of a continuous stream."""
+    return int(load().psk_soft_tune_advance(int(phase), int(step), int(n_complex)))
+
+
+def tune_apply(phase, step, iq):
+    """psk_soft_tune_apply on the host: interleaved float32 I/Q in, the shifted interleaved float32 I/Q out (a new array;
+    an odd last element is dropped)."""
+    x = np.ascontiguousarray(iq, np.float32)
+    n = x.size // 2
+    y = np.empty(2 * n, np.float32)
+    t = Tune(int(phase), int(step))
+    _check(load().psk_soft_tune_apply(ctypes.byref(t), x.ctypes.data, n, y.ctypes.data))
+    return y
 
 
 class Handle:
@@ -381,6 +420,18 @@ class Handle:
         if strides is not None and len(strides) != len(pkts):
             raise ValueError("one stride per packet")
         _check(self._L.psk_soft_process_device_strided(self._h, ch0, len(pkts), pkts, strides, outs, ctypes.c_void_p(stream or 0)))
+
+    def process_device_tuned(self, ch0, pkts, strides, tunes, outs, stream=None):
+        """process_device_strided with a frequency shift per packet, applied on the GPU in front of the demodulator.  tunes:
+        None (nothing tuned), a ctypes Tune array or a sequence of (phase, step) pairs, one per packet; (0, 0) leaves a packet
+        untuned.  strides as for process_device_strided."""
+        if strides is not None and not isinstance(strides, ctypes.Array):
+            strides = (ctypes.c_uint64 * len(strides))(*[int(s) for s in strides])
+        if tunes is not None and not isinstance(tunes, ctypes.Array):
+            tunes = (Tune * len(tunes))(*[Tune(int(p), int(s)) for p, s in tunes])
+        if (strides is not None and len(strides) != len(pkts)) or (tunes is not None and len(tunes) != len(pkts)):
+            raise ValueError("one stride and one tune per packet")
+        _check(self._L.psk_soft_process_device_tuned(self._h, ch0, len(pkts), pkts, strides, tunes, outs, ctypes.c_void_p(stream or 0)))
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with
