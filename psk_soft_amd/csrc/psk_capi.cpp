@@ -211,37 +211,39 @@ private:
     bool stop_ = false;
 };
 
+// One launch set of a call: the channels that go through the same launches, listed together in the compact lists behind the plans;
+// first what the plan pass counts (account), then where and how the set runs (fill_lists, place_tiles).  Plain data, zeroed with the
+// PlanSummary that holds it.
+struct LaunchSet {
+    uint64_t blocks;           // 128-symbol blocks of its calls, in all
+    uint32_t cnt, max_blocks;  // channels; blocks of its longest call
+    // LDS rings of a launch are sized for the largest phaseAvg / numAvg among its channels: a ring of
+    // y_len unwrapped phases (a power of two >= phaseAvg + 128) and, for numAvg <= 128, an energy
+    // ring of r_len positions (even, >= numAvg + 128)
+    uint32_t max_n, max_A;
+    uint32_t off;                    // where its list starts in the compact lists
+    uint32_t tiles_max, pipe_tiles;  // time-tiled: tiles of its longest call; pipelined: tiles of a range
+    uint16_t max_S;                  // largest samplesPerBaud (the sets without an instantiation)
+    uint8_t K;                       // time-tiled: blocks to a tile
+    bool tiled : 1, piped : 1;       // goes through the time-tiled kernels first; ... in ranges of tiles on three streams
+};
+static_assert(sizeof(LaunchSet) == 40, "PlanSummary is zeroed per call: no larger than the tables it replaced");
+
 // What the control-plane pass over a batch found out: the first refusal, if any, and which kernels
 // the accepted plans need.
 struct PlanSummary {
     psk_soft_status st = PSK_SOFT_OK;
     uint32_t bad = 0;  // first refused channel (index into the batch)
     int why = 0;       // 0: status of plan_call, 2: alignment, 3: packet format
-    bool any = false, any_emit = false, any_seq = false, any_quiet = false;
+    bool any_plan = false, any_emit = false, any_seq = false;
     bool long_call = false;  // some channel's call is planned for the reference-order kernel only because of its length
-    bool need_SH[33][17] = {};
-    uint32_t cnt_SH[33][17] = {}, cnt_quiet = 0;  // channels per launch: each launch gets a compact list of its own
-    // LDS rings of a launch are sized for the largest phaseAvg / numAvg among its channels: a ring of
-    // y_len unwrapped phases (a power of two >= phaseAvg + 128) and, for numAvg <= 128, an energy
-    // ring of r_len positions (even, >= numAvg + 128)
-    uint32_t max_n[33][17] = {}, max_A[33][17] = {};
-    uint32_t max_n_quiet = 0;  // ... and of the channels that emit nothing this call
-    // time-tiled kernels: 128-symbol blocks of the class, in all and of its longest call
-    uint64_t blocks_SH[33][17] = {};
-    uint32_t max_blocks_SH[33][17] = {};
-    // the window classes without an instantiation (PLAN_ANYFRONT), one launch set for all of them
-    uint32_t cnt_any = 0, max_n_any = 0, max_A_any = 0, max_blocks_any = 0, max_S_any = 0;
-    uint64_t blocks_any = 0;
-    // ... of them, the wide symbols (samplesPerBaud > kSeqMaxS): a launch set of their own (psk_wide.hip)
-    uint32_t cnt_wide = 0, max_n_wide = 0, max_A_wide = 0, max_blocks_wide = 0, max_S_wide = 0;
-    uint64_t blocks_wide = 0;
-    // ... and of both, the channels of the far fit (PLAN_FARFIT, phaseAvg > kFastFitMax): launch sets of their own, so that the LDS
-    // rings of the two above stay sized for their own channels
-    struct FarSet {
-        uint32_t cnt = 0, max_A = 0, max_blocks = 0, max_S = 0;
-        uint64_t blocks = 0;
-    } anyf, widef;
-    uint32_t cnt_quietf = 0;  // ... and their calls that emit nothing while the window holds values (psk_far_quiet_kernel)
+    // The launch sets, in the order of their lists: the calls that emit nothing (max_n: of those whose window needs room in the launch's
+    // LDS ring); the window classes without an instantiation (PLAN_ANYFRONT), one set for all of them; of them, the wide symbols
+    // (samplesPerBaud > kSeqMaxS, psk_wide.hip); of both, the channels of the far fit (PLAN_FARFIT, phaseAvg > kFastFitMax), so that the
+    // LDS rings of the two stay sized for their own channels; the far fit's calls that emit nothing while the window holds values
+    // (psk_far_quiet_kernel); then the window classes of the wave-scan kernels, [samplesPerBaud][class, see kClassH]
+    LaunchSet quiet{}, any{}, wide{}, anyf{}, widef{}, quietf{};
+    LaunchSet cls[33][17]{};
 };
 
 // One chunk of channels of the host-buffer path in flight: pinned and device buffers for the packed
@@ -568,6 +570,1229 @@ bool ctl_equal(const psk::ChanCtl &a, const psk::ChanCtl &b)
            std::memcmp(&a.lf_xdelta, &b.lf_xdelta, sizeof(float)) == 0 && a.lf_len == b.lf_len && a.lf_count == b.lf_count &&
            a.lf_head == b.lf_head && a.ring_src == b.ring_src && a.lf_recompute_pending == b.lf_recompute_pending;
 }
+
+// ---- one pass of the control plane over a batch and the launches it asks for: process_round and its phases ----
+
+struct Cls { int S, H; };  // a window class of the call
+// What a round works on: what it was called with, where its plans and lists live, what the plan pass found out (res), and what each
+// phase leaves for the ones behind it.
+struct Round {
+    psk_soft_handle *h;
+    uint32_t ch0, nch;
+    const psk_soft_packet_t *pkts;
+    psk_soft_output_t *outs;
+    const uint8_t *cont;  // pieces of a call the library has cut, see process_round
+    hipStream_t stream;
+    int slot;
+    bool dry;
+    uint32_t extra_flags;
+    psk::Limits lim;
+    psk::ChanPlan *plans = nullptr;
+    uint32_t *handed_over = nullptr;  // (psk_plan.h)
+    bool stamped = false;             // the stamped path: one plan and one copy of the control state stand for the range
+    psk::ChanCtl stamp_ctl;
+    psk_soft_handle::UniRun *run = nullptr;
+    PlanSummary res;
+    uint32_t *h_list = nullptr;  // compact lists, one per launch set, behind the plans
+    const uint32_t *d_list = nullptr;
+    const psk::ChanPlan *d_plans = nullptr;  // (the plans and lists as the kernels see them)
+    uint32_t far_rows = 0;  // channels of anyf, widef and quietf: the three lists follow one another
+    // the scratch of the time-tiled kernels: symbols and tiles placed, of them the parallel fit's, what the wide symbols and the pipeline need
+    size_t tile_syms = 0, tile_count = 0, pf_syms = 0, pf_count = 0, wide_rec_need = 0, wide_stat_need = 0, pipe_need = 0;
+    uint32_t wide_z = 0, n_wide_seq = 0, wide_seq_S = 0;  // (n_wide_seq: channels of the reference-order kernel's wide build)
+    bool pf_second = false;
+    // conversion pre-pass: descriptors in all and per format, the longest packet of each, the scratch they convert into
+    uint32_t n_cvt = 0, n_cvt_f[psk::kNumPktFormats] = {};
+    uint64_t cvt_max_n[psk::kNumPktFormats] = {};
+    CvtScratch *cv = nullptr;
+    uint32_t n_in_place = 0, n_in_place_f[psk::kNumPktFormats] = {}, n_seq_narrow = 0;  // the reference-order kernel's lists
+    Cls cls[33 * kNumClassH];  // the schedule
+    int n_cls = 0;
+    bool fork = false, deferred = false;
+    uint64_t sig = 0;
+};
+// (a phase that fails ends the round with its status)
+#define PSK_TRY(call)                       \
+    do {                                    \
+        const psk_soft_status s_ = (call);  \
+        if (s_ != PSK_SOFT_OK)              \
+            return s_;                      \
+    } while (0)
+
+// CS16, CS8 and CF16 channels of the window classes with in-place instantiations (psk_fast_inst.hip, PSK_INST_PKT): a class of
+// their own per format, no conversion.  (What would go through the time-tiled kernels is moved back: move_in_place_back.)
+bool in_place(const psk::ChanPlan &p, const psk::PktFormat &f)
+{
+    return (p.lf_flags & f.flag) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
+           p.lf_n <= kDeepFit && psk::fast_pkt_has((int)f.id, (int)p.S);
+}
+// the class of a planned channel that emits on the wave-scan kernels
+int class_of(const psk::ChanPlan &p)
+{
+    for (const psk::PktFormat &f : psk::kPktFormats)
+        if (p.lf_flags & f.in_place)
+            return f.cls;
+    return psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
+}
+// The launch set a planned channel belongs to; nullptr: the reference-order kernel.  The one place that decides it: the plan pass
+// counts with it (account), the compact lists are filled with it (fill_lists).
+LaunchSet *set_of(const psk::ChanPlan &p, const psk::Limits &lim, PlanSummary &r)
+{
+    if (p.mode != psk::PLAN_FAST)
+        return nullptr;
+    if (p.n_out && (p.lf_flags & psk::PLAN_FARFIT))
+        return p.S > kSeqMaxS ? &r.widef : &r.anyf;
+    if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT))
+        return p.S > kSeqMaxS ? &r.wide : &r.any;
+    if (p.n_out)
+        return &r.cls[p.S][class_of(p)];
+    if (lim.far_fit && p.lf_n > lim.fast_fit_max && p.lf_len0)
+        return &r.quietf;  // (nothing emitted, but prologue and epilogue go through the window: no LDS holds it)
+    return &r.quiet;
+}
+// f(set) for every launch set in the order of the lists: quiet, any, wide, anyf, widef, quietf, then the classes
+template <class F>
+void each_set(PlanSummary &r, F f)
+{
+    for (LaunchSet *s : {&r.quiet, &r.any, &r.wide, &r.anyf, &r.widef, &r.quietf}) f(*s);
+    for (int S : kFastS)
+        for (int H : kClassH) f(r.cls[S][H]);
+}
+// what a planned channel asks of the launches (`mult` channels with this very plan)
+void account(psk::ChanPlan &p, const psk::Limits &lim, PlanSummary &r, uint32_t mult)
+{
+    r.any_plan = true;
+    for (const psk::PktFormat &f : psk::kPktFormats)  // (read in place: the channel joins the class of its format)
+        if (in_place(p, f))
+            p.lf_flags |= f.in_place;
+    LaunchSet *const s = set_of(p, lim, r);
+    if (!s) {
+        r.any_seq = true;
+        if (!lim.force_seq && p.lf_n <= (lim.far_fit ? 65535u : lim.fast_fit_max) &&
+            (p.n_out > psk::kResyncCount || (uint64_t)p.lf_count0 + p.n_out > psk::kResyncCount))
+            r.long_call = true;
+        return;
+    }
+    s->cnt += mult;
+    if (!p.n_out) {
+        // (an empty far window needs no room in the launch's LDS ring: nothing is copied in or out)
+        if (s == &r.quiet && p.lf_n > s->max_n && (p.lf_len0 || p.lf_n <= lim.fast_fit_max)) s->max_n = p.lf_n;
+        return;
+    }
+    r.any_emit = true;
+    const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
+    s->blocks += (uint64_t)nb * mult;
+    if (nb > s->max_blocks) s->max_blocks = nb;
+    if (p.lf_n > s->max_n) s->max_n = p.lf_n;
+    if (p.A > s->max_A) s->max_A = p.A;
+    if (p.S > s->max_S) s->max_S = (uint16_t)p.S;
+}
+// (packet data: 8-byte aligned float pairs, 4-byte aligned int16 and binary16 pairs, 2-byte aligned int8 pairs)
+bool misaligned(const Round &r, const psk::ChanPlan &p)
+{
+    uintptr_t in_mask = 7u;
+    for (const psk::PktFormat &f : psk::kPktFormats)
+        if (p.lf_flags & f.flag)
+            in_mask = f.align_mask;
+    return !r.dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & in_mask) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
+                      ((uintptr_t)p.phase & 3u) || ((uintptr_t)p.sidx & 3u));
+}
+// The plans are written straight into the pinned upload slot of this call: wait until the launch
+// that last used the slot has consumed it.  (A refused call does not advance the slot.)
+psk_soft_status take_slot(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    if (h->dry) {
+        if (h->plans_dry.size() < r.nch)
+            h->plans_dry.resize(r.nch);
+        r.plans = h->plans_dry.data();
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    if (h->ev_used[r.slot])
+        PSK_HIP(hipEventSynchronize(h->ev[r.slot]));
+    for (int a = 0; a < kAuxStreams; a++)
+        if (h->slot_aux_used[r.slot][a]) {  // (a deferred call's classes end on the side streams)
+            PSK_HIP(hipEventSynchronize(h->slot_aux_ev[r.slot][a]));
+            h->slot_aux_used[r.slot][a] = false;
+        }
+    r.plans = h->h_plans[r.slot];
+    r.handed_over = psk::plan_header(h->d_plans[r.slot]);
+    return PSK_SOFT_OK;
+}
+// ---- the stamped path ----
+// Channels configured alike and fed packets of the same length ever since hold IDENTICAL control state, and a batch of equal packets
+// gets the same plan in every channel but for its five pointers: planned ONCE, stamped into the other slots, the new control state
+// kept in ONE copy that stands for the range until somebody looks at a single channel (ctl_sync).  Per channel: ~3 ns against ~14 ns.
+// Anything unusual -- a refused call, a packet that differs, a buffer too small or misaligned -- leaves for the ordinary path.
+//
+// the run that stands for [ch0, ch0 + nch), found or newly made; nullptr: the channels are not known to be alike
+psk_soft_handle::UniRun *uniform_run(psk_soft_handle *h, uint32_t ch0, uint32_t nch)
+{
+    if (psk_soft_handle::UniRun *const run = run_find(h, ch0, ch0 + nch))
+        return run;
+    ctl_touch_range(h, ch0, ch0 + nch);  // (runs that overlap the range without being it)
+    if (h->mixed_ttl > 0 && h->mixed_lo == ch0 && h->mixed_hi == ch0 + nch) {  // (known to be mixed)
+        h->mixed_ttl--;
+        return nullptr;
+    }
+    const psk::ChanCtl &c0 = h->ctl[ch0];
+    for (uint32_t i = 1; i < nch; i++)
+        if (!ctl_equal(c0, h->ctl[ch0 + i])) {
+            h->mixed_lo = ch0, h->mixed_hi = ch0 + nch, h->mixed_ttl = 256;
+            return nullptr;
+        }
+    psk_soft_handle::UniRun *run = nullptr;
+    for (int k = psk_soft_handle::kUniRuns - 1; k >= 0; k--)  // (the first free slot)
+        run = h->uni[k].hi == h->uni[k].lo ? &h->uni[k] : run;
+    if (!run) {  // (every slot taken: the first one makes room)
+        run = &h->uni[0];
+        run_sync(h, *run);
+    }
+    run->lo = ch0, run->hi = ch0 + nch, run->lazy = false;
+    return run;
+}
+// plans the batch the stamped way if it can (r.stamped); if it cannot, nothing of the attempt is left in r.res
+void plan_stamped(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    if (!h->opt_stamp || r.cont || r.nch < 16u || !(r.run = uniform_run(h, r.ch0, r.nch)))
+        return;
+    r.stamp_ctl = r.run->lazy ? r.run->ctl : h->ctl[r.ch0];
+    psk::ChanPlan &p0 = r.plans[0];
+    const psk_soft_packet_t &k0 = r.pkts[0];
+    if (psk::plan_call(r.stamp_ctl, r.lim, k0, r.outs[0], p0, false) != PSK_SOFT_OK || p0.mode == psk::PLAN_SKIP || misaligned(r, p0))
+        return;
+    p0.lf_flags |= r.extra_flags;
+    p0.handed_over = r.handed_over;
+    account(p0, r.lim, r.res, r.nch);
+    const psk_soft_output_t o0 = r.outs[0];
+    uint32_t i = 1;
+    for (const uint32_t n = r.res.long_call ? 0u : r.nch; i < n; i++) {
+        const psk_soft_packet_t &k = r.pkts[i];
+        psk_soft_output_t &o = r.outs[i];
+        if (k.n_floats != k0.n_floats || k.format != k0.format || k.present != k0.present || k.sri_mode != k0.sri_mode || k.sriChanged != k0.sriChanged ||
+            k.inputQueueFlushed != k0.inputQueueFlushed || std::memcmp(&k.sri_xdelta, &k0.sri_xdelta, sizeof(double)) != 0)
+            break;
+        if (p0.n_out > o.cap_symbols && (o.soft || o.phase))
+            break;
+        psk::ChanPlan &p = r.plans[i];
+        p = p0;
+        p.in = k.data, p.soft = o.soft, p.bits = o.bits, p.phase = o.phase, p.sidx = o.sampleIndex;
+        if (misaligned(r, p))
+            break;
+        o.ret = o0.ret, o.n_symbols = o0.n_symbols, o.n_bits = o0.n_bits, o.n_sampleIndex = o0.n_sampleIndex;
+        o.sri_pushed = o0.sri_pushed, o.sri_soft_xdelta = o0.sri_soft_xdelta, o.sri_bits_xdelta = o0.sri_bits_xdelta;
+        o.n_warn = o0.n_warn;
+    }
+    r.stamped = i == r.nch;
+    if (!r.stamped)
+        r.res = PlanSummary();
+}
+// The ordinary path: every channel planned on its own, on copies (ctl_next); committed only if every channel of the batch is accepted.
+// One thread: ~15 ns per channel; a thread pool was measured and dropped (waking the workers costs more than the whole pass).
+void plan_each(Round &r)
+{
+    psk::ChanCtl *const next = r.h->ctl_next.data() + r.ch0;
+    const psk::ChanCtl *const cur = r.h->ctl.data() + r.ch0;
+    PlanSummary &res = r.res;
+    for (uint32_t i = 0; i < r.nch; i++) {
+        next[i] = cur[i];
+        psk::ChanPlan &p = r.plans[i];
+        psk_soft_status st = psk::plan_call(next[i], r.lim, r.pkts[i], r.outs[i], p, r.cont && (r.cont[i] & 1u));
+        if (st != PSK_SOFT_OK) {
+            res.st = st, res.bad = i, res.why = st == PSK_SOFT_ERR_INVALID_ARG ? 3 : 0;
+            return;
+        }
+        if (p.mode == psk::PLAN_SKIP)
+            continue;
+        if (misaligned(r, p)) {
+            res.st = PSK_SOFT_ERR_INVALID_ARG, res.bad = i, res.why = 2;
+            return;
+        }
+        p.lf_flags |= r.extra_flags;
+        p.handed_over = r.handed_over;
+        if (r.cont && (r.cont[i] & 2u))
+            p.lf_flags |= psk::PLAN_NO_WRAP;  // (more pieces of this call follow)
+        if (r.cont && (r.cont[i] & 4u))
+            p.lf_flags |= psk::PLAN_CARRY_DRIFT;  // (a piece cut where the reference does not rebuild its sums)
+        account(p, r.lim, res, 1u);
+    }
+}
+// the refusal the plan pass found, as the caller gets it
+psk_soft_status refusal(const Round &r)
+{
+    const PlanSummary &res = r.res;
+    if (res.why == 2)
+        return fail(PSK_SOFT_ERR_INVALID_ARG,
+                    "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
+    char buf[160];
+    if (res.why == 3) {
+        std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
+                      r.ch0 + res.bad, (unsigned)r.pkts[res.bad].format);
+        return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+    }
+    std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u refused (status %d)", r.ch0 + res.bad, (int)res.st);
+    return fail(res.st, buf);
+}
+// The host mirror (ctl) is committed only once everything the call needs has been enqueued: a HIP error before the first kernel launch
+// leaves the channels untouched; one after it poisons the handle (device state half advanced, nothing to roll it back with).
+void commit(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    if (r.stamped) {  // (one copy stands for the range: see ctl_sync)
+        r.run->ctl = r.stamp_ctl;
+        r.run->mode = r.plans[0].mode;
+        r.run->lazy = true;
+        return;
+    }
+    if (r.ch0 == 0 && r.nch == h->nch)
+        h->ctl.swap(h->ctl_next);
+    else
+        std::memcpy(static_cast<void *>(h->ctl.data() + r.ch0), h->ctl_next.data() + r.ch0, sizeof(psk::ChanCtl) * r.nch);
+    for (uint32_t i = 0; i < r.nch; i++) h->last_mode[r.ch0 + i] = r.plans[i].mode;
+}
+// Calls that touch the same channels must run in order: a call waits for the earlier calls on OTHER streams whose channel range overlaps
+// its own (same stream: the stream orders them; older calls than the plan slots remember have completed -- a slot is only reused after its event).
+psk_soft_status wait_for_overlapping_calls(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    for (int k = 0; k < kPlanSlots; k++)
+        if (k != r.slot && h->ev_used[k] && h->slot_stream[k] != r.stream && h->slot_ch0[k] < r.ch0 + r.nch &&
+            r.ch0 < h->slot_ch0[k] + h->slot_nch[k]) {
+            PSK_HIP(hipStreamWaitEvent(r.stream, h->ev[k], 0));
+            for (int a = 0; a < kAuxStreams; a++)
+                if (h->slot_aux_used[k][a])
+                    PSK_HIP(hipStreamWaitEvent(r.stream, h->slot_aux_ev[k][a], 0));
+        }
+    return PSK_SOFT_OK;
+}
+// CS16, CS8 and CF16 channels read in place have classes of their own (PktFormat::cls), which have no
+// time-tiled kernels: where the float class would go through those (the same choice as in place_all, on the four classes together),
+// their channels go back to the float class and to the conversion pre-pass
+void move_in_place_back(Round &r)
+{
+    const psk_soft_handle *const h = r.h;
+    if (r.stamped && !(r.plans[0].lf_flags & kInPlaceFlags))
+        return;
+    for (int S = 2; S <= 16; S++) {
+        LaunchSet &fl = r.res.cls[S][1];
+        uint32_t cnt = fl.cnt, mb = fl.max_blocks, mn = fl.max_n;
+        for (const psk::PktFormat &f : psk::kPktFormats) {
+            const LaunchSet &c = r.res.cls[S][f.cls];
+            cnt += c.cnt;
+            mb = c.max_blocks > mb ? c.max_blocks : mb;
+            mn = c.max_n > mn ? c.max_n : mn;
+        }
+        if (cnt == fl.cnt || !h->opt_tiled || !psk::tile_front_has(S, 1))  // (no channel read in place, or no time-tiled kernels)
+            continue;
+        const bool pipe = h->opt_pipe == 2 ? mb >= 4u
+                                           : h->opt_pipe && h->opt_tiled == 1 && cnt >= kPipeMinChannels && cnt <= kPipeMaxChannels &&
+                                                 mb >= kPipeMinBlocks && !r.cont && mn + 128u <= kPipeMaxYLen;
+        const bool tiled = h->opt_tiled == 2 || pipe || (cnt <= kTiledFewChannels && mb >= kTiledMinBlocksFew) ||
+                           (cnt <= kTiledMaxChannels && mb >= kTiledMinBlocks);
+        if (!tiled)
+            continue;
+        fl.cnt = cnt, fl.max_blocks = mb, fl.max_n = mn;
+        for (const psk::PktFormat &f : psk::kPktFormats) {
+            LaunchSet &c = r.res.cls[S][f.cls];
+            fl.max_A = fl.max_A > c.max_A ? fl.max_A : c.max_A;
+            fl.blocks += c.blocks;
+            c = LaunchSet{};
+        }
+        for (uint32_t i = 0; i < r.nch; i++)
+            if (r.plans[i].S == (uint32_t)S)
+                r.plans[i].lf_flags &= ~kInPlaceFlags;
+    }
+}
+// compact lists, one per launch set, behind the plans: first the channels that emit nothing, then the sets without an
+// instantiation, then every (S, H) class
+void fill_lists(Round &r)
+{
+    r.h_list = reinterpret_cast<uint32_t *>(r.h->h_plans[r.slot] + r.nch);
+    r.d_plans = r.h->d_plans[r.slot];
+    r.d_list = reinterpret_cast<const uint32_t *>(r.d_plans + r.nch);
+    uint32_t run = 0;
+    each_set(r.res, [&](LaunchSet &s) {
+        s.off = run;
+        run += s.cnt;
+    });
+    r.far_rows = r.res.anyf.cnt + r.res.widef.cnt + r.res.quietf.cnt;
+    // (stamped: one set holds every channel, in order; the offsets of the others are equal to its end -- unless the stamped class was
+    // just moved back to the float class: its offsets are that class's then, the lists the same)
+    if (r.stamped) {
+        for (uint32_t i = 0; i < r.nch; i++) r.h_list[i] = i;
+        return;
+    }
+    for (uint32_t i = 0; i < r.nch; i++)  // (`off` runs along as the set's list fills ...)
+        if (LaunchSet *const s = set_of(r.plans[i], r.lim, r.res))
+            r.h_list[s->off++] = i;
+    each_set(r.res, [](LaunchSet &s) { s.off -= s.cnt; });  // (... and goes back to its start)
+}
+struct TileRule {  // how a launch set is cut into tiles: the four things in which the sets differ
+    uint64_t k_min;  // the least blocks to a tile: 1 for the wide symbols (few symbols a call fill the machine only on short tiles), else 2
+    uint32_t z;      // tiles are counted in waves: a wave per chunk of 1024 timing phases for the wide symbols (wide_z), else 1
+    bool lengthen;   // towards the longest window, which the front stage rebuilds in front of a tile; the window classes keep short tiles
+    bool pfit;       // full fit windows take the parallel fit (never the far fit, whose window is in device memory; never a pipelined class)
+};
+// The set goes through the time-tiled kernels (psk_tile_kernel.h): its channels get a place in the scratch of the call -- symbols
+// padded to whole blocks, K blocks to a tile, K chosen so that the set makes a few thousand tiles.
+void place_tiles(Round &r, LaunchSet &s, const TileRule &rule)
+{
+    const uint64_t blocks_z = s.blocks * rule.z;
+    uint64_t K = blocks_z / kTiledTargetTiles;
+    K = K < rule.k_min ? rule.k_min : K > 16 ? 16 : K;
+    // (a tile rebuilds the window in front of it: tiles at least as long as the longest window keep that a fraction of the
+    // work -- where there are tiles enough to fill the machine anyway; a few channels finish sooner on many short tiles)
+    const uint64_t k_win = (s.max_A + 127u) / 128u;
+    if (rule.lengthen && K < k_win) {
+        const uint64_t k_fill = blocks_z / (kTiledTargetTiles / 2);
+        const uint64_t k_long = k_win > 64 ? 64 : k_win;
+        K = k_fill > k_long ? k_long : k_fill > K ? k_fill : K;
+    }
+    s.tiled = true;
+    s.K = (uint8_t)K;
+    s.tiles_max = (uint32_t)((s.max_blocks + K - 1) / K);
+    for (uint32_t i = 0; i < s.cnt; i++) {
+        psk::ChanPlan &p = r.plans[r.h_list[s.off + i]];
+        const uint64_t nb = (p.n_out + 127u) / 128u;
+        p.lf_flags |= psk::PLAN_TILED;
+        if (rule.pfit && r.h->opt_pfit && p.lf_len0 == p.lf_n && p.lf_n >= 2)
+            p.lf_flags |= psk::PLAN_PFIT;
+        p.tile_blocks = (uint32_t)K;
+        p.tile_base = (uint32_t)r.tile_count;
+        p.tile_off = r.tile_syms;
+        r.tile_count += (size_t)((nb + K - 1) / K);
+        r.tile_syms += (size_t)nb * 128u;
+    }
+}
+// a pipelined class that has its tiles: the tiles of a range
+void place_ranges(Round &r, LaunchSet &s)
+{
+    s.piped = true;
+    const uint32_t T = s.tiles_max;
+    uint32_t tr = (uint32_t)(kTiledTargetTiles / s.cnt);  // (a range = about one machine-load of tiles)
+    tr = tr < 1u ? 1u : tr;
+    if (r.h->opt_pipe == 2 && tr > 3u)
+        tr = 3u;
+    if (const char *e = std::getenv("PSK_SOFT_PIPE_RANGE_TILES"))  // (A/B runs)
+        tr = std::atoi(e) > 0 ? (uint32_t)std::atoi(e) : tr;
+    if ((T + tr - 1) / tr > kPipeMaxRanges)
+        tr = (T + kPipeMaxRanges - 1) / kPipeMaxRanges;
+    s.pipe_tiles = tr;
+    if (s.off + s.cnt > r.pipe_need)
+        r.pipe_need = s.off + s.cnt;
+}
+// Every set that goes through the time-tiled kernels gets its place in the scratch.  The order matters: the wide symbols first -- their
+// places index the chunk records of psk_wide.hip too, which need not cover the others --, then the other sets without an instantiation, then
+// the window classes of few channels and long calls; the pipelined ones last -- the parallel fit's scratch need not cover them.
+void place_all(Round &r)
+{
+    const psk_soft_handle *const h = r.h;
+    PlanSummary &res = r.res;
+    r.wide_z = (res.wide.cnt || res.widef.cnt) ? psk::wide_chunks(res.wide.max_S > res.widef.max_S ? res.wide.max_S : res.widef.max_S) : 0u;
+    // (the sets without an instantiation: always tiled, whatever the option says -- the alternative is the reference-order kernel)
+    if (res.wide.cnt)
+        place_tiles(r, res.wide, TileRule{1, r.wide_z, true, true});
+    if (res.widef.cnt)
+        place_tiles(r, res.widef, TileRule{1, r.wide_z, true, false});
+    r.wide_rec_need = r.tile_syms * r.wide_z * psk::wide_rec_bytes(), r.wide_stat_need = r.tile_count * r.wide_z * psk::wide_stat_bytes();
+    if (res.any.cnt)
+        place_tiles(r, res.any, TileRule{2, 1, true, true});
+    if (res.anyf.cnt)
+        place_tiles(r, res.anyf, TileRule{2, 1, true, false});
+    r.pf_syms = r.tile_syms, r.pf_count = r.tile_count;
+    for (int pass = 0; pass < (h->opt_tiled ? 2 : 0); pass++) {
+        for (int S : kFastS)
+            for (int H : kClassH) {
+                LaunchSet &s = res.cls[S][H];
+                if (!s.cnt || class_pkt(H) || !psk::tile_front_has(S, class_H(H)))
+                    continue;
+                // pipelined: the serial fit of a range under the front stage of the next (see kPipeMinChannels)
+                // (PSK_SOFT_PIPELINED=2, tests: wherever the kernels allow it, a few blocks to a range)
+                const bool pipe = (h->opt_pipe == 2 ? s.max_blocks >= 4u
+                                                    : h->opt_pipe && h->opt_tiled == 1 && s.cnt >= kPipeMinChannels && s.cnt <= kPipeMaxChannels &&
+                                                          s.max_blocks >= kPipeMinBlocks) &&
+                                  !r.cont && s.max_n + 128u <= kPipeMaxYLen && (size_t)s.blocks * 128u <= kPipeMaxSymbols;
+                if (pipe != (pass == 1))
+                    continue;
+                if (!pipe && h->opt_tiled == 1 &&
+                    !((s.cnt <= kTiledFewChannels && s.max_blocks >= kTiledMinBlocksFew) || (s.cnt <= kTiledMaxChannels && s.max_blocks >= kTiledMinBlocks)))
+                    continue;
+                place_tiles(r, s, TileRule{2, 1, false, !pipe});
+                if (pipe)
+                    place_ranges(r, s);
+            }
+        if (pass == 0)
+            r.pf_syms = r.tile_syms, r.pf_count = r.tile_count;
+    }
+}
+
+struct ScratchBuf {  // one buffer of a scratch that grows on demand, and the bytes it is to have
+    void **buf;
+    size_t bytes;
+};
+template <class T>
+inline ScratchBuf scratch_buf(T **p, size_t n) { return ScratchBuf{reinterpret_cast<void **>(p), sizeof(T) * n}; }
+inline size_t plus_quarter(size_t need) { return need + need / 4; }  // (a scratch grows to the largest call seen, plus a quarter)
+// A scratch is too small for the call (rare): the device is waited for -- no call is in flight on a buffer that moves --, the buffers
+// are freed and allocated anew.  *got = false: out of device memory, none of them is held; what the call does then is the caller's business.
+hipError_t grow_scratch(std::initializer_list<ScratchBuf> bufs, bool *got)
+{
+    if (const hipError_t e = hipDeviceSynchronize())
+        return e;
+    for (const ScratchBuf &b : bufs) (void)hipFree(*b.buf), *b.buf = nullptr;
+    *got = true;
+    for (const ScratchBuf &b : bufs) *got = *got && hipMalloc(b.buf, b.bytes) == hipSuccess;
+    if (!*got) {
+        (void)hipGetLastError();
+        for (const ScratchBuf &b : bufs) (void)hipFree(*b.buf), *b.buf = nullptr;
+    }
+    return hipSuccess;
+}
+// the channel's call goes to the reference-order kernel after all
+void to_reference_order(psk::ChanPlan &p)
+{
+    p.mode = p.S == 1u ? psk::PLAN_SEQ_S1 : psk::PLAN_SEQ;
+    p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
+}
+// the scratch of the time-tiled kernels and of the parallel fit
+psk_soft_status scratch_tiles(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    PlanSummary &res = r.res;
+    if (!r.tile_syms || (r.tile_syms <= h->tile_sym_cap && r.tile_count <= h->tile_cap && r.pf_syms <= h->pf_sym_cap && r.pf_count <= h->pf_cap))
+        return PSK_SOFT_OK;
+    h->tile_cap = h->tile_sym_cap = h->pf_cap = h->pf_sym_cap = 0;
+    const size_t syms = plus_quarter(r.tile_syms), cnt = plus_quarter(r.tile_count);
+    const size_t psyms = plus_quarter(r.pf_syms) + 128u, pcnt = plus_quarter(r.pf_count) + 1u;
+    psk::PfScratch &pf = h->pf;
+    bool got = false;
+    PSK_HIP(grow_scratch({scratch_buf(&h->d_tiles, cnt), scratch_buf(&h->d_traw, syms), scratch_buf(&h->d_test, syms), scratch_buf(&h->d_ts, syms),
+                          scratch_buf(&pf.k, psyms), scratch_buf(&pf.y, psyms), scratch_buf(&pf.S, psyms), scratch_buf(&pf.c, psyms),
+                          scratch_buf(&pf.tt, psyms), scratch_buf(&pf.xs, psyms), scratch_buf(&pf.tile, pcnt),
+                          scratch_buf(&pf.blk, psyms / 128u + 1u), scratch_buf(&pf.walk, psyms / 128u + 1u)},
+                         &got));
+    if (got && !pf.chan) {
+        got = hipMalloc((void **)&pf.chan, sizeof(psk::PfChan) * h->nch) == hipSuccess &&
+              hipMemset(pf.chan, 0, sizeof(psk::PfChan) * h->nch) == hipSuccess && hipHostMalloc((void **)&pf.hint, 64) == hipSuccess;
+        if (got)
+            *pf.hint = 0u;
+    }
+    if (got) {
+        h->tile_cap = cnt, h->tile_sym_cap = syms, h->pf_cap = pcnt, h->pf_sym_cap = psyms;
+        return PSK_SOFT_OK;
+    }
+    (void)hipGetLastError();
+    // (out of device memory: the call does without -- the wave-scan kernels carry everything on their own)
+    for (uint32_t i = 0; i < r.nch; i++) {
+        psk::ChanPlan &p = r.plans[i];
+        if (p.lf_flags & psk::PLAN_ANYFRONT) {  // (no kernel but the reference-order one is left for these)
+            to_reference_order(p);
+            res.any_seq = true;
+        }
+        p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT);
+    }
+    res.any.cnt = res.wide.cnt = res.anyf.cnt = res.widef.cnt = 0;
+    for (int S : kFastS)
+        for (int H : kClassH) res.cls[S][H].tiled = res.cls[S][H].piped = false;
+    r.tile_syms = 0;
+    return PSK_SOFT_OK;
+}
+// the chunk records of the wide front stage
+psk_soft_status scratch_wide(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    PlanSummary &res = r.res;
+    if (!(res.wide.cnt || res.widef.cnt) || (r.wide_rec_need <= h->wide_rec_cap && r.wide_stat_need <= h->wide_stat_cap))
+        return PSK_SOFT_OK;
+    h->wide_rec_cap = h->wide_stat_cap = 0;
+    const size_t rb = plus_quarter(r.wide_rec_need), sb = plus_quarter(r.wide_stat_need);
+    bool got = false;
+    PSK_HIP(grow_scratch({ScratchBuf{&h->d_wide_rec, rb}, ScratchBuf{&h->d_wide_stat, sb}}, &got));
+    if (got) {
+        h->wide_rec_cap = rb, h->wide_stat_cap = sb;
+        return PSK_SOFT_OK;
+    }
+    // (out of device memory: the reference-order kernel carries these calls)
+    for (const LaunchSet *s : {&res.wide, &res.widef})
+        for (uint32_t i = 0; i < s->cnt; i++) to_reference_order(r.plans[r.h_list[s->off + i]]);
+    res.wide.cnt = res.widef.cnt = 0;
+    res.any_seq = true;
+    return PSK_SOFT_OK;
+}
+// the far fit's rings: a row of the scratch for every channel of its launch sets (kept from the channel's first such call on);
+// anyf, widef and quietf are walked as one range of the lists
+psk_soft_status scratch_far_rows(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    PlanSummary &res = r.res;
+    if (!r.far_rows)
+        return PSK_SOFT_OK;
+    const uint32_t *const list = r.h_list + res.anyf.off;
+    if (h->far_row.empty())
+        h->far_row.assign(h->nch, 0u);
+    uint32_t used = h->far_rows_used;
+    for (uint32_t i = 0; i < r.far_rows; i++)
+        if (!h->far_row[r.ch0 + list[i]])
+            used++;
+    bool got = true;
+    if (used > h->far_rows_cap) {
+        // (the one place of this path that waits for the device: a row carries nothing from one call to the next)
+        h->far_rows_cap = 0;
+        const uint32_t cap = plus_quarter(used) < h->nch ? (uint32_t)plus_quarter(used) : h->nch;
+        PSK_HIP(grow_scratch({ScratchBuf{(void **)&h->d_far_y, psk::far_ring_bytes() * cap}}, &got));
+        if (got)
+            h->far_rows_cap = cap;
+    }
+    for (uint32_t i = 0; i < r.far_rows; i++) {
+        psk::ChanPlan &p = r.plans[list[i]];
+        if (got) {
+            uint32_t &row = h->far_row[r.ch0 + list[i]];
+            if (!row)
+                row = ++h->far_rows_used;
+            p.far_row = row - 1u;
+        } else if (p.n_out) {  // (out of device memory: the reference-order kernel carries these calls, as with the option off)
+            to_reference_order(p);
+        }
+    }
+    if (!got) {
+        if (res.quietf.cnt)  // (... but a call that emits nothing has no other kernel to go to)
+            return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the fit window of a far channel (PSK_SOFT_OPT_FAR_FIT)");
+        res.anyf.cnt = res.widef.cnt = 0;
+        res.any_seq = true;
+    }
+    return PSK_SOFT_OK;
+}
+// the reference-order kernel's wide build (samplesPerBaud > kSeqMaxS): a list of its own -- the other build's symbolEnergy[] is
+// kSeqMaxS long -- and a row of symbolEnergy[] in device memory for each channel of it, as long as the widest
+psk_soft_status scratch_wide_seq(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    for (uint32_t i = 0; i < r.nch; i++)
+        if (r.plans[i].mode != psk::PLAN_SKIP && r.plans[i].S > kSeqMaxS) {
+            r.n_wide_seq++;
+            r.wide_seq_S = r.plans[i].S > r.wide_seq_S ? r.plans[i].S : r.wide_seq_S;
+        }
+    const size_t need = (size_t)r.n_wide_seq * r.wide_seq_S;
+    if (need <= h->wide_symE_cap)
+        return PSK_SOFT_OK;
+    h->wide_symE_cap = 0;
+    bool got = false;
+    PSK_HIP(grow_scratch({scratch_buf(&h->d_wide_symE, plus_quarter(need))}, &got));
+    if (!got)  // (nothing else carries a wide symbol)
+        return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the symbolEnergy rows of wide symbols");
+    h->wide_symE_cap = plus_quarter(need);
+    return PSK_SOFT_OK;
+}
+// The scratch is one per handle: calls that use it on different streams are ordered by tile_ev (the rows of symbolEnergy[] are
+// ordered like the scratch of the time-tiled kernels).  With it go the note of the parallel fit and the pipelined mode's own scratch.
+psk_soft_status scratch_order(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    if (!r.tile_syms && !r.n_wide_seq)
+        return PSK_SOFT_OK;
+    if (!h->tile_ev)
+        PSK_HIP(hipEventCreateWithFlags(&h->tile_ev, hipEventDisableTiming));
+    if (r.tile_syms) {
+        // second round of the parallel fit: for the next 16 tiled calls after one whose first guess of the unwrap counts
+        // failed somewhere (the kernels leave a note in page-locked memory; a late or lost note costs a call or two)
+        if (h->pf.hint && *static_cast<volatile uint32_t *>(h->pf.hint)) {
+            *static_cast<volatile uint32_t *>(h->pf.hint) = 0u;
+            h->pf_second_ttl = 16;
+        } else if (h->pf_second_ttl) {
+            h->pf_second_ttl--;
+        }
+        r.pf_second = h->opt_pfit == 2 || h->pf_second_ttl > 0;
+    }
+    if (h->tile_ev_used && h->tile_stream != r.stream)
+        PSK_HIP(hipStreamWaitEvent(r.stream, h->tile_ev, 0));
+    if (!r.tile_syms || !r.pipe_need)
+        return PSK_SOFT_OK;
+    // the pipelined mode's own scratch (one PipeCarry and one ring of kPipeMaxYLen floats per channel of a launch) and its
+    // two streams -- of another priority than the caller's, so that they get hardware queues of their own
+    if (r.pipe_need > h->pipe_cap) {
+        h->pipe_cap = 0;
+        const size_t cap = plus_quarter(r.pipe_need);
+        bool got = false;
+        PSK_HIP(grow_scratch({ScratchBuf{&h->d_pipe_carry, psk::pipe_carry_bytes() * cap}, scratch_buf(&h->d_pipe_y, kPipeMaxYLen * cap)}, &got));
+        if (got)
+            h->pipe_cap = cap;
+        else  // (out of device memory: the one-launch kernels do without)
+            for (int S : kFastS)
+                for (int H : kClassH) r.res.cls[S][H].piped = false;
+    }
+    if (!h->pipe_st[0]) {
+        int prio_lo = 0, prio_hi = 0;
+        PSK_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+        // (CU-masked streams for the stages -- the serial ones on every n-th CU, the front stage on the others -- were measured:
+        // no gain, 2.77 ... 2.84 against 2.75 ms at 512 channels)
+        for (hipStream_t &q : h->pipe_st) PSK_HIP(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, prio_hi));
+        for (hipEvent_t &e : h->pipe_ev) PSK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    return PSK_SOFT_OK;
+}
+// (the row in kPktFormats of a packet the pre-pass converts, else -1)
+int cvt_format(const psk::ChanPlan &p)
+{
+    if (p.mode == psk::PLAN_SKIP || !p.n_in)
+        return -1;
+    for (int f = 0; f < psk::kNumPktFormats; f++)
+        if ((p.lf_flags & psk::kPktFormats[f].flag) && !(p.lf_flags & psk::kPktFormats[f].in_place))
+            return f;
+    return -1;
+}
+// CS16, CS8 and CF16 packets (psk_pkt.hip): converted into float2 rows of the conversion scratch by one pre-pass per
+// format in front of the call's first kernel; their plans point at the rows from here on.  The descriptors travel behind the
+// plans, in the same upload: the CS16 packets' first, then the CS8 packets', then the CF16 packets' (the order of kPktFormats).
+psk_soft_status conversion_descriptors(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    size_t need = 0;
+    for (uint32_t i = 0; i < r.nch; i++)
+        if (const int f = cvt_format(r.plans[i]); f >= 0) {
+            need += align_up(sizeof(float2) * r.plans[i].n_in, 128);
+            r.n_cvt++, r.n_cvt_f[f]++;
+        }
+    if (!r.n_cvt)
+        return PSK_SOFT_OK;
+    CvtScratch *cv = &h->cvt[0], *own = nullptr;  // (the stream's own buffer, else the one used longest ago)
+    for (auto &c : h->cvt) {
+        cv = c.last_use < cv->last_use ? &c : cv;
+        own = !own && c.buf && c.stream == r.stream ? &c : own;
+    }
+    r.cv = cv = own ? own : cv;
+    if (!cv->ev)
+        PSK_HIP(hipEventCreateWithFlags(&cv->ev, hipEventDisableTiming));
+    if (cv->ev_used && cv->stream != r.stream)
+        PSK_HIP(hipStreamWaitEvent(r.stream, cv->ev, 0));
+    if (need > cv->cap) {
+        cv->cap = 0;
+        const size_t cap = align_up(plus_quarter(need), 4096);
+        bool got = false;
+        PSK_HIP(grow_scratch({ScratchBuf{(void **)&cv->buf, cap}}, &got));
+        if (!got)  // (nothing else reads these packets)
+            return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the conversion of CS16 / CS8 / CF16 packets");
+        cv->cap = cap;
+    }
+    cv->stream = r.stream, cv->last_use = ++h->cvt_calls;
+    psk::CvtDesc *const desc =
+        reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[r.slot])) + slot_cvt_offset(r.nch));
+    size_t off = 0;
+    uint32_t next[psk::kNumPktFormats] = {};  // (where each format's descriptors go on)
+    for (int f = 1; f < psk::kNumPktFormats; f++) next[f] = next[f - 1] + r.n_cvt_f[f - 1];
+    for (uint32_t i = 0; i < r.nch; i++) {
+        psk::ChanPlan &p = r.plans[i];
+        const int f = cvt_format(p);
+        if (f < 0)
+            continue;
+        const uint32_t k = next[f]++;
+        desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
+        desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
+        desc[k].n = p.n_in;
+        p.in = desc[k].dst;
+        off += align_up(sizeof(float2) * p.n_in, 128);
+        r.cvt_max_n[f] = p.n_in > r.cvt_max_n[f] ? p.n_in : r.cvt_max_n[f];
+    }
+    return PSK_SOFT_OK;
+}
+// the reference-order kernel's lists when CS16 / CS8 / CF16 channels are read in place: float-build channels first, then the
+// CS16 build's, then the CS8 build's, then the CF16 build's (and the wide symbols' last)
+void reference_order_lists(Round &r)
+{
+    for (uint32_t i = 0; i < r.nch; i++)
+        for (int f = 0; f < psk::kNumPktFormats; f++) r.n_in_place_f[f] += (r.plans[i].lf_flags & psk::kPktFormats[f].in_place) ? 1u : 0u;
+    for (const uint32_t n : r.n_in_place_f) r.n_in_place += n;
+    r.n_seq_narrow = r.nch - r.n_in_place - r.n_wide_seq;
+    if (!r.n_in_place && !r.n_wide_seq)
+        return;
+    uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(r.h->h_plans[r.slot])) + slot_seq_offset(r.nch));
+    uint32_t a = 0, b[psk::kNumPktFormats] = {r.n_seq_narrow}, c = r.nch - r.n_wide_seq;
+    for (int f = 1; f < psk::kNumPktFormats; f++) b[f] = b[f - 1] + r.n_in_place_f[f - 1];
+    for (uint32_t i = 0; i < r.nch; i++) {
+        uint32_t *at = &a;
+        for (int f = 0; f < psk::kNumPktFormats; f++)
+            if (r.plans[i].lf_flags & psk::kPktFormats[f].in_place)
+                at = &b[f];
+        if (r.plans[i].mode != psk::PLAN_SKIP && r.plans[i].S > kSeqMaxS)
+            at = &c;
+        seq[(*at)++] = i;
+    }
+}
+// what PSK_SOFT_VALIDATE finds wrong with a plan, or nullptr
+const char *invalid_plan(const Round &r, const psk::ChanPlan &p)
+{
+    const psk_soft_handle *const h = r.h;
+    const uint64_t S = p.S ? p.S : 1u, have = (uint64_t)p.ring_len0 + p.n_in;
+    const uint64_t nb = (p.n_out + 127u) / 128u;
+    const bool emits = p.mode == psk::PLAN_FAST && p.n_out;
+    const uint64_t tiles_end = p.tile_blocks ? (uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks : 0u;
+    if (p.n_out && p.S > 1u && (p.n_out + p.A - 1u) * S > have)
+        return "the call reads samples behind the packet's end";
+    if (p.n_out && p.S <= 1u && p.mode != psk::PLAN_SEQ_S1 && p.n_out > p.n_in)
+        return "more symbols than samples at one sample per symbol";
+    if (p.ring_len0 > h->lim.ring_cap || p.ring_len1 > h->lim.ring_cap || p.ring_src > 1u)
+        return "carried samples beyond the ring";
+    if (p.ring_len1 > have)
+        return "more samples carried out of the call than it holds";
+    if (p.lf_n >= h->lim.fit_cap || p.lf_len0 > p.lf_n || p.lf_head >= h->lim.fit_cap)
+        return "LinearFit window beyond its ring";
+    if ((p.lf_flags & psk::PLAN_TILED) && emits && (!p.tile_blocks || p.tile_off + nb * 128u > h->tile_sym_cap || tiles_end > h->tile_cap))
+        return "place in the time-tiled scratch outside it";
+    if ((p.lf_flags & psk::PLAN_FARFIT) && emits &&
+        (!h->d_far_y || p.far_row >= h->far_rows_cap || (p.lf_flags & psk::PLAN_PFIT) || p.lf_n < 128u))
+        return "far fit without a row of its scratch";
+    if ((p.lf_flags & psk::PLAN_PFIT) && emits && (p.tile_off + nb * 128u > h->pf_sym_cap || tiles_end > h->pf_cap))
+        return "place in the parallel fit's scratch outside it";
+    if (emits && !(p.lf_flags & psk::PLAN_ANYFRONT) && (p.S < 2u || p.S > 32u || p.A > 1024u || (p.S > 16u && p.A > 512u)))
+        return "window class without a wave-scan instantiation planned for one";
+    if (p.mode == psk::PLAN_FAST && p.n_out > psk::kResyncCount)
+        return "a piece longer than 2^20 symbols on the wave-scan kernels";
+    if ((p.lf_flags & psk::PLAN_TILED) && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS && emits &&
+        (psk::wide_chunks(p.S) > r.wide_z || (p.tile_off + nb * 128u) * r.wide_z * psk::wide_rec_bytes() > h->wide_rec_cap ||
+         tiles_end * r.wide_z * psk::wide_stat_bytes() > h->wide_stat_cap))
+        return "place in the wide-symbol scratch outside it";
+    if (p.S > kSeqMaxS && (p.S > r.wide_seq_S || !h->d_wide_symE || (size_t)r.n_wide_seq * r.wide_seq_S > h->wide_symE_cap))
+        return "wide symbol without a row of symbolEnergy";
+    if (cvt_format(p) >= 0 && (!r.cv || (const char *)p.in < (const char *)r.cv->buf ||
+                               (const char *)p.in + sizeof(float2) * p.n_in > (const char *)r.cv->buf + r.cv->cap))
+        return "converted CS16 / CS8 / CF16 packet outside the conversion scratch";
+    return nullptr;
+}
+// PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call reads
+// exist, what it leaves behind fits the rings, its place in the scratch of the time-tiled kernels lies inside it -- is checked here, on the
+// host, in front of the first launch; a violation refuses the call (nothing enqueued, nothing committed) instead of sending a kernel out of bounds.
+psk_soft_status validate(const Round &r)
+{
+    for (uint32_t i = 0; i < r.nch; i++)
+        if (const char *const why = r.plans[i].mode == psk::PLAN_SKIP ? nullptr : invalid_plan(r, r.plans[i])) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "psk_soft_process: plan of channel %u fails validation: %s", r.ch0 + i, why);
+            return fail(PSK_SOFT_ERR_LIMIT, buf);
+        }
+    return PSK_SOFT_OK;
+}
+// The schedule of the call: its window classes in launch order (deepest history first; class 0 stays on the caller's stream, the
+// others take the side streams in turn), and whether they are joined at the end of the call, left on their streams (deferred) or
+// -- *cut -- the call is handed back to be cut in time (nothing committed, nothing enqueued: the caller plans the pieces).
+psk_soft_status choose_schedule(Round &r, bool *cut)
+{
+    psk_soft_handle *const h = r.h;
+    const PlanSummary &res = r.res;
+    for (int k = kNumClassH - 1; k >= 0; k--)
+        for (int S : kFastS)
+            if (res.cls[S][kClassH[k]].cnt)
+                r.cls[r.n_cls++] = Cls{S, kClassH[k]};
+    r.fork = r.n_cls > 1 && h->opt_fork;
+    uint32_t listed = res.quiet.cnt, longest = 0;  // (listed != nch: channels without a packet this call, or on other launch sets)
+    for (int i = 0; i < r.n_cls; i++) {
+        const LaunchSet &s = res.cls[r.cls[i].S][r.cls[i].H];
+        listed += s.cnt;
+        longest = s.max_blocks > longest ? s.max_blocks : longest;
+    }
+    // only calls whose every channel runs on wave-scan launches are deferred or cut (nor calls with CS16 packets: the conversion
+    // scratch is one per stream, and the next call's pre-pass must not overwrite it under the side streams of this one)
+    const bool wave_scan_only = r.fork && !r.tile_syms && !res.any.cnt && !res.any_seq && !r.n_cvt && !r.n_wide_seq;
+    r.deferred = wave_scan_only && (h->opt_deferred || g_split_mode) && (!r.cont || g_split_mode);
+    if (wave_scan_only && !r.cont && !h->opt_deferred && h->opt_split > 1) {
+        // Classes that cannot be resident together take two rounds of waves, and a wave that starts late still needs the whole call's
+        // time at the lone-wave rate: cut in time, the late pieces are short too ("A mixed batch cut in time").
+        static const uint32_t min_blocks = [] {  // (PSK_SOFT_SPLIT_MIN_BLOCKS: tests cut short calls too)
+            const char *e = std::getenv("PSK_SOFT_SPLIT_MIN_BLOCKS");
+            return e && std::atoi(e) > 0 ? (uint32_t)std::atoi(e) : kSplitMinBlocks;
+        }();
+        if (listed == r.nch && longest >= min_blocks) {
+            *cut = true;
+            return PSK_SOFT_OK;
+        }
+    }
+    r.sig = 1469598103934665603ull;
+    if (r.deferred) {
+        auto mix = [&](uint64_t v) { r.sig = (r.sig ^ v) * 1099511628211ull; };
+        mix(r.ch0), mix(r.nch), mix((uint64_t)(uintptr_t)r.stream), mix((uint64_t)r.n_cls), mix(res.quiet.cnt);
+        for (int i = 0; i < r.n_cls; i++) mix(((uint64_t)r.cls[i].S << 40) | ((uint64_t)r.cls[i].H << 32) | res.cls[r.cls[i].S][r.cls[i].H].cnt);
+        for (uint32_t i = 0; i < r.nch; i++) mix(r.h_list[i]);  // (no planned SKIP / SEQ channels here: the lists hold all nch)
+        if (listed != r.nch)  // (channels without a packet this call: they belong to no stream -- the joined way)
+            r.deferred = false;
+    }
+    if (h->deferred_pending && !(r.deferred && r.sig == h->deferred_sig)) {
+        // a channel may be about to change streams: everything the side streams carry first
+        // (its own earlier calls on another stream: wait_for_overlapping_calls has made this stream wait for them and their side streams)
+        PSK_HIP(deferred_join(h, r.stream));
+    }
+    return PSK_SOFT_OK;
+}
+// header, plans, lists and whatever follows them of the call's slot, in one copy
+psk_soft_status upload(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    uint32_t *const hdr = psk::plan_header(h->h_plans[r.slot]);
+    hdr[0] = 0u;                       // channels handed over: counted by the kernels
+    hdr[1] = r.res.any_seq ? 1u : 0u;  // channels planned for the reference-order kernel
+    const size_t up_bytes = (r.n_in_place || r.n_wide_seq) ? slot_seq_offset(r.nch) + sizeof(uint32_t) * r.nch
+                            : r.n_cvt                      ? slot_cvt_offset(r.nch) + sizeof(psk::CvtDesc) * r.n_cvt
+                                                           : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * r.nch;
+    if (h->opt_up_stream) {
+        // (the slot's previous user has finished -- waited for in take_slot --, nothing else reads or writes d_plans[slot])
+        PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[r.slot]), hdr, up_bytes, hipMemcpyHostToDevice, h->up_stream));
+        PSK_HIP(hipEventRecord(h->ev_up[r.slot], h->up_stream));
+        PSK_HIP(hipStreamWaitEvent(r.stream, h->ev_up[r.slot], 0));
+    } else {
+        PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[r.slot]), hdr, up_bytes, hipMemcpyHostToDevice, r.stream));
+    }
+    return PSK_SOFT_OK;
+}
+// phase ring of a launch: a power of two >= phaseAvg + 128 for its channels, at least 512 floats (256 where
+// the energy ring is dynamic too and every byte of LDS counts towards residency)
+inline uint32_t ring_floats(uint32_t n_max, uint32_t at_least)
+{
+    uint32_t y = at_least;
+    while (y < n_max + 128u) y <<= 1;
+    return y;
+}
+// (timing experiments only -- PSK_SOFT_DIAG_NO_TAIL=1: the exact-timing and reference-order launches behind the screened tier are
+// left out, which is wrong as soon as a call is handed over; what the two launches cost a small call is measured that way)
+bool diag_no_tail()
+{
+    static const bool on = std::getenv("PSK_SOFT_DIAG_NO_TAIL") && std::atoi(std::getenv("PSK_SOFT_DIAG_NO_TAIL")) != 0;
+    return on;
+}
+// PSK_SOFT_TRACE_LAUNCHES=1 (debugging a faulting kernel): in front of every launch the host waits for everything enqueued so far and
+// writes one line for the launch and one per channel of its list to stderr -- the last launch named in the log of a run that died is the
+// one that did it, with the shapes it was given.  (=2: the launch lines only.)  off: the launch's place in the lists; ~0u: the whole batch.
+hipError_t mark(const Round &r, hipStream_t st, const char *what, int S, int H, uint32_t off, uint32_t cnt, uint32_t tiles, uint32_t y_len,
+                uint32_t r_len)
+{
+    if (!r.h->opt_trace)
+        return hipSuccess;
+    if (const hipError_t e = hipDeviceSynchronize())
+        return e;
+    std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%u y_len=%u r_len=%u slot=%d stream=%p\n", what, S, H, r.ch0, cnt,
+                 tiles, y_len, r_len, r.slot, (void *)st);
+    for (uint32_t i = 0; i < cnt && r.h->opt_trace == 1; i++) {
+        const uint32_t bi = r.stamped || off == ~0u ? i : r.h_list[off + i];
+        const psk::ChanPlan &p = r.plans[bi];
+        if (off == ~0u && p.mode == psk::PLAN_SKIP)
+            continue;
+        std::fprintf(stderr, "[psk_soft]   ch %u mode=%u S=%u A=%u M=%u n=%u len0=%u n_out=%llu n_in=%llu L0=%u L1=%u flags=0x%x K=%u tbase=%u toff=%llu in=%p\n",
+                     r.ch0 + bi, p.mode, p.S, p.A, p.M, p.lf_n, p.lf_len0, (unsigned long long)p.n_out, (unsigned long long)p.n_in, p.ring_len0,
+                     p.ring_len1, p.lf_flags, p.tile_blocks, p.tile_base, (unsigned long long)p.tile_off, (const void *)p.in);
+    }
+    std::fflush(stderr);
+    return hipSuccess;
+}
+// What tells the time-tiled launch sets apart: the front stage (of a window class, of the sets without an instantiation, of the wide
+// symbols: psk_wide.hip), the fit stage (window in LDS, or the far fit's in device memory) and how their launches are traced: names, and S, H,
+// y_len and r_len as the lines give them (r_front: of the front stage's line -- wide_z for the wide symbols; the parallel fit's has pf_second there)
+enum class Front { window_class, any, wide };
+enum class Fit { lds, far };
+struct TiledTrace {
+    const char *front, *pfit, *fit, *back;
+    int S, H;
+    uint32_t y_len, r_front, r_len;
+};
+// The chain of a time-tiled set that is not pipelined: front stage (screened timing and picks into the scratch), fit stage, back
+// stage (the outputs).  (A call these cannot carry comes out with guard 1 and nothing committed: the launches behind them redo it.)
+psk_soft_status enqueue_tiled(const Round &r, const LaunchSet &s, const TiledTrace &t, Front front, Fit fit, hipStream_t st)
+{
+    psk_soft_handle *const h = r.h;
+    const uint32_t *const l = r.d_list + s.off;
+    const uint32_t ring_cap = h->lim.ring_cap, fit_cap = h->lim.fit_cap;
+    PSK_HIP(mark(r, st, t.front, t.S, t.H, s.off, s.cnt, s.tiles_max, t.y_len, t.r_front));
+    if (front == Front::window_class)
+        PSK_HIP(psk::launch_tile_front(t.S, class_H(t.H), r.d_plans, l, r.ch0, s.cnt, s.tiles_max, h->d_state, h->d_ring, ring_cap, t.r_len, h->d_tiles,
+                                       h->d_traw, h->d_ts, h->pf.chan, 0u, st));
+    else if (front == Front::any)
+        PSK_HIP(psk::launch_tile_front_any(r.d_plans, l, r.ch0, s.cnt, s.tiles_max, s.max_S, h->d_state, h->d_ring, ring_cap, h->d_tiles, h->d_traw,
+                                           h->d_ts, h->pf.chan, st));
+    else
+        PSK_HIP(psk::launch_wide_front(r.d_plans, l, r.ch0, s.cnt, s.tiles_max, s.max_S, h->d_ring, ring_cap, h->d_tiles, h->d_traw, h->d_ts,
+                                       h->pf.chan, h->d_wide_rec, h->d_wide_stat, st));
+    if (fit == Fit::lds && h->opt_pfit) {  // (the parallel fit, then the block-by-block fit for what it leaves)
+        PSK_HIP(mark(r, st, t.pfit, t.S, t.H, s.off, s.cnt, s.tiles_max, t.y_len, r.pf_second));
+        PSK_HIP(psk::launch_pfit(r.d_plans, l, r.ch0, s.cnt, s.tiles_max, h->d_state, h->d_ring, ring_cap, h->d_yv, fit_cap, t.y_len, h->d_tiles,
+                                 h->d_traw, h->d_ts, h->d_test, h->pf, r.pf_second, st));
+    }
+    PSK_HIP(mark(r, st, t.fit, t.S, t.H, s.off, s.cnt, s.tiles_max, t.y_len, t.r_len));
+    if (fit == Fit::lds)
+        PSK_HIP(psk::launch_tile_fit(r.d_plans, l, r.ch0, s.cnt, h->d_state, h->d_ring, ring_cap, h->d_yv, fit_cap, t.y_len, h->d_tiles, h->d_traw,
+                                     h->d_ts, h->d_test, h->pf, st));
+    else
+        PSK_HIP(psk::launch_far_fit(r.d_plans, l, r.ch0, s.cnt, h->d_state, h->d_ring, ring_cap, h->d_yv, fit_cap, h->d_far_y, h->far_rows_cap,
+                                    h->d_tiles, h->d_traw, h->d_ts, h->d_test, st));
+    PSK_HIP(mark(r, st, t.back, t.S, t.H, s.off, s.cnt, s.tiles_max, t.y_len, t.r_len));
+    PSK_HIP(psk::launch_tile_back(r.d_plans, l, r.ch0, s.cnt, s.tiles_max, h->d_state, h->d_tiles, h->d_ts, h->d_test, 0u, 0u, st));
+    return PSK_SOFT_OK;
+}
+// the sets without an instantiation on the caller's stream: any, wide, then the far fit's quiet calls and its two sets -- the same
+// front and back stages around the fit stage with its rings in device memory (no LDS ring: y_len 0)
+psk_soft_status enqueue_any_sets(const Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    const PlanSummary &res = r.res;
+    const LaunchSet &any = res.any, &wide = res.wide, &anyf = res.anyf, &widef = res.widef;
+    if (any.cnt)
+        PSK_TRY(enqueue_tiled(r, any, {"tile_front_any", "pfit (any)", "tile_fit (any)", "tile_back (any)", any.max_S, 0, ring_floats(any.max_n, 512u), 0, 0},
+                              Front::any, Fit::lds, r.stream));
+    if (wide.cnt)
+        PSK_TRY(enqueue_tiled(r, wide, {"wide_front (chunk, pick)", "pfit (wide)", "tile_fit (wide)", "tile_back (wide)", wide.max_S, 0,
+                                        ring_floats(wide.max_n, 512u), r.wide_z, 0},
+                              Front::wide, Fit::lds, r.stream));
+    if (res.quietf.cnt) {
+        PSK_HIP(mark(r, r.stream, "far_quiet (calls that emit nothing)", 0, 0, res.quietf.off, res.quietf.cnt, 0, 0, 0));
+        PSK_HIP(psk::launch_far_quiet(h->d_plans[r.slot], r.d_list + res.quietf.off, r.ch0, res.quietf.cnt, h->d_state, h->d_ring, h->lim.ring_cap,
+                                      h->d_yv, h->lim.fit_cap, h->d_far_y, h->far_rows_cap, r.stream));
+    }
+    if (anyf.cnt)
+        PSK_TRY(enqueue_tiled(r, anyf, {"tile_front_any (far)", nullptr, "far_fit (any)", "tile_back (any, far)", anyf.max_S, 0, 0, 0, 0}, Front::any,
+                              Fit::far, r.stream));
+    if (widef.cnt)
+        PSK_TRY(enqueue_tiled(r, widef, {"wide_front (chunk, pick; far)", nullptr, "far_fit (wide)", "tile_back (wide, far)", widef.max_S, 0, 0, r.wide_z, 0},
+                              Front::wide, Fit::far, r.stream));
+    return PSK_SOFT_OK;
+}
+// A pipelined class: front(range j) on the class's stream, fit(range j) on a second stream behind it -- under front(range j + 1) --,
+// back(range j) on a third behind that (psk_tile.hip: psk_tile_fit_range_kernel)
+psk_soft_status enqueue_piped(const Round &r, const LaunchSet &s, int S, int H, uint32_t y_len, uint32_t r_len, hipStream_t st)
+{
+    psk_soft_handle *const h = r.h;
+    const uint32_t cnt = s.cnt, T = s.tiles_max, tr = s.pipe_tiles;
+    const uint32_t *const l = r.d_list + s.off;
+    char *const carry = static_cast<char *>(h->d_pipe_carry) + psk::pipe_carry_bytes() * s.off;
+    float *const carry_y = h->d_pipe_y + (size_t)kPipeMaxYLen * s.off;
+    const uint32_t y_pipe = ring_floats(s.max_n, 512u);
+    int e = 0;
+    PSK_HIP(hipEventRecord(h->pipe_ev[e], st));  // (the side streams start behind everything this one carries)
+    PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
+    PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
+    e++;
+    for (uint32_t t0 = 0; t0 < T; t0 += tr) {
+        const uint32_t nt = T - t0 < tr ? T - t0 : tr;
+        PSK_HIP(mark(r, st, "pipe_front", S, H, s.off, cnt, nt, y_len, r_len));
+        PSK_HIP(psk::launch_tile_front(S, class_H(H), r.d_plans, l, r.ch0, cnt, nt, h->d_state, h->d_ring, h->lim.ring_cap, r_len, h->d_tiles,
+                                       h->d_traw, h->d_ts, h->pf.chan, t0, st));
+        PSK_HIP(hipEventRecord(h->pipe_ev[e], st));
+        PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
+        e++;
+        PSK_HIP(mark(r, h->pipe_st[0], "pipe_fit", S, H, s.off, cnt, nt, y_pipe, 0));
+        PSK_HIP(psk::launch_tile_fit_range(r.d_plans, l, r.ch0, cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_pipe,
+                                           h->d_tiles, h->d_traw, h->d_ts, h->d_test, carry, carry_y, t0, nt, h->pipe_st[0]));
+        PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[0]));
+        PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
+        e++;
+        PSK_HIP(mark(r, h->pipe_st[1], "pipe_back", S, H, s.off, cnt, nt, y_pipe, 0));
+        PSK_HIP(psk::launch_tile_back(r.d_plans, l, r.ch0, cnt, nt, h->d_state, h->d_tiles, h->d_ts, h->d_test, t0, 1u, h->pipe_st[1]));
+    }
+    PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[1]));  // (behind the last fit too: the last back waited for it)
+    PSK_HIP(hipStreamWaitEvent(st, h->pipe_ev[e], 0));
+    return PSK_SOFT_OK;
+}
+// One window class (samplesPerBaud, history depth) on its stream: the time-tiled kernels first where it has its tiles; then screened
+// timing, then the exact-timing instantiation, which picks up the calls the screening refused (the reference-order kernel: those of both).
+psk_soft_status enqueue_class(const Round &r, int S, int H, hipStream_t st)
+{
+    psk_soft_handle *const h = r.h;
+    const LaunchSet &s = r.res.cls[S][H];
+    const uint32_t *const l = r.d_list + s.off;
+    const uint32_t y_len = ring_floats(s.max_n, psk::ering_dynamic(S) ? 256u : 512u);
+    const uint32_t r_len = class_H(H) == 1 ? ((s.max_A + 128u + 1u) & ~1u) : 0u;
+    if (s.tiled && s.piped)
+        PSK_TRY(enqueue_piped(r, s, S, H, y_len, r_len, st));
+    else if (s.tiled)
+        PSK_TRY(enqueue_tiled(r, s, {"tile_front", "pfit", "tile_fit", "tile_back", S, H, y_len, r_len, r_len}, Front::window_class, Fit::lds, st));
+    // (the exact tier only works on the calls the tier in front of it left; behind the time-tiled kernels, whose front
+    // stage IS the screened timing, it is the exact tier that picks up what they hand over)
+    const psk::PktFormat *const f = class_pkt(H);
+    for (int exact = s.tiled ? 1 : 0; exact <= 1; exact++) {
+        if (exact && diag_no_tail())
+            break;
+        PSK_HIP(mark(r, st, exact ? "fast (exact tier)" : "fast (screened tier)", S, H, s.off, s.cnt, 0, y_len, r_len));
+        if (f)
+            PSK_HIP(psk::launch_fast_pkt((int)f->id, S, exact, r.d_plans, l, r.ch0, s.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                         h->lim.fit_cap, y_len, r_len, st));
+        else
+            PSK_HIP(psk::launch_fast(S, class_H(H), exact, r.d_plans, l, r.ch0, s.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                     h->lim.fit_cap, y_len, r_len, st));
+    }
+    if (r.deferred && f)  // (the class's hand-overs are redone on its own stream, in front of its next call)
+        PSK_HIP(psk::launch_seq_pkt((int)f->id, r.d_plans, l, r.ch0, s.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+    else if (r.deferred)
+        PSK_HIP(psk::launch_seq(r.d_plans, l, r.ch0, s.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+    return PSK_SOFT_OK;
+}
+// The end of the call: deferred, the side streams keep what they carry (an event each, for the slot); joined, the caller's stream waits for
+// them and the reference-order kernel takes the calls planned for it or handed over -- each of its builds on its own channels.
+psk_soft_status enqueue_join_and_tail(Round &r, int used_aux)
+{
+    psk_soft_handle *const h = r.h;
+    const hipStream_t st = r.stream;
+    if (r.deferred) {
+        for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
+            if (!h->slot_aux_ev[r.slot][a])
+                PSK_HIP(hipEventCreateWithFlags(&h->slot_aux_ev[r.slot][a], hipEventDisableTiming));
+            PSK_HIP(hipEventRecord(h->slot_aux_ev[r.slot][a], h->aux[a]));
+            h->slot_aux_used[r.slot][a] = true;
+        }
+        h->deferred_pending = true, h->deferred_sig = r.sig, h->deferred_stream = st;
+        return PSK_SOFT_OK;
+    }
+    for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
+        PSK_HIP(hipEventRecord(h->aux_join[a], h->aux[a]));
+        PSK_HIP(hipStreamWaitEvent(st, h->aux_join[a], 0));
+    }
+    if (!r.res.any_seq && !r.res.any_emit)  // (any_emit: the exactness guard may hand calls over at run time)
+        return PSK_SOFT_OK;
+    PSK_HIP(mark(r, st, "seq (reference order)", 0, 0, ~0u, r.nch, 0, 0, 0));
+    if (diag_no_tail())
+        return PSK_SOFT_OK;
+    if (!r.n_in_place && !r.n_wide_seq) {
+        PSK_HIP(psk::launch_seq(r.d_plans, nullptr, r.ch0, r.nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+        return PSK_SOFT_OK;
+    }
+    const uint32_t *const d_seq =
+        reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(r.d_plans)) + slot_seq_offset(r.nch));
+    PSK_HIP(psk::launch_seq(r.d_plans, d_seq, r.ch0, r.n_seq_narrow, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
+    const uint32_t *d_seq_f = d_seq + r.n_seq_narrow;
+    for (int f = 0; f < psk::kNumPktFormats; d_seq_f += r.n_in_place_f[f], f++)
+        PSK_HIP(psk::launch_seq_pkt((int)psk::kPktFormats[f].id, r.d_plans, d_seq_f, r.ch0, r.n_in_place_f[f], h->d_state, h->d_ring, h->lim.ring_cap,
+                                    h->d_yv, h->lim.fit_cap, st));
+    if (r.n_wide_seq)
+        PSK_HIP(mark(r, st, "seq_wide (reference order, samplesPerBaud > 1024)", (int)r.wide_seq_S, 0, ~0u, 0, 0, 0, 0));
+    PSK_HIP(psk::launch_seq_wide(r.d_plans, d_seq + (r.nch - r.n_wide_seq), r.ch0, r.n_wide_seq, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                 h->lim.fit_cap, h->d_wide_symE, r.wide_seq_S, st));
+    return PSK_SOFT_OK;
+}
+// Every launch of the call, in order: conversion pre-passes, the channels that emit nothing, the sets without an instantiation, then
+// the window classes.  A batch that mixes classes runs them SIDE BY SIDE -- each class is its own instantiation with its own register
+// and LDS appetite, and one after the other each would leave part of the machine idle --: on side streams forked off the caller's
+// behind the plan upload and joined again in front of the reference-order kernel; the deepest histories are launched first.
+psk_soft_status enqueue(Round &r)
+{
+    psk_soft_handle *const h = r.h;
+    const PlanSummary &res = r.res;
+    const hipStream_t stream = r.stream;
+    const psk::CvtDesc *d_desc = reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(r.d_plans)) + slot_cvt_offset(r.nch));
+    for (int f = 0; f < psk::kNumPktFormats; d_desc += r.n_cvt_f[f], f++) {
+        if (!r.n_cvt_f[f])
+            continue;
+        PSK_HIP(mark(r, stream, psk::kPktFormats[f].convert, 0, 0, ~0u, 0, r.n_cvt_f[f], 0, 0));
+        PSK_HIP(psk::launch_convert((int)psk::kPktFormats[f].id, d_desc, r.n_cvt_f[f], r.cvt_max_n[f], stream));
+    }
+    if (res.quiet.cnt) {
+        const uint32_t y_len = ring_floats(res.quiet.max_n, 512u);
+        PSK_HIP(mark(r, stream, "fast<0,1> (calls that emit nothing)", 0, 1, res.quiet.off, res.quiet.cnt, 0, y_len, 0));
+        PSK_HIP(psk::launch_fast(0, 1, 0, r.d_plans, r.d_list + res.quiet.off, r.ch0, res.quiet.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                 h->lim.fit_cap, y_len, 0u, stream));
+    }
+    PSK_TRY(enqueue_any_sets(r));
+    if (res.quiet.cnt && r.deferred)  // (every launch set ends its own calls: the quiet channels' on the caller's stream)
+        PSK_HIP(psk::launch_seq(r.d_plans, r.d_list + res.quiet.off, r.ch0, res.quiet.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
+                                h->lim.fit_cap, stream));
+    if (r.fork) {
+        if (!h->aux_fork) {  // (the side streams, created at the first call that mixes window classes)
+            PSK_HIP(hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming));
+            // (streams of one priority share a few hardware queues, and two streams that land on the same one run their kernels one
+            // after the other: a stream of another priority gets a queue of its own -- DESIGN.md 3.5)
+            int prio_lo = 0, prio_hi = 0;
+            PSK_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+            for (int k = 0; k < kAuxStreams; k++) {
+                const char *pe = getenv("PSK_SOFT_AUX_PRIO");
+                const int mode = pe ? atoi(pe) : 1;
+                if (mode == 0 || prio_lo == prio_hi)
+                    PSK_HIP(hipStreamCreateWithFlags(&h->aux[k], hipStreamNonBlocking));
+                else
+                    PSK_HIP(hipStreamCreateWithPriority(&h->aux[k], hipStreamNonBlocking, mode == 1 ? prio_hi : prio_lo));
+                PSK_HIP(hipEventCreateWithFlags(&h->aux_join[k], hipEventDisableTiming));
+            }
+        }
+        PSK_HIP(hipEventRecord(h->aux_fork, stream));
+    }
+    int used_aux = 0;
+    for (int i = 0; i < r.n_cls; i++) {
+        // class 0 stays on the caller's stream, the others take the side streams in turn
+        hipStream_t st = stream;
+        if (r.fork && i > 0) {
+            const int a = (i - 1) % kAuxStreams;
+            st = h->aux[a];
+            if (i - 1 < kAuxStreams) {
+                PSK_HIP(hipStreamWaitEvent(st, h->aux_fork, 0));
+                used_aux = i;
+            }
+        }
+        PSK_TRY(enqueue_class(r, r.cls[i].S, r.cls[i].H, st));
+    }
+    PSK_TRY(enqueue_join_and_tail(r, used_aux));
+    if (r.tile_syms || r.n_wide_seq)
+        PSK_HIP(hipEventRecord(h->tile_ev, stream));
+    if (r.n_cvt) {
+        PSK_HIP(hipEventRecord(r.cv->ev, stream));
+        r.cv->ev_used = true;
+    }
+    PSK_HIP(hipEventRecord(h->ev[r.slot], stream));
+    return PSK_SOFT_OK;
+}
+// One pass of the control plane over a batch and the launches it asks for, phase by phase.  cont[i], pieces of a call the
+// library has cut (process_device_call): bit 0 = packet i continues the call of the packet before it (plan_call's `cont`), bit 1 = more
+// pieces of the call follow (no end-of-call wrap yet), bit 2 = the piece is cut where the reference does not rebuild its sums.
+psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts, psk_soft_output_t *outs,
+                              void *stream_v, const uint8_t *cont)
+{
+    if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
+    if (h->poisoned)
+        return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: an earlier call failed inside HIP after its kernels were enqueued; the "
+                                      "channel states are undefined -- destroy the handle (or import saved states into a new one)");
+    Round r{h, ch0, nch, pkts, outs, cont, stream_v ? (hipStream_t)stream_v : h->stream, h->slot, h->dry,
+            (h->opt_qpsk_sign_map ? (uint32_t)psk::PLAN_QPSK_SIGN_MAP : 0u) | (h->opt_ties_in_place ? 0u : (uint32_t)psk::PLAN_TIES_HANDOVER), h->lim};
+    PSK_TRY(take_slot(r));
+    plan_stamped(r);
+    if (!r.stamped) {
+        ctl_touch_range(h, ch0, ch0 + nch);  // (the ordinary path writes the channels one by one)
+        plan_each(r);
+    }
+    if (r.res.st == PSK_SOFT_OK && r.res.long_call && !cont) {
+        g_long_call = true;  // (nothing committed, nothing enqueued: the caller cuts the call into pieces)
+        return PSK_SOFT_OK;
+    }
+    if (r.res.st != PSK_SOFT_OK)
+        return refusal(r);
+    if (h->dry || !r.res.any_plan) {
+        commit(r);
+        return PSK_SOFT_OK;
+    }
+    PSK_TRY(wait_for_overlapping_calls(r));
+    // lists and places, then the scratch they need: every phase may send channels to the reference-order kernel instead
+    move_in_place_back(r);
+    fill_lists(r);
+    place_all(r);
+    for (psk_soft_status (*phase)(Round &) : {scratch_tiles, scratch_wide, scratch_far_rows, scratch_wide_seq, scratch_order, conversion_descriptors})
+        PSK_TRY(phase(r));
+    reference_order_lists(r);
+    if (h->opt_validate)
+        PSK_TRY(validate(r));
+    bool cut = false;
+    PSK_TRY(choose_schedule(r, &cut));
+    if (cut) {
+        g_split_pieces = h->opt_split;
+        return PSK_SOFT_OK;
+    }
+    PSK_TRY(upload(r));
+    const psk_soft_status est = enqueue(r);
+    if (est != PSK_SOFT_OK) {
+        h->poisoned = true;
+        return est;
+    }
+    commit(r);
+    if (r.tile_syms || r.n_wide_seq) {
+        h->tile_ev_used = true;
+        h->tile_stream = r.stream;
+    }
+    h->slot = (h->slot + 1) % kPlanSlots;
+    h->ev_used[r.slot] = true;
+    h->slot_stream[r.slot] = r.stream, h->slot_ch0[r.slot] = ch0, h->slot_nch[r.slot] = nch;
+    return PSK_SOFT_OK;
+}
+#undef PSK_TRY
 }  // namespace
 
 extern "C" {
@@ -831,1233 +2056,6 @@ uint64_t psk_soft_output_capacity(const psk_soft_handle_t *h, uint32_t ch, uint6
     ctl_sync(h);
     uint64_t S = h->ctl[ch].props.samplesPerBaud ? h->ctl[ch].props.samplesPerBaud : 1;
     return (n_complex + S - 1) / S + 1;
-}
-
-// One pass of the control plane over a batch and the launches it asks for.  cont[i], pieces of a call the library
-// has cut (process_device below): bit 0 = packet i continues the call of the packet before it (plan_call's `cont`), bit 1 = more
-// pieces of the call follow (no end-of-call wrap yet).
-static psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                     psk_soft_output_t *outs, void *stream_v, const uint8_t *cont)
-{
-    if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
-        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
-    if (h->poisoned)
-        return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: an earlier call failed inside HIP after its kernels were enqueued; the "
-                                      "channel states are undefined -- destroy the handle (or import saved states into a new one)");
-    // The plans are written straight into the pinned upload slot of this call: wait until the launch
-    // that last used the slot has consumed it.  (A refused call does not advance the slot.)
-    const int slot = h->slot;
-    psk::ChanPlan *plans;
-    if (h->dry) {
-        if (h->plans_dry.size() < nch)
-            h->plans_dry.resize(nch);
-        plans = h->plans_dry.data();
-    } else {
-        PSK_HIP(hipSetDevice(h->device));
-        if (h->ev_used[slot])
-            PSK_HIP(hipEventSynchronize(h->ev[slot]));
-        for (int a = 0; a < kAuxStreams; a++)
-            if (h->slot_aux_used[slot][a]) {  // (a deferred call's classes end on the side streams)
-                PSK_HIP(hipEventSynchronize(h->slot_aux_ev[slot][a]));
-                h->slot_aux_used[slot][a] = false;
-            }
-        plans = h->h_plans[slot];
-    }
-    // plan on copies (ctl_next); commit only if every channel of the batch is accepted
-    const bool dry = h->dry;
-    const uint32_t extra_flags = (h->opt_qpsk_sign_map ? (uint32_t)psk::PLAN_QPSK_SIGN_MAP : 0u) |
-                                 (h->opt_ties_in_place ? 0u : (uint32_t)psk::PLAN_TIES_HANDOVER);
-    const psk::Limits lim = h->lim;
-    // what a planned channel asks of the launches (`mult` channels with this very plan)
-    // CS16, CS8 and CF16 channels of the window classes with in-place instantiations (psk_fast_inst.hip, PSK_INST_PKT): a class of
-    // their own per format, no conversion.  (What would go through the time-tiled kernels is moved back to the float class and the
-    // pre-pass below.)
-    auto in_place = [&](const psk::ChanPlan &p, const psk::PktFormat &f) {
-        return (p.lf_flags & f.flag) && p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) && p.A <= 128u &&
-               p.lf_n <= kDeepFit && psk::fast_pkt_has((int)f.id, (int)p.S);
-    };
-    // the class of a planned channel that emits on the wave-scan kernels
-    auto class_of = [&](const psk::ChanPlan &p) {
-        for (const psk::PktFormat &f : psk::kPktFormats)
-            if (p.lf_flags & f.in_place)
-                return f.cls;
-        return psk::fast_hist_blocks(p.A) + (p.lf_n > kDeepFit ? 8 : 0);
-    };
-    auto account = [&](psk::ChanPlan &p, PlanSummary &r, uint32_t mult) {
-        r.any = true;
-        if (p.mode == psk::PLAN_FAST) {
-            if (p.n_out && (p.lf_flags & psk::PLAN_FARFIT)) {
-                r.any_emit = true;
-                PlanSummary::FarSet &f = p.S > kSeqMaxS ? r.widef : r.anyf;
-                f.cnt += mult;
-                const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
-                f.blocks += (uint64_t)nb * mult;
-                if (nb > f.max_blocks) f.max_blocks = nb;
-                if (p.A > f.max_A) f.max_A = p.A;
-                if (p.S > f.max_S) f.max_S = p.S;
-            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
-                r.any_emit = true;
-                r.cnt_wide += mult;
-                const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
-                r.blocks_wide += (uint64_t)nb * mult;
-                if (nb > r.max_blocks_wide) r.max_blocks_wide = nb;
-                if (p.lf_n > r.max_n_wide) r.max_n_wide = p.lf_n;
-                if (p.A > r.max_A_wide) r.max_A_wide = p.A;
-                if (p.S > r.max_S_wide) r.max_S_wide = p.S;
-            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
-                r.any_emit = true;
-                r.cnt_any += mult;
-                const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
-                r.blocks_any += (uint64_t)nb * mult;
-                if (nb > r.max_blocks_any) r.max_blocks_any = nb;
-                if (p.lf_n > r.max_n_any) r.max_n_any = p.lf_n;
-                if (p.A > r.max_A_any) r.max_A_any = p.A;
-                if (p.S > r.max_S_any) r.max_S_any = p.S;
-            } else if (p.n_out) {
-                r.any_emit = true;
-                for (const psk::PktFormat &f : psk::kPktFormats)
-                    if (in_place(p, f))
-                        p.lf_flags |= f.in_place;
-                const int Hh = class_of(p);
-                r.need_SH[p.S][Hh] = true;
-                r.cnt_SH[p.S][Hh] += mult;
-                if (p.lf_n > r.max_n[p.S][Hh]) r.max_n[p.S][Hh] = p.lf_n;
-                if (p.A > r.max_A[p.S][Hh]) r.max_A[p.S][Hh] = p.A;
-                const uint32_t nb = (uint32_t)((p.n_out + 127u) / 128u);
-                r.blocks_SH[p.S][Hh] += (uint64_t)nb * mult;
-                if (nb > r.max_blocks_SH[p.S][Hh]) r.max_blocks_SH[p.S][Hh] = nb;
-            } else if (lim.far_fit && p.lf_n > lim.fast_fit_max && p.lf_len0) {
-                r.cnt_quietf += mult;  // (nothing emitted, but prologue and epilogue go through the window: no LDS holds it)
-            } else {
-                r.any_quiet = true;
-                r.cnt_quiet += mult;
-                // (an empty far window needs no room in the launch's LDS ring: nothing is copied in or out)
-                if (p.lf_n > r.max_n_quiet && (p.lf_len0 || p.lf_n <= lim.fast_fit_max)) r.max_n_quiet = p.lf_n;
-            }
-        } else {
-            r.any_seq = true;
-            if (!lim.force_seq && p.lf_n <= (lim.far_fit ? 65535u : lim.fast_fit_max) &&
-                (p.n_out > psk::kResyncCount || (uint64_t)p.lf_count0 + p.n_out > psk::kResyncCount))
-                r.long_call = true;
-        }
-    };
-    uint32_t *const handed_over = dry ? nullptr : psk::plan_header(h->d_plans[slot]);  // (psk_plan.h)
-    // (packet data: 8-byte aligned float pairs, 4-byte aligned int16 and binary16 pairs, 2-byte aligned int8 pairs)
-    auto misaligned = [&](const psk::ChanPlan &p) {
-        uintptr_t in_mask = 7u;
-        for (const psk::PktFormat &f : psk::kPktFormats)
-            if (p.lf_flags & f.flag)
-                in_mask = f.align_mask;
-        return !dry && ((p.n_in && !p.in) || ((uintptr_t)p.in & in_mask) || ((uintptr_t)p.soft & 7u) || ((uintptr_t)p.bits & 3u) ||
-                        ((uintptr_t)p.phase & 3u) || ((uintptr_t)p.sidx & 3u));
-    };
-
-    // ---- the stamped path ----
-    // Channels that were configured alike and have been fed packets of the same length ever since hold IDENTICAL control state
-    // -- it depends on nothing else (psk_ctl.h) -- and a batch of equal packets then gets the same plan in every channel but for
-    // its five pointers.  Such a batch is planned ONCE: plan_call on channel ch0, the plan stamped into the other slots with
-    // the pointers patched, the result fields of outs[] copied, and the new control state kept in ONE copy (uni_ctl) that
-    // stands for the whole range until somebody looks at a single channel (ctl_sync).  What the loop below still does per
-    // channel is read the packet and the output descriptor (the equal-packets test) and write the plan: ~3 ns against ~14 ns.
-    // Anything unusual -- a refused call, a packet that differs, a buffer too small or misaligned -- leaves the stamped path for
-    // the ordinary one below, which plans every channel on its own and reports the error as it always did.
-    bool stamped = false;
-    psk::ChanCtl stamp_ctl;
-    psk_soft_handle::UniRun *run = nullptr;
-    PlanSummary res;
-    if (h->opt_stamp && !cont && nch >= 16u) {
-        bool uniform = false;
-        run = run_find(h, ch0, ch0 + nch);
-        if (run) {
-            uniform = true;
-        } else {
-            ctl_touch_range(h, ch0, ch0 + nch);  // (runs that overlap the range without being it)
-            const bool known_mixed = h->mixed_ttl > 0 && h->mixed_lo == ch0 && h->mixed_hi == ch0 + nch;
-            if (known_mixed) {
-                h->mixed_ttl--;
-            } else {
-                uniform = true;
-                const psk::ChanCtl &c0 = h->ctl[ch0];
-                for (uint32_t i = 1; i < nch && uniform; i++) uniform = ctl_equal(c0, h->ctl[ch0 + i]);
-                if (uniform) {
-                    for (auto &r : h->uni)
-                        if (r.hi == r.lo) {
-                            run = &r;
-                            break;
-                        }
-                    if (!run) {  // (every slot taken: the first one makes room)
-                        run = &h->uni[0];
-                        run_sync(h, *run);
-                    }
-                    run->lo = ch0, run->hi = ch0 + nch, run->lazy = false;
-                } else {
-                    h->mixed_lo = ch0, h->mixed_hi = ch0 + nch, h->mixed_ttl = 256;
-                }
-            }
-        }
-        if (uniform) {
-            stamp_ctl = run->lazy ? run->ctl : h->ctl[ch0];
-            psk::ChanPlan &p0 = plans[0];
-            const psk_soft_packet_t &k0 = pkts[0];
-            bool ok = psk::plan_call(stamp_ctl, lim, k0, outs[0], p0, false) == PSK_SOFT_OK && p0.mode != psk::PLAN_SKIP &&
-                      !misaligned(p0);
-            if (ok) {
-                p0.lf_flags |= extra_flags;
-                p0.handed_over = handed_over;
-                account(p0, res, nch);
-                ok = !res.long_call;
-            }
-            if (ok) {
-                const psk_soft_output_t o0 = outs[0];
-                const uint64_t n_out = p0.n_out;
-                uint32_t i = 1;
-                for (; i < nch; i++) {
-                    const psk_soft_packet_t &k = pkts[i];
-                    psk_soft_output_t &o = outs[i];
-                    if (k.n_floats != k0.n_floats || k.format != k0.format || k.present != k0.present || k.sri_mode != k0.sri_mode ||
-                        k.sriChanged != k0.sriChanged ||
-                        k.inputQueueFlushed != k0.inputQueueFlushed || std::memcmp(&k.sri_xdelta, &k0.sri_xdelta, sizeof(double)) != 0)
-                        break;
-                    if (n_out > o.cap_symbols && (o.soft || o.phase))
-                        break;
-                    psk::ChanPlan &p = plans[i];
-                    p = p0;
-                    p.in = k.data, p.soft = o.soft, p.bits = o.bits, p.phase = o.phase, p.sidx = o.sampleIndex;
-                    if (misaligned(p))
-                        break;
-                    o.ret = o0.ret, o.n_symbols = o0.n_symbols, o.n_bits = o0.n_bits, o.n_sampleIndex = o0.n_sampleIndex;
-                    o.sri_pushed = o0.sri_pushed, o.sri_soft_xdelta = o0.sri_soft_xdelta, o.sri_bits_xdelta = o0.sri_bits_xdelta;
-                    o.n_warn = o0.n_warn;
-                }
-                ok = i == nch;
-            }
-            stamped = ok;
-            if (!stamped)
-                res = PlanSummary();
-        }
-    }
-    if (!stamped)
-        ctl_touch_range(h, ch0, ch0 + nch);  // (the ordinary path writes the channels one by one)
-    psk::ChanCtl *const next = h->ctl_next.data() + ch0;
-    const psk::ChanCtl *const cur = h->ctl.data() + ch0;
-    auto plan_range = [&](uint32_t lo, uint32_t hi, PlanSummary &r) {
-        for (uint32_t i = lo; i < hi; i++) {
-            next[i] = cur[i];
-            psk::ChanPlan &p = plans[i];
-            psk_soft_status st = psk::plan_call(next[i], lim, pkts[i], outs[i], p, cont && (cont[i] & 1u));
-            if (st != PSK_SOFT_OK) {
-                r.st = st, r.bad = i, r.why = st == PSK_SOFT_ERR_INVALID_ARG ? 3 : 0;
-                return;
-            }
-            if (p.mode == psk::PLAN_SKIP)
-                continue;
-            if (misaligned(p)) {
-                r.st = PSK_SOFT_ERR_INVALID_ARG, r.bad = i, r.why = 2;
-                return;
-            }
-            p.lf_flags |= extra_flags;
-            p.handed_over = handed_over;
-            if (cont && (cont[i] & 2u))
-                p.lf_flags |= psk::PLAN_NO_WRAP;  // (more pieces of this call follow)
-            if (cont && (cont[i] & 4u))
-                p.lf_flags |= psk::PLAN_CARRY_DRIFT;  // (a piece cut where the reference does not rebuild its sums)
-            account(p, r, 1u);
-        }
-    };
-    // One thread: the ordinary pass is ~15 ns and ~0.5 KB of cache traffic per channel (60 us for 4096
-    // channels).  Splitting it over a thread pool was measured and dropped: the workers' share is
-    // done in 10-20 us, after which they sleep until the next call, and waking them costs more than
-    // the whole pass (spinning instead would burn cores between packets).
-    if (!stamped)
-        plan_range(0, nch, res);
-    if (res.st == PSK_SOFT_OK && res.long_call && !cont) {
-        g_long_call = true;  // (nothing committed, nothing enqueued: the caller cuts the call into pieces)
-        return PSK_SOFT_OK;
-    }
-    if (res.st != PSK_SOFT_OK) {
-        if (res.why == 2)
-            return fail(PSK_SOFT_ERR_INVALID_ARG,
-                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
-        if (res.why == 3) {
-            char buf[160];
-            std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
-                          ch0 + res.bad, (unsigned)pkts[res.bad].format);
-            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-        }
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "psk_soft_process: channel %u refused (status %d)", ch0 + res.bad, (int)res.st);
-        return fail(res.st, buf);
-    }
-    // The host mirror (ctl) is committed only once everything the call needs has been enqueued: a HIP error
-    // before the first kernel launch leaves the channels untouched; one after it poisons the handle (device
-    // state half advanced, nothing to roll it back with).
-    auto commit = [&]() {
-        if (stamped) {  // (one copy stands for the range: see ctl_sync)
-            run->ctl = stamp_ctl;
-            run->mode = plans[0].mode;
-            run->lazy = true;
-            return;
-        }
-        if (ch0 == 0 && nch == h->nch)
-            h->ctl.swap(h->ctl_next);
-        else
-            std::memcpy(static_cast<void *>(h->ctl.data() + ch0), next, sizeof(psk::ChanCtl) * nch);
-        for (uint32_t i = 0; i < nch; i++) h->last_mode[ch0 + i] = plans[i].mode;
-    };
-    if (h->dry || !res.any) {
-        commit();
-        return PSK_SOFT_OK;
-    }
-    const bool any_emit = res.any_emit, any_seq = res.any_seq, any_quiet = res.any_quiet;
-    const auto &need_SH = res.need_SH;
-    const auto &max_n = res.max_n;
-    const auto &max_A = res.max_A;
-
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
-    // Calls that touch the same channels must run in order: a call waits for the earlier calls on OTHER streams
-    // whose channel range overlaps its own (same stream: the stream orders them; older calls than the plan slots
-    // remember have completed -- a slot is only reused after its event).
-    for (int k = 0; k < kPlanSlots; k++)
-        if (k != slot && h->ev_used[k] && h->slot_stream[k] != stream && h->slot_ch0[k] < ch0 + nch && ch0 < h->slot_ch0[k] + h->slot_nch[k]) {
-            PSK_HIP(hipStreamWaitEvent(stream, h->ev[k], 0));
-            for (int a = 0; a < kAuxStreams; a++)
-                if (h->slot_aux_used[k][a])
-                    PSK_HIP(hipStreamWaitEvent(stream, h->slot_aux_ev[k][a], 0));
-        }
-    // CS16, CS8 and CF16 channels read in place have classes of their own (PktFormat::cls), which have no
-    // time-tiled kernels: where the float class would go through those (the same choice as below, on the four classes together),
-    // their channels go back to the float class and to the conversion pre-pass
-    if (!stamped || (plans[0].lf_flags & kInPlaceFlags))
-        for (int S = 2; S <= 16; S++) {
-            bool need = false;
-            for (const psk::PktFormat &f : psk::kPktFormats) need = need || res.need_SH[S][f.cls];
-            if (!need || !h->opt_tiled || !psk::tile_front_has(S, 1))
-                continue;
-            uint32_t cnt = res.cnt_SH[S][1], mb = res.max_blocks_SH[S][1], mn = res.max_n[S][1];
-            for (const psk::PktFormat &f : psk::kPktFormats) {
-                const int Hc = f.cls;
-                cnt += res.cnt_SH[S][Hc];
-                mb = res.max_blocks_SH[S][Hc] > mb ? res.max_blocks_SH[S][Hc] : mb;
-                mn = res.max_n[S][Hc] > mn ? res.max_n[S][Hc] : mn;
-            }
-            const bool pipe = h->opt_pipe == 2 ? mb >= 4u
-                                               : h->opt_pipe && h->opt_tiled == 1 && cnt >= kPipeMinChannels && cnt <= kPipeMaxChannels &&
-                                                     mb >= kPipeMinBlocks && !cont && mn + 128u <= kPipeMaxYLen;
-            const bool tiled = h->opt_tiled == 2 || pipe || (cnt <= kTiledFewChannels && mb >= kTiledMinBlocksFew) ||
-                               (cnt <= kTiledMaxChannels && mb >= kTiledMinBlocks);
-            if (!tiled)
-                continue;
-            res.need_SH[S][1] = true;
-            res.cnt_SH[S][1] = cnt;
-            res.max_blocks_SH[S][1] = mb;
-            res.max_n[S][1] = mn;
-            for (const psk::PktFormat &f : psk::kPktFormats) {
-                const int Hc = f.cls;
-                res.max_A[S][1] = res.max_A[S][1] > res.max_A[S][Hc] ? res.max_A[S][1] : res.max_A[S][Hc];
-                res.blocks_SH[S][1] += res.blocks_SH[S][Hc];
-                res.need_SH[S][Hc] = false;
-                res.cnt_SH[S][Hc] = res.max_blocks_SH[S][Hc] = res.max_n[S][Hc] = res.max_A[S][Hc] = 0;
-                res.blocks_SH[S][Hc] = 0;
-            }
-            for (uint32_t i = 0; i < nch; i++)
-                if (plans[i].S == (uint32_t)S)
-                    plans[i].lf_flags &= ~kInPlaceFlags;
-        }
-    // compact lists, one per launch, behind the plans: first the channels that emit nothing, then every (S, H)
-    // class in launch order
-    uint32_t *const h_list = reinterpret_cast<uint32_t *>(h->h_plans[slot] + nch);
-    const uint32_t *const d_list = reinterpret_cast<const uint32_t *>(h->d_plans[slot] + nch);
-    uint32_t off_SH[33][17] = {}, off_quiet = 0;
-    const uint32_t off_any = res.cnt_quiet, off_wide = res.cnt_quiet + res.cnt_any;
-    const uint32_t off_anyf = off_wide + res.cnt_wide, off_widef = off_anyf + res.anyf.cnt;  // (the far fit's two)
-    const uint32_t off_quietf = off_widef + res.widef.cnt;                                   // (... and its quiet calls)
-    const uint32_t cnt_far_rows = res.anyf.cnt + res.widef.cnt + res.cnt_quietf;            // (the three lists follow one another)
-    {
-        uint32_t run = off_quietf + res.cnt_quietf;
-        for (int S : kFastS)
-            for (int H : kClassH) {
-                off_SH[S][H] = run;
-                run += res.cnt_SH[S][H];
-            }
-        uint32_t fill_SH[33][17] = {}, fill_quiet = 0, fill_any = 0, fill_wide = 0, fill_anyf = 0, fill_widef = 0, fill_quietf = 0;
-        // (one class holds every channel, in order; the offsets of the others are equal to its end -- unless the stamped class was just
-        // moved back to the float class: its offsets are that class's then, the lists the same)
-        if (stamped)
-            for (uint32_t i = 0; i < nch; i++) h_list[i] = i;
-        for (uint32_t i = 0; i < nch && !stamped; i++) {
-            const psk::ChanPlan &p = plans[i];
-            if (p.mode != psk::PLAN_FAST)
-                continue;
-            if (p.n_out && (p.lf_flags & psk::PLAN_FARFIT)) {
-                if (p.S > kSeqMaxS)
-                    h_list[off_widef + fill_widef++] = i;
-                else
-                    h_list[off_anyf + fill_anyf++] = i;
-            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS) {
-                h_list[off_wide + fill_wide++] = i;
-            } else if (p.n_out && (p.lf_flags & psk::PLAN_ANYFRONT)) {
-                h_list[off_any + fill_any++] = i;
-            } else if (p.n_out) {
-                const int Hh = class_of(p);
-                h_list[off_SH[p.S][Hh] + fill_SH[p.S][Hh]++] = i;
-            } else if (lim.far_fit && p.lf_n > lim.fast_fit_max && p.lf_len0) {
-                h_list[off_quietf + fill_quietf++] = i;
-            } else {
-                h_list[off_quiet + fill_quiet++] = i;
-            }
-        }
-    }
-    // Window classes of few channels and long calls go through the time-tiled kernels first (psk_tile_kernel.h): their
-    // channels get a place in the scratch of the call -- symbols padded to whole blocks, K blocks to a tile, K chosen so
-    // that the class makes a few thousand tiles.
-    bool tiled_SH[33][17] = {};
-    bool pf_second = false;
-    uint32_t tiles_max_any = 0, tiles_max_wide = 0, tiles_max_anyf = 0, tiles_max_widef = 0;
-    uint32_t tiles_max_SH[33][17] = {};
-    size_t tile_syms = 0, tile_count = 0;
-    // (wide symbols first: their places in the scratch index the chunk records of psk_wide.hip too, which need not cover the others)
-    const uint32_t wide_z = (res.cnt_wide || res.widef.cnt) ? psk::wide_chunks(res.max_S_wide > res.widef.max_S ? res.max_S_wide : res.widef.max_S) : 0u;
-    // the far fit's launch sets get their places the way the two sets they are split off from do (below); never the parallel fit,
-    // whose kernels keep the window in LDS as well
-    auto place_far = [&](const PlanSummary::FarSet &f, uint32_t off, uint64_t blocks_z, uint64_t k_min, uint32_t &tiles_max) {
-        uint64_t K = blocks_z / kTiledTargetTiles;
-        K = K < k_min ? k_min : K > 16 ? 16 : K;
-        const uint64_t k_win = (f.max_A + 127u) / 128u;
-        if (K < k_win) {
-            const uint64_t k_fill = blocks_z / (kTiledTargetTiles / 2);
-            const uint64_t k_long = k_win > 64 ? 64 : k_win;
-            K = k_fill > k_long ? k_long : k_fill > K ? k_fill : K;
-        }
-        tiles_max = (uint32_t)((f.max_blocks + K - 1) / K);
-        for (uint32_t i = 0; i < f.cnt; i++) {
-            psk::ChanPlan &p = plans[h_list[off + i]];
-            const uint64_t nb = (p.n_out + 127u) / 128u;
-            p.lf_flags |= psk::PLAN_TILED;
-            p.tile_blocks = (uint32_t)K;
-            p.tile_base = (uint32_t)tile_count;
-            p.tile_off = tile_syms;
-            tile_count += (size_t)((nb + K - 1) / K);
-            tile_syms += (size_t)nb * 128u;
-        }
-    };
-    if (res.cnt_wide) {
-        // always tiled, like the classes below; a tile is one wave per chunk of 1024 timing phases, and few symbols a call fill
-        // the machine only on short tiles -- as short as one block, unless the window in front of a tile is longer
-        uint64_t K = res.blocks_wide * wide_z / kTiledTargetTiles;
-        K = K < 1 ? 1 : K > 16 ? 16 : K;
-        const uint64_t k_win = (res.max_A_wide + 127u) / 128u;
-        if (K < k_win) {
-            const uint64_t k_fill = res.blocks_wide * wide_z / (kTiledTargetTiles / 2);
-            const uint64_t k_long = k_win > 64 ? 64 : k_win;
-            K = k_fill > k_long ? k_long : k_fill > K ? k_fill : K;
-        }
-        tiles_max_wide = (uint32_t)((res.max_blocks_wide + K - 1) / K);
-        for (uint32_t i = 0; i < res.cnt_wide; i++) {
-            psk::ChanPlan &p = plans[h_list[off_wide + i]];
-            const uint64_t nb = (p.n_out + 127u) / 128u;
-            p.lf_flags |= psk::PLAN_TILED;
-            if (h->opt_pfit && p.lf_len0 == p.lf_n && p.lf_n >= 2)
-                p.lf_flags |= psk::PLAN_PFIT;
-            p.tile_blocks = (uint32_t)K;
-            p.tile_base = (uint32_t)tile_count;
-            p.tile_off = tile_syms;
-            tile_count += (size_t)((nb + K - 1) / K);
-            tile_syms += (size_t)nb * 128u;
-        }
-    }
-    if (res.widef.cnt)  // (behind the wide symbols, in front of everything else: the chunk records cover the two)
-        place_far(res.widef, off_widef, res.widef.blocks * wide_z, 1, tiles_max_widef);
-    const size_t wide_rec_need = tile_syms * wide_z * psk::wide_rec_bytes(), wide_stat_need = tile_count * wide_z * psk::wide_stat_bytes();
-    if (res.cnt_any) {
-        // (window classes without a wave-scan instantiation: always tiled, whatever the option says -- the alternative is the
-        // reference-order kernel; a tile at least as long as the longest window, so that rebuilding it stays a fraction)
-        uint64_t K = res.blocks_any / kTiledTargetTiles;
-        K = K < 2 ? 2 : K > 16 ? 16 : K;
-        // (a tile rebuilds the window in front of it: tiles at least as long as the longest window keep that a fraction of the
-        // work -- where there are tiles enough to fill the machine anyway; a few channels finish sooner on many short tiles)
-        const uint64_t k_win = (res.max_A_any + 127u) / 128u;
-        if (K < k_win) {
-            const uint64_t k_fill = res.blocks_any / (kTiledTargetTiles / 2);
-            const uint64_t k_long = k_win > 64 ? 64 : k_win;
-            K = k_fill > k_long ? k_long : k_fill > K ? k_fill : K;
-        }
-        tiles_max_any = (uint32_t)((res.max_blocks_any + K - 1) / K);
-        for (uint32_t i = 0; i < res.cnt_any; i++) {
-            psk::ChanPlan &p = plans[h_list[off_any + i]];
-            const uint64_t nb = (p.n_out + 127u) / 128u;
-            p.lf_flags |= psk::PLAN_TILED;
-            if (h->opt_pfit && p.lf_len0 == p.lf_n && p.lf_n >= 2)
-                p.lf_flags |= psk::PLAN_PFIT;
-            p.tile_blocks = (uint32_t)K;
-            p.tile_base = (uint32_t)tile_count;
-            p.tile_off = tile_syms;
-            tile_count += (size_t)((nb + K - 1) / K);
-            tile_syms += (size_t)nb * 128u;
-        }
-    }
-    if (res.anyf.cnt)
-        place_far(res.anyf, off_anyf, res.anyf.blocks, 2, tiles_max_anyf);
-    bool piped_SH[33][17] = {};
-    uint32_t pipe_tiles_SH[33][17] = {};  // tiles of a range
-    size_t pipe_need = 0;
-    // (the parallel fit's scratch, 36 of the 52 bytes a symbol, is only needed by the classes that are not pipelined: those get
-    // their places first, so that it need not cover the others)
-    size_t pf_syms = tile_syms, pf_count = tile_count;
-    for (int pass = 0; pass < (h->opt_tiled ? 2 : 0); pass++) {
-        for (int S : kFastS)
-            for (int H : kClassH) {
-                if (!res.need_SH[S][H] || class_pkt(H) || !psk::tile_front_has(S, class_H(H)))
-                    continue;
-                // pipelined: the serial fit of a range under the front stage of the next (see kPipeMinChannels)
-                // (PSK_SOFT_PIPELINED=2, tests: wherever the kernels allow it, a few blocks to a range)
-                const bool pipe = (h->opt_pipe == 2 ? res.max_blocks_SH[S][H] >= 4u
-                                                    : h->opt_pipe && h->opt_tiled == 1 && res.cnt_SH[S][H] >= kPipeMinChannels &&
-                                                          res.cnt_SH[S][H] <= kPipeMaxChannels && res.max_blocks_SH[S][H] >= kPipeMinBlocks) &&
-                                  !cont && res.max_n[S][H] + 128u <= kPipeMaxYLen && (size_t)res.blocks_SH[S][H] * 128u <= kPipeMaxSymbols;
-                if (pipe != (pass == 1))
-                    continue;
-                if (!pipe && h->opt_tiled == 1 &&
-                    !((res.cnt_SH[S][H] <= kTiledFewChannels && res.max_blocks_SH[S][H] >= kTiledMinBlocksFew) ||
-                      (res.cnt_SH[S][H] <= kTiledMaxChannels && res.max_blocks_SH[S][H] >= kTiledMinBlocks)))
-                    continue;
-                uint64_t K = res.blocks_SH[S][H] / kTiledTargetTiles;
-                K = K < 2 ? 2 : K > 16 ? 16 : K;
-                tiled_SH[S][H] = true;
-                if (pipe) {
-                    piped_SH[S][H] = true;
-                    const uint32_t T = (uint32_t)((res.max_blocks_SH[S][H] + K - 1) / K);
-                    uint32_t tr = (uint32_t)(kTiledTargetTiles / res.cnt_SH[S][H]);  // (a range = about one machine-load of tiles)
-                    tr = tr < 1u ? 1u : tr;
-                    if (h->opt_pipe == 2 && tr > 3u)
-                        tr = 3u;
-                    if (const char *e = std::getenv("PSK_SOFT_PIPE_RANGE_TILES"))  // (A/B runs)
-                        tr = std::atoi(e) > 0 ? (uint32_t)std::atoi(e) : tr;
-                    if ((T + tr - 1) / tr > kPipeMaxRanges)
-                        tr = (T + kPipeMaxRanges - 1) / kPipeMaxRanges;
-                    pipe_tiles_SH[S][H] = tr;
-                    if (off_SH[S][H] + res.cnt_SH[S][H] > pipe_need)
-                        pipe_need = off_SH[S][H] + res.cnt_SH[S][H];
-                }
-                tiles_max_SH[S][H] = (uint32_t)((res.max_blocks_SH[S][H] + K - 1) / K);
-                for (uint32_t i = 0; i < res.cnt_SH[S][H]; i++) {
-                    psk::ChanPlan &p = plans[h_list[off_SH[S][H] + i]];
-                    const uint64_t nb = (p.n_out + 127u) / 128u;
-                    p.lf_flags |= psk::PLAN_TILED;
-                    if (!pipe && h->opt_pfit && p.lf_len0 == p.lf_n && p.lf_n >= 2)
-                        p.lf_flags |= psk::PLAN_PFIT;
-                    p.tile_blocks = (uint32_t)K;
-                    p.tile_base = (uint32_t)tile_count;
-                    p.tile_off = tile_syms;
-                    tile_count += (size_t)((nb + K - 1) / K);
-                    tile_syms += (size_t)nb * 128u;
-                }
-            }
-        if (pass == 0)
-            pf_syms = tile_syms, pf_count = tile_count;
-    }
-    if (tile_syms) {
-        if (tile_syms > h->tile_sym_cap || tile_count > h->tile_cap || pf_syms > h->pf_sym_cap || pf_count > h->pf_cap) {
-            // (rare: the scratch grows to the largest call seen, plus a quarter)
-            PSK_HIP(hipDeviceSynchronize());
-            if (h->d_tiles) (void)hipFree(h->d_tiles);
-            if (h->d_traw) (void)hipFree(h->d_traw);
-            if (h->d_test) (void)hipFree(h->d_test);
-            if (h->d_ts) (void)hipFree(h->d_ts);
-            for (void *q : {(void *)h->pf.k, (void *)h->pf.y, (void *)h->pf.S, (void *)h->pf.c, (void *)h->pf.tt, (void *)h->pf.xs,
-                            (void *)h->pf.tile, (void *)h->pf.blk, (void *)h->pf.walk})
-                if (q) (void)hipFree(q);
-            h->d_tiles = nullptr, h->d_traw = h->d_test = nullptr, h->d_ts = nullptr;
-            h->pf.k = nullptr, h->pf.y = nullptr, h->pf.S = h->pf.c = h->pf.xs = nullptr, h->pf.tt = nullptr, h->pf.tile = nullptr,
-            h->pf.blk = nullptr, h->pf.walk = nullptr;
-            h->tile_cap = h->tile_sym_cap = h->pf_cap = h->pf_sym_cap = 0;
-            const size_t syms = tile_syms + tile_syms / 4, cnt = tile_count + tile_count / 4;
-            const size_t psyms = pf_syms + pf_syms / 4 + 128u, pcnt = pf_count + pf_count / 4 + 1u;
-            // (out of device memory: the call does without -- the wave-scan kernels carry everything on their own)
-            auto grab = [](auto **q, size_t bytes) { return hipMalloc((void **)q, bytes) == hipSuccess; };
-            bool got = grab(&h->d_tiles, sizeof(psk::TileInfo) * cnt) && grab(&h->d_traw, sizeof(float) * syms) &&
-                       grab(&h->d_test, sizeof(float) * syms) && grab(&h->d_ts, sizeof(float2) * syms) &&
-                       grab(&h->pf.k, sizeof(int) * psyms) && grab(&h->pf.y, sizeof(float) * psyms) && grab(&h->pf.S, sizeof(double) * psyms) &&
-                       grab(&h->pf.c, sizeof(double) * psyms) && grab(&h->pf.tt, sizeof(float) * psyms) && grab(&h->pf.xs, sizeof(double) * psyms) &&
-                       grab(&h->pf.tile, sizeof(psk::PfTile) * pcnt) && grab(&h->pf.blk, sizeof(psk::PfBlock) * (psyms / 128u + 1u)) &&
-                       grab(&h->pf.walk, sizeof(psk::PfWalk) * (psyms / 128u + 1u));
-            if (got && !h->pf.chan) {
-                got = grab(&h->pf.chan, sizeof(psk::PfChan) * h->nch) && hipMemset(h->pf.chan, 0, sizeof(psk::PfChan) * h->nch) == hipSuccess &&
-                      hipHostMalloc((void **)&h->pf.hint, 64) == hipSuccess;
-                if (got)
-                    *h->pf.hint = 0u;
-            }
-            if (!got) {
-                (void)hipGetLastError();
-                for (uint32_t i = 0; i < nch; i++) {
-                    if (plans[i].lf_flags & psk::PLAN_ANYFRONT) {  // (no kernel but the reference-order one is left for these)
-                        plans[i].mode = plans[i].S == 1u ? psk::PLAN_SEQ_S1 : psk::PLAN_SEQ;
-                        res.any_seq = true;
-                    }
-                    plans[i].lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
-                }
-                res.cnt_any = res.cnt_wide = res.anyf.cnt = res.widef.cnt = 0;
-                for (auto &row : tiled_SH)
-                    for (bool &t : row) t = false;
-                for (auto &row : piped_SH)
-                    for (bool &t : row) t = false;
-                tile_syms = 0;
-            } else {
-                h->tile_cap = cnt;
-                h->tile_sym_cap = syms;
-                h->pf_cap = pcnt;
-                h->pf_sym_cap = psyms;
-            }
-        }
-    }
-    if ((res.cnt_wide || res.widef.cnt) && (wide_rec_need > h->wide_rec_cap || wide_stat_need > h->wide_stat_cap)) {
-        // the chunk records of the wide front stage: grown to the largest call seen, plus a quarter
-        PSK_HIP(hipDeviceSynchronize());
-        if (h->d_wide_rec) (void)hipFree(h->d_wide_rec);
-        if (h->d_wide_stat) (void)hipFree(h->d_wide_stat);
-        h->d_wide_rec = h->d_wide_stat = nullptr;
-        h->wide_rec_cap = h->wide_stat_cap = 0;
-        const size_t rb = wide_rec_need + wide_rec_need / 4, sb = wide_stat_need + wide_stat_need / 4;
-        if (hipMalloc(&h->d_wide_rec, rb) == hipSuccess && hipMalloc(&h->d_wide_stat, sb) == hipSuccess) {
-            h->wide_rec_cap = rb, h->wide_stat_cap = sb;
-        } else {  // (out of device memory: the reference-order kernel carries these calls)
-            (void)hipGetLastError();
-            for (uint32_t i = 0; i < res.cnt_wide + res.widef.cnt; i++) {
-                psk::ChanPlan &p = plans[h_list[(i < res.cnt_wide ? off_wide : off_widef - res.cnt_wide) + i]];
-                p.mode = psk::PLAN_SEQ;
-                p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
-            }
-            res.cnt_wide = res.widef.cnt = 0;
-            res.any_seq = true;
-        }
-    }
-    // the far fit's rings: a row of the scratch for every channel of its two launch sets (kept from the channel's first such call on)
-    if (cnt_far_rows) {
-        if (h->far_row.empty())
-            h->far_row.assign(h->nch, 0u);
-        uint32_t used = h->far_rows_used;
-        for (uint32_t i = 0; i < cnt_far_rows; i++)
-            if (!h->far_row[ch0 + h_list[off_anyf + i]])
-                used++;
-        bool got = true;
-        if (used > h->far_rows_cap) {
-            // (the one place of this path that waits for the device: no call is in flight on a row that moves, and a row carries
-            // nothing from one call to the next)
-            PSK_HIP(hipDeviceSynchronize());
-            if (h->d_far_y) (void)hipFree(h->d_far_y);
-            h->d_far_y = nullptr;
-            h->far_rows_cap = 0;
-            const uint32_t cap = used + used / 4 < h->nch ? used + used / 4 : h->nch;
-            if (hipMalloc((void **)&h->d_far_y, psk::far_ring_bytes() * cap) == hipSuccess) {
-                h->far_rows_cap = cap;
-            } else {  // (out of device memory: the reference-order kernel carries these calls, as with the option off)
-                (void)hipGetLastError();
-                got = false;
-            }
-        }
-        for (uint32_t i = 0; i < cnt_far_rows; i++) {
-            psk::ChanPlan &p = plans[h_list[off_anyf + i]];
-            if (got) {
-                uint32_t &row = h->far_row[ch0 + h_list[off_anyf + i]];
-                if (!row)
-                    row = ++h->far_rows_used;
-                p.far_row = row - 1u;
-            } else if (p.n_out) {
-                p.mode = p.S == 1u ? psk::PLAN_SEQ_S1 : psk::PLAN_SEQ;
-                p.lf_flags &= ~(uint32_t)(psk::PLAN_TILED | psk::PLAN_PFIT | psk::PLAN_ANYFRONT | psk::PLAN_FARFIT);
-            }
-        }
-        if (!got) {
-            if (res.cnt_quietf)
-                return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the fit window of a far channel (PSK_SOFT_OPT_FAR_FIT)");
-            res.anyf.cnt = res.widef.cnt = 0;
-            res.any_seq = true;
-        }
-    }
-    // the reference-order kernel's wide build (samplesPerBaud > kSeqMaxS): a list of its own -- the other build's symbolEnergy[] is
-    // kSeqMaxS long -- and a row of symbolEnergy[] in device memory for each channel of it, as long as the widest
-    uint32_t n_wide_seq = 0, wide_seq_S = 0;
-    for (uint32_t i = 0; i < nch; i++)
-        if (plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS) {
-            n_wide_seq++;
-            wide_seq_S = plans[i].S > wide_seq_S ? plans[i].S : wide_seq_S;
-        }
-    if (n_wide_seq && (size_t)n_wide_seq * wide_seq_S > h->wide_symE_cap) {
-        PSK_HIP(hipDeviceSynchronize());
-        if (h->d_wide_symE) (void)hipFree(h->d_wide_symE);
-        h->d_wide_symE = nullptr;
-        h->wide_symE_cap = 0;
-        const size_t need = (size_t)n_wide_seq * wide_seq_S, cap = need + need / 4;
-        PSK_HIP(hipMalloc((void **)&h->d_wide_symE, sizeof(double) * cap));
-        h->wide_symE_cap = cap;
-    }
-    if (n_wide_seq && !tile_syms) {  // (the rows of symbolEnergy[] are ordered like the scratch of the time-tiled kernels)
-        if (!h->tile_ev)
-            PSK_HIP(hipEventCreateWithFlags(&h->tile_ev, hipEventDisableTiming));
-        if (h->tile_ev_used && h->tile_stream != stream)
-            PSK_HIP(hipStreamWaitEvent(stream, h->tile_ev, 0));
-    }
-    if (tile_syms) {
-        if (!h->tile_ev)
-            PSK_HIP(hipEventCreateWithFlags(&h->tile_ev, hipEventDisableTiming));
-        // second round of the parallel fit: for the next 16 tiled calls after one whose first guess of the unwrap counts
-        // failed somewhere (the kernels leave a note in page-locked memory; a late or lost note costs a call or two)
-        if (h->pf.hint && *static_cast<volatile uint32_t *>(h->pf.hint)) {
-            *static_cast<volatile uint32_t *>(h->pf.hint) = 0u;
-            h->pf_second_ttl = 16;
-        } else if (h->pf_second_ttl) {
-            h->pf_second_ttl--;
-        }
-        pf_second = h->opt_pfit == 2 || h->pf_second_ttl > 0;
-        if (h->tile_ev_used && h->tile_stream != stream)  // the scratch is one per handle
-            PSK_HIP(hipStreamWaitEvent(stream, h->tile_ev, 0));
-        if (pipe_need) {
-            // the pipelined mode's own scratch (one PipeCarry and one ring of kPipeMaxYLen floats per channel of a launch) and its
-            // two streams -- of another priority than the caller's, so that they get hardware queues of their own
-            if (pipe_need > h->pipe_cap) {
-                PSK_HIP(hipDeviceSynchronize());
-                if (h->d_pipe_carry) (void)hipFree(h->d_pipe_carry);
-                if (h->d_pipe_y) (void)hipFree(h->d_pipe_y);
-                h->d_pipe_carry = nullptr, h->d_pipe_y = nullptr, h->pipe_cap = 0;
-                const size_t cap = pipe_need + pipe_need / 4;
-                if (hipMalloc(&h->d_pipe_carry, psk::pipe_carry_bytes() * cap) == hipSuccess &&
-                    hipMalloc((void **)&h->d_pipe_y, sizeof(float) * kPipeMaxYLen * cap) == hipSuccess) {
-                    h->pipe_cap = cap;
-                } else {  // (out of device memory: the one-launch kernels do without)
-                    (void)hipGetLastError();
-                    if (h->d_pipe_carry) (void)hipFree(h->d_pipe_carry);
-                    h->d_pipe_carry = nullptr;
-                    for (auto &row : piped_SH)
-                        for (bool &t : row) t = false;
-                }
-            }
-            if (!h->pipe_st[0]) {
-                int prio_lo = 0, prio_hi = 0;
-                PSK_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-                // (CU-masked streams for the stages -- the serial ones on every n-th CU, the front stage on the others -- were measured:
-                // no gain, 2.77 ... 2.84 against 2.75 ms at 512 channels)
-                for (hipStream_t &q : h->pipe_st) PSK_HIP(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, prio_hi));
-                for (hipEvent_t &e : h->pipe_ev) PSK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            }
-        }
-    }
-    // CS16, CS8 and CF16 packets (psk_pkt.hip): converted into float2 rows of the conversion scratch by one pre-pass per
-    // format in front of the call's first kernel; their plans point at the rows from here on.  The descriptors travel behind the
-    // plans, in the same upload: the CS16 packets' first, then the CS8 packets', then the CF16 packets' (the order of kPktFormats).
-    auto cvt_format = [](const psk::ChanPlan &p) -> int {  // (the row in kPktFormats of a packet the pre-pass converts, else -1)
-        if (p.mode == psk::PLAN_SKIP || !p.n_in)
-            return -1;
-        for (int f = 0; f < psk::kNumPktFormats; f++)
-            if ((p.lf_flags & psk::kPktFormats[f].flag) && !(p.lf_flags & psk::kPktFormats[f].in_place))
-                return f;
-        return -1;
-    };
-    uint32_t n_cvt = 0, n_cvt_f[psk::kNumPktFormats] = {};  // (per format: descriptors)
-    uint64_t cvt_max_n[psk::kNumPktFormats] = {};           // (... and the longest packet)
-    CvtScratch *cv = nullptr;
-    {
-        size_t need = 0;
-        for (uint32_t i = 0; i < nch; i++) {
-            const psk::ChanPlan &p = plans[i];
-            const int f = cvt_format(p);
-            if (f >= 0) {
-                need += align_up(sizeof(float2) * p.n_in, 128);
-                n_cvt++;
-                n_cvt_f[f]++;
-            }
-        }
-        if (n_cvt) {
-            for (auto &c : h->cvt)  // (the stream's own buffer, else the one used longest ago)
-                if (c.buf && c.stream == stream) {
-                    cv = &c;
-                    break;
-                }
-            if (!cv) {
-                cv = &h->cvt[0];
-                for (auto &c : h->cvt)
-                    if (c.last_use < cv->last_use)
-                        cv = &c;
-            }
-            if (!cv->ev)
-                PSK_HIP(hipEventCreateWithFlags(&cv->ev, hipEventDisableTiming));
-            if (cv->ev_used && cv->stream != stream)
-                PSK_HIP(hipStreamWaitEvent(stream, cv->ev, 0));
-            if (need > cv->cap) {  // (rare: grows to the largest call seen, plus a quarter)
-                PSK_HIP(hipDeviceSynchronize());
-                if (cv->buf) (void)hipFree(cv->buf);
-                cv->buf = nullptr;
-                cv->cap = 0;
-                const size_t cap = align_up(need + need / 4, 4096);
-                PSK_HIP(hipMalloc((void **)&cv->buf, cap));
-                cv->cap = cap;
-            }
-            cv->stream = stream;
-            cv->last_use = ++h->cvt_calls;
-            psk::CvtDesc *const desc =
-                reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_cvt_offset(nch));
-            size_t off = 0;
-            uint32_t next[psk::kNumPktFormats] = {};  // (where each format's descriptors go on)
-            for (int f = 1; f < psk::kNumPktFormats; f++) next[f] = next[f - 1] + n_cvt_f[f - 1];
-            for (uint32_t i = 0; i < nch; i++) {
-                psk::ChanPlan &p = plans[i];
-                const int f = cvt_format(p);
-                if (f < 0)
-                    continue;
-                const uint32_t k = next[f]++;
-                desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
-                desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
-                desc[k].n = p.n_in;
-                p.in = desc[k].dst;
-                off += align_up(sizeof(float2) * p.n_in, 128);
-                cvt_max_n[f] = p.n_in > cvt_max_n[f] ? p.n_in : cvt_max_n[f];
-            }
-        }
-    }
-    // the reference-order kernel's lists when CS16 / CS8 / CF16 channels are read in place: float-build channels first, then the
-    // CS16 build's, then the CS8 build's, then the CF16 build's (and the wide symbols' last)
-    uint32_t n_in_place = 0, n_in_place_f[psk::kNumPktFormats] = {};
-    for (uint32_t i = 0; i < nch; i++)
-        for (int f = 0; f < psk::kNumPktFormats; f++) n_in_place_f[f] += (plans[i].lf_flags & psk::kPktFormats[f].in_place) ? 1u : 0u;
-    for (const uint32_t n : n_in_place_f) n_in_place += n;
-    const uint32_t n_seq_narrow = nch - n_in_place - n_wide_seq;
-    if (n_in_place || n_wide_seq) {
-        uint32_t *const seq = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[slot])) + slot_seq_offset(nch));
-        uint32_t a = 0, b[psk::kNumPktFormats] = {n_seq_narrow}, c = nch - n_wide_seq;
-        for (int f = 1; f < psk::kNumPktFormats; f++) b[f] = b[f - 1] + n_in_place_f[f - 1];
-        for (uint32_t i = 0; i < nch; i++) {
-            uint32_t *at = &a;
-            for (int f = 0; f < psk::kNumPktFormats; f++)
-                if (plans[i].lf_flags & psk::kPktFormats[f].in_place)
-                    at = &b[f];
-            if (plans[i].mode != psk::PLAN_SKIP && plans[i].S > kSeqMaxS)
-                at = &c;
-            seq[(*at)++] = i;
-        }
-    }
-    // PSK_SOFT_VALIDATE=1 (tests, the randomised comparison): what the kernels take for granted about a plan -- the samples a call
-    // reads exist, what it leaves behind fits the rings, its place in the scratch of the time-tiled kernels lies inside it -- is
-    // checked here, on the host, in front of the first launch; a violation refuses the call (nothing enqueued, nothing committed)
-    // instead of sending a kernel out of bounds.
-    if (h->opt_validate) {
-        const char *why = nullptr;
-        uint32_t bad = 0;
-        for (uint32_t i = 0; i < nch && !why; i++) {
-            const psk::ChanPlan &p = plans[i];
-            if (p.mode == psk::PLAN_SKIP)
-                continue;
-            bad = i;
-            const uint64_t S = p.S ? p.S : 1u, have = (uint64_t)p.ring_len0 + p.n_in;
-            const uint64_t nb = (p.n_out + 127u) / 128u;
-            if (p.n_out && p.S > 1u && (p.n_out + p.A - 1u) * S > have)
-                why = "the call reads samples behind the packet's end";
-            else if (p.n_out && p.S <= 1u && p.mode != psk::PLAN_SEQ_S1 && p.n_out > p.n_in)
-                why = "more symbols than samples at one sample per symbol";
-            else if (p.ring_len0 > h->lim.ring_cap || p.ring_len1 > h->lim.ring_cap || p.ring_src > 1u)
-                why = "carried samples beyond the ring";
-            else if (p.ring_len1 > have)
-                why = "more samples carried out of the call than it holds";
-            else if (p.lf_n >= h->lim.fit_cap || p.lf_len0 > p.lf_n || p.lf_head >= h->lim.fit_cap)
-                why = "LinearFit window beyond its ring";
-            else if ((p.lf_flags & psk::PLAN_TILED) && p.mode == psk::PLAN_FAST && p.n_out &&
-                     (!p.tile_blocks || p.tile_off + nb * 128u > h->tile_sym_cap ||
-                      (uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks > h->tile_cap))
-                why = "place in the time-tiled scratch outside it";
-            else if ((p.lf_flags & psk::PLAN_FARFIT) && p.mode == psk::PLAN_FAST && p.n_out &&
-                     (!h->d_far_y || p.far_row >= h->far_rows_cap || (p.lf_flags & psk::PLAN_PFIT) || p.lf_n < 128u))
-                why = "far fit without a row of its scratch";
-            else if ((p.lf_flags & psk::PLAN_PFIT) && p.mode == psk::PLAN_FAST && p.n_out &&
-                     (p.tile_off + nb * 128u > h->pf_sym_cap || (uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks > h->pf_cap))
-                why = "place in the parallel fit's scratch outside it";
-            else if (p.mode == psk::PLAN_FAST && p.n_out && !(p.lf_flags & psk::PLAN_ANYFRONT) &&
-                     (p.S < 2u || p.S > 32u || p.A > 1024u || (p.S > 16u && p.A > 512u)))
-                why = "window class without a wave-scan instantiation planned for one";
-            else if (p.mode == psk::PLAN_FAST && p.n_out > psk::kResyncCount)
-                why = "a piece longer than 2^20 symbols on the wave-scan kernels";
-            else if ((p.lf_flags & psk::PLAN_TILED) && (p.lf_flags & psk::PLAN_ANYFRONT) && p.S > kSeqMaxS && p.mode == psk::PLAN_FAST && p.n_out &&
-                     (psk::wide_chunks(p.S) > wide_z || (p.tile_off + nb * 128u) * wide_z * psk::wide_rec_bytes() > h->wide_rec_cap ||
-                      ((uint64_t)p.tile_base + (nb + p.tile_blocks - 1u) / p.tile_blocks) * wide_z * psk::wide_stat_bytes() > h->wide_stat_cap))
-                why = "place in the wide-symbol scratch outside it";
-            else if (p.S > kSeqMaxS && (p.S > wide_seq_S || !h->d_wide_symE || (size_t)n_wide_seq * wide_seq_S > h->wide_symE_cap))
-                why = "wide symbol without a row of symbolEnergy";
-            else if (cvt_format(p) >= 0 &&
-                     (!cv || (const char *)p.in < (const char *)cv->buf ||
-                      (const char *)p.in + sizeof(float2) * p.n_in > (const char *)cv->buf + cv->cap))
-                why = "converted CS16 / CS8 / CF16 packet outside the conversion scratch";
-        }
-        if (why) {
-            char buf[200];
-            std::snprintf(buf, sizeof buf, "psk_soft_process: plan of channel %u fails validation: %s", ch0 + bad, why);
-            return fail(PSK_SOFT_ERR_LIMIT, buf);
-        }
-    }
-    // window classes of the call in launch order (deepest history first); class 0 stays on the caller's stream, the others take
-    // the side streams in turn
-    struct Cls {
-        int S, H;
-    };
-    Cls cls[33 * kNumClassH];
-    int n_cls = 0;
-    for (int k = kNumClassH - 1; k >= 0; k--)
-        for (int S : kFastS)
-            if (need_SH[S][kClassH[k]])
-                cls[n_cls++] = Cls{S, kClassH[k]};
-    const bool fork = n_cls > 1 && h->opt_fork;
-    // deferred join (see psk_soft_handle::opt_deferred): only calls whose every channel runs on wave-scan launches
-    // (nor calls with CS16 packets: the conversion scratch is one per stream, and the next call's pre-pass must not overwrite it
-    // under the side streams of this one)
-    bool deferred = fork && (h->opt_deferred || g_split_mode) && (!cont || g_split_mode) && !tile_syms && !res.cnt_any && !res.any_seq &&
-                    !n_cvt && !n_wide_seq;
-    if (fork && !cont && !h->opt_deferred && h->opt_split > 1 && !tile_syms && !res.cnt_any && !res.any_seq && !n_cvt && !n_wide_seq) {
-        // Classes that cannot be resident together (a SIMD's registers hold four waves of the short windows or two of the long
-        // ones) take two rounds of waves, and a wave that starts late still needs the whole call's time at the lone-wave rate.
-        // Cut in time, the pieces of the short class that start late are short too, and the class runs its last pieces with the
-        // machine to itself: configs[4] 3.4 -> 2.6 ms for ONE joined call.  The pieces are continuations of the one
-        // serviceFunction() call (plan_call's `cont`), the bounds that count the reference's rounding since the call began carry
-        // over (PLAN_CARRY_DRIFT).  Nothing is committed or enqueued here: the caller plans the pieces.
-        uint32_t listed = res.cnt_quiet, longest = 0;
-        for (int i = 0; i < n_cls; i++) {
-            listed += res.cnt_SH[cls[i].S][cls[i].H];
-            longest = res.max_blocks_SH[cls[i].S][cls[i].H] > longest ? res.max_blocks_SH[cls[i].S][cls[i].H] : longest;
-        }
-        static const uint32_t min_blocks = [] {  // (PSK_SOFT_SPLIT_MIN_BLOCKS: tests cut short calls too)
-            const char *e = std::getenv("PSK_SOFT_SPLIT_MIN_BLOCKS");
-            return e && std::atoi(e) > 0 ? (uint32_t)std::atoi(e) : kSplitMinBlocks;
-        }();
-        if (listed == nch && longest >= min_blocks) {
-            g_split_pieces = h->opt_split;
-            return PSK_SOFT_OK;
-        }
-    }
-    uint64_t sig = 1469598103934665603ull;
-    if (deferred) {
-        auto mix = [&](uint64_t v) { sig = (sig ^ v) * 1099511628211ull; };
-        mix(ch0), mix(nch), mix((uint64_t)(uintptr_t)stream), mix((uint64_t)n_cls), mix(res.cnt_quiet);
-        for (int i = 0; i < n_cls; i++) mix(((uint64_t)cls[i].S << 40) | ((uint64_t)cls[i].H << 32) | res.cnt_SH[cls[i].S][cls[i].H]);
-        for (uint32_t i = 0; i < nch; i++) mix(h_list[i]);  // (no planned SKIP / SEQ channels here: the lists hold all nch)
-        uint32_t listed = res.cnt_quiet;
-        for (int i = 0; i < n_cls; i++) listed += res.cnt_SH[cls[i].S][cls[i].H];
-        if (listed != nch)  // (channels without a packet this call: they belong to no stream -- the joined way)
-            deferred = false;
-    }
-    if (h->deferred_pending && !(deferred && sig == h->deferred_sig)) {
-        // a channel may be about to change streams: everything the side streams carry first
-        // (its own earlier calls on another stream: the range logic above has made this stream wait for them and their side streams)
-        PSK_HIP(deferred_join(h, stream));
-    }
-    {
-        uint32_t *hdr = psk::plan_header(h->h_plans[slot]);
-        hdr[0] = 0u;                       // channels handed over: counted by the kernels
-        hdr[1] = res.any_seq ? 1u : 0u;    // channels planned for the reference-order kernel
-    }
-    const size_t up_bytes = (n_in_place || n_wide_seq) ? slot_seq_offset(nch) + sizeof(uint32_t) * nch
-                            : n_cvt    ? slot_cvt_offset(nch) + sizeof(psk::CvtDesc) * n_cvt
-                                       : psk::kPlanHeaderBytes + (sizeof(psk::ChanPlan) + sizeof(uint32_t)) * nch;
-    if (h->opt_up_stream) {
-        // (the slot's previous user has finished -- waited for above --, nothing else reads or writes d_plans[slot])
-        PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[slot]), psk::plan_header(h->h_plans[slot]), up_bytes,
-                               hipMemcpyHostToDevice, h->up_stream));
-        PSK_HIP(hipEventRecord(h->ev_up[slot], h->up_stream));
-        PSK_HIP(hipStreamWaitEvent(stream, h->ev_up[slot], 0));
-    } else {
-        PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[slot]), psk::plan_header(h->h_plans[slot]), up_bytes,
-                               hipMemcpyHostToDevice, stream));
-    }
-    // phase ring of a launch: a power of two >= phaseAvg + 128 for its channels, at least 512 floats (256 where
-    // the energy ring is dynamic too and every byte of LDS counts towards residency)
-    auto ring_floats = [](uint32_t n_max, uint32_t at_least) {
-        uint32_t y = at_least;
-        while (y < n_max + 128u) y <<= 1;
-        return y;
-    };
-    // PSK_SOFT_TRACE_LAUNCHES=1 (debugging a faulting kernel): in front of every launch the host waits for everything enqueued so
-    // far and writes one line for the launch and one per channel of its list to stderr -- the last launch named in the log of a
-    // run that died is the one that did it, with the shapes it was given.  (=2: the launch lines only.)  stream= is the stream the
-    // launch goes to (mark_st): the caller's, or the side stream of the launch's class.
-    hipStream_t mark_st = stream;
-    auto mark = [&](const char *what, int S, int H, uint32_t off, uint32_t cnt, uint32_t tiles, uint32_t y_len, uint32_t r_len) -> hipError_t {
-        if (!h->opt_trace)
-            return hipSuccess;
-        if (const hipError_t e = hipDeviceSynchronize())
-            return e;
-        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%u y_len=%u r_len=%u slot=%d stream=%p\n", what, S, H, ch0, cnt,
-                     tiles, y_len, r_len, slot, (void *)mark_st);
-        for (uint32_t i = 0; i < cnt && h->opt_trace == 1; i++) {
-            const uint32_t bi = stamped || off == ~0u ? i : h_list[off + i];
-            const psk::ChanPlan &p = plans[bi];
-            if (off == ~0u && p.mode == psk::PLAN_SKIP)
-                continue;
-            std::fprintf(stderr, "[psk_soft]   ch %u mode=%u S=%u A=%u M=%u n=%u len0=%u n_out=%llu n_in=%llu L0=%u L1=%u flags=0x%x K=%u tbase=%u toff=%llu in=%p\n",
-                         ch0 + bi, p.mode, p.S, p.A, p.M, p.lf_n, p.lf_len0, (unsigned long long)p.n_out, (unsigned long long)p.n_in, p.ring_len0,
-                         p.ring_len1, p.lf_flags, p.tile_blocks, p.tile_base, (unsigned long long)p.tile_off, (const void *)p.in);
-        }
-        std::fflush(stderr);
-        return hipSuccess;
-    };
-    // (timing experiments only -- PSK_SOFT_DIAG_NO_TAIL=1: the exact-timing and reference-order launches behind the screened tier are
-    // left out, which is wrong as soon as a call is handed over; what the two launches cost a small call is measured that way)
-    static const bool diag_no_tail = std::getenv("PSK_SOFT_DIAG_NO_TAIL") && std::atoi(std::getenv("PSK_SOFT_DIAG_NO_TAIL")) != 0;
-    auto enqueue = [&]() -> psk_soft_status {
-        const psk::CvtDesc *d_desc =
-            reinterpret_cast<const psk::CvtDesc *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) + slot_cvt_offset(nch));
-        for (int f = 0; f < psk::kNumPktFormats; d_desc += n_cvt_f[f], f++) {
-            if (!n_cvt_f[f])
-                continue;
-            PSK_HIP(mark(psk::kPktFormats[f].convert, 0, 0, ~0u, 0, n_cvt_f[f], 0, 0));
-            PSK_HIP(psk::launch_convert((int)psk::kPktFormats[f].id, d_desc, n_cvt_f[f], cvt_max_n[f], stream));
-        }
-        if (any_quiet)
-            PSK_HIP(mark("fast<0,1> (calls that emit nothing)", 0, 1, off_quiet, res.cnt_quiet, 0, ring_floats(res.max_n_quiet, 512u), 0));
-        if (any_quiet)
-            PSK_HIP(psk::launch_fast(0, 1, 0, h->d_plans[slot], d_list + off_quiet, ch0, res.cnt_quiet, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                     h->lim.fit_cap, ring_floats(res.max_n_quiet, 512u), 0u, stream));
-        // Per window class (samplesPerBaud, history depth): screened timing first, then the exact-timing
-        // instantiation, which picks up the calls the screening refused; the reference-order kernel (below) takes
-        // the calls both refused.  A batch that mixes classes runs them SIDE BY SIDE: each class is its own
-        // instantiation with its own register and LDS appetite (numAvg <= 128: 16 waves per CU; numAvg 400: 8), and
-        // one after the other each would leave part of the machine idle.  The classes go to side streams forked off
-        // the caller's stream behind the plan upload and joined again in front of the reference-order kernel; the
-        // deepest histories (fewest waves per CU, longest tails) are launched first.
-        if (res.cnt_any) {
-            const uint32_t y_len = ring_floats(res.max_n_any, 512u);
-            PSK_HIP(mark("tile_front_any", (int)res.max_S_any, 0, off_any, res.cnt_any, tiles_max_any, y_len, 0));
-            PSK_HIP(psk::launch_tile_front_any(h->d_plans[slot], d_list + off_any, ch0, res.cnt_any, tiles_max_any, res.max_S_any, h->d_state, h->d_ring,
-                                               h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, stream));
-            if (h->opt_pfit)
-                PSK_HIP(mark("pfit (any)", (int)res.max_S_any, 0, off_any, res.cnt_any, tiles_max_any, y_len, pf_second));
-            if (h->opt_pfit)
-                PSK_HIP(psk::launch_pfit(h->d_plans[slot], d_list + off_any, ch0, res.cnt_any, tiles_max_any, h->d_state, h->d_ring,
-                                         h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf,
-                                         pf_second, stream));
-            PSK_HIP(mark("tile_fit (any)", (int)res.max_S_any, 0, off_any, res.cnt_any, tiles_max_any, y_len, 0));
-            PSK_HIP(psk::launch_tile_fit(h->d_plans[slot], d_list + off_any, ch0, res.cnt_any, h->d_state, h->d_ring, h->lim.ring_cap,
-                                         h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf, stream));
-            PSK_HIP(mark("tile_back (any)", (int)res.max_S_any, 0, off_any, res.cnt_any, tiles_max_any, y_len, 0));
-            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_any, ch0, res.cnt_any, tiles_max_any, h->d_state, h->d_tiles,
-                                          h->d_ts, h->d_test, 0u, 0u, stream));
-        }
-        if (res.cnt_wide) {  // (wide symbols: the chunk and pick launches of psk_wide.hip in place of the front stage above)
-            const uint32_t y_len = ring_floats(res.max_n_wide, 512u);
-            PSK_HIP(mark("wide_front (chunk, pick)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, wide_z));
-            PSK_HIP(psk::launch_wide_front(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, res.max_S_wide, h->d_ring,
-                                           h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, h->d_wide_rec, h->d_wide_stat, stream));
-            if (h->opt_pfit)
-                PSK_HIP(mark("pfit (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, pf_second));
-            if (h->opt_pfit)
-                PSK_HIP(psk::launch_pfit(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, h->d_state, h->d_ring,
-                                         h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf,
-                                         pf_second, stream));
-            PSK_HIP(mark("tile_fit (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, 0));
-            PSK_HIP(psk::launch_tile_fit(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, h->d_state, h->d_ring, h->lim.ring_cap,
-                                         h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test, h->pf, stream));
-            PSK_HIP(mark("tile_back (wide)", (int)res.max_S_wide, 0, off_wide, res.cnt_wide, tiles_max_wide, y_len, 0));
-            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_wide, ch0, res.cnt_wide, tiles_max_wide, h->d_state, h->d_tiles,
-                                          h->d_ts, h->d_test, 0u, 0u, stream));
-        }
-        if (res.cnt_quietf) {
-            PSK_HIP(mark("far_quiet (calls that emit nothing)", 0, 0, off_quietf, res.cnt_quietf, 0, 0, 0));
-            PSK_HIP(psk::launch_far_quiet(h->d_plans[slot], d_list + off_quietf, ch0, res.cnt_quietf, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                          h->lim.fit_cap, h->d_far_y, h->far_rows_cap, stream));
-        }
-        // the far fit's two launch sets: the same front and back stages around the fit stage with its rings in device memory
-        if (res.anyf.cnt) {
-            PSK_HIP(mark("tile_front_any (far)", (int)res.anyf.max_S, 0, off_anyf, res.anyf.cnt, tiles_max_anyf, 0, 0));
-            PSK_HIP(psk::launch_tile_front_any(h->d_plans[slot], d_list + off_anyf, ch0, res.anyf.cnt, tiles_max_anyf, res.anyf.max_S, h->d_state,
-                                               h->d_ring, h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, stream));
-            PSK_HIP(mark("far_fit (any)", (int)res.anyf.max_S, 0, off_anyf, res.anyf.cnt, tiles_max_anyf, 0, 0));
-            PSK_HIP(psk::launch_far_fit(h->d_plans[slot], d_list + off_anyf, ch0, res.anyf.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                        h->lim.fit_cap, h->d_far_y, h->far_rows_cap, h->d_tiles, h->d_traw, h->d_ts, h->d_test, stream));
-            PSK_HIP(mark("tile_back (any, far)", (int)res.anyf.max_S, 0, off_anyf, res.anyf.cnt, tiles_max_anyf, 0, 0));
-            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_anyf, ch0, res.anyf.cnt, tiles_max_anyf, h->d_state, h->d_tiles,
-                                          h->d_ts, h->d_test, 0u, 0u, stream));
-        }
-        if (res.widef.cnt) {
-            PSK_HIP(mark("wide_front (chunk, pick; far)", (int)res.widef.max_S, 0, off_widef, res.widef.cnt, tiles_max_widef, 0, wide_z));
-            PSK_HIP(psk::launch_wide_front(h->d_plans[slot], d_list + off_widef, ch0, res.widef.cnt, tiles_max_widef, res.widef.max_S, h->d_ring,
-                                           h->lim.ring_cap, h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, h->d_wide_rec, h->d_wide_stat, stream));
-            PSK_HIP(mark("far_fit (wide)", (int)res.widef.max_S, 0, off_widef, res.widef.cnt, tiles_max_widef, 0, 0));
-            PSK_HIP(psk::launch_far_fit(h->d_plans[slot], d_list + off_widef, ch0, res.widef.cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                        h->lim.fit_cap, h->d_far_y, h->far_rows_cap, h->d_tiles, h->d_traw, h->d_ts, h->d_test, stream));
-            PSK_HIP(mark("tile_back (wide, far)", (int)res.widef.max_S, 0, off_widef, res.widef.cnt, tiles_max_widef, 0, 0));
-            PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_widef, ch0, res.widef.cnt, tiles_max_widef, h->d_state, h->d_tiles,
-                                          h->d_ts, h->d_test, 0u, 0u, stream));
-        }
-        if (any_quiet && deferred)  // (every launch set ends its own calls: the quiet channels' on the caller's stream)
-            PSK_HIP(psk::launch_seq(h->d_plans[slot], d_list + off_quiet, ch0, res.cnt_quiet, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                    h->lim.fit_cap, stream));
-        if (fork) {
-            if (!h->aux_fork) {
-                PSK_HIP(hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming));
-                // (streams of one priority share a few hardware queues -- four unless GPU_MAX_HW_QUEUES says otherwise -- and two
-                // streams that land on the same one run their kernels one after the other: measured, the classes of the mixed
-                // batch did, 1.75 + 1.78 ms.  A stream of another priority gets a queue of its own.)
-                int prio_lo = 0, prio_hi = 0;
-                PSK_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-                for (int k = 0; k < kAuxStreams; k++) {
-                    const char *pe = getenv("PSK_SOFT_AUX_PRIO");
-                    const int mode = pe ? atoi(pe) : 1;
-                    if (mode == 0 || prio_lo == prio_hi)
-                        PSK_HIP(hipStreamCreateWithFlags(&h->aux[k], hipStreamNonBlocking));
-                    else
-                        PSK_HIP(hipStreamCreateWithPriority(&h->aux[k], hipStreamNonBlocking, mode == 1 ? prio_hi : prio_lo));
-                    PSK_HIP(hipEventCreateWithFlags(&h->aux_join[k], hipEventDisableTiming));
-                }
-            }
-            PSK_HIP(hipEventRecord(h->aux_fork, stream));
-        }
-        int used_aux = 0;
-        for (int i = 0; i < n_cls; i++) {
-            const int S = cls[i].S, H = cls[i].H;
-            // class 0 stays on the caller's stream, the others take the side streams in turn
-            hipStream_t st = stream;
-            if (fork && i > 0) {
-                const int a = (i - 1) % kAuxStreams;
-                st = h->aux[a];
-                if (i - 1 < kAuxStreams) {
-                    PSK_HIP(hipStreamWaitEvent(st, h->aux_fork, 0));
-                    used_aux = i;
-                }
-            }
-            mark_st = st;
-            const uint32_t y_len = ring_floats(max_n[S][H], psk::ering_dynamic(S) ? 256u : 512u);
-            const uint32_t r_len = class_H(H) == 1 ? ((max_A[S][H] + 128u + 1u) & ~1u) : 0u;
-            if (tiled_SH[S][H] && piped_SH[S][H]) {
-                // pipelined: front(range j) here, fit(range j) on a second stream behind it -- under front(range j + 1) --,
-                // back(range j) on a third behind that (psk_tile.hip: psk_tile_fit_range_kernel)
-                const uint32_t cnt = res.cnt_SH[S][H], T = tiles_max_SH[S][H], tr = pipe_tiles_SH[S][H];
-                const uint32_t *const l = d_list + off_SH[S][H];
-                char *const carry = static_cast<char *>(h->d_pipe_carry) + psk::pipe_carry_bytes() * off_SH[S][H];
-                float *const carry_y = h->d_pipe_y + (size_t)kPipeMaxYLen * off_SH[S][H];
-                const uint32_t y_pipe = ring_floats(max_n[S][H], 512u);
-                int e = 0;
-                PSK_HIP(hipEventRecord(h->pipe_ev[e], st));  // (the side streams start behind everything this one carries)
-                PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
-                PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
-                e++;
-                for (uint32_t t0 = 0; t0 < T; t0 += tr) {
-                    const uint32_t nt = T - t0 < tr ? T - t0 : tr;
-                    mark_st = st;
-                    PSK_HIP(mark("pipe_front", S, H, off_SH[S][H], cnt, nt, y_len, r_len));
-                    PSK_HIP(psk::launch_tile_front(S, class_H(H), h->d_plans[slot], l, ch0, cnt, nt, h->d_state, h->d_ring, h->lim.ring_cap, r_len,
-                                                   h->d_tiles, h->d_traw, h->d_ts, h->pf.chan, t0, st));
-                    PSK_HIP(hipEventRecord(h->pipe_ev[e], st));
-                    PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
-                    e++;
-                    mark_st = h->pipe_st[0];
-                    PSK_HIP(mark("pipe_fit", S, H, off_SH[S][H], cnt, nt, y_pipe, 0));
-                    PSK_HIP(psk::launch_tile_fit_range(h->d_plans[slot], l, ch0, cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                                       h->lim.fit_cap, y_pipe, h->d_tiles, h->d_traw, h->d_ts, h->d_test, carry, carry_y, t0, nt,
-                                                       h->pipe_st[0]));
-                    PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[0]));
-                    PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
-                    e++;
-                    mark_st = h->pipe_st[1];
-                    PSK_HIP(mark("pipe_back", S, H, off_SH[S][H], cnt, nt, y_pipe, 0));
-                    PSK_HIP(psk::launch_tile_back(h->d_plans[slot], l, ch0, cnt, nt, h->d_state, h->d_tiles, h->d_ts, h->d_test, t0, 1u,
-                                                  h->pipe_st[1]));
-                }
-                PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[1]));  // (behind the last fit too: the last back waited for it)
-                PSK_HIP(hipStreamWaitEvent(st, h->pipe_ev[e], 0));
-                mark_st = st;
-            } else if (tiled_SH[S][H]) {
-                // (a call these cannot carry comes out with guard 1 and nothing committed: the launches below redo it)
-                PSK_HIP(mark("tile_front", S, H, off_SH[S][H], res.cnt_SH[S][H], tiles_max_SH[S][H], y_len, r_len));
-                PSK_HIP(psk::launch_tile_front(S, class_H(H), h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], tiles_max_SH[S][H],
-                                               h->d_state, h->d_ring, h->lim.ring_cap, r_len, h->d_tiles, h->d_traw, h->d_ts,
-                                               h->pf.chan, 0u, st));
-                if (h->opt_pfit)
-                    PSK_HIP(mark("pfit", S, H, off_SH[S][H], res.cnt_SH[S][H], tiles_max_SH[S][H], y_len, pf_second));
-                if (h->opt_pfit)
-                    PSK_HIP(psk::launch_pfit(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], tiles_max_SH[S][H], h->d_state,
-                                             h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts,
-                                             h->d_test, h->pf, pf_second, st));
-                PSK_HIP(mark("tile_fit", S, H, off_SH[S][H], res.cnt_SH[S][H], tiles_max_SH[S][H], y_len, r_len));
-                PSK_HIP(psk::launch_tile_fit(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring,
-                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, h->d_tiles, h->d_traw, h->d_ts, h->d_test,
-                                             h->pf, st));
-                PSK_HIP(mark("tile_back", S, H, off_SH[S][H], res.cnt_SH[S][H], tiles_max_SH[S][H], y_len, r_len));
-                PSK_HIP(psk::launch_tile_back(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], tiles_max_SH[S][H], h->d_state,
-                                              h->d_tiles, h->d_ts, h->d_test, 0u, 0u, st));
-            }
-            // (the exact tier only works on the calls the tier in front of it left; behind the time-tiled kernels, whose front
-            // stage IS the screened timing, it is the exact tier that picks up what they hand over)
-            for (int exact = tiled_SH[S][H] ? 1 : 0; exact <= 1; exact++) {
-                if (exact && diag_no_tail)
-                    break;
-                PSK_HIP(mark(exact ? "fast (exact tier)" : "fast (screened tier)", S, H, off_SH[S][H], res.cnt_SH[S][H], 0, y_len, r_len));
-                if (const psk::PktFormat *const f = class_pkt(H))
-                    PSK_HIP(psk::launch_fast_pkt((int)f->id, S, exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
-                                                 h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
-                else
-                    PSK_HIP(psk::launch_fast(S, class_H(H), exact, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
-                                             h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_len, r_len, st));
-            }
-            if (deferred && class_pkt(H))  // (the class's hand-overs are redone on its own stream, in front of its next call)
-                PSK_HIP(psk::launch_seq_pkt((int)class_pkt(H)->id, h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state,
-                                            h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, st));
-            else if (deferred)
-                PSK_HIP(psk::launch_seq(h->d_plans[slot], d_list + off_SH[S][H], ch0, res.cnt_SH[S][H], h->d_state, h->d_ring, h->lim.ring_cap,
-                                        h->d_yv, h->lim.fit_cap, st));
-        }
-        mark_st = stream;
-        if (deferred) {
-            for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
-                if (!h->slot_aux_ev[slot][a])
-                    PSK_HIP(hipEventCreateWithFlags(&h->slot_aux_ev[slot][a], hipEventDisableTiming));
-                PSK_HIP(hipEventRecord(h->slot_aux_ev[slot][a], h->aux[a]));
-                h->slot_aux_used[slot][a] = true;
-            }
-            h->deferred_pending = true;
-            h->deferred_sig = sig;
-            h->deferred_stream = stream;
-        } else {
-            for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
-                PSK_HIP(hipEventRecord(h->aux_join[a], h->aux[a]));
-                PSK_HIP(hipStreamWaitEvent(stream, h->aux_join[a], 0));
-            }
-            if (any_seq || any_emit)
-                PSK_HIP(mark("seq (reference order)", 0, 0, ~0u, nch, 0, 0, 0));
-            if ((any_seq || any_emit) && !diag_no_tail && !n_in_place && !n_wide_seq)  // any_emit: the exactness guard may hand calls over at run time
-                PSK_HIP(psk::launch_seq(h->d_plans[slot], nullptr, ch0, nch, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                        h->lim.fit_cap, stream));
-            if ((any_seq || any_emit) && !diag_no_tail && (n_in_place || n_wide_seq)) {  // (CS16 / CS8 / CF16 read in place, wide symbols: each build on its own channels)
-                const uint32_t *const d_seq = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(psk::plan_header(h->d_plans[slot])) +
-                                                                                 slot_seq_offset(nch));
-                PSK_HIP(psk::launch_seq(h->d_plans[slot], d_seq, ch0, n_seq_narrow, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv,
-                                        h->lim.fit_cap, stream));
-                const uint32_t *d_seq_f = d_seq + n_seq_narrow;
-                for (int f = 0; f < psk::kNumPktFormats; d_seq_f += n_in_place_f[f], f++)
-                    PSK_HIP(psk::launch_seq_pkt((int)psk::kPktFormats[f].id, h->d_plans[slot], d_seq_f, ch0, n_in_place_f[f], h->d_state,
-                                                h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, stream));
-                if (n_wide_seq)
-                    PSK_HIP(mark("seq_wide (reference order, samplesPerBaud > 1024)", (int)wide_seq_S, 0, ~0u, 0, 0, 0, 0));
-                PSK_HIP(psk::launch_seq_wide(h->d_plans[slot], d_seq + (nch - n_wide_seq), ch0, n_wide_seq, h->d_state, h->d_ring,
-                                             h->lim.ring_cap, h->d_yv, h->lim.fit_cap, h->d_wide_symE, wide_seq_S, stream));
-            }
-        }
-        if (tile_syms || n_wide_seq)
-            PSK_HIP(hipEventRecord(h->tile_ev, stream));
-        if (n_cvt) {
-            PSK_HIP(hipEventRecord(cv->ev, stream));
-            cv->ev_used = true;
-        }
-        PSK_HIP(hipEventRecord(h->ev[slot], stream));
-        return PSK_SOFT_OK;
-    };
-    const psk_soft_status est = enqueue();
-    if (est != PSK_SOFT_OK) {
-        h->poisoned = true;
-        return est;
-    }
-    commit();
-    if (tile_syms || n_wide_seq) {
-        h->tile_ev_used = true;
-        h->tile_stream = stream;
-    }
-    h->slot = (h->slot + 1) % kPlanSlots;
-    h->ev_used[slot] = true;
-    h->slot_stream[slot] = stream;
-    h->slot_ch0[slot] = ch0;
-    h->slot_nch[slot] = nch;
-    return PSK_SOFT_OK;
 }
 
 // The call behind the public entry (psk_soft_process_device, below).  A call that would emit more than 2^20 symbols in one channel, or run LinearFit::count past 2^20 in the
