@@ -396,6 +396,84 @@ uint64_t psk_soft_quality_bytes(void);      /* sizeof(psk_soft_quality_t), for b
 psk_soft_status psk_soft_get_quality(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_quality_t *q /* [nch] */);
 psk_soft_status psk_soft_quality_derive(const psk_soft_quality_t *q, psk_soft_quality_derived_t *d);  /* host only, pure */
 
+/* ---- carrier offset of a packet (psk_soft_acquire_device) ---------------------------------------------------------------------
+ * psk_soft_process_device_tuned takes a carrier offset out; this call finds it.  The tracker of serviceFunction() sees the carrier
+ * once per symbol, behind the M-th power: offsets of f and of f + 1/M cycles per SYMBOL look the same to it (and to `lock`), so no
+ * search over `step` that watches `lock` can tell them apart.  The samples can: in front of the timing pick there are
+ * samplesPerBaud of them per symbol, and the lag products below are unambiguous for |f| < 1/(2M) cycles per SAMPLE, which is
+ * samplesPerBaud/(2M) cycles per symbol -- samplesPerBaud/2 times the tracker's range of 1/M cycles per symbol.
+ *
+ * The call looks at one packet per channel and leaves one record per channel.  It emits no symbols and touches no demodulator
+ * state: psk_soft_peek, psk_soft_query, the state blob, warning counts, statistics, quality records and the results of every
+ * later process call are what they are without it.  It ignores sriChanged and inputQueueFlushed.
+ *
+ * The definition.  Lags are L_j = 2^j, j = 0 .. 7 (1, 2, 4 .. 128).  M is the channel's stored constelationSize, the value the
+ * next process call would snapshot.
+ * Samples: the samples of the packet are converted exactly, as its format defines; if tune[i] is given and not {0, 0} they are
+ *   multiplied by the NCO exactly as "tuned packets" (above) defines, bit for bit.  Call the result (re, im) of sample k.
+ * Per sample, every operation float32, rounded once, no fused multiply-add, denormals kept (the terms of the lock sum of the
+ *   quality record):
+ *     e = re*re + im*im,  q = e*e
+ *     (pr, pi) = (re, im), then log2(M) times (pr, pi) <- (pr*pr - pi*pi, pr*pi + pi*pr)
+ *     a = e for M = 2, q for 4, q*q for 8
+ *   Sample k is VALID when re, im, q, pr, pi and a are finite and a >= FLT_MIN.  For a valid sample u_k = (pr / a, pi / a), the
+ *   division correctly rounded.  sum_e is the sum of (double)e over the valid samples, n_valid their count.
+ * Per lag j, for every k >= L_j with k and k - L_j both valid (L = L_j):
+ *     t_re = ur_k*ur_{k-L} + ui_k*ui_{k-L},   t_im = ui_k*ur_{k-L} - ur_k*ui_{k-L}        (float32)
+ *     sum_re[j] += (double)t_re,  sum_im[j] += (double)t_im,  n_pairs[j]++
+ * Order of the additions: the doubles are added in an order fixed by the code, a function of the packet's length only -- not of
+ *   the batch, the grid, the stride, the format or the stream: the same samples give the same bytes whether the packet stands alone
+ *   or among 4095 others.  No floating-point atomics.  (psk_soft_acquire_host adds in index order: its sums agree with the
+ *   device's within n * 2^-53 * sum|t|, not bit for bit.) */
+enum { PSK_SOFT_A_DATA = 1, PSK_SOFT_A_TUNED = 2, PSK_SOFT_A_PLANNED = 128 };
+
+typedef struct psk_soft_acquire {        /* the LAST psk_soft_acquire_device call that covered the channel */
+    uint64_t n_samples, n_valid;         /* complex samples of the packet; of those, valid ones            */
+    uint64_t n_pairs[8];                 /* per lag: pairs that entered the sums                           */
+    double sum_re[8], sum_im[8];         /* per lag: sums of t_re, t_im                                    */
+    double sum_e;                        /* sum of e over the valid samples                                */
+    uint16_t constelationSize; uint8_t flags; uint8_t pad[5];   /* PSK_SOFT_A_*; pad zero                  */
+} psk_soft_acquire_t;                    /* 224 bytes */
+
+/* psk_soft_acquire_derive (doubles; C atan2, hypot, rint), with c_j = |(sum_re[j], sum_im[j])| / n_pairs[j]:
+ *   all three doubles NaN and lags_used 0 without PSK_SOFT_A_DATA, with n_pairs[0] == 0 or with both lag-1 sums zero.  Else
+ *   f = atan2(sum_im[0], sum_re[0]) / (2 pi M), lags_used = 1; then for j = 1 .. 7, stopping at the first j with n_pairs[j] == 0
+ *   or c_j < 0.5 * c_0 (a carrier that decorrelates over long lags is not trusted there; the factor is part of the definition):
+ *     d = atan2(sum_im[j], sum_re[j]) - 2 pi M L_j f,  d -= 2 pi rint(d / (2 pi)),  f += d / (2 pi M L_j),  lags_used++
+ *   offset_cycles_per_sample = f, coherence = c_0, mean_energy = sum_e / n_valid.
+ * coherence is of the order of n^-1/2 for noise and near 1 for a clean PSK signal; where to put the threshold is the host's choice.
+ * Sign: the signal's phase advances by f cycles per sample; take it out with tune.step += psk_soft_tune_step(-f).  If the look was
+ * itself tuned, f is the residual under that tune.  Unambiguous for |f| < 1/(2M) cycles per sample (see the top of the section). */
+typedef struct psk_soft_acquire_derived { double offset_cycles_per_sample, coherence, mean_energy; int32_t lags_used; int32_t pad; } psk_soft_acquire_derived_t;
+
+/* Packets, strides and tunes as for psk_soft_process_device_tuned (DEVICE pointers; enqueued on `stream`, returns without
+ * waiting).  Refused with PSK_SOFT_ERR_INVALID_ARG before anything is enqueued or any record changes: a bad channel range, and on
+ * a present packet a stride of 0, an extent stride x bytes-per-sample x samples that does not fit 64 bits, an unknown format, or
+ * `data` that is missing or not aligned to a whole sample when the packet holds samples the call would read.
+ * A covered channel gets a DATA record (PSK_SOFT_A_DATA, and PSK_SOFT_A_TUNED if it was tuned) when its packet is present, has
+ * sri_mode == 1 and at least one sample, and constelationSize is 2, 4 or 8; every other covered channel gets an all-zero
+ * record, written in stream order; a channel the call does not cover keeps its record.
+ * How: two launches on `stream`, a fold over pieces of a fixed number of samples and a join per packet.  Strided packets in a
+ * run the tiled transpose takes (at least 8 adjacent columns of one matrix, as for psk_soft_process_device_strided) are first
+ * gathered, by that entry's gather launches on `stream`, into rows of their own format in the handle's gather scratch, and the
+ * fold reads the rows; the scratch, its events and the rule of PSK_SOFT_OPT_DEFERRED_JOIN are that entry's: a look that gathers
+ * JOINS the handle's side streams into `stream` first.  Any other strided packet is read where it lies, at its stride: every
+ * load a memory line of its own -- correct, and slow for long looks; keep a matrix's channels consecutive in the call.  Nothing
+ * else is launched.  A control-plane-only handle checks the arguments, then fills in n_samples, constelationSize and
+ * flags = PSK_SOFT_A_PLANNED for the packets that would give a data record, everything else zero. */
+psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts /* [nch] */,
+                                        const uint64_t *sample_stride /* [nch], or NULL */, const psk_soft_tune_t *tune /* [nch], or NULL */,
+                                        void *stream);
+/* waits like psk_soft_get_quality does and copies the records of [ch0, ch0+nch) out */
+psk_soft_status psk_soft_get_acquire(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_acquire_t *rec /* [nch] */);
+psk_soft_status psk_soft_acquire_derive(const psk_soft_acquire_t *rec, psk_soft_acquire_derived_t *d);   /* host only, pure */
+/* host only, pure: the definition for n_complex CF32 samples (tune NULL or {0, 0}: untuned), the sums added in index order;
+ * PSK_SOFT_ERR_INVALID_ARG for a constelationSize other than 2, 4, 8 */
+psk_soft_status psk_soft_acquire_host(uint16_t constelationSize, const psk_soft_tune_t *tune /* or NULL */,
+                                      const float *in, uint64_t n_complex, psk_soft_acquire_t *rec);
+uint64_t psk_soft_acquire_bytes(void);      /* sizeof(psk_soft_acquire_t), for bindings */
+uint32_t psk_soft_acquire_piece(void);      /* samples of one piece of the device's fold (tests: the lengths at its edges) */
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

@@ -21,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "psk_acquire.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -111,6 +112,7 @@ constexpr int kPlanSlots = 4;
 constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that mixes window classes (see psk_soft_process_device)
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
 constexpr int kQualitySlots = 4;  // calls whose quality pass (PSK_SOFT_OPT_QUALITY) may be in flight: descriptors and partials of each
+constexpr int kAcquireSlots = 4;  // psk_soft_acquire_device calls that may be in flight: descriptors and partials of each
 constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 / CF16 packets, one per stream that uses them (see CvtScratch)
 constexpr int kGatherScratch = 4;  // gather scratch buffers of strided packets, one per stream that uses them (see GatherScratch)
 constexpr int kGatherDescSlots = 4;  // strided calls whose gather descriptors may be in flight
@@ -313,6 +315,18 @@ struct QualitySlot {
     uint32_t ch0 = 0, nch = 0;
 };
 
+// psk_soft_acquire_device: what one call owns until its event, as QualitySlot -- the descriptors (pinned, and their copy in device
+// memory: one per channel of the handle) and the partials of the fold (grown on demand)
+struct AcquireSlot {
+    psk::AcquireDesc *h_desc = nullptr, *d_desc = nullptr;
+    psk::AcquirePartial *d_part = nullptr;
+    size_t part_cap = 0;  // partials
+    hipEvent_t ev = nullptr;
+    bool used = false;
+    hipStream_t stream = nullptr;
+    uint32_t ch0 = 0, nch = 0;
+};
+
 // Largest phaseAvg of the wave-scan kernels: their LDS ring of unwrapped phases holds phaseAvg + 128 values in a power
 // of two; 32768 floats (128 KiB) leave room for the energy ring next to it.  Channels with phaseAvg > kDeepFit are
 // launched apart from the others of their window class ("deep" classes, index H + 8): a ring that size allows one wave
@@ -484,6 +498,12 @@ struct psk_soft_handle {
         uint8_t diff;
     };
     std::vector<QualitySnap> q_snap;  // scratch of one call: the properties it ran with
+    // psk_soft_acquire_device: one record per channel, written by the join of the last call that covered it (psk_acquire.hip); a
+    // control-plane-only handle keeps them on the host
+    psk_soft_acquire_t *d_acquire = nullptr;
+    std::vector<psk_soft_acquire_t> acquire_dry;
+    AcquireSlot aslot[kAcquireSlots];
+    int a_turn = 0;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -1829,8 +1849,10 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
     h->last_mode.assign(n_channels, psk::PLAN_SKIP);
     h->device = device;
     h->dry = (device == PSK_SOFT_DEVICE_NONE);
-    if (h->dry)
+    if (h->dry) {
         h->quality_dry.assign(n_channels, psk_soft_quality_t{});
+        h->acquire_dry.assign(n_channels, psk_soft_acquire_t{});
+    }
     if (const char *e = std::getenv("PSK_SOFT_TIME_TILED"))
         h->opt_tiled = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
     if (const char *e = std::getenv("PSK_SOFT_FAR_FIT"))  // (as psk_soft_set_option(PSK_SOFT_OPT_FAR_FIT))
@@ -1899,6 +1921,9 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
         if ((e2 = hipMalloc((void **)&h->d_quality, sizeof(psk_soft_quality_t) * (size_t)n_channels)) != hipSuccess)
             return bail("hipMalloc quality", e2);
         if ((e2 = hipMemset(h->d_quality, 0, sizeof(psk_soft_quality_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
+        if ((e2 = hipMalloc((void **)&h->d_acquire, sizeof(psk_soft_acquire_t) * (size_t)n_channels)) != hipSuccess)
+            return bail("hipMalloc acquire", e2);
+        if ((e2 = hipMemset(h->d_acquire, 0, sizeof(psk_soft_acquire_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
         for (int s = 0; s < kPlanSlots; s++) {
             // (a slot = the plans of a call followed by the compact channel lists of its launches: one upload)
             // (... behind the header the kernels find in front of the plans: psk_plan.h)
@@ -1948,6 +1973,13 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
             if (q.d_part) (void)hipFree(q.d_part);
         }
         if (h->d_quality) (void)hipFree(h->d_quality);
+        for (auto &q : h->aslot) {
+            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
+            if (q.h_desc) (void)hipHostFree(q.h_desc);
+            if (q.d_desc) (void)hipFree(q.d_desc);
+            if (q.d_part) (void)hipFree(q.d_part);
+        }
+        if (h->d_acquire) (void)hipFree(h->d_acquire);
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
         if (h->d_test) (void)hipFree(h->d_test);
@@ -2316,6 +2348,253 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
     return quality_pass(h, ch0, nch, outs, stream_v);
 }
 
+// ---- the gathers of a call with strided packets: psk_soft_process_device_tuned and psk_soft_acquire_device ----
+// What gather_stage leaves behind: where each packet's own-format row and float2 row of tuned samples lie in the scratch (nullptr:
+// the packet has none), and the scratch and descriptor slot it has claimed, whose events gather_release records behind whatever
+// the caller puts on the stream to read the rows.
+struct GatherStage {
+    std::vector<const void *> row;
+    std::vector<float *> tune_row;
+    GatherScratch *sc = nullptr;
+    GatherDescSlot *ds = nullptr;  // (set once the descriptors are on the stream: from then on gather_release is owed)
+};
+
+// Finds the frame groups among the packets marked `gathered` (present, strided, complex data, at least one sample), claims the
+// stream's scratch and a descriptor slot, uploads the descriptors and launches the gathers on `stream`, and behind them the tune
+// kernel over the packets marked `tuned`.  A column of a run of at least kGatherMinGroup goes through the tile kernel into its
+// own-format row.  A column of a shorter run goes through the plain strided gather, unless it is tuned (the tune kernel reads it
+// where it lies) or the caller reads every such column in place itself (`singles_in_place`: it gets no row).  A call with nothing
+// to launch returns before it touches a stream, gs.ds == nullptr.
+static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                    const uint64_t *sample_stride, const psk_soft_tune_t *tune, const std::vector<uint8_t> &gathered,
+                                    const std::vector<uint8_t> &tuned, bool singles_in_place, hipStream_t stream, GatherStage &gs)
+{
+    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
+    // (a column that gets neither a row nor a gather of its own when its run is too short for the tile kernel)
+    auto direct = [&](uint32_t i) { return singles_in_place || tuned[i]; };
+    uint32_t n_tune = 0;
+    for (uint32_t i = 0; i < nch; i++) n_tune += tuned[i];
+    // ---- frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart ----
+    struct Run {
+        uint32_t first, g, bytes;
+    };
+    std::vector<Run> runs;
+    std::vector<size_t> row_off(nch, 0), tune_off(n_tune ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned packet)
+    std::vector<uint8_t> has_row(nch, 0);
+    size_t need = 0;
+    for (uint32_t i = 0; i < nch;) {
+        if (!gathered[i]) {
+            if (tuned[i]) {
+                tune_off[i] = need;
+                need += align_up(sizeof(float2) * (size_t)(pkts[i].n_floats / 2u), 128);
+            }
+            i++;
+            continue;
+        }
+        const uint32_t sb = 2u * (uint32_t)elem_bytes(pkts[i]);
+        uint32_t j = i + 1;
+        while (j < nch && gathered[j] && pkts[j].format == pkts[i].format && sample_stride[j] == sample_stride[i] &&
+               reinterpret_cast<const char *>(pkts[j].data) == reinterpret_cast<const char *>(pkts[j - 1].data) + sb)
+            j++;
+        runs.push_back({i, j - i, sb});
+        for (uint32_t c = i; c < j; c++) {
+            // (a direct column outside the tile kernel's groups has no own-format row: it is read where it lies)
+            if (!direct(c) || j - i >= psk::kGatherMinGroup) {
+                row_off[c] = need;
+                has_row[c] = 1;
+                need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
+            }
+            if (tuned[c]) {
+                tune_off[c] = need;
+                need += align_up(sizeof(float2) * (size_t)(pkts[c].n_floats / 2u), 128);
+            }
+        }
+        i = j;
+    }
+    // descriptors, per sample size (2, 4, 8 bytes: one launch of each kernel per size): [groups | their columns | singles]
+    uint32_t n_groups[3] = {}, n_cols[3] = {}, n_singles[3] = {};
+    auto size_idx = [](uint32_t bytes) { return bytes == 2 ? 0 : bytes == 4 ? 1 : 2; };
+    for (const Run &r : runs) {
+        const int b = size_idx(r.bytes);
+        if (r.g >= psk::kGatherMinGroup)
+            n_groups[b]++, n_cols[b] += r.g;
+        else
+            for (uint32_t c = r.first; c < r.first + r.g; c++) n_singles[b] += !direct(c);
+    }
+    const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
+    const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
+    if (!tot_groups && !tot_singles && !n_tune)
+        return PSK_SOFT_OK;
+    const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
+    const size_t off_tune = off_singles + sizeof(psk::GatherSingle) * tot_singles;
+    const size_t desc_bytes = off_tune + sizeof(psk::TuneDesc) * n_tune;
+
+    // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
+    // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
+    PSK_HIP(deferred_join(h, stream));
+    GatherScratch *sc = nullptr;
+    for (auto &c : h->gat)
+        if (c.buf && c.stream == stream) {
+            sc = &c;
+            break;
+        }
+    if (!sc) {
+        sc = &h->gat[0];
+        for (auto &c : h->gat)
+            if (c.last_use < sc->last_use)
+                sc = &c;
+    }
+    if (!sc->ev)
+        PSK_HIP(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
+    if (sc->ev_used && sc->stream != stream)
+        PSK_HIP(hipStreamWaitEvent(stream, sc->ev, 0));
+    if (need > sc->cap) {  // (rare: grows to the largest call seen, plus a quarter; the one place that waits for the device)
+        PSK_HIP(hipDeviceSynchronize());
+        if (sc->buf) (void)hipFree(sc->buf);
+        sc->buf = nullptr;
+        sc->cap = 0;
+        const size_t cap = align_up(need + need / 4, 4096);
+        PSK_HIP(hipMalloc((void **)&sc->buf, cap));
+        sc->cap = cap;
+    }
+    sc->stream = stream;
+    sc->last_use = ++h->gat_calls;
+    if (n_tune && !h->d_tune_tab) {  // (once per handle)
+        PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
+        PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
+    }
+    GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
+    h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
+    if (!ds.ev)
+        PSK_HIP(hipEventCreateWithFlags(&ds.ev, hipEventDisableTiming));
+    if (ds.used)
+        PSK_HIP(hipEventSynchronize(ds.ev));
+    ds.used = false;
+    if (desc_bytes > ds.cap) {
+        if (ds.h_buf) (void)hipHostFree(ds.h_buf);
+        if (ds.d_buf) (void)hipFree(ds.d_buf);
+        ds.h_buf = ds.d_buf = nullptr;
+        ds.cap = 0;
+        const size_t cap = align_up(desc_bytes + desc_bytes / 4, 4096);
+        PSK_HIP(hipHostMalloc((void **)&ds.h_buf, cap));
+        PSK_HIP(hipMalloc((void **)&ds.d_buf, cap));
+        ds.cap = cap;
+    }
+    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
+    psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + off_cols);
+    psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
+    psk::TuneDesc *const ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + off_tune);
+    uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
+    uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
+    const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
+    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0;
+    gs.row.assign(nch, nullptr);
+    gs.tune_row.assign(nch, nullptr);
+    for (const Run &r : runs) {
+        const int b = size_idx(r.bytes);
+        for (uint32_t c = r.first; c < r.first + r.g; c++)
+            if (has_row[c])
+                gs.row[c] = sc->buf + row_off[c];
+        if (r.g >= psk::kGatherMinGroup) {
+            psk::GatherGroup &g = hg[g_at[b]++];
+            g = psk::GatherGroup{};
+            g.src = pkts[r.first].data;
+            g.stride = sample_stride[r.first];
+            g.first = c_at[b] - c_lo[b];  // (the launch gets the columns of its sample size)
+            g.g = r.g;
+            g.tiles_c = (r.g + psk::kGatherTile - 1u) / psk::kGatherTile;
+            for (uint32_t c = r.first; c < r.first + r.g; c++) {
+                const uint64_t n = pkts[c].n_floats / 2u;
+                hc[c_at[b]++] = psk::GatherChan{sc->buf + row_off[c], n};
+                g.n_max = n > g.n_max ? n : g.n_max;
+            }
+            g.tile0 = n_tiles[b];
+            n_tiles[b] += (uint64_t)g.tiles_c * ((g.n_max + psk::kGatherTile - 1u) / psk::kGatherTile);
+        } else {
+            for (uint32_t c = r.first; c < r.first + r.g; c++) {
+                if (direct(c))
+                    continue;
+                const uint64_t n = pkts[c].n_floats / 2u;
+                hs[s_at[b]++] = psk::GatherSingle{pkts[c].data, sc->buf + row_off[c], sample_stride[c], n};
+                max_n_single[b] = n > max_n_single[b] ? n : max_n_single[b];
+            }
+        }
+    }
+    // the tuned packets: from the row the tile kernel writes (its columns), else from where the caller has them, at their stride
+    {
+        std::vector<uint8_t> in_group(n_tune ? nch : 0, 0);
+        for (const Run &r : runs)
+            if (n_tune && r.g >= psk::kGatherMinGroup)
+                std::fill(in_group.begin() + r.first, in_group.begin() + r.first + r.g, (uint8_t)1);
+        uint32_t t_at = 0;
+        for (uint32_t c = 0; c < nch && n_tune; c++) {
+            if (!tuned[c])
+                continue;
+            psk::TuneDesc &d = ht[t_at++];
+            d = psk::TuneDesc{};
+            d.src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
+            d.dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
+            d.stride = in_group[c] ? 1u : stride_of(c);
+            d.n = pkts[c].n_floats / 2u;
+            d.phase = tune[c].phase, d.step = tune[c].step;
+            d.format = pkts[c].format;
+            max_n_tune = d.n > max_n_tune ? d.n : max_n_tune;
+            gs.tune_row[c] = d.dst;
+        }
+    }
+    PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
+    ds.used = true;  // (from here on the slot waits for its event, which gather_release records whatever happens)
+    gs.sc = sc, gs.ds = &ds;
+    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; S = bytes of a complex sample, cnt = groups / singles covered)
+    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) -> hipError_t {
+        if (!h->opt_trace)
+            return hipSuccess;
+        if (const hipError_t e = hipDeviceSynchronize())
+            return e;
+        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, bytes, 0, ch0, cnt,
+                     (unsigned long long)tiles, 0u, 0u, h->slot, (void *)stream);
+        std::fflush(stderr);
+        return hipSuccess;
+    };
+    const psk::GatherGroup *const dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
+    const psk::GatherChan *const dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + off_cols);
+    const psk::GatherSingle *const dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + off_singles);
+    for (int b = 0; b < 3; b++) {
+        const int bytes = 2 << b;
+        if (n_groups[b]) {
+            PSK_HIP(mark("gather_tiles", bytes, n_groups[b], n_tiles[b]));
+            PSK_HIP(psk::launch_gather_tiles(bytes, dg + g_lo[b], n_groups[b], dc + c_lo[b], n_tiles[b], stream));
+        }
+        if (n_singles[b]) {
+            PSK_HIP(mark("gather_singles", bytes, n_singles[b], 0));
+            PSK_HIP(psk::launch_gather_singles(bytes, dsg + s_lo[b], n_singles[b], max_n_single[b], stream));
+        }
+    }
+    if (n_tune) {  // (cnt = tuned packets)
+        PSK_HIP(mark("tune", 8, n_tune, 0));
+        PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + off_tune), n_tune, max_n_tune, h->d_tune_tab, stream));
+    }
+    return PSK_SOFT_OK;
+}
+
+// The rows and the descriptors of gather_stage are free again behind everything the call has put on the stream (without the
+// deferred join the side streams of a process call are joined into it by now; with it, the next call that gathers joins them
+// first, in gather_stage).  Returns `st`, the call's status so far, or the failure to record.
+static psk_soft_status gather_release(GatherStage &gs, hipStream_t stream, psk_soft_status st)
+{
+    const std::string keep = g_last_error;
+    const hipError_t e1 = hipEventRecord(gs.sc->ev, stream), e2 = hipEventRecord(gs.ds->ev, stream);
+    gs.sc->ev_used = true;
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+        (void)hipStreamSynchronize(stream);
+        gs.ds->used = false;
+        if (st == PSK_SOFT_OK)
+            return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    }
+    g_last_error = keep;
+    return st;
+}
+
 // Strided packets (include/psk_soft_hip.h): every packet whose samples lie `sample_stride[i]` samples apart is gathered into a
 // contiguous row of the gather scratch, in its own element type, on the caller's stream; a copy of the packet array points at the
 // rows and the ordinary call runs on it.  process_round, the plans, the cut into pieces and every kernel behind it see contiguous
@@ -2394,221 +2673,27 @@ psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0
 
     PSK_HIP(hipSetDevice(h->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
-    // ---- frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart ----
-    struct Run {
-        uint32_t first, g, bytes;
-    };
-    std::vector<Run> runs;
-    std::vector<size_t> row_off(nch, 0), tune_off(n_tune ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned packet)
-    size_t need = 0;
-    for (uint32_t i = 0; i < nch;) {
-        if (!gathered(i)) {
-            if (tuned(i)) {
-                tune_off[i] = need;
-                need += align_up(sizeof(float2) * (size_t)(pkts[i].n_floats / 2u), 128);
-            }
-            i++;
-            continue;
-        }
-        const uint32_t sb = 2u * (uint32_t)elem_bytes(pkts[i]);
-        uint32_t j = i + 1;
-        while (j < nch && gathered(j) && pkts[j].format == pkts[i].format && sample_stride[j] == sample_stride[i] &&
-               reinterpret_cast<const char *>(pkts[j].data) == reinterpret_cast<const char *>(pkts[j - 1].data) + sb)
-            j++;
-        runs.push_back({i, j - i, sb});
-        for (uint32_t c = i; c < j; c++) {
-            // (a tuned column outside the tile kernel's groups has no own-format row: the tune kernel reads it where it lies)
-            if (!tuned(c) || j - i >= psk::kGatherMinGroup) {
-                row_off[c] = need;
-                need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
-            }
-            if (tuned(c)) {
-                tune_off[c] = need;
-                need += align_up(sizeof(float2) * (size_t)(pkts[c].n_floats / 2u), 128);
+    std::vector<uint8_t> is_gathered(nch), is_tuned(nch);
+    for (uint32_t i = 0; i < nch; i++) is_gathered[i] = gathered(i), is_tuned[i] = tuned(i);
+    GatherStage gs;
+    psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, tune, is_gathered, is_tuned, false, stream, gs);
+    if (!gs.ds)
+        return st;
+    if (st == PSK_SOFT_OK && !h->opt_diag_gather_only) {
+        // the ordinary call on a copy of the packets that points at the rows: a tuned packet's float2 row, else the gathered one
+        std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
+        for (uint32_t c = 0; c < nch; c++) {
+            if (gs.tune_row[c]) {
+                pk[c].data = gs.tune_row[c];
+                pk[c].n_floats = 2u * (pkts[c].n_floats / 2u);
+                pk[c].format = PSK_SOFT_FORMAT_CF32;
+            } else if (gs.row[c]) {
+                pk[c].data = reinterpret_cast<const float *>(gs.row[c]);
             }
         }
-        i = j;
-    }
-    // descriptors, per sample size (2, 4, 8 bytes: one launch of each kernel per size): [groups | their columns | singles]
-    uint32_t n_groups[3] = {}, n_cols[3] = {}, n_singles[3] = {};
-    auto size_idx = [](uint32_t bytes) { return bytes == 2 ? 0 : bytes == 4 ? 1 : 2; };
-    for (const Run &r : runs) {
-        const int b = size_idx(r.bytes);
-        if (r.g >= psk::kGatherMinGroup)
-            n_groups[b]++, n_cols[b] += r.g;
-        else
-            for (uint32_t c = r.first; c < r.first + r.g; c++) n_singles[b] += !tuned(c);
-    }
-    const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
-    const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
-    const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
-    const size_t off_tune = off_singles + sizeof(psk::GatherSingle) * tot_singles;
-    const size_t desc_bytes = off_tune + sizeof(psk::TuneDesc) * n_tune;
-
-    // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
-    // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
-    PSK_HIP(deferred_join(h, stream));
-    GatherScratch *sc = nullptr;
-    for (auto &c : h->gat)
-        if (c.buf && c.stream == stream) {
-            sc = &c;
-            break;
-        }
-    if (!sc) {
-        sc = &h->gat[0];
-        for (auto &c : h->gat)
-            if (c.last_use < sc->last_use)
-                sc = &c;
-    }
-    if (!sc->ev)
-        PSK_HIP(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
-    if (sc->ev_used && sc->stream != stream)
-        PSK_HIP(hipStreamWaitEvent(stream, sc->ev, 0));
-    if (need > sc->cap) {  // (rare: grows to the largest call seen, plus a quarter; the one place that waits for the device)
-        PSK_HIP(hipDeviceSynchronize());
-        if (sc->buf) (void)hipFree(sc->buf);
-        sc->buf = nullptr;
-        sc->cap = 0;
-        const size_t cap = align_up(need + need / 4, 4096);
-        PSK_HIP(hipMalloc((void **)&sc->buf, cap));
-        sc->cap = cap;
-    }
-    sc->stream = stream;
-    sc->last_use = ++h->gat_calls;
-    if (n_tune && !h->d_tune_tab) {  // (once per handle)
-        PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
-        PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
-    }
-    GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
-    h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
-    if (!ds.ev)
-        PSK_HIP(hipEventCreateWithFlags(&ds.ev, hipEventDisableTiming));
-    if (ds.used)
-        PSK_HIP(hipEventSynchronize(ds.ev));
-    ds.used = false;
-    if (desc_bytes > ds.cap) {
-        if (ds.h_buf) (void)hipHostFree(ds.h_buf);
-        if (ds.d_buf) (void)hipFree(ds.d_buf);
-        ds.h_buf = ds.d_buf = nullptr;
-        ds.cap = 0;
-        const size_t cap = align_up(desc_bytes + desc_bytes / 4, 4096);
-        PSK_HIP(hipHostMalloc((void **)&ds.h_buf, cap));
-        PSK_HIP(hipMalloc((void **)&ds.d_buf, cap));
-        ds.cap = cap;
-    }
-    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
-    psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + off_cols);
-    psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
-    psk::TuneDesc *const ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + off_tune);
-    uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
-    uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
-    const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
-    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0;
-    std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
-    for (const Run &r : runs) {
-        const int b = size_idx(r.bytes);
-        for (uint32_t c = r.first; c < r.first + r.g; c++)
-            if (!tuned(c))
-                pk[c].data = reinterpret_cast<const float *>(sc->buf + row_off[c]);
-        if (r.g >= psk::kGatherMinGroup) {
-            psk::GatherGroup &g = hg[g_at[b]++];
-            g = psk::GatherGroup{};
-            g.src = pkts[r.first].data;
-            g.stride = sample_stride[r.first];
-            g.first = c_at[b] - c_lo[b];  // (the launch gets the columns of its sample size)
-            g.g = r.g;
-            g.tiles_c = (r.g + psk::kGatherTile - 1u) / psk::kGatherTile;
-            for (uint32_t c = r.first; c < r.first + r.g; c++) {
-                const uint64_t n = pkts[c].n_floats / 2u;
-                hc[c_at[b]++] = psk::GatherChan{sc->buf + row_off[c], n};
-                g.n_max = n > g.n_max ? n : g.n_max;
-            }
-            g.tile0 = n_tiles[b];
-            n_tiles[b] += (uint64_t)g.tiles_c * ((g.n_max + psk::kGatherTile - 1u) / psk::kGatherTile);
-        } else {
-            for (uint32_t c = r.first; c < r.first + r.g; c++) {
-                if (tuned(c))
-                    continue;
-                const uint64_t n = pkts[c].n_floats / 2u;
-                hs[s_at[b]++] = psk::GatherSingle{pkts[c].data, sc->buf + row_off[c], sample_stride[c], n};
-                max_n_single[b] = n > max_n_single[b] ? n : max_n_single[b];
-            }
-        }
-    }
-    // the tuned packets: from the row the tile kernel writes (its columns), else from where the caller has them, at their stride
-    {
-        std::vector<uint8_t> in_group(n_tune ? nch : 0, 0);
-        for (const Run &r : runs)
-            if (n_tune && r.g >= psk::kGatherMinGroup)
-                std::fill(in_group.begin() + r.first, in_group.begin() + r.first + r.g, (uint8_t)1);
-        uint32_t t_at = 0;
-        for (uint32_t c = 0; c < nch && n_tune; c++) {
-            if (!tuned(c))
-                continue;
-            psk::TuneDesc &d = ht[t_at++];
-            d = psk::TuneDesc{};
-            d.src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
-            d.dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
-            d.stride = in_group[c] ? 1u : stride_of(c);
-            d.n = pkts[c].n_floats / 2u;
-            d.phase = tune[c].phase, d.step = tune[c].step;
-            d.format = pkts[c].format;
-            max_n_tune = d.n > max_n_tune ? d.n : max_n_tune;
-            pk[c].data = d.dst;
-            pk[c].n_floats = 2u * d.n;
-            pk[c].format = PSK_SOFT_FORMAT_CF32;
-        }
-    }
-    PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
-    ds.used = true;  // (from here on the slot waits for its event, which the end of this function records whatever happens)
-    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; S = bytes of a complex sample, cnt = groups / singles covered)
-    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) -> hipError_t {
-        if (!h->opt_trace)
-            return hipSuccess;
-        if (const hipError_t e = hipDeviceSynchronize())
-            return e;
-        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, bytes, 0, ch0, cnt,
-                     (unsigned long long)tiles, 0u, 0u, h->slot, (void *)stream);
-        std::fflush(stderr);
-        return hipSuccess;
-    };
-    auto enqueue = [&]() -> psk_soft_status {
-        const psk::GatherGroup *const dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
-        const psk::GatherChan *const dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + off_cols);
-        const psk::GatherSingle *const dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + off_singles);
-        for (int b = 0; b < 3; b++) {
-            const int bytes = 2 << b;
-            if (n_groups[b]) {
-                PSK_HIP(mark("gather_tiles", bytes, n_groups[b], n_tiles[b]));
-                PSK_HIP(psk::launch_gather_tiles(bytes, dg + g_lo[b], n_groups[b], dc + c_lo[b], n_tiles[b], stream));
-            }
-            if (n_singles[b]) {
-                PSK_HIP(mark("gather_singles", bytes, n_singles[b], 0));
-                PSK_HIP(psk::launch_gather_singles(bytes, dsg + s_lo[b], n_singles[b], max_n_single[b], stream));
-            }
-        }
-        if (n_tune) {  // (cnt = tuned packets)
-            PSK_HIP(mark("tune", 8, n_tune, 0));
-            PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + off_tune), n_tune, max_n_tune, h->d_tune_tab, stream));
-        }
-        return PSK_SOFT_OK;
-    };
-    psk_soft_status st = enqueue();
-    if (st == PSK_SOFT_OK && !h->opt_diag_gather_only)
         st = psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
-    // the rows and the descriptors are free again behind everything this call has put on the stream (without the deferred join
-    // the side streams of the call are joined into it by now; with it, the next strided call joins them first, above)
-    const std::string keep = g_last_error;
-    const hipError_t e1 = hipEventRecord(sc->ev, stream), e2 = hipEventRecord(ds.ev, stream);
-    sc->ev_used = true;
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        (void)hipStreamSynchronize(stream);
-        ds.used = false;
-        if (st == PSK_SOFT_OK)
-            return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     }
-    g_last_error = keep;
-    return st;
+    return gather_release(gs, stream, st);
 }
 
 psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
@@ -2638,6 +2723,283 @@ psk_soft_status psk_soft_tune_apply(const psk_soft_tune_t *tune, const float *in
         const float xr = in[2u * k], xi = in[2u * k + 1u];  // (in == out is fine)
         psk::tune_rotate(tab, p, xr, xi, &out[2u * k], &out[2u * k + 1u]);
     }
+    return PSK_SOFT_OK;
+}
+
+// ---- psk_soft_acquire_device: the carrier offset of a packet (include/psk_soft_hip.h, psk_acquire.hip) ----
+// One look at a packet per channel: the fold over pieces of kAcquirePiece samples and the join per packet, on the caller's stream,
+// one record per covered channel.  Nothing of the control plane or of the demodulator's state is read but constelationSize, and
+// nothing is written but the records (and, for the columns of a frame group, their rows of the gather scratch: gather_stage).
+// The descriptors go up from pinned memory of a slot of their own, as the quality pass's.
+// (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
+static bool acquire_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t &k)
+{
+    const uint16_t M = ctl_of(h, ch).props.constelationSize;
+    return k.present && k.sri_mode == 1 && k.n_floats >= 2 && (M == 2 || M == 4 || M == 8);
+}
+
+static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                       const uint64_t *sample_stride, const psk_soft_tune_t *tune, const GatherStage *gs, hipStream_t stream);
+
+psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                        const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
+{
+    if (!h || !pkts || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_device: bad arguments");
+    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
+    // (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
+    auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
+    // the refusals, before anything is enqueued or any record changes
+    for (uint32_t i = 0; i < nch; i++) {
+        const psk_soft_packet_t &k = pkts[i];
+        if (!k.present)
+            continue;
+        char buf[160];
+        const uint64_t s = stride_of(i);
+        if (!s) {
+            std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: a sample stride of 0", ch0 + i);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        if (!psk::pkt_format_known(k.format)) {
+            std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
+                          ch0 + i, (unsigned)k.format);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        const uint64_t sb = 2u * elem_bytes(k);
+        uint64_t pitch = 0, extent = 0;
+        if (__builtin_mul_overflow(s, sb, &pitch) || __builtin_mul_overflow(pitch, k.n_floats / 2u, &extent)) {
+            std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: stride x sample size x samples does not fit 64 bits", ch0 + i);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        if (!looked_at(i))
+            continue;
+        if ((!k.data && !h->dry) || reinterpret_cast<uintptr_t>(k.data) % sb)
+            return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_device: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4)");
+    }
+    if (h->dry) {
+        for (uint32_t i = 0; i < nch; i++) {
+            psk_soft_acquire_t r = {};
+            if (looked_at(i)) {
+                r.n_samples = pkts[i].n_floats / 2u;
+                r.constelationSize = ctl_of(h, ch0 + i).props.constelationSize;
+                r.flags = PSK_SOFT_A_PLANNED;
+            }
+            h->acquire_dry[ch0 + i] = r;
+        }
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // strided packets: the columns of a frame group of at least kGatherMinGroup go through the tile gather into own-format rows of
+    // the stream's gather scratch, which the fold reads; any other strided packet is read where it lies, at its stride
+    GatherStage gs;
+    {
+        std::vector<uint8_t> is_gathered(nch), none(nch, 0);
+        for (uint32_t i = 0; i < nch; i++) is_gathered[i] = stride_of(i) != 1 && looked_at(i);
+        const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, is_gathered, none, true, stream, gs);
+        if (!gs.ds) {
+            if (st != PSK_SOFT_OK)
+                return st;
+            return acquire_enqueue(h, ch0, nch, pkts, sample_stride, tune, nullptr, stream);
+        }
+        return gather_release(gs, stream, st != PSK_SOFT_OK ? st : acquire_enqueue(h, ch0, nch, pkts, sample_stride, tune, &gs, stream));
+    }
+}
+
+// the fold and the join of an acquire call whose arguments have passed (gs: the rows of its gathered packets, or nullptr)
+static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                       const uint64_t *sample_stride, const psk_soft_tune_t *tune, const GatherStage *gs, hipStream_t stream)
+{
+    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
+    auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
+    AcquireSlot &q = h->aslot[h->a_turn];
+    if (q.used)
+        PSK_HIP(hipEventSynchronize(q.ev));
+    if (!q.ev)
+        PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+    if (!q.h_desc)
+        PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(psk::AcquireDesc) * (size_t)h->nch));
+    if (!q.d_desc)
+        PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(psk::AcquireDesc) * (size_t)h->nch));
+    uint64_t n_part = 0;
+    uint32_t max_piece = 0;
+    bool any_tuned = false;
+    for (uint32_t i = 0; i < nch; i++) {
+        psk::AcquireDesc &d = q.h_desc[i];
+        d = psk::AcquireDesc{};
+        d.channel = ch0 + i;
+        if (!looked_at(i))
+            continue;  // (its zero record)
+        const psk_soft_packet_t &k = pkts[i];
+        const bool row = gs && gs->row[i];
+        d.src = row ? gs->row[i] : (const void *)k.data;
+        d.stride = row ? 1u : stride_of(i);
+        d.n = k.n_floats / 2u;
+        d.M = ctl_of(h, ch0 + i).props.constelationSize;
+        d.format = k.format;
+        d.flags = PSK_SOFT_A_DATA;
+        if (tune && (tune[i].phase | tune[i].step) != 0) {
+            d.phase = tune[i].phase, d.step = tune[i].step;
+            d.flags |= PSK_SOFT_A_TUNED;
+            any_tuned = true;
+        }
+        const uint64_t pieces = (d.n + psk::kAcquirePiece - 1u) / psk::kAcquirePiece;
+        if (pieces > 0x7fffffffull || n_part + pieces > 0x7fffffffull)
+            return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_acquire_device: too many samples in one call");
+        d.part0 = (uint32_t)n_part;
+        d.n_piece = (uint32_t)pieces;
+        n_part += pieces;
+        max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
+    }
+    if (n_part > q.part_cap) {
+        if (q.d_part) (void)hipFree(q.d_part);
+        q.d_part = nullptr;
+        q.part_cap = 0;
+        const size_t cap = (size_t)n_part + (size_t)n_part / 4u + 256u;
+        PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(psk::AcquirePartial) * cap));
+        q.part_cap = cap;
+    }
+    if (any_tuned && !h->d_tune_tab) {  // (once per handle)
+        PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
+        PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
+    }
+    // (the record of a channel is written by one call at a time: behind the joins of other streams over the same channels)
+    for (const AcquireSlot &k : h->aslot)
+        if (&k != &q && k.used && k.stream != stream && k.ch0 < ch0 + nch && ch0 < k.ch0 + k.nch)
+            PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
+    PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(psk::AcquireDesc) * (size_t)nch, hipMemcpyHostToDevice, stream));
+    q.used = true, q.stream = stream, q.ch0 = ch0, q.nch = nch;
+    h->a_turn = (h->a_turn + 1) % kAcquireSlots;
+    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; cnt = covered channels, tiles = pieces)
+    auto mark = [&](const char *what) -> hipError_t {
+        if (!h->opt_trace)
+            return hipSuccess;
+        if (const hipError_t e = hipDeviceSynchronize())
+            return e;
+        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, 0, 0, ch0, nch,
+                     (unsigned long long)n_part, 0u, 0u, h->slot, (void *)stream);
+        std::fflush(stderr);
+        return hipSuccess;
+    };
+    auto enqueue = [&]() -> psk_soft_status {
+        PSK_HIP(mark("acquire_fold"));
+        PSK_HIP(psk::launch_acquire_fold(q.d_desc, nch, max_piece, any_tuned ? h->d_tune_tab : nullptr, q.d_part, stream));
+        PSK_HIP(mark("acquire_join"));
+        PSK_HIP(psk::launch_acquire_join(q.d_desc, nch, q.d_part, h->d_acquire, stream));
+        return PSK_SOFT_OK;
+    };
+    const psk_soft_status st = enqueue();
+    // (the slot is free again behind whatever this call has put on the stream)
+    const std::string keep = g_last_error;
+    if (const hipError_t e = hipEventRecord(q.ev, stream)) {
+        (void)hipStreamSynchronize(stream);
+        q.used = false;
+        if (st == PSK_SOFT_OK)
+            return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+    }
+    g_last_error = keep;
+    return st;
+}
+
+uint64_t psk_soft_acquire_bytes(void) { return sizeof(psk_soft_acquire_t); }
+uint32_t psk_soft_acquire_piece(void) { return psk::kAcquirePiece; }
+
+psk_soft_status psk_soft_get_acquire(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_acquire_t *rec)
+{
+    if (!h || !rec || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_acquire: bad arguments");
+    if (h->dry) {
+        std::memcpy(rec, h->acquire_dry.data() + ch0, sizeof(psk_soft_acquire_t) * nch);
+        return PSK_SOFT_OK;
+    }
+    const psk_soft_status st = psk_soft_synchronize(h);
+    if (st != PSK_SOFT_OK)
+        return st;
+    for (AcquireSlot &q : h->aslot)
+        if (q.used)
+            PSK_HIP(hipEventSynchronize(q.ev));
+    PSK_HIP(hipMemcpy(rec, h->d_acquire + ch0, sizeof(psk_soft_acquire_t) * nch, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_acquire_host(uint16_t constelationSize, const psk_soft_tune_t *tune, const float *in, uint64_t n_complex,
+                                      psk_soft_acquire_t *rec)
+{
+    const uint16_t M = constelationSize;
+    if (!rec || (n_complex && !in) || !(M == 2 || M == 4 || M == 8))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_host: null pointer, or a constelationSize other than 2, 4, 8");
+    *rec = psk_soft_acquire_t{};
+    if (!n_complex)
+        return PSK_SOFT_OK;  // (no sample: the zero record)
+    const bool tuned = tune && (tune->phase | tune->step) != 0;
+    const float *const tab = tuned ? psk::tune_tables() : nullptr;
+    const int P = M == 2 ? 1 : M == 4 ? 2 : 3;
+    // the phasors of the last kAcquireHalo samples, by index mod kAcquireHalo
+    float ur[psk::kAcquireHalo], ui[psk::kAcquireHalo];
+    bool valid[psk::kAcquireHalo];
+    uint64_t p = tuned ? tune->phase : 0;
+    for (uint64_t k = 0; k < n_complex; k++) {
+        float re = in[2u * k], im = in[2u * k + 1u];
+        if (tuned) {
+            psk::tune_rotate(tab, p, re, im, &re, &im);
+            p += tune->step;
+        }
+        float e, r, i;
+        const bool ok = psk::acq_sample(re, im, P, &e, &r, &i);
+        if (ok) {
+            rec->sum_e += (double)e;
+            rec->n_valid++;
+            for (uint32_t j = 0; j < psk::kAcquireLags; j++) {
+                const uint64_t L = (uint64_t)1 << j;
+                if (k < L)
+                    break;
+                if (!valid[(k - L) % psk::kAcquireHalo])
+                    continue;
+                const float vr = ur[(k - L) % psk::kAcquireHalo], vi = ui[(k - L) % psk::kAcquireHalo];
+                float tr, ti;
+                psk::acq_lag(r, i, vr, vi, &tr, &ti);
+                rec->sum_re[j] += (double)tr;
+                rec->sum_im[j] += (double)ti;
+                rec->n_pairs[j]++;
+            }
+        }
+        ur[k % psk::kAcquireHalo] = r, ui[k % psk::kAcquireHalo] = i, valid[k % psk::kAcquireHalo] = ok;
+    }
+    rec->n_samples = n_complex;
+    rec->constelationSize = M;
+    rec->flags = (uint8_t)(PSK_SOFT_A_DATA | (tuned ? PSK_SOFT_A_TUNED : 0));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_acquire_derive(const psk_soft_acquire_t *rec, psk_soft_acquire_derived_t *d)
+{
+    if (!rec || !d)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_derive: null pointer");
+    const double nan = std::nan(""), two_pi = 2.0 * 3.14159265358979323846;
+    *d = psk_soft_acquire_derived_t{};
+    d->offset_cycles_per_sample = d->coherence = d->mean_energy = nan;
+    if (!(rec->flags & PSK_SOFT_A_DATA) || !rec->n_pairs[0] || (rec->sum_re[0] == 0.0 && rec->sum_im[0] == 0.0))
+        return PSK_SOFT_OK;
+    const double M = (double)rec->constelationSize;
+    const double c0 = std::hypot(rec->sum_re[0], rec->sum_im[0]) / (double)rec->n_pairs[0];
+    double f = std::atan2(rec->sum_im[0], rec->sum_re[0]) / (two_pi * M);
+    int32_t used = 1;
+    for (uint32_t j = 1; j < psk::kAcquireLags; j++) {
+        if (!rec->n_pairs[j])
+            break;
+        const double cj = std::hypot(rec->sum_re[j], rec->sum_im[j]) / (double)rec->n_pairs[j];
+        if (cj < 0.5 * c0)
+            break;
+        const double L = (double)(1u << j);
+        double dd = std::atan2(rec->sum_im[j], rec->sum_re[j]) - two_pi * M * L * f;
+        dd -= two_pi * std::rint(dd / two_pi);
+        f += dd / (two_pi * M * L);
+        used++;
+    }
+    d->offset_cycles_per_sample = f;
+    d->coherence = c0;
+    d->mean_energy = rec->n_valid ? rec->sum_e / (double)rec->n_valid : nan;
+    d->lags_used = used;
     return PSK_SOFT_OK;
 }
 

@@ -142,6 +142,37 @@ class Tune(ctypes.Structure):
     _fields_ = [("phase", ctypes.c_uint64), ("step", ctypes.c_uint64)]
 
 
+# Acquire.flags
+A_DATA, A_TUNED, A_PLANNED = 1, 2, 128
+ACQUIRE_LAGS = 8  # lags 1, 2, 4 .. 128
+
+
+class Acquire(ctypes.Structure):
+    """psk_soft_acquire_t: the record of the last acquire_device call that covered a channel."""
+
+    _fields_ = [
+        ("n_samples", ctypes.c_uint64),
+        ("n_valid", ctypes.c_uint64),
+        ("n_pairs", ctypes.c_uint64 * ACQUIRE_LAGS),
+        ("sum_re", ctypes.c_double * ACQUIRE_LAGS),
+        ("sum_im", ctypes.c_double * ACQUIRE_LAGS),
+        ("sum_e", ctypes.c_double),
+        ("constelationSize", ctypes.c_uint16),
+        ("flags", ctypes.c_uint8),
+        ("pad", ctypes.c_uint8 * 5),
+    ]
+
+
+class AcquireDerived(ctypes.Structure):
+    _fields_ = [
+        ("offset_cycles_per_sample", ctypes.c_double),
+        ("coherence", ctypes.c_double),
+        ("mean_energy", ctypes.c_double),
+        ("lags_used", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_hip.h declares
@@ -172,6 +203,12 @@ EXPORTS = (
     "psk_soft_tune_step",
     "psk_soft_tune_advance",
     "psk_soft_tune_apply",
+    "psk_soft_acquire_device",
+    "psk_soft_get_acquire",
+    "psk_soft_acquire_derive",
+    "psk_soft_acquire_host",
+    "psk_soft_acquire_bytes",
+    "psk_soft_acquire_piece",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -194,7 +231,11 @@ _lib = None
 
 
 def load():
-    """Load the shared library; raises if it has not been built (no fallback)."""
+    """Load the shared library; raises if it has not been built (no fallback).
+
+    The library links the system's HIP runtime, and torch carries one of its own.  A process that uses both (the test suite
+    does) imports torch in front of the first load(): the library then binds to the runtime torch has brought.  The other way
+    round the process maps two runtimes, and torch finds no device."""
     global _lib
     if _lib is not None:
         return _lib
@@ -249,6 +290,14 @@ def load():
     L.psk_soft_quality_bytes.restype = u64
     L.psk_soft_get_quality.argtypes = [vp, u32, u32, ctypes.POINTER(Quality)]
     L.psk_soft_quality_derive.argtypes = [ctypes.POINTER(Quality), ctypes.POINTER(QualityDerived)]
+    L.psk_soft_acquire_device.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Tune), vp]
+    L.psk_soft_get_acquire.argtypes = [vp, u32, u32, ctypes.POINTER(Acquire)]
+    L.psk_soft_acquire_derive.argtypes = [ctypes.POINTER(Acquire), ctypes.POINTER(AcquireDerived)]
+    L.psk_soft_acquire_host.argtypes = [ctypes.c_uint16, ctypes.POINTER(Tune), vp, u64, ctypes.POINTER(Acquire)]
+    L.psk_soft_acquire_bytes.argtypes = []
+    L.psk_soft_acquire_bytes.restype = u64
+    L.psk_soft_acquire_piece.argtypes = []
+    L.psk_soft_acquire_piece.restype = u32
     _lib = L
     return L
 
@@ -328,6 +377,29 @@ def tune_apply(phase, step, iq):
     t = Tune(int(phase), int(step))
     _check(load().psk_soft_tune_apply(ctypes.byref(t), x.ctypes.data, n, y.ctypes.data))
     return y
+
+
+def acquire_derive(rec):
+    """psk_soft_acquire_derive of one Acquire record: dict of offset_cycles_per_sample, coherence, mean_energy (NaN where
+    undefined) and lags_used.  To take the offset out: tune step += tune_step(-offset_cycles_per_sample)."""
+    d = AcquireDerived()
+    _check(load().psk_soft_acquire_derive(ctypes.byref(rec), ctypes.byref(d)))
+    return {k: getattr(d, k) for k, _ in AcquireDerived._fields_ if k != "pad"}
+
+
+def acquire_host(M, iq, tune=None):
+    """psk_soft_acquire_host: the Acquire record of interleaved float32 I/Q on the host (an odd last element is dropped).
+    tune: None or a (phase, step) pair."""
+    x = np.ascontiguousarray(iq, np.float32)
+    rec = Acquire()
+    t = Tune(int(tune[0]), int(tune[1])) if tune is not None else None
+    _check(load().psk_soft_acquire_host(int(M), ctypes.byref(t) if t is not None else None, x.ctypes.data, x.size // 2, ctypes.byref(rec)))
+    return rec
+
+
+def acquire_piece():
+    """Samples of one piece of the device's fold (psk_soft_acquire_piece)."""
+    return int(load().psk_soft_acquire_piece())
 
 
 class Handle:
@@ -592,6 +664,29 @@ class Handle:
             d.update(quality_derive(q))
             res.append(d)
         return res
+
+    def acquire_device(self, ch0, pkts, strides, tunes, stream=None):
+        """One look at a packet per channel (psk_soft_acquire_device): leaves an Acquire record per covered channel, emits
+        nothing and touches no demodulator state.  pkts, strides and tunes as for process_device_tuned."""
+        if strides is not None and not isinstance(strides, ctypes.Array):
+            strides = (ctypes.c_uint64 * len(strides))(*[int(s) for s in strides])
+        if tunes is not None and not isinstance(tunes, ctypes.Array):
+            tunes = (Tune * len(tunes))(*[Tune(int(p), int(s)) for p, s in tunes])
+        if (strides is not None and len(strides) != len(pkts)) or (tunes is not None and len(tunes) != len(pkts)):
+            raise ValueError("one stride and one tune per packet")
+        _check(self._L.psk_soft_acquire_device(self._h, ch0, len(pkts), pkts, strides, tunes, ctypes.c_void_p(stream or 0)))
+
+    def acquire_records(self, ch0=0, nch=None):
+        """The raw Acquire records of [ch0, ch0+nch) (psk_soft_get_acquire), a ctypes array."""
+        nch = self.n_channels - ch0 if nch is None else nch
+        arr = (Acquire * nch)()
+        _check(self._L.psk_soft_get_acquire(self._h, ch0, nch, arr))
+        return arr
+
+    def acquire(self, ch0, pkts, strides=None, tunes=None, stream=None):
+        """acquire_device, then one dict per covered channel: the derived values (acquire_derive) of its record."""
+        self.acquire_device(ch0, pkts, strides, tunes, stream)
+        return [acquire_derive(r) for r in self.acquire_records(ch0, len(pkts))]
 
     def export_state(self, ch):
         n = int(self._L.psk_soft_state_bytes(self._h))
