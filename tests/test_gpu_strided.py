@@ -29,11 +29,12 @@ H_OF = {"cf32": 1, "sc16": H_CS16, "sc8": H_CS8}
 
 def _poison(dtype):
     return {np.dtype(np.float32): np.uint32(0x7FC00ABC).view(np.float32), np.dtype(np.int16): np.int16(-32768),
-            np.dtype(np.int8): np.int8(-128)}[np.dtype(dtype)]
+            np.dtype(np.int8): np.int8(-128), np.dtype(np.float16): np.uint16(0x7E55).view(np.float16)}[np.dtype(dtype)]
 
 
 def _fmt(pl, dtype):
-    return {np.dtype(np.int8): pl.FORMAT_CS8, np.dtype(np.int16): pl.FORMAT_CS16}.get(np.dtype(dtype), pl.FORMAT_CF32)
+    return {np.dtype(np.int8): pl.FORMAT_CS8, np.dtype(np.int16): pl.FORMAT_CS16,
+            np.dtype(np.float16): pl.FORMAT_CF16}.get(np.dtype(dtype), pl.FORMAT_CF32)
 
 
 def gathers(lines):
