@@ -480,6 +480,39 @@ static void resync_energy(psk_oracle_t *o, size_t samplesPerSymbol, size_t numDa
     o->count = 0;
 }
 
+/* :477  numWraps = round((phaseEstimate-thisPhase)/M_2PI), as a long */
+static long orc_unwrap_count(float phaseEstimate, double thisPhase)
+{
+    return orc_to_long(round(((double)phaseEstimate - thisPhase) / ORC_M_2PI));
+}
+
+/* :523-526  the QPSK bit pair; Q1: float -> bool is '!= 0' */
+static void orc_qpsk_pair(float c_re, float c_im, short *b0, short *b1)
+{
+    int real = (c_re != 0);
+    int imag = (c_im != 0);
+    *b0 = (short)(real ^ imag);
+    *b1 = (short)(!imag);
+}
+
+/* :547-555  the 8-PSK symbol index */
+static unsigned short orc_slice8(float c_re, float c_im)
+{
+    float theta = atan2f(c_im, c_re);
+    float softsym = (float)((double)theta / M_PI * 4);
+    if ((double)softsym < -.5)
+        softsym = softsym + 8.0f;
+    double r = round((double)softsym);
+    /* double -> unsigned short the way x86-64 gcc does it: cvttsd2si to a
+     * 32-bit int, keep the low 16 bits (Q17: -1 -> 0xFFFF, NaN -> 0) */
+    int asInt;
+    if (isnan(r) || r >= 2147483648.0 || r < -2147483648.0)
+        asInt = INT_MIN;
+    else
+        asInt = (int)r;
+    return (unsigned short)(unsigned)asInt;
+}
+
 /* the per-symbol body, cpp/psk_soft.cpp:457-585 */
 static void emit_symbol(psk_oracle_t *o, float cur_re, float cur_im, size_t S, size_t numDataPts,
                         size_t numSyms, size_t bitsPerBaud, psk_oracle_result_t *res)
@@ -506,7 +539,7 @@ static void emit_symbol(psk_oracle_t *o, float cur_re, float cur_im, size_t S, s
     double thisPhase = (double)atan2f(p_im, p_re);
 
     /* :477-478 */
-    long numWraps = orc_to_long(round(((double)o->phaseEstimate - thisPhase) / ORC_M_2PI));
+    long numWraps = orc_unwrap_count(o->phaseEstimate, thisPhase);
     thisPhase += (double)numWraps * ORC_M_2PI;
 
     /* :481-482 */
@@ -536,24 +569,12 @@ static void emit_symbol(psk_oracle_t *o, float cur_re, float cur_im, size_t S, s
     if (bitsPerBaud == 1) { /* :503-513 */
         VEC_PUSH(o->bits, short, (short)(c_re < 0));
     } else if (bitsPerBaud == 2) { /* :514-527, Q1: float -> bool is '!= 0' */
-        int real = (c_re != 0);
-        int imag = (c_im != 0);
-        VEC_PUSH(o->bits, short, (short)(real ^ imag));
-        VEC_PUSH(o->bits, short, (short)(!imag));
+        short b0, b1;
+        orc_qpsk_pair(c_re, c_im, &b0, &b1);
+        VEC_PUSH(o->bits, short, b0);
+        VEC_PUSH(o->bits, short, b1);
     } else if (bitsPerBaud == 3) { /* :528-564 */
-        float theta = atan2f(c_im, c_re);
-        float softsym = (float)((double)theta / M_PI * 4);
-        if ((double)softsym < -.5)
-            softsym = softsym + 8.0f;
-        double r = round((double)softsym);
-        /* double -> unsigned short the way x86-64 gcc does it: cvttsd2si to a
-         * 32-bit int, keep the low 16 bits (Q17: -1 -> 0xFFFF, NaN -> 0) */
-        int asInt;
-        if (isnan(r) || r >= 2147483648.0 || r < -2147483648.0)
-            asInt = INT_MIN;
-        else
-            asInt = (int)r;
-        unsigned short sym = (unsigned short)(unsigned)asInt;
+        unsigned short sym = orc_slice8(c_re, c_im);
         for (size_t j = 0; j != 3; j++) {
             VEC_PUSH(o->bits, short, (short)(sym & 1));
             sym = sym >> 1;
@@ -707,4 +728,98 @@ float psk_oracle_prim_denominator(float xdelta, size_t pts)
     f.denominator = 1.0f;
     linfit_calc_denominator(&f);
     return f.denominator;
+}
+
+/* what the service loop computes beyond the above, exported the same way: each is the static it runs */
+long psk_oracle_prim_to_long(double v) { return orc_to_long(v); }
+long psk_oracle_prim_unwrap_count(float phaseEstimate, double thisPhase) { return orc_unwrap_count(phaseEstimate, thisPhase); }
+unsigned short psk_oracle_prim_slice8(float re, float im) { return orc_slice8(re, im); }
+void psk_oracle_prim_qpsk_pair(float re, float im, short *b0, short *b1) { orc_qpsk_pair(re, im, b0, b1); }
+/* linfit_calc_denominator + linfit_calc_fit on a window of `pts` (> 1) points with the given running sums */
+float psk_oracle_prim_calc_fit(double ySum, double xySum, float xdelta, size_t pts, float *denominator, float *xAvg,
+                               float *m, float *b)
+{
+    orc_linfit_t f;
+    memset(&f, 0, sizeof f);
+    f.xdelta = xdelta;
+    f.yvals.len = pts;
+    f.denominator = 1.0f;
+    linfit_calc_denominator(&f);
+    f.ySum = ySum;
+    f.xySum = xySum;
+    float v = linfit_calc_fit(&f);
+    *denominator = f.denominator;
+    *xAvg = f.xAvg;
+    *m = f.m;
+    *b = f.b;
+    return v;
+}
+
+/* array forms: `n` cases of one primitive, inputs and outputs as parallel arrays (in[k], out[k]: see the header) */
+int psk_oracle_prim_array(int op, unsigned param, const void *const *in, void *const *out, size_t n)
+{
+#define IN(k, T) ((const T *)in[k])
+#define OUT(k, T) ((T *)out[k])
+    /* CALC_FIT keeps one LinearFit over the cases, as the service loop does over the symbols: the denominator is
+     * recomputed where (xdelta, window length) change -- calculateDenominator runs on reset() and while the window fills */
+    orc_linfit_t fit;
+    int fit_set = 0;
+    memset(&fit, 0, sizeof fit);
+    for (size_t i = 0; i < n; i++) {
+        switch (op) {
+        case PSK_ORACLE_ARR_ATAN2F: OUT(0, float)[i] = atan2f(IN(0, float)[i], IN(1, float)[i]); break;
+        case PSK_ORACLE_ARR_SINCOSF:
+            OUT(0, float)[i] = sinf(IN(0, float)[i]);
+            OUT(1, float)[i] = cosf(IN(0, float)[i]);
+            break;
+        case PSK_ORACLE_ARR_POLAR1: orc_polar1(IN(0, float)[i], &OUT(0, float)[i], &OUT(1, float)[i]); break;
+        case PSK_ORACLE_ARR_NORM: OUT(0, float)[i] = orc_norm(IN(0, float)[i], IN(1, float)[i]); break;
+        case PSK_ORACLE_ARR_CMUL:
+            orc_cmul(IN(0, float)[i], IN(1, float)[i], IN(2, float)[i], IN(3, float)[i], &OUT(0, float)[i], &OUT(1, float)[i]);
+            break;
+        case PSK_ORACLE_ARR_CDIV:
+            orc_cdiv(IN(0, float)[i], IN(1, float)[i], IN(2, float)[i], IN(3, float)[i], &OUT(0, float)[i], &OUT(1, float)[i]);
+            break;
+        case PSK_ORACLE_ARR_CPOW: orc_cpow(IN(0, float)[i], IN(1, float)[i], param, &OUT(0, float)[i], &OUT(1, float)[i]); break;
+        case PSK_ORACLE_ARR_WRAP_TEST: OUT(0, int32_t)[i] = orc_wrap_test(IN(0, float)[i], IN(1, float)[i]); break;
+        case PSK_ORACLE_ARR_TO_LONG: OUT(0, int64_t)[i] = orc_to_long(IN(0, double)[i]); break;
+        case PSK_ORACLE_ARR_UNWRAP: OUT(0, int64_t)[i] = orc_unwrap_count(IN(0, float)[i], IN(1, double)[i]); break;
+        case PSK_ORACLE_ARR_SLICE8: OUT(0, int32_t)[i] = orc_slice8(IN(0, float)[i], IN(1, float)[i]); break;
+        case PSK_ORACLE_ARR_QPSK: {
+            short b0, b1;
+            orc_qpsk_pair(IN(0, float)[i], IN(1, float)[i], &b0, &b1);
+            OUT(0, int32_t)[i] = b0;
+            OUT(1, int32_t)[i] = b1;
+            break;
+        }
+        case PSK_ORACLE_ARR_DENOMINATOR: {
+            float den, xavg, m, b;
+            (void)psk_oracle_prim_calc_fit(0.0, 0.0, IN(0, float)[i], IN(1, uint32_t)[i], &den, &xavg, &m, &b);
+            OUT(0, float)[i] = den;
+            OUT(1, float)[i] = xavg;
+            break;
+        }
+        case PSK_ORACLE_ARR_CALC_FIT: {
+            const float xd = IN(2, float)[i];
+            const size_t pts = IN(3, uint32_t)[i];
+            if (!fit_set || pts != fit.yvals.len || memcmp(&xd, &fit.xdelta, sizeof xd) != 0) {
+                fit.xdelta = xd;
+                fit.yvals.len = pts;
+                fit.denominator = 1.0f;
+                linfit_calc_denominator(&fit);
+                fit_set = 1;
+            }
+            fit.ySum = IN(0, double)[i];
+            fit.xySum = IN(1, double)[i];
+            OUT(0, float)[i] = linfit_calc_fit(&fit);
+            OUT(1, float)[i] = fit.m;
+            OUT(2, float)[i] = fit.b;
+            break;
+        }
+        default: return -1;
+        }
+    }
+#undef IN
+#undef OUT
+    return 0;
 }

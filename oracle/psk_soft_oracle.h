@@ -102,6 +102,35 @@ float psk_oracle_prim_norm(float a, float b);
 void  psk_oracle_prim_polar1(float theta, float *re, float *im);
 int   psk_oracle_prim_wrap_test(float phaseEstimate, float wrapValue);
 float psk_oracle_prim_denominator(float xdelta, size_t pts);
+/* ... and what the service loop computes besides: each export calls the static the loop itself runs */
+long  psk_oracle_prim_to_long(double v);                                    /* (long) of a double, cvttsd2si    */
+long  psk_oracle_prim_unwrap_count(float phaseEstimate, double thisPhase);  /* cpp/psk_soft.cpp:477             */
+unsigned short psk_oracle_prim_slice8(float re, float im);                  /* :547-555                         */
+void  psk_oracle_prim_qpsk_pair(float re, float im, short *b0, short *b1);  /* :523-526                         */
+float psk_oracle_prim_calc_fit(double ySum, double xySum, float xdelta, size_t pts, float *denominator, float *xAvg,
+                               float *m, float *b);                         /* :135-185, pts > 1                */
+
+/* Array forms: n cases of one primitive in a C loop.  in[k] / out[k] are parallel arrays of n elements:
+ *   ATAN2F      in  y, x (float)                      out atan2f(y, x) of this machine's libm (float)
+ *   SINCOSF     in  t (float)                         out sinf(t), cosf(t) (float)
+ *   POLAR1      in  theta (float)                     out re, im (float)
+ *   NORM        in  re, im (float)                    out float
+ *   CMUL, CDIV  in  a, b, c, d (float)                out re, im (float)
+ *   CPOW        in  re, im (float), param = exponent  out re, im (float)
+ *   WRAP_TEST   in  phaseEstimate, wrapValue (float)  out int32
+ *   TO_LONG     in  v (double)                        out int64
+ *   UNWRAP      in  phaseEstimate (float), thisPhase (double)  out int64
+ *   SLICE8      in  re, im (float)                    out int32 (the unsigned short index)
+ *   QPSK        in  re, im (float)                    out b0, b1 (int32)
+ *   DENOMINATOR in  xdelta (float), pts (uint32, > 1) out denominator, xAvg (float)
+ *   CALC_FIT    in  ySum, xySum (double), xdelta (float), pts (uint32, > 1)   out fit, m, b (float)
+ * Returns 0, or -1 for an unknown op. */
+enum {
+    PSK_ORACLE_ARR_ATAN2F = 0, PSK_ORACLE_ARR_SINCOSF, PSK_ORACLE_ARR_POLAR1, PSK_ORACLE_ARR_NORM, PSK_ORACLE_ARR_CMUL,
+    PSK_ORACLE_ARR_CDIV, PSK_ORACLE_ARR_CPOW, PSK_ORACLE_ARR_WRAP_TEST, PSK_ORACLE_ARR_TO_LONG, PSK_ORACLE_ARR_UNWRAP,
+    PSK_ORACLE_ARR_SLICE8, PSK_ORACLE_ARR_QPSK, PSK_ORACLE_ARR_DENOMINATOR, PSK_ORACLE_ARR_CALC_FIT
+};
+int psk_oracle_prim_array(int op, unsigned param, const void *const *in, void *const *out, size_t n);
 
 #ifdef __cplusplus
 }

@@ -490,13 +490,24 @@ PSK_HD unsigned lm_slice8_fast(float re, float im, bool *near)
 // (Markstein: q = RN(a*rb), r = a - q*b exactly by fma, RN(q + r*rb) is the correctly
 // rounded quotient; the excluded case, a divisor significand of all ones, cannot occur for
 // the divisors used here: 2*pi, float-valued doubles and small integers).  Bit-identical to
-// the reference's IEEE double divisions at cpp/psk_soft.cpp:157-158 and :477.
+// the reference's IEEE double divisions at cpp/psk_soft.cpp:157-158 and :477 -- for every numerator:
+// the three steps above are exact while 2^-500 <= |q| < 2^500 (b is a float's value, an integer or
+// 2*pi, so neither a, q*b nor r leaves the normal range there).  Outside it -- a quotient that is
+// zero, denormal, overflowed, infinite or NaN: a -0.0 comes out +0.0, inf - inf gives NaN for an
+// infinity, r underflows -- the lanes concerned take the division itself, behind a test the whole
+// wave shares, like the other rare operands of this header.  A +0.0 numerator that came out +0.0
+// is right as it stands (an idle channel's phase differences and sums are all +0.0).
 // ---------------------------------------------------------------------------------
 PSK_HD double lm_div_known(double a, double b, double rb)
 {
     double q = a * rb;
     double r = __builtin_fma(-q, b, a);
-    return __builtin_fma(r, rb, q);
+    double res = __builtin_fma(r, rb, q);
+    const uint32_t eq = (uint32_t)(__builtin_bit_cast(uint64_t, q) >> 52) & 0x7ffu;  // biased exponent of q
+    const bool out = (eq - 523u >= 1000u) && (__builtin_bit_cast(uint64_t, a) | __builtin_bit_cast(uint64_t, res)) != 0;
+    if (PSK_LM_ANY(out))
+        res = out ? a / b : res;
+    return res;
 }
 
 }  // namespace psk

@@ -1,7 +1,11 @@
 """The product's libm restatements (psk_soft_amd/csrc/psk_libm.h: atan2f / atanf / sinf / cosf of
 glibc 2.35, and the known-divisor division) compiled for the HOST and compared bit-for-bit
-with this machine's glibc -- the libm the oracle (like the reference) calls.  If this passes,
-the device's transcendental results equal the oracle's whenever their arguments are equal."""
+with this machine's glibc -- the libm the oracle (like the reference) calls.  What this shows is that
+the HOST build of the header returns glibc's floats on 1.2e7 random arguments per function.  What the
+device build executes differs (constants moved into scalar registers through inline asm, guards that are
+per wave instead of per value, the range table read from lanes, the device compiler's conversions and
+divisions): tests/test_gpu_dev_prims.py runs that build on the GPU and holds it to glibc and the oracle,
+tests/test_dev_prim_cases.py holds this host build to glibc on the directed cases as well."""
 import os
 import subprocess
 
