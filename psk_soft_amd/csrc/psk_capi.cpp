@@ -88,12 +88,7 @@ hipError_t launch_tile_back(const ChanPlan *plans, const uint32_t *list, uint32_
 
 namespace {
 
-thread_local std::string g_last_error;
-thread_local bool g_long_call = false;  // process_round's note to psk_soft_process_device: plan the call in pieces
-// ... and: the batch mixes window classes that cannot be resident together -- cut every channel's call into g_split_pieces pieces in
-// time and let the classes run through them on their own streams, joined once at the end of the call (see process_device)
-thread_local int g_split_pieces = 0;
-thread_local bool g_split_mode = false;  // the rounds of such a call: their side streams are not joined in between
+thread_local std::string g_last_error;  // (psk_soft_last_error)
 
 psk_soft_status fail(psk_soft_status st, const std::string &msg)
 {
@@ -113,8 +108,8 @@ constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that
 constexpr int kStageSlots = 3;  // chunks of the host-buffer path in flight (< kPlanSlots)
 constexpr int kQualitySlots = 4;  // calls whose quality pass (PSK_SOFT_OPT_QUALITY) may be in flight: descriptors and partials of each
 constexpr int kAcquireSlots = 4;  // psk_soft_acquire_device calls that may be in flight: descriptors and partials of each
-constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 / CF16 packets, one per stream that uses them (see CvtScratch)
-constexpr int kGatherScratch = 4;  // gather scratch buffers of strided packets, one per stream that uses them (see GatherScratch)
+constexpr int kCvtScratch = 4;  // conversion scratch buffers of CS16 / CS8 / CF16 packets, one per stream that uses them (see StreamScratch)
+constexpr int kGatherScratch = 4;  // gather scratch buffers of strided packets, one per stream that uses them (see StreamScratch)
 constexpr int kGatherDescSlots = 4;  // strided calls whose gather descriptors may be in flight
 // bytes of a packet's element
 inline size_t elem_bytes(const psk_soft_packet_t &k)
@@ -270,61 +265,130 @@ inline size_t region_bits(size_t in_cap) { return in_cap + in_cap + in_cap / 2; 
 inline size_t region_sidx(size_t in_cap) { return in_cap + in_cap + in_cap / 2 + in_cap; }
 inline size_t region_total(size_t in_cap) { return in_cap + in_cap + in_cap / 2 + in_cap + in_cap / 4; }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-// Where the CS16 packets of a call are converted to (psk_pkt.hip): float2 rows, 128-byte aligned, grown on demand.  One buffer
-// per stream that calls with CS16 packets -- the chunks of psk_soft_process_host run on streams of their own and would
-// otherwise wait for each other --; a buffer taken over from another stream is used behind the event that ends its last call.
-struct CvtScratch {
-    hipStream_t stream = nullptr;
-    float *buf = nullptr;
-    size_t cap = 0;  // bytes
-    hipEvent_t ev = nullptr;
-    bool ev_used = false;
-    uint64_t last_use = 0;
-};
-
-// Where the strided packets of a call are gathered to (psk_soft_process_device_strided, psk_gather.hip): rows in the packet's own
-// element type, 128-byte aligned, grown on demand.  As CvtScratch: one buffer per calling stream, a buffer taken over from
-// another stream is used behind the event that ends its last call.
-struct GatherScratch {
+// Where the CS16 / CS8 / CF16 packets of a call are converted to (psk_pkt.hip: float2 rows) and where its strided packets are gathered to
+// (psk_soft_process_device_strided, psk_gather.hip: rows in the packet's own element type): rows on 128-byte boundaries of a buffer
+// grown on demand.  One buffer per stream that calls with such packets -- the chunks of psk_soft_process_host run on streams of their
+// own and would otherwise wait for each other --; a buffer taken over from another stream is used behind the event that ends its last call.
+struct StreamScratch {
     hipStream_t stream = nullptr;
     char *buf = nullptr;
     size_t cap = 0;  // bytes
     hipEvent_t ev = nullptr;
     bool ev_used = false;
     uint64_t last_use = 0;
+    void free()
+    {
+        if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
+        if (buf) (void)hipFree(buf);
+    }
 };
-// ... and the descriptors of one such call (psk_gather.h): written into page-locked memory, uploaded on the caller's stream in
+// ... and the descriptors of one strided call (psk_gather.h): written into page-locked memory, uploaded on the caller's stream in
 // front of the gather, reused behind the event that ends the call
 struct GatherDescSlot {
     char *h_buf = nullptr, *d_buf = nullptr;
     size_t cap = 0;  // bytes
     hipEvent_t ev = nullptr;
     bool used = false;
+    void free()
+    {
+        if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
+        if (h_buf) (void)hipHostFree(h_buf);
+        if (d_buf) (void)hipFree(d_buf);
+    }
 };
 
-// PSK_SOFT_OPT_QUALITY: what the pass behind one call owns until its event -- the descriptors (pinned, and their copy in device
-// memory: one per channel of the handle) and the partials of the fold (grown on demand).  The chunks of psk_soft_process_host run
-// on streams of their own and overlap, hence several.
-struct QualitySlot {
-    psk::QualityDesc *h_desc = nullptr, *d_desc = nullptr;
-    psk::QualityPartial *d_part = nullptr;
-    size_t part_cap = 0;  // partials
-    hipEvent_t ev = nullptr;
-    bool used = false;
-    hipStream_t stream = nullptr;
-    uint32_t ch0 = 0, nch = 0;
-};
+// What a pass of fold + join behind a call owns until its event -- PSK_SOFT_OPT_QUALITY's behind a process call (psk_quality.hip),
+// psk_soft_acquire_device's (psk_acquire.hip): the descriptors (pinned, and their copy in device memory: one per channel of the
+// handle) and the partials of the fold (grown on demand).  The chunks of psk_soft_process_host run on streams of their own and overlap,
+// hence a ring of N of them.  A pass goes through the members in the order they stand in.
+template <class Desc, class Partial, int N>
+struct PassRing {
+    struct Slot {
+        Desc *h_desc = nullptr, *d_desc = nullptr;
+        Partial *d_part = nullptr;
+        size_t part_cap = 0;  // partials
+        hipEvent_t ev = nullptr;
+        bool used = false;
+        hipStream_t stream = nullptr;
+        uint32_t ch0 = 0, nch = 0;
+    } slot[N];
+    int turn = 0;
 
-// psk_soft_acquire_device: what one call owns until its event, as QualitySlot -- the descriptors (pinned, and their copy in device
-// memory: one per channel of the handle) and the partials of the fold (grown on demand)
-struct AcquireSlot {
-    psk::AcquireDesc *h_desc = nullptr, *d_desc = nullptr;
-    psk::AcquirePartial *d_part = nullptr;
-    size_t part_cap = 0;  // partials
-    hipEvent_t ev = nullptr;
-    bool used = false;
-    hipStream_t stream = nullptr;
-    uint32_t ch0 = 0, nch = 0;
+    // the slot of the next pass ...
+    Slot &next()
+    {
+        Slot &q = slot[turn];
+        turn = (turn + 1) % N;
+        return q;
+    }
+    // ... once its last pass has ended; event and descriptors (handle_nch of them) are created on first use
+    static psk_soft_status claim(Slot &q, uint32_t handle_nch)
+    {
+        if (q.used)
+            PSK_HIP(hipEventSynchronize(q.ev));
+        if (!q.ev)
+            PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+        if (!q.h_desc)
+            PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(Desc) * (size_t)handle_nch));
+        if (!q.d_desc)
+            PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(Desc) * (size_t)handle_nch));
+        return PSK_SOFT_OK;
+    }
+    // room for n partials
+    static psk_soft_status grow(Slot &q, uint64_t n)
+    {
+        if (n <= q.part_cap)
+            return PSK_SOFT_OK;
+        if (q.d_part) (void)hipFree(q.d_part);
+        q.d_part = nullptr;
+        q.part_cap = 0;
+        const size_t cap = (size_t)n + (size_t)n / 4u + 256u;
+        PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(Partial) * cap));
+        q.part_cap = cap;
+        return PSK_SOFT_OK;
+    }
+    // The record of a channel is written by one pass at a time: `stream` waits for the passes of other streams over channels of
+    // [ch0, ch0 + nch); then the descriptors go up and the slot is the pass's.
+    psk_soft_status upload(Slot &q, uint32_t ch0, uint32_t nch, hipStream_t stream)
+    {
+        for (const Slot &k : slot)
+            if (&k != &q && k.used && k.stream != stream && k.ch0 < ch0 + nch && ch0 < k.ch0 + k.nch)
+                PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
+        PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(Desc) * (size_t)nch, hipMemcpyHostToDevice, stream));
+        q.used = true, q.stream = stream, q.ch0 = ch0, q.nch = nch;
+        return PSK_SOFT_OK;
+    }
+    // The slot is free again behind whatever the pass has put on the stream.  Returns `st`, the pass's status so far (its error text
+    // kept), or the failure to record.
+    static psk_soft_status finish(Slot &q, hipStream_t stream, psk_soft_status st)
+    {
+        const std::string keep = g_last_error;
+        if (const hipError_t e = hipEventRecord(q.ev, stream)) {
+            (void)hipStreamSynchronize(stream);
+            q.used = false;
+            if (st == PSK_SOFT_OK)
+                return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+        }
+        g_last_error = keep;
+        return st;
+    }
+    // every pass enqueued so far has ended
+    psk_soft_status wait()
+    {
+        for (Slot &q : slot)
+            if (q.used)
+                PSK_HIP(hipEventSynchronize(q.ev));
+        return PSK_SOFT_OK;
+    }
+    void free()
+    {
+        for (Slot &q : slot) {
+            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
+            if (q.h_desc) (void)hipHostFree(q.h_desc);
+            if (q.d_desc) (void)hipFree(q.d_desc);
+            if (q.d_part) (void)hipFree(q.d_part);
+        }
+    }
 };
 
 // Largest phaseAvg of the wave-scan kernels: their LDS ring of unwrapped phases holds phaseAvg + 128 values in a power
@@ -448,7 +512,7 @@ struct psk_soft_handle {
                            // a call reported a first guess that failed (pf.hint, a word the kernels write into page-locked memory)
     int pf_second_ttl = 0;  // tiled calls left with the second round enqueued
     int opt_ties_in_place = 1;              // PSK_SOFT_TIES_IN_PLACE=0 (environment): PLAN_TIES_HANDOVER in every plan (tests, A/B runs)
-    int opt_trace = 0;                      // PSK_SOFT_TRACE_LAUNCHES=1 (environment, debugging): see `mark` in process_round
+    int opt_trace = 0;                      // PSK_SOFT_TRACE_LAUNCHES=1 (environment, debugging): see trace_launch
     int opt_validate = 0;                   // PSK_SOFT_VALIDATE=1 (environment, tests): see `validate` in process_round
     int opt_split = 2;                      // PSK_SOFT_SPLIT_CLASSES=n (environment): pieces a mixed batch's calls are cut into (0 / 1: never)
     int opt_pipe = 1;                       // PSK_SOFT_PIPELINED=0 (environment): never the pipelined mode (A/B runs)
@@ -475,11 +539,11 @@ struct psk_soft_handle {
     uint32_t far_rows_cap = 0, far_rows_used = 0;
     std::vector<uint32_t> far_row;
     bool poisoned = false;  // a HIP call failed after kernels of a call were enqueued: host mirror and device state may disagree
-    // CS16 / CS8 / CF16 packets: conversion scratch (CvtScratch)
-    CvtScratch cvt[kCvtScratch];
+    // CS16 / CS8 / CF16 packets: conversion scratch (StreamScratch)
+    StreamScratch cvt[kCvtScratch];
     uint64_t cvt_calls = 0;
-    // strided packets: gather scratch and descriptor slots (GatherScratch, GatherDescSlot)
-    GatherScratch gat[kGatherScratch];
+    // strided packets: gather scratch and descriptor slots (StreamScratch, GatherDescSlot)
+    StreamScratch gat[kGatherScratch];
     GatherDescSlot gdesc[kGatherDescSlots];
     uint64_t gat_calls = 0;
     int gdesc_turn = 0;
@@ -491,8 +555,7 @@ struct psk_soft_handle {
     int opt_quality = 0;
     psk_soft_quality_t *d_quality = nullptr;
     std::vector<psk_soft_quality_t> quality_dry;
-    QualitySlot qslot[kQualitySlots];
-    int q_turn = 0;
+    PassRing<psk::QualityDesc, psk::QualityPartial, kQualitySlots> qpass;
     struct QualitySnap {
         uint16_t M, S;
         uint8_t diff;
@@ -502,8 +565,7 @@ struct psk_soft_handle {
     // control-plane-only handle keeps them on the host
     psk_soft_acquire_t *d_acquire = nullptr;
     std::vector<psk_soft_acquire_t> acquire_dry;
-    AcquireSlot aslot[kAcquireSlots];
-    int a_turn = 0;
+    PassRing<psk::AcquireDesc, psk::AcquirePartial, kAcquireSlots> apass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -602,6 +664,7 @@ struct Round {
     const psk_soft_packet_t *pkts;
     psk_soft_output_t *outs;
     const uint8_t *cont;  // pieces of a call the library has cut, see process_round
+    bool of_split;        // ... of a mixed batch cut in time: the side streams are not joined between its rounds
     hipStream_t stream;
     int slot;
     bool dry;
@@ -624,7 +687,7 @@ struct Round {
     // conversion pre-pass: descriptors in all and per format, the longest packet of each, the scratch they convert into
     uint32_t n_cvt = 0, n_cvt_f[psk::kNumPktFormats] = {};
     uint64_t cvt_max_n[psk::kNumPktFormats] = {};
-    CvtScratch *cv = nullptr;
+    StreamScratch *cv = nullptr;
     uint32_t n_in_place = 0, n_in_place_f[psk::kNumPktFormats] = {}, n_seq_narrow = 0;  // the reference-order kernel's lists
     Cls cls[33 * kNumClassH];  // the schedule
     int n_cls = 0;
@@ -1070,6 +1133,41 @@ hipError_t grow_scratch(std::initializer_list<ScratchBuf> bufs, bool *got)
     }
     return hipSuccess;
 }
+// The scratch of `ring` for a call on `stream` that needs `need` bytes of it: the stream's own buffer, else the one used longest ago;
+// `stream` waits for the event that ends the buffer's last call on another stream; a buffer too small grows to the need plus a quarter, in
+// whole pages (rare: the one place that waits for the device).  Out of device memory: `oom`, or without one the plain HIP error.
+template <int N>
+psk_soft_status claim_scratch(StreamScratch (&ring)[N], uint64_t *calls, hipStream_t stream, size_t need, const char *oom, StreamScratch **out)
+{
+    StreamScratch *sc = &ring[0], *own = nullptr;
+    for (StreamScratch &c : ring) {
+        sc = c.last_use < sc->last_use ? &c : sc;
+        own = !own && c.buf && c.stream == stream ? &c : own;
+    }
+    *out = sc = own ? own : sc;
+    if (!sc->ev)
+        PSK_HIP(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
+    if (sc->ev_used && sc->stream != stream)
+        PSK_HIP(hipStreamWaitEvent(stream, sc->ev, 0));
+    if (need > sc->cap) {
+        sc->cap = 0;
+        const size_t cap = align_up(plus_quarter(need), 4096);
+        if (oom) {
+            bool got = false;
+            PSK_HIP(grow_scratch({ScratchBuf{(void **)&sc->buf, cap}}, &got));
+            if (!got)
+                return fail(PSK_SOFT_ERR_HIP, oom);
+        } else {
+            PSK_HIP(hipDeviceSynchronize());
+            if (sc->buf) (void)hipFree(sc->buf);
+            sc->buf = nullptr;
+            PSK_HIP(hipMalloc((void **)&sc->buf, cap));
+        }
+        sc->cap = cap;
+    }
+    sc->stream = stream, sc->last_use = ++*calls;
+    return PSK_SOFT_OK;
+}
 // the channel's call goes to the reference-order kernel after all
 void to_reference_order(psk::ChanPlan &p)
 {
@@ -1276,26 +1374,10 @@ psk_soft_status conversion_descriptors(Round &r)
         }
     if (!r.n_cvt)
         return PSK_SOFT_OK;
-    CvtScratch *cv = &h->cvt[0], *own = nullptr;  // (the stream's own buffer, else the one used longest ago)
-    for (auto &c : h->cvt) {
-        cv = c.last_use < cv->last_use ? &c : cv;
-        own = !own && c.buf && c.stream == r.stream ? &c : own;
-    }
-    r.cv = cv = own ? own : cv;
-    if (!cv->ev)
-        PSK_HIP(hipEventCreateWithFlags(&cv->ev, hipEventDisableTiming));
-    if (cv->ev_used && cv->stream != r.stream)
-        PSK_HIP(hipStreamWaitEvent(r.stream, cv->ev, 0));
-    if (need > cv->cap) {
-        cv->cap = 0;
-        const size_t cap = align_up(plus_quarter(need), 4096);
-        bool got = false;
-        PSK_HIP(grow_scratch({ScratchBuf{(void **)&cv->buf, cap}}, &got));
-        if (!got)  // (nothing else reads these packets)
-            return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the conversion of CS16 / CS8 / CF16 packets");
-        cv->cap = cap;
-    }
-    cv->stream = r.stream, cv->last_use = ++h->cvt_calls;
+    // (without the scratch the call fails: nothing else reads these packets)
+    PSK_TRY(claim_scratch(h->cvt, &h->cvt_calls, r.stream, need, "psk_soft_process: out of device memory for the conversion of CS16 / CS8 / CF16 packets",
+                          &r.cv));
+    const StreamScratch *const cv = r.cv;
     psk::CvtDesc *const desc =
         reinterpret_cast<psk::CvtDesc *>(reinterpret_cast<char *>(psk::plan_header(h->h_plans[r.slot])) + slot_cvt_offset(r.nch));
     size_t off = 0;
@@ -1308,7 +1390,7 @@ psk_soft_status conversion_descriptors(Round &r)
             continue;
         const uint32_t k = next[f]++;
         desc[k].src = reinterpret_cast<const uint32_t *>(p.in);
-        desc[k].dst = reinterpret_cast<float *>(reinterpret_cast<char *>(cv->buf) + off);
+        desc[k].dst = reinterpret_cast<float *>(cv->buf + off);
         desc[k].n = p.n_in;
         p.in = desc[k].dst;
         off += align_up(sizeof(float2) * p.n_in, 128);
@@ -1374,8 +1456,7 @@ const char *invalid_plan(const Round &r, const psk::ChanPlan &p)
         return "place in the wide-symbol scratch outside it";
     if (p.S > kSeqMaxS && (p.S > r.wide_seq_S || !h->d_wide_symE || (size_t)r.n_wide_seq * r.wide_seq_S > h->wide_symE_cap))
         return "wide symbol without a row of symbolEnergy";
-    if (cvt_format(p) >= 0 && (!r.cv || (const char *)p.in < (const char *)r.cv->buf ||
-                               (const char *)p.in + sizeof(float2) * p.n_in > (const char *)r.cv->buf + r.cv->cap))
+    if (cvt_format(p) >= 0 && (!r.cv || (const char *)p.in < r.cv->buf || (const char *)p.in + sizeof(float2) * p.n_in > r.cv->buf + r.cv->cap))
         return "converted CS16 / CS8 / CF16 packet outside the conversion scratch";
     return nullptr;
 }
@@ -1413,7 +1494,7 @@ psk_soft_status choose_schedule(Round &r, bool *cut)
     // only calls whose every channel runs on wave-scan launches are deferred or cut (nor calls with CS16 packets: the conversion
     // scratch is one per stream, and the next call's pre-pass must not overwrite it under the side streams of this one)
     const bool wave_scan_only = r.fork && !r.tile_syms && !res.any.cnt && !res.any_seq && !r.n_cvt && !r.n_wide_seq;
-    r.deferred = wave_scan_only && (h->opt_deferred || g_split_mode) && (!r.cont || g_split_mode);
+    r.deferred = wave_scan_only && (h->opt_deferred || r.of_split) && (!r.cont || r.of_split);
     if (wave_scan_only && !r.cont && !h->opt_deferred && h->opt_split > 1) {
         // Classes that cannot be resident together take two rounds of waves, and a wave that starts late still needs the whole call's
         // time at the lone-wave rate: cut in time, the late pieces are short too ("A mixed batch cut in time").
@@ -1479,17 +1560,28 @@ bool diag_no_tail()
 }
 // PSK_SOFT_TRACE_LAUNCHES=1 (debugging a faulting kernel): in front of every launch the host waits for everything enqueued so far and
 // writes one line for the launch and one per channel of its list to stderr -- the last launch named in the log of a run that died is the
-// one that did it, with the shapes it was given.  (=2: the launch lines only.)  off: the launch's place in the lists; ~0u: the whole batch.
-hipError_t mark(const Round &r, hipStream_t st, const char *what, int S, int H, uint32_t off, uint32_t cnt, uint32_t tiles, uint32_t y_len,
-                uint32_t r_len)
+// one that did it, with the shapes it was given.  (=2: the launch lines only.)  trace_launch: the launch line, of every launch of the
+// library -- the rounds' (mark), the quality pass's, the gathers', the acquire pass's.
+hipError_t trace_launch(const psk_soft_handle *h, const char *what, int S, int H, uint32_t ch0, uint32_t cnt, uint64_t tiles, uint32_t y_len,
+                        uint32_t r_len, int slot, hipStream_t stream)
 {
-    if (!r.h->opt_trace)
+    if (!h->opt_trace)
         return hipSuccess;
     if (const hipError_t e = hipDeviceSynchronize())
         return e;
-    std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%u y_len=%u r_len=%u slot=%d stream=%p\n", what, S, H, r.ch0, cnt,
-                 tiles, y_len, r_len, r.slot, (void *)st);
-    for (uint32_t i = 0; i < cnt && r.h->opt_trace == 1; i++) {
+    std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, S, H, ch0, cnt,
+                 (unsigned long long)tiles, y_len, r_len, slot, (void *)stream);
+    std::fflush(stderr);
+    return hipSuccess;
+}
+// ... of a round's launch, and the channel lines behind it.  off: the launch's place in the lists; ~0u: the whole batch.
+hipError_t mark(const Round &r, hipStream_t st, const char *what, int S, int H, uint32_t off, uint32_t cnt, uint32_t tiles, uint32_t y_len,
+                uint32_t r_len)
+{
+    const hipError_t e = trace_launch(r.h, what, S, H, r.ch0, cnt, tiles, y_len, r_len, r.slot, st);
+    if (e != hipSuccess || r.h->opt_trace != 1)
+        return e;
+    for (uint32_t i = 0; i < cnt; i++) {
         const uint32_t bi = r.stamped || off == ~0u ? i : r.h_list[off + i];
         const psk::ChanPlan &p = r.plans[bi];
         if (off == ~0u && p.mode == psk::PLAN_SKIP)
@@ -1751,18 +1843,33 @@ psk_soft_status enqueue(Round &r)
     PSK_HIP(hipEventRecord(h->ev[r.slot], stream));
     return PSK_SOFT_OK;
 }
-// One pass of the control plane over a batch and the launches it asks for, phase by phase.  cont[i], pieces of a call the
-// library has cut (process_device_call): bit 0 = packet i continues the call of the packet before it (plan_call's `cont`), bit 1 = more
-// pieces of the call follow (no end-of-call wrap yet), bit 2 = the piece is cut where the reference does not rebuild its sums.
+// What a round is of: the whole call (cont == nullptr), or a piece of a call the library has cut (process_device_call) -- cont[i]: bit 0 =
+// packet i continues the call of the packet before it (plan_call's `cont`), bit 1 = more pieces of the call follow (no end-of-call wrap
+// yet), bit 2 = the piece is cut where the reference does not rebuild its sums.  of_split: the pieces are those of a mixed batch cut in time.
+struct Pieces {
+    const uint8_t *cont = nullptr;
+    bool of_split = false;
+};
+// What process_round decided about a whole call, next to its status: enqueued (or nothing to do); some channel's call is too long for one
+// piece -- the caller cuts it at the resync boundaries --; or the batch mixes window classes that cannot be resident together -- the caller
+// cuts every channel's call into `pieces` pieces in time and lets the classes run through them on their own streams, joined once at the
+// end of the call (process_device_call).  With the last two nothing is committed and nothing enqueued.
+struct Verdict {
+    enum { done, too_long, mixed } what = done;
+    int pieces = 0;
+};
+// One pass of the control plane over a batch and the launches it asks for, phase by phase.
 psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts, psk_soft_output_t *outs,
-                              void *stream_v, const uint8_t *cont)
+                              void *stream_v, const Pieces &pieces, Verdict *verdict)
 {
+    const uint8_t *const cont = pieces.cont;
+    *verdict = Verdict{};
     if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
     if (h->poisoned)
         return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: an earlier call failed inside HIP after its kernels were enqueued; the "
                                       "channel states are undefined -- destroy the handle (or import saved states into a new one)");
-    Round r{h, ch0, nch, pkts, outs, cont, stream_v ? (hipStream_t)stream_v : h->stream, h->slot, h->dry,
+    Round r{h, ch0, nch, pkts, outs, cont, pieces.of_split, stream_v ? (hipStream_t)stream_v : h->stream, h->slot, h->dry,
             (h->opt_qpsk_sign_map ? (uint32_t)psk::PLAN_QPSK_SIGN_MAP : 0u) | (h->opt_ties_in_place ? 0u : (uint32_t)psk::PLAN_TIES_HANDOVER), h->lim};
     PSK_TRY(take_slot(r));
     plan_stamped(r);
@@ -1771,7 +1878,7 @@ psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, 
         plan_each(r);
     }
     if (r.res.st == PSK_SOFT_OK && r.res.long_call && !cont) {
-        g_long_call = true;  // (nothing committed, nothing enqueued: the caller cuts the call into pieces)
+        verdict->what = Verdict::too_long;
         return PSK_SOFT_OK;
     }
     if (r.res.st != PSK_SOFT_OK)
@@ -1793,7 +1900,7 @@ psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, 
     bool cut = false;
     PSK_TRY(choose_schedule(r, &cut));
     if (cut) {
-        g_split_pieces = h->opt_split;
+        *verdict = Verdict{Verdict::mixed, h->opt_split};
         return PSK_SOFT_OK;
     }
     PSK_TRY(upload(r));
@@ -1812,7 +1919,6 @@ psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, 
     h->slot_stream[r.slot] = r.stream, h->slot_ch0[r.slot] = ch0, h->slot_nch[r.slot] = nch;
     return PSK_SOFT_OK;
 }
-#undef PSK_TRY
 }  // namespace
 
 extern "C" {
@@ -1966,19 +2072,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_state) (void)hipFree(h->d_state);
         if (h->d_ring) (void)hipFree(h->d_ring);
         if (h->d_yv) (void)hipFree(h->d_yv);
-        for (auto &q : h->qslot) {
-            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
-            if (q.h_desc) (void)hipHostFree(q.h_desc);
-            if (q.d_desc) (void)hipFree(q.d_desc);
-            if (q.d_part) (void)hipFree(q.d_part);
-        }
+        h->qpass.free();
         if (h->d_quality) (void)hipFree(h->d_quality);
-        for (auto &q : h->aslot) {
-            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
-            if (q.h_desc) (void)hipHostFree(q.h_desc);
-            if (q.d_desc) (void)hipFree(q.d_desc);
-            if (q.d_part) (void)hipFree(q.d_part);
-        }
+        h->apass.free();
         if (h->d_acquire) (void)hipFree(h->d_acquire);
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
@@ -1989,19 +2085,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
             if (q) (void)hipFree(q);
         if (h->pf.hint) (void)hipHostFree(h->pf.hint);
         if (h->tile_ev) (void)hipEventDestroy(h->tile_ev);
-        for (auto &cv : h->cvt) {
-            if (cv.ev) (void)hipEventSynchronize(cv.ev), (void)hipEventDestroy(cv.ev);
-            if (cv.buf) (void)hipFree(cv.buf);
-        }
-        for (auto &g : h->gat) {
-            if (g.ev) (void)hipEventSynchronize(g.ev), (void)hipEventDestroy(g.ev);
-            if (g.buf) (void)hipFree(g.buf);
-        }
-        for (auto &g : h->gdesc) {
-            if (g.ev) (void)hipEventSynchronize(g.ev), (void)hipEventDestroy(g.ev);
-            if (g.h_buf) (void)hipHostFree(g.h_buf);
-            if (g.d_buf) (void)hipFree(g.d_buf);
-        }
+        for (auto &cv : h->cvt) cv.free();
+        for (auto &g : h->gat) g.free();
+        for (auto &g : h->gdesc) g.free();
         if (h->d_tune_tab) (void)hipFree(h->d_tune_tab);
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
@@ -2100,23 +2186,15 @@ static psk_soft_status process_device_call(psk_soft_handle_t *h, uint32_t ch0, u
 {
     // (the ordinary call is planned as it is; the plan pass itself says when a channel's call is too long for one piece --
     // nothing is committed or enqueued then)
-    g_long_call = false;
-    g_split_pieces = 0;
+    Verdict verdict;
     {
-        const psk_soft_status st = process_round(h, ch0, nch, pkts, outs, stream_v, nullptr);
-        if (st != PSK_SOFT_OK || (!g_long_call && g_split_pieces < 2))
+        const psk_soft_status st = process_round(h, ch0, nch, pkts, outs, stream_v, Pieces{}, &verdict);
+        if (st != PSK_SOFT_OK || verdict.what == Verdict::done)
             return st;
-        g_long_call = false;
     }
-    // (a mixed batch cut in time, see process_round: every channel's call in `split` pieces of whole blocks; the side streams of
+    // (a mixed batch cut in time, see Verdict: every channel's call in `split` pieces of whole blocks; the side streams of
     // the rounds are joined once, behind the last)
-    const uint64_t split = g_split_pieces > 1 ? (uint64_t)g_split_pieces : 0;
-    g_split_pieces = 0;
-    struct SplitScope {
-        bool on;
-        explicit SplitScope(bool v) : on(v) { g_split_mode = v; }
-        ~SplitScope() { g_split_mode = false; }
-    } split_scope(split != 0);
+    const uint64_t split = verdict.what == Verdict::mixed ? (uint64_t)verdict.pieces : 0;
     std::vector<uint64_t> piece_cap(split ? nch : 0, ~0ull);  // symbols a piece of the channel's call may emit
 
     // ---- pieces ----
@@ -2183,7 +2261,7 @@ static psk_soft_status process_device_call(psk_soft_handle_t *h, uint32_t ch0, u
                 cont[i] |= 2u;
             more = more || left[i] != 0;
         }
-        const psk_soft_status st = process_round(h, ch0, nch, pk.data(), ou.data(), stream_v, cont.data());
+        const psk_soft_status st = process_round(h, ch0, nch, pk.data(), ou.data(), stream_v, Pieces{cont.data(), split != 0}, &verdict);
         if (st != PSK_SOFT_OK) {
             if (round > 0)
                 h->poisoned = true;  // (pieces of the call have run: the channels are in the middle of it)
@@ -2252,15 +2330,8 @@ static psk_soft_status quality_pass(psk_soft_handle_t *h, uint32_t ch0, uint32_t
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
     // (a deferred call's classes end on the side streams: the rows must be complete)
     PSK_HIP(deferred_join(h, stream));
-    QualitySlot &q = h->qslot[h->q_turn];
-    if (q.used)
-        PSK_HIP(hipEventSynchronize(q.ev));
-    if (!q.ev)
-        PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-    if (!q.h_desc)
-        PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(psk::QualityDesc) * (size_t)h->nch));
-    if (!q.d_desc)
-        PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(psk::QualityDesc) * (size_t)h->nch));
+    auto &q = h->qpass.next();
+    PSK_TRY(h->qpass.claim(q, h->nch));
     uint64_t n_seg = 0;
     uint32_t max_seg = 0;
     for (uint32_t i = 0; i < nch; i++) {
@@ -2294,38 +2365,18 @@ static psk_soft_status quality_pass(psk_soft_handle_t *h, uint32_t ch0, uint32_t
             max_seg = d.n_seg > max_seg ? d.n_seg : max_seg;
         }
     }
-    if (n_seg > q.part_cap) {
-        if (q.d_part) (void)hipFree(q.d_part);
-        q.d_part = nullptr;
-        q.part_cap = 0;
-        const size_t cap = (size_t)n_seg + (size_t)n_seg / 4u + 256u;
-        PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(psk::QualityPartial) * cap));
-        q.part_cap = cap;
-    }
-    // (the record of a channel is written by one call at a time: behind the passes of other streams over the same channels)
-    for (const QualitySlot &k : h->qslot)
-        if (&k != &q && k.used && k.stream != stream && k.ch0 < ch0 + nch && ch0 < k.ch0 + k.nch)
-            PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
-    PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(psk::QualityDesc) * (size_t)nch, hipMemcpyHostToDevice, stream));
-    q.used = true, q.stream = stream, q.ch0 = ch0, q.nch = nch;
-    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; `slot` is the call's last plan slot)
-    auto mark = [&](const char *what) -> hipError_t {
-        if (!h->opt_trace)
-            return hipSuccess;
-        if (const hipError_t e = hipDeviceSynchronize())
-            return e;
-        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%u y_len=%u r_len=%u slot=%d stream=%p\n", what, 0, 0, ch0, nch,
-                     (uint32_t)n_seg, 0u, 0u, (h->slot + kPlanSlots - 1) % kPlanSlots, (void *)stream);
-        std::fflush(stderr);
-        return hipSuccess;
+    PSK_TRY(h->qpass.grow(q, n_seg));
+    PSK_TRY(h->qpass.upload(q, ch0, nch, stream));
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: tiles = segments; `slot` is the call's last plan slot)
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_seg, 0, 0, (h->slot + kPlanSlots - 1) % kPlanSlots, stream); };
+    auto enqueue = [&]() -> psk_soft_status {
+        PSK_HIP(mark("quality_fold"));
+        PSK_HIP(psk::launch_quality_fold(q.d_desc, nch, max_seg, q.d_part, stream));
+        PSK_HIP(mark("quality_join"));
+        PSK_HIP(psk::launch_quality_join(q.d_desc, nch, q.d_part, h->d_quality, stream));
+        return PSK_SOFT_OK;
     };
-    PSK_HIP(mark("quality_fold"));
-    PSK_HIP(psk::launch_quality_fold(q.d_desc, nch, max_seg, q.d_part, stream));
-    PSK_HIP(mark("quality_join"));
-    PSK_HIP(psk::launch_quality_join(q.d_desc, nch, q.d_part, h->d_quality, stream));
-    PSK_HIP(hipEventRecord(q.ev, stream));
-    h->q_turn = (h->q_turn + 1) % kQualitySlots;
-    return PSK_SOFT_OK;
+    return h->qpass.finish(q, stream, enqueue());
 }
 
 // The public entry: the call, and with PSK_SOFT_OPT_QUALITY the reduction pass behind it.
@@ -2349,13 +2400,54 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
 }
 
 // ---- the gathers of a call with strided packets: psk_soft_process_device_tuned and psk_soft_acquire_device ----
+// the sample stride of packet i (sample_stride == NULL: every packet contiguous)
+static inline uint64_t stride_of(const uint64_t *sample_stride, uint32_t i) { return sample_stride ? sample_stride[i] : 1u; }
+
+// The refusals of a strided argument, for the entries that take one: a stride of 0; for a packet of a known format (what an entry does
+// with an unknown one is its own business) an extent that does not fit 64 bits, and -- `read`: the call reads the packet's samples --
+// data that do not start on a whole sample.  ch: the channel, s: its stride.
+struct StridedEntry {
+    const char *name, *misaligned;  // the entry in the messages about strides; its whole message about alignment
+};
+static const StridedEntry kTunedEntry = {"psk_soft_process_device_strided", "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4"};
+static const StridedEntry kAcquireEntry = {"psk_soft_acquire_device", "psk_soft_acquire_device: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4)"};
+static psk_soft_status strided_refusal(const StridedEntry &e, uint32_t ch, const psk_soft_packet_t &k, uint64_t s, bool read)
+{
+    char buf[160];
+    if (!s) {
+        std::snprintf(buf, sizeof buf, "%s: channel %u: a sample stride of 0", e.name, ch);
+        return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+    }
+    if (!psk::pkt_format_known(k.format))
+        return PSK_SOFT_OK;
+    const uint64_t sb = 2u * elem_bytes(k);
+    uint64_t pitch = 0, extent = 0;
+    if (__builtin_mul_overflow(s, sb, &pitch) || __builtin_mul_overflow(pitch, k.n_floats / 2u, &extent)) {
+        std::snprintf(buf, sizeof buf, "%s: channel %u: stride x sample size x samples does not fit 64 bits", e.name, ch);
+        return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+    }
+    if (read && reinterpret_cast<uintptr_t>(k.data) % sb)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, e.misaligned);
+    return PSK_SOFT_OK;
+}
+
+// tuned packets: the two phasor tables in device memory (once per handle)
+static psk_soft_status ensure_tune_tab(psk_soft_handle *h)
+{
+    if (h->d_tune_tab)
+        return PSK_SOFT_OK;
+    PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
+    PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
+    return PSK_SOFT_OK;
+}
+
 // What gather_stage leaves behind: where each packet's own-format row and float2 row of tuned samples lie in the scratch (nullptr:
 // the packet has none), and the scratch and descriptor slot it has claimed, whose events gather_release records behind whatever
 // the caller puts on the stream to read the rows.
 struct GatherStage {
     std::vector<const void *> row;
     std::vector<float *> tune_row;
-    GatherScratch *sc = nullptr;
+    StreamScratch *sc = nullptr;
     GatherDescSlot *ds = nullptr;  // (set once the descriptors are on the stream: from then on gather_release is owed)
 };
 
@@ -2369,7 +2461,6 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
                                     const uint64_t *sample_stride, const psk_soft_tune_t *tune, const std::vector<uint8_t> &gathered,
                                     const std::vector<uint8_t> &tuned, bool singles_in_place, hipStream_t stream, GatherStage &gs)
 {
-    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
     // (a column that gets neither a row nor a gather of its own when its run is too short for the tile kernel)
     auto direct = [&](uint32_t i) { return singles_in_place || tuned[i]; };
     uint32_t n_tune = 0;
@@ -2432,37 +2523,10 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
     // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
     PSK_HIP(deferred_join(h, stream));
-    GatherScratch *sc = nullptr;
-    for (auto &c : h->gat)
-        if (c.buf && c.stream == stream) {
-            sc = &c;
-            break;
-        }
-    if (!sc) {
-        sc = &h->gat[0];
-        for (auto &c : h->gat)
-            if (c.last_use < sc->last_use)
-                sc = &c;
-    }
-    if (!sc->ev)
-        PSK_HIP(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
-    if (sc->ev_used && sc->stream != stream)
-        PSK_HIP(hipStreamWaitEvent(stream, sc->ev, 0));
-    if (need > sc->cap) {  // (rare: grows to the largest call seen, plus a quarter; the one place that waits for the device)
-        PSK_HIP(hipDeviceSynchronize());
-        if (sc->buf) (void)hipFree(sc->buf);
-        sc->buf = nullptr;
-        sc->cap = 0;
-        const size_t cap = align_up(need + need / 4, 4096);
-        PSK_HIP(hipMalloc((void **)&sc->buf, cap));
-        sc->cap = cap;
-    }
-    sc->stream = stream;
-    sc->last_use = ++h->gat_calls;
-    if (n_tune && !h->d_tune_tab) {  // (once per handle)
-        PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
-        PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
-    }
+    StreamScratch *sc = nullptr;
+    PSK_TRY(claim_scratch(h->gat, &h->gat_calls, stream, need, nullptr, &sc));
+    if (n_tune)
+        PSK_TRY(ensure_tune_tab(h));
     GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
     h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
     if (!ds.ev)
@@ -2534,7 +2598,7 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
             d = psk::TuneDesc{};
             d.src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
             d.dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
-            d.stride = in_group[c] ? 1u : stride_of(c);
+            d.stride = in_group[c] ? 1u : stride_of(sample_stride, c);
             d.n = pkts[c].n_floats / 2u;
             d.phase = tune[c].phase, d.step = tune[c].step;
             d.format = pkts[c].format;
@@ -2545,17 +2609,8 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
     ds.used = true;  // (from here on the slot waits for its event, which gather_release records whatever happens)
     gs.sc = sc, gs.ds = &ds;
-    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; S = bytes of a complex sample, cnt = groups / singles covered)
-    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) -> hipError_t {
-        if (!h->opt_trace)
-            return hipSuccess;
-        if (const hipError_t e = hipDeviceSynchronize())
-            return e;
-        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, bytes, 0, ch0, cnt,
-                     (unsigned long long)tiles, 0u, 0u, h->slot, (void *)stream);
-        std::fflush(stderr);
-        return hipSuccess;
-    };
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: S = bytes of a complex sample, cnt = groups / singles covered)
+    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) { return trace_launch(h, what, bytes, 0, ch0, cnt, tiles, 0, 0, h->slot, stream); };
     const psk::GatherGroup *const dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
     const psk::GatherChan *const dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + off_cols);
     const psk::GatherSingle *const dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + off_singles);
@@ -2618,10 +2673,9 @@ psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0
     // that does not start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
     auto known = [](const psk_soft_packet_t &k) { return psk::pkt_format_known(k.format); };
     // (a strided packet the call reads: present, complex data, at least one sample)
-    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
     auto gathered = [&](uint32_t i) {
         const psk_soft_packet_t &k = pkts[i];
-        return k.present && stride_of(i) != 1 && k.sri_mode == 1 && k.n_floats >= 2 && k.data;
+        return k.present && stride_of(sample_stride, i) != 1 && k.sri_mode == 1 && k.n_floats >= 2 && k.data;
     };
     // (a packet the tune kernel reads: tuned, present, complex data, at least one sample, of a format the library knows)
     auto tuned = [&](uint32_t i) {
@@ -2634,36 +2688,22 @@ psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
-        const uint64_t s = stride_of(i);
-        if (s == 1 && tuned(i)) {
-            if (reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
-                return fail(PSK_SOFT_ERR_INVALID_ARG,
-                            "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
-            n_tune++;
-        }
-        char buf[160];
-        if (!s) {
-            std::snprintf(buf, sizeof buf, "psk_soft_process_device_strided: channel %u: a sample stride of 0", ch0 + i);
-            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-        }
-        if (s == 1)
+        const uint64_t s = stride_of(sample_stride, i);
+        if (s == 1) {  // (contiguous: the ordinary call's business, but for the packets the tune kernel reads)
+            if (tuned(i)) {
+                if (reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
+                    return fail(PSK_SOFT_ERR_INVALID_ARG, kTunedEntry.misaligned);
+                n_tune++;
+            }
             continue;
+        }
+        PSK_TRY(strided_refusal(kTunedEntry, ch0 + i, k, s, gathered(i)));
         if (!known(k)) {
             unknown = true;
             continue;
         }
-        const uint64_t sb = 2u * elem_bytes(k);
-        uint64_t pitch = 0, extent = 0;
-        if (__builtin_mul_overflow(s, sb, &pitch) || __builtin_mul_overflow(pitch, k.n_floats / 2u, &extent)) {
-            std::snprintf(buf, sizeof buf, "psk_soft_process_device_strided: channel %u: stride x sample size x samples does not fit 64 bits",
-                          ch0 + i);
-            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-        }
         if (!gathered(i))
             continue;
-        if (reinterpret_cast<uintptr_t>(k.data) % sb)
-            return fail(PSK_SOFT_ERR_INVALID_ARG,
-                        "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4");
         n_gather++;
         n_tune += tuned(i);
     }
@@ -2746,7 +2786,6 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
 {
     if (!h || !pkts || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_device: bad arguments");
-    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
     // (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
     auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
     // the refusals, before anything is enqueued or any record changes
@@ -2754,27 +2793,15 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
-        char buf[160];
-        const uint64_t s = stride_of(i);
-        if (!s) {
-            std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: a sample stride of 0", ch0 + i);
-            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-        }
+        PSK_TRY(strided_refusal(kAcquireEntry, ch0 + i, k, stride_of(sample_stride, i), looked_at(i)));
         if (!psk::pkt_format_known(k.format)) {
+            char buf[160];
             std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
                           ch0 + i, (unsigned)k.format);
             return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
         }
-        const uint64_t sb = 2u * elem_bytes(k);
-        uint64_t pitch = 0, extent = 0;
-        if (__builtin_mul_overflow(s, sb, &pitch) || __builtin_mul_overflow(pitch, k.n_floats / 2u, &extent)) {
-            std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: stride x sample size x samples does not fit 64 bits", ch0 + i);
-            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-        }
-        if (!looked_at(i))
-            continue;
-        if ((!k.data && !h->dry) || reinterpret_cast<uintptr_t>(k.data) % sb)
-            return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_device: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4)");
+        if (looked_at(i) && !k.data && !h->dry)
+            return fail(PSK_SOFT_ERR_INVALID_ARG, kAcquireEntry.misaligned);
     }
     if (h->dry) {
         for (uint32_t i = 0; i < nch; i++) {
@@ -2795,7 +2822,7 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
     GatherStage gs;
     {
         std::vector<uint8_t> is_gathered(nch), none(nch, 0);
-        for (uint32_t i = 0; i < nch; i++) is_gathered[i] = stride_of(i) != 1 && looked_at(i);
+        for (uint32_t i = 0; i < nch; i++) is_gathered[i] = stride_of(sample_stride, i) != 1 && looked_at(i);
         const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, is_gathered, none, true, stream, gs);
         if (!gs.ds) {
             if (st != PSK_SOFT_OK)
@@ -2810,17 +2837,9 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
 static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
                                        const uint64_t *sample_stride, const psk_soft_tune_t *tune, const GatherStage *gs, hipStream_t stream)
 {
-    auto stride_of = [&](uint32_t i) -> uint64_t { return sample_stride ? sample_stride[i] : 1u; };
     auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
-    AcquireSlot &q = h->aslot[h->a_turn];
-    if (q.used)
-        PSK_HIP(hipEventSynchronize(q.ev));
-    if (!q.ev)
-        PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-    if (!q.h_desc)
-        PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(psk::AcquireDesc) * (size_t)h->nch));
-    if (!q.d_desc)
-        PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(psk::AcquireDesc) * (size_t)h->nch));
+    auto &q = h->apass.next();
+    PSK_TRY(h->apass.claim(q, h->nch));
     uint64_t n_part = 0;
     uint32_t max_piece = 0;
     bool any_tuned = false;
@@ -2833,7 +2852,7 @@ static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_
         const psk_soft_packet_t &k = pkts[i];
         const bool row = gs && gs->row[i];
         d.src = row ? gs->row[i] : (const void *)k.data;
-        d.stride = row ? 1u : stride_of(i);
+        d.stride = row ? 1u : stride_of(sample_stride, i);
         d.n = k.n_floats / 2u;
         d.M = ctl_of(h, ch0 + i).props.constelationSize;
         d.format = k.format;
@@ -2851,36 +2870,12 @@ static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_
         n_part += pieces;
         max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
     }
-    if (n_part > q.part_cap) {
-        if (q.d_part) (void)hipFree(q.d_part);
-        q.d_part = nullptr;
-        q.part_cap = 0;
-        const size_t cap = (size_t)n_part + (size_t)n_part / 4u + 256u;
-        PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(psk::AcquirePartial) * cap));
-        q.part_cap = cap;
-    }
-    if (any_tuned && !h->d_tune_tab) {  // (once per handle)
-        PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
-        PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
-    }
-    // (the record of a channel is written by one call at a time: behind the joins of other streams over the same channels)
-    for (const AcquireSlot &k : h->aslot)
-        if (&k != &q && k.used && k.stream != stream && k.ch0 < ch0 + nch && ch0 < k.ch0 + k.nch)
-            PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
-    PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(psk::AcquireDesc) * (size_t)nch, hipMemcpyHostToDevice, stream));
-    q.used = true, q.stream = stream, q.ch0 = ch0, q.nch = nch;
-    h->a_turn = (h->a_turn + 1) % kAcquireSlots;
-    // (PSK_SOFT_TRACE_LAUNCHES: the lines of process_round's `mark`; cnt = covered channels, tiles = pieces)
-    auto mark = [&](const char *what) -> hipError_t {
-        if (!h->opt_trace)
-            return hipSuccess;
-        if (const hipError_t e = hipDeviceSynchronize())
-            return e;
-        std::fprintf(stderr, "[psk_soft] ok; next: %s S=%d H=%d ch0=%u cnt=%u tiles=%llu y_len=%u r_len=%u slot=%d stream=%p\n", what, 0, 0, ch0, nch,
-                     (unsigned long long)n_part, 0u, 0u, h->slot, (void *)stream);
-        std::fflush(stderr);
-        return hipSuccess;
-    };
+    PSK_TRY(h->apass.grow(q, n_part));
+    if (any_tuned)
+        PSK_TRY(ensure_tune_tab(h));
+    PSK_TRY(h->apass.upload(q, ch0, nch, stream));
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = covered channels, tiles = pieces)
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_part, 0, 0, h->slot, stream); };
     auto enqueue = [&]() -> psk_soft_status {
         PSK_HIP(mark("acquire_fold"));
         PSK_HIP(psk::launch_acquire_fold(q.d_desc, nch, max_piece, any_tuned ? h->d_tune_tab : nullptr, q.d_part, stream));
@@ -2888,17 +2883,7 @@ static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_
         PSK_HIP(psk::launch_acquire_join(q.d_desc, nch, q.d_part, h->d_acquire, stream));
         return PSK_SOFT_OK;
     };
-    const psk_soft_status st = enqueue();
-    // (the slot is free again behind whatever this call has put on the stream)
-    const std::string keep = g_last_error;
-    if (const hipError_t e = hipEventRecord(q.ev, stream)) {
-        (void)hipStreamSynchronize(stream);
-        q.used = false;
-        if (st == PSK_SOFT_OK)
-            return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
-    }
-    g_last_error = keep;
-    return st;
+    return h->apass.finish(q, stream, enqueue());
 }
 
 uint64_t psk_soft_acquire_bytes(void) { return sizeof(psk_soft_acquire_t); }
@@ -2915,9 +2900,7 @@ psk_soft_status psk_soft_get_acquire(psk_soft_handle_t *h, uint32_t ch0, uint32_
     const psk_soft_status st = psk_soft_synchronize(h);
     if (st != PSK_SOFT_OK)
         return st;
-    for (AcquireSlot &q : h->aslot)
-        if (q.used)
-            PSK_HIP(hipEventSynchronize(q.ev));
+    PSK_TRY(h->apass.wait());
     PSK_HIP(hipMemcpy(rec, h->d_acquire + ch0, sizeof(psk_soft_acquire_t) * nch, hipMemcpyDeviceToHost));
     return PSK_SOFT_OK;
 }
@@ -3334,10 +3317,7 @@ static psk_soft_status quality_wait(psk_soft_handle_t *h)
     const psk_soft_status st = psk_soft_synchronize(h);
     if (st != PSK_SOFT_OK)
         return st;
-    for (QualitySlot &q : h->qslot)
-        if (q.used)
-            PSK_HIP(hipEventSynchronize(q.ev));
-    return PSK_SOFT_OK;
+    return h->qpass.wait();
 }
 
 uint64_t psk_soft_quality_bytes(void) { return sizeof(psk_soft_quality_t); }
@@ -3606,3 +3586,4 @@ psk_soft_status psk_soft_peek(const psk_soft_handle_t *h, uint32_t ch, uint64_t 
 }
 
 }  // extern "C"
+#undef PSK_TRY

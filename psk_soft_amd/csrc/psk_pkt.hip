@@ -6,7 +6,7 @@
 // screened and exact tier (psk_fast_inst.hip with PSK_INST_PKT=cs16 | cs8 | cf16: the loads of psk_fast_loop.h convert as they
 // read), and of the reference-order kernel that redoes what they hand over (psk_kernels.hip, launch_seq_<format>).  Every other
 // such channel -- other window classes, calls of the time-tiled kernels, calls that emit nothing -- first goes through the kernel
-// below, which converts its packet into float2 rows of the handle's conversion scratch (psk_capi.cpp: CvtScratch,
+// below, which converts its packet into float2 rows of the handle's conversion scratch (psk_capi.cpp: StreamScratch,
 // psk_soft_handle::cvt); the plan points at the rows and everything after that is the float path.  The casts int16 -> float and
 // int8 -> float and the widening binary16 -> binary32 are exact (subnormal halves become normal floats, never flushed; a quiet NaN
 // keeps sign and payload), so such a packet gives bit for bit what the CF32 packet of the converted values gives, either way.

@@ -382,6 +382,38 @@ def test_zero_records_and_kept_records():
         h.close()
 
 
+# ---- 7b. the slot ring wraps with looks in flight -----------------------------------------------------------------------------------------
+
+def test_slot_ring_wraps_with_looks_in_flight_on_two_streams():
+    """Nine looks back to back -- one more than two turns of the four-slot ring -- over channels [0, 6) and [2, 8) in turn, on the
+    handle's stream and a second one in turn, nothing waited for until the records are read: every channel's record is the
+    model's for the last look that covered it, and byte for byte that of the same looks with a wait after each."""
+    C, K, M = 8, 9, 4
+    spans = [(0, 6) if k % 2 == 0 else (2, 6) for k in range(K)]
+    items = [[_carrier(21000 + 16 * k + c, M, 2400 + 8 * c + k) for c in range(lo, lo + n)] for k, (lo, n) in enumerate(spans)]
+    last = {c: max(k for k, (lo, n) in enumerate(spans) if lo <= c < lo + n) for c in range(C)}
+    second = _second_stream()
+
+    def run(in_flight):
+        h, keep = _handle([M] * C), []
+        try:
+            for k, (lo, n) in enumerate(spans):
+                look(h, items[k], ch0=lo, stream=None if k % 2 == 0 else second.value, keep=keep if in_flight else None)
+            return h.acquire_records()
+        finally:
+            for b in keep:
+                h.device_free(b)
+            h.close()
+
+    try:
+        flight, waited = run(True), run(False)
+        for c in range(C):
+            am.assert_record(flight[c], am.model_record(items[last[c]][c - spans[last[c]][0]], M), "channel %d, look %d" % (c, last[c]))
+        assert bytes(flight) == bytes(waited)
+    finally:
+        pl.load().hipStreamDestroy(second)
+
+
 # ---- 8. look, derive, tune, demodulate -------------------------------------------------------------------------------------------------
 
 def test_the_loop_the_look_is_for(oracle_mod):

@@ -30,11 +30,14 @@ def _fmt(x):
     return {np.dtype(np.int8): pl.FORMAT_CS8, np.dtype(np.int16): pl.FORMAT_CS16}.get(x.dtype, pl.FORMAT_CF32)
 
 
-def device_calls(h, calls, check=None, capfd=None, quality=False, nulls=None, skew=(), k0=0):
+def device_calls(h, calls, check=None, capfd=None, quality=False, nulls=None, skew=(), k0=0, sync_each=True, streams=None, spans=None):
     """psk_soft_process_device, one call per calls[k] (calls[k][c]: interleaved I/Q of channel c -- int8, int16 or float32 -- or
     None: no packet), device-resident packets, every (call, channel) with rows of its own on 128-byte boundaries (channels in
     `skew`: 8 bytes further on for soft, 4 for the others -- the alignment the ABI asks for and no more).  nulls: {channel:
     streams handed over as null pointers}.  After every call the host waits and, with `quality`, reads all records.
+    sync_each=False: the calls are issued back to back, the host waits once behind the last and reads the records once.
+    streams[k]: the raw hipStream_t of call k (None: the handle's own).  spans[k] = (ch0, nch): the channels call k covers
+    (default: all of them; calls[k][c] is None outside).
     Returns Run(got = {c: [dict of the four rows, or None without a packet]}, traces[k], recs[k][c] as bytes, nsym[k][c])."""
     from psk_soft_amd import lib as pl
 
@@ -61,29 +64,37 @@ def device_calls(h, calls, check=None, capfd=None, quality=False, nulls=None, sk
             h.upload(d_in + o[0], calls[k][c])
         h.synchronize()
         for k in range(K):
-            pk, out = (pl.Packet * C)(), (pl.Output * C)()
-            for c in range(C):
+            lo, n = spans[k] if spans else (0, C)
+            assert all(calls[k][c] is None for c in range(C) if not lo <= c < lo + n)
+            pk, out = (pl.Packet * n)(), (pl.Output * n)()
+            for c in range(lo, lo + n):
                 x = calls[k][c]
                 if x is None:
                     continue
                 cap, o = lay[k, c]
                 s8, s4 = (8, 4) if c in skew else (0, 0)
-                pk[c].data, pk[c].n_floats, pk[c].sri_xdelta, pk[c].sri_mode = d_in + o[0], x.size, 0.01, 1
-                pk[c].sriChanged, pk[c].present, pk[c].format = int(k + k0 == 0), 1, _fmt(x)
-                out[c].soft, out[c].phase, out[c].bits, out[c].sampleIndex = d_soft + o[1] + s8, d_phase + o[2] + s4, d_bits + o[3] + s4, d_sidx + o[4] + s4
+                p, q = pk[c - lo], out[c - lo]
+                p.data, p.n_floats, p.sri_xdelta, p.sri_mode = d_in + o[0], x.size, 0.01, 1
+                p.sriChanged, p.present, p.format = int(k + k0 == 0), 1, _fmt(x)
+                q.soft, q.phase, q.bits, q.sampleIndex = d_soft + o[1] + s8, d_phase + o[2] + s4, d_bits + o[3] + s4, d_sidx + o[4] + s4
                 for name in nulls.get(c, ()):
-                    setattr(out[c], STREAM_OF[name], None)
-                out[c].cap_symbols = cap
+                    setattr(q, STREAM_OF[name], None)
+                q.cap_symbols = cap
             if capfd:
                 capfd.readouterr()
-            h.process_device(0, pk, out)
+            h.process_device(lo, pk, out, streams[k] if streams else None)
             if capfd:
                 traces.append(parse_trace(capfd.readouterr().err))
+            if sync_each:
+                h.synchronize()
+                if quality:
+                    recs.append([bytes(q) for q in h.quality_records()])
+            outs.append({c: out[c - lo] for c in range(lo, lo + n)})
+            nsym.append([int(out[c - lo].n_symbols) if lo <= c < lo + n else 0 for c in range(C)])
+        if not sync_each:
             h.synchronize()
             if quality:
                 recs.append([bytes(q) for q in h.quality_records()])
-            outs.append(out)
-            nsym.append([int(out[c].n_symbols) for c in range(C)])
         got = {c: [] for c in check}
 
         def fetch(ptr, n, dt):
@@ -476,3 +487,65 @@ def test_lock_and_snr_order_channels_by_their_signal(oracle_mod, monkeypatch, ca
         snr = [x["snr_db"] for x in der if not math.isnan(x["snr_db"])]
         assert all(a > b for a, b in zip(snr, snr[1:])), (M, d, snr)
         assert (len(snr) == 0) if d else (len(snr) >= 2), (M, d, snr)
+
+
+# ---- 9. the slot ring wraps with calls in flight ---------------------------------------------------------------------------
+
+def wrapping_calls(seed, dtype=np.float32, spans=None):
+    """Nine calls of about 300 symbols a channel (QPSK, samplesPerBaud 8, numAvg 25, phaseAvg 50: less than three blocks, the
+    last one partial) on a handle of 8 channels -- one more than two turns of every four-slot ring.  The first, third, ...
+    cover channels [0, 6), the others [2, 8); they alternate between the handle's stream and a second one.
+    (spans: other channel ranges, one (ch0, nch) per call.)  dtype other than float32: int8 values cast to it.
+    Returns (props, calls, spans): calls[k][c] = the next samples of channel c's stream, None outside the call's span."""
+    S, C, K = 8, 8, 9
+    props = [dict(samplesPerBaud=S, constelationSize=4, numAvg=25, phaseAvg=50)] * C
+    spans = spans or [(0, 6) if k % 2 == 0 else (2, 6) for k in range(K)]
+    lens = [[S * 300 + 8 * c + k if lo <= c < lo + n else 0 for c in range(C)] for k, (lo, n) in enumerate(spans)]
+    raw = _synth(seed, [4] * C, S, [sum(lens[k][c] for k in range(K)) for c in range(C)])
+    if dtype != np.float32:
+        raw = [q8(x).astype(dtype) for x in raw]
+    calls, at = [], [0] * C
+    for k in range(K):
+        calls.append([raw[c][2 * at[c]:2 * (at[c] + lens[k][c])] if lens[k][c] else None for c in range(C)])
+        at = [at[c] + lens[k][c] for c in range(C)]
+    return props, calls, spans
+
+
+def test_slot_ring_wraps_with_calls_in_flight_on_two_streams(oracle_mod, monkeypatch, capfd):
+    """wrapping_calls back to back, no host wait between them, one psk_soft_synchronize at the end: the four streams of all nine
+    calls are the oracle's; the final record of every channel is that of the same calls with a wait after each; under the launch
+    trace nine quality_fold and nine quality_join lines are written."""
+    from psk_soft_amd import lib as pl
+    from tests.test_gpu_acquire import _second_stream
+
+    props, calls, spans = wrapping_calls(71000)
+    C, K = 8, len(calls)
+    second = _second_stream()
+    streams = [None if k % 2 == 0 else second.value for k in range(K)]
+
+    def run(sync_each, cf=None):
+        h = pl.Handle(C, device=0)
+        try:
+            h.configure(0, props)
+            h.set_option(pl.Handle.OPT_QUALITY, 1)
+            return device_calls(h, calls, None, cf, True, sync_each=sync_each, streams=streams, spans=spans)
+        finally:
+            h.close()
+
+    try:
+        monkeypatch.delenv("PSK_SOFT_TRACE_LAUNCHES", raising=False)
+        flight = run(False)
+        check_parity(oracle_mod, flight.got, lambda c: props[c], calls, "ring wrap in flight")
+        waited = run(True)
+        assert_same(flight.got, waited.got, "in flight against a wait after each call")
+        assert len(flight.recs) == 1 and len(waited.recs) == K
+        assert flight.recs[0] == waited.recs[-1], "final records differ from those of the run that waits after each call"
+        assert all(r != bytes(88) for r in flight.recs[0])
+        monkeypatch.setenv("PSK_SOFT_TRACE_LAUNCHES", "2")
+        traced = run(False, capfd)
+        lines = [t for per_call in traced.traces for t in per_call]
+        assert sum(t["what"] == "quality_fold" for t in lines) == K and sum(t["what"] == "quality_join" for t in lines) == K, lines
+        assert len({t["stream"] for t in lines if t["what"] == "quality_fold"}) == 2
+    finally:
+        monkeypatch.delenv("PSK_SOFT_TRACE_LAUNCHES", raising=False)
+        pl.load().hipStreamDestroy(second)

@@ -44,14 +44,15 @@ def gathers(lines):
     return len(t), sum(x["cnt"] for x in t), len(s), sum(x["cnt"] for x in s)
 
 
-def strided_run(h, calls, place, widths, capfd=None, check=None, sync_each=True, k0=0, odd=(), host_mem=False, stream=None):
+def strided_run(h, calls, place, widths, capfd=None, check=None, sync_each=True, k0=0, odd=(), host_mem=False, stream=None, spans=None):
     """psk_soft_process_device_strided with the packets of call k laid out as `place` says: place[c] = None -- channel c's
     packet is contiguous (stride 1) -- or (m, col): it is column `col` of matrix m, widths[m] complex samples wide, as many frames
     as its longest channel of that call, everything else in it poison.  calls[k][c]: interleaved I/Q (float32 / int16 / int8) or
     None (no packet); the channels of one matrix share a format within a call.  odd: channels whose n_floats counts one element
     more than the packet has (an odd last element is ignored: nothing is there to read).  host_mem: the source lies in
     psk_soft_host_alloc memory instead of device memory.  All sources are uploaded in front of the first call and compared with
-    what is there after the last.
+    what is there after the last.  stream: a raw hipStream_t, or a list of them, one per call (None: the handle's own).
+    spans[k] = (ch0, nch): the channels call k covers (default: all of them; calls[k][c] is None outside).
     Returns ({c: [per-call dicts]} for c in check, [launch lines of call k], [n_symbols[k][c]])."""
     from psk_soft_amd import lib as pl
 
@@ -109,28 +110,31 @@ def strided_run(h, calls, place, widths, capfd=None, check=None, sync_each=True,
     try:
         h.synchronize()
         for k in range(K):
-            pk, out = (pl.Packet * C)(), (pl.Output * C)()
-            strides = [1] * C
-            for c in range(C):
+            lo, n = spans[k] if spans else (0, C)
+            assert all(calls[k][c] is None for c in range(C) if not lo <= c < lo + n)
+            pk, out = (pl.Packet * n)(), (pl.Output * n)()
+            strides = [1] * n
+            for c in range(lo, lo + n):
                 x = calls[k][c]
                 if x is None:
-                    strides[c] = widths[place[c][0]] if place[c] is not None else 1
+                    strides[c - lo] = widths[place[c][0]] if place[c] is not None else 1
                     continue
                 cap, o = lay[k, c]
-                off, strides[c] = where[k, c]
-                pk[c].data, pk[c].n_floats, pk[c].sri_xdelta, pk[c].sri_mode = base + off, x.size + (1 if c in odd else 0), 0.01, 1
-                pk[c].sriChanged, pk[c].present, pk[c].format = int(k + k0 == 0), 1, _fmt(pl, x.dtype)
-                out[c].soft, out[c].phase, out[c].bits, out[c].sampleIndex = d_soft + o[0], d_phase + o[1], d_bits + o[2], d_sidx + o[3]
-                out[c].cap_symbols = cap
+                p, q = pk[c - lo], out[c - lo]
+                off, strides[c - lo] = where[k, c]
+                p.data, p.n_floats, p.sri_xdelta, p.sri_mode = base + off, x.size + (1 if c in odd else 0), 0.01, 1
+                p.sriChanged, p.present, p.format = int(k + k0 == 0), 1, _fmt(pl, x.dtype)
+                q.soft, q.phase, q.bits, q.sampleIndex = d_soft + o[0], d_phase + o[1], d_bits + o[2], d_sidx + o[3]
+                q.cap_symbols = cap
             if capfd:
                 capfd.readouterr()
-            h.process_device_strided(0, pk, strides, out, stream)
+            h.process_device_strided(lo, pk, strides, out, stream[k] if isinstance(stream, list) else stream)
             if capfd:
                 traces.append(parse_trace(capfd.readouterr().err))
             if sync_each:
                 h.synchronize()
-            outs.append(out)
-            nsym.append([int(out[c].n_symbols) for c in range(C)])
+            outs.append({c: out[c - lo] for c in range(lo, lo + n)})
+            nsym.append([int(out[c - lo].n_symbols) if lo <= c < lo + n else 0 for c in range(C)])
         if not sync_each:
             h.join()
         h.synchronize()
@@ -511,6 +515,34 @@ def test_zero_copy_from_page_locked_memory(oracle_mod, monkeypatch, capfd):
 
 
 # ---- 4. the machine-filling batch ------------------------------------------------------------------------------------------
+
+# ---- the descriptor ring wraps with calls in flight ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("cover", ["six of eight", "all eight"])
+def test_descriptor_ring_wraps_with_calls_in_flight_on_two_streams(oracle_mod, cover):
+    """The nine calls of test_gpu_quality.wrapping_calls, their packets columns of a frame-major matrix 8 wide, issued back to back
+    on the handle's stream and a second one in turn, one wait at the end: more calls than the gather descriptor ring has slots,
+    each stream with a gather scratch of its own, the channel ranges overlapping across the streams.  Bit for bit the oracle.
+    "six of eight": calls over channels [0, 6) and [2, 8) in turn, runs of six columns (below kGatherMinGroup: the plain strided
+    gather); "all eight": every call over all eight columns (the tile kernel)."""
+    from psk_soft_amd import lib as pl
+    from tests.test_gpu_acquire import _second_stream
+    from tests.test_gpu_quality import wrapping_calls
+
+    props, calls, spans = wrapping_calls(92000, np.int16, None if cover == "six of eight" else [(0, 8)] * 9)
+    C, K = 8, len(calls)
+    second = _second_stream()
+    h = pl.Handle(C, device=0)
+    try:
+        h.configure(0, props)
+        got, _, nsym = strided_run(h, calls, [(0, c) for c in range(C)], {0: 8}, sync_each=False,
+                                   stream=[None if k % 2 == 0 else second.value for k in range(K)], spans=spans)
+        assert all(nsym[k][c] > 250 for k, (lo, n) in enumerate(spans) for c in range(lo, lo + n))
+        check_parity(oracle_mod, got, lambda c: props[c], calls, "descriptor ring wrap, " + cover)
+    finally:
+        h.close()
+        pl.load().hipStreamDestroy(second)
+
 
 def _machine_child(path):
     """(a fresh process, torch initialised before the library) 4096 channels x 2^16 samples, frame-major and device-resident,
