@@ -117,7 +117,11 @@ typedef struct psk_soft_output {
     int16_t *bits;              /* bits_dataShort_out: log2(M) shorts per symbol        */
     float *phase;               /* phase_dataFloat_out: one per symbol                  */
     int16_t *sampleIndex;       /* sampleIndex_dataShort_out: one per symbol            */
-    uint64_t cap_symbols;       /* capacity of the buffers above, in symbols            */
+    uint64_t cap_symbols;       /* capacity of the buffers above, in symbols: soft holds 2 * cap floats, phase cap, bits
+                                   cap * log2(M) shorts, sampleIndex cap.  One rule on every entry: a call that emits more
+                                   symbols into the channel than cap_symbols is refused with PSK_SOFT_ERR_CAPACITY, before
+                                   anything is committed or enqueued, when ANY of the four pointers is non-null (bits or
+                                   sampleIndex alone count); exactly n_symbols is enough; all four null needs no room (0) */
     /* results */
     int32_t ret;                /* PSK_SOFT_NOOP / PSK_SOFT_NORMAL                      */
     uint64_t n_symbols;         /* symbols emitted: soft has 2*n, phase n                */

@@ -857,7 +857,7 @@ void plan_stamped(Round &r)
         if (k.n_floats != k0.n_floats || k.format != k0.format || k.present != k0.present || k.sri_mode != k0.sri_mode || k.sriChanged != k0.sriChanged ||
             k.inputQueueFlushed != k0.inputQueueFlushed || std::memcmp(&k.sri_xdelta, &k0.sri_xdelta, sizeof(double)) != 0)
             break;
-        if (p0.n_out > o.cap_symbols && (o.soft || o.phase))
+        if (p0.n_out > o.cap_symbols && (o.soft || o.bits || o.phase || o.sampleIndex))  // (plan_call's rule)
             break;
         psk::ChanPlan &p = r.plans[i];
         p = p0;
@@ -3077,7 +3077,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
             std::snprintf(buf, sizeof buf, "psk_soft_process_host: channel %u refused (status %d)", ch0 + i, (int)st);
             return fail(st, buf);
         }
-        if (o.n_symbols > outs[i].cap_symbols)
+        if (o.n_symbols > outs[i].cap_symbols && (outs[i].soft || outs[i].bits || outs[i].phase || outs[i].sampleIndex))  // (plan_call's rule)
             return fail(PSK_SOFT_ERR_CAPACITY, "psk_soft_process_host: output buffer too small");
         // every channel's rows start on a cache line: rows that straddle lines cost 6-8 % of the
         // kernel's streaming rate (tools/micro/placement_probe.hip)

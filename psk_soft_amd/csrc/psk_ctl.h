@@ -380,7 +380,9 @@ inline psk_soft_status plan_call(ChanCtl &c, const Limits &lim, const psk_soft_p
     out.n_sampleIndex = (S > 1) ? n_out : 0;
     if (n_out && bpb == 0)
         out.n_warn += (int32_t)(n_out > 0x7fffffff ? 0x7fffffff : n_out);  // :565-566, one per symbol
-    if (n_out > out.cap_symbols && plan.mode != PLAN_SKIP && (out.soft || out.phase))
+    // (one rule for every entry: cap_symbols is the capacity of every row the channel has -- a row of bits or sampleIndex alone is
+    // a row like the others; a channel without rows needs no room)
+    if (n_out > out.cap_symbols && plan.mode != PLAN_SKIP && (out.soft || out.bits || out.phase || out.sampleIndex))
         return PSK_SOFT_ERR_CAPACITY;
     return PSK_SOFT_OK;
 }

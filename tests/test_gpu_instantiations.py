@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import instantiation_census as ic
+from tests import row_guards as rg
 from tests.test_gpu_cs16_schedules import KEYS, parse_trace, untraced_then_traced
 from tests.test_gpu_parity import assert_parity
 
@@ -52,8 +53,12 @@ def _wrong_stats(row, k, st):
     return "call %d (%d blocks): %s" % (k, row.blocks()[k], {key: v for key, v in st.items() if v})
 
 
-def run_rows(oracle_mod, monkeypatch, capfd, rows):
-    """The rows as one batch of one handle, untraced and traced; returns {row name: [what is wrong with it]} (empty: nothing)."""
+def run_rows(oracle_mod, monkeypatch, capfd, rows, guarded=False):
+    """The rows as one batch of one handle, untraced and traced; returns {row name: [what is wrong with it]} (empty: nothing).
+    guarded: the calls go through psk_soft_process_device on rows of exactly n_symbols between guard words (tests/row_guards.py)
+    instead of psk_soft_process_host, and a changed guard or packet byte is one more thing wrong with a row; a third handle
+    then takes the same calls with the rows cycling over the sets of absent streams (row_guards.NULL_SETS): the streams it has
+    pointers for, its statistics and its state blobs must be the first handle's."""
     from psk_soft_amd import lib as pl
 
     rows = [r for r in rows if r.name not in UNREACHABLE]
@@ -62,33 +67,68 @@ def run_rows(oracle_mod, monkeypatch, capfd, rows):
     for r in rows:
         assert r.env == rows[0].env and r.time_tiled == rows[0].time_tiled
     env.update(rows[0].env)
+    window = max(r.props["samplesPerBaud"] * r.props["numAvg"] for r in rows) + 64
+    overruns, blobs = [], []  # (the findings and the state blobs of every handle)
 
-    def body(h, cap):
+    def body(h, cap, absent=None):
         h.configure(0, [r.props for r in rows])
         if rows[0].time_tiled is not None:
             h.set_option(pl.Handle.OPT_TIME_TILED, rows[0].time_tiled)
+        if guarded:
+            planner, dev = rg.Planner(n, max_window_samples=window, max_phase_avg=512), rg.DeviceRows(h)
+            planner.h.configure(0, [r.props for r in rows])
         got, traces, stats = {c: [] for c in range(n)}, [], []
-        for k in range(3):
-            if cap:
-                cap.readouterr()
-            res = h.process_host(0, [dict(data=r.packets[k], xdelta=0.01, sriChanged=(k == 0)) for r in rows])
-            if cap:
-                traces.append(parse_trace(cap.readouterr().err))
-            stats.append(h.channel_stats())
-            for c in range(n):
-                got[c].append({key: res[c][key] for key in KEYS})
+        try:
+            for k in range(3):
+                if guarded:
+                    packets = [r.packets[k] for r in rows]
+                    lay = rg.Layout(planner.counts(0, packets, k == 0), absent=absent, packets=packets, call=k)
+                if cap:
+                    cap.readouterr()
+                if guarded:
+                    res, found, _ = dev.run(lay, 0, sri_changed=(k == 0))
+                    overruns.extend(found)
+                else:
+                    res = h.process_host(0, [dict(data=r.packets[k], xdelta=0.01, sriChanged=(k == 0)) for r in rows])
+                if cap:
+                    traces.append(parse_trace(cap.readouterr().err))
+                stats.append(h.channel_stats())
+                for c in range(n):
+                    got[c].append({key: res[c][key] for key in KEYS})
+            if guarded:
+                blobs.append([h.export_state(c) for c in range(n)])
+        finally:
+            if guarded:
+                dev.close()
+                planner.h.close()
         return got, traces, stats
 
     t0 = time.perf_counter()
     ref = [ic.oracle_calls(oracle_mod, r) for r in rows]
     t1 = time.perf_counter()
-    window = max(r.props["samplesPerBaud"] * r.props["numAvg"] for r in rows) + 64
     (got, _, stats), (_, traces, stats_traced) = untraced_then_traced(monkeypatch, capfd, env, n, body, max_window_samples=window,
                                                                        max_phase_avg=512)
+    sets = [rg.NULL_SETS[c % len(rg.NULL_SETS)] for c in range(n)]
+    if guarded:
+        h = pl.Handle(n, device=0, max_window_samples=window, max_phase_avg=512)  # (under `env` still)
+        try:
+            got_part, _, stats_part = body(h, None, sets)
+        finally:
+            h.close()
     t2 = time.perf_counter()
     wrong = {}
     for c, r in enumerate(rows):
         w = []
+        if guarded:
+            for k in range(3):
+                for key in KEYS:
+                    x = got_part[c][k][key]
+                    if (x is None) != (key in sets[c]) or (x is not None and x.tobytes() != got[c][k][key].tobytes()):
+                        w.append("absent streams %s: call %d, %s is not the stream of the call with all rows" % (list(sets[c]), k, key))
+                if stats_part[k][c] != stats[k][c]:
+                    w.append("absent streams %s: the statistics of call %d differ" % (list(sets[c]), k))
+            if blobs[2][c] != blobs[0][c]:
+                w.append("absent streams %s: the state blob differs from the one after the calls with all rows" % list(sets[c]))
         for k in range(3):
             try:
                 assert_parity(got[c][k], ref[c][k], "call %d" % k)
@@ -103,9 +143,10 @@ def run_rows(oracle_mod, monkeypatch, capfd, rows):
                 w.append("trace: call %d has no '%s' S=%d H=%d" % (k, LINE[r.path], r.S, H))
             if r.path == "format_settle" and any(t["what"].endswith("_convert") for t in traces[k]):
                 w.append("trace: call %d converts packets in front of the kernels" % k)
+        w += ["guards: " + f["message"] for f in overruns if f["channel"] == c or (c == 0 and f["channel"] is None)]
         if w:
             wrong[r.name] = w
-    print("%s: %d rows, oracle %.2f s, two handles x three calls %.2f s, %d rows wrong" % (rows[0].path, n, t1 - t0, t2 - t1, len(wrong)))
+    print("%s: %d rows, oracle %.2f s, %s handles x three calls %.2f s, %d rows wrong" % (rows[0].path, n, t1 - t0, "three" if guarded else "two", t2 - t1, len(wrong)))
     for name, w in wrong.items():
         print("  %s %s\n    %s" % (name, next(r.props for r in rows if r.name == name), "\n    ".join(w)))
     return wrong
@@ -148,6 +189,17 @@ def test_tile_front(oracle_mod, monkeypatch, capfd):
     assert not run_rows(oracle_mod, monkeypatch, capfd, ic.rows("tile_front"))
 
 
+def run_child_with_reread_0(test_file, child_test):
+    """`child_test` of `test_file` in a fresh process started with PSK_SOFT_REREAD=0; it must pass there, not skip"""
+    env = dict(os.environ, PSK_SOFT_REREAD="0")
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [
+        "-m", "pytest", test_file, "-k", child_test, "-m", "gpu", "-q", "-rA", "-p", "no:cacheprovider"]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, timeout=120, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    print(r.stdout[-4000:])
+    assert r.returncode == 0, "the child ended with status %d" % r.returncode
+    assert "1 passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], r.stdout[-500:]
+
+
 def test_settle_in_place_h8_child(oracle_mod, monkeypatch, capfd):
     """The 15 H8_E0 units (the body of test_settle_in_place_h8, which starts it in a process of its own)."""
     if os.environ.get("PSK_SOFT_REREAD") != "0":
@@ -158,10 +210,4 @@ def test_settle_in_place_h8_child(oracle_mod, monkeypatch, capfd):
 def test_settle_in_place_h8():
     """psk_fast_S{2..16}_H8_E0: the H 0 rows over again in a fresh process with PSK_SOFT_REREAD=0 (launch_fast reads the
     variable once per process).  This process does not touch the GPU here, whatever becomes of the child."""
-    env = dict(os.environ, PSK_SOFT_REREAD="0")
-    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [
-        "-m", "pytest", os.path.abspath(__file__), "-k", "test_settle_in_place_h8_child", "-m", "gpu", "-q", "-rA", "-p", "no:cacheprovider"]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, timeout=120, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0, "the child ended with status %d" % r.returncode
-    assert "1 passed" in r.stdout and "skipped" not in r.stdout.splitlines()[-1], r.stdout[-500:]
+    run_child_with_reread_0(os.path.abspath(__file__), "test_settle_in_place_h8_child")
