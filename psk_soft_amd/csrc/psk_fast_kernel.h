@@ -3,6 +3,8 @@
 #ifndef PSK_FAST_KERNEL_H
 #define PSK_FAST_KERNEL_H
 
+#include <mutex>
+
 #include "psk_fast_loop.h"
 
 namespace psk {
@@ -285,9 +287,13 @@ __global__ __launch_bounds__(64, ((HV == 0 && SV <= 5 && !EXACT) ? 4 : (HV == 0 
         float *yvs, uint32_t fit_cap, uint32_t y_len, uint32_t r_len, hipStream_t stream
 
 // Dynamic LDS beyond the 64 KiB a kernel gets by default (a phase ring for phaseAvg in the thousands) has to be asked
-// for, per kernel, device and size; LdsGrant is the kernel's own record of what it has asked for so far.
+// for, per kernel, device and size; LdsGrant is the kernel's own record of what it has asked for so far.  The record is shared
+// by every handle of the process (a function-local static per kernel), and handles are serviced from threads of their own: the
+// lock is held across the compare, the call and the update, so that a smaller request can never be set behind a larger one that
+// the record already shows.  Grants of 64 KiB or less return in front of it.
 struct LdsGrant {
     size_t bytes[32] = {};  // per device
+    std::mutex lock;
 };
 inline hipError_t lds_grant(const void *kernel, size_t bytes, LdsGrant &granted)
 {
@@ -296,6 +302,7 @@ inline hipError_t lds_grant(const void *kernel, size_t bytes, LdsGrant &granted)
     int dev = 0;
     if (const hipError_t e = hipGetDevice(&dev))
         return e;
+    std::lock_guard<std::mutex> hold(granted.lock);
     size_t &have = granted.bytes[dev & 31];
     if (bytes <= have)
         return hipSuccess;

@@ -21,6 +21,8 @@ struct Time {
 };
 
 // dataFloat_in (T = float), dataShort_in (T = short: complex int16 packets) or dataChar_in (T = char: complex int8 packets)
+// (live: the dataTransfer objects of this port that exist, queued or handed out by getPacket and not yet deleted -- the component
+// owns what it takes, and psk_harness_live_packets shows a packet it forgot)
 template <class Sample>
 struct InPort {
     struct dataTransfer {
@@ -31,8 +33,17 @@ struct InPort {
         std::string streamID;
         bool sriChanged;
         bool inputQueueFlushed;
+        explicit dataTransfer(int *live_) : live(live_) { ++*live; }
+        ~dataTransfer() { --*live; }
+
+      private:
+        int *live;
+        dataTransfer(const dataTransfer &);
+        dataTransfer &operator=(const dataTransfer &);
     };
     std::deque<dataTransfer *> q;
+    int live;
+    InPort() : live(0) {}
     dataTransfer *getPacket(float)
     {
         if (q.empty())
@@ -139,7 +150,7 @@ template <class T>
 void push_packet(InPort<T> &in, const T *data, size_t n, double xdelta, int mode, int sriChanged, int flushed, int eos,
                  const char *streamID, double twsec)
 {
-    typename InPort<T>::dataTransfer *p = new typename InPort<T>::dataTransfer();
+    typename InPort<T>::dataTransfer *p = new typename InPort<T>::dataTransfer(&in.live);
     p->dataBuffer.assign(data, data + n);
     p->SRI.xdelta = xdelta;
     p->SRI.mode = mode;
@@ -151,6 +162,20 @@ void push_packet(InPort<T> &in, const T *data, size_t n, double xdelta, int mode
     p->sriChanged = sriChanged != 0;
     p->inputQueueFlushed = flushed != 0;
     in.q.push_back(p);
+}
+
+template <class C>
+long get_prop(const C &c, int id)
+{
+    switch (id) {
+    case 0: return c.samplesPerBaud;
+    case 1: return (long)c.numAvg;
+    case 2: return c.constelationSize;
+    case 3: return c.phaseAvg;
+    case 4: return c.differentialDecoding ? 1 : 0;
+    case 5: return c.resetState ? 1 : 0;
+    }
+    return -1;
 }
 
 }  // namespace
@@ -297,6 +322,19 @@ size_t psk_harness_port_sri(void *hv, int port, double *xdelta, int *mode, size_
 }
 int psk_harness_last_eos(void *hv) { return ((Harness *)hv)->soft.last_eos ? 1 : 0; }
 const char *psk_harness_last_stream(void *hv) { return ((Harness *)hv)->soft.last_stream.c_str(); }
+// dataTransfer objects of the input port that exist: the queued ones, and any that a serviceFunction() took and did not delete
+int psk_harness_live_packets(void *hv)
+{
+    Harness *h = (Harness *)hv;
+    return h->in.live + h->in_s.live + h->in_c.live;
+}
+// a property as the component holds it now (resetState: as the last serviceFunction() left it).  ids as psk_harness_configure
+long psk_harness_property(void *hv, int id)
+{
+    Harness *h = (Harness *)hv;
+    return h->comp ? get_prop(*h->comp, id) : h->comp_s ? get_prop(*h->comp_s, id) : get_prop(*h->comp_c, id);
+}
+// the component's library handle (a psk_soft_handle_t *, owned by the component): psk_soft_peek, psk_soft_get_channel_stats ...
 void *psk_harness_handle(void *hv)
 {
     Harness *h = (Harness *)hv;

@@ -89,7 +89,12 @@ class component {
         transfer_t *tmp = dataFloat_in->getPacket(BLOCKING);
         if (!tmp)  // cpp/psk_soft.cpp:350-352
             return NOOP;
-        push_properties();  // numAvg / differentialDecoding / resetState have no listener (:374-378)
+        try {
+            push_properties();  // numAvg / differentialDecoding / resetState have no listener (:374-378)
+        } catch (...) {
+            delete tmp;  // (a refused property, numAvg past the window: the packet is dropped, not leaked)
+            throw;
+        }
 
         psk_soft_packet_t pkt;
         pkt.data = tmp->dataBuffer.empty() ? 0 : reinterpret_cast<const float *>(&tmp->dataBuffer[0]);
@@ -119,10 +124,14 @@ class component {
             throw std::runtime_error(msg);
         }
         warnings += o.n_warn;
-        resetState = false;  // consumed by the library (:365-372); inputQueueFlushed sets and clears it there
+        // resetState is the library's after the call: cleared where the call did the three resets (:365-372), still set where a
+        // real-data packet returned in front of them (:359-363) -- a flushed one has set it there (:353-357) --, so that the next
+        // push_properties() hands it back and the resets happen at the next complex packet, as in the reference
         psk_soft_props_t now;
-        if (psk_soft_query(handle_, 0, &now) == PSK_SOFT_OK)
+        if (psk_soft_query(handle_, 0, &now) == PSK_SOFT_OK) {
             pushed_ = now;
+            resetState = now.resetState != 0;
+        }
 
         if (o.sri_pushed) {  // cpp/psk_soft.cpp:399-404
             tmp->SRI.xdelta = o.sri_soft_xdelta;

@@ -414,10 +414,24 @@ class Handle:
         h = ctypes.c_void_p()
         _check(L.psk_soft_create(int(device), self.n_channels, ctypes.byref(lim), ctypes.byref(h)))
         self._h = h
+        self._owned = True
+
+    @classmethod
+    def borrow(cls, pointer, n_channels, device=None):
+        """A Handle around a psk_soft_handle_t that somebody else owns (the component of psk_soft_amd/sandbox.py): every method
+        works on it, close() only lets go of the pointer.  Valid for as long as the owner keeps the handle."""
+        h = cls.__new__(cls)
+        h._L = load()
+        h.n_channels = int(n_channels)
+        h.device = device
+        h._h = ctypes.c_void_p(pointer)
+        h._owned = False
+        return h
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.psk_soft_destroy(self._h)
+            if self._owned:
+                self._L.psk_soft_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -10,6 +10,8 @@ import os
 
 import numpy as np
 
+from . import lib as _pl
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PATH = os.path.join(_HERE, "libpsk_soft_host_harness.so")
 PROP_IDS = {"samplesPerBaud": 0, "numAvg": 1, "constelationSize": 2, "phaseAvg": 3, "differentialDecoding": 4, "resetState": 5}
@@ -54,6 +56,11 @@ def _load():
         L.psk_harness_last_eos.argtypes = [vp]
         L.psk_harness_last_stream.argtypes = [vp]
         L.psk_harness_last_stream.restype = ctypes.c_char_p
+        L.psk_harness_live_packets.argtypes = [vp]
+        L.psk_harness_property.argtypes = [vp, ctypes.c_int]
+        L.psk_harness_property.restype = ctypes.c_long
+        L.psk_harness_handle.argtypes = [vp]
+        L.psk_harness_handle.restype = vp
         _lib = L
     return _lib
 
@@ -76,8 +83,7 @@ class Component:
         object.__setattr__(self, "_h", ctypes.c_void_p(h))
         object.__setattr__(self, "_short", input == "short")
         object.__setattr__(self, "_char", input == "char")
-        object.__setattr__(self, "_vals", dict(samplesPerBaud=10, numAvg=100, constelationSize=4, phaseAvg=50,
-                                               differentialDecoding=0, resetState=0))
+        object.__setattr__(self, "_device", int(device))
 
     def close(self):
         if self.__dict__.get("_h"):
@@ -95,14 +101,22 @@ class Component:
             rc = _load().psk_harness_configure(self._h, PROP_IDS[name], int(value))
             if rc:
                 raise RuntimeError(_load().psk_harness_error(self._h).decode())
-            self._vals[name] = int(value)
         else:
             object.__setattr__(self, name, value)
 
     def __getattr__(self, name):
-        if name in PROP_IDS:
-            return self._vals[name]
+        if name in PROP_IDS:  # as the component holds it: resetState is what the last service() left
+            return int(_load().psk_harness_property(self._h, PROP_IDS[name]))
         raise AttributeError(name)
+
+    def handle(self):
+        """The component's own library handle (no copy; valid until close())."""
+        return _pl.Handle.borrow(_load().psk_harness_handle(self._h), 1, self._device)
+
+    @property
+    def live_packets(self):
+        """dataTransfer objects of the input port that exist: queued, or taken by a service() and not deleted."""
+        return _load().psk_harness_live_packets(self._h)
 
     def push(self, data, sampleRate=None, xdelta=None, complexData=True, sriChanged=False, inputQueueFlushed=False,
              EOS=False, streamID="stream", twsec=0.0):
