@@ -287,6 +287,91 @@ uint64_t psk_soft_tune_step(double cycles_per_sample);
 uint64_t psk_soft_tune_advance(uint64_t phase, uint64_t step, uint64_t n_complex);
 psk_soft_status psk_soft_tune_apply(const psk_soft_tune_t *tune, const float *in, uint64_t n_complex, float *out);
 
+/* ---- resampled packets: a fractional resampler per packet, applied on the GPU in front of the demodulator --------------------
+ * samplesPerBaud is an integer (the reference's ushort property): the per-symbol loop of serviceFunction() steps a whole number
+ * of samples per symbol.  A channelizer hands every bin the same sample rate, and a signal's symbol rate almost never divides
+ * it; QPSK at 8.37 samples a symbol demodulated with samplesPerBaud 8 is lost, not degraded.  A resampled packet is brought to
+ * an integer number of samples per symbol before anything else looks at it: `step` input samples per output sample.
+ *
+ * The definition (host and device alike).  pos and step are in input samples x 2^32.
+ *   Input samples.  Sample k of the packet is converted to float exactly, as its format defines; if the packet is also tuned it
+ *     is multiplied by the NCO exactly as "tuned packets" (above) defines, k counted from the packet's sample 0.  Call the result
+ *     s[k], k = 0 .. n-1, n = n_floats / 2.  s[-3], s[-2], s[-1] are the channel's HISTORY: the last three s values in front of
+ *     this packet, already tuned, oldest first; zeros with PSK_SOFT_RS_RESTART.
+ *   Output instants.  t_m = pos + m * step for m = 0, 1, .. while t_m < n * 2^32; n_out is the count of those m.
+ *   Per output:  i = t_m >> 32,  mu = (float)((t_m & 0xffffffff) >> 8) * 0x1p-24f  (the conversion is exact), then
+ *       a = mu, b = mu - 1, c = mu - 2, d = mu + 1
+ *       w0 = ((a*b)*c) * (float)(-1.0/6.0)     w1 = ((d*b)*c) * 0.5f
+ *       w2 = ((d*a)*c) * -0.5f                 w3 = ((d*a)*b) * (float)(1.0/6.0)
+ *       y  = ((w0*s[i-3] + w1*s[i-2]) + w2*s[i-1]) + w3*s[i]                  (re and im separately)
+ *     every operation float32, rounded once, no fused multiply-add, denormals kept.
+ *   This is the cubic Lagrange polynomial through four consecutive samples, evaluated between s[i-2] and s[i-1]: a pure delay
+ *   of TWO input samples, which is what lets a packet be resampled without its successor.  At mu = 0 the result is s[i-2]:
+ *   step = 2^32, pos = 0 returns the stream delayed by two samples, bit for bit (the weights are -0, 1, +0, -0: only the sign of
+ *   a zero sample can change, with its neighbours' signs).
+ *   After the packet.  The new history is the last three of (old history || s[0 .. n-1]); the next packet's position is
+ *     pos + n_out * step - n * 2^32, always below step (psk_soft_resample_advance).
+ * The result of the call is bit for bit what the contiguous PSK_SOFT_FORMAT_CF32 packet holding y[0 .. n_out-1] gives, with
+ * sri_xdelta * ((double)step * 0x1p-32) as its sri_xdelta: all four streams, counts, SRI fields, warnings, statistics and quality
+ * records, under every schedule and option.  That contract covers finite y; with non-finite samples the formula above is still
+ * what runs, and which NaN comes out is unspecified.
+ * THERE IS NO ANTI-ALIAS FILTER.  The signal must be oversampled (as a signal at several samples per symbol is) and step must
+ * stay near 1 -- the use case is a sample rate a few percent to a few tens of percent off an integer number of samples per
+ * symbol.  Size the output rows with psk_soft_output_capacity(h, ch, n_out), n_out from psk_soft_resample_count(). */
+enum { PSK_SOFT_RS_RESTART = 1 };
+typedef struct psk_soft_resample {
+    uint64_t pos;     /* position of the packet's first output sample, in input samples x 2^32, counted from the packet's sample 0 */
+    uint64_t step;    /* input samples per output sample x 2^32; 0 = this packet is not resampled (pos, flags ignored)            */
+    uint32_t flags;   /* PSK_SOFT_RS_RESTART: the history in front of the packet is three zero samples                            */
+    uint32_t pad;     /* zero */
+} psk_soft_resample_t;   /* 24 bytes */
+
+/* psk_soft_process_device_tuned with resample[i] applied to packet i.  resample == NULL is psk_soft_process_device_tuned: the
+ * same code path; a packet with step == 0 takes exactly the path it takes there, the in-place builds of the integer formats
+ * included, and costs no extra launch.  A packet that is absent, has sri_mode != 1 or has no samples is left to the ordinary
+ * call (a NOOP or a warning, as before) and the channel's history does not change.  One call may mix resampled and
+ * not-resampled packets, tuned or not, strides and formats.
+ * Refused with PSK_SOFT_ERR_INVALID_ARG before anything is planned, committed or enqueued, on a present packet with step != 0:
+ * a step outside [2^31, 2^33], pos > 2^33, n_floats / 2 >= 2^30, a non-zero pad, unknown flag bits; and whatever
+ * psk_soft_process_device_strided refuses.
+ * How: every resampled packet gets a float2 row of n_out samples (128-byte aligned) in the gather scratch, and ONE more launch
+ * on `stream` behind the gathers writes the rows; the ordinary call runs on them as on CF32 packets of n_out samples with the
+ * scaled sri_xdelta.  A resampled packet that is also tuned is tuned inside that launch (no tune row, no second pass); tuned-only
+ * packets of the call still go through the tune pass.  A strided packet in a run the tiled transpose takes (at least 8 adjacent
+ * columns) is read from its gathered row, any other where it lies.  Scratch, descriptor slots, events and the deferred-join
+ * rule are those of psk_soft_process_device_strided.
+ * History: device memory the handle owns, two slots of three float2 per channel, allocated at the first resampled call.  A
+ * launch reads the channel's current slot and writes the other; the slots change roles only when the whole call returned
+ * PSK_SOFT_OK, so a refused call (PSK_SOFT_ERR_CAPACITY, PSK_SOFT_ERR_LIMIT, ..) changes nothing a later call can see.  The
+ * history is not part of the state blob (psk_soft_state_bytes is unchanged): checkpoint it with the two calls below.
+ * A control-plane-only handle checks the arguments, then plans and counts on n_out and the scaled sri_xdelta; its history stays
+ * zero.  No host-pointer counterpart; psk_soft_acquire_device does not resample. */
+psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
+                                                  const psk_soft_packet_t *pkts /* [nch] */,
+                                                  const uint64_t *sample_stride /* [nch], or NULL */,
+                                                  const psk_soft_tune_t *tune /* [nch], or NULL */,
+                                                  const psk_soft_resample_t *resample /* [nch], or NULL */,
+                                                  psk_soft_output_t *outs /* [nch] */, void *stream);
+/* the history of channel ch, three (re, im) pairs, oldest first.  _get waits for the last resampled call's pass, as
+ * psk_soft_get_quality waits for its own; _set replaces it (continue a checkpointed stream, tests). */
+psk_soft_status psk_soft_resample_get_history(psk_soft_handle_t *h, uint32_t ch, float *out /* [6] */);
+psk_soft_status psk_soft_resample_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in /* [6] */);
+
+/* Host only, pure.
+ * psk_soft_resample_step: the step word of `in_per_out` input samples per output sample, (uint64_t)(r * 2^32), truncated; 0 for
+ *   a non-finite value or one outside [0.5, 2].  For a signal at sps samples per symbol and samplesPerBaud S: sps / S.
+ * psk_soft_resample_count: n_out of a packet of n_complex samples (step == 0: n_complex, the packet goes as it is).
+ * psk_soft_resample_advance: pos of the stream's next packet (step == 0: pos).
+ * psk_soft_resample_apply: the definition above for n_complex untuned CF32 samples.  hist_in NULL or PSK_SOFT_RS_RESTART: a
+ *   history of zeros; hist_out (may be NULL) receives the history behind the packet; `out` holds psk_soft_resample_count()
+ *   samples; `in` and `out` must not overlap.  Refuses what the entry refuses, and step == 0. */
+uint64_t psk_soft_resample_step(double in_per_out);
+uint64_t psk_soft_resample_count(const psk_soft_resample_t *rs, uint64_t n_complex);
+uint64_t psk_soft_resample_advance(const psk_soft_resample_t *rs, uint64_t n_complex);
+psk_soft_status psk_soft_resample_apply(const psk_soft_resample_t *rs, const float *hist_in /* [6] or NULL */, const float *in,
+                                        uint64_t n_complex, float *out, float *hist_out /* [6] or NULL */);
+uint32_t psk_soft_resample_piece(void);     /* outputs of one workgroup's piece of the device's pass (tests: the lengths at its edges) */
+
 /* PSK_SOFT_OPT_DEFERRED_JOIN: make `stream` (a hipStream_t; NULL = the handle's own) wait for everything the calls made so
  * far have put on the handle's side streams -- the point in stream order behind which their results may be used.  A no-op
  * without pending deferred calls.  (There is no counterpart in the reference: its serviceFunction() is synchronous.) */

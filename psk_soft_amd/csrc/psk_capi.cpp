@@ -27,6 +27,7 @@
 #include "psk_plan.h"
 #include "psk_quality.h"
 #include "psk_soft_hip.h"
+#include "psk_resample.h"
 #include "psk_tune.h"
 
 namespace psk {
@@ -548,6 +549,12 @@ struct psk_soft_handle {
     uint64_t gat_calls = 0;
     int gdesc_turn = 0;
     float *d_tune_tab = nullptr;  // tuned packets: the two phasor tables (psk_tune.h), uploaded when the first tuned packet comes
+    // resampled packets: the history of every channel (two slots of three float2 in 64 bytes: a launch reads the current one and
+    // writes the other), allocated when the first resampled packet comes; which slot is current; the event behind the last launch
+    float *d_rs_hist = nullptr;
+    std::vector<uint8_t> rs_cur;
+    hipEvent_t rs_ev = nullptr;
+    bool rs_ev_used = false;
     int opt_diag_gather_only = 0;  // PSK_SOFT_DIAG_GATHER_ONLY=1 (environment, timing experiments only -- tools/strided_rates.py): a
                                    // strided call gathers and returns; the ordinary call behind it is left out, outs[] untouched
     // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
@@ -2089,6 +2096,8 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         for (auto &g : h->gat) g.free();
         for (auto &g : h->gdesc) g.free();
         if (h->d_tune_tab) (void)hipFree(h->d_tune_tab);
+        if (h->d_rs_hist) (void)hipFree(h->d_rs_hist);
+        if (h->rs_ev) (void)hipEventDestroy(h->rs_ev);
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
             if (sl.h_buf) (void)hipHostFree(sl.h_buf);
@@ -2441,43 +2450,69 @@ static psk_soft_status ensure_tune_tab(psk_soft_handle *h)
     return PSK_SOFT_OK;
 }
 
+// resampled packets: the histories in device memory (once per handle), zeros
+constexpr uint32_t kResampleHistFloats = 16;  // two slots of three float2, padded to 64 bytes a channel
+static psk_soft_status ensure_resample_history(psk_soft_handle *h)
+{
+    if (h->d_rs_hist)
+        return PSK_SOFT_OK;
+    float *d = nullptr;
+    PSK_HIP(hipMalloc((void **)&d, sizeof(float) * kResampleHistFloats * h->nch));
+    if (hipMemset(d, 0, sizeof(float) * kResampleHistFloats * h->nch) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(d);  // (the memset is through before a launch on any stream reads a slot)
+        return fail(PSK_SOFT_ERR_HIP, "resample history: hipMemset failed");
+    }
+    h->rs_cur.assign(h->nch, 0);
+    h->d_rs_hist = d;
+    return PSK_SOFT_OK;
+}
+
 // What gather_stage leaves behind: where each packet's own-format row and float2 row of tuned samples lie in the scratch (nullptr:
 // the packet has none), and the scratch and descriptor slot it has claimed, whose events gather_release records behind whatever
 // the caller puts on the stream to read the rows.
 struct GatherStage {
     std::vector<const void *> row;
     std::vector<float *> tune_row;
+    std::vector<uint64_t> rs_out;  // (a resampled packet: the samples of its float2 row, which tune_row points at)
     StreamScratch *sc = nullptr;
     GatherDescSlot *ds = nullptr;  // (set once the descriptors are on the stream: from then on gather_release is owed)
 };
 
 // Finds the frame groups among the packets marked `gathered` (present, strided, complex data, at least one sample), claims the
 // stream's scratch and a descriptor slot, uploads the descriptors and launches the gathers on `stream`, and behind them the tune
-// kernel over the packets marked `tuned`.  A column of a run of at least kGatherMinGroup goes through the tile kernel into its
-// own-format row.  A column of a shorter run goes through the plain strided gather, unless it is tuned (the tune kernel reads it
-// where it lies) or the caller reads every such column in place itself (`singles_in_place`: it gets no row).  A call with nothing
-// to launch returns before it touches a stream, gs.ds == nullptr.
+// kernel over the packets marked `tuned` and the resample kernel over the packets marked `resampled` (which tunes those of them
+// that have a tune: a packet is marked one or the other).  A column of a run of at least kGatherMinGroup goes through the tile
+// kernel into its own-format row.  A column of a shorter run goes through the plain strided gather, unless it is tuned or
+// resampled (those kernels read it where it lies) or the caller reads every such column in place itself (`singles_in_place`: it
+// gets no row).  A call with nothing to launch returns before it touches a stream, gs.ds == nullptr.
 static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                    const uint64_t *sample_stride, const psk_soft_tune_t *tune, const std::vector<uint8_t> &gathered,
-                                    const std::vector<uint8_t> &tuned, bool singles_in_place, hipStream_t stream, GatherStage &gs)
+                                    const uint64_t *sample_stride, const psk_soft_tune_t *tune, const psk_soft_resample_t *resample,
+                                    const std::vector<uint8_t> &gathered, const std::vector<uint8_t> &tuned,
+                                    const std::vector<uint8_t> &resampled, bool singles_in_place, hipStream_t stream, GatherStage &gs)
 {
     // (a column that gets neither a row nor a gather of its own when its run is too short for the tile kernel)
-    auto direct = [&](uint32_t i) { return singles_in_place || tuned[i]; };
-    uint32_t n_tune = 0;
-    for (uint32_t i = 0; i < nch; i++) n_tune += tuned[i];
+    auto direct = [&](uint32_t i) { return singles_in_place || tuned[i] || resampled[i]; };
+    uint32_t n_tune = 0, n_rs = 0;
+    for (uint32_t i = 0; i < nch; i++) n_tune += tuned[i], n_rs += resampled[i];
+    // (the float2 row of a tuned packet holds its samples, that of a resampled one its outputs)
+    auto rs_n_out = [&](uint32_t i) { return psk::resample_count(resample[i].pos, resample[i].step, pkts[i].n_floats / 2u); };
+    auto f2_row = [&](uint32_t i) {
+        const uint64_t n = resampled[i] ? rs_n_out(i) : pkts[i].n_floats / 2u;
+        return align_up(sizeof(float2) * (size_t)(n ? n : 1u), 128);
+    };
     // ---- frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart ----
     struct Run {
         uint32_t first, g, bytes;
     };
     std::vector<Run> runs;
-    std::vector<size_t> row_off(nch, 0), tune_off(n_tune ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned packet)
+    std::vector<size_t> row_off(nch, 0), tune_off(n_tune || n_rs ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned or resampled packet)
     std::vector<uint8_t> has_row(nch, 0);
     size_t need = 0;
     for (uint32_t i = 0; i < nch;) {
         if (!gathered[i]) {
-            if (tuned[i]) {
+            if (tuned[i] || resampled[i]) {
                 tune_off[i] = need;
-                need += align_up(sizeof(float2) * (size_t)(pkts[i].n_floats / 2u), 128);
+                need += f2_row(i);
             }
             i++;
             continue;
@@ -2495,9 +2530,9 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
                 has_row[c] = 1;
                 need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
             }
-            if (tuned[c]) {
+            if (tuned[c] || resampled[c]) {
                 tune_off[c] = need;
-                need += align_up(sizeof(float2) * (size_t)(pkts[c].n_floats / 2u), 128);
+                need += f2_row(c);
             }
         }
         i = j;
@@ -2514,19 +2549,24 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     }
     const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
     const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
-    if (!tot_groups && !tot_singles && !n_tune)
+    if (!tot_groups && !tot_singles && !n_tune && !n_rs)
         return PSK_SOFT_OK;
     const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
     const size_t off_tune = off_singles + sizeof(psk::GatherSingle) * tot_singles;
-    const size_t desc_bytes = off_tune + sizeof(psk::TuneDesc) * n_tune;
+    const size_t off_rs = off_tune + sizeof(psk::TuneDesc) * n_tune;
+    const size_t desc_bytes = off_rs + sizeof(psk::ResampleDesc) * n_rs;
 
     // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
     // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
     PSK_HIP(deferred_join(h, stream));
     StreamScratch *sc = nullptr;
     PSK_TRY(claim_scratch(h->gat, &h->gat_calls, stream, need, nullptr, &sc));
-    if (n_tune)
+    bool rs_tuned = false;  // (a resampled packet that is tuned as well: the resample kernel needs the tables)
+    for (uint32_t i = 0; i < nch && tune; i++) rs_tuned |= resampled[i] && (tune[i].phase | tune[i].step) != 0;
+    if (n_tune || rs_tuned)
         PSK_TRY(ensure_tune_tab(h));
+    if (n_rs)
+        PSK_TRY(ensure_resample_history(h));
     GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
     h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
     if (!ds.ev)
@@ -2548,12 +2588,14 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + off_cols);
     psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
     psk::TuneDesc *const ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + off_tune);
+    psk::ResampleDesc *const hr = reinterpret_cast<psk::ResampleDesc *>(ds.h_buf + off_rs);
     uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
     uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
     const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
-    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0;
+    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0, max_n_rs = 0;
     gs.row.assign(nch, nullptr);
     gs.tune_row.assign(nch, nullptr);
+    gs.rs_out.assign(nch, 0);
     for (const Run &r : runs) {
         const int b = size_idx(r.bytes);
         for (uint32_t c = r.first; c < r.first + r.g; c++)
@@ -2584,26 +2626,47 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
             }
         }
     }
-    // the tuned packets: from the row the tile kernel writes (its columns), else from where the caller has them, at their stride
+    // the tuned and the resampled packets: from the row the tile kernel writes (its columns), else from where the caller has
+    // them, at their stride
     {
-        std::vector<uint8_t> in_group(n_tune ? nch : 0, 0);
+        std::vector<uint8_t> in_group(n_tune || n_rs ? nch : 0, 0);
         for (const Run &r : runs)
-            if (n_tune && r.g >= psk::kGatherMinGroup)
+            if ((n_tune || n_rs) && r.g >= psk::kGatherMinGroup)
                 std::fill(in_group.begin() + r.first, in_group.begin() + r.first + r.g, (uint8_t)1);
-        uint32_t t_at = 0;
-        for (uint32_t c = 0; c < nch && n_tune; c++) {
-            if (!tuned[c])
+        uint32_t t_at = 0, r_at = 0;
+        for (uint32_t c = 0; c < nch && (n_tune || n_rs); c++) {
+            if (!tuned[c] && !resampled[c])
                 continue;
-            psk::TuneDesc &d = ht[t_at++];
-            d = psk::TuneDesc{};
-            d.src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
-            d.dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
-            d.stride = in_group[c] ? 1u : stride_of(sample_stride, c);
+            const void *const src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
+            float *const dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
+            const uint64_t stride = in_group[c] ? 1u : stride_of(sample_stride, c);
+            gs.tune_row[c] = dst;
+            if (tuned[c]) {
+                psk::TuneDesc &d = ht[t_at++];
+                d = psk::TuneDesc{};
+                d.src = src, d.dst = dst, d.stride = stride;
+                d.n = pkts[c].n_floats / 2u;
+                d.phase = tune[c].phase, d.step = tune[c].step;
+                d.format = pkts[c].format;
+                max_n_tune = d.n > max_n_tune ? d.n : max_n_tune;
+                continue;
+            }
+            psk::ResampleDesc &d = hr[r_at++];
+            d = psk::ResampleDesc{};
+            d.src = src, d.dst = dst, d.stride = stride;
             d.n = pkts[c].n_floats / 2u;
-            d.phase = tune[c].phase, d.step = tune[c].step;
             d.format = pkts[c].format;
-            max_n_tune = d.n > max_n_tune ? d.n : max_n_tune;
-            gs.tune_row[c] = d.dst;
+            d.flags = (resample[c].flags & PSK_SOFT_RS_RESTART) ? psk::kResampleRestart : 0u;
+            if (tune && (tune[c].phase | tune[c].step) != 0) {
+                d.phase = tune[c].phase, d.step = tune[c].step;
+                d.flags |= psk::kResampleTuned;
+            }
+            d.pos = resample[c].pos, d.rstep = resample[c].step, d.n_out = rs_n_out(c);
+            // (the channel's current slot in, the other out: psk_soft_process_device_resampled flips them when the call is through)
+            float *const slots = h->d_rs_hist + (size_t)kResampleHistFloats * (ch0 + c);
+            d.hist_in = slots + 6u * h->rs_cur[ch0 + c], d.hist_out = slots + 6u * (h->rs_cur[ch0 + c] ^ 1u);
+            max_n_rs = d.n_out > max_n_rs ? d.n_out : max_n_rs;
+            gs.rs_out[c] = d.n_out;
         }
     }
     PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
@@ -2628,6 +2691,14 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     if (n_tune) {  // (cnt = tuned packets)
         PSK_HIP(mark("tune", 8, n_tune, 0));
         PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + off_tune), n_tune, max_n_tune, h->d_tune_tab, stream));
+    }
+    if (n_rs) {  // (cnt = resampled packets)
+        PSK_HIP(mark("resample", 8, n_rs, 0));
+        PSK_HIP(psk::launch_resample(reinterpret_cast<const psk::ResampleDesc *>(ds.d_buf + off_rs), n_rs, max_n_rs, h->d_tune_tab, stream));
+        if (!h->rs_ev)
+            PSK_HIP(hipEventCreateWithFlags(&h->rs_ev, hipEventDisableTiming));
+        PSK_HIP(hipEventRecord(h->rs_ev, stream));
+        h->rs_ev_used = true;
     }
     return PSK_SOFT_OK;
 }
@@ -2661,11 +2732,16 @@ static psk_soft_status gather_release(GatherStage &gs, hipStream_t stream, psk_s
 // each of them, shifted, as a float2 row of the same scratch, and the packet copy points at that row with format CF32.  The kernel reads a contiguous packet where the caller
 // has it, a column of a frame group of at least kGatherMinGroup columns from the own-format row the tile kernel has just written,
 // and any other strided packet where it lies, at its stride (no gather of its own).
-psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                              const uint64_t *sample_stride, const psk_soft_tune_t *tune, psk_soft_output_t *outs,
-                                              void *stream_v)
+//
+// Resampled packets (`resample` non-NULL and the packet's step not 0; psk_soft_process_device_tuned, below, is this entry with
+// resample == NULL): one launch of the resample kernel (psk_resample.hip) behind the gathers and the tune kernel writes each of
+// them, tuned inside the same pass if it has a tune, as a float2 row of n_out samples; the packet copy points at that row with
+// format CF32, n_out samples and the scaled sri_xdelta.  It reads its source as the tune kernel does.
+psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                                  const uint64_t *sample_stride, const psk_soft_tune_t *tune,
+                                                  const psk_soft_resample_t *resample, psk_soft_output_t *outs, void *stream_v)
 {
-    if (!sample_stride && !tune)
+    if (!sample_stride && !tune && !resample)
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
     if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
@@ -2682,18 +2758,39 @@ psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0
         const psk_soft_packet_t &k = pkts[i];
         return tune && (tune[i].phase | tune[i].step) != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && k.data && known(k);
     };
-    uint32_t n_gather = 0, n_tune = 0;
+    // (a packet the call resamples: a step, present, complex data, at least one sample, of a format the library knows; the
+    // resample kernel reads it -- and tunes it, if it has a tune: tuned() above then counts it as well)
+    auto resampled = [&](uint32_t i) {
+        const psk_soft_packet_t &k = pkts[i];
+        return resample && resample[i].step != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && known(k);
+    };
+    uint32_t n_gather = 0, n_tune = 0, n_rs = 0;
     bool unknown = false;
     for (uint32_t i = 0; i < nch; i++) {
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
+        if (resample && resample[i].step != 0) {
+            const psk_soft_resample_t &r = resample[i];
+            char buf[160];
+            const char *what = r.step < psk::kResampleStepMin || r.step > psk::kResampleStepMax ? "a step outside [2^31, 2^33]"
+                               : r.pos > psk::kResamplePosMax                                  ? "a position above 2^33"
+                               : k.n_floats / 2u >= psk::kResampleMaxN                         ? "2^30 samples or more"
+                               : r.pad                                                         ? "a non-zero pad"
+                               : (r.flags & ~(uint32_t)PSK_SOFT_RS_RESTART)                    ? "unknown flag bits"
+                                                                                               : nullptr;
+            if (what) {
+                std::snprintf(buf, sizeof buf, "psk_soft_process_device_resampled: channel %u: %s", ch0 + i, what);
+                return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+            }
+            n_rs += resampled(i);
+        }
         const uint64_t s = stride_of(sample_stride, i);
         if (s == 1) {  // (contiguous: the ordinary call's business, but for the packets the tune kernel reads)
-            if (tuned(i)) {
+            if (tuned(i) || (resampled(i) && k.data)) {
                 if (reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
                     return fail(PSK_SOFT_ERR_INVALID_ARG, kTunedEntry.misaligned);
-                n_tune++;
+                n_tune += tuned(i);
             }
             continue;
         }
@@ -2707,23 +2804,46 @@ psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0
         n_gather++;
         n_tune += tuned(i);
     }
-    // (a control-plane-only handle plans and counts: lengths and formats are all it looks at)
-    if ((!n_gather && !n_tune) || unknown || h->dry)
+    // the packet the ordinary call sees in place of a resampled one: CF32, n_out samples, the sample period scaled by the step
+    auto resampled_packet = [&](psk_soft_packet_t &k, uint32_t i) {
+        k.n_floats = 2u * psk::resample_count(resample[i].pos, resample[i].step, pkts[i].n_floats / 2u);
+        k.format = PSK_SOFT_FORMAT_CF32;
+        k.sri_xdelta = pkts[i].sri_xdelta * ((double)resample[i].step * 0x1p-32);
+    };
+    // (a control-plane-only handle plans and counts: lengths, formats and sample periods are all it looks at)
+    if (h->dry && n_rs && !unknown) {
+        std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
+        for (uint32_t c = 0; c < nch; c++)
+            if (resampled(c))
+                resampled_packet(pk[c], c);
+        return psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
+    }
+    // (a resampled packet without data is the ordinary call's to refuse)
+    for (uint32_t i = 0; i < nch && n_rs; i++) n_rs -= resampled(i) && !pkts[i].data;
+    if ((!n_gather && !n_tune && !n_rs) || unknown || h->dry)
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
 
     PSK_HIP(hipSetDevice(h->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
-    std::vector<uint8_t> is_gathered(nch), is_tuned(nch);
-    for (uint32_t i = 0; i < nch; i++) is_gathered[i] = gathered(i), is_tuned[i] = tuned(i);
+    std::vector<uint8_t> is_gathered(nch), is_tuned(nch), is_rs(nch);
+    for (uint32_t i = 0; i < nch; i++) {
+        is_gathered[i] = gathered(i);
+        is_rs[i] = resampled(i) && pkts[i].data;
+        is_tuned[i] = tuned(i) && !is_rs[i];  // (a packet both tuned and resampled is tuned inside the resample kernel)
+    }
     GatherStage gs;
-    psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, tune, is_gathered, is_tuned, false, stream, gs);
+    psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, tune, resample, is_gathered, is_tuned, is_rs, false, stream, gs);
     if (!gs.ds)
         return st;
     if (st == PSK_SOFT_OK && !h->opt_diag_gather_only) {
-        // the ordinary call on a copy of the packets that points at the rows: a tuned packet's float2 row, else the gathered one
+        // the ordinary call on a copy of the packets that points at the rows: a tuned or resampled packet's float2 row, else the
+        // gathered one
         std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
         for (uint32_t c = 0; c < nch; c++) {
-            if (gs.tune_row[c]) {
+            if (is_rs[c]) {
+                pk[c].data = gs.tune_row[c];
+                resampled_packet(pk[c], c);
+            } else if (gs.tune_row[c]) {
                 pk[c].data = gs.tune_row[c];
                 pk[c].n_floats = 2u * (pkts[c].n_floats / 2u);
                 pk[c].format = PSK_SOFT_FORMAT_CF32;
@@ -2733,7 +2853,20 @@ psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0
         }
         st = psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
     }
-    return gather_release(gs, stream, st);
+    st = gather_release(gs, stream, st);
+    // the histories the launch has written become the current ones only now that the whole call is through
+    if (st == PSK_SOFT_OK)
+        for (uint32_t c = 0; c < nch; c++)
+            if (is_rs[c])
+                h->rs_cur[ch0 + c] ^= 1u;
+    return st;
+}
+
+psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                              const uint64_t *sample_stride, const psk_soft_tune_t *tune, psk_soft_output_t *outs,
+                                              void *stream_v)
+{
+    return psk_soft_process_device_resampled(h, ch0, nch, pkts, sample_stride, tune, nullptr, outs, stream_v);
 }
 
 psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
@@ -2763,6 +2896,96 @@ psk_soft_status psk_soft_tune_apply(const psk_soft_tune_t *tune, const float *in
         const float xr = in[2u * k], xi = in[2u * k + 1u];  // (in == out is fine)
         psk::tune_rotate(tab, p, xr, xi, &out[2u * k], &out[2u * k + 1u]);
     }
+    return PSK_SOFT_OK;
+}
+
+// ---- resampled packets: the host-side helpers (pure) ----
+uint64_t psk_soft_resample_step(double in_per_out)
+{
+    if (!std::isfinite(in_per_out) || in_per_out < 0.5 || in_per_out > 2.0)
+        return 0;
+    return (uint64_t)(in_per_out * 0x1p32);
+}
+
+// (any n_complex: 128-bit arithmetic, so the helpers answer for lengths the entry refuses too)
+uint64_t psk_soft_resample_count(const psk_soft_resample_t *rs, uint64_t n_complex)
+{
+    if (!rs || !rs->step)
+        return n_complex;
+    const unsigned __int128 end = (unsigned __int128)n_complex << 32;
+    return rs->pos >= end ? 0u : (uint64_t)((end - rs->pos + rs->step - 1u) / rs->step);
+}
+
+uint64_t psk_soft_resample_advance(const psk_soft_resample_t *rs, uint64_t n_complex)
+{
+    if (!rs)
+        return 0;
+    if (!rs->step)
+        return rs->pos;
+    const unsigned __int128 end = (unsigned __int128)n_complex << 32;
+    return (uint64_t)(rs->pos + (unsigned __int128)psk_soft_resample_count(rs, n_complex) * rs->step - end);
+}
+
+psk_soft_status psk_soft_resample_apply(const psk_soft_resample_t *rs, const float *hist_in, const float *in, uint64_t n_complex,
+                                        float *out, float *hist_out)
+{
+    if (!rs || (n_complex && !in))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_apply: null pointer");
+    if (rs->step < psk::kResampleStepMin || rs->step > psk::kResampleStepMax || rs->pos > psk::kResamplePosMax ||
+        n_complex >= psk::kResampleMaxN || rs->pad || (rs->flags & ~(uint32_t)PSK_SOFT_RS_RESTART))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_apply: step outside [2^31, 2^33], pos above 2^33, 2^30 samples or more, pad or flags");
+    const uint64_t n_out = psk::resample_count(rs->pos, rs->step, n_complex);
+    if (n_out && !out)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_apply: null pointer");
+    float hist[6] = {};
+    if (hist_in && !(rs->flags & PSK_SOFT_RS_RESTART))
+        std::memcpy(hist, hist_in, sizeof hist);
+    // component q (0 re, 1 im) of s[j], j >= -3
+    auto s = [&](int64_t j, int q) { return j < 0 ? hist[2 * (j + 3) + q] : in[2 * j + q]; };
+    uint64_t t = rs->pos;
+    for (uint64_t m = 0; m < n_out; m++, t += rs->step) {
+        const int64_t i = (int64_t)(t >> 32);
+        float w[4];
+        psk::resample_taps((uint32_t)t, w);
+        for (int q = 0; q < 2; q++) out[2u * m + q] = psk::resample_mix(w, s(i - 3, q), s(i - 2, q), s(i - 1, q), s(i, q));
+    }
+    if (hist_out) {
+        float nh[6];
+        for (int64_t j = 0; j < 3; j++)
+            for (int q = 0; q < 2; q++) nh[2 * j + q] = s((int64_t)n_complex - 3 + j, q);
+        std::memcpy(hist_out, nh, sizeof nh);
+    }
+    return PSK_SOFT_OK;
+}
+
+uint32_t psk_soft_resample_piece(void) { return psk::kResamplePiece; }
+
+// the history of a channel: its current slot, behind the last resample launch
+psk_soft_status psk_soft_resample_get_history(psk_soft_handle_t *h, uint32_t ch, float *out)
+{
+    if (!h || !out || ch >= h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_get_history: bad arguments");
+    std::memset(out, 0, sizeof(float) * 6u);
+    if (h->dry || !h->d_rs_hist)
+        return PSK_SOFT_OK;
+    PSK_HIP(hipSetDevice(h->device));
+    if (h->rs_ev_used)
+        PSK_HIP(hipEventSynchronize(h->rs_ev));
+    PSK_HIP(hipMemcpy(out, h->d_rs_hist + (size_t)kResampleHistFloats * ch + 6u * h->rs_cur[ch], sizeof(float) * 6u, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_resample_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in)
+{
+    if (!h || !in || ch >= h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_set_history: bad arguments");
+    if (h->dry)
+        return PSK_SOFT_OK;  // (a control-plane-only handle keeps zeros)
+    PSK_HIP(hipSetDevice(h->device));
+    PSK_TRY(ensure_resample_history(h));
+    if (h->rs_ev_used)
+        PSK_HIP(hipEventSynchronize(h->rs_ev));  // (no launch is still reading the slot)
+    PSK_HIP(hipMemcpy(h->d_rs_hist + (size_t)kResampleHistFloats * ch + 6u * h->rs_cur[ch], in, sizeof(float) * 6u, hipMemcpyHostToDevice));
     return PSK_SOFT_OK;
 }
 
@@ -2823,7 +3046,7 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
     {
         std::vector<uint8_t> is_gathered(nch), none(nch, 0);
         for (uint32_t i = 0; i < nch; i++) is_gathered[i] = stride_of(sample_stride, i) != 1 && looked_at(i);
-        const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, is_gathered, none, true, stream, gs);
+        const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, nullptr, is_gathered, none, none, true, stream, gs);
         if (!gs.ds) {
             if (st != PSK_SOFT_OK)
                 return st;

@@ -142,6 +142,16 @@ class Tune(ctypes.Structure):
     _fields_ = [("phase", ctypes.c_uint64), ("step", ctypes.c_uint64)]
 
 
+RS_RESTART = 1  # Resample.flags
+
+
+class Resample(ctypes.Structure):
+    """psk_soft_resample_t: position of a packet's first output and step per output, both in input samples x 2^32; step 0
+    leaves the packet as it is."""
+
+    _fields_ = [("pos", ctypes.c_uint64), ("step", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
+
+
 # Acquire.flags
 A_DATA, A_TUNED, A_PLANNED = 1, 2, 128
 ACQUIRE_LAGS = 8  # lags 1, 2, 4 .. 128
@@ -203,6 +213,14 @@ EXPORTS = (
     "psk_soft_tune_step",
     "psk_soft_tune_advance",
     "psk_soft_tune_apply",
+    "psk_soft_process_device_resampled",
+    "psk_soft_resample_get_history",
+    "psk_soft_resample_set_history",
+    "psk_soft_resample_step",
+    "psk_soft_resample_count",
+    "psk_soft_resample_advance",
+    "psk_soft_resample_apply",
+    "psk_soft_resample_piece",
     "psk_soft_acquire_device",
     "psk_soft_get_acquire",
     "psk_soft_acquire_derive",
@@ -265,6 +283,20 @@ def load():
     L.psk_soft_tune_advance.argtypes = [u64, u64, u64]
     L.psk_soft_tune_advance.restype = u64
     L.psk_soft_tune_apply.argtypes = [ctypes.POINTER(Tune), vp, u64, vp]
+    L.psk_soft_process_device_resampled.argtypes = [
+        vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Tune), ctypes.POINTER(Resample), ctypes.POINTER(Output), vp
+    ]
+    L.psk_soft_resample_get_history.argtypes = [vp, u32, vp]
+    L.psk_soft_resample_set_history.argtypes = [vp, u32, vp]
+    L.psk_soft_resample_step.argtypes = [ctypes.c_double]
+    L.psk_soft_resample_step.restype = u64
+    L.psk_soft_resample_count.argtypes = [ctypes.POINTER(Resample), u64]
+    L.psk_soft_resample_count.restype = u64
+    L.psk_soft_resample_advance.argtypes = [ctypes.POINTER(Resample), u64]
+    L.psk_soft_resample_advance.restype = u64
+    L.psk_soft_resample_apply.argtypes = [ctypes.POINTER(Resample), vp, vp, u64, vp, vp]
+    L.psk_soft_resample_piece.argtypes = []
+    L.psk_soft_resample_piece.restype = u32
     L.psk_soft_process_host.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(Output)]
     L.psk_soft_synchronize.argtypes = [vp]
     L.psk_soft_join.argtypes = [vp, vp]
@@ -377,6 +409,49 @@ def tune_apply(phase, step, iq):
     t = Tune(int(phase), int(step))
     _check(load().psk_soft_tune_apply(ctypes.byref(t), x.ctypes.data, n, y.ctypes.data))
     return y
+
+
+def _resample(rs):
+    """a Resample from a Resample or a (pos, step[, flags]) tuple"""
+    return rs if isinstance(rs, Resample) else Resample(int(rs[0]), int(rs[1]), int(rs[2]) if len(rs) > 2 else 0, 0)
+
+
+def resample_step(in_per_out):
+    """psk_soft_resample_step: the step word (input samples per output sample x 2^32); 0 outside [0.5, 2] or non-finite.  For a
+    signal at sps samples per symbol demodulated with samplesPerBaud S: resample_step(sps / S)."""
+    return int(load().psk_soft_resample_step(float(in_per_out)))
+
+
+def resample_count(rs, n_complex):
+    """psk_soft_resample_count: the outputs of a packet of n_complex samples.  rs: a Resample or (pos, step[, flags])."""
+    r = _resample(rs)
+    return int(load().psk_soft_resample_count(ctypes.byref(r), int(n_complex)))
+
+
+def resample_advance(rs, n_complex):
+    """psk_soft_resample_advance: pos of the next packet of a continuous stream."""
+    r = _resample(rs)
+    return int(load().psk_soft_resample_advance(ctypes.byref(r), int(n_complex)))
+
+
+def resample_apply(rs, iq, history=None):
+    """psk_soft_resample_apply on the host: interleaved float32 I/Q in (an odd last element is dropped), history None (zeros)
+    or six floats.  Returns (the resampled interleaved float32 I/Q, the history behind the packet as six float32)."""
+    r = _resample(rs)
+    x = np.ascontiguousarray(iq, np.float32)
+    n = x.size // 2
+    y = np.empty(2 * resample_count(r, n), np.float32)
+    hi = None if history is None else np.ascontiguousarray(history, np.float32)
+    if hi is not None and hi.size != 6:
+        raise ValueError("a history is three complex samples: six floats")
+    ho = np.empty(6, np.float32)
+    _check(load().psk_soft_resample_apply(ctypes.byref(r), None if hi is None else hi.ctypes.data, x.ctypes.data, n, y.ctypes.data, ho.ctypes.data))
+    return y, ho
+
+
+def resample_piece():
+    """Outputs of one workgroup's piece of the device's resample pass (psk_soft_resample_piece)."""
+    return int(load().psk_soft_resample_piece())
 
 
 def acquire_derive(rec):
@@ -518,6 +593,35 @@ class Handle:
         if (strides is not None and len(strides) != len(pkts)) or (tunes is not None and len(tunes) != len(pkts)):
             raise ValueError("one stride and one tune per packet")
         _check(self._L.psk_soft_process_device_tuned(self._h, ch0, len(pkts), pkts, strides, tunes, outs, ctypes.c_void_p(stream or 0)))
+
+    def process_device_resampled(self, ch0, pkts, strides, tunes, resamples, outs, stream=None):
+        """process_device_tuned with a fractional resampler per packet, applied on the GPU in front of the demodulator (and
+        behind the frequency shift, in the same pass).  resamples: None (nothing resampled), a ctypes Resample array or a sequence
+        of Resample / (pos, step[, flags]), one per packet; step 0 leaves a packet as it is.  Size the output rows with
+        output_capacity(ch, resample_count(rs, n)).  strides and tunes as for process_device_tuned."""
+        if strides is not None and not isinstance(strides, ctypes.Array):
+            strides = (ctypes.c_uint64 * len(strides))(*[int(s) for s in strides])
+        if tunes is not None and not isinstance(tunes, ctypes.Array):
+            tunes = (Tune * len(tunes))(*[Tune(int(p), int(s)) for p, s in tunes])
+        if resamples is not None and not isinstance(resamples, ctypes.Array):
+            resamples = (Resample * len(resamples))(*[_resample(r) for r in resamples])
+        if any(a is not None and len(a) != len(pkts) for a in (strides, tunes, resamples)):
+            raise ValueError("one stride, one tune and one resample per packet")
+        _check(self._L.psk_soft_process_device_resampled(self._h, ch0, len(pkts), pkts, strides, tunes, resamples, outs,
+                                                         ctypes.c_void_p(stream or 0)))
+
+    def resample_history(self, ch):
+        """The resampler's history of channel ch (psk_soft_resample_get_history): six float32, three (re, im) pairs, oldest first."""
+        out = np.zeros(6, np.float32)
+        _check(self._L.psk_soft_resample_get_history(self._h, int(ch), out.ctypes.data))
+        return out
+
+    def set_resample_history(self, ch, six):
+        """psk_soft_resample_set_history: replace the resampler's history of channel ch."""
+        x = np.ascontiguousarray(six, np.float32)
+        if x.size != 6:
+            raise ValueError("a history is three complex samples: six floats")
+        _check(self._L.psk_soft_resample_set_history(self._h, int(ch), x.ctypes.data))
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with

@@ -38,6 +38,8 @@ others psk_quality
 others psk_gather
 # the tune pre-pass of psk_soft_process_device_tuned (psk_tune.hip): one kernel, the four formats behind a switch
 others psk_tune
+# the resample pre-pass of psk_soft_process_device_resampled (psk_resample.hip): one kernel, the four formats behind a switch
+others psk_resample
 # the far fit (PSK_SOFT_OPT_FAR_FIT, psk_farfit.hip): the fit stage and the quiet call with the fit window in device memory
 others psk_farfit
 echo "instantiations with D sites / with E sites (tools/isa_lane_loss.py):"; grep -c "no covering save) [1-9]" $out.lanes; grep -c "mask restore) [1-9]" $out.lanes
