@@ -1,0 +1,409 @@
+"""The pre-pass kernels by themselves: ctypes binding of the test-only probe library (tests/support/prepass_probe.hip ->
+psk_soft_amd/libpsk_prepass_probe.so: a shim linked with the product's own psk_gather.o, psk_tune.o and psk_resample.o), the
+ARENA the kernels run in, the arena the models expect, and the comparator.
+
+An arena is one byte image: sources, destination rows, history slots, and poison everywhere else.  The descriptors have the
+product's layout (psk_gather.h, psk_tune.h, psk_resample.h) with byte offsets into the arena where the product has pointers.  A
+case below lays the arena out, fills the descriptors and computes the arena the launch must leave: a byte copy for the gathers,
+tune_model.apply for the tune kernel, tune_model.apply followed by resample_model.apply for the resample kernel.  Arena.compare
+holds the whole downloaded arena to it byte for byte: every row sample, both history slots, every source byte, the padding of
+every row up to its 128 bytes and every guard byte.
+
+Everything is placed on a 128-byte line (plus the skew a case asks for: the least alignment of a packet) and followed by a
+guard of 128 bytes; the extents behind every descriptor are checked against the arena here, in front of every launch."""
+import ctypes
+import os
+
+import numpy as np
+
+from tests import resample_model as rm
+from tests import tune_model as tm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB_PATH = os.path.join(ROOT, "psk_soft_amd", "libpsk_prepass_probe.so")
+
+F32 = np.float32
+FORMAT_CF32, FORMAT_CS16, FORMAT_CS8, FORMAT_CF16 = 0, 1, 3, 4  # PSK_SOFT_FORMAT_*
+FORMATS = (FORMAT_CF32, FORMAT_CS16, FORMAT_CS8, FORMAT_CF16)
+DTYPE_OF = {FORMAT_CF32: np.dtype(np.float32), FORMAT_CS16: np.dtype(np.int16), FORMAT_CS8: np.dtype(np.int8), FORMAT_CF16: np.dtype(np.float16)}
+SAMPLE_BYTES = {f: 2 * d.itemsize for f, d in DTYPE_OF.items()}
+# what lies in the other columns of a strided packet's matrix: a NaN for the float formats, the most negative integer
+POISON_OF = {FORMAT_CF32: np.uint32(0x7FC00ABC).view(np.float32), FORMAT_CS16: np.int16(-32768), FORMAT_CS8: np.int8(-128),
+             FORMAT_CF16: np.uint16(0x7E55).view(np.float16)}
+RS_RESTART, RS_TUNED = 1, 2  # ResampleDesc::flags (psk_resample.h)
+LINE, GUARD = 128, 128
+GUARD_BYTE, ROW_BYTE = 0xA5, 0xC3
+REPORTED = 8  # findings a comparison lists at the most
+
+_U8, _U4 = "<u8", "<u4"
+GROUP = np.dtype([("src", _U8), ("stride", _U8), ("n_max", _U8), ("tile0", _U8), ("first", _U4), ("g", _U4), ("tiles_c", _U4), ("pad", _U4)])
+CHAN = np.dtype([("dst", _U8), ("n", _U8)])
+SINGLE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8)])
+TUNE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("format", _U4), ("pad", _U4)])
+RESAMPLE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("format", _U4), ("flags", _U4),
+                     ("pos", _U8), ("rstep", _U8), ("n_out", _U8), ("hist_in", _U8), ("hist_out", _U8)])
+MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE)  # in the order of psk_prepass_probe_sizeof
+CONSTANTS = ("resample_piece", "resample_inputs", "gather_tile", "gather_min_group", "tune_table_floats")
+
+
+# ---- the binding -----------------------------------------------------------------------------------------------------------------
+
+_lib = None
+_failed = None  # the first HIP error of this process: nothing more is launched after one
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError("%s is not built (make -C psk_soft_amd/csrc)" % LIB_PATH)
+        L = ctypes.CDLL(LIB_PATH)
+        vp, u64, u32, i = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
+        for name, args in (("psk_prepass_probe_sizeof", [i]), ("psk_prepass_probe_constant", [i]),
+                           ("psk_prepass_probe_gather_singles", [vp, u64, i, vp, u32, u64]),
+                           ("psk_prepass_probe_gather_tiles", [vp, u64, i, vp, u32, vp, u32, u64]),
+                           ("psk_prepass_probe_tune", [vp, u64, vp, u32, u64, vp]),
+                           ("psk_prepass_probe_resample", [vp, u64, vp, u32, u64])):
+            getattr(L, name).argtypes, getattr(L, name).restype = args, i
+        _lib = L
+    return _lib
+
+
+def sizeof(which):
+    """sizeof of the product's descriptor MIRRORS[which] mirrors"""
+    return int(load().psk_prepass_probe_sizeof(which))
+
+
+def constant(name):
+    """a constant of the kernels' headers, by its name in CONSTANTS"""
+    return int(load().psk_prepass_probe_constant(CONSTANTS.index(name)))
+
+
+def _launch(what, fn, image, *args):
+    """the arena after the launch (a new array); raises on a HIP error, and at every call after one"""
+    global _failed
+    if _failed is not None:
+        raise RuntimeError("not run: an earlier launch failed (%s)" % _failed)
+    after = np.array(image, np.uint8)
+    err = fn(after.ctypes.data, after.size, *args)
+    if err != 0:
+        _failed = "%s: HIP error %d" % (what, err)
+        raise RuntimeError(_failed)
+    return after
+
+
+# ---- launch_resample's grid rule ---------------------------------------------------------------------------------------------------
+
+def resample_grid(n_desc, max_n_out, piece):
+    """Workgroups per packet, as psk::launch_resample (psk_resample.hip) shapes its grid: min(pieces of the longest packet,
+    ceil(2048 / n_desc)), at least 1, at most 65535.  2048 and the bounds are that function's literals."""
+    per = min(-(-max_n_out // piece), -(-2048 // n_desc))
+    return max(1, min(per, 65535))
+
+
+def resample_walk(n_out, per, piece):
+    """(the pieces each of the `per` workgroups of a packet takes, the workgroup that writes the history), as
+    psk_resample_kernel and rs_packet (psk_resample.hip) have it: piece p goes to workgroup p % per; the owner of the last
+    piece, or workgroup 0 of a packet without outputs, writes the history."""
+    n_pieces = -(-n_out // piece)
+    return [list(range(y, n_pieces, per)) for y in range(per)], ((n_pieces - 1) % per if n_pieces else 0)
+
+
+def length_for(n_out, step):
+    """(n, pos): a packet length and a position below or at 2^33 with exactly n_out outputs"""
+    one = 1 << 32
+    for pos in (step // 3, step // 3 + (1 << 31), 5, one + 7, (1 << 33) - 9, 1 << 33):
+        for n in range(max(1, n_out * step // one - 3), n_out * step // one + 6):
+            if rm.count(pos, step, n) == n_out:
+                return n, pos
+    raise AssertionError((n_out, step))
+
+
+# ---- the arena ---------------------------------------------------------------------------------------------------------------------
+
+class Region:
+    """bytes [start, end) of the arena.  kind: "source" (never written), "row" (the samples a descriptor's kernel writes),
+    "padding" (the rest of the row's lines), "hist_in" (the slot read), "hist_out" (the slot written); desc: the descriptor it
+    belongs to; unit: bytes of one sample of it"""
+
+    def __init__(self, start, end, kind, desc, unit):
+        self.start, self.end, self.kind, self.desc, self.unit = start, end, kind, desc, unit
+
+
+class Arena:
+    def __init__(self):
+        self._parts, self.size, self.regions = [], 0, []
+        self._fill(GUARD)
+
+    def _fill(self, n, byte=GUARD_BYTE):
+        if n:
+            self._parts.append(np.full(n, byte, np.uint8))
+            self.size += n
+
+    def _place(self, data, skew=0):
+        """data on a line (+ skew bytes), the rest of its last line and a guard behind it; its offset"""
+        assert self.size % LINE == 0 and 0 <= skew < LINE
+        self._fill(skew)
+        at = self.size
+        self._parts.append(np.frombuffer(np.ascontiguousarray(data).tobytes(), np.uint8))
+        self.size += self._parts[-1].size
+        self._fill(-self.size % LINE + GUARD)
+        return at
+
+    def source(self, data, desc, unit, skew=0):
+        at = self._place(data, skew)
+        self.regions.append(Region(at, at + np.asarray(data).nbytes, "source", desc, unit))
+        return at
+
+    def row(self, n, unit, desc):
+        """a row of n samples of `unit` bytes: as the product sizes it, whole lines, one at the least"""
+        cap = (max(n, 1) * unit + LINE - 1) // LINE * LINE
+        at = self._place(np.full(cap, ROW_BYTE, np.uint8))
+        self.regions.append(Region(at, at + n * unit, "row", desc, unit))
+        self.regions.append(Region(at + n * unit, at + cap, "padding", desc, unit))
+        return at
+
+    def history(self, slot_in, values, desc):
+        """the two slots of a channel, 24 bytes each, back to back as the handle has them: slot `slot_in` holds `values`
+        (six floats), the other one poison.  (offset of the slot read, offset of the slot written)"""
+        pair = np.full(48, ROW_BYTE, np.uint8)
+        pair[24 * slot_in : 24 * slot_in + 24] = np.frombuffer(np.asarray(values, F32).tobytes(), np.uint8)
+        at = self._place(pair)
+        a, b = at + 24 * slot_in, at + 24 * (slot_in ^ 1)
+        self.regions.append(Region(a, a + 24, "hist_in", desc, 8))
+        self.regions.append(Region(b, b + 24, "hist_out", desc, 8))
+        return a, b
+
+    def image(self):
+        img = np.concatenate(self._parts)
+        assert img.size == self.size
+        # (a row without samples is an empty region: it holds no byte, so the lookups below leave it out)
+        self._solid = sorted((r for r in self.regions if r.end > r.start), key=lambda r: r.start)
+        self._empty = {(r.kind, r.start) for r in self.regions if r.end == r.start}
+        self._starts = np.array([r.start for r in self._solid], np.int64)
+        assert all(x.end <= y.start for x, y in zip(self._solid, self._solid[1:]))
+        return img
+
+    def _region_at(self, off):
+        """(index into the non-empty regions of the last one that starts at or in front of byte `off`, or -1; does it hold it?)"""
+        k = int(np.searchsorted(self._starts, off, "right")) - 1
+        return k, k >= 0 and off < self._solid[k].end
+
+    def inside(self, kind, off, nbytes):
+        """is [off, off + nbytes) inside one region of that kind (an empty range: is it such an empty region)?"""
+        if nbytes == 0:
+            return (kind, off) in self._empty
+        k, holds = self._region_at(off)
+        return holds and self._solid[k].kind == kind and off + nbytes <= self._solid[k].end
+
+    def compare(self, want, got):
+        """[] if the two images are equal; else at most REPORTED findings in arena order, one per region (or guard) that
+        differs: dict(desc, where, sample, offset, n_bytes, want, got, message) -- the first differing sample of the region,
+        its bytes as hex strings, and how many bytes of the region differ"""
+        assert want.size == got.size == self.size
+        diff = np.flatnonzero(want != got)
+        found, at = [], 0
+        while at < diff.size and len(found) < REPORTED:
+            off = int(diff[at])
+            k, holds = self._region_at(off)
+            r, guard = (self._solid[k] if k >= 0 else None), not holds
+            if guard:
+                lo = r.end if r is not None else 0
+                hi = self._solid[k + 1].start if k + 1 < len(self._solid) else self.size
+                where, unit, sample, first = "guard", 1, None, off
+            else:
+                lo, hi, where, unit = r.start, r.end, r.kind, r.unit
+                sample = (off - lo) // unit
+                first = lo + sample * unit
+            stop = int(np.searchsorted(diff, hi, "left"))
+            w, g = want[first : first + unit].tobytes().hex(), got[first : first + unit].tobytes().hex()
+            desc = r.desc if r is not None else None
+            if guard:
+                msg = "guard: %d byte(s) changed, the first %d byte(s) behind the %s of descriptor %s (offset %d): %s -> %s" % (
+                    stop - at, off - lo, r.kind if r is not None else "start", desc, off, w, g)
+            else:
+                msg = "descriptor %s %s: %d byte(s) differ, the first in sample %d (offset %d): want %s, got %s" % (
+                    desc, where, stop - at, sample, off, w, g)
+            found.append(dict(desc=desc, where=where, sample=sample, offset=off, n_bytes=stop - at, want=w, got=g, message=msg))
+            at = stop
+        return found
+
+
+def messages(found):
+    return "\n".join(f["message"] for f in found)
+
+
+# ---- cases: an arena, its descriptors, the arena expected behind the launch ----------------------------------------------------
+
+def _strided(iq, fmt, stride, col):
+    """the matrix a packet of stride `stride` is column `col` of -- n frames, everything else poison -- and the byte offset of
+    the packet's sample 0 in it; the packet itself for stride 1"""
+    dt = DTYPE_OF[fmt]
+    x = np.ascontiguousarray(iq, dt)
+    n = x.size // 2
+    if stride == 1:
+        return x[: 2 * n], 0
+    mat = np.full((n, stride, 2), POISON_OF[fmt], dt)
+    mat[:, col, :] = x[: 2 * n].reshape(n, 2)
+    return mat, col * SAMPLE_BYTES[fmt]
+
+
+class _Case:
+    def __init__(self):
+        self.arena = Arena()
+        self._writes = []  # (offset, bytes the launch must leave there)
+
+    def _finish(self):
+        self.image = self.arena.image()
+        self.want = self.image.copy()
+        for off, data in self._writes:
+            b = np.frombuffer(np.ascontiguousarray(data).tobytes(), np.uint8)
+            self.want[off : off + b.size] = b
+
+    def _extents(self, src, sb, stride, n, dst, unit, n_dst):
+        """what a kernel may touch behind a descriptor lies in the arena's source and row of it"""
+        a = self.arena
+        assert n >= 1 and stride >= 1
+        assert a.inside("source", src, sb) and a.inside("source", src + (n - 1) * stride * sb, sb), (src, sb, stride, n)
+        assert dst % LINE == 0 and a.inside("row", dst, n_dst * unit), (dst, unit, n_dst)
+
+    def check(self, after):
+        return self.arena.compare(self.want, after)
+
+
+class ResampleCase(_Case):
+    """One launch of the resample kernel.  packets: dicts of fmt, stride (1 or more; the packet is column i % stride of its
+    matrix), iq (interleaved I/Q in the format's dtype), tune ((phase, step) or None), pos, rstep, restart, hist (six floats in
+    the slot that is read, or None: the handle's zeros), slot (which of the two is read; default i % 2)."""
+
+    def __init__(self, packets):
+        super().__init__()
+        self.packets = packets
+        self.desc = np.zeros(len(packets), RESAMPLE)
+        self.rows, self.hists = [], []
+        for i, p in enumerate(packets):
+            fmt, stride, sb = p["fmt"], p["stride"], SAMPLE_BYTES[p["fmt"]]
+            data, col_off = _strided(p["iq"], fmt, stride, i % stride)
+            n = np.asarray(p["iq"]).size // 2
+            x = np.ascontiguousarray(p["iq"], DTYPE_OF[fmt])[: 2 * n]
+            s = x.astype(F32) if p["tune"] is None else tm.apply(p["tune"][0], p["tune"][1], x)
+            hist = np.zeros(6, F32) if p["hist"] is None else np.asarray(p["hist"], F32)
+            y, h_out = rm.apply(p["pos"], p["rstep"], s, hist, p["restart"])
+            n_out = y.size // 2
+            assert n_out == rm.count(p["pos"], p["rstep"], n)
+            d = self.desc[i]
+            # (the least alignment of a packet, one sample, for every second contiguous one)
+            d["src"] = self.arena.source(data, i, sb, skew=sb if stride == 1 and i % 2 else 0) + col_off
+            d["dst"] = self.arena.row(n_out, 8, i)
+            d["hist_in"], d["hist_out"] = self.arena.history(p.get("slot", i % 2), hist, i)
+            d["stride"], d["n"], d["format"] = stride, n, fmt
+            d["flags"] = (RS_RESTART if p["restart"] else 0) | (RS_TUNED if p["tune"] is not None else 0)
+            if p["tune"] is not None:
+                d["phase"], d["step"] = p["tune"][0] & tm.MASK, p["tune"][1] & tm.MASK
+            d["pos"], d["rstep"], d["n_out"] = p["pos"], p["rstep"], n_out
+            self._writes += [(int(d["dst"]), y), (int(d["hist_out"]), h_out)]
+            self.rows.append(y)
+            self.hists.append(h_out)
+        self.max_n_out = int(self.desc["n_out"].max())
+        self._finish()
+        for d in self.desc:
+            self._extents(int(d["src"]), SAMPLE_BYTES[int(d["format"])], int(d["stride"]), int(d["n"]), int(d["dst"]), 8, int(d["n_out"]))
+            assert self.arena.inside("hist_in", int(d["hist_in"]), 24) and self.arena.inside("hist_out", int(d["hist_out"]), 24)
+            assert (1 << 31) <= int(d["rstep"]) <= (1 << 33) and int(d["pos"]) <= (1 << 33)  # (what the entry lets through)
+
+    def run(self):
+        return _launch("resample", load().psk_prepass_probe_resample, self.image, self.desc.ctypes.data, len(self.desc), self.max_n_out)
+
+
+class TuneCase(_Case):
+    """One launch of the tune kernel.  packets: dicts of fmt, stride, iq, phase, step."""
+
+    def __init__(self, packets):
+        super().__init__()
+        self.packets = packets
+        self.desc = np.zeros(len(packets), TUNE)
+        self.rows = []
+        for i, p in enumerate(packets):
+            fmt, stride, sb = p["fmt"], p["stride"], SAMPLE_BYTES[p["fmt"]]
+            data, col_off = _strided(p["iq"], fmt, stride, i % stride)
+            n = np.asarray(p["iq"]).size // 2
+            y = tm.apply(p["phase"], p["step"], np.ascontiguousarray(p["iq"], DTYPE_OF[fmt])[: 2 * n])
+            d = self.desc[i]
+            d["src"] = self.arena.source(data, i, sb, skew=sb if stride == 1 and i % 2 else 0) + col_off
+            d["dst"] = self.arena.row(n, 8, i)
+            d["stride"], d["n"], d["format"] = stride, n, fmt
+            d["phase"], d["step"] = p["phase"] & tm.MASK, p["step"] & tm.MASK
+            self._writes.append((int(d["dst"]), y))
+            self.rows.append(y)
+        self.max_n = int(self.desc["n"].max())
+        self._finish()
+        for d in self.desc:
+            self._extents(int(d["src"]), SAMPLE_BYTES[int(d["format"])], int(d["stride"]), int(d["n"]), int(d["dst"]), 8, int(d["n"]))
+
+    def run(self):
+        """(the arena behind the launch, the device's tables behind it as (C, F), shaped like tune_model.tables())"""
+        tab = np.zeros(constant("tune_table_floats"), F32)
+        after = _launch("tune", load().psk_prepass_probe_tune, self.image, self.desc.ctypes.data, len(self.desc), self.max_n, tab.ctypes.data)
+        return after, (tab[: tab.size // 2].reshape(-1, 2), tab[tab.size // 2 :].reshape(-1, 2))
+
+
+class SinglesCase(_Case):
+    """One launch of the plain strided gather.  sample_bytes 2, 4 or 8; packets: (n, stride); the samples are drawn here."""
+
+    def __init__(self, sample_bytes, packets, seed):
+        super().__init__()
+        rng = np.random.default_rng(seed)
+        self.sample_bytes = sb = sample_bytes
+        self.desc = np.zeros(len(packets), SINGLE)
+        for i, (n, stride) in enumerate(packets):
+            mat = rng.integers(0, 256, (n, stride, sb), dtype=np.uint8)
+            col = i % stride
+            d = self.desc[i]
+            d["src"] = self.arena.source(mat, i, sb, skew=sb if i % 2 else 0) + col * sb
+            d["dst"] = self.arena.row(n, sb, i)
+            d["stride"], d["n"] = stride, n
+            self._writes.append((int(d["dst"]), mat[:, col, :]))
+        self.max_n = int(self.desc["n"].max())
+        self._finish()
+        for d in self.desc:
+            self._extents(int(d["src"]), sb, int(d["stride"]), int(d["n"]), int(d["dst"]), sb, int(d["n"]))
+
+    def run(self):
+        return _launch("gather_singles", load().psk_prepass_probe_gather_singles, self.image, self.sample_bytes, self.desc.ctypes.data,
+                       len(self.desc), self.max_n)
+
+
+class TilesCase(_Case):
+    """One launch of the tile gather.  groups: (lengths of the g adjacent columns, columns of the matrix in front of them,
+    columns behind them); the descriptors are filled as gather_stage (psk_capi.cpp) fills them."""
+
+    def __init__(self, sample_bytes, groups, seed):
+        super().__init__()
+        rng = np.random.default_rng(seed)
+        tile = 64  # (kGatherTile: tests/test_prepass_probe.py holds it to the header's)
+        self.sample_bytes = sb = sample_bytes
+        self.groups = np.zeros(len(groups), GROUP)
+        self.chans = np.zeros(sum(len(g[0]) for g in groups), CHAN)
+        c_at, self.n_tiles = 0, 0
+        for k, (lens, front, behind) in enumerate(groups):
+            g, n_max, width = len(lens), max(lens), front + len(lens) + behind
+            mat = rng.integers(0, 256, (n_max, width, sb), dtype=np.uint8)
+            src = self.arena.source(mat, c_at, sb, skew=sb if k % 2 else 0) + front * sb
+            G = self.groups[k]
+            G["src"], G["stride"], G["n_max"], G["tile0"], G["first"], G["g"], G["tiles_c"] = src, width, n_max, self.n_tiles, c_at, g, -(-g // tile)
+            self.n_tiles += int(G["tiles_c"]) * -(-n_max // tile)
+            for j, n in enumerate(lens):
+                c = self.chans[c_at]
+                c["dst"], c["n"] = self.arena.row(n, sb, c_at), n
+                self._writes.append((int(c["dst"]), mat[:n, front + j, :]))
+                c_at += 1
+        self._finish()
+        for G in self.groups:
+            for j in range(int(G["g"])):
+                c = self.chans[int(G["first"]) + j]
+                assert 1 <= int(c["n"]) <= int(G["n_max"])
+                self._extents(int(G["src"]) + j * sb, sb, int(G["stride"]), int(c["n"]), int(c["dst"]), sb, int(c["n"]))
+
+    def run(self):
+        return _launch("gather_tiles", load().psk_prepass_probe_gather_tiles, self.image, self.sample_bytes, self.groups.ctypes.data,
+                       len(self.groups), self.chans.ctypes.data, len(self.chans), self.n_tiles)

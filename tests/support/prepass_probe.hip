@@ -1,0 +1,182 @@
+// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip) launched by
+// themselves, so that tests can hold every byte they write -- each row sample, both history slots -- and every byte they must
+// not write to the models, bit for bit (tests/prepass_probe.py, tests/test_gpu_prepass_probe.py).
+//
+// This file holds no kernel.  It is linked with the product's own objects psk_gather.o, psk_tune.o and psk_resample.o as the
+// product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
+// the product's.  Nothing of it is linked into the product library.
+//
+// One C entry per kernel.  The caller passes one host ARENA -- sources, destination rows, histories, poison everywhere else --
+// and descriptors of the product's layout that hold byte offsets into the arena where the product's hold pointers.  An entry
+// refuses an offset outside the arena (hipErrorInvalidValue; the extents behind the offsets are the caller's to check),
+// allocates a device arena, uploads the host's, turns the offsets into pointers, uploads the descriptors, launches once through
+// the product's launch function on a stream of its own, synchronises, downloads the WHOLE arena into the host's and returns the
+// HIP status.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "psk_gather.h"
+#include "psk_resample.h"
+#include "psk_tune.h"
+
+using namespace psk;
+
+namespace {
+
+struct Run {
+    char *d_arena = nullptr;
+    void *d_desc[2] = {nullptr, nullptr};
+    float *d_tab = nullptr;
+    hipStream_t stream = nullptr;
+    hipError_t err = hipSuccess;
+
+    bool ok(hipError_t e)
+    {
+        if (err == hipSuccess && e != hipSuccess)
+            err = e;
+        return err == hipSuccess;
+    }
+    bool begin(const void *arena, uint64_t bytes)
+    {
+        return ok(hipStreamCreate(&stream)) && ok(hipMalloc((void **)&d_arena, bytes)) &&
+               ok(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
+    }
+    bool descriptors(int k, const void *host, size_t bytes)
+    {
+        return ok(hipMalloc(&d_desc[k], bytes ? bytes : 16)) && (!bytes || ok(hipMemcpy(d_desc[k], host, bytes, hipMemcpyHostToDevice)));
+    }
+    bool tables()
+    {
+        return ok(hipMalloc((void **)&d_tab, sizeof(float) * kTuneTableFloats)) &&
+               ok(hipMemcpy(d_tab, tune_tables(), sizeof(float) * kTuneTableFloats, hipMemcpyHostToDevice));
+    }
+    // behind the launch: wait, bring the arena (and the device's copy of the tables) back, release everything
+    int end(hipError_t launched, void *arena, uint64_t bytes, float *tables_out)
+    {
+        if (ok(launched) && ok(hipStreamSynchronize(stream)) && ok(hipMemcpy(arena, d_arena, bytes, hipMemcpyDeviceToHost)) && tables_out && d_tab)
+            ok(hipMemcpy(tables_out, d_tab, sizeof(float) * kTuneTableFloats, hipMemcpyDeviceToHost));
+        if (d_tab) (void)hipFree(d_tab);
+        for (void *p : d_desc)
+            if (p) (void)hipFree(p);
+        if (d_arena) (void)hipFree(d_arena);
+        if (stream) (void)hipStreamDestroy(stream);
+        return (int)err;
+    }
+};
+
+// an offset of a descriptor as the pointer it stands for; false outside the arena
+template <class P>
+bool point(P &field, const char *d_arena, uint64_t bytes)
+{
+    const uint64_t off = (uint64_t)(uintptr_t)field;
+    if (off >= bytes)
+        return false;
+    field = (P)(d_arena + off);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// 0 GatherGroup, 1 GatherChan, 2 GatherSingle, 3 TuneDesc, 4 ResampleDesc
+int psk_prepass_probe_sizeof(int which)
+{
+    switch (which) {
+    case 0: return (int)sizeof(GatherGroup);
+    case 1: return (int)sizeof(GatherChan);
+    case 2: return (int)sizeof(GatherSingle);
+    case 3: return (int)sizeof(TuneDesc);
+    case 4: return (int)sizeof(ResampleDesc);
+    default: return -1;
+    }
+}
+
+// 0 kResamplePiece, 1 kResampleInputs, 2 kGatherTile, 3 kGatherMinGroup, 4 kTuneTableFloats
+int psk_prepass_probe_constant(int which)
+{
+    switch (which) {
+    case 0: return (int)kResamplePiece;
+    case 1: return (int)kResampleInputs;
+    case 2: return (int)kGatherTile;
+    case 3: return (int)kGatherMinGroup;
+    case 4: return (int)kTuneTableFloats;
+    default: return -1;
+    }
+}
+
+int psk_prepass_probe_gather_singles(void *arena, uint64_t bytes, int sample_bytes, const void *desc, uint32_t n_desc, uint64_t max_n)
+{
+    if (!arena || !bytes || !desc || !n_desc)
+        return (int)hipErrorInvalidValue;
+    std::vector<GatherSingle> d((const GatherSingle *)desc, (const GatherSingle *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (GatherSingle &s : d)
+        if (!point(s.src, r.d_arena, bytes) || !point(s.dst, r.d_arena, bytes))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(GatherSingle) * d.size()))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    return r.end(launch_gather_singles(sample_bytes, (const GatherSingle *)r.d_desc[0], n_desc, max_n, r.stream), arena, bytes, nullptr);
+}
+
+int psk_prepass_probe_gather_tiles(void *arena, uint64_t bytes, int sample_bytes, const void *groups, uint32_t n_groups, const void *chans,
+                                   uint32_t n_chans, uint64_t n_tiles)
+{
+    if (!arena || !bytes || !groups || !n_groups || !chans || !n_chans)
+        return (int)hipErrorInvalidValue;
+    std::vector<GatherGroup> g((const GatherGroup *)groups, (const GatherGroup *)groups + n_groups);
+    std::vector<GatherChan> c((const GatherChan *)chans, (const GatherChan *)chans + n_chans);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (GatherGroup &x : g)
+        if (!point(x.src, r.d_arena, bytes) || (uint64_t)x.first + x.g > n_chans)
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    for (GatherChan &x : c)
+        if (!point(x.dst, r.d_arena, bytes))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, g.data(), sizeof(GatherGroup) * g.size()) || !r.descriptors(1, c.data(), sizeof(GatherChan) * c.size()))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    return r.end(launch_gather_tiles(sample_bytes, (const GatherGroup *)r.d_desc[0], n_groups, (const GatherChan *)r.d_desc[1], n_tiles, r.stream),
+                 arena, bytes, nullptr);
+}
+
+// tables_out: kTuneTableFloats floats, the device's copy of tune_tables() as it is behind the launch
+int psk_prepass_probe_tune(void *arena, uint64_t bytes, const void *desc, uint32_t n_desc, uint64_t max_n, float *tables_out)
+{
+    if (!arena || !bytes || !desc || !n_desc)
+        return (int)hipErrorInvalidValue;
+    std::vector<TuneDesc> d((const TuneDesc *)desc, (const TuneDesc *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (TuneDesc &t : d)
+        if (!point(t.src, r.d_arena, bytes) || !point(t.dst, r.d_arena, bytes))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(TuneDesc) * d.size()) || !r.tables())
+        return r.end(hipSuccess, arena, 0, nullptr);
+    return r.end(launch_tune((const TuneDesc *)r.d_desc[0], n_desc, max_n, r.d_tab, r.stream), arena, bytes, tables_out);
+}
+
+int psk_prepass_probe_resample(void *arena, uint64_t bytes, const void *desc, uint32_t n_desc, uint64_t max_n_out)
+{
+    if (!arena || !bytes || !desc || !n_desc)
+        return (int)hipErrorInvalidValue;
+    std::vector<ResampleDesc> d((const ResampleDesc *)desc, (const ResampleDesc *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (ResampleDesc &t : d)
+        if (!point(t.src, r.d_arena, bytes) || !point(t.dst, r.d_arena, bytes) || !point(t.hist_in, r.d_arena, bytes) ||
+            !point(t.hist_out, r.d_arena, bytes))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(ResampleDesc) * d.size()) || !r.tables())
+        return r.end(hipSuccess, arena, 0, nullptr);
+    return r.end(launch_resample((const ResampleDesc *)r.d_desc[0], n_desc, max_n_out, r.d_tab, r.stream), arena, bytes, nullptr);
+}
+
+}  // extern "C"

@@ -91,10 +91,12 @@ def device_run(h, calls, capfd=None, check=None, sync_each=True, before=None, k0
                     continue
                 o, (cap, off) = outs[k][c], lay[k, c]
                 ns = int(o.n_symbols)
+                assert int(o.n_sampleIndex) in (0, ns), (k, c, int(o.n_sampleIndex), ns)
                 got[c].append(dict(soft=h.download(d_soft + off[1], (2 * ns,), np.float32),
                                    phase=h.download(d_phase + off[2], (ns,), np.float32),
                                    bits=h.download(d_bits + off[3], (int(o.n_bits),), np.int16),
-                                   index=h.download(d_sidx + off[4], (ns,), np.int16)))
+                                   # (n_sampleIndex is n_symbols, or 0 at samplesPerBaud 1: that row is not written)
+                                   index=h.download(d_sidx + off[4], (int(o.n_sampleIndex),), np.int16)))
     finally:
         for b in bufs:
             h.device_free(b)

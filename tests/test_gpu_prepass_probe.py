@@ -1,0 +1,83 @@
+"""The gather, tune and resample kernels by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim linked
+with the product's own psk_gather.o, psk_tune.o and psk_resample.o).  The demodulator behind these kernels shows one row sample
+in eight at samplesPerBaud 8; here every byte of the arena a launch ran in is compared with the arena
+the models expect -- a byte copy for the gathers, tests/tune_model.py for the tune kernel, tests/tune_model.py followed by
+tests/resample_model.py for the resample kernel: every row sample and both history slots bit for bit, no tolerance, and every
+source byte, every byte of row padding and every guard byte unchanged.  The inputs hold finite samples only.
+
+The inputs come from tests/prepass_probe_cases.py; tests/test_prepass_probe.py asserts, without a GPU, the launch shapes and the
+edges each of them reaches, and that the comparator reports a wrong store at its place."""
+import numpy as np
+import pytest
+
+from tests import prepass_probe as pp
+from tests import prepass_probe_cases as pc
+from tests import tune_model as tm
+
+pytestmark = pytest.mark.gpu
+
+
+def _clean(case, after, ctx):
+    found = case.check(after)
+    assert not found, "%s:\n%s" % (ctx, pp.messages(found))
+
+
+# ---- resample ------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("variant", range(4))
+def test_resample_one_packet_a_workgroup_per_piece(variant):
+    """one packet of 3P+1 outputs: four workgroups, a piece each (the shape the rest of the suite runs), in each format"""
+    case = pc.resample_shape(1, variant)
+    _clean(case, case.run(), "one packet, variant %d" % variant)
+
+
+@pytest.mark.parametrize("packets", [700, 1100, 2100])
+def test_resample_workgroups_that_walk_several_pieces(packets):
+    """700 packets: three workgroups a packet, up to three pieces each; 1100: two, the history's owner workgroup 0 for some
+    packets and 1 for others; 2100: one workgroup walks every piece, then writes the history.  All but ten packets have 1 .. 40
+    samples, some no output at all: their histories still move."""
+    case = pc.resample_shape(packets)
+    _clean(case, case.run(), "%d packets" % packets)
+
+
+def test_resample_arithmetic_edges():
+    """every step with the pos fractions 0, 255, 256 and 2^32 - 1; pos 2^33; samples scaled by 2^-130 (a flush to zero anywhere
+    would show) and up to 2^125; zeros of both signs at step 2^32, pos 0"""
+    case, kinds = pc.resample_edges()
+    _clean(case, case.run(), "arithmetic edges %s" % {k: (v[0], v[-1]) for k, v in kinds.items()})
+
+
+# ---- tune ------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("count", pc.TUNE_COUNTS)
+def test_tune(count):
+    """lengths at the edges of kTuneMinPiece and of the 512-sample unit, both loops of tune_piece with their tails, the four
+    formats, steps 0 (with a phase), 1, 2^63 and 2^64 - 1, packets scaled by 2^-130; and the device's tables behind the launch"""
+    case = pc.tune_case(count)
+    after, (C, F) = case.run()
+    wc, wf = tm.tables()
+    assert np.array_equal(C.view(np.uint32), wc.view(np.uint32)) and np.array_equal(F.view(np.uint32), wf.view(np.uint32)), "tune_tables()"
+    _clean(case, after, "%d tuned packets" % count)
+
+
+# ---- gathers ---------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("count", pc.SINGLES_COUNTS)
+@pytest.mark.parametrize("sample_bytes", [2, 4, 8])
+def test_gather_singles(sample_bytes, count):
+    case = pc.singles_case(sample_bytes, count)
+    _clean(case, case.run(), "%d singles of %d-byte samples" % (count, sample_bytes))
+
+
+@pytest.mark.parametrize("sample_bytes", [2, 4, 8])
+def test_gather_tiles_group_widths_and_ragged_columns(sample_bytes):
+    """groups 8, 9, 63, 64, 65 and 130 columns wide, the columns of each 1, 63, 64, 65 and 200 frames long"""
+    case = pc.tiles_widths_case(sample_bytes)
+    _clean(case, case.run(), "tile widths, %d-byte samples" % sample_bytes)
+
+
+@pytest.mark.parametrize("sample_bytes", [2, 4, 8])
+def test_gather_tiles_more_tiles_than_workgroups(sample_bytes):
+    """2100 groups of 8 columns by 10 frames: workgroups 0 .. 51 take a second tile"""
+    case = pc.tiles_many_case(sample_bytes)
+    _clean(case, case.run(), "%d tiles, %d-byte samples" % (case.n_tiles, sample_bytes))

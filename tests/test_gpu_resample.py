@@ -441,7 +441,63 @@ def test_a_refused_call_changes_nothing(oracle_mod, monkeypatch, capfd):
     _check(oracle_mod, plan, props, res, proxies, "refused call", skip=(1,))
 
 
-# ---- 7. schedules and quality records ----------------------------------------------------------------------------------------------------
+# ---- 7. a call of 1100 packets: workgroups that walk several pieces -------------------------------------------------------------------------
+
+def test_1100_packets_in_one_call_and_their_histories_carried(oracle_mod, monkeypatch, capfd):
+    """1100 resampled packets in one call: launch_resample gives a packet two workgroups, so the ten packets of 2P+1 .. 5P+3
+    outputs are walked by workgroups that take several pieces each, and the history behind them is written by workgroup 0 for
+    some and by workgroup 1 for others.  Those ten sit on channels with samplesPerBaud 1 and numAvg 0: every row sample is a
+    symbol.  The other packets have 1 .. 40 samples; every 50th has pos 2^33 and 1 or 2 samples -- no output, but its history
+    moves.  A second call reads the histories back and carries them.  What tests/test_gpu_prepass_probe.py cannot see is
+    checked here: the descriptor offsets, row offsets and history slots gather_stage computes for a call of this size."""
+    from psk_soft_amd import lib as pl
+
+    P = pl.resample_piece()
+    C, calls = 1100, 2
+    targets = (2 * P + 1, 3 * P, 4 * P + 2, 5 * P + 3, 2 * P + 1, 3 * P, 4 * P + 2, 5 * P + 3, 5 * P + 1, 2 * P + 2)
+    big = {3 + 110 * j: t for j, t in enumerate(targets)}
+    quiet = [c for c in range(C) if c % 50 == 10]
+    props = _props(C)
+    for c in big:
+        props[c] = dict(props[c], samplesPerBaud=1, numAvg=0)
+    dts = [DT[c % 4] for c in range(C)]
+    steps = [STEPS[(c + c // 4) % 4] for c in range(C)]
+    pos0 = [(c * 0x3243F6A9) % steps[c] for c in range(C)]
+    lens = [[1 + (13 * c) % 40 for c in range(C)], [1 + (7 * c + 3) % 40 for c in range(C)]]
+    for c, t in big.items():
+        lens[0][c], pos0[c] = _length_for(t, steps[c])
+        lens[1][c] = 300 + c % 7
+    for c in quiet:
+        lens[0][c], pos0[c] = 1 + (c // 50) % 2, 1 << 33
+    assert {1, 2, 3, 40} <= set(lens[0]) and not set(quiet) & set(big)
+    # every eighth channel is a single column of a matrix 7 wide: read where it lies, at its stride
+    place = [(c, 2) if c % 8 == 5 else None for c in range(C)]
+    widths = {c: 7 for c in range(C) if c % 8 == 5}
+    assert any(place[c] is not None for c in big) and any(place[c] is None for c in big)
+    data = _pieces(_signals(96700, props, [lens[0][c] + lens[1][c] for c in range(C)], dts), lens)
+    tsteps = [None if c % 3 == 0 else (tm.step_word(0.003), tm.step_word(-0.01), 1, NEG)[c % 4] for c in range(C)]
+    # even channels restart in call 0; odd ones, and every second packet without output, start from a history set in front of it
+    carried = [c % 2 == 1 or c % 100 == 10 for c in range(C)]
+    hist0 = [np.array([3.5, -1.25, 1e-3, 40.0, -7.0, 0.5], np.float32) * (c % 9 + 1) if carried[c] else None for c in range(C)]
+    restart = [[not carried[c] for c in range(C)], [c % 11 == 5 for c in range(C)]]
+    plan = Plan(data, steps, pos0, restart, tsteps, [(0x9E3779B97F4A7C15 * (c + 1)) % (1 << 64) for c in range(C)], hist0)
+    assert all(plan.n_out[0][c] == t for c, t in big.items()) and all(plan.n_out[0][c] == 0 for c in quiet)
+    assert any(plan.hist[0][c].any() for c in quiet), "a packet without output moved its history"
+    assert max(plan.n_out[0]) == 5 * P + 3 and sorted(plan.n_out[0])[-11] <= 80
+    proxies = []
+
+    def run(h, cf):
+        h.configure(0, props)
+        proxies.append(Resampled(h, plan))
+        return strided_run(proxies[-1], data, place, widths, cf)
+
+    res = untraced_then_traced(monkeypatch, capfd, {}, C, run)
+    for k, lines in enumerate(res[1][1]):
+        assert resamples_of(lines) == [C] and lines[0]["what"] == "resample" and not tunes_of(lines) and gathers(lines) == (0, 0, 0, 0), (k, lines[:3])
+    _check(oracle_mod, plan, props, res, proxies, "1100 packets")
+
+
+# ---- 8. schedules and quality records ----------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("schedule", ["time_tiled", "deferred_join", "quality"])
 def test_schedules_and_quality_records(oracle_mod, monkeypatch, capfd, schedule):

@@ -146,10 +146,12 @@ def strided_run(h, calls, place, widths, capfd=None, check=None, sync_each=True,
                     continue
                 o, (cap, off) = outs[k][c], lay[k, c]
                 ns = int(o.n_symbols)
+                assert int(o.n_sampleIndex) in (0, ns), (k, c, int(o.n_sampleIndex), ns)
                 got[c].append(dict(soft=h.download(d_soft + off[0], (2 * ns,), np.float32),
                                    phase=h.download(d_phase + off[1], (ns,), np.float32),
                                    bits=h.download(d_bits + off[2], (int(o.n_bits),), np.int16),
-                                   index=h.download(d_sidx + off[3], (ns,), np.int16)))
+                                   # (n_sampleIndex is n_symbols, or 0 at samplesPerBaud 1: that row is not written)
+                                   index=h.download(d_sidx + off[3], (int(o.n_sampleIndex),), np.int16)))
         after = np.array(h_src) if host_mem else h.download(base, (src.size,), np.uint8)
         assert np.array_equal(after, src), "the source buffer changed"
     finally:
