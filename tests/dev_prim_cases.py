@@ -2,8 +2,9 @@
 
 Everything here is pure: a case set is drawn from a generator seeded by its own name (section 4.2's rule), its sha256 is pinned in
 tests/golden/dev_prim_cases.json.  The reference side is the oracle's exported primitives (array forms, oracle/psk_soft_oracle.h),
-this machine's glibc through them, IEEE division, and numpy models of pure data movement and of the DPP step order that
-psk_wave.h documents -- never the code under test.  The one exception the design asks for: lm_slice8_fast's `near` flag is held
+this machine's glibc through them, IEEE division, and numpy models of pure data movement, of the DPP step order that
+psk_wave.h documents and of what psk_tile_any.h's reductions are to compute (the maximum and the minimum over 64 values, the
+merge's three lines) -- never the code under test.  The one exception the design asks for: lm_slice8_fast's `near` flag is held
 to the host build of the same header (tests/support/libm_host.cpp), which tests/test_dev_prim_cases.py pins on the CPU.
 
 A `kind` is an input domain; several operations and forms share the cases of a kind (tests/test_gpu_dev_prims.py: FORMS)."""
@@ -514,10 +515,109 @@ def _med3_sets():
     return [("specials", _grid(s, s, s)), ("random", tuple(r))]
 
 
+# ---- the first-maximum reductions of psk_tile_any.h: a case is a wave of 64 values (times U for the level-by-level forms) ----
+ANY_PAIR_LANES = (0, 15, 16, 31, 32, 47, 48, 63)  # the first and last lane of every DPP row: both sides of each cross-row step
+ANY_PAIRS = tuple((a, b) for i, a in enumerate(ANY_PAIR_LANES) for b in ANY_PAIR_LANES[i + 1:])
+ANY_U = 8  # the width psk_tile_front_any_kernel<1> instantiates
+N_ANY_RANDOM = 512
+
+
+def _any_finite(rng, shape):
+    """doubles of both signs over 2^+-40"""
+    return np.ldexp(1.0 + rng.random(shape), rng.integers(-40, 41, shape).astype(np.int32)) * rng.choice([-1.0, 1.0], shape)
+
+
+def _any_f64_waves(rng):
+    """Named runs of waves for the maximum: the extremum in each lane in turn (far above the others; one ulp above 64 equal
+    values), equal extrema in two lanes for every pair of ANY_PAIR_LANES, all lanes equal, -inf in every lane but one, finite
+    values next to NaN (some lanes; every lane but one), random bit patterns (a NaN among them made the quiet one: what an
+    addition leaves behind)."""
+    ar = np.arange(64)
+    far = _any_finite(rng, (64, 64))
+    far[ar, ar] = np.ldexp(1.0 + rng.random(64), 41)
+    base = _any_finite(rng, 64)
+    ulp = np.repeat(base[:, None], 64, axis=1)
+    ulp[ar, ar] = np.nextafter(base, np.inf)
+    pairs = _any_finite(rng, (len(ANY_PAIRS), 64))
+    for w, (a, b) in enumerate(ANY_PAIRS):
+        pairs[w, a] = pairs[w, b] = np.ldexp(1.0 + rng.random(), 41)
+    vals = np.array([0.1, 1.0, -3.0, 2.0 ** -1040, 0.0, -0.0, -np.inf, np.inf, 1e300, -1e300], f64)
+    equal = np.repeat(vals[:, None], 64, axis=1)
+    zeros = np.where(rng.random((8, 64)) < 0.5, 0.0, -0.0)  # zeros of both signs, some above negative values only
+    zeros[4:][rng.random((4, 64)) < 0.5] = -1.5
+    one = np.full((64, 64), -np.inf)
+    one[ar, ar] = _any_finite(rng, 64)
+    some_nan = _any_finite(rng, (64, 64))
+    some_nan[rng.random((64, 64)) < rng.random((64, 1))] = np.nan
+    lane = rng.permutation(64)
+    some_nan[ar, lane] = np.nan
+    some_nan[ar, (lane + rng.integers(1, 64, 64)) % 64] = _any_finite(rng, 64)  # (a NaN and a finite value in every wave)
+    but_one = np.full((64, 64), np.nan)
+    but_one[ar, ar] = _any_finite(rng, 64)
+    rnd = _random_f64(rng, N_ANY_RANDOM * 64).reshape(-1, 64).copy()
+    rnd[np.isnan(rnd)] = np.nan
+    return [("each_lane", np.concatenate([far, ulp])), ("pairs", pairs), ("equal", np.concatenate([equal, zeros])), ("inf_but_one", one),
+            ("nan", np.concatenate([some_nan, but_one])), ("random", rnd)]
+
+
+def _any_u32_waves(rng):
+    """The same for the unsigned minimum: the extremum in each lane in turn (far below; one below 64 equal values), equal
+    minima in two lanes for every pair, all lanes equal, 0xFFFFFFFF in every lane but one, random (values on both sides of
+    2^31 in every wave: a signed comparison shows)."""
+    ar = np.arange(64)
+    far = rng.integers(1 << 16, 1 << 32, (64, 64), dtype=u64).astype(u32)
+    far[ar, ar] = rng.integers(0, 1 << 16, 64, dtype=u64).astype(u32)
+    base = rng.integers(1, 1 << 32, 64, dtype=u64).astype(u32)
+    base[::4] = 0x80000000  # (one below: the largest positive int)
+    one_below = np.repeat(base[:, None], 64, axis=1)
+    one_below[ar, ar] = base - u32(1)
+    pairs = rng.integers(1 << 16, 1 << 32, (len(ANY_PAIRS), 64), dtype=u64).astype(u32)
+    for w, (a, b) in enumerate(ANY_PAIRS):
+        pairs[w, a] = pairs[w, b] = u32(rng.integers(0, 1 << 16))
+    equal = np.repeat(np.array([0, 0xFFFFFFFF, 0x80000000, 0x7FFFFFFF, 7], u32)[:, None], 64, axis=1)
+    one = np.full((64, 64), 0xFFFFFFFF, u32)
+    one[ar, ar] = rng.integers(0, 1 << 32, 64, dtype=u64).astype(u32)
+    one[ar[::8], ar[::8]] = u32(0xFFFFFFFE)
+    rnd = rng.integers(0, 1 << 32, (N_ANY_RANDOM, 64), dtype=u64).astype(u32)
+    return [("each_lane", np.concatenate([far, one_below])), ("pairs", pairs), ("equal", equal), ("max_but_one", one), ("random", rnd)]
+
+
+ANY_MERGE_VALUES = np.array([-np.inf, -1.0, -0.0, 0.0, 1.0, 1.0 + 2.0 ** -52, 2.5, 1e300, np.inf, np.nan], f64)
+ANY_MERGE_K = np.array([0, 1, 15, 16, 63, 64, 1023, 0x7FFFFFFF], i32)  # (0x7fffffff: the sentinel the front stage starts from)
+
+
+def _any_merge_sets():
+    """(a.best, a.second, b.best, b.second, a.k, b.k).  `best_k`: every pair of values with every pair of phases, both seconds
+    -inf as the front stage builds its operands -- equal `best` with the lower phase on either side, and equal `k`;
+    `seconds`: every combination of the four doubles with the phases in either order; `random`: all six drawn from the pools,
+    so that a tie is common."""
+    V, K = ANY_MERGE_VALUES, ANY_MERGE_K
+    ab, bb, ak, bk = _grid(V, V, K, K)
+    ninf = np.full(ab.size, -np.inf)
+    out = [("best_k", (ab, ninf, bb, ninf.copy(), ak, bk))]
+    ab, as_, bb, bs, flip = _grid(V, V, V, V, np.array([0, 1], i32))
+    out.append(("seconds", (ab, as_, bb, bs, np.where(flip, 5, 3).astype(i32), np.where(flip, 3, 5).astype(i32))))
+    rng = _rng("any_merge/random")
+    n = 1 << 16
+    out.append(("random", tuple(V[rng.integers(0, V.size, n)] for _ in range(4)) + tuple(K[rng.integers(0, K.size, n)] for _ in range(2))))
+    return out
+
+
+def _any_sets(kind):
+    base = kind.split("/")[0]
+    waves = _any_f64_waves if "f64" in base else _any_u32_waves
+    if "/" not in kind:
+        return [(name, (w.ravel(),), 64) for name, w in waves(_rng(kind + "/waves"))]
+    U = int(kind.split("/")[1])  # each of the U interleaved reductions has data of its own
+    per = [waves(_rng("%s/%d" % (kind, k))) for k in range(U)]
+    return [(name, (np.stack([p[j][1] for p in per], axis=2).ravel(),), 64 * U) for j, (name, _) in enumerate(per[0])]
+
+
+ANY_KINDS = ("any_f64", "any_u32", "any_f64_multi/%d" % ANY_U, "any_u32_multi/%d" % ANY_U)
 WAVE_KINDS = (("scan_f64", "scan_i32") + tuple("scan_f32_multi/%d" % n for n in range(1, 33)) + ("max_f32", "u32")
-              + tuple("up1/" + t for t in ("i32", "f32", "f64")) + tuple("read_lane/" + t for t in ("f32", "f64")))
+              + tuple("up1/" + t for t in ("i32", "f32", "f64")) + tuple("read_lane/" + t for t in ("f32", "f64")) + ANY_KINDS)
 POINT_KINDS = (("atan2", "sincos", "slice8", "norm", "qpsk", "cmul", "cdiv") + tuple("cpow/%d" % m for m in CPOW_M)
-               + ("div_known", "to_long", "wrap_test", "unwrap", "fit_den", "fit_value", "med3"))
+               + ("div_known", "to_long", "wrap_test", "unwrap", "fit_den", "fit_value", "med3", "any_merge"))
 KINDS = POINT_KINDS + ("fit_known",) + WAVE_KINDS
 
 
@@ -534,6 +634,10 @@ def case_sets(kind):
         raw = _cpow_sets(int(kind.split("/")[1]))
     elif kind in ("norm", "qpsk"):
         raw = _pair_sets(kind)
+    elif kind in ANY_KINDS:
+        raw = _any_sets(kind)
+    elif kind == "any_merge":
+        raw = _any_merge_sets()
     else:
         raw = {"atan2": _atan2_sets, "sincos": _sincos_sets, "slice8": _slice8_sets, "cmul": _cmul_sets, "cdiv": _cdiv_sets,
                "div_known": _div_known_sets, "to_long": _to_long_sets, "wrap_test": _wrap_test_sets, "unwrap": _unwrap_sets,
@@ -545,7 +649,7 @@ def case_sets(kind):
 def unit_of(kind):
     """elements of an input per case: 64 for a wave (times N for the interleaved scans), 64 for fit_known's uniform waves"""
     if kind in WAVE_KINDS:
-        return 64 * (int(kind.split("/")[1]) if kind.startswith("scan_f32_multi/") else 1)
+        return 64 * (int(kind.split("/")[1]) if "_multi/" in kind else 1)
     return 64 if kind == "fit_known" else 1
 
 
@@ -813,15 +917,32 @@ def reference(op, inputs, param=0):
         w = v.reshape(-1, 64)
         lane = inputs[1].reshape(-1, 64)[:, 0] & 63
         return (np.repeat(w[np.arange(w.shape[0]), lane], 64),)
+    # ---- psk_tile_any.h: "the maximum over 64 values" (fmax: a NaN next to a number drops out), "the minimum over 64 values",
+    # and the three lines of the merge -- every lane holds the result
+    if op in ("any_max_f64", "any_min_u32"):
+        w = v.reshape(-1, 64)
+        return (np.repeat(np.fmax.reduce(w, axis=1) if op == "any_max_f64" else w.min(axis=1), 64),)
+    if op in ("any_max_f64_multi", "any_min_u32_multi"):
+        w = v.reshape(-1, 64, param)
+        r = np.fmax.reduce(w, axis=1) if op == "any_max_f64_multi" else w.min(axis=1)
+        return (np.ascontiguousarray(np.broadcast_to(r[:, None, :], w.shape)).ravel(),)
+    if op == "any_merge":
+        ab, as_, bb, bs, ak, bk = inputs
+        with np.errstate(invalid="ignore"):
+            b_wins = (bb > ab) | ((bb == ab) & (bk < ak))  # the larger sum, the lower phase on a tie
+            loser = np.where(b_wins, ab, bb)
+            s2 = np.where(as_ > bs, as_, bs)
+            return (np.where(b_wins, bb, ab), np.where(loser > s2, loser, s2), np.where(b_wins, bk, ak))
     raise KeyError(op)
 
 
 # =====================================================================================================================
 # the comparison rule: the suite's own (tests/test_gpu_parity.py: assert_parity), per element
 # =====================================================================================================================
-def differs(got, ref, raw=False):
+def differs(got, ref, raw=False, zeros=False):
     """True where got is not ref: every finite value by its bit pattern (signed zeros included), infinities by position and
-    sign, NaN by position only; integers equal.  raw: bit patterns throughout (pure data movement)."""
+    sign, NaN by position only; integers equal.  raw: bit patterns throughout (pure data movement).  zeros: a zero of either
+    sign equals a zero of the other (psk_tile_any.h: the callers only test the results with ==)."""
     got, ref = np.asarray(got), np.asarray(ref)
     assert got.dtype == ref.dtype and got.shape == ref.shape, (got.dtype, ref.dtype, got.shape, ref.shape)
     if got.dtype.kind != "f":
@@ -830,6 +951,8 @@ def differs(got, ref, raw=False):
     d = got.view(ut) != ref.view(ut)
     if raw:
         return d
+    if zeros:
+        d &= ~((got == 0) & (ref == 0))
     return d & ~(np.isnan(got) & np.isnan(ref))
 
 
@@ -848,7 +971,8 @@ def hexes(inputs, i):
 class Form:
     """label; op and param of tests/dev_prims_lib.py; kind; n_in: the leading inputs of the kind the op takes;
     divergent: run once more inside a lane-divergent branch; rule: "all", "finite" (the screened tier: wherever the oracle's
-    result is finite in both parts), "slice8_fast" (sector wherever near is false, near everywhere), "raw" (bit patterns)"""
+    result is finite in both parts), "slice8_fast" (sector wherever near is false, near everywhere), "raw" (bit patterns),
+    "zeros" (as "all", zeros of either sign equal)"""
 
     def __init__(self, family, label, op, kind, param=0, divergent=False, rule="all", n_in=None):
         self.family, self.label, self.op, self.kind, self.param = family, label, op, kind, param
@@ -900,11 +1024,16 @@ def _forms():
     add("wave", "read_lane(f32)", "read_lane", "read_lane/f32", 1, rule="raw")
     add("wave", "read_lane(f64)", "read_lane", "read_lane/f64", 2, rule="raw")
     add("wave", "med3_i32", "med3", "med3")
+    add("any", "any_merge", "any_merge", "any_merge", rule="zeros")
+    add("any", "any_max_f64", "any_max_f64", "any_f64", rule="zeros")
+    add("any", "any_min_u32", "any_min_u32", "any_u32")
+    add("any", "any_max_f64_multi<%d>" % ANY_U, "any_max_f64_multi", "any_f64_multi/%d" % ANY_U, ANY_U, rule="zeros")
+    add("any", "any_min_u32_multi<%d>" % ANY_U, "any_min_u32_multi", "any_u32_multi/%d" % ANY_U, ANY_U)
     return T
 
 
 FORMS = _forms()
-FAMILIES = ("libm", "slicing", "complex", "cpow", "unwrap_fit", "fit_known", "wave")
+FAMILIES = ("libm", "slicing", "complex", "cpow", "unwrap_fit", "fit_known", "wave", "any")
 assert {f.family for f in FORMS} == set(FAMILIES) and {f.kind for f in FORMS} == set(KINDS)
 
 

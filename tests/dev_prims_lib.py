@@ -43,7 +43,14 @@ OPS = {
     "up1_zero": (26, lambda p: (_T[p],), lambda p: (_T[p],), False),
     "read_lane": (27, lambda p: (_T[p], i32), lambda p: (_T[p],), False),
     "med3": (28, (i32, i32, i32), (i32,), True),
+    # psk_tile_any.h: the front stages call these with the whole wave, none has a lane-divergent form
+    "any_merge": (29, (f64, f64, f64, f64, i32, i32), (f64, f64, i32), False),  # a.best, a.second, b.best, b.second, a.k, b.k
+    "any_max_f64": (30, (f64,), (f64,), False),
+    "any_min_u32": (31, (u32,), (u32,), False),
+    "any_max_f64_multi": (32, (f64,), (f64,), False),  # parameter U = 8: arrays of n * U elements, case-major
+    "any_min_u32_multi": (33, (u32,), (u32,), False),
 }
+MULTI = ("scan_f32_multi", "any_max_f64_multi", "any_min_u32_multi")  # the parameter is the number of elements per case
 TAB_DEV, TAB_WAVE = 0, 1  # the parameter of atan2 / slice8 / slice8_atan
 
 
@@ -81,7 +88,7 @@ def run(name, inputs, param=0, divergent=False):
     if _failed is not None:
         raise RuntimeError("not run: an earlier call failed (%s)" % _failed)
     oid, ins, outs, div = signature(name, param)
-    mult = param if name == "scan_f32_multi" else 1
+    mult = param if name in MULTI else 1
     assert len(inputs) == len(ins), name
     n = inputs[0].size // mult
     assert n > 0 and n % 64 == 0, (name, n)

@@ -1,5 +1,5 @@
 // dev_prims.hip -- TEST SUPPORT: every device-math and wave primitive of the product headers (psk_libm.h,
-// psk_device_math.h, psk_wave.h, psk_wave_scan_gen.h) behind an elementwise kernel of its own, so that tests can hold
+// psk_device_math.h, psk_wave.h, psk_wave_scan_gen.h, and the first-maximum reductions of psk_tile_any.h) behind an elementwise kernel of its own, so that tests can hold
 // each of them, run on the device by itself, to the oracle bit for bit (tests/test_gpu_dev_prims.py).
 //
 // The headers are included unchanged and this file is compiled with the product's flags (psk_soft_amd/csrc/Makefile,
@@ -12,11 +12,13 @@
 //   launches, synchronises, copies back and returns the HIP error code (hipErrorInvalidValue for a bad op or n).
 // With PSK_DP_DIVERGENT the primitive runs inside a lane-divergent branch, twice: first with the lanes of LANE_MASK_A
 // active, then in a second launch with the others; either way only some of lanes 0-29 are active.  The forms that read the
-// range table from lanes (AtanTabDev) need every lane active and are refused in that mode.
+// range table from lanes (AtanTabDev) need every lane active and are refused in that mode; so are the reductions of
+// psk_tile_any.h, which the front stages call with the whole wave.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "psk_wave.h"
+#include "psk_tile_any.h"
 
 using namespace psk;
 
@@ -51,12 +53,17 @@ enum {
     OP_UP1_ZERO = 26,  // param: type                             in v                          out
     OP_READ_LANE = 27,  // param: 1 float, 2 double               in v, lane (i32, the wave's first counts)   out
     OP_MED3 = 28,      //                                         in a, b, c (i32)              out i32
+    OP_ANY_MERGE = 29,  //                 in a.best, a.second, b.best, b.second (f64), a.k, b.k (i32)   out best, second (f64), k (i32)
+    OP_ANY_MAX_F64 = 30,  //                                      in f64                        out f64 (every lane)
+    OP_ANY_MIN_U32 = 31,  //                                      in u32                        out u32 (every lane)
+    OP_ANY_MAX_F64_MULTI = 32,  // param: U = 8                   in f64 [n][U]                 out f64 [n][U]
+    OP_ANY_MIN_U32_MULTI = 33,  // param: U = 8                   in u32 [n][U]                 out u32 [n][U]
     OP_COUNT
 };
 constexpr int PSK_DP_DIVERGENT = 1 << 30;
 constexpr uint64_t LANE_MASK_A = 0x9249A4D2B5A56A95ull;  // 30 lanes, 16 of them among lanes 0-29
 
-constexpr int MAX_IN = 4, MAX_OUT = 3;
+constexpr int MAX_IN = 6, MAX_OUT = 3;
 struct Args {
     const void *in[MAX_IN];
     void *out[MAX_OUT];
@@ -305,6 +312,48 @@ struct Med3 {
         st<int>(a, 0, i, med3_i32(ld<int>(a, 0, i), ld<int>(a, 1, i), ld<int>(a, 2, i)));
     }
 };
+struct AnyMerge {
+    static __device__ __forceinline__ void run(const Args &a, long long i, int)
+    {
+        AnyTop x, y;
+        x.best = ld<double>(a, 0, i), x.second = ld<double>(a, 1, i), x.k = ld<int>(a, 4, i);
+        y.best = ld<double>(a, 2, i), y.second = ld<double>(a, 3, i), y.k = ld<int>(a, 5, i);
+        const AnyTop r = any_merge(x, y);
+        st<double>(a, 0, i, r.best);
+        st<double>(a, 1, i, r.second);
+        st<int>(a, 2, i, r.k);
+    }
+};
+struct AnyMaxF64 {
+    static __device__ __forceinline__ void run(const Args &a, long long i, int) { st<double>(a, 0, i, any_max_f64(ld<double>(a, 0, i))); }
+};
+struct AnyMinU32 {
+    static __device__ __forceinline__ void run(const Args &a, long long i, int) { st<uint32_t>(a, 0, i, any_min_u32(ld<uint32_t>(a, 0, i))); }
+};
+template <int U>
+struct AnyMaxF64Multi {
+    static __device__ __forceinline__ void run(const Args &a, long long i, int)
+    {
+        double v[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) v[k] = ld<double>(a, 0, i * U + k);
+        any_max_f64_multi(v);
+#pragma unroll
+        for (int k = 0; k < U; k++) st<double>(a, 0, i * U + k, v[k]);
+    }
+};
+template <int U>
+struct AnyMinU32Multi {
+    static __device__ __forceinline__ void run(const Args &a, long long i, int)
+    {
+        unsigned v[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) v[k] = ld<uint32_t>(a, 0, i * U + k);
+        any_min_u32_multi(v);
+#pragma unroll
+        for (int k = 0; k < U; k++) st<uint32_t>(a, 0, i * U + k, v[k]);
+    }
+};
 
 // every lane of every wave active: the grid is exactly n / 64 blocks of 64 threads
 template <class Op>
@@ -403,6 +452,19 @@ extern "C" int psk_dev_prims_run(int op, const void *const *in, void *const *out
     case OP_UP1_ZERO: shape(1, tsz, 0, 0, 0, 1, tsz, 0, 0, true); break;
     case OP_READ_LANE: shape(2, tsz, F, 0, 0, 1, tsz, 0, 0, true); break;
     case OP_MED3: shape(3, F, F, F, 0, 1, F, 0, 0, false); break;
+    case OP_ANY_MERGE:
+        shape(6, D, D, D, D, 3, D, D, F, true);
+        s.in_sz[4] = s.in_sz[5] = F;
+        break;
+    case OP_ANY_MAX_F64: shape(1, D, 0, 0, 0, 1, D, 0, 0, true); break;
+    case OP_ANY_MIN_U32: shape(1, F, 0, 0, 0, 1, F, 0, 0, true); break;
+    case OP_ANY_MAX_F64_MULTI:
+    case OP_ANY_MIN_U32_MULTI:
+        if (param != 8)  // (the one width the front stage instantiates)
+            return (int)hipErrorInvalidValue;
+        shape(1, id == OP_ANY_MAX_F64_MULTI ? D : F, 0, 0, 0, 1, id == OP_ANY_MAX_F64_MULTI ? D : F, 0, 0, true);
+        s.mult = param;
+        break;
     default: return (int)hipErrorInvalidValue;
     }
     if (divergent && s.whole_wave)
@@ -466,6 +528,11 @@ extern "C" int psk_dev_prims_run(int op, const void *const *in, void *const *out
             break;
         case OP_READ_LANE: e = param == 2 ? launch<ReadLane<double>>(a, n, false) : launch<ReadLane<float>>(a, n, false); break;
         case OP_MED3: e = launch<Med3>(a, n, divergent); break;
+        case OP_ANY_MERGE: e = launch<AnyMerge>(a, n, false); break;
+        case OP_ANY_MAX_F64: e = launch<AnyMaxF64>(a, n, false); break;
+        case OP_ANY_MIN_U32: e = launch<AnyMinU32>(a, n, false); break;
+        case OP_ANY_MAX_F64_MULTI: e = launch<AnyMaxF64Multi<8>>(a, n, false); break;
+        case OP_ANY_MIN_U32_MULTI: e = launch<AnyMinU32Multi<8>>(a, n, false); break;
         default: e = hipErrorInvalidValue; break;
         }
     }

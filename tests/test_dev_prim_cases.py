@@ -50,18 +50,25 @@ def test_the_table_lists_every_operation_and_form():
     """every entry of the device library is driven, in every form the issue lists, and the library is built the product's way"""
     assert {f.op for f in dc.FORMS} == set(dp.OPS)
     labels = {f.label for f in dc.FORMS}
-    assert len(labels) == len(dc.FORMS) == 88
+    assert len(labels) == len(dc.FORMS) == 93
     for N in range(1, 33):
         assert "wave_scan_f32_multi<%d>" % N in labels
     for M in (1, 2, 3, 4, 5, 8, 16, 64):
         assert {"cpow_uint<true>(M=%d)" % M, "cpow_uint<false>(M=%d)" % M} <= labels
+    assert {"any_merge", "any_max_f64", "any_min_u32", "any_max_f64_multi<8>", "any_min_u32_multi<8>"} <= labels
+    for f in dc.FORMS:
+        if f.family == "any":  # psk_tile_any.h: whole waves only, refused in the divergent mode like the AtanTabDev forms
+            assert not f.divergent and not dp.signature(f.op, f.param)[3], f.label
     for f in dc.FORMS:  # a lane-divergent run only of what has one, and of everything behind an __any guard or AtanTabWave
         _, _, _, can = dp.signature(f.op, f.param)
         assert can or not f.divergent, f.label
     guarded = {"atan2f_wave<AtanTabWave>", "sincosf_wave(dep=0)", "slice_8psk<AtanTabWave>", "slice_8psk_atan<AtanTabWave>",
                "cmul<true>", "cdiv<true>"} | {"cpow_uint<true>(M=%d)" % M for M in dc.CPOW_M}
     assert {f.label for f in dc.FORMS if f.divergent} == guarded
+    src = open(os.path.join(ROOT, "tests", "support", "dev_prims.hip")).read()
+    assert '#include "psk_tile_any.h"' in src  # (the header itself, unchanged: not a copy of its functions)
     mk = open(os.path.join(ROOT, "psk_soft_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^\$\(OBJDIR\)/dev_prims\.o:.*\bpsk_tile_any\.h\b", mk, re.M)
     rule = re.search(r"^\$\(OBJDIR\)/dev_prims\.o:.*\n\t(.*)$", mk, re.M).group(1)
     assert rule == "$(HIPCC) --offload-arch=$(ARCH) $(CXXFLAGS) -c ../../tests/support/dev_prims.hip -o $@"
     assert "dev_prims" not in re.search(r"^\$\(LIB\):.*$", mk, re.M).group(0)
@@ -266,3 +273,52 @@ def test_division_numerators_of_every_kind(cases):
         for v in (ys, xys):
             assert ((v == 0) & np.signbit(v)).any() and np.isinf(v).any() and np.isnan(v).any(), kind
             assert ((np.abs(v) > 0) & (np.abs(v) < tiny)).any() and (np.abs(v) > 1e300).any(), kind
+
+
+def test_first_maximum_cases_reach_every_lane_and_tie(cases):
+    """psk_tile_any.h's case sets: the extremum sits in each of the 64 lanes in turn (far from the others and one step from
+    them), equal extrema occur in every pair of lanes from {0, 15, 16, 31, 32, 47, 48, 63} and nowhere else in the wave, every
+    lane but one holds the identity (-inf, 0xFFFFFFFF) for each of the 64 lanes, finite values stand next to NaN (and the
+    reference drops the NaN), the unsigned values lie on both sides of 2^31 -- in each of the eight interleaved planes too,
+    which all differ; the merges hold equal `best` with the lower phase on either side, and equal phases."""
+    for kind in dc.ANY_KINDS:
+        c = cases(kind)[0]
+        U = c.unit // 64
+        v = c.inputs[0].reshape(-1, 64, U)
+        is_f = v.dtype == f64
+        names = [n.rsplit("/", 1)[1] for n in c.sets]
+        assert len({v[:, :, u].tobytes() for u in range(U)}) == U, kind
+        for u in range(U):
+            w = v[:, :, u]
+            part = {n: w[c.set_of == j] for j, n in enumerate(names)}
+            best = (lambda x: np.fmax.reduce(x, axis=1)) if is_f else (lambda x: x.min(axis=1))
+            e = part["each_lane"]
+            hit = e == best(e)[:, None]
+            assert (hit.sum(axis=1) == 1).all() and np.array_equal(np.nonzero(hit[:64])[1], np.arange(64)), kind
+            assert np.array_equal(np.nonzero(hit[64:])[1], np.arange(64)), kind
+            rest = e[64:][~hit[64:]].reshape(64, 63)  # (one step from 63 equal values)
+            assert (rest == rest[:, :1]).all(), kind
+            p = part["pairs"]
+            hit = p == best(p)[:, None]
+            assert [tuple(np.nonzero(h)[0]) for h in hit] == list(dc.ANY_PAIRS) and len(dc.ANY_PAIRS) == 28, kind
+            one = part["inf_but_one" if is_f else "max_but_one"]
+            ident = np.isneginf(one) if is_f else one == 0xFFFFFFFF
+            assert ((~ident).sum(axis=1) <= 1).all() and np.array_equal(np.nonzero(~ident | np.eye(64, dtype=bool))[1], np.arange(64)), kind
+            eq = part["equal"][: (10 if is_f else 5)]
+            assert (eq.view(np.uint64 if is_f else u32) == eq.view(np.uint64 if is_f else u32)[:, :1]).all(), kind
+            if is_f:
+                n = part["nan"]
+                assert (np.isnan(n).any(axis=1) & np.isfinite(n).any(axis=1)).all() and np.isfinite(best(n)).all(), kind
+                assert (np.isfinite(n).sum(axis=1) == 1).sum() >= 64, kind
+                z = part["equal"][10:]
+                assert (np.signbit(z) & (z == 0)).any() and (~np.signbit(z) & (z == 0)).any(), kind
+            else:
+                r = part["random"]
+                assert ((r < 1 << 31).any(axis=1) & (r >= 1 << 31).any(axis=1)).all(), kind
+                assert (r.astype(np.int32).min(axis=1).astype(u32) != r.min(axis=1)).mean() > 0.9, kind  # a signed minimum is another
+    ab, as_, bb, bs, ak, bk = cases("any_merge")[0].inputs
+    tie = ab == bb
+    assert (tie & (ak < bk)).sum() > 1000 and (tie & (ak > bk)).sum() > 1000 and (tie & (ak == bk)).sum() > 100
+    best, second, k = dc.reference("any_merge", (ab, as_, bb, bs, ak, bk))
+    assert (k[tie] == np.minimum(ak, bk)[tie]).all()  # the first of equal sums
+    assert ((ab == 0) & (bb == 0) & (np.signbit(ab) != np.signbit(bb))).any() and np.isnan(ab).any() and (ak == 0x7FFFFFFF).any()

@@ -1,5 +1,5 @@
-"""Every device-math and wave primitive of psk_libm.h, psk_device_math.h, psk_wave.h and psk_wave_scan_gen.h run on the GPU
-by itself (tests/support/dev_prims.hip, compiled with the product's flags into psk_soft_amd/libpsk_dev_prims.so) and held bit
+"""Every device-math and wave primitive of psk_libm.h, psk_device_math.h, psk_wave.h, psk_wave_scan_gen.h and psk_tile_any.h run
+on the GPU by itself (tests/support/dev_prims.hip, compiled with the product's flags into psk_soft_amd/libpsk_dev_prims.so) and held bit
 for bit to the reference side of tests/dev_prim_cases.py: the oracle's exported primitives, this machine's glibc, numpy models
 of the documented DPP step order.  The comparison rule is assert_parity's, per element and without a tolerance.  Every case set
 runs grouped by class (whole waves ordinary, whole waves rare) and under a fixed shuffle (rare and ordinary lanes share waves:
@@ -47,7 +47,7 @@ def run_family(family):
                 want = dc.take(ref, ix, c.unit)
                 got = dp.run(form.op, ins, form.param, divergent=divergent)
                 for k, mask in enumerate(dc.compare_mask(form, want)):
-                    bad = dc.differs(got[k], want[k], raw=form.rule == "raw")
+                    bad = dc.differs(got[k], want[k], raw=form.rule == "raw", zeros=form.rule == "zeros")
                     if mask is not None:
                         bad &= mask
                     compared += int(bad.size if mask is None else mask.sum())
@@ -93,3 +93,12 @@ def test_fit_known():
 def test_wave_primitives():
     """the DPP scans (all 32 generated interleaved ones among them), maxima and minima, lane shifts and reads, v_med3_i32"""
     run_family("wave")
+
+
+def test_first_maximum_reductions():
+    """psk_tile_any.h, the reductions behind every timing pick of the run-time and wide front stages: any_merge, any_max_f64,
+    any_min_u32 and their level-by-level forms of eight, held to "the maximum over 64 values", "the minimum over 64 values"
+    and the merge's three lines -- the extremum in every lane in turn, equal extrema on both sides of every DPP row boundary,
+    -inf / 0xFFFFFFFF in every lane but one, finite values next to NaN; zeros of either sign count as equal (the callers only
+    test ==)"""
+    run_family("any")
