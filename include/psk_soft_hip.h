@@ -372,6 +372,101 @@ psk_soft_status psk_soft_resample_apply(const psk_soft_resample_t *rs, const flo
                                         uint64_t n_complex, float *out, float *hist_out /* [6] or NULL */);
 uint32_t psk_soft_resample_piece(void);     /* outputs of one workgroup's piece of the device's pass (tests: the lengths at its edges) */
 
+/* ---- filtered packets: a decimating FIR (a matched filter) per packet, applied on the GPU in front of the demodulator ---------
+ * The demodulator has no integrate-and-dump: its timing stage integrates ENERGY per intra-symbol phase and then picks ONE sample
+ * per symbol, so at samplesPerBaud 8 seven of eight samples contribute nothing to a decision.  A matched filter in front puts
+ * the whole symbol's energy into the sample the timing stage picks (QPSK at 8 samples a symbol, noise sigma 0.5 a component:
+ * 1688 of 5700 differential decisions wrong without, 9 behind eight taps of 1/8), and it is the anti-alias filter the resampler
+ * does not have.  Filters are real-tap FIRs the handle keeps in PSK_SOFT_FIR_SLOTS numbered slots (psk_soft_fir_define).
+ *
+ * The definition (host and device alike).
+ *   Input samples.  Sample k of the packet is converted to float exactly, as its format defines; if the packet is also tuned it
+ *     is multiplied by the NCO exactly as "tuned packets" (above) defines.  Call the result s[k], k = 0 .. n-1, n = n_floats / 2.
+ *   History.  s[-127] .. s[-1] are the channel's HISTORY: the last PSK_SOFT_FIR_MAX_TAPS - 1 values of s in front of this packet,
+ *     already tuned, oldest first; zeros with PSK_SOFT_FIR_RESTART.  It always holds 127 samples, whatever the filter's length:
+ *     a stream may change its filter between packets and the result is still defined.
+ *   Outputs.  m = 0, 1, .. while i_m = pos + m * decim < n; n_out is their count: 0 if pos >= n, else (n - pos + decim - 1) / decim.
+ *   Per output, with the taps h[0 .. T-1], re and im separately:
+ *       acc = h[0] * s[i]
+ *       acc = acc + h[j] * s[i-j]     for j = 1 .. T-1, in that order
+ *     every operation float32, rounded once, no fused multiply-add, denormals kept.
+ *   After the packet.  The new history is the last 127 of (old history || s[0 .. n-1]); the next packet's pos is
+ *     pos + n_out * decim - n, always below decim (psk_soft_fir_advance).  A packet with samples but no outputs (pos >= n) still
+ *     moves the history.
+ * The result of the call is bit for bit what psk_soft_process_device_resampled gives for the contiguous PSK_SOFT_FORMAT_CF32
+ * packet holding y[0 .. n_out-1], untuned, with the same resample[i] and sri_xdelta * (double)decim as its sri_xdelta (which the
+ * resampler then scales as it always does): all four streams, counts, SRI fields, warnings, statistics and quality records, under
+ * every schedule and option.  That contract covers finite y; with non-finite samples or taps the formula above is still what
+ * runs, and which NaN comes out is unspecified.
+ * Two identities follow.  The taps {1.0f} with decim 1 give the unfiltered call bit for bit for finite samples, the sign of a
+ * zero included (y = 1 * s).  The taps {0, 0, 1} give the stream delayed by two samples, except for the sign of a zero sample
+ * (0*a + 0*b + (-0) is +0).
+ * The filter's group delay ((T-1)/2 input samples for symmetric taps) is the caller's bookkeeping: nothing in the SRI moves.
+ * THE DECIMATION PHASE MATTERS: of the decim possible values of pos one keeps the matched filter's peak ("A
+ * matched filter in front of the demodulator").  Size the output rows with psk_soft_output_capacity(h, ch, n_out), n_out from
+ * psk_soft_fir_count() (and psk_soft_resample_count() on that, if the packet is resampled as well). */
+#define PSK_SOFT_FIR_MAX_TAPS 128
+#define PSK_SOFT_FIR_SLOTS    64
+#define PSK_SOFT_FIR_MAX_DECIM 16
+enum { PSK_SOFT_FIR_RESTART = 1 };
+typedef struct psk_soft_fir {
+    uint32_t filter;  /* 1 + slot; 0 = this packet is not filtered (decim, pos, flags ignored) */
+    uint32_t decim;   /* D: 1 .. 16, input samples per output sample                           */
+    uint32_t pos;     /* index, in the packet, of the newest input of the first output; < decim */
+    uint32_t flags;   /* PSK_SOFT_FIR_RESTART: the history in front of the packet is zeros      */
+} psk_soft_fir_t;     /* 16 bytes */
+
+/* The taps of slot `slot` (0 .. PSK_SOFT_FIR_SLOTS - 1): 1 .. PSK_SOFT_FIR_MAX_TAPS floats, copied into device memory the
+ * handle owns (SLOTS x MAX_TAPS floats, allocated at the first define).  Waits first for the last filter launch of the handle, so
+ * redefining a slot never races a launch that reads it -- the one place besides scratch growth that waits.  A control-plane-only
+ * handle records n_taps only.  PSK_SOFT_ERR_INVALID_ARG: null, slot >= 64, n_taps 0 or above 128. */
+psk_soft_status psk_soft_fir_define(psk_soft_handle_t *h, uint32_t slot, const float *taps, uint32_t n_taps);
+
+/* psk_soft_process_device_resampled with fir[i] applied to packet i, behind the frequency shift and in front of the resampler.
+ * fir == NULL is psk_soft_process_device_resampled: the same code path; a packet with filter == 0 takes exactly the path it
+ * takes there.  A packet that is absent, has sri_mode != 1 or has no samples is left to the ordinary call and the channel's
+ * history does not change.  One call may mix packets that are filtered, tuned, resampled and strided in every combination, and
+ * may mix formats.
+ * Refused with PSK_SOFT_ERR_INVALID_ARG before anything is planned, committed or enqueued, on a present packet with
+ * filter != 0: a slot >= 64 or never defined, decim 0 or above 16, pos >= decim, unknown flag bits, n_floats / 2 >= 2^30; and
+ * whatever psk_soft_process_device_resampled refuses.
+ * How: every filtered packet gets a float2 row of n_out samples (128-byte aligned) in the gather scratch, and ONE more launch on
+ * `stream`, behind the gathers and the tune pass and in front of the resample pass, writes the rows.  A filtered packet that is
+ * also tuned is tuned inside that launch (no tune row).  A packet both filtered and resampled is resampled from its filter row
+ * (CF32, n_out samples, not tuned) into a row of its own: it pays two passes.  A strided packet in a run the tiled transpose
+ * takes (at least 8 adjacent columns) is read from its gathered row, any other where it lies.  The ordinary call then runs on CF32
+ * packets of the final count with the scaled sri_xdelta.  Scratch, descriptor slots, events and the deferred-join rule are those
+ * of psk_soft_process_device_strided.
+ * History: device memory the handle owns, two slots of 127 float2 (1 KiB each) per channel, allocated at the first filtered
+ * call.  A launch reads the channel's current slot and writes the other; the slots change roles only when the whole call
+ * returned PSK_SOFT_OK, so a refused call (PSK_SOFT_ERR_CAPACITY, PSK_SOFT_ERR_LIMIT, ..) changes nothing a later call can see.
+ * The history is not part of the state blob: checkpoint it with the two calls below.
+ * A control-plane-only handle checks the arguments, then plans and counts on the final count and sri_xdelta; its history stays
+ * zero.  No host-pointer counterpart; psk_soft_acquire_device does not filter. */
+psk_soft_status psk_soft_process_device_filtered(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch,
+                                                 const psk_soft_packet_t *pkts /* [nch] */,
+                                                 const uint64_t *sample_stride /* [nch], or NULL */,
+                                                 const psk_soft_tune_t *tune /* [nch], or NULL */,
+                                                 const psk_soft_fir_t *fir /* [nch], or NULL */,
+                                                 const psk_soft_resample_t *resample /* [nch], or NULL */,
+                                                 psk_soft_output_t *outs /* [nch] */, void *stream);
+/* the history of channel ch, 127 (re, im) pairs, oldest first.  _get waits for the last filter pass; _set replaces it. */
+psk_soft_status psk_soft_fir_get_history(psk_soft_handle_t *h, uint32_t ch, float *out /* [254] */);
+psk_soft_status psk_soft_fir_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in /* [254] */);
+
+/* Host only, pure.
+ * psk_soft_fir_count: n_out of a packet of n_complex samples (filter == 0: n_complex, the packet goes as it is).
+ * psk_soft_fir_advance: pos of the stream's next packet (filter == 0: pos).
+ * psk_soft_fir_apply: the definition above for n_complex untuned CF32 samples and the given taps (f->filter is not looked at).
+ *   hist_in NULL or PSK_SOFT_FIR_RESTART: a history of zeros; hist_out (may be NULL) receives the history behind the packet;
+ *   `out` holds psk_soft_fir_count() samples; `in` and `out` must not overlap.  Refuses what the entry refuses.
+ * psk_soft_fir_piece: outputs of one workgroup's piece of the device's pass at that decim (tests: the lengths at its edges). */
+uint64_t psk_soft_fir_count(const psk_soft_fir_t *f, uint64_t n_complex);
+uint32_t psk_soft_fir_advance(const psk_soft_fir_t *f, uint64_t n_complex);
+psk_soft_status psk_soft_fir_apply(const psk_soft_fir_t *f, const float *taps, uint32_t n_taps, const float *hist_in /* [254] or NULL */,
+                                   const float *in, uint64_t n_complex, float *out, float *hist_out /* [254] or NULL */);
+uint32_t psk_soft_fir_piece(uint32_t decim);
+
 /* PSK_SOFT_OPT_DEFERRED_JOIN: make `stream` (a hipStream_t; NULL = the handle's own) wait for everything the calls made so
  * far have put on the handle's side streams -- the point in stream order behind which their results may be used.  A no-op
  * without pending deferred calls.  (There is no counterpart in the reference: its serviceFunction() is synchronous.) */

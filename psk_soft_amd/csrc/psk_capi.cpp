@@ -27,6 +27,7 @@
 #include "psk_plan.h"
 #include "psk_quality.h"
 #include "psk_soft_hip.h"
+#include "psk_fir.h"
 #include "psk_resample.h"
 #include "psk_tune.h"
 
@@ -555,6 +556,15 @@ struct psk_soft_handle {
     std::vector<uint8_t> rs_cur;
     hipEvent_t rs_ev = nullptr;
     bool rs_ev_used = false;
+    // filtered packets: the taps of every slot (kFirSlots x kFirMaxTaps floats, allocated at the first psk_soft_fir_define) and
+    // their counts (0: never defined); the history of every channel (two slots of 127 float2 in 1 KiB each, as the resampler's),
+    // allocated when the first filtered packet comes; which slot is current; the event behind the last launch
+    float *d_fir_taps = nullptr;
+    uint32_t fir_ntaps[psk::kFirSlots] = {};
+    float *d_fir_hist = nullptr;
+    std::vector<uint8_t> fir_cur;
+    hipEvent_t fir_ev = nullptr;
+    bool fir_ev_used = false;
     int opt_diag_gather_only = 0;  // PSK_SOFT_DIAG_GATHER_ONLY=1 (environment, timing experiments only -- tools/strided_rates.py): a
                                    // strided call gathers and returns; the ordinary call behind it is left out, outs[] untouched
     // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
@@ -2098,6 +2108,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_tune_tab) (void)hipFree(h->d_tune_tab);
         if (h->d_rs_hist) (void)hipFree(h->d_rs_hist);
         if (h->rs_ev) (void)hipEventDestroy(h->rs_ev);
+        if (h->d_fir_taps) (void)hipFree(h->d_fir_taps);
+        if (h->d_fir_hist) (void)hipFree(h->d_fir_hist);
+        if (h->fir_ev) (void)hipEventDestroy(h->fir_ev);
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
             if (sl.h_buf) (void)hipHostFree(sl.h_buf);
@@ -2467,13 +2480,30 @@ static psk_soft_status ensure_resample_history(psk_soft_handle *h)
     return PSK_SOFT_OK;
 }
 
+// filtered packets: the histories in device memory (once per handle), zeros
+static psk_soft_status ensure_fir_history(psk_soft_handle *h)
+{
+    if (h->d_fir_hist)
+        return PSK_SOFT_OK;
+    float *d = nullptr;
+    const size_t bytes = sizeof(float) * 2u * psk::kFirHistSlotFloats * h->nch;
+    PSK_HIP(hipMalloc((void **)&d, bytes));
+    if (hipMemset(d, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(d);  // (the memset is through before a launch on any stream reads a slot)
+        return fail(PSK_SOFT_ERR_HIP, "filter history: hipMemset failed");
+    }
+    h->fir_cur.assign(h->nch, 0);
+    h->d_fir_hist = d;
+    return PSK_SOFT_OK;
+}
+
 // What gather_stage leaves behind: where each packet's own-format row and float2 row of tuned samples lie in the scratch (nullptr:
 // the packet has none), and the scratch and descriptor slot it has claimed, whose events gather_release records behind whatever
 // the caller puts on the stream to read the rows.
 struct GatherStage {
     std::vector<const void *> row;
     std::vector<float *> tune_row;
-    std::vector<uint64_t> rs_out;  // (a resampled packet: the samples of its float2 row, which tune_row points at)
+    std::vector<uint64_t> rs_out;  // (a resampled or filtered packet: the samples of its last float2 row, which tune_row points at)
     StreamScratch *sc = nullptr;
     GatherDescSlot *ds = nullptr;  // (set once the descriptors are on the stream: from then on gather_release is owed)
 };
@@ -2481,39 +2511,52 @@ struct GatherStage {
 // Finds the frame groups among the packets marked `gathered` (present, strided, complex data, at least one sample), claims the
 // stream's scratch and a descriptor slot, uploads the descriptors and launches the gathers on `stream`, and behind them the tune
 // kernel over the packets marked `tuned` and the resample kernel over the packets marked `resampled` (which tunes those of them
-// that have a tune: a packet is marked one or the other).  A column of a run of at least kGatherMinGroup goes through the tile
+// that have a tune: a packet is marked one or the other).  Between the two comes the filter kernel over the packets marked
+// `filtered` (which tunes those of them that have a tune as well: they are not marked `tuned`); a packet both filtered and
+// resampled is resampled from its filter row.  A column of a run of at least kGatherMinGroup goes through the tile
 // kernel into its own-format row.  A column of a shorter run goes through the plain strided gather, unless it is tuned or
-// resampled (those kernels read it where it lies) or the caller reads every such column in place itself (`singles_in_place`: it
+// resampled or filtered (those kernels read it where it lies) or the caller reads every such column in place itself (`singles_in_place`: it
 // gets no row).  A call with nothing to launch returns before it touches a stream, gs.ds == nullptr.
 static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
                                     const uint64_t *sample_stride, const psk_soft_tune_t *tune, const psk_soft_resample_t *resample,
                                     const std::vector<uint8_t> &gathered, const std::vector<uint8_t> &tuned,
-                                    const std::vector<uint8_t> &resampled, bool singles_in_place, hipStream_t stream, GatherStage &gs)
+                                    const std::vector<uint8_t> &resampled, const psk_soft_fir_t *fir, const std::vector<uint8_t> &filtered,
+                                    bool singles_in_place, hipStream_t stream, GatherStage &gs)
 {
     // (a column that gets neither a row nor a gather of its own when its run is too short for the tile kernel)
-    auto direct = [&](uint32_t i) { return singles_in_place || tuned[i] || resampled[i]; };
-    uint32_t n_tune = 0, n_rs = 0;
-    for (uint32_t i = 0; i < nch; i++) n_tune += tuned[i], n_rs += resampled[i];
-    // (the float2 row of a tuned packet holds its samples, that of a resampled one its outputs)
-    auto rs_n_out = [&](uint32_t i) { return psk::resample_count(resample[i].pos, resample[i].step, pkts[i].n_floats / 2u); };
-    auto f2_row = [&](uint32_t i) {
-        const uint64_t n = resampled[i] ? rs_n_out(i) : pkts[i].n_floats / 2u;
-        return align_up(sizeof(float2) * (size_t)(n ? n : 1u), 128);
+    auto direct = [&](uint32_t i) { return singles_in_place || tuned[i] || resampled[i] || filtered[i]; };
+    uint32_t n_tune = 0, n_rs = 0, n_fir = 0;
+    for (uint32_t i = 0; i < nch; i++) n_tune += tuned[i], n_rs += resampled[i], n_fir += filtered[i];
+    // (the float2 row of a tuned packet holds its samples, that of a filtered or resampled one its outputs; the resampler of a
+    // filtered packet reads the filter's outputs)
+    auto fir_n_out = [&](uint32_t i) { return psk::fir_count(fir[i].pos, fir[i].decim, pkts[i].n_floats / 2u); };
+    auto rs_n_out = [&](uint32_t i) {
+        return psk::resample_count(resample[i].pos, resample[i].step, filtered[i] ? fir_n_out(i) : pkts[i].n_floats / 2u);
     };
+    auto row_bytes = [&](uint64_t n) { return align_up(sizeof(float2) * (size_t)(n ? n : 1u), 128); };
+    auto f2_row = [&](uint32_t i) { return row_bytes(resampled[i] ? rs_n_out(i) : pkts[i].n_floats / 2u); };
     // ---- frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart ----
     struct Run {
         uint32_t first, g, bytes;
     };
     std::vector<Run> runs;
     std::vector<size_t> row_off(nch, 0), tune_off(n_tune || n_rs ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned or resampled packet)
+    std::vector<size_t> fir_off(n_fir ? nch : 0, 0);  // (float2 row of a filtered packet)
     std::vector<uint8_t> has_row(nch, 0);
     size_t need = 0;
+    auto f2_rows = [&](uint32_t i) {
+        if (filtered[i]) {
+            fir_off[i] = need;
+            need += row_bytes(fir_n_out(i));
+        }
+        if (tuned[i] || resampled[i]) {
+            tune_off[i] = need;
+            need += f2_row(i);
+        }
+    };
     for (uint32_t i = 0; i < nch;) {
         if (!gathered[i]) {
-            if (tuned[i] || resampled[i]) {
-                tune_off[i] = need;
-                need += f2_row(i);
-            }
+            f2_rows(i);
             i++;
             continue;
         }
@@ -2530,10 +2573,7 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
                 has_row[c] = 1;
                 need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
             }
-            if (tuned[c] || resampled[c]) {
-                tune_off[c] = need;
-                need += f2_row(c);
-            }
+            f2_rows(c);
         }
         i = j;
     }
@@ -2549,24 +2589,27 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     }
     const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
     const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
-    if (!tot_groups && !tot_singles && !n_tune && !n_rs)
+    if (!tot_groups && !tot_singles && !n_tune && !n_rs && !n_fir)
         return PSK_SOFT_OK;
     const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
     const size_t off_tune = off_singles + sizeof(psk::GatherSingle) * tot_singles;
     const size_t off_rs = off_tune + sizeof(psk::TuneDesc) * n_tune;
-    const size_t desc_bytes = off_rs + sizeof(psk::ResampleDesc) * n_rs;
+    const size_t off_fir = off_rs + sizeof(psk::ResampleDesc) * n_rs;
+    const size_t desc_bytes = off_fir + sizeof(psk::FirDesc) * n_fir;
 
     // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
     // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
     PSK_HIP(deferred_join(h, stream));
     StreamScratch *sc = nullptr;
     PSK_TRY(claim_scratch(h->gat, &h->gat_calls, stream, need, nullptr, &sc));
-    bool rs_tuned = false;  // (a resampled packet that is tuned as well: the resample kernel needs the tables)
-    for (uint32_t i = 0; i < nch && tune; i++) rs_tuned |= resampled[i] && (tune[i].phase | tune[i].step) != 0;
+    bool rs_tuned = false;  // (a resampled or filtered packet that is tuned as well: its kernel needs the tables)
+    for (uint32_t i = 0; i < nch && tune; i++) rs_tuned |= (resampled[i] || filtered[i]) && (tune[i].phase | tune[i].step) != 0;
     if (n_tune || rs_tuned)
         PSK_TRY(ensure_tune_tab(h));
     if (n_rs)
         PSK_TRY(ensure_resample_history(h));
+    if (n_fir)
+        PSK_TRY(ensure_fir_history(h));
     GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
     h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
     if (!ds.ev)
@@ -2589,10 +2632,11 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
     psk::TuneDesc *const ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + off_tune);
     psk::ResampleDesc *const hr = reinterpret_cast<psk::ResampleDesc *>(ds.h_buf + off_rs);
+    psk::FirDesc *const hf = reinterpret_cast<psk::FirDesc *>(ds.h_buf + off_fir);
     uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
     uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
     const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
-    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0, max_n_rs = 0;
+    uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0, max_n_rs = 0, max_fir_pieces = 0;
     gs.row.assign(nch, nullptr);
     gs.tune_row.assign(nch, nullptr);
     gs.rs_out.assign(nch, 0);
@@ -2626,20 +2670,47 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
             }
         }
     }
-    // the tuned and the resampled packets: from the row the tile kernel writes (its columns), else from where the caller has
-    // them, at their stride
+    // the tuned, the filtered and the resampled packets: from the row the tile kernel writes (its columns), else from where the
+    // caller has them, at their stride; a packet both filtered and resampled is resampled from its filter row
     {
-        std::vector<uint8_t> in_group(n_tune || n_rs ? nch : 0, 0);
+        const bool any = n_tune || n_rs || n_fir;
+        std::vector<uint8_t> in_group(any ? nch : 0, 0);
         for (const Run &r : runs)
-            if ((n_tune || n_rs) && r.g >= psk::kGatherMinGroup)
+            if (any && r.g >= psk::kGatherMinGroup)
                 std::fill(in_group.begin() + r.first, in_group.begin() + r.first + r.g, (uint8_t)1);
-        uint32_t t_at = 0, r_at = 0;
-        for (uint32_t c = 0; c < nch && (n_tune || n_rs); c++) {
-            if (!tuned[c] && !resampled[c])
+        uint32_t t_at = 0, r_at = 0, f_at = 0;
+        for (uint32_t c = 0; c < nch && any; c++) {
+            if (!tuned[c] && !resampled[c] && !filtered[c])
                 continue;
             const void *const src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
-            float *const dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
             const uint64_t stride = in_group[c] ? 1u : stride_of(sample_stride, c);
+            const bool has_tune = tune && (tune[c].phase | tune[c].step) != 0;
+            if (filtered[c]) {
+                psk::FirDesc &d = hf[f_at++];
+                d = psk::FirDesc{};
+                d.src = src, d.dst = reinterpret_cast<float *>(sc->buf + fir_off[c]), d.stride = stride;
+                d.n = pkts[c].n_floats / 2u;
+                d.format = pkts[c].format;
+                d.flags = (fir[c].flags & PSK_SOFT_FIR_RESTART) ? psk::kFirRestart : 0u;
+                if (has_tune) {
+                    d.phase = tune[c].phase, d.step = tune[c].step;
+                    d.flags |= psk::kFirTuned;
+                }
+                d.decim = fir[c].decim, d.pos = fir[c].pos, d.n_taps = h->fir_ntaps[fir[c].filter - 1u], d.n_out = fir_n_out(c);
+                d.taps = h->d_fir_taps + (size_t)psk::kFirMaxTaps * (fir[c].filter - 1u);
+                // (the channel's current slot in, the other out: psk_soft_process_device_filtered flips them when the call is through)
+                float *const slots = h->d_fir_hist + (size_t)2u * psk::kFirHistSlotFloats * (ch0 + c);
+                d.hist_in = slots + psk::kFirHistSlotFloats * h->fir_cur[ch0 + c];
+                d.hist_out = slots + psk::kFirHistSlotFloats * (h->fir_cur[ch0 + c] ^ 1u);
+                const uint32_t piece = psk::fir_piece(d.decim);
+                const uint64_t pieces = (d.n_out + piece - 1u) / piece;
+                max_fir_pieces = pieces > max_fir_pieces ? pieces : max_fir_pieces;
+                gs.tune_row[c] = d.dst;
+                gs.rs_out[c] = d.n_out;
+                if (!resampled[c])
+                    continue;
+            }
+            float *const dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
             gs.tune_row[c] = dst;
             if (tuned[c]) {
                 psk::TuneDesc &d = ht[t_at++];
@@ -2657,7 +2728,11 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
             d.n = pkts[c].n_floats / 2u;
             d.format = pkts[c].format;
             d.flags = (resample[c].flags & PSK_SOFT_RS_RESTART) ? psk::kResampleRestart : 0u;
-            if (tune && (tune[c].phase | tune[c].step) != 0) {
+            if (filtered[c]) {  // (the filter's outputs, which are tuned already)
+                d.src = sc->buf + fir_off[c], d.stride = 1u;
+                d.n = fir_n_out(c);
+                d.format = PSK_SOFT_FORMAT_CF32;
+            } else if (has_tune) {
                 d.phase = tune[c].phase, d.step = tune[c].step;
                 d.flags |= psk::kResampleTuned;
             }
@@ -2691,6 +2766,14 @@ static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t n
     if (n_tune) {  // (cnt = tuned packets)
         PSK_HIP(mark("tune", 8, n_tune, 0));
         PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + off_tune), n_tune, max_n_tune, h->d_tune_tab, stream));
+    }
+    if (n_fir) {  // (cnt = filtered packets)
+        PSK_HIP(mark("fir", 8, n_fir, 0));
+        PSK_HIP(psk::launch_fir(reinterpret_cast<const psk::FirDesc *>(ds.d_buf + off_fir), n_fir, max_fir_pieces, h->d_tune_tab, stream));
+        if (!h->fir_ev)
+            PSK_HIP(hipEventCreateWithFlags(&h->fir_ev, hipEventDisableTiming));
+        PSK_HIP(hipEventRecord(h->fir_ev, stream));
+        h->fir_ev_used = true;
     }
     if (n_rs) {  // (cnt = resampled packets)
         PSK_HIP(mark("resample", 8, n_rs, 0));
@@ -2737,11 +2820,17 @@ static psk_soft_status gather_release(GatherStage &gs, hipStream_t stream, psk_s
 // resample == NULL): one launch of the resample kernel (psk_resample.hip) behind the gathers and the tune kernel writes each of
 // them, tuned inside the same pass if it has a tune, as a float2 row of n_out samples; the packet copy points at that row with
 // format CF32, n_out samples and the scaled sri_xdelta.  It reads its source as the tune kernel does.
-psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                                  const uint64_t *sample_stride, const psk_soft_tune_t *tune,
-                                                  const psk_soft_resample_t *resample, psk_soft_output_t *outs, void *stream_v)
+//
+// Filtered packets (`fir` non-NULL and the packet's filter not 0; psk_soft_process_device_resampled, below, is this entry with
+// fir == NULL): one launch of the filter kernel (psk_fir.hip) behind the gathers and the tune kernel and in front of the resample
+// kernel writes each of them, tuned inside the same pass if it has a tune, filtered and decimated, as a float2 row of n_out
+// samples.  A packet that is resampled as well is resampled from that row into a second one.  The packet copy points at the last
+// row with format CF32, its count and the scaled sri_xdelta.
+psk_soft_status psk_soft_process_device_filtered(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                                 const uint64_t *sample_stride, const psk_soft_tune_t *tune, const psk_soft_fir_t *fir,
+                                                 const psk_soft_resample_t *resample, psk_soft_output_t *outs, void *stream_v)
 {
-    if (!sample_stride && !tune && !resample)
+    if (!sample_stride && !tune && !resample && !fir)
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
     if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
@@ -2760,16 +2849,39 @@ psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t
     };
     // (a packet the call resamples: a step, present, complex data, at least one sample, of a format the library knows; the
     // resample kernel reads it -- and tunes it, if it has a tune: tuned() above then counts it as well)
+    // (a packet the call filters: a filter, present, complex data, at least one sample, of a format the library knows; the filter
+    // kernel reads it -- and tunes it, if it has a tune -- and the resampler, if it has one, sees the filter's outputs)
+    auto filtered = [&](uint32_t i) {
+        const psk_soft_packet_t &k = pkts[i];
+        return fir && fir[i].filter != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && known(k);
+    };
+    auto fir_n_out = [&](uint32_t i) { return psk::fir_count(fir[i].pos, fir[i].decim, pkts[i].n_floats / 2u); };
     auto resampled = [&](uint32_t i) {
         const psk_soft_packet_t &k = pkts[i];
-        return resample && resample[i].step != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && known(k);
+        return resample && resample[i].step != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && known(k) &&
+               (!filtered(i) || fir_n_out(i) != 0);
     };
-    uint32_t n_gather = 0, n_tune = 0, n_rs = 0;
+    uint32_t n_gather = 0, n_tune = 0, n_rs = 0, n_fir = 0;
     bool unknown = false;
     for (uint32_t i = 0; i < nch; i++) {
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
+        if (fir && fir[i].filter != 0) {
+            const psk_soft_fir_t &f = fir[i];
+            char buf[160];
+            const char *what = f.filter > psk::kFirSlots || !h->fir_ntaps[f.filter - 1u] ? "a filter slot that is not defined"
+                               : !f.decim || f.decim > psk::kFirMaxDecim                 ? "a decimation outside 1 .. 16"
+                               : f.pos >= f.decim                                        ? "a position not below the decimation"
+                               : (f.flags & ~(uint32_t)PSK_SOFT_FIR_RESTART)             ? "unknown flag bits"
+                               : k.n_floats / 2u >= psk::kFirMaxN                        ? "2^30 samples or more"
+                                                                                         : nullptr;
+            if (what) {
+                std::snprintf(buf, sizeof buf, "psk_soft_process_device_filtered: channel %u: %s", ch0 + i, what);
+                return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+            }
+            n_fir += filtered(i);
+        }
         if (resample && resample[i].step != 0) {
             const psk_soft_resample_t &r = resample[i];
             char buf[160];
@@ -2787,7 +2899,7 @@ psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t
         }
         const uint64_t s = stride_of(sample_stride, i);
         if (s == 1) {  // (contiguous: the ordinary call's business, but for the packets the tune kernel reads)
-            if (tuned(i) || (resampled(i) && k.data)) {
+            if (tuned(i) || ((resampled(i) || filtered(i)) && k.data)) {
                 if (reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
                     return fail(PSK_SOFT_ERR_INVALID_ARG, kTunedEntry.misaligned);
                 n_tune += tuned(i);
@@ -2804,43 +2916,61 @@ psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t
         n_gather++;
         n_tune += tuned(i);
     }
-    // the packet the ordinary call sees in place of a resampled one: CF32, n_out samples, the sample period scaled by the step
-    auto resampled_packet = [&](psk_soft_packet_t &k, uint32_t i) {
-        k.n_floats = 2u * psk::resample_count(resample[i].pos, resample[i].step, pkts[i].n_floats / 2u);
+    // the packet behind the filter: CF32, the filter's n_out samples, the sample period scaled by the decimation
+    auto filtered_packet = [&](psk_soft_packet_t &k, uint32_t i) {
+        k.n_floats = 2u * fir_n_out(i);
         k.format = PSK_SOFT_FORMAT_CF32;
-        k.sri_xdelta = pkts[i].sri_xdelta * ((double)resample[i].step * 0x1p-32);
+        k.sri_xdelta = k.sri_xdelta * (double)fir[i].decim;
+    };
+    // the packet the ordinary call sees in place of a resampled one (k: the caller's, or the one behind the filter): CF32, n_out
+    // samples, the sample period scaled by the step
+    auto resampled_packet = [&](psk_soft_packet_t &k, uint32_t i) {
+        k.n_floats = 2u * psk::resample_count(resample[i].pos, resample[i].step, k.n_floats / 2u);
+        k.format = PSK_SOFT_FORMAT_CF32;
+        k.sri_xdelta = k.sri_xdelta * ((double)resample[i].step * 0x1p-32);
     };
     // (a control-plane-only handle plans and counts: lengths, formats and sample periods are all it looks at)
-    if (h->dry && n_rs && !unknown) {
+    if (h->dry && (n_rs || n_fir) && !unknown) {
         std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
-        for (uint32_t c = 0; c < nch; c++)
+        for (uint32_t c = 0; c < nch; c++) {
+            if (filtered(c))
+                filtered_packet(pk[c], c);
             if (resampled(c))
                 resampled_packet(pk[c], c);
+        }
         return psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
     }
-    // (a resampled packet without data is the ordinary call's to refuse)
+    // (a resampled or filtered packet without data is the ordinary call's to refuse)
     for (uint32_t i = 0; i < nch && n_rs; i++) n_rs -= resampled(i) && !pkts[i].data;
-    if ((!n_gather && !n_tune && !n_rs) || unknown || h->dry)
+    for (uint32_t i = 0; i < nch && n_fir; i++) n_fir -= filtered(i) && !pkts[i].data;
+    if ((!n_gather && !n_tune && !n_rs && !n_fir) || unknown || h->dry)
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
 
     PSK_HIP(hipSetDevice(h->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
-    std::vector<uint8_t> is_gathered(nch), is_tuned(nch), is_rs(nch);
+    std::vector<uint8_t> is_gathered(nch), is_tuned(nch), is_rs(nch), is_fir(nch);
     for (uint32_t i = 0; i < nch; i++) {
         is_gathered[i] = gathered(i);
         is_rs[i] = resampled(i) && pkts[i].data;
-        is_tuned[i] = tuned(i) && !is_rs[i];  // (a packet both tuned and resampled is tuned inside the resample kernel)
+        is_fir[i] = filtered(i) && pkts[i].data;
+        // (a packet both tuned and resampled or filtered is tuned inside the first of those kernels that reads it)
+        is_tuned[i] = tuned(i) && !is_rs[i] && !is_fir[i];
     }
     GatherStage gs;
-    psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, tune, resample, is_gathered, is_tuned, is_rs, false, stream, gs);
+    psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, tune, resample, is_gathered, is_tuned, is_rs, fir, is_fir, false, stream, gs);
     if (!gs.ds)
         return st;
     if (st == PSK_SOFT_OK && !h->opt_diag_gather_only) {
-        // the ordinary call on a copy of the packets that points at the rows: a tuned or resampled packet's float2 row, else the
-        // gathered one
+        // the ordinary call on a copy of the packets that points at the rows: a tuned, filtered or resampled packet's (last)
+        // float2 row, else the gathered one
         std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
         for (uint32_t c = 0; c < nch; c++) {
-            if (is_rs[c]) {
+            if (is_fir[c]) {
+                pk[c].data = gs.tune_row[c];
+                filtered_packet(pk[c], c);
+                if (is_rs[c])
+                    resampled_packet(pk[c], c);
+            } else if (is_rs[c]) {
                 pk[c].data = gs.tune_row[c];
                 resampled_packet(pk[c], c);
             } else if (gs.tune_row[c]) {
@@ -2859,7 +2989,18 @@ psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t
         for (uint32_t c = 0; c < nch; c++)
             if (is_rs[c])
                 h->rs_cur[ch0 + c] ^= 1u;
+    if (st == PSK_SOFT_OK)
+        for (uint32_t c = 0; c < nch; c++)
+            if (is_fir[c])
+                h->fir_cur[ch0 + c] ^= 1u;
     return st;
+}
+
+psk_soft_status psk_soft_process_device_resampled(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                                  const uint64_t *sample_stride, const psk_soft_tune_t *tune,
+                                                  const psk_soft_resample_t *resample, psk_soft_output_t *outs, void *stream_v)
+{
+    return psk_soft_process_device_filtered(h, ch0, nch, pkts, sample_stride, tune, nullptr, resample, outs, stream_v);
 }
 
 psk_soft_status psk_soft_process_device_tuned(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
@@ -2989,6 +3130,108 @@ psk_soft_status psk_soft_resample_set_history(psk_soft_handle_t *h, uint32_t ch,
     return PSK_SOFT_OK;
 }
 
+// ---- filtered packets: the filters of a handle, the host-side helpers (pure) and the histories ----
+psk_soft_status psk_soft_fir_define(psk_soft_handle_t *h, uint32_t slot, const float *taps, uint32_t n_taps)
+{
+    if (!h || !taps || slot >= psk::kFirSlots || !n_taps || n_taps > psk::kFirMaxTaps)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_define: null pointer, a slot above 63 or a tap count outside 1 .. 128");
+    if (h->dry) {
+        h->fir_ntaps[slot] = n_taps;  // (a control-plane-only handle checks and counts: the count is all it needs)
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    if (!h->d_fir_taps)
+        PSK_HIP(hipMalloc((void **)&h->d_fir_taps, sizeof(float) * psk::kFirSlots * psk::kFirMaxTaps));
+    if (h->fir_ev_used)
+        PSK_HIP(hipEventSynchronize(h->fir_ev));  // (no launch is still reading the slot)
+    PSK_HIP(hipMemcpy(h->d_fir_taps + (size_t)psk::kFirMaxTaps * slot, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice));
+    h->fir_ntaps[slot] = n_taps;
+    return PSK_SOFT_OK;
+}
+
+uint64_t psk_soft_fir_count(const psk_soft_fir_t *f, uint64_t n_complex)
+{
+    if (!f || !f->filter || !f->decim)
+        return n_complex;
+    return psk::fir_count(f->pos, f->decim, n_complex);
+}
+
+uint32_t psk_soft_fir_advance(const psk_soft_fir_t *f, uint64_t n_complex)
+{
+    if (!f)
+        return 0;
+    if (!f->filter || !f->decim)
+        return f->pos;
+    // (pos + n_out * D - n: below D; 128-bit arithmetic, so the helper answers for any length)
+    return (uint32_t)((unsigned __int128)f->pos + (unsigned __int128)psk::fir_count(f->pos, f->decim, n_complex) * f->decim - n_complex);
+}
+
+psk_soft_status psk_soft_fir_apply(const psk_soft_fir_t *f, const float *taps, uint32_t n_taps, const float *hist_in, const float *in,
+                                   uint64_t n_complex, float *out, float *hist_out)
+{
+    if (!f || !taps || (n_complex && !in))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_apply: null pointer");
+    if (!n_taps || n_taps > psk::kFirMaxTaps || !f->decim || f->decim > psk::kFirMaxDecim || f->pos >= f->decim ||
+        (f->flags & ~(uint32_t)PSK_SOFT_FIR_RESTART) || n_complex >= psk::kFirMaxN)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_apply: taps outside 1 .. 128, decim outside 1 .. 16, pos >= decim, flags, or 2^30 samples or more");
+    const uint64_t n_out = psk::fir_count(f->pos, f->decim, n_complex);
+    if (n_out && !out)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_apply: null pointer");
+    float hist[2u * psk::kFirHist] = {};
+    if (hist_in && !(f->flags & PSK_SOFT_FIR_RESTART))
+        std::memcpy(hist, hist_in, sizeof hist);
+    // component q (0 re, 1 im) of s[j], j >= -127
+    auto s = [&](int64_t j, int q) { return j < 0 ? hist[2 * (j + (int64_t)psk::kFirHist) + q] : in[2 * j + q]; };
+    for (uint64_t m = 0; m < n_out; m++) {
+        const int64_t i = (int64_t)(f->pos + m * f->decim);
+        for (int q = 0; q < 2; q++) {
+            float acc = 0.0f;
+            for (uint32_t j = 0; j < n_taps; j++) acc = psk::fir_step(j == 0, acc, taps[j], s(i - (int64_t)j, q));
+            out[2u * m + q] = acc;
+        }
+    }
+    if (hist_out) {
+        float nh[2u * psk::kFirHist];
+        for (int64_t j = 0; j < (int64_t)psk::kFirHist; j++)
+            for (int q = 0; q < 2; q++) nh[2 * j + q] = s((int64_t)n_complex - (int64_t)psk::kFirHist + j, q);
+        std::memcpy(hist_out, nh, sizeof nh);
+    }
+    return PSK_SOFT_OK;
+}
+
+uint32_t psk_soft_fir_piece(uint32_t decim) { return decim && decim <= psk::kFirMaxDecim ? psk::fir_piece(decim) : 0u; }
+
+// the history of a channel: its current slot, behind the last filter launch
+psk_soft_status psk_soft_fir_get_history(psk_soft_handle_t *h, uint32_t ch, float *out)
+{
+    if (!h || !out || ch >= h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_get_history: bad arguments");
+    std::memset(out, 0, sizeof(float) * 2u * psk::kFirHist);
+    if (h->dry || !h->d_fir_hist)
+        return PSK_SOFT_OK;
+    PSK_HIP(hipSetDevice(h->device));
+    if (h->fir_ev_used)
+        PSK_HIP(hipEventSynchronize(h->fir_ev));
+    PSK_HIP(hipMemcpy(out, h->d_fir_hist + (size_t)psk::kFirHistSlotFloats * (2u * ch + h->fir_cur[ch]), sizeof(float) * 2u * psk::kFirHist,
+                      hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_fir_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in)
+{
+    if (!h || !in || ch >= h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_set_history: bad arguments");
+    if (h->dry)
+        return PSK_SOFT_OK;  // (a control-plane-only handle keeps zeros)
+    PSK_HIP(hipSetDevice(h->device));
+    PSK_TRY(ensure_fir_history(h));
+    if (h->fir_ev_used)
+        PSK_HIP(hipEventSynchronize(h->fir_ev));  // (no launch is still reading the slot)
+    PSK_HIP(hipMemcpy(h->d_fir_hist + (size_t)psk::kFirHistSlotFloats * (2u * ch + h->fir_cur[ch]), in, sizeof(float) * 2u * psk::kFirHist,
+                      hipMemcpyHostToDevice));
+    return PSK_SOFT_OK;
+}
+
 // ---- psk_soft_acquire_device: the carrier offset of a packet (include/psk_soft_hip.h, psk_acquire.hip) ----
 // One look at a packet per channel: the fold over pieces of kAcquirePiece samples and the join per packet, on the caller's stream,
 // one record per covered channel.  Nothing of the control plane or of the demodulator's state is read but constelationSize, and
@@ -3046,7 +3289,7 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
     {
         std::vector<uint8_t> is_gathered(nch), none(nch, 0);
         for (uint32_t i = 0; i < nch; i++) is_gathered[i] = stride_of(sample_stride, i) != 1 && looked_at(i);
-        const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, nullptr, is_gathered, none, none, true, stream, gs);
+        const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, nullptr, is_gathered, none, none, nullptr, none, true, stream, gs);
         if (!gs.ds) {
             if (st != PSK_SOFT_OK)
                 return st;

@@ -152,6 +152,18 @@ class Resample(ctypes.Structure):
     _fields_ = [("pos", ctypes.c_uint64), ("step", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("pad", ctypes.c_uint32)]
 
 
+FIR_RESTART = 1  # Fir.flags
+FIR_MAX_TAPS, FIR_SLOTS, FIR_MAX_DECIM = 128, 64, 16
+FIR_HISTORY_FLOATS = 2 * (FIR_MAX_TAPS - 1)
+
+
+class Fir(ctypes.Structure):
+    """psk_soft_fir_t: filter = 1 + the slot of the taps (0 leaves the packet as it is), decim input samples per output, pos the
+    index of the newest input of the packet's first output (< decim)."""
+
+    _fields_ = [("filter", ctypes.c_uint32), ("decim", ctypes.c_uint32), ("pos", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 # Acquire.flags
 A_DATA, A_TUNED, A_PLANNED = 1, 2, 128
 ACQUIRE_LAGS = 8  # lags 1, 2, 4 .. 128
@@ -221,6 +233,14 @@ EXPORTS = (
     "psk_soft_resample_advance",
     "psk_soft_resample_apply",
     "psk_soft_resample_piece",
+    "psk_soft_fir_define",
+    "psk_soft_process_device_filtered",
+    "psk_soft_fir_get_history",
+    "psk_soft_fir_set_history",
+    "psk_soft_fir_count",
+    "psk_soft_fir_advance",
+    "psk_soft_fir_apply",
+    "psk_soft_fir_piece",
     "psk_soft_acquire_device",
     "psk_soft_get_acquire",
     "psk_soft_acquire_derive",
@@ -297,6 +317,20 @@ def load():
     L.psk_soft_resample_apply.argtypes = [ctypes.POINTER(Resample), vp, vp, u64, vp, vp]
     L.psk_soft_resample_piece.argtypes = []
     L.psk_soft_resample_piece.restype = u32
+    L.psk_soft_fir_define.argtypes = [vp, u32, vp, u32]
+    L.psk_soft_process_device_filtered.argtypes = [
+        vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Tune), ctypes.POINTER(Fir), ctypes.POINTER(Resample),
+        ctypes.POINTER(Output), vp
+    ]
+    L.psk_soft_fir_get_history.argtypes = [vp, u32, vp]
+    L.psk_soft_fir_set_history.argtypes = [vp, u32, vp]
+    L.psk_soft_fir_count.argtypes = [ctypes.POINTER(Fir), u64]
+    L.psk_soft_fir_count.restype = u64
+    L.psk_soft_fir_advance.argtypes = [ctypes.POINTER(Fir), u64]
+    L.psk_soft_fir_advance.restype = u32
+    L.psk_soft_fir_apply.argtypes = [ctypes.POINTER(Fir), vp, u32, vp, vp, u64, vp, vp]
+    L.psk_soft_fir_piece.argtypes = [u32]
+    L.psk_soft_fir_piece.restype = u32
     L.psk_soft_process_host.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(Output)]
     L.psk_soft_synchronize.argtypes = [vp]
     L.psk_soft_join.argtypes = [vp, vp]
@@ -452,6 +486,47 @@ def resample_apply(rs, iq, history=None):
 def resample_piece():
     """Outputs of one workgroup's piece of the device's resample pass (psk_soft_resample_piece)."""
     return int(load().psk_soft_resample_piece())
+
+
+def _fir(f):
+    """a Fir from a Fir or a (filter, decim, pos[, flags]) tuple"""
+    return f if isinstance(f, Fir) else Fir(int(f[0]), int(f[1]), int(f[2]), int(f[3]) if len(f) > 3 else 0)
+
+
+def fir_count(f, n_complex):
+    """psk_soft_fir_count: the outputs of a packet of n_complex samples.  f: a Fir or (filter, decim, pos[, flags])."""
+    r = _fir(f)
+    return int(load().psk_soft_fir_count(ctypes.byref(r), int(n_complex)))
+
+
+def fir_advance(f, n_complex):
+    """psk_soft_fir_advance: pos of the next packet of a continuous stream."""
+    r = _fir(f)
+    return int(load().psk_soft_fir_advance(ctypes.byref(r), int(n_complex)))
+
+
+def fir_apply(f, taps, iq, history=None):
+    """psk_soft_fir_apply on the host: the taps (1 .. 128 floats), interleaved float32 I/Q in (an odd last element is dropped),
+    history None (zeros) or 254 floats.  f.filter is not looked at.  Returns (the filtered interleaved float32 I/Q, the history
+    behind the packet as 254 float32)."""
+    r = _fir(f)
+    h = np.ascontiguousarray(taps, np.float32)
+    x = np.ascontiguousarray(iq, np.float32)
+    n = x.size // 2
+    n_out = 0 if r.pos >= n or not r.decim else (n - r.pos + r.decim - 1) // r.decim
+    y = np.empty(2 * n_out, np.float32)
+    hi = None if history is None else np.ascontiguousarray(history, np.float32)
+    if hi is not None and hi.size != FIR_HISTORY_FLOATS:
+        raise ValueError("a history is 127 complex samples: 254 floats")
+    ho = np.empty(FIR_HISTORY_FLOATS, np.float32)
+    _check(load().psk_soft_fir_apply(ctypes.byref(r), h.ctypes.data, h.size, None if hi is None else hi.ctypes.data, x.ctypes.data, n,
+                                     y.ctypes.data, ho.ctypes.data))
+    return y, ho
+
+
+def fir_piece(decim):
+    """Outputs of one workgroup's piece of the device's filter pass at that decimation (psk_soft_fir_piece)."""
+    return int(load().psk_soft_fir_piece(int(decim)))
 
 
 def acquire_derive(rec):
@@ -622,6 +697,43 @@ class Handle:
         if x.size != 6:
             raise ValueError("a history is three complex samples: six floats")
         _check(self._L.psk_soft_resample_set_history(self._h, int(ch), x.ctypes.data))
+
+    def fir_define(self, slot, taps):
+        """psk_soft_fir_define: the taps (1 .. 128 floats, copied) of filter slot `slot` (0 .. 63); a packet names it as
+        Fir.filter = slot + 1."""
+        h = np.ascontiguousarray(taps, np.float32)
+        _check(self._L.psk_soft_fir_define(self._h, int(slot), h.ctypes.data if h.size else None, h.size))
+
+    def process_device_filtered(self, ch0, pkts, strides, tunes, firs, resamples, outs, stream=None):
+        """process_device_resampled with a decimating real-tap FIR per packet, applied on the GPU behind the frequency shift and
+        in front of the resampler.  firs: None (nothing filtered), a ctypes Fir array or a sequence of Fir / (filter, decim,
+        pos[, flags]), one per packet; filter 0 leaves a packet as it is.  Size the output rows with output_capacity(ch,
+        resample_count(rs, fir_count(f, n))).  strides, tunes and resamples as for process_device_resampled."""
+        if strides is not None and not isinstance(strides, ctypes.Array):
+            strides = (ctypes.c_uint64 * len(strides))(*[int(s) for s in strides])
+        if tunes is not None and not isinstance(tunes, ctypes.Array):
+            tunes = (Tune * len(tunes))(*[Tune(int(p), int(s)) for p, s in tunes])
+        if firs is not None and not isinstance(firs, ctypes.Array):
+            firs = (Fir * len(firs))(*[_fir(f) for f in firs])
+        if resamples is not None and not isinstance(resamples, ctypes.Array):
+            resamples = (Resample * len(resamples))(*[_resample(r) for r in resamples])
+        if any(a is not None and len(a) != len(pkts) for a in (strides, tunes, firs, resamples)):
+            raise ValueError("one stride, one tune, one fir and one resample per packet")
+        _check(self._L.psk_soft_process_device_filtered(self._h, ch0, len(pkts), pkts, strides, tunes, firs, resamples, outs,
+                                                        ctypes.c_void_p(stream or 0)))
+
+    def fir_history(self, ch):
+        """The filter's history of channel ch (psk_soft_fir_get_history): 254 float32, 127 (re, im) pairs, oldest first."""
+        out = np.zeros(FIR_HISTORY_FLOATS, np.float32)
+        _check(self._L.psk_soft_fir_get_history(self._h, int(ch), out.ctypes.data))
+        return out
+
+    def set_fir_history(self, ch, floats):
+        """psk_soft_fir_set_history: replace the filter's history of channel ch."""
+        x = np.ascontiguousarray(floats, np.float32)
+        if x.size != FIR_HISTORY_FLOATS:
+            raise ValueError("a history is 127 complex samples: 254 floats")
+        _check(self._L.psk_soft_fir_set_history(self._h, int(ch), x.ctypes.data))
 
     def process_host(self, ch0, packets):
         """packets: list (one per channel from ch0) of None (no packet) or dict with

@@ -40,6 +40,8 @@ others psk_gather
 others psk_tune
 # the resample pre-pass of psk_soft_process_device_resampled (psk_resample.hip): one kernel, the four formats behind a switch
 others psk_resample
+# the filter pre-pass of psk_soft_process_device_filtered (psk_fir.hip): one kernel, the four formats and three blockings behind switches
+others psk_fir
 # the far fit (PSK_SOFT_OPT_FAR_FIT, psk_farfit.hip): the fit stage and the quiet call with the fit window in device memory
 others psk_farfit
 echo "instantiations with D sites / with E sites (tools/isa_lane_loss.py):"; grep -c "no covering save) [1-9]" $out.lanes; grep -c "mask restore) [1-9]" $out.lanes
