@@ -24,17 +24,13 @@
 #include <stdint.h>
 
 #include "psk_acquire.h"
-#include "psk_pkt_cvt.h"
+#include "psk_front_src.h"
 #include "psk_tune.h"
 
 namespace psk {
 
 namespace {
 
-// (the descriptors carry plain pointers; they are global memory, and the loads say so: see psk_quality.hip)
-#define PSK_A_GLOBAL __attribute__((address_space(1)))
-typedef float a_f2 __attribute__((ext_vector_type(2)));
-typedef float a_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t a_u2 __attribute__((ext_vector_type(2)));
 
 constexpr uint32_t kWaves = kAcquireThreads / 64u;
@@ -57,24 +53,24 @@ __device__ __forceinline__ float a_scalar(float v)
 
 // samples k and k + 1 (k even) of a packet of format FMT as they lie, `pair`: both exist and one load may take them
 template <int FMT>
-__device__ __forceinline__ void a_load2(const PSK_A_GLOBAL void *src, uint64_t stride, uint64_t k, bool two, bool wide, a_f2 *x0, a_f2 *x1)
+__device__ __forceinline__ void a_load2(const PSK_GLOBAL void *src, uint64_t stride, uint64_t k, bool two, bool wide, f2 *x0, f2 *x1)
 {
-    *x1 = a_f2{0.0f, 0.0f};
+    *x1 = f2{0.0f, 0.0f};
     if constexpr (FMT == PSK_SOFT_FORMAT_CF32) {
-        const PSK_A_GLOBAL a_f2 *p = reinterpret_cast<const PSK_A_GLOBAL a_f2 *>(src);
+        const PSK_GLOBAL f2 *p = reinterpret_cast<const PSK_GLOBAL f2 *>(src);
         if (two && wide) {
-            const a_f4 z = *reinterpret_cast<const PSK_A_GLOBAL a_f4 *>(p + k);
-            *x0 = a_f2{z.x, z.y}, *x1 = a_f2{z.z, z.w};
+            const f4 z = *reinterpret_cast<const PSK_GLOBAL f4 *>(p + k);
+            *x0 = f2{z.x, z.y}, *x1 = f2{z.z, z.w};
             return;
         }
         *x0 = p[k * stride];
         if (two)
             *x1 = p[(k + 1u) * stride];
     } else if constexpr (FMT == PSK_SOFT_FORMAT_CS8) {
-        const PSK_A_GLOBAL uint16_t *p = reinterpret_cast<const PSK_A_GLOBAL uint16_t *>(src);
+        const PSK_GLOBAL uint16_t *p = reinterpret_cast<const PSK_GLOBAL uint16_t *>(src);
         uint32_t w0, w1 = 0;
         if (two && wide) {
-            const uint32_t z = *reinterpret_cast<const PSK_A_GLOBAL uint32_t *>(p + k);
+            const uint32_t z = *reinterpret_cast<const PSK_GLOBAL uint32_t *>(p + k);
             w0 = z & 0xffffu, w1 = z >> 16;
         } else {
             w0 = p[k * stride];
@@ -82,12 +78,12 @@ __device__ __forceinline__ void a_load2(const PSK_A_GLOBAL void *src, uint64_t s
                 w1 = p[(k + 1u) * stride];
         }
         const float2 a = pkt_cvt<FMT>(w0), b = pkt_cvt<FMT>(w1);
-        *x0 = a_f2{a.x, a.y}, *x1 = a_f2{b.x, b.y};
+        *x0 = f2{a.x, a.y}, *x1 = f2{b.x, b.y};
     } else {
-        const PSK_A_GLOBAL uint32_t *p = reinterpret_cast<const PSK_A_GLOBAL uint32_t *>(src);
+        const PSK_GLOBAL uint32_t *p = reinterpret_cast<const PSK_GLOBAL uint32_t *>(src);
         uint32_t w0, w1 = 0;
         if (two && wide) {
-            const a_u2 z = *reinterpret_cast<const PSK_A_GLOBAL a_u2 *>(p + k);
+            const a_u2 z = *reinterpret_cast<const PSK_GLOBAL a_u2 *>(p + k);
             w0 = z.x, w1 = z.y;
         } else {
             w0 = p[k * stride];
@@ -95,7 +91,7 @@ __device__ __forceinline__ void a_load2(const PSK_A_GLOBAL void *src, uint64_t s
                 w1 = p[(k + 1u) * stride];
         }
         const float2 a = pkt_cvt<FMT>(w0), b = pkt_cvt<FMT>(w1);
-        *x0 = a_f2{a.x, a.y}, *x1 = a_f2{b.x, b.y};
+        *x0 = f2{a.x, a.y}, *x1 = f2{b.x, b.y};
     }
 }
 
@@ -103,10 +99,10 @@ __device__ __forceinline__ void a_load2(const PSK_A_GLOBAL void *src, uint64_t s
 // zeros behind them up to `end` (the piece rounded up to whole turns of stage 2); energies of [lo, hi) into se, their count --
 // the same in every lane of the wave -- into nv.
 template <int FMT, bool TAB>
-__device__ __forceinline__ void a_stage1(const AcquireDesc &d, const float *tab, a_f2 *u, uint64_t start, uint64_t lo, uint64_t hi, uint64_t end,
+__device__ __forceinline__ void a_stage1(const AcquireDesc &d, const float *tab, f2 *u, uint64_t start, uint64_t lo, uint64_t hi, uint64_t end,
                                          int P, double &se, uint32_t &nv)
 {
-    const PSK_A_GLOBAL void *__restrict__ src = (const PSK_A_GLOBAL void *)d.src;
+    const PSK_GLOBAL void *__restrict__ src = (const PSK_GLOBAL void *)d.src;
     const bool tuned = TAB && (d.flags & PSK_SOFT_A_TUNED) != 0;
     // one load for the pair: a contiguous row whose pairs are aligned to their size (start and every k below are even)
     const uint32_t pair_bytes = FMT == PSK_SOFT_FORMAT_CF32 ? 16u : FMT == PSK_SOFT_FORMAT_CS8 ? 4u : 8u;
@@ -116,22 +112,19 @@ __device__ __forceinline__ void a_stage1(const AcquireDesc &d, const float *tab,
     const uint64_t adv = step * (2u * kAcquireThreads);
     for (uint64_t k = start + 2u * threadIdx.x; k < end; k += 2u * kAcquireThreads, p += adv) {  // (end - start is a multiple of 128)
         const bool one = k < hi, two = k + 1u < hi;
-        a_f2 x0 = a_f2{0.0f, 0.0f}, x1 = a_f2{0.0f, 0.0f};
+        f2 x0 = f2{0.0f, 0.0f}, x1 = f2{0.0f, 0.0f};
         if (one)
             a_load2<FMT>(src, d.stride, k, two, wide, &x0, &x1);
         if (tuned) {
-            float yr, yi;
-            tune_rotate(tab, p, x0.x, x0.y, &yr, &yi);
-            x0 = a_f2{yr, yi};
-            tune_rotate(tab, p + step, x1.x, x1.y, &yr, &yi);
-            x1 = a_f2{yr, yi};
+            x0 = src_rotate(tab, p, x0);
+            x1 = src_rotate(tab, p + step, x1);
         }
         float e0, e1, r0, i0, r1, i1;
         // (a sample that is not there is (0, 0): invalid, its phasor (0, 0))
         const bool ok0 = acq_sample(x0.x, x0.y, P, &e0, &r0, &i0);
         const bool ok1 = acq_sample(x1.x, x1.y, P, &e1, &r1, &i1);
         const uint32_t s = (uint32_t)(k + kAcquireHalo - lo);
-        *reinterpret_cast<a_f4 *>(u + s) = a_f4{r0, i0, r1, i1};  // (s is even)
+        *reinterpret_cast<f4 *>(u + s) = f4{r0, i0, r1, i1};  // (s is even)
         const bool in = k >= lo;  // (lo is even: a pair never straddles it)
         se += (double)(in && ok0 ? e0 : 0.0f);
         se += (double)(in && ok1 ? e1 : 0.0f);
@@ -148,16 +141,12 @@ __global__ __launch_bounds__(kAcquireThreads) void psk_acquire_fold_kernel(const
                                                                            AcquirePartial *__restrict__ part)
 {
     __shared__ __attribute__((aligned(16))) float tab[TAB ? kTuneTableFloats : 4u];
-    __shared__ __attribute__((aligned(16))) a_f2 u[kAcquireHalo + kAcquirePiece];
+    __shared__ __attribute__((aligned(16))) f2 u[kAcquireHalo + kAcquirePiece];
     __shared__ double red_d[kWaves][kSums];
     __shared__ uint32_t red_c[kWaves][kCounts];
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-    if constexpr (TAB) {
-        const PSK_A_GLOBAL a_f4 *g = (const PSK_A_GLOBAL a_f4 *)d_tab;
-        a_f4 *const l = reinterpret_cast<a_f4 *>(tab);
-#pragma unroll
-        for (uint32_t k = 0; k < kTuneTableFloats / 4u / kAcquireThreads; k++) l[t + k * kAcquireThreads] = g[t + k * kAcquireThreads];
-    }
+    if constexpr (TAB)
+        src_tables_to_lds<kAcquireThreads>(tab, d_tab);
     for (uint32_t c = blockIdx.y; c < nch; c += gridDim.y) {
         const AcquireDesc d = desc[c];
         // (uniform for the workgroup, like every branch on the descriptor below)
@@ -170,16 +159,10 @@ __global__ __launch_bounds__(kAcquireThreads) void psk_acquire_fold_kernel(const
         const int P = d.M == 2 ? 1 : d.M == 4 ? 2 : 3;
         __syncthreads();  // (the tables are in place; the LDS of the packet before is read out)
         if (!lo && t < kAcquireHalo)
-            u[t] = a_f2{0.0f, 0.0f};  // (nothing lies in front of the packet: no pairs)
+            u[t] = f2{0.0f, 0.0f};  // (nothing lies in front of the packet: no pairs)
         double se = 0.0;
         uint32_t nv = 0;
-        switch (d.format) {
-        case PSK_SOFT_FORMAT_CF32: a_stage1<PSK_SOFT_FORMAT_CF32, TAB>(d, tab, u, start, lo, hi, end, P, se, nv); break;
-        case PSK_SOFT_FORMAT_CS16: a_stage1<PSK_SOFT_FORMAT_CS16, TAB>(d, tab, u, start, lo, hi, end, P, se, nv); break;
-        case PSK_SOFT_FORMAT_CS8: a_stage1<PSK_SOFT_FORMAT_CS8, TAB>(d, tab, u, start, lo, hi, end, P, se, nv); break;
-        case PSK_SOFT_FORMAT_CF16: a_stage1<PSK_SOFT_FORMAT_CF16, TAB>(d, tab, u, start, lo, hi, end, P, se, nv); break;
-        default: break;
-        }
+        src_dispatch(d.format, [&](auto fmt) { a_stage1<decltype(fmt)::value, TAB>(d, tab, u, start, lo, hi, end, P, se, nv); });
         __syncthreads();
         // stage 2: sample k of the piece sits in slot k + halo - lo, its partner of lag L in the slot L in front of it
         double sr[kAcquireLags], si[kAcquireLags];
@@ -190,11 +173,11 @@ __global__ __launch_bounds__(kAcquireThreads) void psk_acquire_fold_kernel(const
         const uint32_t turns = (uint32_t)(end - lo) / kAcquireThreads;
         for (uint32_t turn = 0; turn < turns; turn++) {
             const uint32_t s = kAcquireHalo + turn * kAcquireThreads + t;
-            const a_f2 a = u[s];
+            const f2 a = u[s];
             const float ar = a_scalar(a.x), ai = a_scalar(a.y);
 #pragma unroll
             for (uint32_t j = 0; j < kAcquireLags; j++) {
-                const a_f2 b = u[s - (1u << j)];
+                const f2 b = u[s - (1u << j)];
                 float tr, ti;
                 acq_lag(ar, ai, a_scalar(b.x), a_scalar(b.y), &tr, &ti);
                 // (a pair of valid samples: acq_sample's a >= FLT_MIN keeps |u| within a few ulp of 1, so |t| is within a few
@@ -217,7 +200,7 @@ __global__ __launch_bounds__(kAcquireThreads) void psk_acquire_fold_kernel(const
                 red_d[wave][2u * kAcquireLags] = e, red_c[wave][kAcquireLags] = nv;
         }
         __syncthreads();
-        PSK_A_GLOBAL AcquirePartial *const out = (PSK_A_GLOBAL AcquirePartial *)part + (d.part0 + blockIdx.x);
+        PSK_GLOBAL AcquirePartial *const out = (PSK_GLOBAL AcquirePartial *)part + (d.part0 + blockIdx.x);
         if (t < kSums) {
             double v = red_d[0][t];
             for (uint32_t w = 1; w < kWaves; w++) v += red_d[w][t];
@@ -246,7 +229,7 @@ __global__ __launch_bounds__(64) void psk_acquire_join_kernel(const AcquireDesc 
         for (uint32_t j = 0; j < kCounts; j++) n[j] = 0;
         // lane l adds the partials l, l + 64, ... in that order; then the fixed tree
         for (uint32_t k = lane; data && k < d.n_piece; k += 64u) {
-            const PSK_A_GLOBAL AcquirePartial *const p = (const PSK_A_GLOBAL AcquirePartial *)part + (d.part0 + k);
+            const PSK_GLOBAL AcquirePartial *const p = (const PSK_GLOBAL AcquirePartial *)part + (d.part0 + k);
 #pragma unroll
             for (uint32_t j = 0; j < kSums; j++) s[j] += p->d[j];
 #pragma unroll

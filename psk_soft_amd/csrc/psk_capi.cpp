@@ -291,11 +291,103 @@ struct GatherDescSlot {
     size_t cap = 0;  // bytes
     hipEvent_t ev = nullptr;
     bool used = false;
+    // the slot for a call with `bytes` of descriptors: behind the event of its last call, grown on demand
+    psk_soft_status claim(size_t bytes)
+    {
+        if (!ev)
+            PSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if (used)
+            PSK_HIP(hipEventSynchronize(ev));
+        used = false;
+        if (bytes <= cap)
+            return PSK_SOFT_OK;
+        if (h_buf) (void)hipHostFree(h_buf);
+        if (d_buf) (void)hipFree(d_buf);
+        h_buf = d_buf = nullptr;
+        cap = 0;
+        const size_t grown = align_up(bytes + bytes / 4, 4096);
+        PSK_HIP(hipHostMalloc((void **)&h_buf, grown));
+        PSK_HIP(hipMalloc((void **)&d_buf, grown));
+        cap = grown;
+        return PSK_SOFT_OK;
+    }
     void free()
     {
         if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
         if (h_buf) (void)hipHostFree(h_buf);
         if (d_buf) (void)hipFree(d_buf);
+    }
+};
+// The history of every channel in front of a pre-pass that needs one (the resampler's, the filter's): two slots a channel in
+// device memory, allocated (zeros) when the first packet of the kind comes.  A launch reads the channel's current slot and
+// writes the other; the call flips the two once ALL of it has succeeded, so a failed call leaves the history as it was.  The
+// event is behind the last launch that read or wrote a slot.
+struct HistoryBank {
+    const char *name;                                  // in messages
+    uint32_t slot_floats, chan_floats, live_floats;    // a slot, a channel's two slots with their padding, what of a slot is history
+    float *d = nullptr;
+    std::vector<uint8_t> cur;  // the current slot of each channel
+    hipEvent_t ev = nullptr;
+    bool ev_used = false;
+
+    psk_soft_status ensure(uint32_t nch)
+    {
+        if (d)
+            return PSK_SOFT_OK;
+        float *p = nullptr;
+        const size_t bytes = sizeof(float) * chan_floats * nch;
+        PSK_HIP(hipMalloc((void **)&p, bytes));
+        if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            (void)hipFree(p);  // (the memset is through before a launch on any stream reads a slot)
+            return fail(PSK_SOFT_ERR_HIP, std::string(name) + ": hipMemset failed");
+        }
+        cur.assign(nch, 0);
+        d = p;
+        return PSK_SOFT_OK;
+    }
+    float *slot(uint32_t ch, uint32_t which) const { return d + (size_t)chan_floats * ch + slot_floats * which; }
+    const float *in(uint32_t ch) const { return slot(ch, cur[ch]); }
+    float *out(uint32_t ch) const { return slot(ch, cur[ch] ^ 1u); }
+    void flip(uint32_t ch) { cur[ch] ^= 1u; }
+    psk_soft_status record(hipStream_t stream)
+    {
+        if (!ev)
+            PSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        PSK_HIP(hipEventRecord(ev, stream));
+        ev_used = true;
+        return PSK_SOFT_OK;
+    }
+    // no launch is still reading or writing a slot
+    psk_soft_status wait()
+    {
+        if (ev_used)
+            PSK_HIP(hipEventSynchronize(ev));
+        return PSK_SOFT_OK;
+    }
+    // the current slot of a channel, live_floats floats: zeros while nothing is allocated
+    psk_soft_status get(uint32_t ch, float *to)
+    {
+        std::memset(to, 0, sizeof(float) * live_floats);
+        if (!d)
+            return PSK_SOFT_OK;
+        if (const psk_soft_status st = wait())
+            return st;
+        PSK_HIP(hipMemcpy(to, in(ch), sizeof(float) * live_floats, hipMemcpyDeviceToHost));
+        return PSK_SOFT_OK;
+    }
+    psk_soft_status set(uint32_t nch, uint32_t ch, const float *from)
+    {
+        if (const psk_soft_status st = ensure(nch))
+            return st;
+        if (const psk_soft_status st = wait())
+            return st;
+        PSK_HIP(hipMemcpy(slot(ch, cur[ch]), from, sizeof(float) * live_floats, hipMemcpyHostToDevice));
+        return PSK_SOFT_OK;
+    }
+    void free()
+    {
+        if (d) (void)hipFree(d);
+        if (ev) (void)hipEventDestroy(ev);
     }
 };
 
@@ -550,21 +642,13 @@ struct psk_soft_handle {
     uint64_t gat_calls = 0;
     int gdesc_turn = 0;
     float *d_tune_tab = nullptr;  // tuned packets: the two phasor tables (psk_tune.h), uploaded when the first tuned packet comes
-    // resampled packets: the history of every channel (two slots of three float2 in 64 bytes: a launch reads the current one and
-    // writes the other), allocated when the first resampled packet comes; which slot is current; the event behind the last launch
-    float *d_rs_hist = nullptr;
-    std::vector<uint8_t> rs_cur;
-    hipEvent_t rs_ev = nullptr;
-    bool rs_ev_used = false;
+    // resampled packets: the history of every channel, two slots of three float2 in 64 bytes
+    HistoryBank rs_hist{"resample history", psk::kResampleHistSlotFloats, psk::kResampleHistFloats, psk::kResampleHistSlotFloats};
     // filtered packets: the taps of every slot (kFirSlots x kFirMaxTaps floats, allocated at the first psk_soft_fir_define) and
-    // their counts (0: never defined); the history of every channel (two slots of 127 float2 in 1 KiB each, as the resampler's),
-    // allocated when the first filtered packet comes; which slot is current; the event behind the last launch
+    // their counts (0: never defined); the history of every channel, two slots of 127 float2 in 1 KiB each
     float *d_fir_taps = nullptr;
     uint32_t fir_ntaps[psk::kFirSlots] = {};
-    float *d_fir_hist = nullptr;
-    std::vector<uint8_t> fir_cur;
-    hipEvent_t fir_ev = nullptr;
-    bool fir_ev_used = false;
+    HistoryBank fir_hist{"filter history", psk::kFirHistSlotFloats, 2u * psk::kFirHistSlotFloats, 2u * psk::kFirHist};
     int opt_diag_gather_only = 0;  // PSK_SOFT_DIAG_GATHER_ONLY=1 (environment, timing experiments only -- tools/strided_rates.py): a
                                    // strided call gathers and returns; the ordinary call behind it is left out, outs[] untouched
     // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
@@ -2106,11 +2190,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         for (auto &g : h->gat) g.free();
         for (auto &g : h->gdesc) g.free();
         if (h->d_tune_tab) (void)hipFree(h->d_tune_tab);
-        if (h->d_rs_hist) (void)hipFree(h->d_rs_hist);
-        if (h->rs_ev) (void)hipEventDestroy(h->rs_ev);
+        h->rs_hist.free();
         if (h->d_fir_taps) (void)hipFree(h->d_fir_taps);
-        if (h->d_fir_hist) (void)hipFree(h->d_fir_hist);
-        if (h->fir_ev) (void)hipEventDestroy(h->fir_ev);
+        h->fir_hist.free();
         for (auto &sl : h->stage) {
             if (sl.stream) (void)hipStreamSynchronize(sl.stream);
             if (sl.h_buf) (void)hipHostFree(sl.h_buf);
@@ -2421,17 +2503,13 @@ psk_soft_status psk_soft_process_device(psk_soft_handle_t *h, uint32_t ch0, uint
     return quality_pass(h, ch0, nch, outs, stream_v);
 }
 
-// ---- the gathers of a call with strided packets: psk_soft_process_device_tuned and psk_soft_acquire_device ----
-// the sample stride of packet i (sample_stride == NULL: every packet contiguous)
-static inline uint64_t stride_of(const uint64_t *sample_stride, uint32_t i) { return sample_stride ? sample_stride[i] : 1u; }
-
 // The refusals of a strided argument, for the entries that take one: a stride of 0; for a packet of a known format (what an entry does
 // with an unknown one is its own business) an extent that does not fit 64 bits, and -- `read`: the call reads the packet's samples --
 // data that do not start on a whole sample.  ch: the channel, s: its stride.
 struct StridedEntry {
     const char *name, *misaligned;  // the entry in the messages about strides; its whole message about alignment
 };
-static const StridedEntry kTunedEntry = {"psk_soft_process_device_strided", "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4"};
+static const StridedEntry kProcessEntry = {"psk_soft_process_device_strided", "psk_soft_process: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4), soft 8, bits 4, phase 4, sampleIndex 4"};
 static const StridedEntry kAcquireEntry = {"psk_soft_acquire_device", "psk_soft_acquire_device: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4)"};
 static psk_soft_status strided_refusal(const StridedEntry &e, uint32_t ch, const psk_soft_packet_t &k, uint64_t s, bool read)
 {
@@ -2463,345 +2541,417 @@ static psk_soft_status ensure_tune_tab(psk_soft_handle *h)
     return PSK_SOFT_OK;
 }
 
-// resampled packets: the histories in device memory (once per handle), zeros
-constexpr uint32_t kResampleHistFloats = 16;  // two slots of three float2, padded to 64 bytes a channel
-static psk_soft_status ensure_resample_history(psk_soft_handle *h)
-{
-    if (h->d_rs_hist)
-        return PSK_SOFT_OK;
-    float *d = nullptr;
-    PSK_HIP(hipMalloc((void **)&d, sizeof(float) * kResampleHistFloats * h->nch));
-    if (hipMemset(d, 0, sizeof(float) * kResampleHistFloats * h->nch) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(d);  // (the memset is through before a launch on any stream reads a slot)
-        return fail(PSK_SOFT_ERR_HIP, "resample history: hipMemset failed");
-    }
-    h->rs_cur.assign(h->nch, 0);
-    h->d_rs_hist = d;
-    return PSK_SOFT_OK;
-}
-
-// filtered packets: the histories in device memory (once per handle), zeros
-static psk_soft_status ensure_fir_history(psk_soft_handle *h)
-{
-    if (h->d_fir_hist)
-        return PSK_SOFT_OK;
-    float *d = nullptr;
-    const size_t bytes = sizeof(float) * 2u * psk::kFirHistSlotFloats * h->nch;
-    PSK_HIP(hipMalloc((void **)&d, bytes));
-    if (hipMemset(d, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(d);  // (the memset is through before a launch on any stream reads a slot)
-        return fail(PSK_SOFT_ERR_HIP, "filter history: hipMemset failed");
-    }
-    h->fir_cur.assign(h->nch, 0);
-    h->d_fir_hist = d;
-    return PSK_SOFT_OK;
-}
-
-// What gather_stage leaves behind: where each packet's own-format row and float2 row of tuned samples lie in the scratch (nullptr:
-// the packet has none), and the scratch and descriptor slot it has claimed, whose events gather_release records behind whatever
-// the caller puts on the stream to read the rows.
-struct GatherStage {
-    std::vector<const void *> row;
-    std::vector<float *> tune_row;
-    std::vector<uint64_t> rs_out;  // (a resampled or filtered packet: the samples of its last float2 row, which tune_row points at)
-    StreamScratch *sc = nullptr;
-    GatherDescSlot *ds = nullptr;  // (set once the descriptors are on the stream: from then on gather_release is owed)
+// ---- the front stages of a call: gathers, tune, filter, resample (psk_soft_process_device_filtered, psk_soft_acquire_device) ----
+// A call is classified once (front_classify: which kernel reads each packet, what the ordinary call sees in its place, the
+// refusals) and the plan is then read by one function per step, in the order a call goes through them: front_layout,
+// front_describe, front_launch, front_release, front_commit.  DESIGN.md 2.11.
+struct FrontCall {
+    psk_soft_handle *h;
+    uint32_t ch0, nch;
+    const psk_soft_packet_t *pkts;
+    const uint64_t *sample_stride;  // NULL: every packet contiguous
+    const psk_soft_tune_t *tune;    // NULL: none tuned
+    const psk_soft_fir_t *fir;
+    const psk_soft_resample_t *resample;
+    hipStream_t stream;
+    uint64_t stride(uint32_t i) const { return sample_stride ? sample_stride[i] : 1u; }
+    // packet i has a tune: its {phase, step} is not {0, 0}
+    bool has_tune(uint32_t i) const { return tune && (tune[i].phase | tune[i].step) != 0; }
 };
 
-// Finds the frame groups among the packets marked `gathered` (present, strided, complex data, at least one sample), claims the
-// stream's scratch and a descriptor slot, uploads the descriptors and launches the gathers on `stream`, and behind them the tune
-// kernel over the packets marked `tuned` and the resample kernel over the packets marked `resampled` (which tunes those of them
-// that have a tune: a packet is marked one or the other).  Between the two comes the filter kernel over the packets marked
-// `filtered` (which tunes those of them that have a tune as well: they are not marked `tuned`); a packet both filtered and
-// resampled is resampled from its filter row.  A column of a run of at least kGatherMinGroup goes through the tile
-// kernel into its own-format row.  A column of a shorter run goes through the plain strided gather, unless it is tuned or
-// resampled or filtered (those kernels read it where it lies) or the caller reads every such column in place itself (`singles_in_place`: it
-// gets no row).  A call with nothing to launch returns before it touches a stream, gs.ds == nullptr.
-static psk_soft_status gather_stage(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                    const uint64_t *sample_stride, const psk_soft_tune_t *tune, const psk_soft_resample_t *resample,
-                                    const std::vector<uint8_t> &gathered, const std::vector<uint8_t> &tuned,
-                                    const std::vector<uint8_t> &resampled, const psk_soft_fir_t *fir, const std::vector<uint8_t> &filtered,
-                                    bool singles_in_place, hipStream_t stream, GatherStage &gs)
-{
-    // (a column that gets neither a row nor a gather of its own when its run is too short for the tile kernel)
-    auto direct = [&](uint32_t i) { return singles_in_place || tuned[i] || resampled[i] || filtered[i]; };
-    uint32_t n_tune = 0, n_rs = 0, n_fir = 0;
-    for (uint32_t i = 0; i < nch; i++) n_tune += tuned[i], n_rs += resampled[i], n_fir += filtered[i];
-    // (the float2 row of a tuned packet holds its samples, that of a filtered or resampled one its outputs; the resampler of a
-    // filtered packet reads the filter's outputs)
-    auto fir_n_out = [&](uint32_t i) { return psk::fir_count(fir[i].pos, fir[i].decim, pkts[i].n_floats / 2u); };
-    auto rs_n_out = [&](uint32_t i) {
-        return psk::resample_count(resample[i].pos, resample[i].step, filtered[i] ? fir_n_out(i) : pkts[i].n_floats / 2u);
-    };
-    auto row_bytes = [&](uint64_t n) { return align_up(sizeof(float2) * (size_t)(n ? n : 1u), 128); };
-    auto f2_row = [&](uint32_t i) { return row_bytes(resampled[i] ? rs_n_out(i) : pkts[i].n_floats / 2u); };
-    // ---- frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart ----
+// One packet of the call.  At most one of tune / fir reads it, the resample kernel reads it or the filter's row of it; all false:
+// the ordinary call gets the packet as it is (or its gathered row).
+struct FrontPkt {
+    bool gathered = false;  // strided and read: a column of a frame group, or a strided single
+    bool tune = false;      // the tune kernel reads it (tuned, neither filtered nor resampled)
+    bool fir = false;       // the filter kernel reads it
+    bool resample = false;  // the resample kernel reads it, or the row the filter has made of it
+    bool has_tune = false;  // whichever of the three reads it first rotates it
+    bool data = false;      // it has data -- or the handle is control-plane-only, which never looks
+    uint64_t n_in = 0, n_fir = 0, n_out = 0;  // samples: of the packet, behind the filter, of what the ordinary call sees
+    // front_layout: offsets into the scratch of its own-format row (has_own), the filter's float2 row, the last float2 row
+    bool has_own = false, in_group = false;
+    size_t own_off = 0, fir_off = 0, f2_off = 0;
+    // front_describe: the rows themselves (nullptr: none)
+    const void *own_row = nullptr;
+    float *f2_row = nullptr;  // the row the ordinary call reads: the tune kernel's, the resampler's, else the filter's
+};
+
+struct FrontPlan {
+    std::vector<FrontPkt> pkt;
+    uint32_t n_gather = 0, n_tune = 0, n_fir = 0, n_rs = 0;
+    bool unknown = false;  // a strided packet of an unknown format: the whole call is the ordinary call's to refuse
+    bool rotates = false;  // a filtered or resampled packet has a tune: those kernels need the tables
+    // a strided single is read where it lies by the caller's own kernel (psk_soft_acquire_device): no row, no gather
+    bool singles_in_place = false;
+    // frame groups: maximal runs of gathered packets of one format and stride whose data lie one sample apart
     struct Run {
         uint32_t first, g, bytes;
     };
     std::vector<Run> runs;
-    std::vector<size_t> row_off(nch, 0), tune_off(n_tune || n_rs ? nch : 0, 0);  // (own-format row of a gather; float2 row of a tuned or resampled packet)
-    std::vector<size_t> fir_off(n_fir ? nch : 0, 0);  // (float2 row of a filtered packet)
-    std::vector<uint8_t> has_row(nch, 0);
-    size_t need = 0;
-    auto f2_rows = [&](uint32_t i) {
-        if (filtered[i]) {
-            fir_off[i] = need;
-            need += row_bytes(fir_n_out(i));
-        }
-        if (tuned[i] || resampled[i]) {
-            tune_off[i] = need;
-            need += f2_row(i);
-        }
-    };
-    for (uint32_t i = 0; i < nch;) {
-        if (!gathered[i]) {
-            f2_rows(i);
-            i++;
-            continue;
-        }
-        const uint32_t sb = 2u * (uint32_t)elem_bytes(pkts[i]);
-        uint32_t j = i + 1;
-        while (j < nch && gathered[j] && pkts[j].format == pkts[i].format && sample_stride[j] == sample_stride[i] &&
-               reinterpret_cast<const char *>(pkts[j].data) == reinterpret_cast<const char *>(pkts[j - 1].data) + sb)
-            j++;
-        runs.push_back({i, j - i, sb});
-        for (uint32_t c = i; c < j; c++) {
-            // (a direct column outside the tile kernel's groups has no own-format row: it is read where it lies)
-            if (!direct(c) || j - i >= psk::kGatherMinGroup) {
-                row_off[c] = need;
-                has_row[c] = 1;
-                need += align_up((size_t)sb * (pkts[c].n_floats / 2u), 128);
-            }
-            f2_rows(c);
-        }
-        i = j;
-    }
-    // descriptors, per sample size (2, 4, 8 bytes: one launch of each kernel per size): [groups | their columns | singles]
+    size_t need = 0;  // bytes of scratch
+    // descriptors, per sample size (2, 4, 8 bytes: one launch of each gather kernel per size):
+    // [groups | their columns | singles | tune | resample | fir]
     uint32_t n_groups[3] = {}, n_cols[3] = {}, n_singles[3] = {};
-    auto size_idx = [](uint32_t bytes) { return bytes == 2 ? 0 : bytes == 4 ? 1 : 2; };
-    for (const Run &r : runs) {
-        const int b = size_idx(r.bytes);
-        if (r.g >= psk::kGatherMinGroup)
-            n_groups[b]++, n_cols[b] += r.g;
-        else
-            for (uint32_t c = r.first; c < r.first + r.g; c++) n_singles[b] += !direct(c);
-    }
-    const uint32_t tot_groups = n_groups[0] + n_groups[1] + n_groups[2], tot_cols = n_cols[0] + n_cols[1] + n_cols[2];
-    const uint32_t tot_singles = n_singles[0] + n_singles[1] + n_singles[2];
-    if (!tot_groups && !tot_singles && !n_tune && !n_rs && !n_fir)
-        return PSK_SOFT_OK;
-    const size_t off_cols = sizeof(psk::GatherGroup) * tot_groups, off_singles = off_cols + sizeof(psk::GatherChan) * tot_cols;
-    const size_t off_tune = off_singles + sizeof(psk::GatherSingle) * tot_singles;
-    const size_t off_rs = off_tune + sizeof(psk::TuneDesc) * n_tune;
-    const size_t off_fir = off_rs + sizeof(psk::ResampleDesc) * n_rs;
-    const size_t desc_bytes = off_fir + sizeof(psk::FirDesc) * n_fir;
-
-    // ---- scratch: the stream's own buffer, else the one used longest ago, behind the event of its last call ----
-    // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
-    PSK_HIP(deferred_join(h, stream));
-    StreamScratch *sc = nullptr;
-    PSK_TRY(claim_scratch(h->gat, &h->gat_calls, stream, need, nullptr, &sc));
-    bool rs_tuned = false;  // (a resampled or filtered packet that is tuned as well: its kernel needs the tables)
-    for (uint32_t i = 0; i < nch && tune; i++) rs_tuned |= (resampled[i] || filtered[i]) && (tune[i].phase | tune[i].step) != 0;
-    if (n_tune || rs_tuned)
-        PSK_TRY(ensure_tune_tab(h));
-    if (n_rs)
-        PSK_TRY(ensure_resample_history(h));
-    if (n_fir)
-        PSK_TRY(ensure_fir_history(h));
-    GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
-    h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
-    if (!ds.ev)
-        PSK_HIP(hipEventCreateWithFlags(&ds.ev, hipEventDisableTiming));
-    if (ds.used)
-        PSK_HIP(hipEventSynchronize(ds.ev));
-    ds.used = false;
-    if (desc_bytes > ds.cap) {
-        if (ds.h_buf) (void)hipHostFree(ds.h_buf);
-        if (ds.d_buf) (void)hipFree(ds.d_buf);
-        ds.h_buf = ds.d_buf = nullptr;
-        ds.cap = 0;
-        const size_t cap = align_up(desc_bytes + desc_bytes / 4, 4096);
-        PSK_HIP(hipHostMalloc((void **)&ds.h_buf, cap));
-        PSK_HIP(hipMalloc((void **)&ds.d_buf, cap));
-        ds.cap = cap;
-    }
-    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
-    psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + off_cols);
-    psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + off_singles);
-    psk::TuneDesc *const ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + off_tune);
-    psk::ResampleDesc *const hr = reinterpret_cast<psk::ResampleDesc *>(ds.h_buf + off_rs);
-    psk::FirDesc *const hf = reinterpret_cast<psk::FirDesc *>(ds.h_buf + off_fir);
-    uint32_t g_at[3] = {0, n_groups[0], n_groups[0] + n_groups[1]}, c_at[3] = {0, n_cols[0], n_cols[0] + n_cols[1]};
-    uint32_t s_at[3] = {0, n_singles[0], n_singles[0] + n_singles[1]};
-    const uint32_t g_lo[3] = {g_at[0], g_at[1], g_at[2]}, c_lo[3] = {c_at[0], c_at[1], c_at[2]}, s_lo[3] = {s_at[0], s_at[1], s_at[2]};
+    size_t off_cols = 0, off_singles = 0, off_tune = 0, off_rs = 0, off_fir = 0, desc_bytes = 0;
     uint64_t n_tiles[3] = {}, max_n_single[3] = {}, max_n_tune = 0, max_n_rs = 0, max_fir_pieces = 0;
-    gs.row.assign(nch, nullptr);
-    gs.tune_row.assign(nch, nullptr);
-    gs.rs_out.assign(nch, 0);
-    for (const Run &r : runs) {
-        const int b = size_idx(r.bytes);
-        for (uint32_t c = r.first; c < r.first + r.g; c++)
-            if (has_row[c])
-                gs.row[c] = sc->buf + row_off[c];
-        if (r.g >= psk::kGatherMinGroup) {
-            psk::GatherGroup &g = hg[g_at[b]++];
-            g = psk::GatherGroup{};
-            g.src = pkts[r.first].data;
-            g.stride = sample_stride[r.first];
-            g.first = c_at[b] - c_lo[b];  // (the launch gets the columns of its sample size)
-            g.g = r.g;
-            g.tiles_c = (r.g + psk::kGatherTile - 1u) / psk::kGatherTile;
-            for (uint32_t c = r.first; c < r.first + r.g; c++) {
-                const uint64_t n = pkts[c].n_floats / 2u;
-                hc[c_at[b]++] = psk::GatherChan{sc->buf + row_off[c], n};
-                g.n_max = n > g.n_max ? n : g.n_max;
+    StreamScratch *sc = nullptr;
+    GatherDescSlot *ds = nullptr;
+    bool owed = false;  // the descriptors are on the stream: front_release is owed
+
+    bool nothing() const { return !n_gather && !n_tune && !n_fir && !n_rs; }
+    bool direct(uint32_t i) const { return singles_in_place || pkt[i].tune || pkt[i].fir || pkt[i].resample; }
+    static int size_idx(uint32_t bytes) { return bytes == 2 ? 0 : bytes == 4 ? 1 : 2; }
+};
+
+// Classifies the packets of a process call, one pass, no HIP call.  The refusals of the entry come out of it, before anything is
+// planned: per packet the filter's, the resampler's, then a stride of 0, an extent that does not fit 64 bits, data that do not
+// start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
+static psk_soft_status front_classify(const FrontCall &c, FrontPlan &plan)
+{
+    const psk_soft_handle *h = c.h;
+    plan.pkt.assign(c.nch, FrontPkt{});
+    for (uint32_t i = 0; i < c.nch; i++) {
+        const psk_soft_packet_t &k = c.pkts[i];
+        FrontPkt &p = plan.pkt[i];
+        if (!k.present)
+            continue;
+        p.data = k.data || h->dry;
+        p.has_tune = c.has_tune(i);
+        p.n_in = p.n_fir = p.n_out = k.n_floats / 2u;
+        // (a packet a front kernel can read: complex data, at least one sample, of a format the library knows)
+        const bool known = psk::pkt_format_known(k.format);
+        const bool reads = k.sri_mode == 1 && k.n_floats >= 2 && known && p.data;
+        char buf[160];
+        if (c.fir && c.fir[i].filter != 0) {
+            const psk_soft_fir_t &f = c.fir[i];
+            const char *what = f.filter > psk::kFirSlots || !h->fir_ntaps[f.filter - 1u] ? "a filter slot that is not defined"
+                               : !f.decim || f.decim > psk::kFirMaxDecim                 ? "a decimation outside 1 .. 16"
+                               : f.pos >= f.decim                                        ? "a position not below the decimation"
+                               : (f.flags & ~(uint32_t)PSK_SOFT_FIR_RESTART)             ? "unknown flag bits"
+                               : p.n_in >= psk::kFirMaxN                                 ? "2^30 samples or more"
+                                                                                         : nullptr;
+            if (what) {
+                std::snprintf(buf, sizeof buf, "psk_soft_process_device_filtered: channel %u: %s", c.ch0 + i, what);
+                return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
             }
-            g.tile0 = n_tiles[b];
-            n_tiles[b] += (uint64_t)g.tiles_c * ((g.n_max + psk::kGatherTile - 1u) / psk::kGatherTile);
+            p.n_fir = p.n_out = psk::fir_count(f.pos, f.decim, p.n_in);
+            p.fir = reads;
+        }
+        if (c.resample && c.resample[i].step != 0) {
+            const psk_soft_resample_t &r = c.resample[i];
+            const char *what = r.step < psk::kResampleStepMin || r.step > psk::kResampleStepMax ? "a step outside [2^31, 2^33]"
+                               : r.pos > psk::kResamplePosMax                                  ? "a position above 2^33"
+                               : p.n_in >= psk::kResampleMaxN                                  ? "2^30 samples or more"
+                               : r.pad                                                         ? "a non-zero pad"
+                               : (r.flags & ~(uint32_t)PSK_SOFT_RS_RESTART)                    ? "unknown flag bits"
+                                                                                               : nullptr;
+            if (what) {
+                std::snprintf(buf, sizeof buf, "psk_soft_process_device_resampled: channel %u: %s", c.ch0 + i, what);
+                return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+            }
+            // (a filter without outputs leaves the resampler nothing: its packet is the filter's alone)
+            if (reads && p.n_fir != 0) {
+                p.resample = true;
+                p.n_out = psk::resample_count(r.pos, r.step, p.n_fir);
+            }
+        }
+        // (a packet both tuned and filtered or resampled is tuned inside the first of those kernels that reads it)
+        p.tune = p.has_tune && reads && !p.fir && !p.resample;
+        const uint64_t s = c.stride(i);
+        if (s == 1) {  // (contiguous: the ordinary call's business, but for the packets a front kernel reads)
+            if ((p.tune || p.fir || p.resample) && reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
+                return fail(PSK_SOFT_ERR_INVALID_ARG, kProcessEntry.misaligned);
         } else {
-            for (uint32_t c = r.first; c < r.first + r.g; c++) {
-                if (direct(c))
-                    continue;
-                const uint64_t n = pkts[c].n_floats / 2u;
-                hs[s_at[b]++] = psk::GatherSingle{pkts[c].data, sc->buf + row_off[c], sample_stride[c], n};
-                max_n_single[b] = n > max_n_single[b] ? n : max_n_single[b];
-            }
-        }
-    }
-    // the tuned, the filtered and the resampled packets: from the row the tile kernel writes (its columns), else from where the
-    // caller has them, at their stride; a packet both filtered and resampled is resampled from its filter row
-    {
-        const bool any = n_tune || n_rs || n_fir;
-        std::vector<uint8_t> in_group(any ? nch : 0, 0);
-        for (const Run &r : runs)
-            if (any && r.g >= psk::kGatherMinGroup)
-                std::fill(in_group.begin() + r.first, in_group.begin() + r.first + r.g, (uint8_t)1);
-        uint32_t t_at = 0, r_at = 0, f_at = 0;
-        for (uint32_t c = 0; c < nch && any; c++) {
-            if (!tuned[c] && !resampled[c] && !filtered[c])
-                continue;
-            const void *const src = in_group[c] ? (const void *)(sc->buf + row_off[c]) : (const void *)pkts[c].data;
-            const uint64_t stride = in_group[c] ? 1u : stride_of(sample_stride, c);
-            const bool has_tune = tune && (tune[c].phase | tune[c].step) != 0;
-            if (filtered[c]) {
-                psk::FirDesc &d = hf[f_at++];
-                d = psk::FirDesc{};
-                d.src = src, d.dst = reinterpret_cast<float *>(sc->buf + fir_off[c]), d.stride = stride;
-                d.n = pkts[c].n_floats / 2u;
-                d.format = pkts[c].format;
-                d.flags = (fir[c].flags & PSK_SOFT_FIR_RESTART) ? psk::kFirRestart : 0u;
-                if (has_tune) {
-                    d.phase = tune[c].phase, d.step = tune[c].step;
-                    d.flags |= psk::kFirTuned;
-                }
-                d.decim = fir[c].decim, d.pos = fir[c].pos, d.n_taps = h->fir_ntaps[fir[c].filter - 1u], d.n_out = fir_n_out(c);
-                d.taps = h->d_fir_taps + (size_t)psk::kFirMaxTaps * (fir[c].filter - 1u);
-                // (the channel's current slot in, the other out: psk_soft_process_device_filtered flips them when the call is through)
-                float *const slots = h->d_fir_hist + (size_t)2u * psk::kFirHistSlotFloats * (ch0 + c);
-                d.hist_in = slots + psk::kFirHistSlotFloats * h->fir_cur[ch0 + c];
-                d.hist_out = slots + psk::kFirHistSlotFloats * (h->fir_cur[ch0 + c] ^ 1u);
-                const uint32_t piece = psk::fir_piece(d.decim);
-                const uint64_t pieces = (d.n_out + piece - 1u) / piece;
-                max_fir_pieces = pieces > max_fir_pieces ? pieces : max_fir_pieces;
-                gs.tune_row[c] = d.dst;
-                gs.rs_out[c] = d.n_out;
-                if (!resampled[c])
-                    continue;
-            }
-            float *const dst = reinterpret_cast<float *>(sc->buf + tune_off[c]);
-            gs.tune_row[c] = dst;
-            if (tuned[c]) {
-                psk::TuneDesc &d = ht[t_at++];
-                d = psk::TuneDesc{};
-                d.src = src, d.dst = dst, d.stride = stride;
-                d.n = pkts[c].n_floats / 2u;
-                d.phase = tune[c].phase, d.step = tune[c].step;
-                d.format = pkts[c].format;
-                max_n_tune = d.n > max_n_tune ? d.n : max_n_tune;
+            p.gathered = k.sri_mode == 1 && k.n_floats >= 2 && p.data;
+            PSK_TRY(strided_refusal(kProcessEntry, c.ch0 + i, k, s, p.gathered));
+            if (!known) {
+                plan.unknown = true;
                 continue;
             }
-            psk::ResampleDesc &d = hr[r_at++];
-            d = psk::ResampleDesc{};
-            d.src = src, d.dst = dst, d.stride = stride;
-            d.n = pkts[c].n_floats / 2u;
-            d.format = pkts[c].format;
-            d.flags = (resample[c].flags & PSK_SOFT_RS_RESTART) ? psk::kResampleRestart : 0u;
-            if (filtered[c]) {  // (the filter's outputs, which are tuned already)
-                d.src = sc->buf + fir_off[c], d.stride = 1u;
-                d.n = fir_n_out(c);
-                d.format = PSK_SOFT_FORMAT_CF32;
-            } else if (has_tune) {
-                d.phase = tune[c].phase, d.step = tune[c].step;
-                d.flags |= psk::kResampleTuned;
-            }
-            d.pos = resample[c].pos, d.rstep = resample[c].step, d.n_out = rs_n_out(c);
-            // (the channel's current slot in, the other out: psk_soft_process_device_resampled flips them when the call is through)
-            float *const slots = h->d_rs_hist + (size_t)kResampleHistFloats * (ch0 + c);
-            d.hist_in = slots + 6u * h->rs_cur[ch0 + c], d.hist_out = slots + 6u * (h->rs_cur[ch0 + c] ^ 1u);
-            max_n_rs = d.n_out > max_n_rs ? d.n_out : max_n_rs;
-            gs.rs_out[c] = d.n_out;
         }
-    }
-    PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, desc_bytes, hipMemcpyHostToDevice, stream));
-    ds.used = true;  // (from here on the slot waits for its event, which gather_release records whatever happens)
-    gs.sc = sc, gs.ds = &ds;
-    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: S = bytes of a complex sample, cnt = groups / singles covered)
-    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) { return trace_launch(h, what, bytes, 0, ch0, cnt, tiles, 0, 0, h->slot, stream); };
-    const psk::GatherGroup *const dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
-    const psk::GatherChan *const dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + off_cols);
-    const psk::GatherSingle *const dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + off_singles);
-    for (int b = 0; b < 3; b++) {
-        const int bytes = 2 << b;
-        if (n_groups[b]) {
-            PSK_HIP(mark("gather_tiles", bytes, n_groups[b], n_tiles[b]));
-            PSK_HIP(psk::launch_gather_tiles(bytes, dg + g_lo[b], n_groups[b], dc + c_lo[b], n_tiles[b], stream));
-        }
-        if (n_singles[b]) {
-            PSK_HIP(mark("gather_singles", bytes, n_singles[b], 0));
-            PSK_HIP(psk::launch_gather_singles(bytes, dsg + s_lo[b], n_singles[b], max_n_single[b], stream));
-        }
-    }
-    if (n_tune) {  // (cnt = tuned packets)
-        PSK_HIP(mark("tune", 8, n_tune, 0));
-        PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + off_tune), n_tune, max_n_tune, h->d_tune_tab, stream));
-    }
-    if (n_fir) {  // (cnt = filtered packets)
-        PSK_HIP(mark("fir", 8, n_fir, 0));
-        PSK_HIP(psk::launch_fir(reinterpret_cast<const psk::FirDesc *>(ds.d_buf + off_fir), n_fir, max_fir_pieces, h->d_tune_tab, stream));
-        if (!h->fir_ev)
-            PSK_HIP(hipEventCreateWithFlags(&h->fir_ev, hipEventDisableTiming));
-        PSK_HIP(hipEventRecord(h->fir_ev, stream));
-        h->fir_ev_used = true;
-    }
-    if (n_rs) {  // (cnt = resampled packets)
-        PSK_HIP(mark("resample", 8, n_rs, 0));
-        PSK_HIP(psk::launch_resample(reinterpret_cast<const psk::ResampleDesc *>(ds.d_buf + off_rs), n_rs, max_n_rs, h->d_tune_tab, stream));
-        if (!h->rs_ev)
-            PSK_HIP(hipEventCreateWithFlags(&h->rs_ev, hipEventDisableTiming));
-        PSK_HIP(hipEventRecord(h->rs_ev, stream));
-        h->rs_ev_used = true;
+        plan.n_gather += p.gathered, plan.n_tune += p.tune, plan.n_fir += p.fir, plan.n_rs += p.resample;
+        plan.rotates |= p.has_tune && (p.fir || p.resample);
     }
     return PSK_SOFT_OK;
 }
 
-// The rows and the descriptors of gather_stage are free again behind everything the call has put on the stream (without the
-// deferred join the side streams of a process call are joined into it by now; with it, the next call that gathers joins them
-// first, in gather_stage).  Returns `st`, the call's status so far, or the failure to record.
-static psk_soft_status gather_release(GatherStage &gs, hipStream_t stream, psk_soft_status st)
+// The copy of the packet array the ordinary call runs on.  It sees a filtered or resampled packet as CF32 with the samples and the
+// sample period behind those stages; with `rows` (a control-plane-only handle has none: lengths, formats and sample periods are
+// all it looks at) a packet a front kernel has written points at its last float2 row, a tuned one as CF32, and any other
+// gathered packet at its own-format row.
+static void front_packets(const FrontCall &c, const FrontPlan &plan, bool rows, std::vector<psk_soft_packet_t> &pk)
+{
+    pk.assign(c.pkts, c.pkts + c.nch);
+    for (uint32_t i = 0; i < c.nch; i++) {
+        const FrontPkt &p = plan.pkt[i];
+        psk_soft_packet_t &k = pk[i];
+        if (p.fir)
+            k.sri_xdelta = k.sri_xdelta * (double)c.fir[i].decim;
+        if (p.resample)
+            k.sri_xdelta = k.sri_xdelta * ((double)c.resample[i].step * 0x1p-32);
+        if (p.fir || p.resample || (rows && p.tune)) {
+            k.n_floats = 2u * p.n_out;
+            k.format = PSK_SOFT_FORMAT_CF32;
+        }
+        if (rows && p.f2_row)
+            k.data = p.f2_row;
+        else if (rows && p.own_row)
+            k.data = reinterpret_cast<const float *>(p.own_row);
+    }
+}
+
+// 1. Layout: the frame groups among the gathered packets, the rows of the scratch and the descriptor block.  A column of a run of at
+// least kGatherMinGroup goes through the tile kernel into its own-format row.  A column of a shorter run goes through the plain
+// strided gather, unless a front kernel reads it where it lies (FrontPlan::direct: it gets no own-format row).  Every row starts
+// on a 128-byte boundary; a float2 row holds its kernel's outputs (a tuned packet's samples), one sample's room at the least.
+static void front_layout(const FrontCall &c, FrontPlan &plan)
+{
+    auto row_bytes = [](uint64_t n) { return align_up(sizeof(float2) * (size_t)(n ? n : 1u), 128); };
+    auto f2_rows = [&](FrontPkt &p) {
+        if (p.fir) {
+            p.fir_off = plan.need;
+            plan.need += row_bytes(p.n_fir);
+        }
+        if (p.tune || p.resample) {
+            p.f2_off = plan.need;
+            plan.need += row_bytes(p.n_out);
+        }
+    };
+    for (uint32_t i = 0; i < c.nch;) {
+        if (!plan.pkt[i].gathered) {
+            f2_rows(plan.pkt[i]);
+            i++;
+            continue;
+        }
+        const uint32_t sb = 2u * (uint32_t)elem_bytes(c.pkts[i]);
+        uint32_t j = i + 1;
+        while (j < c.nch && plan.pkt[j].gathered && c.pkts[j].format == c.pkts[i].format && c.sample_stride[j] == c.sample_stride[i] &&
+               reinterpret_cast<const char *>(c.pkts[j].data) == reinterpret_cast<const char *>(c.pkts[j - 1].data) + sb)
+            j++;
+        plan.runs.push_back({i, j - i, sb});
+        const bool group = j - i >= psk::kGatherMinGroup;
+        const int b = FrontPlan::size_idx(sb);
+        if (group)
+            plan.n_groups[b]++, plan.n_cols[b] += j - i;
+        for (uint32_t k = i; k < j; k++) {
+            FrontPkt &p = plan.pkt[k];
+            p.in_group = group;
+            if (group || !plan.direct(k)) {
+                p.own_off = plan.need;
+                p.has_own = true;
+                plan.need += align_up((size_t)sb * p.n_in, 128);
+                plan.n_singles[b] += !group;
+            }
+            f2_rows(p);
+        }
+        i = j;
+    }
+    const uint32_t tot_groups = plan.n_groups[0] + plan.n_groups[1] + plan.n_groups[2];
+    const uint32_t tot_cols = plan.n_cols[0] + plan.n_cols[1] + plan.n_cols[2];
+    const uint32_t tot_singles = plan.n_singles[0] + plan.n_singles[1] + plan.n_singles[2];
+    plan.off_cols = sizeof(psk::GatherGroup) * tot_groups;
+    plan.off_singles = plan.off_cols + sizeof(psk::GatherChan) * tot_cols;
+    plan.off_tune = plan.off_singles + sizeof(psk::GatherSingle) * tot_singles;
+    plan.off_rs = plan.off_tune + sizeof(psk::TuneDesc) * plan.n_tune;
+    plan.off_fir = plan.off_rs + sizeof(psk::ResampleDesc) * plan.n_rs;
+    plan.desc_bytes = plan.off_fir + sizeof(psk::FirDesc) * plan.n_fir;
+}
+
+// 2. Describe: claims the stream's scratch (its own buffer, else the one used longest ago, behind the event of its last call) and a
+// descriptor slot, and fills the pinned descriptors.  The tune, filter and resample kernels read a column of a frame group from
+// the row the tile kernel writes, any other packet where the caller has it, at its stride; a packet both filtered and resampled
+// is resampled from its filter row.
+static psk_soft_status front_describe(const FrontCall &c, FrontPlan &plan)
+{
+    psk_soft_handle *h = c.h;
+    // PSK_SOFT_OPT_DEFERRED_JOIN: a class of an earlier call may still be reading its rows on a side stream -- joined first
+    PSK_HIP(deferred_join(h, c.stream));
+    PSK_TRY(claim_scratch(h->gat, &h->gat_calls, c.stream, plan.need, nullptr, &plan.sc));
+    if (plan.n_tune || plan.rotates)
+        PSK_TRY(ensure_tune_tab(h));
+    if (plan.n_rs)
+        PSK_TRY(h->rs_hist.ensure(h->nch));
+    if (plan.n_fir)
+        PSK_TRY(h->fir_hist.ensure(h->nch));
+    GatherDescSlot &ds = h->gdesc[h->gdesc_turn];
+    h->gdesc_turn = (h->gdesc_turn + 1) % kGatherDescSlots;
+    PSK_TRY(ds.claim(plan.desc_bytes));
+    plan.ds = &ds;
+    char *const buf = plan.sc->buf;
+    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
+    psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + plan.off_cols);
+    psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + plan.off_singles);
+    psk::TuneDesc *ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + plan.off_tune);
+    psk::ResampleDesc *hr = reinterpret_cast<psk::ResampleDesc *>(ds.h_buf + plan.off_rs);
+    psk::FirDesc *hf = reinterpret_cast<psk::FirDesc *>(ds.h_buf + plan.off_fir);
+    // (the launch of a sample size gets the groups, columns and singles of that size: they lie together, sizes in ascending order)
+    uint32_t g_at[3] = {0, plan.n_groups[0], plan.n_groups[0] + plan.n_groups[1]};
+    uint32_t c_at[3] = {0, plan.n_cols[0], plan.n_cols[0] + plan.n_cols[1]};
+    uint32_t s_at[3] = {0, plan.n_singles[0], plan.n_singles[0] + plan.n_singles[1]};
+    const uint32_t c_lo[3] = {c_at[0], c_at[1], c_at[2]};
+    for (const FrontPlan::Run &r : plan.runs) {
+        const int b = FrontPlan::size_idx(r.bytes);
+        psk::GatherGroup *g = nullptr;
+        if (r.g >= psk::kGatherMinGroup) {
+            g = &hg[g_at[b]++];
+            *g = psk::GatherGroup{};
+            g->src = c.pkts[r.first].data;
+            g->stride = c.sample_stride[r.first];
+            g->first = c_at[b] - c_lo[b];
+            g->g = r.g;
+            g->tiles_c = (r.g + psk::kGatherTile - 1u) / psk::kGatherTile;
+        }
+        for (uint32_t k = r.first; k < r.first + r.g; k++) {
+            FrontPkt &p = plan.pkt[k];
+            if (!p.has_own)
+                continue;
+            p.own_row = buf + p.own_off;
+            if (g) {
+                hc[c_at[b]++] = psk::GatherChan{buf + p.own_off, p.n_in};
+                g->n_max = p.n_in > g->n_max ? p.n_in : g->n_max;
+            } else {
+                hs[s_at[b]++] = psk::GatherSingle{c.pkts[k].data, buf + p.own_off, c.sample_stride[k], p.n_in};
+                plan.max_n_single[b] = p.n_in > plan.max_n_single[b] ? p.n_in : plan.max_n_single[b];
+            }
+        }
+        if (g) {
+            g->tile0 = plan.n_tiles[b];
+            plan.n_tiles[b] += (uint64_t)g->tiles_c * ((g->n_max + psk::kGatherTile - 1u) / psk::kGatherTile);
+        }
+    }
+    for (uint32_t i = 0; i < c.nch; i++) {
+        FrontPkt &p = plan.pkt[i];
+        if (!p.tune && !p.fir && !p.resample)
+            continue;
+        // the packet as its first kernel reads it
+        psk::FrontIo io = {};
+        io.src = p.in_group ? (const void *)(buf + p.own_off) : (const void *)c.pkts[i].data;
+        io.stride = p.in_group ? 1u : c.stride(i);
+        io.n = p.n_in;
+        io.format = c.pkts[i].format;
+        if (p.has_tune)
+            io.phase = c.tune[i].phase, io.step = c.tune[i].step, io.flags = p.tune ? 0u : psk::kFrontTuned;
+        if (p.tune) {
+            io.dst = p.f2_row = reinterpret_cast<float *>(buf + p.f2_off);
+            *ht++ = io;
+            plan.max_n_tune = io.n > plan.max_n_tune ? io.n : plan.max_n_tune;
+            continue;
+        }
+        if (p.fir) {
+            const psk_soft_fir_t &f = c.fir[i];
+            psk::FirDesc &d = *hf++;
+            d = psk::FirDesc{};
+            d.io = io;
+            d.io.dst = p.f2_row = reinterpret_cast<float *>(buf + p.fir_off);
+            d.io.flags |= (f.flags & PSK_SOFT_FIR_RESTART) ? psk::kFrontRestart : 0u;
+            d.decim = f.decim, d.pos = f.pos, d.n_taps = h->fir_ntaps[f.filter - 1u], d.n_out = p.n_fir;
+            d.taps = h->d_fir_taps + (size_t)psk::kFirMaxTaps * (f.filter - 1u);
+            d.hist_in = h->fir_hist.in(c.ch0 + i), d.hist_out = h->fir_hist.out(c.ch0 + i);
+            const uint32_t piece = psk::fir_piece(d.decim);
+            const uint64_t pieces = (d.n_out + piece - 1u) / piece;
+            plan.max_fir_pieces = pieces > plan.max_fir_pieces ? pieces : plan.max_fir_pieces;
+            if (!p.resample)
+                continue;
+            // (the resampler reads the filter's outputs, which are tuned already)
+            io = psk::FrontIo{};
+            io.src = d.io.dst, io.stride = 1u, io.n = p.n_fir, io.format = PSK_SOFT_FORMAT_CF32;
+        }
+        const psk_soft_resample_t &r = c.resample[i];
+        psk::ResampleDesc &d = *hr++;
+        d = psk::ResampleDesc{};
+        d.io = io;
+        d.io.dst = p.f2_row = reinterpret_cast<float *>(buf + p.f2_off);
+        d.io.flags |= (r.flags & PSK_SOFT_RS_RESTART) ? psk::kFrontRestart : 0u;
+        d.pos = r.pos, d.rstep = r.step, d.n_out = p.n_out;
+        d.hist_in = h->rs_hist.in(c.ch0 + i), d.hist_out = h->rs_hist.out(c.ch0 + i);
+        plan.max_n_rs = d.n_out > plan.max_n_rs ? d.n_out : plan.max_n_rs;
+    }
+    return PSK_SOFT_OK;
+}
+
+// 3. Launch: the descriptors in one copy, then the gathers per sample size, the tune kernel, the filter kernel and the resample
+// kernel, all on the call's stream; the histories' events behind their kernels.
+static psk_soft_status front_launch(const FrontCall &c, FrontPlan &plan)
+{
+    psk_soft_handle *h = c.h;
+    GatherDescSlot &ds = *plan.ds;
+    PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, plan.desc_bytes, hipMemcpyHostToDevice, c.stream));
+    ds.used = true;  // (from here on the slot waits for its event, which front_release records whatever happens)
+    plan.owed = true;
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: S = bytes of a complex sample, cnt = groups / singles / packets covered)
+    auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) {
+        return trace_launch(h, what, bytes, 0, c.ch0, cnt, tiles, 0, 0, h->slot, c.stream);
+    };
+    const psk::GatherGroup *dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
+    const psk::GatherChan *dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + plan.off_cols);
+    const psk::GatherSingle *dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + plan.off_singles);
+    for (int b = 0; b < 3; b++) {
+        const int bytes = 2 << b;
+        if (plan.n_groups[b]) {
+            PSK_HIP(mark("gather_tiles", bytes, plan.n_groups[b], plan.n_tiles[b]));
+            PSK_HIP(psk::launch_gather_tiles(bytes, dg, plan.n_groups[b], dc, plan.n_tiles[b], c.stream));
+        }
+        if (plan.n_singles[b]) {
+            PSK_HIP(mark("gather_singles", bytes, plan.n_singles[b], 0));
+            PSK_HIP(psk::launch_gather_singles(bytes, dsg, plan.n_singles[b], plan.max_n_single[b], c.stream));
+        }
+        dg += plan.n_groups[b], dc += plan.n_cols[b], dsg += plan.n_singles[b];
+    }
+    if (plan.n_tune) {
+        PSK_HIP(mark("tune", 8, plan.n_tune, 0));
+        PSK_HIP(psk::launch_tune(reinterpret_cast<const psk::TuneDesc *>(ds.d_buf + plan.off_tune), plan.n_tune, plan.max_n_tune, h->d_tune_tab, c.stream));
+    }
+    if (plan.n_fir) {
+        PSK_HIP(mark("fir", 8, plan.n_fir, 0));
+        PSK_HIP(psk::launch_fir(reinterpret_cast<const psk::FirDesc *>(ds.d_buf + plan.off_fir), plan.n_fir, plan.max_fir_pieces, h->d_tune_tab, c.stream));
+        PSK_TRY(h->fir_hist.record(c.stream));
+    }
+    if (plan.n_rs) {
+        PSK_HIP(mark("resample", 8, plan.n_rs, 0));
+        PSK_HIP(psk::launch_resample(reinterpret_cast<const psk::ResampleDesc *>(ds.d_buf + plan.off_rs), plan.n_rs, plan.max_n_rs, h->d_tune_tab, c.stream));
+        PSK_TRY(h->rs_hist.record(c.stream));
+    }
+    return PSK_SOFT_OK;
+}
+
+// Steps 1 to 3.  A call with nothing to launch returns before it touches a stream, plan.owed == false.
+static psk_soft_status front_enqueue(const FrontCall &c, FrontPlan &plan)
+{
+    front_layout(c, plan);
+    if (!plan.desc_bytes)
+        return PSK_SOFT_OK;
+    PSK_TRY(front_describe(c, plan));
+    return front_launch(c, plan);
+}
+
+// 4. Release: the rows and the descriptors are free again behind everything the call has put on the stream (without the deferred
+// join the side streams of a process call are joined into it by now; with it, the next call that gathers joins them first, in
+// front_describe).  Returns `st`, the call's status so far, or the failure to record.
+static psk_soft_status front_release(const FrontCall &c, FrontPlan &plan, psk_soft_status st)
 {
     const std::string keep = g_last_error;
-    const hipError_t e1 = hipEventRecord(gs.sc->ev, stream), e2 = hipEventRecord(gs.ds->ev, stream);
-    gs.sc->ev_used = true;
+    const hipError_t e1 = hipEventRecord(plan.sc->ev, c.stream), e2 = hipEventRecord(plan.ds->ev, c.stream);
+    plan.sc->ev_used = true;
     if (e1 != hipSuccess || e2 != hipSuccess) {
-        (void)hipStreamSynchronize(stream);
-        gs.ds->used = false;
+        (void)hipStreamSynchronize(c.stream);
+        plan.ds->used = false;
         if (st == PSK_SOFT_OK)
             return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     }
     g_last_error = keep;
     return st;
+}
+
+// 5. Commit: the histories the launches have written become the current ones -- only now that the whole call has succeeded.
+static void front_commit(const FrontCall &c, const FrontPlan &plan)
+{
+    for (uint32_t i = 0; i < c.nch; i++) {
+        if (plan.pkt[i].resample)
+            c.h->rs_hist.flip(c.ch0 + i);
+        if (plan.pkt[i].fir)
+            c.h->fir_hist.flip(c.ch0 + i);
+    }
 }
 
 // Strided packets (include/psk_soft_hip.h): every packet whose samples lie `sample_stride[i]` samples apart is gathered into a
@@ -2810,22 +2960,13 @@ static psk_soft_status gather_release(GatherStage &gs, hipStream_t stream, psk_s
 // packets.  Runs of packets that are adjacent columns of one frame-major matrix (frame groups, psk_gather.h) go through the tile
 // kernel, the rest through the plain strided gather.
 //
-// Tuned packets (`tune` non-NULL and the packet's {phase, step} not {0, 0}; psk_soft_process_device_strided, below, is this
-// entry with tune == NULL) go through the same machinery: behind the gathers one launch of the tune kernel (psk_tune.hip) writes
-// each of them, shifted, as a float2 row of the same scratch, and the packet copy points at that row with format CF32.  The kernel reads a contiguous packet where the caller
-// has it, a column of a frame group of at least kGatherMinGroup columns from the own-format row the tile kernel has just written,
-// and any other strided packet where it lies, at its stride (no gather of its own).
-//
-// Resampled packets (`resample` non-NULL and the packet's step not 0; psk_soft_process_device_tuned, below, is this entry with
-// resample == NULL): one launch of the resample kernel (psk_resample.hip) behind the gathers and the tune kernel writes each of
-// them, tuned inside the same pass if it has a tune, as a float2 row of n_out samples; the packet copy points at that row with
-// format CF32, n_out samples and the scaled sri_xdelta.  It reads its source as the tune kernel does.
-//
-// Filtered packets (`fir` non-NULL and the packet's filter not 0; psk_soft_process_device_resampled, below, is this entry with
-// fir == NULL): one launch of the filter kernel (psk_fir.hip) behind the gathers and the tune kernel and in front of the resample
-// kernel writes each of them, tuned inside the same pass if it has a tune, filtered and decimated, as a float2 row of n_out
-// samples.  A packet that is resampled as well is resampled from that row into a second one.  The packet copy points at the last
-// row with format CF32, its count and the scaled sri_xdelta.
+// Tuned packets (`tune` non-NULL and the packet's {phase, step} not {0, 0}), filtered packets (`fir` non-NULL and the packet's
+// filter not 0) and resampled packets (`resample` non-NULL and the packet's step not 0) go through the same machinery: behind the
+// gathers one launch each of the tune kernel (psk_tune.hip), the filter kernel (psk_fir.hip) and the resample kernel
+// (psk_resample.hip) writes each of them as a float2 row of the same scratch -- shifted; tuned inside the same pass if it has a
+// tune, filtered and decimated; tuned likewise, or read from the filter's row, and interpolated -- and the packet copy points at
+// the last row with format CF32, its count and the scaled sri_xdelta.  The entries below with fewer arguments are this one with
+// NULL for the rest.
 psk_soft_status psk_soft_process_device_filtered(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
                                                  const uint64_t *sample_stride, const psk_soft_tune_t *tune, const psk_soft_fir_t *fir,
                                                  const psk_soft_resample_t *resample, psk_soft_output_t *outs, void *stream_v)
@@ -2834,165 +2975,27 @@ psk_soft_status psk_soft_process_device_filtered(psk_soft_handle_t *h, uint32_t 
         return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
     if (!h || !pkts || !outs || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_process: bad arguments");
-    // the refusals of this entry, before anything is planned: a stride of 0, an extent that does not fit 64 bits, a strided packet
-    // that does not start on a whole sample.  (A packet of an unknown format is left to the ordinary call, which refuses it.)
-    auto known = [](const psk_soft_packet_t &k) { return psk::pkt_format_known(k.format); };
-    // (a strided packet the call reads: present, complex data, at least one sample)
-    auto gathered = [&](uint32_t i) {
-        const psk_soft_packet_t &k = pkts[i];
-        return k.present && stride_of(sample_stride, i) != 1 && k.sri_mode == 1 && k.n_floats >= 2 && k.data;
-    };
-    // (a packet the tune kernel reads: tuned, present, complex data, at least one sample, of a format the library knows)
-    auto tuned = [&](uint32_t i) {
-        const psk_soft_packet_t &k = pkts[i];
-        return tune && (tune[i].phase | tune[i].step) != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && k.data && known(k);
-    };
-    // (a packet the call resamples: a step, present, complex data, at least one sample, of a format the library knows; the
-    // resample kernel reads it -- and tunes it, if it has a tune: tuned() above then counts it as well)
-    // (a packet the call filters: a filter, present, complex data, at least one sample, of a format the library knows; the filter
-    // kernel reads it -- and tunes it, if it has a tune -- and the resampler, if it has one, sees the filter's outputs)
-    auto filtered = [&](uint32_t i) {
-        const psk_soft_packet_t &k = pkts[i];
-        return fir && fir[i].filter != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && known(k);
-    };
-    auto fir_n_out = [&](uint32_t i) { return psk::fir_count(fir[i].pos, fir[i].decim, pkts[i].n_floats / 2u); };
-    auto resampled = [&](uint32_t i) {
-        const psk_soft_packet_t &k = pkts[i];
-        return resample && resample[i].step != 0 && k.present && k.sri_mode == 1 && k.n_floats >= 2 && known(k) &&
-               (!filtered(i) || fir_n_out(i) != 0);
-    };
-    uint32_t n_gather = 0, n_tune = 0, n_rs = 0, n_fir = 0;
-    bool unknown = false;
-    for (uint32_t i = 0; i < nch; i++) {
-        const psk_soft_packet_t &k = pkts[i];
-        if (!k.present)
-            continue;
-        if (fir && fir[i].filter != 0) {
-            const psk_soft_fir_t &f = fir[i];
-            char buf[160];
-            const char *what = f.filter > psk::kFirSlots || !h->fir_ntaps[f.filter - 1u] ? "a filter slot that is not defined"
-                               : !f.decim || f.decim > psk::kFirMaxDecim                 ? "a decimation outside 1 .. 16"
-                               : f.pos >= f.decim                                        ? "a position not below the decimation"
-                               : (f.flags & ~(uint32_t)PSK_SOFT_FIR_RESTART)             ? "unknown flag bits"
-                               : k.n_floats / 2u >= psk::kFirMaxN                        ? "2^30 samples or more"
-                                                                                         : nullptr;
-            if (what) {
-                std::snprintf(buf, sizeof buf, "psk_soft_process_device_filtered: channel %u: %s", ch0 + i, what);
-                return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-            }
-            n_fir += filtered(i);
-        }
-        if (resample && resample[i].step != 0) {
-            const psk_soft_resample_t &r = resample[i];
-            char buf[160];
-            const char *what = r.step < psk::kResampleStepMin || r.step > psk::kResampleStepMax ? "a step outside [2^31, 2^33]"
-                               : r.pos > psk::kResamplePosMax                                  ? "a position above 2^33"
-                               : k.n_floats / 2u >= psk::kResampleMaxN                         ? "2^30 samples or more"
-                               : r.pad                                                         ? "a non-zero pad"
-                               : (r.flags & ~(uint32_t)PSK_SOFT_RS_RESTART)                    ? "unknown flag bits"
-                                                                                               : nullptr;
-            if (what) {
-                std::snprintf(buf, sizeof buf, "psk_soft_process_device_resampled: channel %u: %s", ch0 + i, what);
-                return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-            }
-            n_rs += resampled(i);
-        }
-        const uint64_t s = stride_of(sample_stride, i);
-        if (s == 1) {  // (contiguous: the ordinary call's business, but for the packets the tune kernel reads)
-            if (tuned(i) || ((resampled(i) || filtered(i)) && k.data)) {
-                if (reinterpret_cast<uintptr_t>(k.data) % (2u * elem_bytes(k)))
-                    return fail(PSK_SOFT_ERR_INVALID_ARG, kTunedEntry.misaligned);
-                n_tune += tuned(i);
-            }
-            continue;
-        }
-        PSK_TRY(strided_refusal(kTunedEntry, ch0 + i, k, s, gathered(i)));
-        if (!known(k)) {
-            unknown = true;
-            continue;
-        }
-        if (!gathered(i))
-            continue;
-        n_gather++;
-        n_tune += tuned(i);
-    }
-    // the packet behind the filter: CF32, the filter's n_out samples, the sample period scaled by the decimation
-    auto filtered_packet = [&](psk_soft_packet_t &k, uint32_t i) {
-        k.n_floats = 2u * fir_n_out(i);
-        k.format = PSK_SOFT_FORMAT_CF32;
-        k.sri_xdelta = k.sri_xdelta * (double)fir[i].decim;
-    };
-    // the packet the ordinary call sees in place of a resampled one (k: the caller's, or the one behind the filter): CF32, n_out
-    // samples, the sample period scaled by the step
-    auto resampled_packet = [&](psk_soft_packet_t &k, uint32_t i) {
-        k.n_floats = 2u * psk::resample_count(resample[i].pos, resample[i].step, k.n_floats / 2u);
-        k.format = PSK_SOFT_FORMAT_CF32;
-        k.sri_xdelta = k.sri_xdelta * ((double)resample[i].step * 0x1p-32);
-    };
-    // (a control-plane-only handle plans and counts: lengths, formats and sample periods are all it looks at)
-    if (h->dry && (n_rs || n_fir) && !unknown) {
-        std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
-        for (uint32_t c = 0; c < nch; c++) {
-            if (filtered(c))
-                filtered_packet(pk[c], c);
-            if (resampled(c))
-                resampled_packet(pk[c], c);
-        }
+    const FrontCall c = {h, ch0, nch, pkts, sample_stride, tune, fir, resample, stream_v ? (hipStream_t)stream_v : h->stream};
+    FrontPlan plan;
+    PSK_TRY(front_classify(c, plan));
+    if (plan.nothing() || plan.unknown)
+        return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
+    std::vector<psk_soft_packet_t> pk;
+    if (h->dry) {  // (a control-plane-only handle plans and counts)
+        front_packets(c, plan, false, pk);
         return psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
     }
-    // (a resampled or filtered packet without data is the ordinary call's to refuse)
-    for (uint32_t i = 0; i < nch && n_rs; i++) n_rs -= resampled(i) && !pkts[i].data;
-    for (uint32_t i = 0; i < nch && n_fir; i++) n_fir -= filtered(i) && !pkts[i].data;
-    if ((!n_gather && !n_tune && !n_rs && !n_fir) || unknown || h->dry)
-        return psk_soft_process_device(h, ch0, nch, pkts, outs, stream_v);
-
     PSK_HIP(hipSetDevice(h->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
-    std::vector<uint8_t> is_gathered(nch), is_tuned(nch), is_rs(nch), is_fir(nch);
-    for (uint32_t i = 0; i < nch; i++) {
-        is_gathered[i] = gathered(i);
-        is_rs[i] = resampled(i) && pkts[i].data;
-        is_fir[i] = filtered(i) && pkts[i].data;
-        // (a packet both tuned and resampled or filtered is tuned inside the first of those kernels that reads it)
-        is_tuned[i] = tuned(i) && !is_rs[i] && !is_fir[i];
-    }
-    GatherStage gs;
-    psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, tune, resample, is_gathered, is_tuned, is_rs, fir, is_fir, false, stream, gs);
-    if (!gs.ds)
+    psk_soft_status st = front_enqueue(c, plan);
+    if (!plan.owed)
         return st;
     if (st == PSK_SOFT_OK && !h->opt_diag_gather_only) {
-        // the ordinary call on a copy of the packets that points at the rows: a tuned, filtered or resampled packet's (last)
-        // float2 row, else the gathered one
-        std::vector<psk_soft_packet_t> pk(pkts, pkts + nch);
-        for (uint32_t c = 0; c < nch; c++) {
-            if (is_fir[c]) {
-                pk[c].data = gs.tune_row[c];
-                filtered_packet(pk[c], c);
-                if (is_rs[c])
-                    resampled_packet(pk[c], c);
-            } else if (is_rs[c]) {
-                pk[c].data = gs.tune_row[c];
-                resampled_packet(pk[c], c);
-            } else if (gs.tune_row[c]) {
-                pk[c].data = gs.tune_row[c];
-                pk[c].n_floats = 2u * (pkts[c].n_floats / 2u);
-                pk[c].format = PSK_SOFT_FORMAT_CF32;
-            } else if (gs.row[c]) {
-                pk[c].data = reinterpret_cast<const float *>(gs.row[c]);
-            }
-        }
+        front_packets(c, plan, true, pk);
         st = psk_soft_process_device(h, ch0, nch, pk.data(), outs, stream_v);
     }
-    st = gather_release(gs, stream, st);
-    // the histories the launch has written become the current ones only now that the whole call is through
+    st = front_release(c, plan, st);
     if (st == PSK_SOFT_OK)
-        for (uint32_t c = 0; c < nch; c++)
-            if (is_rs[c])
-                h->rs_cur[ch0 + c] ^= 1u;
-    if (st == PSK_SOFT_OK)
-        for (uint32_t c = 0; c < nch; c++)
-            if (is_fir[c])
-                h->fir_cur[ch0 + c] ^= 1u;
+        front_commit(c, plan);
     return st;
 }
 
@@ -3014,6 +3017,21 @@ psk_soft_status psk_soft_process_device_strided(psk_soft_handle_t *h, uint32_t c
                                                 const uint64_t *sample_stride, psk_soft_output_t *outs, void *stream_v)
 {
     return psk_soft_process_device_tuned(h, ch0, nch, pkts, sample_stride, nullptr, outs, stream_v);
+}
+
+// psk_soft_{resample,fir}_{get,set}_history behind their argument checks (a control-plane-only handle keeps zeros)
+static psk_soft_status history_get(psk_soft_handle *h, HistoryBank &bank, uint32_t ch, float *out)
+{
+    if (!h->dry)
+        PSK_HIP(hipSetDevice(h->device));
+    return bank.get(ch, out);
+}
+static psk_soft_status history_set(psk_soft_handle *h, HistoryBank &bank, uint32_t ch, const float *in)
+{
+    if (h->dry)
+        return PSK_SOFT_OK;
+    PSK_HIP(hipSetDevice(h->device));
+    return bank.set(h->nch, ch, in);
 }
 
 // ---- tuned packets: the host-side helpers (pure) ----
@@ -3106,28 +3124,14 @@ psk_soft_status psk_soft_resample_get_history(psk_soft_handle_t *h, uint32_t ch,
 {
     if (!h || !out || ch >= h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_get_history: bad arguments");
-    std::memset(out, 0, sizeof(float) * 6u);
-    if (h->dry || !h->d_rs_hist)
-        return PSK_SOFT_OK;
-    PSK_HIP(hipSetDevice(h->device));
-    if (h->rs_ev_used)
-        PSK_HIP(hipEventSynchronize(h->rs_ev));
-    PSK_HIP(hipMemcpy(out, h->d_rs_hist + (size_t)kResampleHistFloats * ch + 6u * h->rs_cur[ch], sizeof(float) * 6u, hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return history_get(h, h->rs_hist, ch, out);
 }
 
 psk_soft_status psk_soft_resample_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in)
 {
     if (!h || !in || ch >= h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_resample_set_history: bad arguments");
-    if (h->dry)
-        return PSK_SOFT_OK;  // (a control-plane-only handle keeps zeros)
-    PSK_HIP(hipSetDevice(h->device));
-    PSK_TRY(ensure_resample_history(h));
-    if (h->rs_ev_used)
-        PSK_HIP(hipEventSynchronize(h->rs_ev));  // (no launch is still reading the slot)
-    PSK_HIP(hipMemcpy(h->d_rs_hist + (size_t)kResampleHistFloats * ch + 6u * h->rs_cur[ch], in, sizeof(float) * 6u, hipMemcpyHostToDevice));
-    return PSK_SOFT_OK;
+    return history_set(h, h->rs_hist, ch, in);
 }
 
 // ---- filtered packets: the filters of a handle, the host-side helpers (pure) and the histories ----
@@ -3142,8 +3146,7 @@ psk_soft_status psk_soft_fir_define(psk_soft_handle_t *h, uint32_t slot, const f
     PSK_HIP(hipSetDevice(h->device));
     if (!h->d_fir_taps)
         PSK_HIP(hipMalloc((void **)&h->d_fir_taps, sizeof(float) * psk::kFirSlots * psk::kFirMaxTaps));
-    if (h->fir_ev_used)
-        PSK_HIP(hipEventSynchronize(h->fir_ev));  // (no launch is still reading the slot)
+    PSK_TRY(h->fir_hist.wait());  // (no launch is still reading the slot)
     PSK_HIP(hipMemcpy(h->d_fir_taps + (size_t)psk::kFirMaxTaps * slot, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice));
     h->fir_ntaps[slot] = n_taps;
     return PSK_SOFT_OK;
@@ -3206,36 +3209,20 @@ psk_soft_status psk_soft_fir_get_history(psk_soft_handle_t *h, uint32_t ch, floa
 {
     if (!h || !out || ch >= h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_get_history: bad arguments");
-    std::memset(out, 0, sizeof(float) * 2u * psk::kFirHist);
-    if (h->dry || !h->d_fir_hist)
-        return PSK_SOFT_OK;
-    PSK_HIP(hipSetDevice(h->device));
-    if (h->fir_ev_used)
-        PSK_HIP(hipEventSynchronize(h->fir_ev));
-    PSK_HIP(hipMemcpy(out, h->d_fir_hist + (size_t)psk::kFirHistSlotFloats * (2u * ch + h->fir_cur[ch]), sizeof(float) * 2u * psk::kFirHist,
-                      hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return history_get(h, h->fir_hist, ch, out);
 }
 
 psk_soft_status psk_soft_fir_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in)
 {
     if (!h || !in || ch >= h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_fir_set_history: bad arguments");
-    if (h->dry)
-        return PSK_SOFT_OK;  // (a control-plane-only handle keeps zeros)
-    PSK_HIP(hipSetDevice(h->device));
-    PSK_TRY(ensure_fir_history(h));
-    if (h->fir_ev_used)
-        PSK_HIP(hipEventSynchronize(h->fir_ev));  // (no launch is still reading the slot)
-    PSK_HIP(hipMemcpy(h->d_fir_hist + (size_t)psk::kFirHistSlotFloats * (2u * ch + h->fir_cur[ch]), in, sizeof(float) * 2u * psk::kFirHist,
-                      hipMemcpyHostToDevice));
-    return PSK_SOFT_OK;
+    return history_set(h, h->fir_hist, ch, in);
 }
 
 // ---- psk_soft_acquire_device: the carrier offset of a packet (include/psk_soft_hip.h, psk_acquire.hip) ----
 // One look at a packet per channel: the fold over pieces of kAcquirePiece samples and the join per packet, on the caller's stream,
 // one record per covered channel.  Nothing of the control plane or of the demodulator's state is read but constelationSize, and
-// nothing is written but the records (and, for the columns of a frame group, their rows of the gather scratch: gather_stage).
+// nothing is written but the records (and, for the columns of a frame group, their rows of the gather scratch: front_layout).
 // The descriptors go up from pinned memory of a slot of their own, as the quality pass's.
 // (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
 static bool acquire_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t &k)
@@ -3244,14 +3231,14 @@ static bool acquire_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_pac
     return k.present && k.sri_mode == 1 && k.n_floats >= 2 && (M == 2 || M == 4 || M == 8);
 }
 
-static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                       const uint64_t *sample_stride, const psk_soft_tune_t *tune, const GatherStage *gs, hipStream_t stream);
+static psk_soft_status acquire_enqueue(const FrontCall &c, const FrontPlan &plan);
 
 psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
                                         const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
 {
     if (!h || !pkts || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_device: bad arguments");
+    const FrontCall c = {h, ch0, nch, pkts, sample_stride, tune, nullptr, nullptr, stream_v ? (hipStream_t)stream_v : h->stream};
     // (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
     auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
     // the refusals, before anything is enqueued or any record changes
@@ -3259,7 +3246,7 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
-        PSK_TRY(strided_refusal(kAcquireEntry, ch0 + i, k, stride_of(sample_stride, i), looked_at(i)));
+        PSK_TRY(strided_refusal(kAcquireEntry, ch0 + i, k, c.stride(i), looked_at(i)));
         if (!psk::pkt_format_known(k.format)) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
@@ -3282,28 +3269,28 @@ psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint
         return PSK_SOFT_OK;
     }
     PSK_HIP(hipSetDevice(h->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
     // strided packets: the columns of a frame group of at least kGatherMinGroup go through the tile gather into own-format rows of
     // the stream's gather scratch, which the fold reads; any other strided packet is read where it lies, at its stride
-    GatherStage gs;
-    {
-        std::vector<uint8_t> is_gathered(nch), none(nch, 0);
-        for (uint32_t i = 0; i < nch; i++) is_gathered[i] = stride_of(sample_stride, i) != 1 && looked_at(i);
-        const psk_soft_status st = gather_stage(h, ch0, nch, pkts, sample_stride, nullptr, nullptr, is_gathered, none, none, nullptr, none, true, stream, gs);
-        if (!gs.ds) {
-            if (st != PSK_SOFT_OK)
-                return st;
-            return acquire_enqueue(h, ch0, nch, pkts, sample_stride, tune, nullptr, stream);
-        }
-        return gather_release(gs, stream, st != PSK_SOFT_OK ? st : acquire_enqueue(h, ch0, nch, pkts, sample_stride, tune, &gs, stream));
+    FrontPlan plan;
+    plan.singles_in_place = true;
+    plan.pkt.assign(nch, FrontPkt{});
+    for (uint32_t i = 0; i < nch; i++) {
+        plan.pkt[i].gathered = c.stride(i) != 1 && looked_at(i);
+        plan.pkt[i].n_in = pkts[i].n_floats / 2u;
     }
+    psk_soft_status st = front_enqueue(c, plan);
+    if (st == PSK_SOFT_OK)
+        st = acquire_enqueue(c, plan);
+    return plan.owed ? front_release(c, plan, st) : st;
 }
 
-// the fold and the join of an acquire call whose arguments have passed (gs: the rows of its gathered packets, or nullptr)
-static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                       const uint64_t *sample_stride, const psk_soft_tune_t *tune, const GatherStage *gs, hipStream_t stream)
+// the fold and the join of an acquire call whose arguments have passed (plan: the rows of its gathered packets)
+static psk_soft_status acquire_enqueue(const FrontCall &c, const FrontPlan &plan)
 {
-    auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
+    psk_soft_handle *const h = c.h;
+    const uint32_t ch0 = c.ch0, nch = c.nch;
+    const hipStream_t stream = c.stream;
+    auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, c.pkts[i]); };
     auto &q = h->apass.next();
     PSK_TRY(h->apass.claim(q, h->nch));
     uint64_t n_part = 0;
@@ -3315,16 +3302,16 @@ static psk_soft_status acquire_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_
         d.channel = ch0 + i;
         if (!looked_at(i))
             continue;  // (its zero record)
-        const psk_soft_packet_t &k = pkts[i];
-        const bool row = gs && gs->row[i];
-        d.src = row ? gs->row[i] : (const void *)k.data;
-        d.stride = row ? 1u : stride_of(sample_stride, i);
+        const psk_soft_packet_t &k = c.pkts[i];
+        const void *const row = plan.pkt[i].own_row;
+        d.src = row ? row : (const void *)k.data;
+        d.stride = row ? 1u : c.stride(i);
         d.n = k.n_floats / 2u;
         d.M = ctl_of(h, ch0 + i).props.constelationSize;
         d.format = k.format;
         d.flags = PSK_SOFT_A_DATA;
-        if (tune && (tune[i].phase | tune[i].step) != 0) {
-            d.phase = tune[i].phase, d.step = tune[i].step;
+        if (c.has_tune(i)) {
+            d.phase = c.tune[i].phase, d.step = c.tune[i].step;
             d.flags |= PSK_SOFT_A_TUNED;
             any_tuned = true;
         }

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "psk_front_src.h"
+
 namespace psk {
 
 constexpr uint32_t kFirMaxTaps = 128, kFirSlots = 64, kFirMaxDecim = 16;
@@ -18,26 +20,21 @@ constexpr uint32_t kFirHistSlotFloats = 256;        // one slot of the history: 
 constexpr uint32_t kFirWindow = 4096;               // inputs (float2) of one piece: the LDS window of a workgroup
 constexpr uint64_t kFirMaxN = 1ull << 30;           // a filtered packet is shorter than this many samples
 
-enum : uint32_t { kFirRestart = 1u, kFirTuned = 2u };  // FirDesc::flags
-
-// One filtered packet: what TuneDesc carries (n complex samples of `format`, `stride` samples apart at src; phase / step of the
-// NCO if kFirTuned), and the filter's own: n_taps taps at `taps` (device memory), n_out float2 at dst, the history in front of
-// the packet (127 float2, oldest first; zeros if kFirRestart) and where the history behind it goes -- the channel's other slot,
-// never the one read.
+// One filtered packet: its source (io; phase / step of the NCO if kFrontTuned), and the filter's own: n_taps taps at `taps`
+// (device memory), n_out float2 at io.dst, the history in front of the packet (127 float2, oldest first; zeros if kFrontRestart)
+// and where the history behind it goes -- the channel's other slot, never the one read.
 struct FirDesc {
-    const void *src;
-    float *dst;       // 128-byte aligned, in the handle's gather scratch
-    uint64_t stride;  // 1: contiguous (the caller's packet, or its row behind the tile gather)
-    uint64_t n;
-    uint64_t phase, step;
-    uint32_t format;  // PSK_SOFT_FORMAT_*
-    uint32_t flags;
+    FrontIo io;
     uint32_t decim, pos, n_taps, pad;
     uint64_t n_out;
     const float *taps;
     const float *hist_in;
     float *hist_out;
 };
+static_assert(sizeof(FirDesc) == 104 && offsetof(FirDesc, io) == 0 && offsetof(FirDesc, decim) == 56 && offsetof(FirDesc, pos) == 60 &&
+                  offsetof(FirDesc, n_taps) == 64 && offsetof(FirDesc, pad) == 68 && offsetof(FirDesc, n_out) == 72 &&
+                  offsetof(FirDesc, taps) == 80 && offsetof(FirDesc, hist_in) == 88 && offsetof(FirDesc, hist_out) == 96,
+              "FirDesc: the shared head, then the filter's own");
 
 // outputs of a packet of n samples: the m with pos + m * decim < n
 #if defined(__HIPCC__)

@@ -1,5 +1,5 @@
 // psk_fir.hip -- the filter pre-pass of psk_soft_process_device_filtered: every filtered packet of a call, whatever its format and
-// stride, read once, shifted in frequency if it is also tuned (psk_tune.h: tune_rotate), filtered with the real taps of its slot
+// stride, read once, shifted in frequency if it is also tuned (psk_front_src.h: tune_rotate), filtered with the real taps of its slot
 // and decimated (psk_fir.h: fir_step) and written as float2 rows of the handle's gather scratch; the resample pass or the ordinary
 // call then runs on the rows as on CF32 packets.  One launch per call.
 //
@@ -28,15 +28,11 @@
 #include <stdint.h>
 
 #include "psk_fir.h"
-#include "psk_pkt_cvt.h"
+#include "psk_front_src.h"
 #include "psk_soft_hip.h"
 #include "psk_tune.h"
 
 namespace psk {
-
-#define PSK_GLOBAL __attribute__((address_space(1)))
-typedef float fir_f2 __attribute__((ext_vector_type(2)));
-typedef float fir_f4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kFirThreads = 256;
 constexpr uint32_t kFirLoads = kFirWindow / kFirThreads;  // inputs a lane loads per piece, at most
@@ -55,74 +51,12 @@ __host__ __device__ constexpr uint32_t fir_outputs_per_lane(uint32_t decim) { re
 // padding behind every 32 samples where the lanes' stride, R * D samples, is even; none (k >> 31 = 0) where it is odd
 __host__ __device__ constexpr uint32_t fir_pad_shift(uint32_t decim) { return (fir_outputs_per_lane(decim) * decim) & 1u ? 31u : 5u; }
 
-// one sample as it lies in the packet (a load), and its float2 (arithmetic only: a lane keeps its loads apart from their first use)
-template <int FMT>
-struct FirRaw {
-    typedef typename PktWord<FMT>::type type;
-};
-template <>
-struct FirRaw<PSK_SOFT_FORMAT_CF32> {
-    typedef fir_f2 type;
-};
-template <int FMT>
-__device__ inline typename FirRaw<FMT>::type fir_load_raw(const PSK_GLOBAL void *src, uint64_t idx)
-{
-    return reinterpret_cast<const PSK_GLOBAL typename FirRaw<FMT>::type *>(src)[idx];
-}
-template <int FMT>
-__device__ inline fir_f2 fir_cvt(typename FirRaw<FMT>::type raw)
-{
-    if constexpr (FMT == PSK_SOFT_FORMAT_CF32) {
-        return raw;
-    } else {
-        const float2 v = pkt_cvt<FMT>(raw);
-        return fir_f2{v.x, v.y};
-    }
-}
-
 // entry q (0 .. 126, oldest first) of the history in front of the packet
-__device__ inline fir_f2 fir_history(const FirDesc &d, uint32_t q)
+__device__ inline f2 fir_history(const FirDesc &d, uint32_t q)
 {
-    if (d.flags & kFirRestart)
-        return fir_f2{0.0f, 0.0f};
-    return ((const PSK_GLOBAL fir_f2 *)d.hist_in)[q];
-}
-
-// the LDS entry of sample k < cnt <= kFirWindow becomes s[g0 + k]; g0 >= -(T-1), g0 + cnt <= d.n
-template <int FMT>
-__device__ inline void fir_fill(const FirDesc &d, const float *tab, fir_f2 *s, int64_t g0, uint32_t cnt)
-{
-    // All of a lane's loads are issued before the first is used: the index of a lane with nothing to load (k >= cnt, or an entry
-    // the history supplies) is clamped into the packet, so the loads are unconditional within an iteration, and the iterations'
-    // bound is the workgroup's.
-    const PSK_GLOBAL void *__restrict__ src = (const PSK_GLOBAL void *)d.src;
-    const uint32_t iters = (cnt + kFirThreads - 1u) / kFirThreads;
-    typename FirRaw<FMT>::type v[kFirLoads];
-#pragma unroll
-    for (uint32_t j = 0; j < kFirLoads; j++) {
-        const int64_t g = g0 + (int64_t)(threadIdx.x + j * kFirThreads);
-        const uint64_t idx = g < 0 ? 0u : (uint64_t)g < d.n ? (uint64_t)g : d.n - 1u;
-        v[j] = j < iters ? fir_load_raw<FMT>(src, idx * d.stride) : typename FirRaw<FMT>::type{};
-    }
-    uint64_t p = d.phase + (uint64_t)(g0 + (int64_t)threadIdx.x) * d.step;  // (mod 2^64; not used below index 0)
-    const uint64_t adv = d.step * kFirThreads;
-    const uint32_t sh = fir_pad_shift(d.decim);
-#pragma unroll
-    for (uint32_t j = 0; j < kFirLoads; j++, p += adv) {
-        const uint32_t k = threadIdx.x + j * kFirThreads;
-        if (k >= cnt)
-            continue;
-        const int64_t g = g0 + (int64_t)k;
-        fir_f2 x = fir_cvt<FMT>(v[j]);
-        if (g < 0) {
-            x = fir_history(d, (uint32_t)(g + (int64_t)kFirHist));
-        } else if (d.flags & kFirTuned) {
-            float yr, yi;
-            tune_rotate(tab, p, x.x, x.y, &yr, &yi);
-            x = fir_f2{yr, yi};
-        }
-        s[fir_pad(k, sh)] = x;
-    }
+    if (d.io.flags & kFrontRestart)
+        return f2{0.0f, 0.0f};
+    return ((const PSK_GLOBAL f2 *)d.hist_in)[q];
 }
 
 // the row of G of step q
@@ -130,10 +64,10 @@ template <int R>
 __device__ inline void fir_row(const float *G, uint32_t q, float *h)
 {
     if constexpr (R == 4) {
-        const fir_f4 v = reinterpret_cast<const fir_f4 *>(G)[q];
+        const f4 v = reinterpret_cast<const f4 *>(G)[q];
         h[0] = v.x, h[1] = v.y, h[2] = v.z, h[3] = v.w;
     } else if constexpr (R == 2) {
-        const fir_f2 v = reinterpret_cast<const fir_f2 *>(G)[q];
+        const f2 v = reinterpret_cast<const f2 *>(G)[q];
         h[0] = v.x, h[1] = v.y;
     } else {
         h[0] = G[q];
@@ -142,9 +76,9 @@ __device__ inline void fir_row(const float *G, uint32_t q, float *h)
 
 // outputs [m0, m0 + cnt_out) of the packet of d from the window whose entry 0 is s[i(m0) - (T-1)]; R outputs a lane
 template <int R>
-__device__ inline void fir_sums(const FirDesc &d, const float *G, const fir_f2 *s, uint64_t m0, uint32_t cnt_out)
+__device__ inline void fir_sums(const FirDesc &d, const float *G, const f2 *s, uint64_t m0, uint32_t cnt_out)
 {
-    PSK_GLOBAL fir_f2 *__restrict__ dst = (PSK_GLOBAL fir_f2 *)d.dst;
+    PSK_GLOBAL f2 *__restrict__ dst = (PSK_GLOBAL f2 *)d.io.dst;
     const uint32_t D = d.decim, T = d.n_taps, sh = fir_pad_shift(D);
     const uint32_t lead = (uint32_t)(R - 1) * D, Q = lead + T;
     // steps [0, head): some output has not started; [head, mid): every output has a tap, none its first; [mid, Q): some are through
@@ -157,7 +91,7 @@ __device__ inline void fir_sums(const FirDesc &d, const float *G, const fir_f2 *
         // (c = R-1-r: the output c behind the lane's last one meets the tap q - c*D at step q)
         auto tested = [&](uint32_t q0, uint32_t q1) {
             for (uint32_t q = q0; q < q1; q++) {
-                const fir_f2 x = s[fir_pad(top - q, sh)];
+                const f2 x = s[fir_pad(top - q, sh)];
                 float h[R];
                 fir_row<R>(G, q, h);
 #pragma unroll
@@ -173,7 +107,7 @@ __device__ inline void fir_sums(const FirDesc &d, const float *G, const fir_f2 *
         tested(0u, head);
 #pragma unroll 4
         for (uint32_t q = head; q < mid; q++) {
-            const fir_f2 x = s[fir_pad(top - q, sh)];
+            const f2 x = s[fir_pad(top - q, sh)];
             float h[R];
             fir_row<R>(G, q, h);
 #pragma unroll
@@ -188,22 +122,26 @@ __device__ inline void fir_sums(const FirDesc &d, const float *G, const fir_f2 *
 #pragma unroll
         for (int r = 0; r < R; r += 2) {
             if (R > 1 && (uint32_t)r + 1u < left)
-                *reinterpret_cast<PSK_GLOBAL fir_f4 *>(dst + m + r) = fir_f4{ar[r], ai[r], ar[R > 1 ? r + 1 : r], ai[R > 1 ? r + 1 : r]};
+                *reinterpret_cast<PSK_GLOBAL f4 *>(dst + m + r) = f4{ar[r], ai[r], ar[R > 1 ? r + 1 : r], ai[R > 1 ? r + 1 : r]};
             else if ((uint32_t)r < left)
-                dst[m + r] = fir_f2{ar[r], ai[r]};
+                dst[m + r] = f2{ar[r], ai[r]};
         }
     }
 }
 
 // outputs [m0, m1) of the packet of d, m0 even, m1 - m0 <= fir_piece(D)
 template <int FMT>
-__device__ inline void fir_one_piece(const FirDesc &d, const float *tab, const float *G, fir_f2 *s, uint64_t m0, uint64_t m1)
+__device__ inline void fir_one_piece(const FirDesc &d, const float *tab, const float *G, f2 *s, uint64_t m0, uint64_t m1)
 {
     const uint32_t cnt_out = (uint32_t)(m1 - m0);
-    const uint32_t cnt = (cnt_out - 1u) * d.decim + d.n_taps;  // s[i(m0) - (T-1) .. i(m1-1)]; i(m1-1) < d.n
+    const uint32_t cnt = (cnt_out - 1u) * d.decim + d.n_taps;  // s[i(m0) - (T-1) .. i(m1-1)]; i(m1-1) < d.io.n
     if (cnt > kFirWindow)
         return;  // (a descriptor the entry would have refused: the whole workgroup leaves the piece out)
-    fir_fill<FMT>(d, tab, s, (int64_t)(d.pos + m0 * d.decim) - (int64_t)(d.n_taps - 1u), cnt);
+    // the LDS entry of sample k < cnt becomes s[i(m0) - (T-1) + k]
+    const uint32_t sh = fir_pad_shift(d.decim);
+    src_fill<FMT, kFirThreads, kFirLoads>(
+        d.io, (d.io.flags & kFrontTuned) != 0, tab, (int64_t)(d.pos + m0 * d.decim) - (int64_t)(d.n_taps - 1u), cnt,
+        [&](int64_t g) { return fir_history(d, (uint32_t)(g + (int64_t)kFirHist)); }, [&](uint32_t k, f2 x) { s[fir_pad(k, sh)] = x; });
     __syncthreads();
     switch (fir_outputs_per_lane(d.decim)) {
     case 4: fir_sums<4>(d, G, s, m0, cnt_out); break;
@@ -219,24 +157,21 @@ __device__ inline void fir_write_history(const FirDesc &d, const float *tab)
 {
     if (threadIdx.x >= kFirHist)
         return;
-    const uint64_t q = d.n + threadIdx.x;  // index into the joined sequence, whose last 127 are n .. n + 126
-    fir_f2 v;
+    const uint64_t q = d.io.n + threadIdx.x;  // index into the joined sequence, whose last 127 are n .. n + 126
+    f2 v;
     if (q < kFirHist) {
         v = fir_history(d, (uint32_t)q);
     } else {
         const uint64_t idx = q - kFirHist;
-        v = fir_cvt<FMT>(fir_load_raw<FMT>((const PSK_GLOBAL void *)d.src, idx * d.stride));
-        if (d.flags & kFirTuned) {
-            float yr, yi;
-            tune_rotate(tab, d.phase + idx * d.step, v.x, v.y, &yr, &yi);
-            v = fir_f2{yr, yi};
-        }
+        v = src_load<FMT>((const PSK_GLOBAL void *)d.io.src, idx * d.io.stride);
+        if (d.io.flags & kFrontTuned)
+            v = src_rotate(tab, d.io.phase + idx * d.io.step, v);
     }
-    ((PSK_GLOBAL fir_f2 *)d.hist_out)[threadIdx.x] = v;
+    ((PSK_GLOBAL f2 *)d.hist_out)[threadIdx.x] = v;
 }
 
 template <int FMT>
-__device__ inline void fir_packet(const FirDesc &d, const float *tab, const float *G, fir_f2 *s, uint64_t n_pieces, bool owns_tail)
+__device__ inline void fir_packet(const FirDesc &d, const float *tab, const float *G, f2 *s, uint64_t n_pieces, bool owns_tail)
 {
     const uint32_t piece = fir_piece(d.decim);
     for (uint64_t p = blockIdx.y; p < n_pieces; p += gridDim.y) {
@@ -253,7 +188,7 @@ __global__ __launch_bounds__(kFirThreads) void psk_fir_kernel(const FirDesc *__r
     __shared__ __attribute__((aligned(16))) float lds[kTuneTableFloats + kFirGFloats + 2u * kFirSampleEntries];
     float *const tab = lds;
     float *const G = lds + kTuneTableFloats;
-    fir_f2 *const s = reinterpret_cast<fir_f2 *>(lds + kTuneTableFloats + kFirGFloats);
+    f2 *const s = reinterpret_cast<f2 *>(lds + kTuneTableFloats + kFirGFloats);
     const FirDesc d = desc[blockIdx.x];
     if (!d.decim || d.decim > kFirMaxDecim || !d.n_taps || d.n_taps > kFirMaxTaps)
         return;  // (the entry refuses these)
@@ -262,12 +197,8 @@ __global__ __launch_bounds__(kFirThreads) void psk_fir_kernel(const FirDesc *__r
     const bool owns_tail = n_pieces ? (n_pieces - 1u) % gridDim.y == blockIdx.y : blockIdx.y == 0;
     if (blockIdx.y >= n_pieces && !owns_tail)
         return;  // (the whole workgroup: nothing of this packet is left for it)
-    if (d.flags & kFirTuned) {
-        const PSK_GLOBAL fir_f4 *g = (const PSK_GLOBAL fir_f4 *)d_tab;
-        fir_f4 *const t = reinterpret_cast<fir_f4 *>(tab);
-#pragma unroll
-        for (uint32_t k = 0; k < kTuneTableFloats / 4u / kFirThreads; k++) t[threadIdx.x + k * kFirThreads] = g[threadIdx.x + k * kFirThreads];
-    }
+    if (d.io.flags & kFrontTuned)
+        src_tables_to_lds<kFirThreads>(tab, d_tab);
     if (blockIdx.y < n_pieces) {
         // G[q][c] = h[q - c*D], zero where that is no tap (those entries are never used)
         const uint32_t R = fir_outputs_per_lane(d.decim), rows = (R - 1u) * d.decim + d.n_taps;
@@ -278,25 +209,14 @@ __global__ __launch_bounds__(kFirThreads) void psk_fir_kernel(const FirDesc *__r
         }
     }
     __syncthreads();
-    switch (d.format) {
-    case PSK_SOFT_FORMAT_CF32: fir_packet<PSK_SOFT_FORMAT_CF32>(d, tab, G, s, n_pieces, owns_tail); break;
-    case PSK_SOFT_FORMAT_CS16: fir_packet<PSK_SOFT_FORMAT_CS16>(d, tab, G, s, n_pieces, owns_tail); break;
-    case PSK_SOFT_FORMAT_CS8: fir_packet<PSK_SOFT_FORMAT_CS8>(d, tab, G, s, n_pieces, owns_tail); break;
-    case PSK_SOFT_FORMAT_CF16: fir_packet<PSK_SOFT_FORMAT_CF16>(d, tab, G, s, n_pieces, owns_tail); break;
-    default: break;
-    }
+    src_dispatch(d.io.format, [&](auto fmt) { fir_packet<decltype(fmt)::value>(d, tab, G, s, n_pieces, owns_tail); });
 }
 
 hipError_t launch_fir(const FirDesc *desc, uint32_t n_desc, uint64_t max_pieces, const float *d_tab, hipStream_t stream)
 {
     if (!n_desc)
         return hipSuccess;
-    // as launch_resample shapes its grid: about 2048 workgroups in all, none without a piece of the longest packet
-    uint64_t per = max_pieces;
-    const uint64_t fill = (2048u + n_desc - 1u) / n_desc;
-    per = per < fill ? per : fill;
-    per = per < 1u ? 1u : per > 65535u ? 65535u : per;
-    hipLaunchKernelGGL(psk_fir_kernel, dim3(n_desc, (uint32_t)per), dim3(kFirThreads), 0, stream, desc, d_tab);
+    hipLaunchKernelGGL(psk_fir_kernel, dim3(n_desc, front_grid_y(max_pieces, n_desc)), dim3(kFirThreads), 0, stream, desc, d_tab);
     return hipGetLastError();
 }
 

@@ -10,13 +10,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psk_front_src.h"
 #include "psk_gather.h"
 
 namespace psk {
 
-// (the descriptors carry plain pointers; the kernels read and write through them as global memory -- device memory or page-locked
-// host memory, never LDS or scratch -- so that the compiler issues global, not flat, loads and stores)
-#define PSK_GLOBAL __attribute__((address_space(1)))
+// (PSK_GLOBAL, psk_front_src.h: the descriptors carry plain pointers; the kernels read and write through them as global memory --
+// device memory or page-locked host memory, never LDS or scratch -- so that the compiler issues global, not flat, loads and stores)
 
 // LDS tile: tile[column][frame], kGatherTile x kGatherTile samples, every row padded so that neither side conflicts on the 64
 // banks of 4 bytes.  The load side writes tile[lane][f] (a column per lane): the row pitch in 4-byte words must be odd (4-byte
@@ -144,12 +144,8 @@ hipError_t launch_gather_singles(int bytes, const GatherSingle *desc, uint32_t n
 {
     if (!n_desc)
         return hipSuccess;
-    // about 2048 workgroups in all, no piece shorter than 1024 samples (a thread's four)
-    uint64_t per = (max_n + 1023u) / 1024u;
-    const uint64_t fill = (2048u + n_desc - 1u) / n_desc;
-    per = per < fill ? per : fill;
-    per = per < 1u ? 1u : per > 65535u ? 65535u : per;
-    const dim3 grid(n_desc, (uint32_t)per);
+    // no piece shorter than 1024 samples (a thread's four)
+    const dim3 grid(n_desc, front_grid_y((max_n + 1023u) / 1024u, n_desc));
     if (bytes == 2)
         hipLaunchKernelGGL(psk_gather_single_kernel<uint16_t>, grid, dim3(256), 0, stream, desc);
     else if (bytes == 4)

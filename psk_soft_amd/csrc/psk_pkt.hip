@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psk_front_src.h"
 #include "psk_pkt_cvt.h"
 #include "psk_plan.h"
 #include "psk_soft_hip.h"
@@ -54,14 +55,11 @@ hipError_t launch_convert(int fmt, const CvtDesc *desc, uint32_t n_desc, uint64_
 {
     if (!n_desc)
         return hipSuccess;
-    // about 2048 workgroups in all (eight per CU), no piece shorter than 1024 samples (a thread's four)
-    uint64_t per = (max_n + 1023u) / 1024u;
-    const uint64_t fill = (2048u + n_desc - 1u) / n_desc;
-    per = per < fill ? per : fill;
-    per = per < 1u ? 1u : per > 65535u ? 65535u : per;
+    // no piece shorter than 1024 samples (a thread's four)
+    const uint32_t per = front_grid_y((max_n + 1023u) / 1024u, n_desc);
 #define PSK_PKT_CONVERT(f, id) \
     if (fmt == id)             \
-        hipLaunchKernelGGL(psk_pkt_convert_kernel<id>, dim3(n_desc, (uint32_t)per), dim3(256), 0, stream, desc);
+        hipLaunchKernelGGL(psk_pkt_convert_kernel<id>, dim3(n_desc, per), dim3(256), 0, stream, desc);
     PSK_PKT_FORMATS(PSK_PKT_CONVERT)
 #undef PSK_PKT_CONVERT
     return hipGetLastError();

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "psk_front_src.h"
+
 namespace psk {
 
 // Outputs of one piece of a packet (one pass of a workgroup over its LDS); even.  Samples (16 KiB) and the tune tables (16 KiB)
@@ -21,23 +23,23 @@ constexpr uint32_t kResampleInputs = 2u * kResamplePiece + 4u;
 constexpr uint64_t kResampleStepMin = 1ull << 31, kResampleStepMax = 1ull << 33, kResamplePosMax = 1ull << 33;
 constexpr uint64_t kResampleMaxN = 1ull << 30;  // a resampled packet is shorter than this many samples
 
-enum : uint32_t { kResampleRestart = 1u, kResampleTuned = 2u };  // ResampleDesc::flags
+// a channel's history: two slots of kResampleHist float2 (a launch reads the current one and writes the other), padded to 64 bytes
+constexpr uint32_t kResampleHist = 3, kResampleHistSlotFloats = 2u * kResampleHist, kResampleHistFloats = 16;
 
-// One resampled packet: what TuneDesc carries (n complex samples of `format`, `stride` samples apart at src; phase / step of the
-// NCO if kResampleTuned), and the resampler's own: n_out float2 at dst, the history in front of the packet (three float2, oldest
-// first; zeros if kResampleRestart) and where the history behind it goes -- the channel's other slot, never the one read.
+// One resampled packet: its source (io; phase / step of the NCO if kFrontTuned), and the resampler's own: n_out float2 at io.dst,
+// the history in front of the packet (three float2, oldest first; zeros if kFrontRestart) and where the history behind it goes --
+// the channel's other slot, never the one read.
 struct ResampleDesc {
-    const void *src;
-    float *dst;       // 128-byte aligned, in the handle's gather scratch
-    uint64_t stride;  // 1: contiguous (the caller's packet, or its row behind the tile gather)
-    uint64_t n;
-    uint64_t phase, step;
-    uint32_t format;  // PSK_SOFT_FORMAT_*
-    uint32_t flags;
+    FrontIo io;
     uint64_t pos, rstep, n_out;
     const float *hist_in;
     float *hist_out;
 };
+// (tests/prepass_probe.py mirrors the layout)
+static_assert(sizeof(ResampleDesc) == 96 && offsetof(ResampleDesc, io) == 0 && offsetof(ResampleDesc, pos) == 56 &&
+                  offsetof(ResampleDesc, rstep) == 64 && offsetof(ResampleDesc, n_out) == 72 && offsetof(ResampleDesc, hist_in) == 80 &&
+                  offsetof(ResampleDesc, hist_out) == 88,
+              "ResampleDesc: the shared head, then the resampler's own");
 
 // outputs of a packet of n samples: the m with pos + m * step < n * 2^32 (n < 2^30, step >= 2^31: nothing overflows)
 #if defined(__HIPCC__)

@@ -9,17 +9,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psk_front_src.h"
 #include "psk_libm.h"
-#include "psk_pkt_cvt.h"
 #include "psk_soft_hip.h"
 #include "psk_tune.h"
 
 namespace psk {
-
-// (the descriptors carry plain pointers; the kernel reads and writes through them as global memory, see psk_gather.hip)
-#define PSK_GLOBAL __attribute__((address_space(1)))
-typedef float tune_f2 __attribute__((ext_vector_type(2)));
-typedef float tune_f4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t kTuneThreads = 256;
 // No piece shorter than this many samples (but the packet's last): the 16 KiB of tables a workgroup copies, from the L2 after
@@ -27,30 +22,12 @@ constexpr uint32_t kTuneThreads = 256;
 // piece starts on an even sample, so the 16-byte stores of the contiguous path are aligned.
 constexpr uint64_t kTuneMinPiece = 8192;
 
-template <int FMT>
-__device__ inline tune_f2 tune_load(const PSK_GLOBAL void *src, uint64_t idx)
-{
-    if constexpr (FMT == PSK_SOFT_FORMAT_CF32) {
-        return reinterpret_cast<const PSK_GLOBAL tune_f2 *>(src)[idx];
-    } else {
-        const float2 v = pkt_cvt<FMT>(reinterpret_cast<const PSK_GLOBAL typename PktWord<FMT>::type *>(src)[idx]);
-        return tune_f2{v.x, v.y};
-    }
-}
-
-__device__ inline tune_f2 tune_mul(const float *tab, uint64_t p, tune_f2 x)
-{
-    float yr, yi;
-    tune_rotate(tab, p, x.x, x.y, &yr, &yi);
-    return tune_f2{yr, yi};
-}
-
 // samples [i0, i1) of the packet of d; i0 is a multiple of 2 * kTuneThreads
 template <int FMT>
 __device__ inline void tune_piece(const TuneDesc &d, const float *tab, uint64_t i0, uint64_t i1)
 {
     const PSK_GLOBAL void *__restrict__ src = (const PSK_GLOBAL void *)d.src;
-    PSK_GLOBAL tune_f2 *__restrict__ dst = (PSK_GLOBAL tune_f2 *)d.dst;
+    PSK_GLOBAL f2 *__restrict__ dst = (PSK_GLOBAL f2 *)d.dst;
     const uint64_t step = d.step;
     if (d.stride == 1) {
         // a lane takes two adjacent samples: 16 bytes a store.  Two such pairs an iteration, the loads issued before the stores.
@@ -58,18 +35,18 @@ __device__ inline void tune_piece(const TuneDesc &d, const float *tab, uint64_t 
         uint64_t p = d.phase + i * step;
         const uint64_t adv = step * (2u * kTuneThreads);
         for (; i + 2u * kTuneThreads + 1u < i1; i += 4u * kTuneThreads, p += 2u * adv) {
-            const tune_f2 a = tune_load<FMT>(src, i), b = tune_load<FMT>(src, i + 1u);
-            const tune_f2 c = tune_load<FMT>(src, i + 2u * kTuneThreads), e = tune_load<FMT>(src, i + 2u * kTuneThreads + 1u);
-            const tune_f2 ya = tune_mul(tab, p, a), yb = tune_mul(tab, p + step, b);
-            const tune_f2 yc = tune_mul(tab, p + adv, c), ye = tune_mul(tab, p + adv + step, e);
-            *reinterpret_cast<PSK_GLOBAL tune_f4 *>(dst + i) = tune_f4{ya.x, ya.y, yb.x, yb.y};
-            *reinterpret_cast<PSK_GLOBAL tune_f4 *>(dst + i + 2u * kTuneThreads) = tune_f4{yc.x, yc.y, ye.x, ye.y};
+            const f2 a = src_load<FMT>(src, i), b = src_load<FMT>(src, i + 1u);
+            const f2 c = src_load<FMT>(src, i + 2u * kTuneThreads), e = src_load<FMT>(src, i + 2u * kTuneThreads + 1u);
+            const f2 ya = src_rotate(tab, p, a), yb = src_rotate(tab, p + step, b);
+            const f2 yc = src_rotate(tab, p + adv, c), ye = src_rotate(tab, p + adv + step, e);
+            *reinterpret_cast<PSK_GLOBAL f4 *>(dst + i) = f4{ya.x, ya.y, yb.x, yb.y};
+            *reinterpret_cast<PSK_GLOBAL f4 *>(dst + i + 2u * kTuneThreads) = f4{yc.x, yc.y, ye.x, ye.y};
         }
         for (; i < i1; i += 2u * kTuneThreads, p += adv) {
-            const tune_f2 ya = tune_mul(tab, p, tune_load<FMT>(src, i));
+            const f2 ya = src_rotate(tab, p, src_load<FMT>(src, i));
             if (i + 1u < i1) {
-                const tune_f2 yb = tune_mul(tab, p + step, tune_load<FMT>(src, i + 1u));
-                *reinterpret_cast<PSK_GLOBAL tune_f4 *>(dst + i) = tune_f4{ya.x, ya.y, yb.x, yb.y};
+                const f2 yb = src_rotate(tab, p + step, src_load<FMT>(src, i + 1u));
+                *reinterpret_cast<PSK_GLOBAL f4 *>(dst + i) = f4{ya.x, ya.y, yb.x, yb.y};
             } else {
                 dst[i] = ya;
             }
@@ -80,11 +57,11 @@ __device__ inline void tune_piece(const TuneDesc &d, const float *tab, uint64_t 
         uint64_t p = d.phase + i * step;
         const uint64_t adv = step * kTuneThreads;
         for (; i + kTuneThreads < i1; i += 2u * kTuneThreads, p += 2u * adv) {
-            const tune_f2 a = tune_load<FMT>(src, i * d.stride), b = tune_load<FMT>(src, (i + kTuneThreads) * d.stride);
-            dst[i] = tune_mul(tab, p, a);
-            dst[i + kTuneThreads] = tune_mul(tab, p + adv, b);
+            const f2 a = src_load<FMT>(src, i * d.stride), b = src_load<FMT>(src, (i + kTuneThreads) * d.stride);
+            dst[i] = src_rotate(tab, p, a);
+            dst[i + kTuneThreads] = src_rotate(tab, p + adv, b);
         }
-        for (; i < i1; i += kTuneThreads, p += adv) dst[i] = tune_mul(tab, p, tune_load<FMT>(src, i * d.stride));
+        for (; i < i1; i += kTuneThreads, p += adv) dst[i] = src_rotate(tab, p, src_load<FMT>(src, i * d.stride));
     }
 }
 
@@ -97,31 +74,17 @@ __global__ __launch_bounds__(kTuneThreads) void psk_tune_kernel(const TuneDesc *
     if (i0 >= d.n)
         return;  // (the whole workgroup: nothing of this packet is left for it)
     const uint64_t i1 = d.n - i0 < piece ? d.n : i0 + piece;
-    {
-        const PSK_GLOBAL tune_f4 *g = (const PSK_GLOBAL tune_f4 *)d_tab;
-        tune_f4 *const t = reinterpret_cast<tune_f4 *>(tab);
-#pragma unroll
-        for (uint32_t k = 0; k < kTuneTableFloats / 4u / kTuneThreads; k++) t[threadIdx.x + k * kTuneThreads] = g[threadIdx.x + k * kTuneThreads];
-    }
+    src_tables_to_lds<kTuneThreads>(tab, d_tab);
     __syncthreads();
-    switch (d.format) {
-    case PSK_SOFT_FORMAT_CF32: tune_piece<PSK_SOFT_FORMAT_CF32>(d, tab, i0, i1); break;
-    case PSK_SOFT_FORMAT_CS16: tune_piece<PSK_SOFT_FORMAT_CS16>(d, tab, i0, i1); break;
-    case PSK_SOFT_FORMAT_CS8: tune_piece<PSK_SOFT_FORMAT_CS8>(d, tab, i0, i1); break;
-    case PSK_SOFT_FORMAT_CF16: tune_piece<PSK_SOFT_FORMAT_CF16>(d, tab, i0, i1); break;
-    default: break;
-    }
+    src_dispatch(d.format, [&](auto fmt) { tune_piece<decltype(fmt)::value>(d, tab, i0, i1); });
 }
 
 hipError_t launch_tune(const TuneDesc *desc, uint32_t n_desc, uint64_t max_n, const float *d_tab, hipStream_t stream)
 {
     if (!n_desc || !max_n)
         return hipSuccess;
-    // as launch_convert shapes its grid: about 2048 workgroups in all (eight per CU), no piece shorter than kTuneMinPiece
-    uint64_t per = (max_n + kTuneMinPiece - 1u) / kTuneMinPiece;
-    const uint64_t fill = (2048u + n_desc - 1u) / n_desc;
-    per = per < fill ? per : fill;
-    per = per < 1u ? 1u : per > 65535u ? 65535u : per;
+    // no piece shorter than kTuneMinPiece
+    const uint64_t per = front_grid_y((max_n + kTuneMinPiece - 1u) / kTuneMinPiece, n_desc);
     const uint64_t unit = 2u * kTuneThreads;
     const uint64_t piece = ((max_n + per - 1u) / per + unit - 1u) / unit * unit;
     hipLaunchKernelGGL(psk_tune_kernel, dim3(n_desc, (uint32_t)per), dim3(kTuneThreads), 0, stream, desc, d_tab, piece);

@@ -375,7 +375,7 @@ class SinglesCase(_Case):
 
 class TilesCase(_Case):
     """One launch of the tile gather.  groups: (lengths of the g adjacent columns, columns of the matrix in front of them,
-    columns behind them); the descriptors are filled as gather_stage (psk_capi.cpp) fills them."""
+    columns behind them); the descriptors are filled as front_describe (psk_capi.cpp) fills them."""
 
     def __init__(self, sample_bytes, groups, seed):
         super().__init__()

@@ -171,7 +171,7 @@ int psk_prepass_probe_resample(void *arena, uint64_t bytes, const void *desc, ui
     if (!r.begin(arena, bytes))
         return r.end(hipSuccess, arena, 0, nullptr);
     for (ResampleDesc &t : d)
-        if (!point(t.src, r.d_arena, bytes) || !point(t.dst, r.d_arena, bytes) || !point(t.hist_in, r.d_arena, bytes) ||
+        if (!point(t.io.src, r.d_arena, bytes) || !point(t.io.dst, r.d_arena, bytes) || !point(t.hist_in, r.d_arena, bytes) ||
             !point(t.hist_out, r.d_arena, bytes))
             return r.end(hipErrorInvalidValue, arena, 0, nullptr);
     if (!r.descriptors(0, d.data(), sizeof(ResampleDesc) * d.size()) || !r.tables())

@@ -449,7 +449,7 @@ def test_1100_packets_in_one_call_and_their_histories_carried(oracle_mod, monkey
     some and by workgroup 1 for others.  Those ten sit on channels with samplesPerBaud 1 and numAvg 0: every row sample is a
     symbol.  The other packets have 1 .. 40 samples; every 50th has pos 2^33 and 1 or 2 samples -- no output, but its history
     moves.  A second call reads the histories back and carries them.  What tests/test_gpu_prepass_probe.py cannot see is
-    checked here: the descriptor offsets, row offsets and history slots gather_stage computes for a call of this size."""
+    checked here: the descriptor offsets, row offsets and history slots front_layout and front_describe compute for a call of this size."""
     from psk_soft_amd import lib as pl
 
     P = pl.resample_piece()

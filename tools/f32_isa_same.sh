@@ -1,6 +1,7 @@
 #!/bin/bash
 # Is the machine code unchanged?  Compiles every wave-scan instantiation of tools/lint_all.sh's list and the other translation
-# units (psk_tile.hip, psk_kernels.hip, psk_farfit.hip, psk_tune.hip, psk_tile_inst.hip S 2 .. 16) to gfx950 assembly twice -- from the working tree and from
+# units (psk_tile.hip, psk_kernels.hip, psk_farfit.hip, the pre-passes psk_tune.hip, psk_resample.hip, psk_fir.hip, psk_acquire.hip,
+# psk_gather.hip and psk_pkt.hip, psk_tile_inst.hip S 2 .. 16) to gfx950 assembly twice -- from the working tree and from
 # git ref REF -- and compares the instruction streams with comments, directives, metadata and labels stripped.  The units of the
 # packet formats read in place (cs16, cs8, cf16) are compared too: the wave-scan kernel for samplesPerBaud 2 .. 16, both tiers,
 # the reference-order kernel and the conversion kernel of psk_pkt.hip, 32 each.  Either tree may still spell them the old way
@@ -84,6 +85,11 @@ for s in $(seq 2 16); do list="$list $s,0,0"; done
     echo "kernels psk_kernels.hip"
     echo "farfit psk_farfit.hip"
     echo "tune psk_tune.hip"
+    echo "resample psk_resample.hip"
+    echo "fir psk_fir.hip"
+    echo "acquire psk_acquire.hip"
+    echo "gather psk_gather.hip"
+    echo "pkt psk_pkt.hip"
     for s in $(seq 2 16); do echo "tile_inst_S$s psk_tile_inst.hip -DPSK_INST_S=$s -DPSK_INST_H=1"; done
     for f in cs16 cs8 cf16; do
         for s in $(seq 2 16); do for e in 0 1; do echo "${f}_fast_S${s}_H1_E$e psk_fast_inst.hip PKT=$f -DPSK_INST_S=$s -DPSK_INST_H=1 -DPSK_INST_E=$e"; done; done
