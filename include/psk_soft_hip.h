@@ -658,6 +658,91 @@ psk_soft_status psk_soft_acquire_host(uint16_t constelationSize, const psk_soft_
 uint64_t psk_soft_acquire_bytes(void);      /* sizeof(psk_soft_acquire_t), for bindings */
 uint32_t psk_soft_acquire_piece(void);      /* samples of one piece of the device's fold (tests: the lengths at its edges) */
 
+/* ---- symbol rate of a packet (psk_soft_symrate_device) ------------------------------------------------------------------------
+ * psk_soft_process_device_resampled takes a symbol rate that does not divide the sample rate to samplesPerBaud samples a symbol;
+ * this call finds the ratio.  It is the carrier look's lag ladder applied to the timing tone: the envelope of a shaped PSK signal,
+ * and the transition energy of a rectangular one, carry a line at the symbol rate; folded over blocks of S = samplesPerBaud
+ * samples that line turns by f = S/sps - 1 cycles from one block to the next, and the lag products of the block sums measure f.
+ *
+ * The call looks at one packet per channel and leaves one record per channel.  It emits no symbols, keeps no history and touches
+ * no demodulator state, resampler history or filter history: psk_soft_peek, psk_soft_query, the state blob, warning counts,
+ * statistics, quality records, carrier-look records and the results of every later process call are what they are without it.
+ * It ignores sriChanged and inputQueueFlushed.
+ *
+ * The definition.  S is the channel's stored samplesPerBaud, the value the next process call would snapshot.  Lags are L_j = 2^j
+ * blocks, j = 0 .. 7.
+ * Samples: converted, and tuned if tune[i] is given and not {0, 0}, exactly as for psk_soft_acquire_device.  Call the result
+ *   (re, im) of sample k.  The look uses the first n_used = min(n, 4096 S) samples rounded down to whole blocks of S samples:
+ *   n_blocks = min(n, 4096 S) / S, n_used = n_blocks S.  Block m holds the samples k = m S + p, p = 0 .. S - 1.
+ * Per sample, every operation float32, rounded once, no fused multiply-add, denormals kept -- two detectors of the line:
+ *     e_k = re*re + im*im                                                   (the envelope: shaped pulses)
+ *     g_k = dr*dr + di*di,  dr = re_k - re_{k-1},  di = im_k - im_{k-1};  g_0 = 0  (the transition energy: rectangular pulses)
+ * Per position p: (c_p, s_p) is the phasor W that "tuned packets" (above) defines for the phase word
+ *   (0 - p * floor(2^64 / S)) mod 2^64 -- the two table entries multiplied as there.  It restarts in every block and does not drift.
+ * Per block m and detector z in {e, g} (index 0, 1):
+ *     B_z[m] = (sum_p (double)(z_k * c_p), sum_p (double)(z_k * s_p))      the products float32, the sums double
+ *   A block is VALID when all its samples are finite, the sample in front of its first one is finite if there is one, and all
+ *   its e and g are finite.  An invalid block enters nothing.  Over the valid blocks: sum_pow[z] = sum of
+ *   Br*Br + Bi*Bi (doubles, no fused multiply-add), sum_lvl[z] = sum of (double)z_k over their samples, n_valid their count.
+ * Per lag j, for every m >= L_j with blocks m and m - L_j both valid (a = B_z[m], b = B_z[m - L_j]; doubles, no fused multiply-add):
+ *     sum_re[z][j] += ar*br + ai*bi,  sum_im[z][j] += ai*br - ar*bi;  n_pairs[j]++ (the same for both detectors)
+ * Order of the additions: fixed by the code, a function of (n_used, S) only -- not of the batch, the grid, the stride, the format
+ *   or the stream: the same samples give the same bytes whether the packet stands alone or among 4095 others.  No floating-point
+ *   atomics.  (psk_soft_symrate_host adds in index order: its sums agree with the device's within n * 2^-53 * sum|t| -- for the
+ *   lag sums with the block sums' own error of S * 2^-53 * sum|term| carried through the product --, not bit for bit.) */
+enum { PSK_SOFT_SR_DATA = 1, PSK_SOFT_SR_TUNED = 2, PSK_SOFT_SR_PLANNED = 128 };
+
+typedef struct psk_soft_symrate {        /* the LAST psk_soft_symrate_device call that covered the channel */
+    uint64_t n_samples, n_used;          /* complex samples of the packet; of those, the ones the look used */
+    uint64_t n_blocks, n_valid;          /* n_used / samplesPerBaud; of those, valid ones                   */
+    uint64_t n_pairs[8];                 /* per lag: pairs of blocks that entered the sums                  */
+    double sum_re[2][8], sum_im[2][8];   /* per detector (0: e, 1: g) and lag: sums of the lag products     */
+    double sum_pow[2], sum_lvl[2];       /* per detector: sum of |B|^2, sum of z, over the valid blocks     */
+    uint16_t samplesPerBaud; uint8_t flags; uint8_t pad[5];     /* PSK_SOFT_SR_*; pad zero                 */
+} psk_soft_symrate_t;                    /* 392 bytes */
+
+/* psk_soft_symrate_derive (doubles; C atan2, hypot, rint).  Per detector z, with p_z = sum_pow[z] / n_valid the mean power of a
+ * block sum:  c_j[z] = |(sum_re[z][j], sum_im[z][j])| / (n_pairs[j] * p_z); c_0[z] = 0 for a detector whose lag-1 sums are both
+ * zero.  The detector with the larger c_0 answers, a tie goes to e (detector = 0).
+ *   All doubles NaN, detector -1 and lags_used 0 without PSK_SOFT_SR_DATA, with n_pairs[0] == 0 or with the lag-1 sums of both
+ *   detectors zero.  Else, on the chosen detector,
+ *   f = atan2(sum_im[0], sum_re[0]) / (2 pi), lags_used = 1; then for j = 1 .. 7, stopping at the first j with n_pairs[j] < 8 or
+ *   c_j < 0.5 * c_0 (the factor is part of the definition):
+ *     d = atan2(sum_im[j], sum_re[j]) - 2 pi L_j f,  d -= 2 pi rint(d / (2 pi)),  f += d / (2 pi L_j),  lags_used++
+ *   samples_per_symbol = S / (1 + f), step_ratio = 1 / (1 + f) -- what psk_soft_resample_step takes to bring the signal to S samples
+ *   a symbol --, coherence = c_0, mean_level = sum_lvl / (n_valid * S) of the chosen detector.
+ * Range: f is unambiguous for |f| < 1/2, but the USEFUL range is a symbol rate within about +-20 % of S samples a symbol: the
+ * line's image at -1/sps leaks through the block sum beyond that and pulls the estimate (11.0 at S = 8 and 5.2 at S = 4 fail).
+ * coherence is of the order of n_blocks^-1/2 for noise and near 1 for a clean signal; the threshold is the host's choice.
+ * Which detector answers: e for band-limited (shaped) pulses, whose envelope dips between symbols; g for rectangular pulses,
+ * whose envelope is flat (c_0[e] ~ noise) and whose only trace of the symbol clock is the jump at a transition. */
+typedef struct psk_soft_symrate_derived { double samples_per_symbol, step_ratio, coherence, mean_level; int32_t detector, lags_used; } psk_soft_symrate_derived_t;
+
+/* Packets, strides and tunes as for psk_soft_acquire_device, and its refusals (PSK_SOFT_ERR_INVALID_ARG before anything is enqueued
+ * or any record changes): a bad channel range, and on a present packet a stride of 0, an extent that does not fit 64 bits, an
+ * unknown format, or `data` that is missing or not aligned to a whole sample when the packet holds samples the call would read.
+ * A covered channel gets a DATA record (PSK_SOFT_SR_DATA, and PSK_SOFT_SR_TUNED if it was tuned) when its packet is present, has
+ * sri_mode == 1, 4 <= samplesPerBaud <= 1024 and at least 2 samplesPerBaud samples; every other covered channel gets an all-zero
+ * record, written in stream order; a channel the call does not cover keeps its record.
+ * How: two launches on `stream`, a fold over pieces of a fixed number of blocks (the 128 blocks in front of a piece are computed
+ * again; the block sums stay in LDS) and a join per packet.  Strided packets go through the gather exactly as the carrier look's
+ * do -- the first n_used samples of a column of a run of at least 8, any other strided packet read where it lies --, with that
+ * entry's scratch, events and rule of PSK_SOFT_OPT_DEFERRED_JOIN.  Nothing else is launched.  A control-plane-only handle checks
+ * the arguments, then fills in n_samples, n_used, n_blocks, samplesPerBaud and flags = PSK_SOFT_SR_PLANNED for the packets that
+ * would give a data record, everything else zero. */
+psk_soft_status psk_soft_symrate_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts /* [nch] */,
+                                        const uint64_t *sample_stride /* [nch], or NULL */, const psk_soft_tune_t *tune /* [nch], or NULL */,
+                                        void *stream);
+/* waits like psk_soft_get_acquire does and copies the records of [ch0, ch0+nch) out */
+psk_soft_status psk_soft_get_symrate(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_symrate_t *rec /* [nch] */);
+psk_soft_status psk_soft_symrate_derive(const psk_soft_symrate_t *rec, psk_soft_symrate_derived_t *d);   /* host only, pure */
+/* host only, pure: the definition for n_complex CF32 samples (tune NULL or {0, 0}: untuned), the sums added in index order; the
+ * zero record for n_complex < 2 samplesPerBaud; PSK_SOFT_ERR_INVALID_ARG for a samplesPerBaud outside 4 .. 1024 */
+psk_soft_status psk_soft_symrate_host(uint16_t samplesPerBaud, const psk_soft_tune_t *tune /* or NULL */,
+                                      const float *in, uint64_t n_complex, psk_soft_symrate_t *rec);
+uint64_t psk_soft_symrate_bytes(void);      /* sizeof(psk_soft_symrate_t), for bindings */
+uint32_t psk_soft_symrate_piece(void);      /* blocks of one piece of the device's fold (tests: the lengths at its edges) */
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "psk_acquire.h"
+#include "psk_symrate.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -667,6 +668,10 @@ struct psk_soft_handle {
     psk_soft_acquire_t *d_acquire = nullptr;
     std::vector<psk_soft_acquire_t> acquire_dry;
     PassRing<psk::AcquireDesc, psk::AcquirePartial, kAcquireSlots> apass;
+    // psk_soft_symrate_device: the same for the symbol-rate look (psk_symrate.hip)
+    psk_soft_symrate_t *d_symrate = nullptr;
+    std::vector<psk_soft_symrate_t> symrate_dry;
+    PassRing<psk::SymrateDesc, psk::SymratePartial, kAcquireSlots> spass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -2059,6 +2064,7 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
     if (h->dry) {
         h->quality_dry.assign(n_channels, psk_soft_quality_t{});
         h->acquire_dry.assign(n_channels, psk_soft_acquire_t{});
+        h->symrate_dry.assign(n_channels, psk_soft_symrate_t{});
     }
     if (const char *e = std::getenv("PSK_SOFT_TIME_TILED"))
         h->opt_tiled = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
@@ -2131,6 +2137,9 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
         if ((e2 = hipMalloc((void **)&h->d_acquire, sizeof(psk_soft_acquire_t) * (size_t)n_channels)) != hipSuccess)
             return bail("hipMalloc acquire", e2);
         if ((e2 = hipMemset(h->d_acquire, 0, sizeof(psk_soft_acquire_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
+        if ((e2 = hipMalloc((void **)&h->d_symrate, sizeof(psk_soft_symrate_t) * (size_t)n_channels)) != hipSuccess)
+            return bail("hipMalloc symrate", e2);
+        if ((e2 = hipMemset(h->d_symrate, 0, sizeof(psk_soft_symrate_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
         for (int s = 0; s < kPlanSlots; s++) {
             // (a slot = the plans of a call followed by the compact channel lists of its launches: one upload)
             // (... behind the header the kernels find in front of the plans: psk_plan.h)
@@ -2177,6 +2186,8 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_quality) (void)hipFree(h->d_quality);
         h->apass.free();
         if (h->d_acquire) (void)hipFree(h->d_acquire);
+        h->spass.free();
+        if (h->d_symrate) (void)hipFree(h->d_symrate);
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
         if (h->d_test) (void)hipFree(h->d_test);
@@ -3435,6 +3446,260 @@ psk_soft_status psk_soft_acquire_derive(const psk_soft_acquire_t *rec, psk_soft_
     d->offset_cycles_per_sample = f;
     d->coherence = c0;
     d->mean_energy = rec->n_valid ? rec->sum_e / (double)rec->n_valid : nan;
+    d->lags_used = used;
+    return PSK_SOFT_OK;
+}
+
+// ---- psk_soft_symrate_device: the symbol rate of a packet (include/psk_soft_hip.h, psk_symrate.hip) ----
+// The carrier look's shape, one for one: a fold over pieces of kSymratePiece blocks and a join per packet on the caller's stream,
+// one record per covered channel; its refusals, its gather (of the samples the look uses), a pass ring of its own.  Nothing of the
+// control plane is read but samplesPerBaud, nothing is written but the records and the rows of the gather scratch.
+// (a packet the call reads: present, complex data, a block length the look is defined for, at least two blocks)
+static bool symrate_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t &k)
+{
+    const uint32_t S = ctl_of(h, ch).props.samplesPerBaud;
+    return k.present && k.sri_mode == 1 && S >= psk::kSymrateMinS && S <= psk::kSymrateMaxS && k.n_floats / 2u >= 2u * (uint64_t)S;
+}
+// blocks the look uses of n samples
+static uint32_t symrate_blocks(uint64_t n, uint32_t S)
+{
+    const uint64_t b = n / S;
+    return (uint32_t)(b < psk::kSymrateMaxBlocks ? b : psk::kSymrateMaxBlocks);
+}
+
+static const StridedEntry kSymrateEntry = {"psk_soft_symrate_device", "psk_soft_symrate_device: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4)"};
+static psk_soft_status symrate_enqueue(const FrontCall &c, const FrontPlan &plan);
+
+psk_soft_status psk_soft_symrate_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                        const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
+{
+    if (!h || !pkts || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_symrate_device: bad arguments");
+    const FrontCall c = {h, ch0, nch, pkts, sample_stride, tune, nullptr, nullptr, stream_v ? (hipStream_t)stream_v : h->stream};
+    auto looked_at = [&](uint32_t i) { return symrate_looks_at(h, ch0 + i, pkts[i]); };
+    // the refusals, before anything is enqueued or any record changes
+    for (uint32_t i = 0; i < nch; i++) {
+        const psk_soft_packet_t &k = pkts[i];
+        if (!k.present)
+            continue;
+        PSK_TRY(strided_refusal(kSymrateEntry, ch0 + i, k, c.stride(i), looked_at(i)));
+        if (!psk::pkt_format_known(k.format)) {
+            char buf[160];
+            std::snprintf(buf, sizeof buf, "psk_soft_symrate_device: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
+                          ch0 + i, (unsigned)k.format);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        if (looked_at(i) && !k.data && !h->dry)
+            return fail(PSK_SOFT_ERR_INVALID_ARG, kSymrateEntry.misaligned);
+    }
+    if (h->dry) {
+        for (uint32_t i = 0; i < nch; i++) {
+            psk_soft_symrate_t r = {};
+            if (looked_at(i)) {
+                const uint32_t S = ctl_of(h, ch0 + i).props.samplesPerBaud;
+                r.n_samples = pkts[i].n_floats / 2u;
+                r.n_blocks = symrate_blocks(r.n_samples, S);
+                r.n_used = r.n_blocks * S;
+                r.samplesPerBaud = (uint16_t)S;
+                r.flags = PSK_SOFT_SR_PLANNED;
+            }
+            h->symrate_dry[ch0 + i] = r;
+        }
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    // strided packets as in psk_soft_acquire_device; a row holds the samples the look uses, no more
+    FrontPlan plan;
+    plan.singles_in_place = true;
+    plan.pkt.assign(nch, FrontPkt{});
+    for (uint32_t i = 0; i < nch; i++) {
+        plan.pkt[i].gathered = c.stride(i) != 1 && looked_at(i);
+        plan.pkt[i].n_in = pkts[i].n_floats / 2u;
+        if (looked_at(i)) {
+            const uint32_t S = ctl_of(h, ch0 + i).props.samplesPerBaud;
+            plan.pkt[i].n_in = (uint64_t)symrate_blocks(plan.pkt[i].n_in, S) * S;
+        }
+    }
+    psk_soft_status st = front_enqueue(c, plan);
+    if (st == PSK_SOFT_OK)
+        st = symrate_enqueue(c, plan);
+    return plan.owed ? front_release(c, plan, st) : st;
+}
+
+// the fold and the join of a symbol-rate call whose arguments have passed (plan: the rows of its gathered packets)
+static psk_soft_status symrate_enqueue(const FrontCall &c, const FrontPlan &plan)
+{
+    psk_soft_handle *const h = c.h;
+    const uint32_t ch0 = c.ch0, nch = c.nch;
+    const hipStream_t stream = c.stream;
+    auto &q = h->spass.next();
+    PSK_TRY(h->spass.claim(q, h->nch));
+    uint64_t n_part = 0;
+    uint32_t max_piece = 0;
+    for (uint32_t i = 0; i < nch; i++) {
+        psk::SymrateDesc &d = q.h_desc[i];
+        d = psk::SymrateDesc{};
+        d.channel = ch0 + i;
+        if (!symrate_looks_at(h, ch0 + i, c.pkts[i]))
+            continue;  // (its zero record)
+        const psk_soft_packet_t &k = c.pkts[i];
+        const void *const row = plan.pkt[i].own_row;
+        d.src = row ? row : (const void *)k.data;
+        d.stride = row ? 1u : c.stride(i);
+        d.n = k.n_floats / 2u;
+        d.S = ctl_of(h, ch0 + i).props.samplesPerBaud;
+        d.wstep = psk::sr_wstep(d.S);
+        d.n_blocks = symrate_blocks(d.n, d.S);
+        d.format = k.format;
+        d.flags = PSK_SOFT_SR_DATA;
+        if (c.has_tune(i)) {
+            d.phase = c.tune[i].phase, d.step = c.tune[i].step;
+            d.flags |= PSK_SOFT_SR_TUNED;
+        }
+        d.part0 = (uint32_t)n_part;
+        d.n_piece = (d.n_blocks + psk::kSymratePiece - 1u) / psk::kSymratePiece;  // (at most 8 a packet: no overflow to refuse)
+        n_part += d.n_piece;
+        max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
+    }
+    PSK_TRY(h->spass.grow(q, n_part));
+    PSK_TRY(ensure_tune_tab(h));  // (the block phasors come from the tables, tuned or not)
+    PSK_TRY(h->spass.upload(q, ch0, nch, stream));
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = covered channels, tiles = pieces)
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_part, 0, 0, h->slot, stream); };
+    auto enqueue = [&]() -> psk_soft_status {
+        PSK_HIP(mark("symrate_fold"));
+        PSK_HIP(psk::launch_symrate_fold(q.d_desc, nch, max_piece, h->d_tune_tab, q.d_part, stream));
+        PSK_HIP(mark("symrate_join"));
+        PSK_HIP(psk::launch_symrate_join(q.d_desc, nch, q.d_part, h->d_symrate, stream));
+        return PSK_SOFT_OK;
+    };
+    return h->spass.finish(q, stream, enqueue());
+}
+
+uint64_t psk_soft_symrate_bytes(void) { return sizeof(psk_soft_symrate_t); }
+uint32_t psk_soft_symrate_piece(void) { return psk::kSymratePiece; }
+
+psk_soft_status psk_soft_get_symrate(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_symrate_t *rec)
+{
+    if (!h || !rec || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_symrate: bad arguments");
+    if (h->dry) {
+        std::memcpy(rec, h->symrate_dry.data() + ch0, sizeof(psk_soft_symrate_t) * nch);
+        return PSK_SOFT_OK;
+    }
+    const psk_soft_status st = psk_soft_synchronize(h);
+    if (st != PSK_SOFT_OK)
+        return st;
+    PSK_TRY(h->spass.wait());
+    PSK_HIP(hipMemcpy(rec, h->d_symrate + ch0, sizeof(psk_soft_symrate_t) * nch, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_symrate_host(uint16_t samplesPerBaud, const psk_soft_tune_t *tune, const float *in, uint64_t n_complex,
+                                      psk_soft_symrate_t *rec)
+{
+    const uint32_t S = samplesPerBaud;
+    if (!rec || (n_complex && !in) || S < psk::kSymrateMinS || S > psk::kSymrateMaxS)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_symrate_host: null pointer, or a samplesPerBaud outside 4 .. 1024");
+    *rec = psk_soft_symrate_t{};
+    if (n_complex < 2u * (uint64_t)S)
+        return PSK_SOFT_OK;  // (fewer than two blocks: the zero record)
+    const bool tuned = tune && (tune->phase | tune->step) != 0;
+    const float *const tab = psk::tune_tables();
+    const uint64_t wstep = psk::sr_wstep(S);
+    const uint32_t n_blocks = symrate_blocks(n_complex, S);
+    // the sums of the last kSymrateHalo blocks, by index mod kSymrateHalo: B_e (re, im), B_g (re, im)
+    double B[psk::kSymrateHalo][4];
+    bool valid[psk::kSymrateHalo];
+    uint64_t ph = tuned ? tune->phase : 0;
+    float pre = 0.0f, pim = 0.0f;
+    for (uint32_t m = 0; m < n_blocks; m++) {
+        double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        bool ok = true;
+        for (uint32_t p = 0; p < S; p++) {
+            const uint64_t k = (uint64_t)m * S + p;
+            float re = in[2u * k], im = in[2u * k + 1u];
+            if (tuned) {
+                psk::tune_rotate(tab, ph, re, im, &re, &im);
+                ph += tune->step;
+            }
+            float e, g, cs, sn, tr, ti;
+            ok = psk::sr_sample(re, im, pre, pim, k != 0, &e, &g) && ok;
+            psk::tune_phasor(tab, psk::sr_phase(p, wstep), &cs, &sn);
+            psk::sr_term(e, cs, sn, &tr, &ti);
+            a[0] += (double)tr, a[1] += (double)ti;
+            psk::sr_term(g, cs, sn, &tr, &ti);
+            a[2] += (double)tr, a[3] += (double)ti;
+            a[4] += (double)e, a[5] += (double)g;
+            pre = re, pim = im;
+        }
+        if (ok) {
+        rec->n_valid++;
+        rec->sum_pow[0] += psk::sr_pow(a[0], a[1]), rec->sum_pow[1] += psk::sr_pow(a[2], a[3]);
+        rec->sum_lvl[0] += a[4], rec->sum_lvl[1] += a[5];
+        for (uint32_t j = 0; j < psk::kSymrateLags; j++) {
+            const uint32_t L = 1u << j;
+            if (m < L)
+                break;
+            if (!valid[(m - L) % psk::kSymrateHalo])
+                continue;
+            const double *const o = B[(m - L) % psk::kSymrateHalo];
+            double tr, ti;
+            psk::sr_lag(a[0], a[1], o[0], o[1], &tr, &ti);
+            rec->sum_re[0][j] += tr, rec->sum_im[0][j] += ti;
+            psk::sr_lag(a[2], a[3], o[2], o[3], &tr, &ti);
+            rec->sum_re[1][j] += tr, rec->sum_im[1][j] += ti;
+            rec->n_pairs[j]++;
+        }
+        }
+        // (behind the lags: lag 128 reads the slot this block takes)
+        double *const b = B[m % psk::kSymrateHalo];
+        b[0] = a[0], b[1] = a[1], b[2] = a[2], b[3] = a[3];
+        valid[m % psk::kSymrateHalo] = ok;
+    }
+    rec->n_samples = n_complex;
+    rec->n_blocks = n_blocks;
+    rec->n_used = (uint64_t)n_blocks * S;
+    rec->samplesPerBaud = samplesPerBaud;
+    rec->flags = (uint8_t)(PSK_SOFT_SR_DATA | (tuned ? PSK_SOFT_SR_TUNED : 0));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_symrate_derive(const psk_soft_symrate_t *rec, psk_soft_symrate_derived_t *d)
+{
+    if (!rec || !d)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_symrate_derive: null pointer");
+    const double nan = std::nan(""), two_pi = 2.0 * 3.14159265358979323846;
+    *d = psk_soft_symrate_derived_t{};
+    d->samples_per_symbol = d->step_ratio = d->coherence = d->mean_level = nan;
+    d->detector = -1;
+    if (!(rec->flags & PSK_SOFT_SR_DATA) || !rec->n_pairs[0] || !rec->n_valid)
+        return PSK_SOFT_OK;
+    // c_j of detector z
+    auto coh = [&](int z, uint32_t j) {
+        return std::hypot(rec->sum_re[z][j], rec->sum_im[z][j]) / ((double)rec->n_pairs[j] * (rec->sum_pow[z] / (double)rec->n_valid));
+    };
+    double c0[2];
+    for (int z = 0; z < 2; z++) c0[z] = rec->sum_re[z][0] == 0.0 && rec->sum_im[z][0] == 0.0 ? 0.0 : coh(z, 0);
+    if (c0[0] == 0.0 && c0[1] == 0.0)
+        return PSK_SOFT_OK;
+    const int z = c0[1] > c0[0] ? 1 : 0;
+    double f = std::atan2(rec->sum_im[z][0], rec->sum_re[z][0]) / two_pi;
+    int32_t used = 1;
+    for (uint32_t j = 1; j < psk::kSymrateLags; j++) {
+        if (rec->n_pairs[j] < 8u || coh(z, j) < 0.5 * c0[z])
+            break;
+        const double L = (double)(1u << j);
+        double dd = std::atan2(rec->sum_im[z][j], rec->sum_re[z][j]) - two_pi * L * f;
+        dd -= two_pi * std::rint(dd / two_pi);
+        f += dd / (two_pi * L);
+        used++;
+    }
+    d->samples_per_symbol = (double)rec->samplesPerBaud / (1.0 + f);
+    d->step_ratio = 1.0 / (1.0 + f);
+    d->coherence = c0[z];
+    d->mean_level = rec->sum_lvl[z] / ((double)rec->n_valid * (double)rec->samplesPerBaud);
+    d->detector = z;
     d->lags_used = used;
     return PSK_SOFT_OK;
 }

@@ -51,6 +51,20 @@ inline void tune_rotate(const float *tab, uint64_t p, float xr, float xi, float 
     *yi = xr * wi + xi * wr;
 }
 
+// W(p) by itself, the (wr, wi) of tune_rotate: the phasor of a phase word for a pass that multiplies something other than a
+// sample by it (psk_symrate.h)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void tune_phasor(const float *tab, uint64_t p, float *wr, float *wi)
+{
+    const uint32_t top = (uint32_t)(p >> 44);
+    const float *const c = tab + 2u * (top >> 10), *const f = tab + 2u * (kTuneTable + (top & (kTuneTable - 1u)));
+    const float cr = c[0], ci = c[1], fr = f[0], fi = f[1];
+    *wr = cr * fr - ci * fi;
+    *wi = cr * fi + ci * fr;
+}
+
 // The grid rule of a pass whose grid is (descriptors, workgroups per descriptor): about 2048 workgroups in all (eight per CU),
 // none without a piece of the longest packet, which has `pieces` of them.
 inline uint32_t front_grid_y(uint64_t pieces, uint32_t n_desc)

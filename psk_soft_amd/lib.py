@@ -195,6 +195,41 @@ class AcquireDerived(ctypes.Structure):
     ]
 
 
+# Symrate.flags
+SR_DATA, SR_TUNED, SR_PLANNED = 1, 2, 128
+SYMRATE_LAGS = 8  # lags of 1, 2, 4 .. 128 blocks
+
+
+class Symrate(ctypes.Structure):
+    """psk_soft_symrate_t: the record of the last symrate_device call that covered a channel (detector 0: e, 1: g)."""
+
+    _fields_ = [
+        ("n_samples", ctypes.c_uint64),
+        ("n_used", ctypes.c_uint64),
+        ("n_blocks", ctypes.c_uint64),
+        ("n_valid", ctypes.c_uint64),
+        ("n_pairs", ctypes.c_uint64 * SYMRATE_LAGS),
+        ("sum_re", (ctypes.c_double * SYMRATE_LAGS) * 2),
+        ("sum_im", (ctypes.c_double * SYMRATE_LAGS) * 2),
+        ("sum_pow", ctypes.c_double * 2),
+        ("sum_lvl", ctypes.c_double * 2),
+        ("samplesPerBaud", ctypes.c_uint16),
+        ("flags", ctypes.c_uint8),
+        ("pad", ctypes.c_uint8 * 5),
+    ]
+
+
+class SymrateDerived(ctypes.Structure):
+    _fields_ = [
+        ("samples_per_symbol", ctypes.c_double),
+        ("step_ratio", ctypes.c_double),
+        ("coherence", ctypes.c_double),
+        ("mean_level", ctypes.c_double),
+        ("detector", ctypes.c_int32),
+        ("lags_used", ctypes.c_int32),
+    ]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_hip.h declares
@@ -247,6 +282,12 @@ EXPORTS = (
     "psk_soft_acquire_host",
     "psk_soft_acquire_bytes",
     "psk_soft_acquire_piece",
+    "psk_soft_symrate_device",
+    "psk_soft_get_symrate",
+    "psk_soft_symrate_derive",
+    "psk_soft_symrate_host",
+    "psk_soft_symrate_bytes",
+    "psk_soft_symrate_piece",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -364,6 +405,14 @@ def load():
     L.psk_soft_acquire_bytes.restype = u64
     L.psk_soft_acquire_piece.argtypes = []
     L.psk_soft_acquire_piece.restype = u32
+    L.psk_soft_symrate_device.argtypes = [vp, u32, u32, ctypes.POINTER(Packet), ctypes.POINTER(u64), ctypes.POINTER(Tune), vp]
+    L.psk_soft_get_symrate.argtypes = [vp, u32, u32, ctypes.POINTER(Symrate)]
+    L.psk_soft_symrate_derive.argtypes = [ctypes.POINTER(Symrate), ctypes.POINTER(SymrateDerived)]
+    L.psk_soft_symrate_host.argtypes = [ctypes.c_uint16, ctypes.POINTER(Tune), vp, u64, ctypes.POINTER(Symrate)]
+    L.psk_soft_symrate_bytes.argtypes = []
+    L.psk_soft_symrate_bytes.restype = u64
+    L.psk_soft_symrate_piece.argtypes = []
+    L.psk_soft_symrate_piece.restype = u32
     _lib = L
     return L
 
@@ -550,6 +599,30 @@ def acquire_host(M, iq, tune=None):
 def acquire_piece():
     """Samples of one piece of the device's fold (psk_soft_acquire_piece)."""
     return int(load().psk_soft_acquire_piece())
+
+
+def symrate_derive(rec):
+    """psk_soft_symrate_derive of one Symrate record: dict of samples_per_symbol, step_ratio, coherence, mean_level (NaN where
+    undefined), detector (0: e, 1: g, -1: none) and lags_used.  To bring the signal to samplesPerBaud samples a symbol:
+    resample step = resample_step(step_ratio)."""
+    d = SymrateDerived()
+    _check(load().psk_soft_symrate_derive(ctypes.byref(rec), ctypes.byref(d)))
+    return {k: getattr(d, k) for k, _ in SymrateDerived._fields_}
+
+
+def symrate_host(S, iq, tune=None):
+    """psk_soft_symrate_host: the Symrate record of interleaved float32 I/Q on the host (an odd last element is dropped) for
+    samplesPerBaud S.  tune: None or a (phase, step) pair."""
+    x = np.ascontiguousarray(iq, np.float32)
+    rec = Symrate()
+    t = Tune(int(tune[0]), int(tune[1])) if tune is not None else None
+    _check(load().psk_soft_symrate_host(int(S), ctypes.byref(t) if t is not None else None, x.ctypes.data, x.size // 2, ctypes.byref(rec)))
+    return rec
+
+
+def symrate_piece():
+    """Blocks of one piece of the device's fold (psk_soft_symrate_piece)."""
+    return int(load().psk_soft_symrate_piece())
 
 
 class Handle:
@@ -917,6 +990,29 @@ class Handle:
         """acquire_device, then one dict per covered channel: the derived values (acquire_derive) of its record."""
         self.acquire_device(ch0, pkts, strides, tunes, stream)
         return [acquire_derive(r) for r in self.acquire_records(ch0, len(pkts))]
+
+    def symrate_device(self, ch0, pkts, strides, tunes, stream=None):
+        """One look at a packet per channel (psk_soft_symrate_device): leaves a Symrate record per covered channel, emits
+        nothing and touches no demodulator state.  pkts, strides and tunes as for acquire_device."""
+        if strides is not None and not isinstance(strides, ctypes.Array):
+            strides = (ctypes.c_uint64 * len(strides))(*[int(s) for s in strides])
+        if tunes is not None and not isinstance(tunes, ctypes.Array):
+            tunes = (Tune * len(tunes))(*[Tune(int(p), int(s)) for p, s in tunes])
+        if (strides is not None and len(strides) != len(pkts)) or (tunes is not None and len(tunes) != len(pkts)):
+            raise ValueError("one stride and one tune per packet")
+        _check(self._L.psk_soft_symrate_device(self._h, ch0, len(pkts), pkts, strides, tunes, ctypes.c_void_p(stream or 0)))
+
+    def symrate_records(self, ch0=0, nch=None):
+        """The raw Symrate records of [ch0, ch0+nch) (psk_soft_get_symrate), a ctypes array."""
+        nch = self.n_channels - ch0 if nch is None else nch
+        arr = (Symrate * nch)()
+        _check(self._L.psk_soft_get_symrate(self._h, ch0, nch, arr))
+        return arr
+
+    def symrate(self, ch0, pkts, strides=None, tunes=None, stream=None):
+        """symrate_device, then one dict per covered channel: the derived values (symrate_derive) of its record."""
+        self.symrate_device(ch0, pkts, strides, tunes, stream)
+        return [symrate_derive(r) for r in self.symrate_records(ch0, len(pkts))]
 
     def export_state(self, ch):
         n = int(self._L.psk_soft_state_bytes(self._h))

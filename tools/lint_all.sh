@@ -44,6 +44,8 @@ others psk_resample
 others psk_fir
 # the far fit (PSK_SOFT_OPT_FAR_FIT, psk_farfit.hip): the fit stage and the quiet call with the fit window in device memory
 others psk_farfit
+# the symbol-rate pass of psk_soft_symrate_device (psk_symrate.hip): fold and join
+others psk_symrate
 echo "instantiations with D sites / with E sites (tools/isa_lane_loss.py):"; grep -c "no covering save) [1-9]" $out.lanes; grep -c "mask restore) [1-9]" $out.lanes
 grep -c . $out; grep -v "C (lane carrier moved under a partial mask) 0" $out | wc -l
 rmdir $tmp
