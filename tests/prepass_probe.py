@@ -1,13 +1,14 @@
 """The pre-pass kernels by themselves: ctypes binding of the test-only probe library (tests/support/prepass_probe.hip ->
-psk_soft_amd/libpsk_prepass_probe.so: a shim linked with the product's own psk_gather.o, psk_tune.o and psk_resample.o), the
-ARENA the kernels run in, the arena the models expect, and the comparator.
+psk_soft_amd/libpsk_prepass_probe.so: a shim linked with the product's own psk_gather.o, psk_tune.o, psk_resample.o and
+psk_fir.o), the ARENA the kernels run in, the arena the models expect, and the comparator.
 
 An arena is one byte image: sources, destination rows, history slots, and poison everywhere else.  The descriptors have the
-product's layout (psk_gather.h, psk_tune.h, psk_resample.h) with byte offsets into the arena where the product has pointers.  A
+product's layout (psk_gather.h, psk_tune.h, psk_resample.h, psk_fir.h) with byte offsets into the arena where the product has pointers.  A
 case below lays the arena out, fills the descriptors and computes the arena the launch must leave: a byte copy for the gathers,
-tune_model.apply for the tune kernel, tune_model.apply followed by resample_model.apply for the resample kernel.  Arena.compare
-holds the whole downloaded arena to it byte for byte: every row sample, both history slots, every source byte, the padding of
-every row up to its 128 bytes and every guard byte.
+tune_model.apply for the tune kernel, tune_model.apply followed by resample_model.apply for the resample kernel and by
+fir_model.apply for the filter kernel.  Arena.compare holds the whole downloaded arena to it byte for byte: every row sample,
+both history slots (and the padding of a slot behind its payload), every source byte -- the taps are one --, the padding of every
+row up to its 128 bytes and every guard byte.
 
 Everything is placed on a 128-byte line (plus the skew a case asks for: the least alignment of a packet) and followed by a
 guard of 128 bytes; the extents behind every descriptor are checked against the arena here, in front of every launch."""
@@ -16,6 +17,7 @@ import os
 
 import numpy as np
 
+from tests import fir_model as fm
 from tests import resample_model as rm
 from tests import tune_model as tm
 
@@ -30,7 +32,7 @@ SAMPLE_BYTES = {f: 2 * d.itemsize for f, d in DTYPE_OF.items()}
 # what lies in the other columns of a strided packet's matrix: a NaN for the float formats, the most negative integer
 POISON_OF = {FORMAT_CF32: np.uint32(0x7FC00ABC).view(np.float32), FORMAT_CS16: np.int16(-32768), FORMAT_CS8: np.int8(-128),
              FORMAT_CF16: np.uint16(0x7E55).view(np.float16)}
-RS_RESTART, RS_TUNED = 1, 2  # ResampleDesc::flags (psk_resample.h)
+RS_RESTART, RS_TUNED = 1, 2  # FrontIo::flags (psk_front_src.h): kFrontRestart, kFrontTuned
 LINE, GUARD = 128, 128
 GUARD_BYTE, ROW_BYTE = 0xA5, 0xC3
 REPORTED = 8  # findings a comparison lists at the most
@@ -42,8 +44,13 @@ SINGLE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8)])
 TUNE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("format", _U4), ("pad", _U4)])
 RESAMPLE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("format", _U4), ("flags", _U4),
                      ("pos", _U8), ("rstep", _U8), ("n_out", _U8), ("hist_in", _U8), ("hist_out", _U8)])
-MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE)  # in the order of psk_prepass_probe_sizeof
-CONSTANTS = ("resample_piece", "resample_inputs", "gather_tile", "gather_min_group", "tune_table_floats")
+# (psk_fir.h's static_assert pins these offsets: io 0, decim 56, pos 60, n_taps 64, pad 68, n_out 72, taps 80, hist_in 88, hist_out 96)
+FIR = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("format", _U4), ("flags", _U4),
+                ("decim", _U4), ("pos", _U4), ("n_taps", _U4), ("pad", _U4), ("n_out", _U8), ("taps", _U8), ("hist_in", _U8), ("hist_out", _U8)])
+MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE, FIR)  # in the order of psk_prepass_probe_sizeof
+CONSTANTS = ("resample_piece", "resample_inputs", "gather_tile", "gather_min_group", "tune_table_floats", "fir_window", "fir_max_taps",
+             "fir_hist_slot_floats")
+FIR_HIST_BYTES = 8 * fm.HIST  # the payload of a history slot of the filter: 127 float2
 
 
 # ---- the binding -----------------------------------------------------------------------------------------------------------------
@@ -63,7 +70,8 @@ def load():
                            ("psk_prepass_probe_gather_singles", [vp, u64, i, vp, u32, u64]),
                            ("psk_prepass_probe_gather_tiles", [vp, u64, i, vp, u32, vp, u32, u64]),
                            ("psk_prepass_probe_tune", [vp, u64, vp, u32, u64, vp]),
-                           ("psk_prepass_probe_resample", [vp, u64, vp, u32, u64])):
+                           ("psk_prepass_probe_resample", [vp, u64, vp, u32, u64]), ("psk_prepass_probe_fir_piece", [i]),
+                           ("psk_prepass_probe_fir", [vp, u64, vp, u32, u64])):
             getattr(L, name).argtypes, getattr(L, name).restype = args, i
         _lib = L
     return _lib
@@ -77,6 +85,11 @@ def sizeof(which):
 def constant(name):
     """a constant of the kernels' headers, by its name in CONSTANTS"""
     return int(load().psk_prepass_probe_constant(CONSTANTS.index(name)))
+
+
+def fir_piece(decim):
+    """fir_piece(decim) of psk_fir.h: the outputs of one piece of the filter pass at that decimation"""
+    return int(load().psk_prepass_probe_fir_piece(int(decim)))
 
 
 def _launch(what, fn, image, *args):
@@ -119,12 +132,45 @@ def length_for(n_out, step):
     raise AssertionError((n_out, step))
 
 
+# ---- launch_fir's grid rule, the kernel's walk and its lanes -----------------------------------------------------------------------
+
+def fir_grid(n_desc, max_pieces):
+    """Workgroups per packet, as front_grid_y (psk_front_src.h) has it for psk::launch_fir: min(pieces of the packet with the
+    most, ceil(2048 / n_desc)), at least 1, at most 65535.  2048 and the bounds are that function's literals."""
+    per = min(max_pieces, -(-2048 // n_desc))
+    return max(1, min(per, 65535))
+
+
+def fir_walk(n_out, per, piece):
+    """(the pieces each of the `per` workgroups of a packet takes, the workgroup that writes the history), as psk_fir_kernel and
+    fir_packet (psk_fir.hip) have it: piece p goes to workgroup p % per; the owner of the last piece, or workgroup 0 of a
+    packet without outputs, writes the history."""
+    n_pieces = -(-n_out // piece)
+    return [list(range(y, n_pieces, per)) for y in range(per)], ((n_pieces - 1) % per if n_pieces else 0)
+
+
+def fir_lanes(decim):
+    """(R, padded): the outputs a lane produces at that decimation -- 4 at D <= 3, 2 at D <= 7, else 1 -- and whether the LDS
+    window is padded, which it is where the lanes' stride R * D is even (fir_outputs_per_lane, fir_pad_shift: psk_fir.hip)"""
+    R = 4 if decim <= 3 else 2 if decim <= 7 else 1
+    return R, (R * decim) % 2 == 0
+
+
+def fir_split(decim, n_taps):
+    """(lead, head, mid, Q): fir_sums (psk_fir.hip) walks the steps [0, head) and [mid, Q) with a test per output and
+    [head, mid) without one; lead = (R-1) * D, Q = lead + T, head = min(lead + 1, Q), mid = max(T, head)"""
+    lead = (fir_lanes(decim)[0] - 1) * decim
+    Q = lead + n_taps
+    head = min(lead + 1, Q)
+    return lead, head, max(n_taps, head), Q
+
+
 # ---- the arena ---------------------------------------------------------------------------------------------------------------------
 
 class Region:
     """bytes [start, end) of the arena.  kind: "source" (never written), "row" (the samples a descriptor's kernel writes),
-    "padding" (the rest of the row's lines), "hist_in" (the slot read), "hist_out" (the slot written); desc: the descriptor it
-    belongs to; unit: bytes of one sample of it"""
+    "padding" (the rest of the row's lines), "hist_in" (the slot read), "hist_out" (the slot written), "hist_pad" (the bytes of
+    a history slot behind its payload: never written); desc: the descriptor it belongs to; unit: bytes of one sample of it"""
 
     def __init__(self, start, end, kind, desc, unit):
         self.start, self.end, self.kind, self.desc, self.unit = start, end, kind, desc, unit
@@ -163,15 +209,22 @@ class Arena:
         self.regions.append(Region(at + n * unit, at + cap, "padding", desc, unit))
         return at
 
-    def history(self, slot_in, values, desc):
-        """the two slots of a channel, 24 bytes each, back to back as the handle has them: slot `slot_in` holds `values`
-        (six floats), the other one poison.  (offset of the slot read, offset of the slot written)"""
-        pair = np.full(48, ROW_BYTE, np.uint8)
-        pair[24 * slot_in : 24 * slot_in + 24] = np.frombuffer(np.asarray(values, F32).tobytes(), np.uint8)
+    def history(self, slot_in, values, desc, slot_bytes=24, payload_bytes=24):
+        """the two slots of a channel, `slot_bytes` each, back to back as the handle has them: the first `payload_bytes` of slot
+        `slot_in` hold `values` (floats), everything else -- the other slot, and the padding of either slot behind its payload
+        -- poison.  The resampler's slots are 24 bytes and all payload, the filter's 1 KiB with 1016 bytes of payload.
+        (offset of the slot read, offset of the slot written)"""
+        data = np.frombuffer(np.asarray(values, F32).tobytes(), np.uint8)
+        assert data.size == payload_bytes <= slot_bytes and payload_bytes % 8 == 0
+        pair = np.full(2 * slot_bytes, ROW_BYTE, np.uint8)
+        pair[slot_bytes * slot_in : slot_bytes * slot_in + payload_bytes] = data
         at = self._place(pair)
-        a, b = at + 24 * slot_in, at + 24 * (slot_in ^ 1)
-        self.regions.append(Region(a, a + 24, "hist_in", desc, 8))
-        self.regions.append(Region(b, b + 24, "hist_out", desc, 8))
+        a, b = at + slot_bytes * slot_in, at + slot_bytes * (slot_in ^ 1)
+        self.regions.append(Region(a, a + payload_bytes, "hist_in", desc, 8))
+        self.regions.append(Region(b, b + payload_bytes, "hist_out", desc, 8))
+        if payload_bytes < slot_bytes:
+            for slot in (a, b):
+                self.regions.append(Region(slot + payload_bytes, slot + slot_bytes, "hist_pad", desc, 1))
         return a, b
 
     def image(self):
@@ -313,6 +366,58 @@ class ResampleCase(_Case):
 
     def run(self):
         return _launch("resample", load().psk_prepass_probe_resample, self.image, self.desc.ctypes.data, len(self.desc), self.max_n_out)
+
+
+class FirCase(_Case):
+    """One launch of the filter kernel.  packets: dicts of fmt, stride (the packet is column i % stride of its matrix), iq
+    (interleaved I/Q in the format's dtype), tune ((phase, step) or None), taps (1 .. 128 floats), D, pos (below D), restart,
+    hist (254 floats in the slot that is read, or None: the handle's zeros), slot (which of the two is read; default i % 2)."""
+
+    def __init__(self, packets):
+        super().__init__()
+        self.packets = packets
+        self.desc = np.zeros(len(packets), FIR)
+        self.rows, self.hists = [], []
+        slot_bytes = 4 * constant("fir_hist_slot_floats")
+        for i, p in enumerate(packets):
+            fmt, stride, sb = p["fmt"], p["stride"], SAMPLE_BYTES[p["fmt"]]
+            data, col_off = _strided(p["iq"], fmt, stride, i % stride)
+            n = np.asarray(p["iq"]).size // 2
+            x = np.ascontiguousarray(p["iq"], DTYPE_OF[fmt])[: 2 * n]
+            s = x.astype(F32) if p["tune"] is None else tm.apply(p["tune"][0], p["tune"][1], x)
+            taps = np.ascontiguousarray(p["taps"], F32).reshape(-1)
+            hist = np.zeros(2 * fm.HIST, F32) if p["hist"] is None else np.asarray(p["hist"], F32)
+            y, h_out = fm.apply(taps, p["D"], p["pos"], s, hist, p["restart"])
+            d = self.desc[i]
+            # (the least alignment of a packet, one sample, for every second contiguous one)
+            d["src"] = self.arena.source(data, i, sb, skew=sb if stride == 1 and i % 2 else 0) + col_off
+            d["taps"] = self.arena.source(taps, i, 4)
+            d["dst"] = self.arena.row(y.size // 2, 8, i)
+            d["hist_in"], d["hist_out"] = self.arena.history(p.get("slot", i % 2), hist, i, slot_bytes, FIR_HIST_BYTES)
+            d["stride"], d["n"], d["format"] = stride, n, fmt
+            d["flags"] = (RS_RESTART if p["restart"] else 0) | (RS_TUNED if p["tune"] is not None else 0)
+            if p["tune"] is not None:
+                d["phase"], d["step"] = p["tune"][0] & tm.MASK, p["tune"][1] & tm.MASK
+            d["decim"], d["pos"], d["n_taps"], d["n_out"] = p["D"], p["pos"], taps.size, y.size // 2
+            self._writes += [(int(d["dst"]), y), (int(d["hist_out"]), h_out)]
+            self.rows.append(y)
+            self.hists.append(h_out)
+        self.pieces = [-(-int(d["n_out"]) // fir_piece(int(d["decim"]))) for d in self.desc]
+        self.max_pieces = max(self.pieces)
+        self._finish()
+        a = self.arena
+        for d in self.desc:
+            D, T, pos, n, n_out = int(d["decim"]), int(d["n_taps"]), int(d["pos"]), int(d["n"]), int(d["n_out"])
+            self._extents(int(d["src"]), SAMPLE_BYTES[int(d["format"])], int(d["stride"]), n, int(d["dst"]), 8, n_out)
+            # (what the entry lets through: nothing is launched that the kernel's own guards would have to reject)
+            assert 1 <= D <= fm.MAX_DECIM and 1 <= T <= fm.MAX_TAPS == constant("fir_max_taps") and 0 <= pos < D, (D, T, pos)
+            assert n_out == fm.count(pos, D, n) and n < (1 << 30) and int(d["pad"]) == 0
+            assert int(d["taps"]) % 4 == 0 and a.inside("source", int(d["taps"]), 4 * T)
+            assert int(d["hist_in"]) % 8 == 0 and a.inside("hist_in", int(d["hist_in"]), FIR_HIST_BYTES)
+            assert int(d["hist_out"]) % 8 == 0 and a.inside("hist_out", int(d["hist_out"]), FIR_HIST_BYTES)
+
+    def run(self):
+        return _launch("fir", load().psk_prepass_probe_fir, self.image, self.desc.ctypes.data, len(self.desc), self.max_pieces)
 
 
 class TuneCase(_Case):

@@ -5,6 +5,7 @@ import functools
 
 import numpy as np
 
+from tests import fir_model as fm
 from tests import prepass_probe as pp
 from tests import resample_model as rm  # noqa: F401  (the tests reach the model through this module)
 from tests import tune_model as tm
@@ -225,3 +226,149 @@ TILE_MANY = 2100
 def tiles_many_case(sample_bytes):
     """2100 groups of 8 columns by 10 frames: 2100 tiles on a grid of 2048 workgroups, so `tl += gridDim.x` takes a second trip"""
     return pp.TilesCase(sample_bytes, [([10] * 8, k % 2, 1) for k in range(TILE_MANY)], 7500 + sample_bytes)
+
+
+# ---- fir -------------------------------------------------------------------------------------------------------------------------------
+
+FIR_DS = tuple(range(1, fm.MAX_DECIM + 1))
+
+
+def fir_taps(rng, T):
+    return (rng.standard_normal(T) / np.sqrt(T)).astype(F32)
+
+
+def fir_length(n_out, D, pos, extra=0):
+    """a packet length with exactly n_out >= 1 outputs at (D, pos): the last output's newest input, and up to D - 1 more"""
+    n = pos + (n_out - 1) * D + 1 + extra % D
+    assert fm.count(pos, D, n) == n_out
+    return n
+
+
+def _fir_packet(rng, k, D, pos, n, T, fmt=None, stride=None, tuned=None, restart=None):
+    """packet k of a launch: format, stride, tune, restart and the kind of history follow from k as in _packet"""
+    fmt = pp.FORMATS[k % 4] if fmt is None else fmt
+    stride = (1, 7)[(k // 4 + k) % 2] if stride is None else stride
+    tuned = (k // 2) % 3 != 1 if tuned is None else tuned
+    restart = k % 5 == 2 if restart is None else restart
+    hist = None if k % 3 == 0 else (rng.standard_normal(2 * fm.HIST) * 30.0).astype(F32)
+    tune = ((0x9E3779B97F4A7C15 * (k + 1)) % (1 << 64), TUNE_STEPS[(k // 3) % 4]) if tuned else None
+    return dict(fmt=fmt, stride=stride, iq=samples(rng, fmt, n), tune=tune, taps=fir_taps(rng, T), D=D, pos=pos, restart=restart, hist=hist)
+
+
+def fir_grid_taps(D):
+    """the tap counts of the grid at D: 1, 2, the three around the lead of the lane's first output, 64, 127, 128"""
+    lead = pp.fir_split(D, 1)[0]
+    return sorted({min(max(t, 1), fm.MAX_TAPS) for t in (1, 2, lead, lead + 1, lead + 2, 64, 127, 128)})
+
+
+def fir_grid_outputs(D):
+    P = pp.fir_piece(D)
+    return (1, 2, 3, 4, 5, P - 1, P, P + 1, 2 * P + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def fir_grid(D):
+    """One launch at the decimation D: fir_grid_taps(D) x fir_grid_outputs(D), pos walking every value below D"""
+    rng = np.random.default_rng(7600 + D)
+    out = []
+    for T in fir_grid_taps(D):
+        for n_out in fir_grid_outputs(D):
+            k = len(out)
+            pos = k % D
+            out.append(_fir_packet(rng, k, D, pos, fir_length(n_out, D, pos, k), T))
+    return pp.FirCase(out)
+
+
+FIR_SHAPES = (700, 1100, 2100)
+# the ten long packets of a shape: a D of each lane class and of both LDS layouts, and tap counts of every part of the walk
+FIR_LONG_DS = (1, 4, 9, 16, 3, 7, 15, 8, 2, 12)
+FIR_LONG_TAPS = (128, 2, 64, 127, 10, 1, 33, 128, 5, 64)
+FIR_JOIN_LENGTHS = (1, 2, 126, 127, 128)  # the join of the old history and a packet shorter than it
+
+
+@functools.lru_cache(maxsize=None)
+def fir_shape(packets):
+    """A launch of `packets` packets, D mixed by index over 1 .. 16.  Ten are long, spread over the launch: their outputs are
+    _long_outputs(P)[packets] at the P of their own D.  The others have 1 .. 40 samples, or one of FIR_JOIN_LENGTHS; every 50th
+    has pos >= n: no output, and a history that still moves."""
+    rng = np.random.default_rng(7700 + packets)
+    at = {(j * packets) // 10 + 3: j for j in range(10)}
+    out = []
+    for k in range(packets):
+        if k in at:
+            j = at[k]
+            D = FIR_LONG_DS[j]
+            pos = (j * 5) % D
+            n_out = _long_outputs(pp.fir_piece(D))[packets][2][j]
+            out.append(_fir_packet(rng, j, D, pos, fir_length(n_out, D, pos, j), FIR_LONG_TAPS[j]))
+            continue
+        T = 1 + (k * 29) % fm.MAX_TAPS
+        if k % 50 == 10:  # no output, but the history moves
+            D = 2 + (k // 50) % 15
+            pos = D - 1
+            out.append(_fir_packet(rng, k, D, pos, 1 + (k // 50) % pos, T))
+        else:
+            D = 1 + (k * 7 + k // 16) % 16
+            n = FIR_JOIN_LENGTHS[(k // 20) % 5] if k % 20 == 1 else 1 + (k * 13) % 40
+            out.append(_fir_packet(rng, k, D, (k * 3 + k // 16) % D, n, T))
+    return pp.FirCase(out)
+
+
+FIR_EDGE_DS = (3, 5, 9)  # one D of each lane class: R = 4, 2 and 1
+FIR_SUBNORMAL = np.uint32(0x00000011).view(F32)
+# (None: an ordinary tap)
+FIR_SPECIAL_TAPS = (FIR_SUBNORMAL, F32(0.0), F32(-0.0), None, -FIR_SUBNORMAL)
+
+
+@functools.lru_cache(maxsize=None)
+def fir_edges():
+    """(the case, {name: descriptors of that kind}), every kind at each D of FIR_EDGE_DS with T = 1 among its tap counts.
+    tiny: float32 samples (and history) scaled by 2^-130 under taps of 0.5 .. 1.5 in magnitude: every product is subnormal.
+    subtaps: taps that are subnormal (0x00000011, either sign), +0 and -0 between ordinary ones, each of them as tap 0.
+    zeros: samples that are zeros of both signs (alone, and between small integers) under negative taps.
+    huge: samples up to 2^125 / T under taps of at most 1 in magnitude: no sum overflows."""
+    rng = np.random.default_rng(7800)
+    out, kinds = [], {}
+
+    def add(kind, p):
+        kinds.setdefault(kind, []).append(len(out))
+        out.append(p)
+
+    for a, D in enumerate(FIR_EDGE_DS):
+        for b, T in enumerate((1, 7, 40)):
+            k = len(out)
+            p = _fir_packet(rng, k, D, k % D, 150 + 7 * k, T, fmt=pp.FORMAT_CF32, stride=(1, 7)[(a + b) % 2], tuned=(a + b) % 3 == 2, restart=b == 1 and a != 1)
+            p["iq"] = samples(rng, pp.FORMAT_CF32, 150 + 7 * k, TINY)
+            p["hist"] = samples(rng, pp.FORMAT_CF32, fm.HIST, TINY)
+            p["taps"] = (rng.uniform(0.5, 1.5, T) * rng.choice((-1.0, 1.0), T)).astype(F32)
+            add("tiny", p)
+        for v in range(3):  # (tap 0 is the subnormal, +0, -0)
+            k = len(out)
+            T = (1, 6, 19)[(a + v) % 3]
+            p = _fir_packet(rng, k, D, k % D, 90 + 11 * k, T, tuned=v == 1)
+            for i in range(T):
+                if FIR_SPECIAL_TAPS[(i + v) % 5] is not None:
+                    p["taps"][i] = FIR_SPECIAL_TAPS[(i + v) % 5]
+            add("subtaps", p)
+        for b, T in enumerate((1, 3)):
+            k = len(out)
+            fmt = (pp.FORMAT_CF32, pp.FORMAT_CF16)[(a + b) % 2]
+            p = _fir_packet(rng, k, D, k % D, 120 + 5 * k, T, fmt=fmt, stride=(1, 7)[b], tuned=False, restart=b == 0)
+            z = np.where(rng.integers(0, 2, p["iq"].size) == 1, -0.0, 0.0)
+            if (a + b) % 2:  # zeros of both signs between samples that are not zero
+                z = np.where(rng.integers(0, 3, z.size) == 0, rng.integers(-9, 10, z.size).astype(np.float64), z)
+            p["iq"] = z.astype(pp.DTYPE_OF[fmt])
+            p["hist"] = np.where(rng.integers(0, 2, 2 * fm.HIST) == 1, -0.0, 0.0).astype(F32)
+            p["taps"] = (-rng.uniform(0.25, 1.0, T)).astype(F32)
+            add("zeros", p)
+        for b, T in enumerate((1, 16, 128)):
+            k = len(out)
+            tuned = (a + b) % 3 == 0
+            top = HUGE / T * (0.5 if tuned else 1.0)  # (a tuned sample grows by sqrt(2) at the most)
+            p = _fir_packet(rng, k, D, k % D, 300 + 9 * k, T, fmt=pp.FORMAT_CF32, stride=1, tuned=tuned, restart=True)
+            p["iq"] = (rng.uniform(-1.0, 1.0, p["iq"].size) * top).astype(F32)
+            p["iq"][:4] = F32(top) * np.array([1, -1, -1, 1], F32)
+            p["taps"] = rng.uniform(-1.0, 1.0, T).astype(F32)
+            p["taps"][0] = 1.0
+            add("huge", p)
+    return pp.FirCase(out), kinds

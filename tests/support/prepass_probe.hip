@@ -1,9 +1,9 @@
-// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip) launched by
+// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip, psk_fir.hip) launched by
 // themselves, so that tests can hold every byte they write -- each row sample, both history slots -- and every byte they must
 // not write to the models, bit for bit (tests/prepass_probe.py, tests/test_gpu_prepass_probe.py).
 //
-// This file holds no kernel.  It is linked with the product's own objects psk_gather.o, psk_tune.o and psk_resample.o as the
-// product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
+// This file holds no kernel.  It is linked with the product's own objects psk_gather.o, psk_tune.o, psk_resample.o and psk_fir.o as
+// the product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
 // the product's.  Nothing of it is linked into the product library.
 //
 // One C entry per kernel.  The caller passes one host ARENA -- sources, destination rows, histories, poison everywhere else --
@@ -17,6 +17,7 @@
 
 #include <vector>
 
+#include "psk_fir.h"
 #include "psk_gather.h"
 #include "psk_resample.h"
 #include "psk_tune.h"
@@ -81,7 +82,7 @@ bool point(P &field, const char *d_arena, uint64_t bytes)
 
 extern "C" {
 
-// 0 GatherGroup, 1 GatherChan, 2 GatherSingle, 3 TuneDesc, 4 ResampleDesc
+// 0 GatherGroup, 1 GatherChan, 2 GatherSingle, 3 TuneDesc, 4 ResampleDesc, 5 FirDesc
 int psk_prepass_probe_sizeof(int which)
 {
     switch (which) {
@@ -90,11 +91,13 @@ int psk_prepass_probe_sizeof(int which)
     case 2: return (int)sizeof(GatherSingle);
     case 3: return (int)sizeof(TuneDesc);
     case 4: return (int)sizeof(ResampleDesc);
+    case 5: return (int)sizeof(FirDesc);
     default: return -1;
     }
 }
 
-// 0 kResamplePiece, 1 kResampleInputs, 2 kGatherTile, 3 kGatherMinGroup, 4 kTuneTableFloats
+// 0 kResamplePiece, 1 kResampleInputs, 2 kGatherTile, 3 kGatherMinGroup, 4 kTuneTableFloats, 5 kFirWindow, 6 kFirMaxTaps,
+// 7 kFirHistSlotFloats
 int psk_prepass_probe_constant(int which)
 {
     switch (which) {
@@ -103,8 +106,17 @@ int psk_prepass_probe_constant(int which)
     case 2: return (int)kGatherTile;
     case 3: return (int)kGatherMinGroup;
     case 4: return (int)kTuneTableFloats;
+    case 5: return (int)kFirWindow;
+    case 6: return (int)kFirMaxTaps;
+    case 7: return (int)kFirHistSlotFloats;
     default: return -1;
     }
+}
+
+// fir_piece(decim): outputs of one piece of the filter pass at that decimation; -1 outside 1 .. kFirMaxDecim
+int psk_prepass_probe_fir_piece(int decim)
+{
+    return decim >= 1 && decim <= (int)kFirMaxDecim ? (int)fir_piece((uint32_t)decim) : -1;
 }
 
 int psk_prepass_probe_gather_singles(void *arena, uint64_t bytes, int sample_bytes, const void *desc, uint32_t n_desc, uint64_t max_n)
@@ -177,6 +189,24 @@ int psk_prepass_probe_resample(void *arena, uint64_t bytes, const void *desc, ui
     if (!r.descriptors(0, d.data(), sizeof(ResampleDesc) * d.size()) || !r.tables())
         return r.end(hipSuccess, arena, 0, nullptr);
     return r.end(launch_resample((const ResampleDesc *)r.d_desc[0], n_desc, max_n_out, r.d_tab, r.stream), arena, bytes, nullptr);
+}
+
+// max_pieces: the most pieces (of fir_piece(decim) outputs) any packet of the launch has
+int psk_prepass_probe_fir(void *arena, uint64_t bytes, const void *desc, uint32_t n_desc, uint64_t max_pieces)
+{
+    if (!arena || !bytes || !desc || !n_desc)
+        return (int)hipErrorInvalidValue;
+    std::vector<FirDesc> d((const FirDesc *)desc, (const FirDesc *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (FirDesc &t : d)
+        if (!point(t.io.src, r.d_arena, bytes) || !point(t.io.dst, r.d_arena, bytes) || !point(t.taps, r.d_arena, bytes) ||
+            !point(t.hist_in, r.d_arena, bytes) || !point(t.hist_out, r.d_arena, bytes))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(FirDesc) * d.size()) || !r.tables())
+        return r.end(hipSuccess, arena, 0, nullptr);
+    return r.end(launch_fir((const FirDesc *)r.d_desc[0], n_desc, max_pieces, r.d_tab, r.stream), arena, bytes, nullptr);
 }
 
 }  // extern "C"

@@ -239,7 +239,7 @@ NEG = (1 << 63) + 12345
 
 # ---- 1. every format, every place a packet can lie, tuned or not, the edges of a piece -------------------------------------------------
 
-@pytest.mark.parametrize("D", [1, 2, 3, 16])
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 7, 9, 15, 16])
 @pytest.mark.parametrize("dt", DT, ids=["cf32", "cs16", "cs8", "cf16"])
 def test_formats_places_and_piece_edges(dt, D):
     """ten kinds of length -- n_out = P-1, P, P+1, 2P-1, 2P, 2P+1 (P = psk_soft_fir_piece(D)), one sample, T-1 samples, a

@@ -1,9 +1,10 @@
-"""The gather, tune and resample kernels by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim linked
-with the product's own psk_gather.o, psk_tune.o and psk_resample.o).  The demodulator behind these kernels shows one row sample
+"""The gather, tune, resample and filter kernels by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim
+linked with the product's own psk_gather.o, psk_tune.o, psk_resample.o and psk_fir.o).  The demodulator behind these kernels shows one row sample
 in eight at samplesPerBaud 8; here every byte of the arena a launch ran in is compared with the arena
 the models expect -- a byte copy for the gathers, tests/tune_model.py for the tune kernel, tests/tune_model.py followed by
-tests/resample_model.py for the resample kernel: every row sample and both history slots bit for bit, no tolerance, and every
-source byte, every byte of row padding and every guard byte unchanged.  The inputs hold finite samples only.
+tests/resample_model.py for the resample kernel, tests/tune_model.py followed by tests/fir_model.py for the filter kernel: every
+row sample and both history slots bit for bit, no tolerance, and every source byte (the taps among them), every byte of row
+padding, the padding of the filter's history slots and every guard byte unchanged.  The inputs hold finite samples only.
 
 The inputs come from tests/prepass_probe_cases.py; tests/test_prepass_probe.py asserts, without a GPU, the launch shapes and the
 edges each of them reaches, and that the comparator reports a wrong store at its place."""
@@ -44,6 +45,33 @@ def test_resample_arithmetic_edges():
     """every step with the pos fractions 0, 255, 256 and 2^32 - 1; pos 2^33; samples scaled by 2^-130 (a flush to zero anywhere
     would show) and up to 2^125; zeros of both signs at step 2^32, pos 0"""
     case, kinds = pc.resample_edges()
+    _clean(case, case.run(), "arithmetic edges %s" % {k: (v[0], v[-1]) for k, v in kinds.items()})
+
+
+# ---- fir -------------------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("D", pc.FIR_DS)
+def test_fir_every_decimation(D):
+    """one launch at D: tap counts 1, 2, lead, lead + 1, lead + 2 (the edges of the three-way split of the tap walk), 64, 127,
+    128 x outputs 1 .. 5, P-1, P, P+1, 2P+1 (every tail of a lane's R outputs, both sides of a piece edge), every pos below D,
+    the four formats, strides 1 and 7, tuned and not, restart, a preset history and zeros; every piece has its own workgroup"""
+    case = pc.fir_grid(D)
+    _clean(case, case.run(), "D = %d, %d packets" % (D, len(case.desc)))
+
+
+@pytest.mark.parametrize("packets", pc.FIR_SHAPES)
+def test_fir_workgroups_that_walk_several_pieces(packets):
+    """700 packets: three workgroups a packet take pieces (0,3,6), (1,4,7), (2,5) of the longest; 1100: two, the history's owner
+    workgroup 0 for some packets and 1 for others; 2100: one workgroup walks every piece, then writes the history.  D is mixed
+    over 1 .. 16 within a launch; all but ten packets are short, every 50th has pos >= n: no output, and its history moves."""
+    case = pc.fir_shape(packets)
+    _clean(case, case.run(), "%d filtered packets" % packets)
+
+
+def test_fir_arithmetic_edges():
+    """at a D of each lane class: float32 samples scaled by 2^-130 under taps near 1 (every product subnormal); subnormal, +0 and
+    -0 taps, each as tap 0; zeros of both signs under negative taps; samples up to 2^125 / T"""
+    case, kinds = pc.fir_edges()
     _clean(case, case.run(), "arithmetic edges %s" % {k: (v[0], v[-1]) for k, v in kinds.items()})
 
 

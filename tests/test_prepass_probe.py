@@ -4,11 +4,16 @@ First the comparator, the way tests/test_row_guards.py validates its module: a n
 a clean fill is reported clean, and each of five injected faults -- the stores a wrong pre-pass kernel would make -- is reported
 at its place.  Then the inputs of tests/test_gpu_prepass_probe.py: every launch shape, piece edge and arithmetic edge those
 tests are there for is asserted to be in them, against restatements of the launch functions' grid rules; nothing about the
-inputs is left to chance.  The descriptors' mirrors are held to the sizeof the probe library exports."""
+inputs is left to chance.  The descriptors' mirrors are held to the sizeof the probe library exports.
+
+The filter kernel (psk_fir.hip) follows in the same order at the end of the file: the mirror and the constants, the comparator on
+a FirCase with eight injected faults, what the grid, the three launch shapes and the arithmetic edges reach, and fir_model.apply
+held to the rounding bound of a float64 convolution."""
 import numpy as np
 import pytest
 
 from psk_soft_amd import lib as pl
+from tests import fir_model as fm
 from tests import prepass_probe as pp
 from tests import prepass_probe_cases as pc
 from tests import resample_model as rm
@@ -344,3 +349,386 @@ def test_gather_cases():
         assert len(m.groups) == 2100 and (m.groups["g"] == 8).all() and (m.chans["n"] == 10).all()
         assert m.n_tiles == 2100 > 2048, "more tiles than launch_gather_tiles gives workgroups: a second trip of tl += gridDim.x"
         assert [int(t) for t in m.groups["tile0"][:3]] == [0, 1, 2]
+
+
+# ---- fir: the mirror, the comparator ------------------------------------------------------------------------------------------------------
+
+def test_the_fir_mirror_and_constants():
+    assert pp.MIRRORS[5] is pp.FIR and pp.FIR.itemsize == 104 == pp.sizeof(5)
+    assert [pp.FIR.fields[f][1] for f in ("src", "decim", "pos", "n_taps", "pad", "n_out", "taps", "hist_in", "hist_out")] == [0, 56, 60, 64, 68, 72, 80, 88, 96]
+    assert pp.constant("fir_window") == fm.WINDOW and pp.constant("fir_max_taps") == fm.MAX_TAPS
+    assert 4 * pp.constant("fir_hist_slot_floats") == 1024 == pp.FIR_HIST_BYTES + 8
+    for D in pc.FIR_DS:
+        assert pp.fir_piece(D) == fm.piece(D) == pl.fir_piece(D) and pp.fir_piece(D) % 2 == 0
+    assert (pp.fir_piece(1), pp.fir_piece(16), pp.fir_piece(0), pp.fir_piece(17)) == (3968, 248, -1, -1)
+    assert [pp.fir_lanes(D)[0] for D in pc.FIR_DS] == [4] * 3 + [2] * 4 + [1] * 9
+    assert [D for D in pc.FIR_DS if not pp.fir_lanes(D)[1]] == [9, 11, 13, 15], "the unpadded layout"
+
+
+@pytest.fixture(scope="module")
+def fir_small():
+    """six packets: the four formats, strides 1 and 7, tuned and not, restart and histories, a D of each lane class and of both
+    layouts, odd and even n_out, one packet without output"""
+    rng = np.random.default_rng(12)
+    spec = [(3, 1, 50, 10), (5, 0, 50, 7), (9, 2, 100, 128), (4, 3, 2, 5), (16, 5, 215, 2), (1, 0, 33, 1)]
+    return pp.FirCase([pc._fir_packet(rng, k, D, pos, n, T) for k, (D, pos, n, T) in enumerate(spec)])
+
+
+def _fir_ext(p):
+    """(history in front ‖ the samples the filter sees) of a packet, float32 complex, as (127 + n, 2)"""
+    s = _tuned(p)
+    hist = np.zeros(2 * fm.HIST, F32) if p["restart"] or p["hist"] is None else np.asarray(p["hist"], F32)
+    return np.concatenate([hist, s[: 2 * (s.size // 2)]]).reshape(-1, 2)
+
+
+def test_fir_a_correct_writer_is_clean(fir_small):
+    c = fir_small
+    assert [int(n) for n in c.desc["n_out"]] == [17, 10, 11, 0, 14, 33]
+    assert [int(n) for n in c.desc["n_out"]] == [fm.count(p["pos"], p["D"], p["iq"].size // 2) for p in c.packets]
+    assert {int(f) for f in c.desc["format"]} == set(pp.FORMATS) and {int(s) for s in c.desc["stride"]} == {1, 7}
+    assert {int(f) & 2 for f in c.desc["flags"]} == {0, 2} and {int(f) & 1 for f in c.desc["flags"]} == {0, 1}
+    assert c.check(_written(c)) == []
+    assert c.check(c.image) != [], "an arena nothing was written to is not clean"
+    assert all(np.array_equal(h, _fir_ext(p)[-fm.HIST:].reshape(-1)) for h, p in zip(c.hists, c.packets))
+
+
+def test_fir_one_ulp_in_one_output(fir_small):
+    after = _written(fir_small)
+    d = fir_small.desc[4]
+    k = int(d["n_out"]) - 3
+    after[int(d["dst"]) + 8 * k + 4] ^= 1  # (the lowest mantissa bit of the imaginary part)
+    f = _one(fir_small, after)
+    assert (f["desc"], f["where"], f["sample"], f["n_bytes"]) == (4, "row", k, 1), f
+    assert "descriptor 4 row" in f["message"] and "sample %d" % k in f["message"]
+
+
+def test_fir_an_output_summed_in_descending_tap_order(fir_small):
+    after = _written(fir_small)
+    i, m = 2, 6
+    p, d = fir_small.packets[i], fir_small.desc[i]
+    h, ext, T = np.asarray(p["taps"], F32), _fir_ext(p), int(d["n_taps"])
+    at = p["pos"] + m * p["D"] + fm.HIST
+    up = (h[0] * ext[at]).astype(F32)
+    for j in range(1, T):
+        up = (up + (h[j] * ext[at - j]).astype(F32)).astype(F32)
+    assert up.tobytes() == fir_small.rows[i][2 * m : 2 * m + 2].tobytes(), "the ascending sum is the model's"
+    down = (h[T - 1] * ext[at - (T - 1)]).astype(F32)
+    for j in range(T - 2, -1, -1):
+        down = (down + (h[j] * ext[at - j]).astype(F32)).astype(F32)
+    assert T == 128 and down.tobytes() != up.tobytes() and np.allclose(down, up, rtol=1e-4, atol=1e-3)
+    after[int(d["dst"]) + 8 * m : int(d["dst"]) + 8 * m + 8] = np.frombuffer(down.tobytes(), np.uint8)
+    f = _one(fir_small, after)
+    assert (f["desc"], f["where"], f["sample"]) == (i, "row", m), f
+    assert f["want"] == up.tobytes().hex() and f["got"] == down.tobytes().hex()
+
+
+def test_fir_the_odd_last_output_stored_as_sixteen_bytes(fir_small):
+    after = _written(fir_small)
+    for i in (0, 2, 5):  # (a D of each lane class)
+        d = fir_small.desc[i]
+        assert int(d["n_out"]) % 2 == 1
+        last = int(d["dst"]) + 8 * (int(d["n_out"]) - 1)
+        assert (last + 8) % pp.LINE != 0
+        after[last + 8 : last + 16] = after[last : last + 8]
+    found = fir_small.check(after)
+    assert [(f["desc"], f["where"], f["sample"], f["n_bytes"]) for f in found] == [(i, "padding", 0, 8) for i in (0, 2, 5)], pp.messages(found)
+    assert all(f["want"] == "c3" * 8 for f in found)
+
+
+def test_fir_a_history_shifted_by_one_sample(fir_small):
+    after = _written(fir_small)
+    for i in (1, 3):  # (3 is the packet without output: two samples joined to the old history)
+        d, p = fir_small.desc[i], fir_small.packets[i]
+        ext = _fir_ext(p)
+        off = int(d["hist_out"])
+        after[off : off + pp.FIR_HIST_BYTES] = np.frombuffer(ext[-fm.HIST - 1 : -1].tobytes(), np.uint8)
+    found = fir_small.check(after)
+    assert [(f["desc"], f["where"]) for f in found] == [(1, "hist_out"), (3, "hist_out")], pp.messages(found)
+    assert found[0]["sample"] <= 1 and found[0]["n_bytes"] > 900
+
+
+def test_fir_a_history_written_to_the_slot_that_was_read(fir_small):
+    after = _written(fir_small)
+    H = pp.FIR_HIST_BYTES
+    for i in (2, 3):  # (either order of the two slots)
+        d = fir_small.desc[i]
+        h = after[int(d["hist_out"]) : int(d["hist_out"]) + H].copy()
+        after[int(d["hist_out"]) : int(d["hist_out"]) + H] = pp.ROW_BYTE
+        after[int(d["hist_in"]) : int(d["hist_in"]) + H] = h
+    found = fir_small.check(after)
+    assert sorted((f["desc"], f["where"]) for f in found) == [(2, "hist_in"), (2, "hist_out"), (3, "hist_in"), (3, "hist_out")], pp.messages(found)
+    assert fir_small.desc[2]["hist_in"] < fir_small.desc[2]["hist_out"] and fir_small.desc[3]["hist_in"] > fir_small.desc[3]["hist_out"]
+    assert abs(int(fir_small.desc[2]["hist_in"]) - int(fir_small.desc[2]["hist_out"])) == 1024
+
+
+def test_fir_a_changed_pad_byte_of_a_history_slot(fir_small):
+    for i, slot in ((0, "hist_out"), (1, "hist_in")):  # (lane 127 storing a 128th sample; the same behind the slot that is read)
+        after = _written(fir_small)
+        off = int(fir_small.desc[i][slot]) + pp.FIR_HIST_BYTES + 3
+        assert fir_small.image[off] == pp.ROW_BYTE
+        after[off] = 0
+        f = _one(fir_small, after)
+        assert (f["desc"], f["where"], f["sample"], f["offset"], f["want"], f["got"]) == (i, "hist_pad", 3, off, "c3", "00"), f
+
+
+def test_fir_a_changed_tap_and_a_changed_guard_byte(fir_small):
+    after = _written(fir_small)
+    d = fir_small.desc[0]
+    off = int(d["taps"]) + 4 * 9
+    after[off] ^= 0x01
+    f = _one(fir_small, after)
+    assert (f["desc"], f["where"], f["sample"], f["offset"], f["n_bytes"]) == (0, "source", 9, off, 1), f
+    after = _written(fir_small)
+    behind = max(int(d["hist_in"]), int(d["hist_out"])) + 1024
+    after[behind + 2] = 0
+    f = _one(fir_small, after)
+    assert (f["desc"], f["where"], f["offset"]) == (0, "guard", behind + 2), f
+    assert "2 byte(s) behind the hist_pad of descriptor 0" in f["message"]
+    after = _written(fir_small)
+    after[int(d["taps"]) + 4 * int(d["n_taps"])] = 0  # (the byte behind the last tap)
+    assert _one(fir_small, after)["where"] == "guard"
+
+
+# ---- fir: what the grid reaches -------------------------------------------------------------------------------------------------------------
+
+def _fir_mixes(case):
+    """every format at both strides, tuned (every step of TUNE_STEPS) and untuned, restart and a carried history (preset and
+    the handle's zeros), either order of the two slots"""
+    d = case.desc
+    assert {(int(f), int(s)) for f, s in zip(d["format"], d["stride"])} == {(f, s) for f in pp.FORMATS for s in (1, 7)}
+    assert {int(f) for f in d["flags"]} == {0, 1, 2, 3}
+    assert {int(s) for s, f in zip(d["step"], d["flags"]) if int(f) & 2} == {s & tm.MASK for s in pc.TUNE_STEPS}
+    kept = [p for p in case.packets if not p["restart"]]
+    assert any(p["hist"] is None for p in kept) and any(p["hist"] is not None for p in kept)
+    assert any(p["hist"] is not None for p in case.packets if p["restart"]), "a preset history that must not show"
+    assert {int(a > b) for a, b in zip(d["hist_in"], d["hist_out"])} == {0, 1}
+
+
+def test_fir_grid_reaches_every_decimation_tap_edge_and_tail():
+    assert pc.FIR_DS == tuple(range(1, 17))
+    for D in pc.FIR_DS:
+        c = pc.fir_grid(D)
+        d = c.desc
+        P = pp.fir_piece(D)
+        R, padded = pp.fir_lanes(D)
+        lead = (R - 1) * D
+        assert (d["decim"] == D).all() and len(d) <= 80
+        # every piece has a workgroup of its own
+        assert c.max_pieces == 3 and pp.fir_grid(len(d), c.max_pieces) == 3
+        assert pp.fir_walk(2 * P + 1, 3, P) == ([[0], [1], [2]], 2)
+        taps = sorted({int(t) for t in d["n_taps"]})
+        assert taps == pc.fir_grid_taps(D) and {1, 2, 64, 127, 128} <= set(taps)
+        for T in taps:
+            mine = d[d["n_taps"] == T]
+            assert sorted(int(n) for n in mine["n_out"]) == sorted(pc.fir_grid_outputs(D)), (D, T)
+        assert set(pc.fir_grid_outputs(D)) == {1, 2, 3, 4, 5, P - 1, P, P + 1, 2 * P + 1}
+        counts = {min(P, int(n) - m0) for n in d["n_out"] for m0 in range(0, int(n), P)}  # (cnt_out of every piece)
+        assert counts == {1, 2, 3, 4, 5, P - 1, P} and {n % R for n in counts} == set(range(R)), "every tail of a lane's R outputs"
+        assert {int(p) for p in d["pos"]} == set(range(D))
+        splits = {T: pp.fir_split(D, T) for T in taps}
+        assert all(s[0] == lead and s[1] == lead + 1 and s[3] == lead + T for T, s in splits.items())
+        if lead > 0:
+            assert {lead, lead + 1, lead + 2} <= set(taps)
+            # T below, at and above head; the loop without tests [head, mid) with zero trips (T = lead, lead + 1), one, many
+            assert {(T > s[1]) - (T < s[1]) for T, s in splits.items()} == {-1, 0, 1}
+            assert [splits[T][2] - splits[T][1] for T in (1, lead, lead + 1, lead + 2)] == [0, 0, 0, 1]
+            assert splits[128][2] - splits[128][1] == 127 - lead > 4
+        else:
+            assert R == 1 and lead == 0 and [splits[T][2] - splits[T][1] for T in (1, 2, 128)] == [0, 1, 127]
+        assert padded == (D not in (9, 11, 13, 15))
+        _fir_mixes(c)
+
+
+def _fir_walks(case):
+    per = pp.fir_grid(len(case.desc), case.max_pieces)
+    return per, [pp.fir_walk(int(d["n_out"]), per, pp.fir_piece(int(d["decim"]))) for d in case.desc]
+
+
+def _fir_long(case):
+    return [i for i in range(len(case.desc)) if int(case.desc["n"][i]) > 128]
+
+
+def _fir_short_ones(case):
+    d = case.desc
+    long_ = _fir_long(case)
+    assert len(long_) == 10, "all but ten packets are short"
+    short = np.delete(d, long_)
+    lens = {int(n) for n in short["n"]}
+    assert lens <= set(range(1, 41)) | set(pc.FIR_JOIN_LENGTHS), "1 .. 40 samples, or the join of an old history and a shorter packet"
+    assert lens >= set(pc.FIR_JOIN_LENGTHS) | {3, 39, 40} and len(lens) >= 40
+    assert {int(D) for D in short["decim"]} == set(pc.FIR_DS)
+    quiet = [i for i in range(len(d)) if i % 50 == 10 and i not in long_]
+    assert len(quiet) >= len(d) // 50 - 1
+    for i in quiet:
+        assert int(d["pos"][i]) >= int(d["n"][i]) and int(d["n_out"][i]) == 0 and case.pieces[i] == 0
+        p = case.packets[i]
+        before = np.zeros(2 * fm.HIST, F32) if p["restart"] or p["hist"] is None else np.asarray(p["hist"], F32)
+        assert case.hists[i].tobytes() != before.tobytes(), "no output, and a history that still moves"
+    assert {int(d["n"][i]) for i in quiet} >= {1, 2, 3}
+
+
+def _fir_long_cover(case):
+    d = case.desc[_fir_long(case)]
+    assert [int(D) for D in d["decim"]] == list(pc.FIR_LONG_DS)
+    assert {pp.fir_lanes(int(D))[0] for D in d["decim"]} == {4, 2, 1}, "a D of each lane class"
+    assert {D for D in pc.FIR_LONG_DS if not pp.fir_lanes(D)[1]} == {9, 15} and {D for D in pc.FIR_LONG_DS if D >= 8 and pp.fir_lanes(D)[1]} == {8, 12, 16}
+    assert {int(f) for f in d["format"]} == set(pp.FORMATS) and {int(s) for s in d["stride"]} == {1, 7}
+    assert {int(f) & 2 for f in d["flags"]} == {0, 2}
+    assert {int(n) % 2 for n in d["n_out"]} == {0, 1}
+
+
+def test_fir_shape_700_packets():
+    c = pc.fir_shape(700)
+    per, walks = _fir_walks(c)
+    assert len(c.desc) == 700 and c.max_pieces == 8 and per == 3
+    long_ = _fir_long(c)
+    P = pp.fir_piece(int(c.desc["decim"][long_[0]]))
+    assert int(c.desc["n_out"][long_[0]]) == 7 * P + 1
+    assert walks[long_[0]] == ([[0, 3, 6], [1, 4, 7], [2, 5]], 1), "three workgroups; two of them take three pieces, one writes the history"
+    assert {walks[i][1] for i in long_} == {0, 1, 2}, "the history's owner is each of the workgroups for some packet"
+    assert all(w == ([[0], [], []], 0) or w == ([[], [], []], 0) for i, w in enumerate(walks) if i not in long_)
+    _fir_mixes(c)
+    _fir_short_ones(c)
+    _fir_long_cover(c)
+
+
+def test_fir_shape_1100_packets():
+    c = pc.fir_shape(1100)
+    per, walks = _fir_walks(c)
+    assert len(c.desc) == 1100 and c.max_pieces == 6 and per == 2
+    long_ = _fir_long(c)
+    assert [c.pieces[i] for i in long_] == [3, 3, 5, 6, 6, 6, 5, 3, 3, 2]
+    assert [walks[i][1] for i in long_] == [0, 0, 0, 1, 1, 1, 0, 0, 0, 1], "the owner is not always the highest-numbered workgroup"
+    assert walks[long_[4]] == ([[0, 2, 4], [1, 3, 5]], 1) and walks[long_[2]] == ([[0, 2, 4], [1, 3]], 0)
+    _fir_mixes(c)
+    _fir_short_ones(c)
+    _fir_long_cover(c)
+
+
+def test_fir_shape_2100_packets():
+    c = pc.fir_shape(2100)
+    per, walks = _fir_walks(c)
+    assert len(c.desc) == 2100 and c.max_pieces == 4 and per == 1
+    long_ = _fir_long(c)
+    assert walks[long_[0]] == ([[0, 1, 2, 3]], 0), "one workgroup walks every piece, then writes the history"
+    assert sorted({c.pieces[i] for i in long_}) == [1, 2, 3, 4]
+    _fir_mixes(c)
+    _fir_short_ones(c)
+    _fir_long_cover(c)
+
+
+def _fir_cases():
+    return [pc.fir_grid(D) for D in pc.FIR_DS] + [pc.fir_shape(n) for n in pc.FIR_SHAPES] + [pc.fir_edges()[0]]
+
+
+def test_fir_every_input_and_model_row_is_finite():
+    for c in _fir_cases():
+        assert all(np.isfinite(y).all() for y in c.rows) and all(np.isfinite(h).all() for h in c.hists)
+        for p in c.packets:
+            assert np.isfinite(np.asarray(p["iq"], np.float64)).all() and np.isfinite(p["taps"]).all()
+            assert p["hist"] is None or np.isfinite(p["hist"]).all()
+        assert c.image.size < 48 << 20
+
+
+# ---- fir: the arithmetic edges ------------------------------------------------------------------------------------------------------------
+
+def test_fir_edges_reach_each_lane_class_with_one_tap_among_the_counts():
+    case, kinds = pc.fir_edges()
+    d = case.desc
+    assert set(kinds) == {"tiny", "subtaps", "zeros", "huge"} and 24 <= len(d) <= 48 and case.max_pieces == 1
+    assert [pp.fir_lanes(D)[0] for D in pc.FIR_EDGE_DS] == [4, 2, 1]
+    for kind, idx in kinds.items():
+        for D in pc.FIR_EDGE_DS:
+            mine = [i for i in idx if int(d["decim"][i]) == D]
+            assert 1 in {int(d["n_taps"][i]) for i in mine} and len({int(d["n_taps"][i]) for i in mine}) >= 2, (kind, D)
+
+
+def test_fir_edges_every_product_of_the_scaled_packets_is_subnormal():
+    case, kinds = pc.fir_edges()
+    for i in kinds["tiny"]:
+        p, d = case.packets[i], case.desc[i]
+        assert d["format"] == pp.FORMAT_CF32
+        h = np.asarray(p["taps"], np.float64)
+        assert (np.abs(h) >= 0.5).all() and (np.abs(h) <= 1.5).all()
+        ext = _fir_ext(p).astype(np.float64)
+        at = p["pos"] + np.arange(int(d["n_out"])) * p["D"] + fm.HIST
+        prods = np.stack([h[j] * ext[at - j] for j in range(h.size)])
+        assert np.abs(prods).max() < SUBNORMAL
+        if not p["restart"]:
+            assert np.count_nonzero(prods) > 0.95 * prods.size
+        if p["tune"] is not None:  # (the products of the rotation as well)
+            assert np.abs(np.asarray(p["iq"], np.float64)).max() * 1.000001 < SUBNORMAL
+        y = case.rows[i]
+        assert np.abs(y).max() < 64 * SUBNORMAL and np.count_nonzero(y) > 0.95 * y.size, "the model keeps its denormals"
+        assert np.count_nonzero(case.hists[i]) > 0.95 * case.hists[i].size
+    assert {bool(case.packets[i]["tune"]) for i in kinds["tiny"]} == {False, True}
+    assert {bool(case.packets[i]["restart"]) for i in kinds["tiny"]} == {False, True}
+
+
+def test_fir_edges_subnormal_and_zero_taps_signed_zeros_and_large_samples():
+    case, kinds = pc.fir_edges()
+    sub = pc.FIR_SUBNORMAL
+    assert sub.view(np.uint32) == 0x11 and 0 < float(sub) < SUBNORMAL
+    first = set()
+    for i in kinds["subtaps"]:
+        h = np.asarray(case.packets[i]["taps"], F32)
+        first.add((int(case.desc["decim"][i]), int(h[:1].view(np.uint32)[0])))
+        if h.size >= 5:
+            assert {0x11, 0x0, 0x80000000, 0x80000011} <= {int(b) for b in h.view(np.uint32)} and (np.abs(h) > 1e-3).any()
+        y = case.rows[i]
+        if h.size == 1:  # (a product with the subnormal tap is subnormal; with a zero it is a zero of the product's sign)
+            assert (np.count_nonzero(y) > 0.9 * y.size and np.abs(y).max() < SUBNORMAL) if h[0] != 0 else {bool(b) for b in np.signbit(y)} == {False, True}
+        else:
+            assert np.count_nonzero(y) > 0.9 * y.size
+    assert first == {(D, b) for D in pc.FIR_EDGE_DS for b in (0x11, 0x0, 0x80000000)}, "each of them as tap 0, at every D"
+    seen = set()
+    for i in kinds["zeros"]:
+        p, d = case.packets[i], case.desc[i]
+        x = np.asarray(p["iq"], F32)
+        assert (np.asarray(p["taps"]) < 0).all() and int(d["flags"]) & 2 == 0
+        assert {bool(b) for b in np.signbit(x[x == 0])} == {False, True}
+        seen.add((int(d["format"]), bool((x != 0).any()), int(d["n_taps"])))
+        y = case.rows[i]
+        assert {bool(b) for b in np.signbit(y[y == 0])} == {False, True}
+        if int(d["n_taps"]) == 1:
+            # h[0] * s keeps the sign of the product; an addition to +0 in the first step would lose it
+            s0 = _fir_ext(p)[p["pos"] + np.arange(int(d["n_out"])) * p["D"] + fm.HIST].reshape(-1)
+            assert np.array_equal(np.signbit(y), ~np.signbit(s0)) and (np.signbit(y) & (y == 0)).any()
+            assert not np.signbit((F32(0.0) + y)[y == 0]).any()
+    assert {s[0] for s in seen} == {pp.FORMAT_CF32, pp.FORMAT_CF16} and {s[1] for s in seen} == {False, True} and {s[2] for s in seen} == {1, 3}
+    for i in kinds["huge"]:
+        p, T = case.packets[i], int(case.desc["n_taps"][i])
+        top = pc.HUGE / T * (0.5 if p["tune"] is not None else 1.0)
+        assert np.abs(p["iq"]).max() == F32(top) and np.abs(p["taps"]).max() == 1.0
+        assert np.isfinite(case.rows[i]).all() and np.abs(case.rows[i]).max() > top / 4
+    assert {bool(case.packets[i]["tune"]) for i in kinds["huge"]} == {False, True}
+    assert max(np.abs(case.rows[i]).max() for i in kinds["huge"]) > 2.0 ** 123
+
+
+# ---- fir: a second reference -----------------------------------------------------------------------------------------------------------------
+
+def test_fir_model_lies_within_the_rounding_bound_of_a_float64_convolution():
+    """over the grid's untuned float32 packets: |y - y64| <= gamma_T * sum_j |h[j]| |s[i-j]|, gamma_T = T u / (1 - T u), u = 2^-24
+    -- T products and T - 1 additions, each rounded once.  (The packets scaled by 2^-130 are not among these: underflow adds
+    an absolute term.)"""
+    u = 2.0 ** -24
+    seen, tightest = 0, 0.0
+    for D in pc.FIR_DS:
+        c = pc.fir_grid(D)
+        for i, p in enumerate(c.packets):
+            if p["fmt"] != pp.FORMAT_CF32 or p["tune"] is not None:
+                continue
+            h = np.asarray(p["taps"], np.float64)
+            T, n_out = h.size, int(c.desc["n_out"][i])
+            ext = _fir_ext(p).astype(np.float64)
+            at = p["pos"] + np.arange(n_out) * D + fm.HIST
+            win = ext[at[:, None] - np.arange(T)[None, :]]  # (n_out, T, 2)
+            y64 = np.einsum("j,mjq->mq", h, win)
+            mag = np.einsum("j,mjq->mq", np.abs(h), np.abs(win))
+            err = np.abs(c.rows[i].astype(np.float64).reshape(-1, 2) - y64)
+            gamma = T * u / (1.0 - T * u)
+            # (y64 itself is off by gamma_T(2^-53) * mag at the most: 2^-29 of the bound)
+            assert (err <= gamma * mag * (1.0 + 2.0 ** -20)).all(), (D, i, T, float((err / np.maximum(mag, 1e-300)).max()), gamma)
+            tightest = max(tightest, float((err / np.maximum(gamma * mag, 1e-300)).max()))
+            seen += 1
+    assert seen >= 4 * len(pc.FIR_DS) and 0.0 < tightest <= 1.0
