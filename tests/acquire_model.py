@@ -7,6 +7,7 @@ n * 2^-53 * sum|t_i| of the exact sum of its n float32 terms t_i -- the textbook
 that was off by one float rounding (6e-8 relative) would miss that bound by orders of magnitude.  Tuned samples come from
 tests/tune_model.py."""
 import math
+import struct
 
 import numpy as np
 
@@ -82,6 +83,122 @@ def model_record(iq, M, tune=None):
         sums["sum_im"].append(_sum_and_bound(t_im))
     rec["sums"] = sums
     return rec
+
+
+# ---- the device's order of additions (psk_soft_amd/csrc/psk_acquire.hip), restated: bytes, not bounds -----------------------------
+#
+#   a piece     4096 samples.  Lag sums (stage 2): lane t of 256 adds the float32 products of the samples t, t + 256, ... of the
+#               piece as doubles from +0.0 (a pair that does not enter adds a zero); each wave of 64 lanes by the xor tree
+#               32, .., 1; then the four waves in order.  Energy (stage 1): lane t takes the sample pairs start + 2t, + 512, ...
+#               (start: 128 samples in front of the piece, or 0 in the first piece), adds e of the first then of the second
+#               sample, only of valid samples of the piece itself; the same tree, the same order of waves.
+#   the packet  lane l of 64 adds the partials l, l + 64, ... from +0.0, then the xor tree.
+#
+# The per-sample and per-lag float32 terms are sample_terms' and lag_terms' arithmetic; model_record above stays the judge of this
+# restatement (tests/test_prepass_probe.py holds device_record to it under assert_record on every packet the probe uses).
+
+PIECE, HALO, THREADS = 4096, 128, 256
+RECORD_BYTES, PARTIAL_SUMS, PARTIAL_COUNTS = 224, 17, 9
+F64 = np.float64
+
+
+def _tree64(a):
+    """the xor tree 32, .., 1 over the last axis (64 lanes): lane 0's value"""
+    idx = np.arange(64)
+    off = 32
+    while off >= 1:
+        a = a + a[..., idx ^ off]
+        off >>= 1
+    return a[..., 0]
+
+
+def _in_turn(t):
+    """t: (..., turns, lanes): every lane adds its terms in turn order from +0.0"""
+    acc = np.zeros(t.shape[:-2] + t.shape[-1:], F64)
+    for i in range(t.shape[-2]):
+        acc = acc + t[..., i, :]
+    return acc
+
+
+def _waves(lanes):
+    """lanes: (..., 256): each wave by the tree, the four waves in order"""
+    w = _tree64(lanes.reshape(lanes.shape[:-1] + (THREADS // 64, 64)))
+    p = w[..., 0]
+    for k in range(1, THREADS // 64):
+        p = p + w[..., k]
+    return p
+
+
+def _converted(iq, tune):
+    n = np.asarray(iq).size // 2
+    tuned = tune is not None and (int(tune[0]) | int(tune[1])) != 0
+    return (tm.apply(tune[0], tune[1], iq) if tuned else np.asarray(iq)[: 2 * n].astype(F32)), tuned
+
+
+def device_partials(iq, M, tune=None):
+    """[(d: 17 float64 -- sum_re[8], sum_im[8], sum_e --, c: 9 int64 -- n_pairs[8], n_valid)] per piece of the packet, as the fold
+    kernel leaves them in its AcquirePartial; [] for no packet"""
+    n = 0 if iq is None else np.asarray(iq).size // 2
+    if n == 0 or M not in (2, 4, 8):
+        return []
+    t = sample_terms(_converted(iq, tune)[0], M)
+    ur, ui, valid = t["ur"], t["ui"], t["valid"]
+    with np.errstate(all="ignore"):
+        e = np.where(valid, t["e"], F32(0)).astype(F64)
+    lag = np.zeros((16, n), F64)
+    hit = np.zeros((8, n), bool)
+    for j, L in enumerate(LAGS):
+        if n <= L:
+            continue
+        ok = valid[L:] & valid[:-L]
+        t_re = (_mul(ur[L:], ur[:-L]) + _mul(ui[L:], ui[:-L])).astype(F32)
+        t_im = (_mul(ui[L:], ur[:-L]) - _mul(ur[L:], ui[:-L])).astype(F32)
+        lag[j, L:] = np.where(ok, t_re, F32(0))
+        lag[8 + j, L:] = np.where(ok, t_im, F32(0))
+        # (the device counts the products that are not (0, 0); an invalid sample's phasor is (0, 0))
+        hit[j, L:] = ok & ((t_re != 0) | (t_im != 0))
+    out = []
+    for lo in range(0, n, PIECE):
+        hi = min(lo + PIECE, n)
+        turns = -(-(hi - lo) // THREADS)
+        end = lo + turns * THREADS
+        seg = np.zeros((16, end - lo), F64)
+        seg[:, : hi - lo] = lag[:, lo:hi]
+        d = np.empty(PARTIAL_SUMS, F64)
+        d[:16] = _waves(_in_turn(seg.reshape(16, turns, THREADS)))
+        start = lo - HALO if lo else 0
+        trips = -(-(end - start) // (2 * THREADS))
+        es = np.zeros(trips * 2 * THREADS, F64)
+        es[lo - start : hi - start] = e[lo:hi]
+        es = es.reshape(trips, THREADS, 2)  # (trip, lane, first / second sample of the lane's pair)
+        d[16] = _waves(_in_turn(es.transpose(0, 2, 1).reshape(2 * trips, THREADS)))
+        c = np.array([int(hit[j, lo:hi].sum()) for j in range(8)] + [int(valid[lo:hi].sum())], np.int64)
+        out.append((d, c))
+    return out
+
+
+def partial_bytes(p):
+    """the 172 bytes of an AcquirePartial in front of its pad"""
+    d, c = p
+    return np.asarray(d, "<f8").tobytes() + np.asarray(c, "<u4").tobytes()
+
+
+def join_bytes(parts, n, M, tuned):
+    """the record the join makes of a packet's partials: 224 bytes"""
+    k = len(parts)
+    t = np.zeros((PARTIAL_SUMS, -(-k // 64) * 64), F64)
+    t[:, :k] = np.stack([d for d, _ in parts], axis=1)
+    s = _tree64(_in_turn(t.reshape(PARTIAL_SUMS, -1, 64)))
+    c = sum(c for _, c in parts)
+    return struct.pack("<2Q8Q17dHB5x", n, int(c[8]), *[int(v) for v in c[:8]], *[float(v) for v in s], M, A_DATA | (A_TUNED if tuned else 0))
+
+
+def device_record(iq, M, tune=None):
+    """the 224 bytes of the device's record of a packet; the zero record for no packet"""
+    parts = device_partials(iq, M, tune)
+    if not parts:
+        return bytes(RECORD_BYTES)
+    return join_bytes(parts, np.asarray(iq).size // 2, M, tune is not None and (int(tune[0]) | int(tune[1])) != 0)
 
 
 def assert_record(r, model, ctx=""):

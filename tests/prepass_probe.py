@@ -11,14 +11,23 @@ both history slots (and the padding of a slot behind its payload), every source 
 row up to its 128 bytes and every guard byte.
 
 Everything is placed on a 128-byte line (plus the skew a case asks for: the least alignment of a packet) and followed by a
-guard of 128 bytes; the extents behind every descriptor are checked against the arena here, in front of every launch."""
+guard of 128 bytes; the extents behind every descriptor are checked against the arena here, in front of every launch.
+
+The two looks (psk_symrate.hip, psk_acquire.hip; the shim links psk_symrate.o and psk_acquire.o too) run in an arena as well: a
+LookCase at the end of this file lays out the sources, a region of partials and a region of records -- memory the handle
+allocates in the product, which tests/row_guards.py cannot fence --, launches fold and join once each, and expects the bytes
+of symrate_model.partials / join_bytes and acquire_model.device_partials / join_bytes: every partial, every record, and poison
+in every partial's pad, in every slot no descriptor owns and in the guards."""
 import ctypes
+import math
 import os
 
 import numpy as np
 
+from tests import acquire_model as am
 from tests import fir_model as fm
 from tests import resample_model as rm
+from tests import symrate_model as sm
 from tests import tune_model as tm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,9 +56,24 @@ RESAMPLE = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("
 # (psk_fir.h's static_assert pins these offsets: io 0, decim 56, pos 60, n_taps 64, pad 68, n_out 72, taps 80, hist_in 88, hist_out 96)
 FIR = np.dtype([("src", _U8), ("dst", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("format", _U4), ("flags", _U4),
                 ("decim", _U4), ("pos", _U4), ("n_taps", _U4), ("pad", _U4), ("n_out", _U8), ("taps", _U8), ("hist_in", _U8), ("hist_out", _U8)])
-MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE, FIR)  # in the order of psk_prepass_probe_sizeof
+# the two looks (psk_symrate.h, psk_acquire.h; the records: include/psk_soft_hip.h)
+_F8, _U2, _U1 = "<f8", "<u2", "u1"
+SYMRATE_DESC = np.dtype([("src", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("wstep", _U8), ("n_blocks", _U4), ("part0", _U4),
+                         ("n_piece", _U4), ("channel", _U4), ("S", _U2), ("format", _U1), ("flags", _U1), ("tail", _U4)])
+SYMRATE_PART = np.dtype([("d", _F8, 36), ("c", _U4, 9), ("pad", _U4)])
+ACQUIRE_DESC = np.dtype([("src", _U8), ("stride", _U8), ("n", _U8), ("phase", _U8), ("step", _U8), ("part0", _U4), ("n_piece", _U4), ("channel", _U4),
+                         ("M", _U2), ("format", _U1), ("flags", _U1)])
+ACQUIRE_PART = np.dtype([("d", _F8, 17), ("c", _U4, 9), ("pad", _U4)])
+SYMRATE_REC = np.dtype([("n_samples", _U8), ("n_used", _U8), ("n_blocks", _U8), ("n_valid", _U8), ("n_pairs", _U8, 8), ("sum_re", _F8, (2, 8)),
+                        ("sum_im", _F8, (2, 8)), ("sum_pow", _F8, 2), ("sum_lvl", _F8, 2), ("samplesPerBaud", _U2), ("flags", _U1), ("pad", _U1, 5)])
+ACQUIRE_REC = np.dtype([("n_samples", _U8), ("n_valid", _U8), ("n_pairs", _U8, 8), ("sum_re", _F8, 8), ("sum_im", _F8, 8), ("sum_e", _F8),
+                        ("constelationSize", _U2), ("flags", _U1), ("pad", _U1, 5)])
+# in the order of psk_prepass_probe_sizeof
+MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE, FIR, SYMRATE_DESC, SYMRATE_PART, ACQUIRE_DESC, ACQUIRE_PART, SYMRATE_REC, ACQUIRE_REC)
 CONSTANTS = ("resample_piece", "resample_inputs", "gather_tile", "gather_min_group", "tune_table_floats", "fir_window", "fir_max_taps",
-             "fir_hist_slot_floats")
+             "fir_hist_slot_floats", "symrate_piece", "symrate_halo", "symrate_threads", "symrate_min_s", "symrate_max_s", "symrate_max_blocks",
+             "acquire_piece", "acquire_halo", "acquire_threads")
+LOOK_DATA, LOOK_TUNED = 1, 2  # PSK_SOFT_SR_DATA / PSK_SOFT_A_DATA, PSK_SOFT_SR_TUNED / PSK_SOFT_A_TUNED
 FIR_HIST_BYTES = 8 * fm.HIST  # the payload of a history slot of the filter: 127 float2
 
 
@@ -71,7 +95,9 @@ def load():
                            ("psk_prepass_probe_gather_tiles", [vp, u64, i, vp, u32, vp, u32, u64]),
                            ("psk_prepass_probe_tune", [vp, u64, vp, u32, u64, vp]),
                            ("psk_prepass_probe_resample", [vp, u64, vp, u32, u64]), ("psk_prepass_probe_fir_piece", [i]),
-                           ("psk_prepass_probe_fir", [vp, u64, vp, u32, u64])):
+                           ("psk_prepass_probe_fir", [vp, u64, vp, u32, u64]),
+                           ("psk_prepass_probe_symrate", [vp, u64, vp, u32, u32, u64, u64]),
+                           ("psk_prepass_probe_acquire", [vp, u64, vp, u32, u32, u64, u64, i])):
             getattr(L, name).argtypes, getattr(L, name).restype = args, i
         _lib = L
     return _lib
@@ -512,3 +538,177 @@ class TilesCase(_Case):
     def run(self):
         return _launch("gather_tiles", load().psk_prepass_probe_gather_tiles, self.image, self.sample_bytes, self.groups.ctypes.data,
                        len(self.groups), self.chans.ctypes.data, len(self.chans), self.n_tiles)
+
+
+# ---- the two looks: fold and join, their partials and their records ----------------------------------------------------------------
+
+LOOK_GRID_MAX = 65535  # packets a grid of launch_*_fold / launch_*_join covers in one trip (their literal)
+
+
+def look_trips(n_desc):
+    """trips of the packet loop `c += gridDim` of both folds and both joins: one up to 65535 descriptors"""
+    return -(-n_desc // LOOK_GRID_MAX)
+
+
+def _coprime(n, near):
+    """a multiplier coprime to n, at or above `near`: i -> i * a % n is a permutation of range(n)"""
+    a = max(1, near)
+    while math.gcd(a, n) != 1:
+        a += 1
+    return a
+
+
+class LookCase(_Case):
+    """One launch of a look's fold and one of its join.  kind: "symrate" or "acquire".  protos: the distinct packets -- dicts of
+    fmt, stride (the packet is column `col` of its matrix), iq (interleaved I/Q in the format's dtype), tune ((phase, step) or
+    None), S (symrate) or M (acquire), skew (bytes in front of a contiguous packet: its least alignment); their models run once.
+    uses: one (proto, data) per descriptor -- a descriptor without `data` has everything but its DATA flag and its source: the
+    join gives it the zero record, the fold must leave its partials alone.
+
+    The layout gives a wrong store something to hit: the descriptors take their partials in another order than their own (i ->
+    i * a % n), with a slot nobody owns behind every `spare_every`-th; `channel` is a permutation with slots no descriptor names;
+    the partials' pads, the unowned slots and a guard of 128 bytes behind each region are poison that has to come back."""
+
+    def __init__(self, kind, protos, uses, spare_every=3, tables=True):
+        super().__init__()
+        self.kind, self.protos, self.uses, self.tables = kind, protos, uses, tables
+        sym = kind == "symrate"
+        self.desc_dt, self.part_dt, self.rec_dt = (SYMRATE_DESC, SYMRATE_PART, SYMRATE_REC) if sym else (ACQUIRE_DESC, ACQUIRE_PART, ACQUIRE_REC)
+        self.piece = sm.PIECE if sym else am.PIECE
+        psize, rsize, body = self.part_dt.itemsize, self.rec_dt.itemsize, self.part_dt.fields["pad"][1]
+        a = self.arena
+        for k, p in enumerate(protos):
+            fmt, sb = p["fmt"], SAMPLE_BYTES[p["fmt"]]
+            x = np.ascontiguousarray(p["iq"], DTYPE_OF[fmt])
+            p["n"] = n = x.size // 2
+            data, col_off = _strided(x, fmt, p["stride"], k % p["stride"])
+            p["src"] = a.source(data, k, sb, skew=p.get("skew", 0) if p["stride"] == 1 else 0) + col_off
+            tuned = p["tune"] is not None and (int(p["tune"][0]) | int(p["tune"][1])) != 0
+            if sym:
+                p["parts"] = sm.partials(x, p["S"], p["tune"])
+                p["units"] = sm.n_blocks_of(n, p["S"])
+                assert p["parts"], "a packet the look does not take"
+                p["record"] = sm.join_bytes(p["parts"], n, p["S"], tuned)
+            else:
+                p["parts"] = am.device_partials(x, p["M"], p["tune"])
+                p["units"] = n
+                p["record"] = am.join_bytes(p["parts"], n, p["M"], tuned)
+            p["flags"] = LOOK_DATA | (LOOK_TUNED if tuned else 0)
+            p["part_bytes"] = [(sm if sym else am).partial_bytes(q) for q in p["parts"]]
+            assert len(p["parts"]) == -(-p["units"] // self.piece) and len(p["record"]) == rsize and len(p["part_bytes"][0]) == body
+        n = len(uses)
+        self.desc = np.zeros(n, self.desc_dt)
+        # the partials: descriptor order[0] takes the first slots, order[1] the next ..; a spare slot behind every spare_every-th
+        mul = _coprime(n, int(0.618 * n))
+        order = [(i * mul + n // 2) % n for i in range(n)]
+        part0, spare, at = [0] * n, [], 0
+        for j, i in enumerate(order):
+            part0[i] = at
+            at += len(protos[uses[i][0]]["parts"])
+            if j % spare_every == spare_every - 1:
+                spare.append(at)
+                at += 1
+        self.n_slots = at
+        self.n_rec = n + max(2, n // 16)
+        cmul = _coprime(self.n_rec, int(0.382 * self.n_rec))
+        channel = [(i * cmul + 1) % self.n_rec for i in range(n)]
+        self.part_off = a._place(np.full(self.n_slots * psize, ROW_BYTE, np.uint8))
+        self.rec_off = a._place(np.full(self.n_rec * rsize, ROW_BYTE, np.uint8))
+        R, zero = a.regions, bytes(rsize)
+        for i, (k, data) in enumerate(uses):
+            p = protos[k]
+            for q in range(len(p["parts"])):
+                o = self.part_off + (part0[i] + q) * psize
+                if data:
+                    R.append(Region(o, o + body, "partial", i, 4))
+                    R.append(Region(o + body, o + psize, "partial_pad", i, 4))
+                    self._writes.append((o, p["part_bytes"][q]))
+                else:
+                    R.append(Region(o, o + psize, "spare_partial", i, 4))
+            o = self.rec_off + channel[i] * rsize
+            R.append(Region(o, o + rsize, "record", i, 8))
+            self._writes.append((o, p["record"] if data else zero))
+        for sl in spare:
+            R.append(Region(self.part_off + sl * psize, self.part_off + (sl + 1) * psize, "spare_partial", None, 4))
+        for ch in sorted(set(range(self.n_rec)) - set(channel)):
+            R.append(Region(self.rec_off + ch * rsize, self.rec_off + (ch + 1) * rsize, "spare_record", None, 8))
+        d = self.desc
+        pk = [protos[k] for k, _ in uses]
+        d["src"] = [p["src"] if data else 0 for p, (_, data) in zip(pk, uses)]
+        d["stride"], d["n"] = [p["stride"] for p in pk], [p["n"] for p in pk]
+        d["phase"] = [p["tune"][0] & tm.MASK if p["flags"] & LOOK_TUNED else 0 for p in pk]
+        d["step"] = [p["tune"][1] & tm.MASK if p["flags"] & LOOK_TUNED else 0 for p in pk]
+        d["part0"], d["n_piece"], d["channel"] = part0, [len(p["parts"]) for p in pk], channel
+        d["format"] = [p["fmt"] for p in pk]
+        d["flags"] = [p["flags"] if data else p["flags"] & ~LOOK_DATA for p, (_, data) in zip(pk, uses)]
+        if sym:
+            d["S"], d["n_blocks"] = [p["S"] for p in pk], [p["units"] for p in pk]
+            d["wstep"] = [(1 << 64) // p["S"] for p in pk]  # (sr_wstep: floor(2^64 / S))
+        else:
+            d["M"] = [p["M"] for p in pk]
+        self.part0, self.channel, self.spare = part0, channel, spare
+        self.max_piece = max(len(protos[k]["parts"]) for k, data in uses if data)
+        self._finish()
+        self._check_extents()
+
+    def _check_extents(self):
+        """what the two kernels may touch behind every descriptor lies where the arena has it"""
+        a, d, sym = self.arena, self.desc, self.kind == "symrate"
+        psize, rsize = self.part_dt.itemsize, self.rec_dt.itemsize
+        assert self.part_off % 8 == 0 and self.rec_off % 8 == 0 and a.size < (1 << 31)
+        assert len(set(self.channel)) == len(self.channel) and max(self.channel) < self.n_rec
+        ends = np.asarray(d["part0"], np.int64) + np.asarray(d["n_piece"], np.int64)
+        assert int(ends.max()) <= self.n_slots and int(d["n_piece"].min()) >= 1
+        taken = np.zeros(self.n_slots, np.int32)
+        for lo, hi in zip(d["part0"], ends):
+            taken[lo:hi] += 1
+        assert taken.max() == 1 and not taken[self.spare].any()
+        assert a.inside("spare_partial", self.part_off + self.spare[0] * psize, psize) if self.spare else True
+        seen = {}
+        for i, (k, data) in enumerate(self.uses):
+            if not data:
+                assert int(d["src"][i]) == 0 and not int(d["flags"][i]) & LOOK_DATA
+                continue
+            p = self.protos[k]
+            assert int(d["flags"][i]) & LOOK_DATA and (self.tables or not int(d["flags"][i]) & LOOK_TUNED)
+            if k in seen:
+                continue
+            seen[k] = i
+            sb, stride, n = SAMPLE_BYTES[p["fmt"]], p["stride"], p["n"]
+            used = int(d["n_blocks"][i]) * int(d["S"][i]) if sym else n
+            assert 1 <= used <= n and stride >= 1 and int(d["n_piece"][i]) == -(-p["units"] // self.piece)
+            if sym:
+                assert sm.MIN_S <= int(d["S"][i]) <= sm.MAX_S and 2 <= int(d["n_blocks"][i]) <= sm.MAX_BLOCKS
+            else:
+                assert int(d["M"][i]) in (2, 4, 8)
+            src = int(d["src"][i])
+            assert src % sb == 0 and a.inside("source", src, sb) and a.inside("source", src + (used - 1) * stride * sb, sb), (i, src, used)
+            assert a.inside("partial", self.part_off + int(d["part0"][i]) * psize, psize - 4)
+            assert a.inside("record", self.rec_off + int(d["channel"][i]) * rsize, rsize)
+
+    def field(self, f):
+        """the field of the partial or of the record a finding's first byte lies in"""
+        if f["where"] in ("partial", "partial_pad", "spare_partial"):
+            dt, at = self.part_dt, (f["offset"] - self.part_off) % self.part_dt.itemsize
+        elif f["where"] in ("record", "spare_record"):
+            dt, at = self.rec_dt, (f["offset"] - self.rec_off) % self.rec_dt.itemsize
+        else:
+            return None
+        for name in dt.names:
+            sub, off = dt.fields[name][:2]
+            if off <= at < off + sub.itemsize:
+                return "%s[%d]" % (name, (at - off) // sub.base.itemsize) if sub.shape else name
+        return "padding"
+
+    def check(self, after):
+        found = self.arena.compare(self.want, after)
+        for f in found:
+            f["field"] = self.field(f)
+            if f["field"]:
+                f["message"] += " (%s)" % f["field"]
+        return found
+
+    def run(self):
+        fn = load().psk_prepass_probe_symrate if self.kind == "symrate" else load().psk_prepass_probe_acquire
+        extra = () if self.kind == "symrate" else (1 if self.tables else 0,)
+        return _launch(self.kind, fn, self.image, self.desc.ctypes.data, len(self.desc), self.max_piece, self.part_off, self.rec_off, *extra)

@@ -5,9 +5,11 @@ import functools
 
 import numpy as np
 
+from tests import acquire_model as am
 from tests import fir_model as fm
 from tests import prepass_probe as pp
 from tests import resample_model as rm  # noqa: F401  (the tests reach the model through this module)
+from tests import symrate_model as sm
 from tests import tune_model as tm
 
 F32 = np.float32
@@ -372,3 +374,296 @@ def fir_edges():
             p["taps"][0] = 1.0
             add("huge", p)
     return pp.FirCase(out), kinds
+
+
+# ---- the two looks (psk_symrate.hip, psk_acquire.hip): fold and join ---------------------------------------------------------------
+
+SR_WIDTHS = (1, 2, 4, 8, 16, 32, 64)
+SR_CLASS_S = {1: (4, 5, 8), 2: (9, 16), 4: (17, 24, 32), 8: (33, 64), 16: (65, 100, 128), 32: (129, 200, 256), 64: (257, 511, 1000, 1024)}
+NONFINITE = (np.nan, np.inf, -np.inf)
+BIG_PACKET_BYTES = 1 << 20  # a source matrix above this is laid out contiguous, in a narrow format: the arenas stay below 64 MiB
+LOOP_DESCRIPTORS, LOOP_PAIRS = 70000, 70000 - pp.LOOK_GRID_MAX  # 4465 descriptors have a partner on the second trip
+
+
+def sr_block_counts(W):
+    """the block counts of a width's launch, G = 64 / W blocks a wave at a time: either side of one wave, of the four waves of a
+    workgroup, of a turn of stage 2 (256), of a piece (512), of the halo behind it (128) and of two pieces; without 1025 at the two
+    widest classes"""
+    G = 64 // W
+    c = {2, 3, G - 1, G, G + 1, 4 * G - 1, 4 * G, 4 * G + 1, 255, 256, 257, 511, 512, 513, 512 + 127, 512 + 128, 512 + 129, 1025}
+    return sorted(b for b in c if b >= 2 and not (W >= 32 and b == 1025))
+
+
+def sr_signal(S, n, seed):
+    """interleaved float32: noisy QPSK at 1.04 S samples a symbol with a shaped pulse (the signal of tests/test_symrate_control.py)"""
+    rng = np.random.default_rng(seed)
+    u = np.arange(n) / (1.04 * S)
+    sym = rng.integers(0, 4, int(u[-1]) + 2)[np.floor(u).astype(int)]
+    z = (0.2 + 0.8 * np.sin(np.pi * (u - np.floor(u)))) * np.exp(2j * np.pi * (sym / 4 + 0.002 * np.arange(n)))
+    x = np.empty(2 * n, F32)
+    x[0::2] = z.real + 0.05 * rng.standard_normal(n)
+    x[1::2] = z.imag + 0.05 * rng.standard_normal(n)
+    return x
+
+
+def _as_format(x, fmt):
+    """float32 samples of about unit size in the format's dtype (the integer and half formats: scaled by 40, int8's range)"""
+    return x if fmt == pp.FORMAT_CF32 else np.clip(np.round(40.0 * x), -127, 127).astype(pp.DTYPE_OF[fmt])
+
+
+def _look_mix(k, n):
+    """format, stride, skew and tune of packet k of a look launch, mixed by index as _packet mixes them; a packet whose matrix
+    would be large is contiguous, and CS8 if it still is"""
+    fmt, stride = pp.FORMATS[k % 4], (1, 7)[(k // 4 + k) % 2]
+    if n * pp.SAMPLE_BYTES[fmt] * stride > BIG_PACKET_BYTES:
+        stride = 1
+        if n * pp.SAMPLE_BYTES[fmt] > BIG_PACKET_BYTES:
+            fmt = (pp.FORMAT_CS8, pp.FORMAT_CS16, pp.FORMAT_CF16)[k % 3] if n * 4 <= BIG_PACKET_BYTES else pp.FORMAT_CS8
+    tune = ((0x9E3779B97F4A7C15 * (k + 1)) % (1 << 64), TUNE_STEPS[(k // 3) % 4]) if (k // 2) % 3 != 1 else None
+    return dict(fmt=fmt, stride=stride, skew=pp.SAMPLE_BYTES[fmt] if k % 2 else 0, tune=tune)
+
+
+@functools.lru_cache(maxsize=None)
+def symrate_width(W):
+    """One launch of every S of a width class x sr_block_counts(W): a ragged tail of 0, S - 1 or 3 samples; the four formats,
+    strides 1 and 7, tuned and not, mixed by index"""
+    protos = []
+    for S in SR_CLASS_S[W]:
+        assert sm.width(S) == W
+        for b in sr_block_counts(W):
+            k = len(protos)
+            n = b * S + (0, S - 1, 3)[k % 3]
+            p = _look_mix(k, n)
+            p.update(S=S, blocks=b, iq=_as_format(sr_signal(S, n, 8000 + 64 * S + k), p["fmt"]))
+            protos.append(p)
+    return pp.LookCase("symrate", protos, [(k, True) for k in range(len(protos))])
+
+
+SR_VALIDITY_S = {1: 5, 2: 9, 4: 17, 8: 33, 16: 100, 32: 200, 64: 257}  # an S of each width whose last turn is ragged (W > 1)
+
+
+def sr_bad_positions(S):
+    """positions of a block a bad sample goes to: 0, W - 1, W (lane 0's second turn), the first position of the last turn --
+    ragged: `p < S` is false for part of the wave --, S - 1"""
+    W = sm.width(S)
+    return sorted({0, W - 1, min(W, S - 1), (S - 1) // W * W, S - 1})
+
+
+def sr_wave_slot(b, G):
+    """(turn-and-wave index, sub) of block b in stage 1's walk of its own piece: `base = start + wave * G + turn * 4 G`, start a
+    multiple of 64 -- the blocks of one index share a wave's ballot"""
+    lo = b // sm.PIECE * sm.PIECE
+    start = lo - sm.HALO if lo else 0
+    return (b - start) // G, (b - start) % G
+
+
+def sr_bad_blocks(nb, G):
+    """blocks a bad sample goes to: one that is sub 0 of its wave, one that is sub G - 1, the packet's last block; with two
+    pieces, in the second piece's own blocks"""
+    at = 512 + 2 * G if nb > 512 + 3 * G else (17 // G) * G
+    return sorted({at, min(at + G - 1, nb - 2), nb - 1})
+
+
+@functools.lru_cache(maxsize=None)
+def symrate_validity(W):
+    """One launch at S = SR_VALIDITY_S[W]: packets of 40, 41 and 642 blocks, one non-finite value each (NaN, +inf, -inf in turn,
+    real or imaginary part) at every sr_bad_positions x sr_bad_blocks; the last sample of block 511 (it takes blocks 511 and 512
+    out, in piece 1's own blocks and in its halo) and of block 383 (in piece 1's halo only).  p["bad"]: the blocks the
+    definition invalidates."""
+    S, G = SR_VALIDITY_S[W], 64 // W
+    assert sm.width(S) == W
+    base = {nb: sr_signal(S, nb * S + 3, 8500 + S + nb) for nb in (40, 41, 642)}
+    spots = [(nb, b, pos) for nb in (40, 41, 642) for b in sr_bad_blocks(nb, G) for pos in sr_bad_positions(S)]
+    spots += [(642, 511, S - 1), (642, 383, S - 1)]
+    protos = []
+    for nb, b, pos in spots:
+        k = len(protos)
+        p = _look_mix(k, nb * S + 3)
+        # (a non-finite value needs a float format; half the packets are CF16)
+        p["fmt"] = (pp.FORMAT_CF32, pp.FORMAT_CF16)[k % 2] if (nb * S + 3) * 8 * p["stride"] <= BIG_PACKET_BYTES else pp.FORMAT_CF16
+        p["skew"] = pp.SAMPLE_BYTES[p["fmt"]] if k % 2 else 0
+        x = base[nb].copy() if p["fmt"] == pp.FORMAT_CF32 else (40.0 * base[nb]).astype(np.float16)
+        x[2 * (b * S + pos) + (k // 3) % 2] = NONFINITE[k % 3]
+        bad = {b, b + 1} if pos == S - 1 and b + 1 < nb else {b}
+        p.update(S=S, blocks=nb, iq=x, bad=bad, spot=(nb, b, pos))
+        protos.append(p)
+    return pp.LookCase("symrate", protos, [(k, True) for k in range(len(protos))])
+
+
+@functools.lru_cache(maxsize=None)
+def symrate_edges():
+    """(the case, {name: descriptors of that kind}), at an S of four widths.  tiny: float32 samples scaled by 2^-130 (every e and g
+    is zero or subnormal: a flush anywhere would show); huge: 3e19 -- every e overflows, no block is valid; zeros: zeros of both
+    signs, alone and between small integers"""
+    rng = np.random.default_rng(8700)
+    protos, kinds = [], {}
+    for j, S in enumerate((8, 24, 200, 257)):
+        for kind in ("tiny", "huge", "zeros"):
+            k = len(protos)
+            n = (40, 530, 700)[(j + k) % 3] * S + 3
+            p = _look_mix(k, n)
+            p["fmt"] = pp.FORMAT_CF32 if kind != "zeros" or k % 2 else pp.FORMAT_CF16
+            p["skew"] = pp.SAMPLE_BYTES[p["fmt"]] if k % 2 else 0
+            if n * pp.SAMPLE_BYTES[p["fmt"]] * p["stride"] > BIG_PACKET_BYTES:
+                p["stride"] = 1
+            x = sr_signal(S, n, 8700 + k)
+            if kind == "tiny":
+                x = (x * F32(TINY)).astype(F32)
+            elif kind == "huge":
+                x = (x * F32(3e19)).astype(F32)
+            else:
+                z = np.where(rng.integers(0, 2, x.size) == 1, -0.0, 0.0)
+                if j % 2:
+                    z = np.where(rng.integers(0, 3, z.size) == 0, rng.integers(-9, 10, z.size).astype(np.float64), z)
+                x = z.astype(pp.DTYPE_OF[p["fmt"]])
+            p.update(S=S, iq=x)
+            kinds.setdefault(kind, []).append(k)
+            protos.append(p)
+    return pp.LookCase("symrate", protos, [(k, True) for k in range(len(protos))]), kinds
+
+
+# ---- the packet loop: more descriptors than a grid has workgroups ------------------------------------------------------------------
+
+LOOP_KINDS = ("two pieces, then a first piece of three", "a first piece of three, then two pieces", "data, then none", "invalid, then valid")
+
+
+def loop_uses(n_small):
+    """the (proto, data) of the 70000 descriptors over protos 0 two pieces, every unit valid; 1 a first piece of three units; 2
+    two pieces with invalid units; 3 one short valid piece; 4 .. 4 + n_small - 1 short packets.  Descriptor c < 4465 and its
+    partner c + 65535, which the same workgroups take on their second trip, are of LOOP_KINDS[c % 4]; of the others every
+    seventh has no data."""
+    first = ((0, True), (1, True), (0, True), (2, True))
+    second = ((1, True), (0, True), (4, False), (3, True))
+    uses = []
+    for c in range(LOOP_DESCRIPTORS):
+        if c < LOOP_PAIRS:
+            uses.append(first[c % 4] if c % 4 != 2 or c % 8 == 2 else (4 + c % n_small, True))
+        elif c >= pp.LOOK_GRID_MAX:
+            uses.append(second[(c - pp.LOOK_GRID_MAX) % 4])
+        else:
+            uses.append((4 + (c * 7) % n_small, c % 7 != 0))
+    return uses
+
+
+@functools.lru_cache(maxsize=None)
+def symrate_loop():
+    """70000 descriptors, max_piece 2, 24 distinct packets: loop_uses over two pieces of S = 4 (600 blocks), three blocks of S =
+    5, 600 blocks of S = 4 with NaNs in blocks 100, 511 and 599, five blocks of S = 8, and 2 .. 5 blocks of S = 4 .. 8"""
+    protos = []
+
+    def add(S, blocks, tail, bad=()):
+        k = len(protos)
+        n = blocks * S + tail
+        p = _look_mix(k, n)
+        if bad:
+            p["fmt"] = pp.FORMAT_CF32
+        x = _as_format(sr_signal(S, n, 8800 + k), p["fmt"])
+        for b in bad:
+            x[2 * (b * S + 1)] = np.nan
+        p.update(S=S, blocks=blocks, iq=x, bad=set(bad))
+        protos.append(p)
+
+    add(4, 600, 3)
+    add(5, 3, 4)
+    add(4, 600, 0, bad=(100, 511, 599))
+    add(8, 5, 7)
+    for S in (4, 5, 6, 7, 8):
+        for blocks in (2, 3, 4, 5):
+            add(S, blocks, (0, S - 1, 3)[len(protos) % 3])
+    return pp.LookCase("symrate", protos, loop_uses(20), spare_every=97)
+
+
+# ---- acquire -----------------------------------------------------------------------------------------------------------------------
+
+def acquire_lengths():
+    """EDGE_LENGTHS of tests/test_gpu_acquire.py, and the three at which the join takes a second trip over the partials"""
+    P = am.PIECE
+    return (1, 2, 127, 128, 129, P - 1, P, P + 1, P + 127, P + 129, 2 * P + 5, 3 * P + 1, 64 * P, 64 * P + 1, 65 * P + 131)
+
+
+def carrier(seed, M, n):
+    """a noisy M-PSK carrier at 0.007 cycles per sample, 4 samples per symbol, interleaved float32"""
+    rng = np.random.default_rng(seed)
+    z = np.exp(2j * np.pi * (np.repeat(rng.integers(0, M, n // 4 + 1), 4)[:n] / M + 0.007 * np.arange(n))) * rng.uniform(0.8, 1.25)
+    x = np.empty(2 * n, F32)
+    x[0::2] = z.real + 0.08 * rng.standard_normal(n)
+    x[1::2] = z.imag + 0.08 * rng.standard_normal(n)
+    return x
+
+
+PLACEMENTS = ("aligned", "skewed", "strided")
+
+
+def _acquire_packet(k, n, M, fmt, place, tuned):
+    """packet k: across the piece boundaries an inf, a NaN (float formats), a run of 200 zeros and a run of samples too small
+    to be valid (float32: a = e, q or q * q lies below FLT_MIN), as the lengths allow"""
+    P = am.PIECE
+    x = carrier(9000 + 13 * k + M, M, n)
+    floats = fmt in (pp.FORMAT_CF32, pp.FORMAT_CF16)
+    x = _as_format(x, fmt) if fmt != pp.FORMAT_CF16 else (40.0 * x).astype(np.float16)
+    marks = set()
+    if n > P and k % 2 == 1 and floats:
+        x[2 * (P - 1)], x[2 * P + 1] = np.inf, np.nan  # the last sample of piece 0, the first of piece 1
+        marks.add("nonfinite")
+    if n >= P + 127 and k % 3 == 0:
+        x[2 * (P - 100) : 2 * min(n, P + 100)] = 0
+        marks.add("zeros")
+    if n >= 2 * P + 5 and floats:
+        x[2 * (2 * P - 64) + 1] = -np.inf  # reaches over the next boundary through the longer lags
+        marks.add("nonfinite")
+    if n >= 129 and fmt == pp.FORMAT_CF32 and k % 2 == 0:
+        lo = min(n, P) - 60 if n > 200 else 40
+        x[2 * lo : 2 * min(n, lo + 90)] *= F32(1e-20)  # (e about 1e-40: below FLT_MIN)
+        marks.add("underflow")
+    tune = ((0x9E3779B97F4A7C15 * (k + 1)) % (1 << 64), TUNE_STEPS[(k // 3) % 4]) if tuned else None
+    return dict(fmt=fmt, stride=7 if place == "strided" else 1, skew=pp.SAMPLE_BYTES[fmt] if place == "skewed" else 0, tune=tune, M=M, iq=x,
+                place=place, marks=marks)
+
+
+ACQUIRE_LONG = {False: ((pp.FORMAT_CF32, "aligned", 4), (pp.FORMAT_CS16, "skewed", 8), (pp.FORMAT_CS8, "strided", 2)),
+                True: ((pp.FORMAT_CF16, "skewed", 2), (pp.FORMAT_CS8, "strided", 4), (pp.FORMAT_CF32, "aligned", 8))}
+
+
+@functools.lru_cache(maxsize=None)
+def acquire_lengths_case(mixed):
+    """One launch.  Every (format, placement) takes every third of the twelve short lengths, so that each length meets four of
+    them, M turning over 2, 4, 8; the three long lengths once each (ACQUIRE_LONG).  mixed False: no packet is tuned, the fold gets
+    no tables; True: two packets in three are tuned."""
+    lens = acquire_lengths()
+    protos = []
+    for q, (fmt, place) in enumerate((f, pl_) for f in pp.FORMATS for pl_ in PLACEMENTS):
+        for i, n in enumerate(lens[:12]):
+            if (i + q) % 3 == 0:
+                k = len(protos)
+                protos.append(_acquire_packet(k, n, (2, 4, 8)[(i // 3 + q) % 3], fmt, place, mixed and k % 3 != 1))
+    for n, (fmt, place, M) in zip(lens[12:], ACQUIRE_LONG[mixed]):
+        k = len(protos)
+        protos.append(_acquire_packet(k, n, M, fmt, place, mixed and k % 3 != 1))
+    return pp.LookCase("acquire", protos, [(k, True) for k in range(len(protos))], tables=mixed)
+
+
+@functools.lru_cache(maxsize=None)
+def acquire_loop():
+    """70000 descriptors, max_piece 2, 24 distinct packets: loop_uses over P + 200 valid samples, three samples, P + 200 samples
+    with invalid ones, five samples, and 2 .. 40 samples; tuned and untuned mixed"""
+    P = am.PIECE
+    protos = []
+
+    def add(n, M, bad=False):
+        k = len(protos)
+        p = _look_mix(k, n)
+        if bad:
+            p["fmt"] = pp.FORMAT_CF32
+        x = _as_format(carrier(9500 + k, M, n), p["fmt"])
+        if bad:
+            x[2 * 77], x[2 * (P - 1) + 1], x[2 * (n - 1)] = np.nan, np.inf, 0.0
+        p.update(M=M, iq=x, bad=bad)
+        protos.append(p)
+
+    add(P + 200, 4)
+    add(3, 2)
+    add(P + 200, 8, bad=True)
+    add(5, 4)
+    for i in range(20):
+        add(2 + (i * 7) % 39, (2, 4, 8)[i % 3])
+    return pp.LookCase("acquire", protos, loop_uses(20), spare_every=97)

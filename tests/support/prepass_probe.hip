@@ -1,9 +1,10 @@
-// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip, psk_fir.hip) launched by
-// themselves, so that tests can hold every byte they write -- each row sample, both history slots -- and every byte they must
-// not write to the models, bit for bit (tests/prepass_probe.py, tests/test_gpu_prepass_probe.py).
+// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip, psk_fir.hip) and the two
+// looks (psk_symrate.hip, psk_acquire.hip: fold and join) launched by themselves, so that tests can hold every byte they write -- each
+// row sample, both history slots, every partial and record -- and every byte they must not write to the models, bit for bit
+// (tests/prepass_probe.py, tests/test_gpu_prepass_probe.py).
 //
-// This file holds no kernel.  It is linked with the product's own objects psk_gather.o, psk_tune.o, psk_resample.o and psk_fir.o as
-// the product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
+// This file holds no kernel.  It is linked with the product's own objects psk_gather.o, psk_tune.o, psk_resample.o, psk_fir.o,
+// psk_symrate.o and psk_acquire.o as the product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
 // the product's.  Nothing of it is linked into the product library.
 //
 // One C entry per kernel.  The caller passes one host ARENA -- sources, destination rows, histories, poison everywhere else --
@@ -17,9 +18,11 @@
 
 #include <vector>
 
+#include "psk_acquire.h"
 #include "psk_fir.h"
 #include "psk_gather.h"
 #include "psk_resample.h"
+#include "psk_symrate.h"
 #include "psk_tune.h"
 
 using namespace psk;
@@ -82,7 +85,8 @@ bool point(P &field, const char *d_arena, uint64_t bytes)
 
 extern "C" {
 
-// 0 GatherGroup, 1 GatherChan, 2 GatherSingle, 3 TuneDesc, 4 ResampleDesc, 5 FirDesc
+// 0 GatherGroup, 1 GatherChan, 2 GatherSingle, 3 TuneDesc, 4 ResampleDesc, 5 FirDesc, 6 SymrateDesc, 7 SymratePartial, 8 AcquireDesc,
+// 9 AcquirePartial, 10 psk_soft_symrate_t, 11 psk_soft_acquire_t
 int psk_prepass_probe_sizeof(int which)
 {
     switch (which) {
@@ -92,12 +96,19 @@ int psk_prepass_probe_sizeof(int which)
     case 3: return (int)sizeof(TuneDesc);
     case 4: return (int)sizeof(ResampleDesc);
     case 5: return (int)sizeof(FirDesc);
+    case 6: return (int)sizeof(SymrateDesc);
+    case 7: return (int)sizeof(SymratePartial);
+    case 8: return (int)sizeof(AcquireDesc);
+    case 9: return (int)sizeof(AcquirePartial);
+    case 10: return (int)sizeof(psk_soft_symrate_t);
+    case 11: return (int)sizeof(psk_soft_acquire_t);
     default: return -1;
     }
 }
 
 // 0 kResamplePiece, 1 kResampleInputs, 2 kGatherTile, 3 kGatherMinGroup, 4 kTuneTableFloats, 5 kFirWindow, 6 kFirMaxTaps,
-// 7 kFirHistSlotFloats
+// 7 kFirHistSlotFloats, 8 kSymratePiece, 9 kSymrateHalo, 10 kSymrateThreads, 11 kSymrateMinS, 12 kSymrateMaxS, 13 kSymrateMaxBlocks,
+// 14 kAcquirePiece, 15 kAcquireHalo, 16 kAcquireThreads
 int psk_prepass_probe_constant(int which)
 {
     switch (which) {
@@ -109,6 +120,15 @@ int psk_prepass_probe_constant(int which)
     case 5: return (int)kFirWindow;
     case 6: return (int)kFirMaxTaps;
     case 7: return (int)kFirHistSlotFloats;
+    case 8: return (int)kSymratePiece;
+    case 9: return (int)kSymrateHalo;
+    case 10: return (int)kSymrateThreads;
+    case 11: return (int)kSymrateMinS;
+    case 12: return (int)kSymrateMaxS;
+    case 13: return (int)kSymrateMaxBlocks;
+    case 14: return (int)kAcquirePiece;
+    case 15: return (int)kAcquireHalo;
+    case 16: return (int)kAcquireThreads;
     default: return -1;
     }
 }
@@ -207,6 +227,51 @@ int psk_prepass_probe_fir(void *arena, uint64_t bytes, const void *desc, uint32_
     if (!r.descriptors(0, d.data(), sizeof(FirDesc) * d.size()) || !r.tables())
         return r.end(hipSuccess, arena, 0, nullptr);
     return r.end(launch_fir((const FirDesc *)r.d_desc[0], n_desc, max_pieces, r.d_tab, r.stream), arena, bytes, nullptr);
+}
+
+// The two looks: fold, then join, one launch each.  part_off, rec_off: where the partials (slot 0) and the records (channel 0) lie
+// in the arena; a descriptor without its DATA flag keeps the null source the product gives it.
+int psk_prepass_probe_symrate(void *arena, uint64_t bytes, const void *desc, uint32_t n_desc, uint32_t max_piece, uint64_t part_off,
+                              uint64_t rec_off)
+{
+    if (!arena || !bytes || !desc || !n_desc || part_off >= bytes || rec_off >= bytes || part_off % 8u || rec_off % 8u)
+        return (int)hipErrorInvalidValue;
+    std::vector<SymrateDesc> d((const SymrateDesc *)desc, (const SymrateDesc *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (SymrateDesc &t : d)
+        if ((t.flags & PSK_SOFT_SR_DATA) && !point(t.src, r.d_arena, bytes))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(SymrateDesc) * d.size()) || !r.tables())
+        return r.end(hipSuccess, arena, 0, nullptr);
+    SymratePartial *const part = (SymratePartial *)(r.d_arena + part_off);
+    hipError_t e = launch_symrate_fold((const SymrateDesc *)r.d_desc[0], n_desc, max_piece, r.d_tab, part, r.stream);
+    if (e == hipSuccess)
+        e = launch_symrate_join((const SymrateDesc *)r.d_desc[0], n_desc, part, (psk_soft_symrate_t *)(r.d_arena + rec_off), r.stream);
+    return r.end(e, arena, bytes, nullptr);
+}
+
+// with_tables 0: the launch has no tuned packet, the fold gets no tables (psk_acquire_fold_kernel<false>)
+int psk_prepass_probe_acquire(void *arena, uint64_t bytes, const void *desc, uint32_t n_desc, uint32_t max_piece, uint64_t part_off,
+                              uint64_t rec_off, int with_tables)
+{
+    if (!arena || !bytes || !desc || !n_desc || part_off >= bytes || rec_off >= bytes || part_off % 8u || rec_off % 8u)
+        return (int)hipErrorInvalidValue;
+    std::vector<AcquireDesc> d((const AcquireDesc *)desc, (const AcquireDesc *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (AcquireDesc &t : d)
+        if (((t.flags & PSK_SOFT_A_DATA) && !point(t.src, r.d_arena, bytes)) || ((t.flags & PSK_SOFT_A_TUNED) && !with_tables))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(AcquireDesc) * d.size()) || (with_tables && !r.tables()))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    AcquirePartial *const part = (AcquirePartial *)(r.d_arena + part_off);
+    hipError_t e = launch_acquire_fold((const AcquireDesc *)r.d_desc[0], n_desc, max_piece, r.d_tab, part, r.stream);
+    if (e == hipSuccess)
+        e = launch_acquire_join((const AcquireDesc *)r.d_desc[0], n_desc, part, (psk_soft_acquire_t *)(r.d_arena + rec_off), r.stream);
+    return r.end(e, arena, bytes, nullptr);
 }
 
 }  // extern "C"

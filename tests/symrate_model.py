@@ -65,9 +65,10 @@ def _lanes(terms, w):
     return acc
 
 
-def block_sums(x, S):
+def block_sums(x, S, tree=None):
     """x: interleaved float32 I/Q (converted, tuned).  Returns dict(B (nb, 4) float64: B_e re, im, B_g re, im; lvl (nb, 2);
-    valid (nb,) bool) in the device's order, invalid blocks zeroed; and absz (nb, 2): the sum of |z| per block, for the bounds."""
+    valid (nb,) bool) in the device's order, invalid blocks zeroed; and absz (nb, 2): the sum of |z| per block, for the bounds.
+    tree: another xor tree in place of _tree (tests/test_prepass_probe.py builds a wrong writer with one)."""
     n = x.size // 2
     nb = n_blocks_of(n, S)
     nu = nb * S
@@ -94,7 +95,7 @@ def block_sums(x, S):
         for q, t in enumerate(cols):
             t = np.where(valid[:, None], t.astype(F64).reshape(nb, S), 0.0)  # (keeps NaN out of the arithmetic below)
             t = np.concatenate([t, np.zeros((nb, pad), F64)], axis=1)
-            out[:, q] = _tree(_lanes(t, w), w)[:, 0]
+            out[:, q] = (tree or _tree)(_lanes(t, w), w)[:, 0]
         absz = np.stack([np.where(valid[:, None], np.abs(z.astype(F64)).reshape(nb, S), 0.0).sum(axis=1) for z in (e, g)], axis=1)
     out[~valid] = 0.0
     return dict(B=out[:, :4].copy(), lvl=out[:, 4:].copy(), valid=valid, absz=absz)
@@ -126,26 +127,65 @@ def _piece_terms(b, lo, hi):
     return terms, counts
 
 
+def piece_partial(b, lo, hi):
+    """(36 doubles, 9 counts): what the fold leaves in the SymratePartial of the piece of the blocks [lo, hi)"""
+    t, c = _piece_terms(b, lo, hi)
+    turns = -(-(hi - lo) // THREADS)
+    t = np.concatenate([t, np.zeros((36, turns * THREADS - (hi - lo)), F64)], axis=1)
+    lanes = _lanes(t, THREADS)  # (36, 256)
+    waves = _tree(lanes.reshape(36, THREADS // 64, 64), 64)[:, :, 0]
+    p = waves[:, 0]
+    for w in range(1, THREADS // 64):
+        p = p + waves[:, w]
+    return p, c
+
+
+def _piece_partials(b):
+    nb = b["valid"].size
+    return [piece_partial(b, lo, min(lo + PIECE, nb)) for lo in range(0, nb, PIECE)]
+
+
+def partial_bytes(p):
+    """the 324 bytes of a SymratePartial in front of its pad"""
+    d, c = p
+    return np.asarray(d, "<f8").tobytes() + np.asarray(c, "<u4").tobytes()
+
+
+def join_bytes(parts, n, S, tuned):
+    """the record the join makes of a packet's partials: 392 bytes"""
+    s, c = _join(parts)
+    nb = n_blocks_of(n, S)
+    return struct.pack("<4Q8Q36dHB5x", n, nb * S, nb, int(c[8]), *[int(v) for v in c[:8]], *[float(v) for v in np.concatenate(
+        [s[0:8], s[16:24], s[8:16], s[24:32], s[32:36]])], S, SR_DATA | (SR_TUNED if tuned else 0))
+
+
+def _join(parts):
+    """the packet's 36 sums and 9 counts: the join of its pieces' partials in the device's order"""
+    n_piece = len(parts)
+    t = np.stack([p for p, _ in parts], axis=1)  # (36, n_piece)
+    t = np.concatenate([t, np.zeros((36, (-n_piece) % 64), F64)], axis=1)
+    return _tree(_lanes(t, 64), 64)[:, 0], sum(c for _, c in parts)
+
+
 def _fold(b):
     """the packet's 36 sums and 9 counts in the device's order"""
-    nb = b["valid"].size
-    partials, counts = [], np.zeros(9, np.int64)
-    for lo in range(0, nb, PIECE):
-        hi = min(lo + PIECE, nb)
-        t, c = _piece_terms(b, lo, hi)
-        counts += c
-        turns = -(-(hi - lo) // THREADS)
-        t = np.concatenate([t, np.zeros((36, turns * THREADS - (hi - lo)), F64)], axis=1)
-        lanes = _lanes(t, THREADS)  # (36, 256)
-        waves = _tree(lanes.reshape(36, THREADS // 64, 64), 64)[:, :, 0]
-        p = waves[:, 0]
-        for w in range(1, THREADS // 64):
-            p = p + waves[:, w]
-        partials.append(p)
-    n_piece = len(partials)
-    t = np.stack(partials, axis=1)  # (36, n_piece)
-    t = np.concatenate([t, np.zeros((36, (-n_piece) % 64), F64)], axis=1)
-    return _tree(_lanes(t, 64), 64)[:, 0], counts
+    return _join(_piece_partials(b))
+
+
+def _converted(iq, S, tune):
+    """(the float32 samples the look uses -- converted, tuned --, tuned?)"""
+    tuned = tune is not None and (int(tune[0]) | int(tune[1])) != 0
+    x = np.asarray(iq)[: 2 * n_blocks_of(np.asarray(iq).size // 2, S) * S]
+    return (tm.apply(tune[0], tune[1], x) if tuned else x.astype(F32)), tuned
+
+
+def partials(iq, S, tune=None):
+    """[(d: 36 float64, c: 9 int64)] per piece of the packet, as the fold kernel leaves them in its SymratePartial (the record
+    is their join: model_record); [] for a packet the look does not take"""
+    n = 0 if iq is None else np.asarray(iq).size // 2
+    if not (MIN_S <= S <= MAX_S) or n < 2 * S:
+        return []
+    return _piece_partials(block_sums(_converted(iq, S, tune)[0], S))
 
 
 def zero_record():
@@ -160,15 +200,14 @@ def model_record(iq, S, tune=None):
     n = 0 if iq is None else np.asarray(iq).size // 2
     if not (MIN_S <= S <= MAX_S) or n < 2 * S:
         return zero_record()  # (the zero record of a covered channel without a look)
-    tuned = tune is not None and (int(tune[0]) | int(tune[1])) != 0
     nb = n_blocks_of(n, S)
-    x = np.asarray(iq)[: 2 * nb * S]
-    x = tm.apply(tune[0], tune[1], x) if tuned else x.astype(F32)
+    x, tuned = _converted(iq, S, tune)
     b = block_sums(x, S)
-    s, c = _fold(b)
+    parts = _piece_partials(b)
+    s, c = _join(parts)
     r = zero_record()
     r.update(n_samples=n, n_used=nb * S, n_blocks=nb, n_valid=int(c[8]), n_pairs=[int(v) for v in c[:8]], samplesPerBaud=S,
-             flags=SR_DATA | (SR_TUNED if tuned else 0), blocks=b)
+             flags=SR_DATA | (SR_TUNED if tuned else 0), blocks=b, parts=parts)
     for z in range(2):
         r["sum_re"][z] = [float(v) for v in s[16 * z : 16 * z + 8]]
         r["sum_im"][z] = [float(v) for v in s[16 * z + 8 : 16 * z + 16]]

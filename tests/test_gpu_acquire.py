@@ -166,6 +166,36 @@ def test_lengths_at_the_edges_of_a_piece_against_the_model(M):
         h.close()
 
 
+def test_a_packet_of_66_pieces_among_short_ones():
+    """65 P + 131 samples of CS16: the join's lanes 0 and 1 take two partials each, and the handle's scratch grows to 66 partials
+    and more.  At this length assert_record's bound is two orders wider than one float32 rounding of a term, so the record is
+    held to acquire_model.device_record -- the device's order of additions restated -- byte for byte as well; the short packets
+    around it, the edge packets of M = 4, keep their model records."""
+    n, M = 65 * P + 131, 8
+    long = np.round(_carrier(8100, M, n, 40.0)).astype(np.int16)
+    long[2 * (64 * P - 1) : 2 * (64 * P + 90)] = 0  # (91 invalid samples across the boundary of piece 64)
+    xs, models = _edge_models(4)
+    items = xs[:5] + [long] + xs[5:]
+    h = _handle([4] * 5 + [M] + [4] * (len(xs) - 5))
+    try:
+        got, recs, _ = look(h, items)
+        assert got[5] == am.device_record(long, M), "65 P + 131 samples: the record is not the restated order's"
+        model = am.model_record(long, M)
+        am.assert_record(recs[5], model, "65 P + 131 samples")
+        assert recs[5].n_samples == n and recs[5].n_valid == n - 91 and recs[5].flags == pl.A_DATA
+        am.assert_derived(pl.acquire_derive(recs[5]), am.derive(recs[5]), "65 P + 131 samples")
+        for i, r in enumerate(recs[:5] + recs[6:]):
+            am.assert_record(r, models[i], "beside the long packet, n %d" % EDGE_LENGTHS[i])
+        # alone on a fresh handle, whose scratch grows from nothing: the same bytes
+        g = _handle([M])
+        try:
+            assert look(g, [long])[0][0] == got[5]
+        finally:
+            g.close()
+    finally:
+        h.close()
+
+
 # ---- 2. independence of the batch --------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("rot", (0, 1, 2))

@@ -1,4 +1,4 @@
-"""The gather, tune, resample and filter kernels by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim
+"""The gather, tune, resample and filter kernels and (at the end of the file) the two looks by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim
 linked with the product's own psk_gather.o, psk_tune.o, psk_resample.o and psk_fir.o).  The demodulator behind these kernels shows one row sample
 in eight at samplesPerBaud 8; here every byte of the arena a launch ran in is compared with the arena
 the models expect -- a byte copy for the gathers, tests/tune_model.py for the tune kernel, tests/tune_model.py followed by
@@ -109,3 +109,56 @@ def test_gather_tiles_more_tiles_than_workgroups(sample_bytes):
     """2100 groups of 8 columns by 10 frames: workgroups 0 .. 51 take a second tile"""
     case = pc.tiles_many_case(sample_bytes)
     _clean(case, case.run(), "%d tiles, %d-byte samples" % (case.n_tiles, sample_bytes))
+
+
+# ---- the two looks: fold and join ------------------------------------------------------------------------------------------------------
+#
+# psk_symrate.hip and psk_acquire.hip through the shim, psk_symrate.o and psk_acquire.o as the product's build made them: one
+# launch of the fold, one of the join.  The arena holds the sources, the partials and the records; the expected bytes are
+# tests/symrate_model.py's and tests/acquire_model.py's restatements of the device's order of additions -- every partial of every
+# piece and every record byte for byte, and every pad of a partial, every partial and record slot no descriptor owns, every
+# source byte and every guard byte unchanged.
+
+@pytest.mark.parametrize("W", pc.SR_WIDTHS)
+def test_symrate_every_lane_width(W):
+    """every S of the width class x block counts either side of one wave's blocks, of the workgroup's four waves, of a turn of
+    stage 2, of a piece and of its halo; ragged tails; the four formats, strides 1 and 7, tuned and not"""
+    case = pc.symrate_width(W)
+    _clean(case, case.run(), "width %d, %d packets, arena %d bytes" % (W, len(case.desc), case.arena.size))
+
+
+@pytest.mark.parametrize("W", pc.SR_WIDTHS)
+def test_symrate_a_non_finite_sample_takes_its_block_and_no_other_of_the_wave(W):
+    """40, 41 and 642 blocks, one NaN or inf a packet: in the first lane's first and second turn, the group's last lane, a ragged
+    last turn; in a block that is the first and one that is the last of its wave, in the packet's last block with the rest of
+    the wave idle; the last sample of block 511 (piece 1's own blocks and its halo) and of block 383 (its halo alone)"""
+    case = pc.symrate_validity(W)
+    _clean(case, case.run(), "validity at width %d, %d packets" % (W, len(case.desc)))
+
+
+def test_symrate_arithmetic_edges():
+    """samples scaled by 2^-130, samples whose e overflows, zeros of both signs"""
+    case, kinds = pc.symrate_edges()
+    _clean(case, case.run(), "arithmetic edges %s" % {k: (v[0], v[-1]) for k, v in kinds.items()})
+
+
+def test_symrate_more_packets_than_the_grid_has_rows():
+    """70000 descriptors: the workgroups of packets 0 .. 4464 take packets 65535 .. 69999 on a second trip, with the LDS of the
+    first still in place -- two pieces in front of a first piece of three blocks and the reverse, data in front of none, invalid
+    blocks in front of valid ones"""
+    case = pc.symrate_loop()
+    _clean(case, case.run(), "%d symrate descriptors, arena %d bytes" % (len(case.desc), case.arena.size))
+
+
+@pytest.mark.parametrize("mixed", (False, True))
+def test_acquire_lengths_formats_and_placements(mixed):
+    """the lengths at the edges of a piece and the three of 64 pieces and more (the join's lanes 0 and 1 take two partials), each
+    format aligned to its pair, one sample off and at stride 7; inf, NaN, zeros and underflowing samples across piece boundaries;
+    without a tuned packet (no tables) and with"""
+    case = pc.acquire_lengths_case(mixed)
+    _clean(case, case.run(), "acquire lengths, mixed %d, arena %d bytes" % (mixed, case.arena.size))
+
+
+def test_acquire_more_packets_than_the_grid_has_rows():
+    case = pc.acquire_loop()
+    _clean(case, case.run(), "%d acquire descriptors, arena %d bytes" % (len(case.desc), case.arena.size))

@@ -51,7 +51,7 @@ def _handle(Ss, **kw):
 
 def _edge_blocks(S):
     """block counts at the edges: two blocks, either side of the piece boundaries and of the halo behind the first, 129, the cap"""
-    every = [k * P for k in range(1, 8)] if S <= 33 else [P]
+    every = [k * P for k in range(1, 8)] if S in (4, 5, 8, 33) else [P]  # (every piece edge up to the cap at four block lengths)
     return [2] + sorted({b + e for b in every for e in (-1, 0, 1)} | {P + H - 1, P + H, P + H + 1, 129, 4096})
 
 
@@ -83,7 +83,7 @@ def _edge_models(S):
 
 # ---- 1. lengths at the edges of the kernel ---------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("S", (4, 5, 8, 33, 1024))
+@pytest.mark.parametrize("S", (4, 5, 8, 17, 33, 200, 257, 1024))
 def test_lengths_at_the_edges_of_a_piece_against_the_model(S):
     xs, models = _edge_models(S)
     lens = _edge_lengths(S)
@@ -245,11 +245,11 @@ def test_tuned_packets_give_the_records_of_their_model_packets():
 # ---- 6. non-finite samples -----------------------------------------------------------------------------------------------------------
 
 def test_a_non_finite_sample_invalidates_the_blocks_the_definition_says():
-    """S = 8 and S = 33, 40 blocks: a NaN or an inf in the first, a middle or the last sample of block 17 (its real or its
+    """S = 8, 16, 24, 33, 100, 200 and 1000 (1, 2, 4, 8, 16, 32 and 64 lanes a block), 40 blocks: a NaN or an inf in the first, a middle or the last sample of block 17 (its real or its
     imaginary part) takes block 17 out, in the last sample block 18 too (its first g reaches back); every block's last sample NaN:
     no block is valid, n_pairs all zero, a NaN derive.  Every record is the model's, byte for byte."""
     cases = []
-    for S in (8, 33):
+    for S in (8, 16, 24, 33, 100, 200, 1000):
         for v in (np.nan, np.inf, -np.inf):
             for where, part, bad in (("first", 0, {17}), ("middle", 1, {17}), ("last", 0, {17, 18})):
                 x = _samples(S, 40 * S + 3, "signal", 23000 + S)

@@ -8,15 +8,25 @@ inputs is left to chance.  The descriptors' mirrors are held to the sizeof the p
 
 The filter kernel (psk_fir.hip) follows in the same order at the end of the file: the mirror and the constants, the comparator on
 a FirCase with eight injected faults, what the grid, the three launch shapes and the arithmetic edges reach, and fir_model.apply
-held to the rounding bound of a float64 convolution."""
+held to the rounding bound of a float64 convolution.
+
+The two looks (psk_symrate.hip, psk_acquire.hip) close the file: the mirrors of their descriptors, partials and records and the
+constants; the comparator on a LookCase -- a clean numpy writer, then one ulp in one term of one block, a validity ballot over
+the whole wave, a tree one level short at four and at 32 lanes a block, a written pad, a record of 400 bytes, a record at the
+descriptor's index, n_pairs off by one at lag 128, a halo taken from the partner packet of the second trip, a second-trip packet
+skipped, and an acquire join without the partials 64 and above --; what the width, validity, edge and 70000-descriptor cases
+reach, against restatements of sr_width, the wave / sub walk of stage 1 and the grid rule; and acquire_model.device_record, the
+restated order of additions, held to the exact model_record on every acquire packet of the probe."""
 import numpy as np
 import pytest
 
 from psk_soft_amd import lib as pl
+from tests import acquire_model as am
 from tests import fir_model as fm
 from tests import prepass_probe as pp
 from tests import prepass_probe_cases as pc
 from tests import resample_model as rm
+from tests import symrate_model as sm
 from tests import tune_model as tm
 
 F32 = np.float32
@@ -732,3 +742,358 @@ def test_fir_model_lies_within_the_rounding_bound_of_a_float64_convolution():
             tightest = max(tightest, float((err / np.maximum(gamma * mag, 1e-300)).max()))
             seen += 1
     assert seen >= 4 * len(pc.FIR_DS) and 0.0 < tightest <= 1.0
+
+
+# ---- the two looks (psk_symrate.hip, psk_acquire.hip): the mirrors, the comparator on a LookCase, what the cases reach ---------------
+
+def test_the_look_constants_are_the_models():
+    assert (pp.constant("symrate_piece"), pp.constant("symrate_halo"), pp.constant("symrate_threads")) == (sm.PIECE, sm.HALO, sm.THREADS)
+    assert (pp.constant("symrate_min_s"), pp.constant("symrate_max_s"), pp.constant("symrate_max_blocks")) == (sm.MIN_S, sm.MAX_S, sm.MAX_BLOCKS)
+    assert (pp.constant("acquire_piece"), pp.constant("acquire_halo"), pp.constant("acquire_threads")) == (am.PIECE, am.HALO, am.THREADS)
+    assert pp.constant("acquire_piece") == pl.acquire_piece() and pp.constant("symrate_piece") == pl.symrate_piece()
+    assert pp.SYMRATE_REC.itemsize == sm.RECORD_BYTES and pp.ACQUIRE_REC.itemsize == am.RECORD_BYTES
+    assert pp.SYMRATE_PART.fields["pad"][1] == 324 and pp.ACQUIRE_PART.fields["pad"][1] == 172
+    assert [pp.SYMRATE_REC.fields[k][1] for k in ("n_pairs", "sum_re", "sum_im", "sum_pow", "sum_lvl", "samplesPerBaud", "flags", "pad")] == [
+        32, 96, 224, 352, 368, 384, 386, 387]  # (tests/test_symrate_control.py holds the binding's record to the same offsets)
+
+
+def _sr_width(S):
+    """sr_width of psk_symrate.h, restated: used to choose inputs, never to compute an expected byte"""
+    return 1 if S <= 8 else 2 if S <= 16 else 4 if S <= 32 else 8 if S <= 64 else 16 if S <= 128 else 32 if S <= 256 else 64
+
+
+def _float_packet(S, blocks, seed, bad=None):
+    x = pc.sr_signal(S, blocks * S + 3, seed)
+    if bad is not None:
+        x[2 * (bad * S + 2)] = np.nan
+    return dict(fmt=pp.FORMAT_CF32, stride=1, skew=0, tune=None, S=S, iq=x)
+
+
+@pytest.fixture(scope="module")
+def look_small():
+    """six symrate descriptors over five packets: width 4 with two pieces, width 32, width 4 with a NaN in block 17 of 40, a
+    tuned strided CS16 packet, a short one used twice -- once without data"""
+    protos = [_float_packet(24, 600, 1), _float_packet(200, 40, 2), _float_packet(24, 40, 3, bad=17), _float_packet(8, 5, 4)]
+    q = pc._look_mix(4, 9 * 70)
+    q.update(fmt=pp.FORMAT_CS16, stride=7, S=9, iq=pc._as_format(pc.sr_signal(9, 9 * 70, 5), pp.FORMAT_CS16))
+    assert q["tune"] is not None
+    protos.append(q)
+    return pp.LookCase("symrate", protos, [(0, True), (1, True), (3, False), (2, True), (4, True), (3, True)], spare_every=2)
+
+
+def _look_written(case, over=None, skip=(), at_index=(), tail=None):
+    """The arena after a stand-in for fold and join that writes what the models say.  over: {descriptor: (partials, n, S or M,
+    tuned)} -- that descriptor's partials come from a wrong fold, its record is the join of them; skip: descriptors neither kernel
+    reaches; at_index: descriptors whose record goes to records[c], not records[channel]; tail: (descriptor, bytes): a join that
+    stores that many bytes more behind the record."""
+    after = case.image.copy()
+    mod = sm if case.kind == "symrate" else am
+    psize, rsize = case.part_dt.itemsize, case.rec_dt.itemsize
+
+    def put(off, b):
+        after[off : off + len(b)] = np.frombuffer(b, np.uint8)
+
+    for i, (k, data) in enumerate(case.uses):
+        if i in skip:
+            continue
+        p = case.protos[k]
+        parts, rec = p["part_bytes"], p["record"] if data else bytes(rsize)
+        if over and i in over:
+            wrong, n, unit, tuned = over[i]
+            parts, rec = [mod.partial_bytes(q) for q in wrong], mod.join_bytes(wrong, n, unit, tuned)
+        if data:
+            for q, b in enumerate(parts):
+                put(case.part_off + (case.part0[i] + q) * psize, b)
+        put(case.rec_off + (i if i in at_index else case.channel[i]) * rsize, rec)
+    if tail:  # (behind every rightful store: the join's workgroups run in no order)
+        put(case.rec_off + case.channel[tail[0]] * rsize + rsize, b"\x11" * tail[1])
+    return after
+
+
+def _places(found):
+    return sorted((f["desc"] if f["desc"] is not None else -1, f["where"]) for f in found)
+
+
+def _pieces(b):
+    nb = b["valid"].size
+    return [sm.piece_partial(b, lo, min(lo + sm.PIECE, nb)) for lo in range(0, nb, sm.PIECE)]
+
+
+def test_look_a_correct_writer_is_clean(look_small):
+    c = look_small
+    assert c.check(_look_written(c)) == []
+    nothing = c.check(c.image)
+    assert nothing and {f["where"] for f in nothing} <= {"partial", "record"}, "an arena nothing was written to is not clean"
+    # the layout has what a wrong store would hit
+    assert list(c.desc["channel"]) != list(range(len(c.desc))) and sorted(c.part0) != c.part0 and c.spare
+    assert len(set(c.channel)) == len(c.channel) < c.n_rec and c.desc["n_piece"][0] == 2 and c.max_piece == 2
+    assert not c.desc["flags"][2] & pp.LOOK_DATA and c.desc["src"][2] == 0 and c.desc["flags"][4] & pp.LOOK_TUNED
+    assert c.want[c.rec_off + c.channel[2] * 392 :][:392].tobytes() == bytes(392)
+    assert [_sr_width(int(S)) for S in c.desc["S"]] == [4, 32, 1, 4, 2, 1] == [sm.width(int(S)) for S in c.desc["S"]]
+
+
+def test_look_one_ulp_in_one_term_of_one_block(look_small):
+    c, p = look_small, look_small.protos[0]
+    b = sm.block_sums(p["iq"], 24)
+    term = F32(b["B"][300, 0] / 24)
+    b["B"][300, 0] += float(np.spacing(term))  # (one float32 ulp of one of the block's 24 terms)
+    after = _look_written(c, over={0: (_pieces(b), p["n"], 24, False)})
+    found = c.check(after)
+    assert _places(found) == [(0, "partial"), (0, "record")], pp.messages(found)
+    part, rec = sorted(found, key=lambda f: f["where"])
+    assert part["offset"] < c.part_off + (c.part0[0] + 1) * 328, "block 300 and its partners lie in piece 0"
+    assert part["field"].startswith("d[") and rec["field"].startswith("sum_re") and "descriptor 0 record" in rec["message"]
+
+
+def test_look_a_ballot_over_the_whole_wave(look_small):
+    """validity taken from the wave's ballot without the lane group's mask: the 16 blocks that share block 17's wave go with it"""
+    c, p = look_small, look_small.protos[2]
+    b = sm.block_sums(p["iq"], 24)
+    assert [int(m) for m in np.flatnonzero(~b["valid"])] == [17]
+    G = 64 // _sr_width(24)
+    lo = 17 // G * G
+    b["valid"][lo : lo + G], b["B"][lo : lo + G], b["lvl"][lo : lo + G] = False, 0.0, 0.0
+    found = c.check(_look_written(c, over={3: (_pieces(b), p["n"], 24, False)}))
+    assert _places(found) == [(3, "partial"), (3, "record")], pp.messages(found)
+    assert [f["field"] for f in found if f["where"] == "record"] == ["n_valid"]
+
+
+def _short_tree(a, w):
+    """the xor tree without its last level"""
+    idx = np.arange(w)
+    off = w >> 1
+    while off >= 2:
+        a = a + a[..., idx ^ off]
+        off >>= 1
+    return a
+
+
+@pytest.mark.parametrize("i, S, W", [(0, 24, 4), (1, 200, 32)])
+def test_look_a_tree_one_level_short(look_small, i, S, W):
+    c, p = look_small, look_small.protos[i]
+    assert _sr_width(S) == W == sm.width(S)
+    b = sm.block_sums(p["iq"], S, tree=_short_tree)
+    found = c.check(_look_written(c, over={i: (_pieces(b), p["n"], S, False)}))
+    assert _places(found) == [(i, "partial")] * int(c.desc["n_piece"][i]) + [(i, "record")], pp.messages(found)
+    assert all(f["field"].startswith(("d[", "sum_")) for f in found)
+
+
+def test_look_a_written_pad_a_long_record_and_a_record_at_the_descriptors_index(look_small):
+    c = look_small
+    after = _look_written(c)
+    o = c.part_off + (c.part0[4]) * 328 + 324
+    after[o : o + 4] = 0
+    f = _one(c, after)
+    assert (f["desc"], f["where"], f["field"], f["n_bytes"]) == (4, "partial_pad", "pad", 4), f
+    # 400 bytes stored: the eight behind the record are the next slot's
+    found = c.check(_look_written(c, tail=(1, 8)))
+    assert len(found) == 1 and found[0]["n_bytes"] <= 8 and found[0]["offset"] == c.rec_off + (c.channel[1] + 1) * 392, pp.messages(found)
+    assert found[0]["where"] in ("record", "spare_record", "guard") and found[0]["desc"] != 1
+    # records[c] in place of records[d.channel]
+    assert c.channel[5] != 5
+    found = c.check(_look_written(c, at_index=(5,)))
+    owner = c.channel.index(5) if 5 in c.channel else None
+    assert _places(found) == sorted([(5, "record"), (owner if owner is not None else -1, "record" if owner is not None else "spare_record")])
+    assert next(f for f in found if f["desc"] == 5)["got"] == "c3" * 8
+
+
+def test_look_n_pairs_off_by_one_at_lag_128(look_small):
+    c, p = look_small, look_small.protos[0]
+    parts = [(d.copy(), k.copy()) for d, k in p["parts"]]
+    parts[1][1][7] += 1
+    found = c.check(_look_written(c, over={0: (parts, p["n"], 24, False)}))
+    assert [(f["desc"], f["where"], f["field"]) for f in found] == [(0, "partial", "c[7]"), (0, "record", "n_pairs[7]")], pp.messages(found)
+
+
+# ---- the packet loop's second trip -----------------------------------------------------------------------------------------------------
+
+def _pair_kind(case, c):
+    """which of pc.LOOP_KINDS the descriptors c and c + 65535 are, from the descriptors and the packets themselves"""
+    (ka, da), (kb, db) = case.uses[c], case.uses[c + pp.LOOK_GRID_MAX]
+    a, b = case.protos[ka], case.protos[kb]
+    clean = lambda p: not p.get("bad")  # noqa: E731
+    if da and db and len(a["parts"]) == 2 and clean(a) and len(b["parts"]) == 1 and b["units"] == 3:
+        return 0
+    if da and db and len(b["parts"]) == 2 and clean(b) and len(a["parts"]) == 1 and a["units"] == 3:
+        return 1
+    if da and not db:
+        return 2
+    if da and db and a.get("bad") and clean(b):
+        return 3
+    return None
+
+
+@pytest.mark.parametrize("which", ("symrate", "acquire"))
+def test_look_loop_reaches_the_second_trip_with_partners_that_differ(which):
+    case = pc.symrate_loop() if which == "symrate" else pc.acquire_loop()
+    n = len(case.desc)
+    assert n == pc.LOOP_DESCRIPTORS > pp.LOOK_GRID_MAX + 1 and pp.look_trips(n) == 2 and pp.look_trips(pp.LOOK_GRID_MAX) == 1
+    assert case.max_piece == 2 and len(case.protos) <= 32 and case.arena.size <= 64 << 20
+    kinds = [_pair_kind(case, c) for c in range(pc.LOOP_PAIRS)]
+    assert all(k is not None for k in kinds) and {0, 1, 2, 3} == set(kinds)
+    if which == "symrate":
+        # the invalid-block packet's model says so, and the two-piece packet is valid throughout
+        assert sm.model_record(case.protos[2]["iq"], 4)["n_valid"] == 600 - 3 and {100, 511, 599} == case.protos[2]["bad"]
+        m = sm.model_record(case.protos[0]["iq"], 4, case.protos[0]["tune"])
+        assert m["n_valid"] == m["n_blocks"] == 600
+    else:
+        assert int(case.protos[2]["parts"][0][1][8]) < am.PIECE and int(case.protos[0]["parts"][0][1][8]) == am.PIECE
+    data = np.array([d for _, d in case.uses])
+    assert 0.1 < 1 - data[pc.LOOP_PAIRS : pp.LOOK_GRID_MAX].mean() < 0.2, "every seventh of the rest has no data"
+    assert case.check(_look_written(case)) == []
+
+
+def test_look_a_halo_taken_from_the_partner_of_the_second_trip():
+    """descriptor 65535 + 4 is a first piece of three blocks; its workgroup's partner on the first trip, descriptor 4, left 512
+    valid blocks in LDS.  A fold that kept them as the halo pairs blocks 0 .. 2 with them."""
+    case = pc.symrate_loop()
+    c = 4
+    assert _pair_kind(case, c) == 0
+    a, b = case.protos[case.uses[c][0]], case.protos[case.uses[c + pp.LOOK_GRID_MAX][0]]
+    ba, bb = (sm.model_record(p["iq"], p["S"], p["tune"])["blocks"] for p in (a, b))
+    fake = {k: np.concatenate([ba[k][384:512], bb[k]]) for k in ("B", "lvl", "valid")}
+    wrong = [sm.piece_partial(fake, sm.HALO, sm.HALO + 3)]
+    i = c + pp.LOOK_GRID_MAX
+    found = case.check(_look_written(case, over={i: (wrong, b["n"], b["S"], b["tune"] is not None)}))
+    assert _places(found) == [(i, "partial"), (i, "record")], pp.messages(found)
+    assert next(f for f in found if f["where"] == "record")["field"] == "n_pairs[0]"
+
+
+@pytest.mark.parametrize("which", ("symrate", "acquire"))
+def test_look_a_second_trip_packet_skipped(which):
+    case = pc.symrate_loop() if which == "symrate" else pc.acquire_loop()
+    i = pp.LOOK_GRID_MAX + 1
+    assert case.uses[i][1]
+    found = case.check(_look_written(case, skip=(i,)))
+    assert _places(found) == [(i, "partial")] * int(case.desc["n_piece"][i]) + [(i, "record")], pp.messages(found)
+    assert all(f["got"].startswith("c3c3c3c3") for f in found)
+
+
+def test_look_acquire_partials_64_and_above_left_out_of_the_join():
+    case = pc.acquire_lengths_case(False)
+    i = len(case.desc) - 1
+    p = case.protos[i]
+    assert p["n"] == 65 * am.PIECE + 131 and len(p["parts"]) == 66
+    after = _look_written(case)
+    rec = am.join_bytes(p["parts"][:64], p["n"], p["M"], False)
+    o = case.rec_off + case.channel[i] * 224
+    after[o : o + 224] = np.frombuffer(rec, np.uint8)
+    f = _one(case, after)
+    assert (f["desc"], f["where"], f["field"]) == (i, "record", "n_valid"), f
+
+
+# ---- what the look cases reach -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("W", pc.SR_WIDTHS)
+def test_symrate_width_launch_reaches_the_edges_of_its_lane_groups(W):
+    case = pc.symrate_width(W)
+    G = 64 // W
+    Ss = sorted({p["S"] for p in case.protos})
+    assert Ss == list(pc.SR_CLASS_S[W]) and all(_sr_width(S) == W == sm.width(S) for S in Ss)
+    want = {2, 3, G - 1, G, G + 1, 4 * G - 1, 4 * G, 4 * G + 1, 255, 256, 257, 511, 512, 513, 639, 640, 641, 1025}
+    want = {b for b in want if b >= 2} - ({1025} if W >= 32 else set())
+    for S in Ss:
+        assert {p["blocks"] for p in case.protos if p["S"] == S} == want
+    assert {p["n"] - p["blocks"] * p["S"] for p in case.protos} >= {0, 3} and any(p["n"] - p["blocks"] * p["S"] == p["S"] - 1 for p in case.protos)
+    assert {p["fmt"] for p in case.protos} == set(pp.FORMATS) and {p["stride"] for p in case.protos} == {1, 7}
+    assert {p["tune"] is None for p in case.protos} == {False, True} and {bool(p["skew"]) for p in case.protos if p["stride"] == 1} == {False, True}
+    assert {len(p["parts"]) for p in case.protos} >= {1, 2} and case.arena.size <= 64 << 20
+    if W == 64:  # a ragged last turn of the widest lane group: 257 .. 1023
+        assert [S for S in Ss if S % 64] == [257, 511, 1000]
+    assert case.check(_look_written(case)) == []
+
+
+@pytest.mark.parametrize("W", (4, 32))
+def test_symrate_model_at_the_widths_nothing_had_compared_against_the_host(W):
+    """symrate_model.width and _tree at the widths of two and of five tree levels, held to psk_soft_symrate_host's index order"""
+    case = pc.symrate_width(W)
+    for p in [q for q in case.protos if q["blocks"] in (3, 257, 641)]:
+        m = sm.model_record(p["iq"], p["S"], p["tune"])
+        assert sm.record_bytes(m) == p["record"]
+        sm.assert_close(pl.symrate_host(p["S"], np.asarray(p["iq"], F32), p["tune"]), m, "S %d, %d blocks" % (p["S"], p["blocks"]))
+
+
+@pytest.mark.parametrize("W", pc.SR_WIDTHS)
+def test_symrate_validity_cases_invalidate_the_blocks_the_definition_says(W):
+    case = pc.symrate_validity(W)
+    S, G = pc.SR_VALIDITY_S[W], 64 // W
+    assert _sr_width(S) == W and (W == 1 or S % W), "the last turn is ragged"
+    seen = set()
+    for p in case.protos:
+        nb, b, pos = p["spot"]
+        m = sm.model_record(p["iq"], S, p["tune"])
+        bad = {b, b + 1} if pos == S - 1 and b + 1 < nb else {b}
+        # (the definition: a block with a non-finite sample, and the one whose first g reaches back to it; every other block --
+        # the neighbours of the same wave among them -- stays valid)
+        assert set(np.flatnonzero(~m["blocks"]["valid"])) == bad == p["bad"], p["spot"]
+        assert m["n_valid"] == nb - len(bad) and sm.record_bytes(m) == p["record"]
+        turn, sub = pc.sr_wave_slot(b, G)
+        seen |= {("sub", sub == 0, sub == G - 1), ("pos", pos)}
+        if b == nb - 1 and sub < G - 1:
+            seen.add("last block, the rest of its wave not live")
+        if pos >= (S - 1) // W * W and S % W:
+            seen.add("ragged turn")
+    assert {("pos", q) for q in {0, W - 1, min(W, S - 1), S - 1}} <= seen
+    assert ("sub", True, G == 1) in seen and ("sub", G == 1, True) in seen
+    assert G == 1 or "last block, the rest of its wave not live" in seen
+    assert W == 1 or "ragged turn" in seen
+    spots = {p["spot"] for p in case.protos}
+    assert (642, 511, S - 1) in spots and (642, 383, S - 1) in spots and {p["blocks"] for p in case.protos} == {40, 41, 642}
+    assert case.check(_look_written(case)) == []
+
+
+def test_symrate_edges_reach_subnormals_overflow_and_signed_zeros():
+    case, kinds = pc.symrate_edges()
+    assert set(kinds) == {"tiny", "huge", "zeros"} and {_sr_width(p["S"]) for p in case.protos} == {1, 4, 32, 64}
+    for k in kinds["tiny"]:
+        p = case.protos[k]
+        x = np.asarray(p["iq"], F32)
+        assert 0 < np.abs(x).max() < SUBNORMAL
+        m = sm.model_record(p["iq"], p["S"], p["tune"])
+        assert m["n_valid"] == m["n_blocks"] and m["sum_lvl"] == [0.0, 0.0], "every e underflows to zero: valid blocks, zero sums"
+    for k in kinds["huge"]:
+        p = case.protos[k]
+        m = sm.model_record(p["iq"], p["S"], p["tune"])
+        assert m["n_valid"] == 0 and not any(m["n_pairs"]) and p["record"][96:384] == bytes(288)
+    for k in kinds["zeros"]:
+        p = case.protos[k]
+        assert np.signbit(np.asarray(p["iq"], F32)[np.asarray(p["iq"], F32) == 0]).any()
+        assert sm.model_record(p["iq"], p["S"], p["tune"])["n_valid"] == p["units"]
+    assert case.check(_look_written(case)) == []
+
+
+@pytest.mark.parametrize("mixed", (False, True))
+def test_acquire_cases_reach_every_length_format_and_placement_and_the_restated_order_is_the_exact_one(mixed):
+    case = pc.acquire_lengths_case(mixed)
+    P, lens = am.PIECE, pc.acquire_lengths()
+    assert lens[-3:] == (64 * P, 64 * P + 1, 65 * P + 131) and {p["n"] for p in case.protos} == set(lens)
+    assert {(p["fmt"], p["place"]) for p in case.protos} == {(f, q) for f in pp.FORMATS for q in pc.PLACEMENTS}
+    assert {(p["fmt"], p["place"]) for p in case.protos if p["n"] > 64 * P - 1} >= {(pp.FORMAT_CF32, "aligned"), (pp.FORMAT_CS8, "strided")}
+    assert {p["M"] for p in case.protos if p["n"] >= 64 * P} == {2, 4, 8} == {p["M"] for p in case.protos if p["n"] < 64 * P}
+    assert set().union(*(p["marks"] for p in case.protos)) == {"nonfinite", "zeros", "underflow"}
+    assert {p["tune"] is not None for p in case.protos} == ({False, True} if mixed else {False}) and case.tables == mixed
+    assert max(len(p["parts"]) for p in case.protos) == 66 == case.max_piece
+    for i, d in enumerate(case.desc):  # aligned: one load takes a pair; skewed: the pair's size does not divide the address
+        p = case.protos[i]
+        pair = 2 * pp.SAMPLE_BYTES[p["fmt"]]
+        assert (int(d["src"]) % pair == 0) == (p["place"] != "skewed") or p["place"] == "strided", (i, p["place"])
+    for p in case.protos:
+        r = pl.Acquire.from_buffer_copy(p["record"])
+        m = am.model_record(p["iq"], p["M"], p["tune"])
+        am.assert_record(r, m, "n %d M %d" % (p["n"], p["M"]))
+        assert p["record"] == am.device_record(p["iq"], p["M"], p["tune"])
+        if "underflow" in p["marks"] or "nonfinite" in p["marks"]:
+            assert m["n_valid"] < p["n"]
+    assert case.check(_look_written(case)) == []
+
+
+def test_acquire_loop_packets_the_restated_order_is_the_exact_one():
+    for p in pc.acquire_loop().protos:
+        am.assert_record(pl.Acquire.from_buffer_copy(p["record"]), am.model_record(p["iq"], p["M"], p["tune"]), "n %d M %d" % (p["n"], p["M"]))
+
+
+def test_the_bound_of_a_long_acquire_packet_is_wider_than_one_float32_rounding():
+    """why the long packets are held byte for byte: at 65 P + 131 samples assert_record's bound passes a term off by a float32 ulp"""
+    p = pc.acquire_lengths_case(False).protos[-1]
+    exact, bound = am.model_record(p["iq"], p["M"])["sums"]["sum_re"][0]
+    assert bound > 2.0 ** -24 and p["n"] == 65 * am.PIECE + 131

@@ -41,7 +41,9 @@ def test_the_symbols_are_exported_and_the_record_has_its_layout():
 
 _TUNE = (0x0123456789ABCDEF, tm.step_word(-0.0137))
 # (S, samples): two blocks and one sample more; blocks that are no power of two wide; more than one piece, the halo, a ragged end
-SHAPES = ((4, 8), (4, 9), (5, 5 * 131 + 4), (8, 8 * 700 + 7), (33, 33 * 515), (100, 100 * 300 + 99), (1024, 1024 * 3 + 5))
+# (24, 200 and 257: four, 32 and 64 lanes a block in the device's fold, the last with a ragged last turn -- the model restates them)
+SHAPES = ((4, 8), (4, 9), (5, 5 * 131 + 4), (8, 8 * 700 + 7), (33, 33 * 515), (100, 100 * 300 + 99), (1024, 1024 * 3 + 5),
+          (24, 24 * 530 + 23), (200, 200 * 140 + 199), (257, 257 * 130 + 3))
 KINDS = ("signal", "nonfinite", "huge", "zeros")
 
 
