@@ -743,6 +743,119 @@ psk_soft_status psk_soft_symrate_host(uint16_t samplesPerBaud, const psk_soft_tu
 uint64_t psk_soft_symrate_bytes(void);      /* sizeof(psk_soft_symrate_t), for bindings */
 uint32_t psk_soft_symrate_piece(void);      /* blocks of one piece of the device's fold (tests: the lengths at its edges) */
 
+/* ---- where frames start: a known word in the soft symbols (psk_soft_sync_device) ----------------------------------------------
+ * The M-th-power tracker leaves the constellation turned by an unknown multiple of 2 pi / M and nothing in the four streams says
+ * where a frame starts.  A receiver slides a word it knows (unique word, preamble, sync marker) along the soft symbols: the
+ * correlation peak gives the frame start, the peak's angle the rotation.  This call does that on the GPU over rows that are
+ * already in device memory -- typically the `soft` rows of the process call enqueued on the same stream just before -- and leaves
+ * one small record per channel.
+ *
+ * The call touches no demodulator state, statistics, quality or look records and no filter or resampler history: psk_soft_peek,
+ * psk_soft_query, the state blob, warning counts, statistics and the results of every later process call are what they are
+ * without it.  The rows are read, never written.
+ *
+ * Words.  The handle keeps PSK_SOFT_SYNC_SLOTS numbered words (psk_soft_sync_define): L = 1 .. PSK_SOFT_SYNC_MAX_WORD complex
+ *   float32 points w[0] .. w[L-1], interleaved (re, im), as the caller expects them in `soft`.
+ *   Ew = the float32 sum, in index order, of w.re*w.re + w.im*w.im (each term rounded, then added; the sum starts from term 0).
+ * Input.  One psk_soft_sync_in_t per covered channel: n = n_symbols (re, im) pairs at `soft`, x[0] .. x[n-1].
+ * History.  x[-127] .. x[-1] are the channel's HISTORY: the last PSK_SOFT_SYNC_MAX_WORD - 1 soft symbols of its stream in front
+ *   of this row, oldest first; zeros with PSK_SOFT_SYNC_RESTART.  It always holds 127 symbols, whatever L.
+ * Windows.  Window p covers x[p] .. x[p + L - 1].  p runs from p0 to n - L, p0 = 0 with PSK_SOFT_SYNC_RESTART (no window starts in
+ *   front of the row) and -(L - 1) otherwise; n_windows = n - L - p0 + 1, or 0 if n - L < p0.  Every symbol position of a
+ *   continuous stream so starts exactly one window across its calls.
+ * Per window -- every operation float32, rounded once, no fused multiply-add, denormals kept; j = 0 .. L-1 in that order, the
+ *   accumulators starting from the j = 0 term:
+ *     tr = x[p+j].re*w[j].re + x[p+j].im*w[j].im     ti = x[p+j].im*w[j].re - x[p+j].re*w[j].im     te = x.re*x.re + x.im*x.im
+ *     cr += tr;  ci += ti;  e += te
+ *   then  q = cr*cr + ci*ci,  d = e*Ew,  m = q / d  (the division correctly rounded): the squared correlation over the product of
+ *   the energies, 1 for a window that is the word times any complex factor, by Cauchy-Schwarz never above 1 but for rounding.
+ *   The window is VALID when cr, ci, e, q and d are finite and d >= FLT_MIN; a HIT when it is valid and m >= threshold; the BEST
+ *   window is the valid one with the greatest m, the first such on a tie.
+ * Every term is float32 in a fixed order per window, so no reduction order enters any stored value: psk_soft_sync_host and the
+ *   device agree byte for byte, and the same symbols give the same bytes whatever the batch, the grid or the stream.
+ * After the call the history is the last 127 of (old history || row), zeros for the old history with PSK_SOFT_SYNC_RESTART.  A
+ *   short first row after a restart therefore leaves zeros in the history, and the windows of the NEXT call that reach into them
+ *   correlate against those zeros: they are the host's to drop -- it knows its stream offset (positions below -(symbols since
+ *   the restart)).  The history is not part of the state blob; psk_soft_sync_get_history / _set_history carry it. */
+#define PSK_SOFT_SYNC_MAX_WORD 128
+#define PSK_SOFT_SYNC_SLOTS    16
+#define PSK_SOFT_SYNC_HITS     16
+enum { PSK_SOFT_SYNC_RESTART = 1 };                          /* psk_soft_sync_in_t.flags */
+enum { PSK_SOFT_SYNC_DATA = 1, PSK_SOFT_SYNC_PLANNED = 128 }; /* psk_soft_sync_t.flags    */
+
+typedef struct psk_soft_sync_in {
+    const float *soft;    /* DEVICE pointer: n_symbols (re, im) pairs, 8-byte aligned; NULL: not searched                  */
+    uint64_t n_symbols;   /* below 2^30; 0: not searched                                                                   */
+    uint32_t word;        /* 1 + the slot of the word; 0: not searched                                                     */
+    uint32_t flags;       /* PSK_SOFT_SYNC_RESTART: the history in front of the row is zeros, no window starts in front    */
+    float threshold;      /* a hit is a valid window with m >= threshold; in (0, 1]                                        */
+    uint32_t pad;         /* zero                                                                                          */
+} psk_soft_sync_in_t;     /* 32 bytes */
+
+typedef struct psk_soft_sync_hit {
+    int64_t pos;          /* p, relative to the row's symbol 0: negative for a window that starts in the history           */
+    float cr, ci, e, m;   /* the window's sums and its metric                                                              */
+} psk_soft_sync_hit_t;    /* 24 bytes */
+
+typedef struct psk_soft_sync {           /* the LAST psk_soft_sync_device call that covered the channel */
+    uint64_t n_symbols, n_windows;       /* symbols of the row; windows searched                                           */
+    uint64_t n_valid, n_hits;            /* of those, valid ones; of those, hits (all of them, not only the stored ones)   */
+    psk_soft_sync_hit_t best;            /* the best window; all-zero bytes without a valid window                         */
+    psk_soft_sync_hit_t hits[PSK_SOFT_SYNC_HITS];   /* the first 16 hits in position order; unused ones all-zero bytes    */
+    uint32_t word_len, flags;            /* L; PSK_SOFT_SYNC_DATA or PSK_SOFT_SYNC_PLANNED                                 */
+    uint32_t pad[2];                     /* zero                                                                           */
+} psk_soft_sync_t;                       /* 456 bytes */
+
+/* The word of slot `slot` (0 .. PSK_SOFT_SYNC_SLOTS - 1): n = 1 .. PSK_SOFT_SYNC_MAX_WORD points (2 n floats), copied into device
+ * memory the handle owns; a searched channel names it as word = slot + 1.  Redefining a slot waits for the handle's last sync
+ * launch first.  A control-plane-only handle records the length only.  PSK_SOFT_ERR_INVALID_ARG: null pointer, slot or n out of
+ * range. */
+psk_soft_status psk_soft_sync_define(psk_soft_handle_t *h, uint32_t slot, const float *word, uint32_t n);
+
+/* The search of in[i] for channel ch0 + i.  The rows must be complete on `stream` (a process call enqueued there just before
+ * is: no synchronize lies between the two); with PSK_SOFT_OPT_DEFERRED_JOIN pending the call joins the side streams into `stream`
+ * first, exactly as the quality pass does.  The call returns without waiting.
+ * A covered channel with word == 0, soft == NULL or n_symbols == 0 is not searched: it gets an all-zero record, written in stream
+ * order, and its history does not move.  A channel the call does not cover keeps record and history.
+ * Refusals (PSK_SOFT_ERR_INVALID_ARG before anything is enqueued, any record changes or any history flips): a bad channel range,
+ * a null pointer; on a searched channel a slot >= 16 or never defined, a threshold that is NaN, <= 0 or > 1, unknown flag bits,
+ * a non-zero pad, a `soft` that is not 8-byte aligned, n_symbols >= 2^30.
+ * How: two launches on `stream`.  The fold's grid is pieces x channels; a piece is a fixed number of windows
+ * (psk_soft_sync_piece), staged with the L - 1 symbols behind them and the word in LDS, consecutive lanes taking consecutive
+ * windows; each piece leaves its counts, its best and its first 16 hits (compacted in position order by ballot and prefix
+ * count: no atomics decide an order), and piece 0 writes the channel's new history into its other slot.  The join, one wave per
+ * channel, walks the pieces in order and writes the record.  The histories flip when the whole call returned PSK_SOFT_OK.
+ * A control-plane-only handle checks the arguments, then fills in n_symbols, n_windows, word_len and flags =
+ * PSK_SOFT_SYNC_PLANNED for the searched channels, everything else zero. */
+psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in /* [nch] */,
+                                     void *stream);
+/* waits like psk_soft_get_quality does and copies the records of [ch0, ch0+nch) out */
+psk_soft_status psk_soft_get_sync(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_sync_t *rec /* [nch] */);
+/* the history of a channel -- 127 (re, im) pairs, oldest first -- read or replaced behind the last sync launch (zeros before the
+ * first; a control-plane-only handle keeps zeros) */
+psk_soft_status psk_soft_sync_get_history(psk_soft_handle_t *h, uint32_t ch, float *out /* [254] */);
+psk_soft_status psk_soft_sync_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in /* [254] */);
+
+/* psk_soft_sync_derive (host only, pure, doubles; C atan2, rint, sqrt) of one hit, for constelationSize M, word length L and the
+ * word's Ew:  angle = atan2(ci, cr);  rotation = rint(angle M / (2 pi)) mod M, in 0 .. M-1: the multiple of 2 pi / M by which the
+ * symbols are turned against the word;  residual = angle - rint(angle M / (2 pi)) 2 pi / M, within +-pi / M;  amplitude =
+ * sqrt(e / L), the rms symbol amplitude of the window;  metric = (cr*cr + ci*ci) / (e * Ew), the hit's m formed again in doubles.  An all-zero hit gives NaN everywhere and rotation -1.  A
+ * different rotation at two frames of one stream is a cycle slip of the tracker between them.  The positions are relative to each
+ * call's row: the host keeps the absolute symbol count (add n_symbols of every call).
+ * PSK_SOFT_ERR_INVALID_ARG: null pointer, M other than 2, 4, 8, L outside 1 .. 128. */
+typedef struct psk_soft_sync_derived { double angle, residual, amplitude, metric; int32_t rotation, pad; } psk_soft_sync_derived_t;
+psk_soft_status psk_soft_sync_derive(const psk_soft_sync_hit_t *hit, uint16_t constelationSize, uint32_t word_len, float Ew,
+                                     psk_soft_sync_derived_t *out);
+/* host only, pure: the definition for one row on the host.  hist_in NULL or PSK_SOFT_SYNC_RESTART: a history of zeros; hist_out
+ * (may be NULL) receives the history behind the row; *rec and hist_out are byte for byte what the device writes (flags =
+ * PSK_SOFT_SYNC_DATA).  n == 0 gives the zero record and hist_out = the history in front.  Refuses what the entry refuses of
+ * L, threshold, flags and n. */
+psk_soft_status psk_soft_sync_host(const float *word, uint32_t L, float threshold, uint32_t flags, const float *hist_in /* [254] or NULL */,
+                                   const float *soft, uint64_t n, psk_soft_sync_t *rec, float *hist_out /* [254] or NULL */);
+uint64_t psk_soft_sync_bytes(void);         /* sizeof(psk_soft_sync_t), for bindings */
+uint64_t psk_soft_sync_in_bytes(void);      /* sizeof(psk_soft_sync_in_t), for bindings */
+uint32_t psk_soft_sync_piece(void);         /* windows of one piece of the device's fold (tests: the counts at its edges) */
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

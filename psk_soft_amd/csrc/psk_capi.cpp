@@ -23,6 +23,7 @@
 
 #include "psk_acquire.h"
 #include "psk_symrate.h"
+#include "psk_sync.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -672,6 +673,16 @@ struct psk_soft_handle {
     psk_soft_symrate_t *d_symrate = nullptr;
     std::vector<psk_soft_symrate_t> symrate_dry;
     PassRing<psk::SymrateDesc, psk::SymratePartial, kAcquireSlots> spass;
+    // psk_soft_sync_device: the words of every slot (kSyncSlots x kSyncMaxWord float2, allocated at the first psk_soft_sync_define),
+    // their lengths (0: never defined) and energies Ew; one record per channel, allocated (zeros) at the first call -- a
+    // control-plane-only handle keeps them on the host --; the history of every channel, two slots of 127 float2 in 1 KiB each
+    float *d_sync_words = nullptr;
+    uint32_t sync_len[psk::kSyncSlots] = {};
+    float sync_ew[psk::kSyncSlots] = {};
+    psk_soft_sync_t *d_sync = nullptr;
+    std::vector<psk_soft_sync_t> sync_dry;
+    PassRing<psk::SyncDesc, psk::SyncPartial, kAcquireSlots> ypass;
+    HistoryBank sync_hist{"sync history", psk::kSyncHistSlotFloats, 2u * psk::kSyncHistSlotFloats, 2u * psk::kSyncHist};
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -2188,6 +2199,10 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_acquire) (void)hipFree(h->d_acquire);
         h->spass.free();
         if (h->d_symrate) (void)hipFree(h->d_symrate);
+        h->ypass.free();
+        if (h->d_sync) (void)hipFree(h->d_sync);
+        if (h->d_sync_words) (void)hipFree(h->d_sync_words);
+        h->sync_hist.free();
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
         if (h->d_test) (void)hipFree(h->d_test);
@@ -3701,6 +3716,274 @@ psk_soft_status psk_soft_symrate_derive(const psk_soft_symrate_t *rec, psk_soft_
     d->mean_level = rec->sum_lvl[z] / ((double)rec->n_valid * (double)rec->samplesPerBaud);
     d->detector = z;
     d->lags_used = used;
+    return PSK_SOFT_OK;
+}
+
+// ---- psk_soft_sync_device: a known word in the soft symbols (include/psk_soft_hip.h, psk_sync.hip) ----
+// The second reduction behind a call, after the quality pass: a fold over pieces of kSyncPiece windows and a join per channel on
+// the caller's stream, one record per covered channel; a pass ring of its own, a history bank like the filter's.  Nothing of the
+// control plane or of the demodulator's state is read, nothing is written but the records and the histories.
+psk_soft_status psk_soft_sync_define(psk_soft_handle_t *h, uint32_t slot, const float *word, uint32_t n)
+{
+    if (!h || !word || slot >= psk::kSyncSlots || !n || n > psk::kSyncMaxWord)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_define: null pointer, a slot above 15 or a word length outside 1 .. 128");
+    if (!h->dry) {
+        PSK_HIP(hipSetDevice(h->device));
+        if (!h->d_sync_words)
+            PSK_HIP(hipMalloc((void **)&h->d_sync_words, sizeof(float) * 2u * psk::kSyncSlots * psk::kSyncMaxWord));
+        PSK_TRY(h->sync_hist.wait());  // (no launch is still reading the slot)
+        PSK_HIP(hipMemcpy(h->d_sync_words + (size_t)2u * psk::kSyncMaxWord * slot, word, sizeof(float) * 2u * n, hipMemcpyHostToDevice));
+        h->sync_ew[slot] = psk::sy_word_energy(word, n);
+    }
+    h->sync_len[slot] = n;  // (a control-plane-only handle checks and counts: the length is all it needs)
+    return PSK_SOFT_OK;
+}
+
+// a channel the call searches
+static bool sync_searched(const psk_soft_sync_in_t &k) { return k.word != 0u && k.soft != nullptr && k.n_symbols != 0u; }
+static bool sync_threshold_ok(float t) { return t > 0.0f && t <= 1.0f; }  // (false for NaN)
+
+// the records of a handle, zeros until a call writes one
+static psk_soft_status sync_records_ensure(psk_soft_handle *h)
+{
+    if (h->dry) {
+        if (h->sync_dry.empty())
+            h->sync_dry.assign(h->nch, psk_soft_sync_t{});
+        return PSK_SOFT_OK;
+    }
+    if (h->d_sync)
+        return PSK_SOFT_OK;
+    psk_soft_sync_t *p = nullptr;
+    const size_t bytes = sizeof(psk_soft_sync_t) * (size_t)h->nch;
+    PSK_HIP(hipMalloc((void **)&p, bytes));
+    if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(p);  // (the memset is through before a launch on any stream writes a record)
+        return fail(PSK_SOFT_ERR_HIP, "sync records: hipMemset failed");
+    }
+    h->d_sync = p;
+    return PSK_SOFT_OK;
+}
+
+static psk_soft_status sync_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in, hipStream_t stream);
+
+psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in, void *stream_v)
+{
+    if (!h || !in || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_device: bad arguments");
+    // the refusals, before anything is enqueued, any record changes or any history flips
+    for (uint32_t i = 0; i < nch; i++) {
+        const psk_soft_sync_in_t &k = in[i];
+        if (!sync_searched(k))
+            continue;
+        const char *what = nullptr;
+        if (k.word > psk::kSyncSlots || !h->sync_len[k.word - 1u])
+            what = "a word slot above 15 or never defined (psk_soft_sync_define)";
+        else if (!sync_threshold_ok(k.threshold))
+            what = "a threshold that is NaN, <= 0 or > 1";
+        else if (k.flags & ~(uint32_t)PSK_SOFT_SYNC_RESTART)
+            what = "unknown flag bits";
+        else if (k.pad)
+            what = "pad must be zero";
+        else if ((uintptr_t)k.soft & 7u)
+            what = "soft must be 8-byte aligned";
+        else if (k.n_symbols >= psk::kSyncMaxN)
+            what = "2^30 symbols or more";
+        if (what) {
+            char buf[160];
+            std::snprintf(buf, sizeof buf, "psk_soft_sync_device: channel %u: %s", ch0 + i, what);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+    }
+    PSK_TRY(sync_records_ensure(h));
+    if (h->dry) {
+        for (uint32_t i = 0; i < nch; i++) {
+            psk_soft_sync_t r = {};
+            if (sync_searched(in[i])) {
+                int64_t p0;
+                r.word_len = h->sync_len[in[i].word - 1u];
+                r.n_symbols = in[i].n_symbols;
+                r.n_windows = psk::sync_windows(in[i].n_symbols, r.word_len, (in[i].flags & PSK_SOFT_SYNC_RESTART) != 0, &p0);
+                r.flags = PSK_SOFT_SYNC_PLANNED;
+            }
+            h->sync_dry[ch0 + i] = r;
+        }
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: the rows must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    PSK_TRY(h->sync_hist.ensure(h->nch));
+    const psk_soft_status st = sync_enqueue(h, ch0, nch, in, stream);
+    if (st == PSK_SOFT_OK)  // (the whole call went through: the new histories are the channels')
+        for (uint32_t i = 0; i < nch; i++)
+            if (sync_searched(in[i]))
+                h->sync_hist.flip(ch0 + i);
+    return st;
+}
+
+// the fold and the join of a sync call whose arguments have passed
+static psk_soft_status sync_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in, hipStream_t stream)
+{
+    auto &q = h->ypass.next();
+    PSK_TRY(h->ypass.claim(q, h->nch));
+    uint64_t n_part = 0;
+    uint32_t max_piece = 0;
+    for (uint32_t i = 0; i < nch; i++) {
+        psk::SyncDesc &d = q.h_desc[i];
+        d = psk::SyncDesc{};
+        d.channel = ch0 + i;
+        const psk_soft_sync_in_t &k = in[i];
+        if (!sync_searched(k))
+            continue;  // (its zero record; the history stays)
+        const uint32_t slot = k.word - 1u;
+        const bool restart = (k.flags & PSK_SOFT_SYNC_RESTART) != 0;
+        d.soft = k.soft;
+        d.word = h->d_sync_words + (size_t)2u * psk::kSyncMaxWord * slot;
+        d.hist_in = h->sync_hist.in(ch0 + i), d.hist_out = h->sync_hist.out(ch0 + i);
+        d.n = k.n_symbols;
+        d.L = h->sync_len[slot];
+        d.n_windows = psk::sync_windows(d.n, d.L, restart, &d.p0);
+        d.flags = psk::kSyncData | (restart ? psk::kSyncRestart : 0u);
+        d.threshold = k.threshold, d.Ew = h->sync_ew[slot];
+        // (a row without a window still has a piece: its workgroup writes the history)
+        const uint32_t pieces = d.n_windows ? (d.n_windows + psk::kSyncPiece - 1u) / psk::kSyncPiece : 1u;
+        if (n_part + pieces > 0x7fffffffull)
+            return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_sync_device: too many symbols in one call");
+        d.part0 = (uint32_t)n_part;
+        d.n_piece = pieces;
+        n_part += pieces;
+        max_piece = pieces > max_piece ? pieces : max_piece;
+    }
+    PSK_TRY(h->ypass.grow(q, n_part));
+    PSK_TRY(h->ypass.upload(q, ch0, nch, stream));
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = covered channels, tiles = pieces)
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_part, 0, 0, h->slot, stream); };
+    auto enqueue = [&]() -> psk_soft_status {
+        PSK_HIP(mark("sync_fold"));
+        PSK_HIP(psk::launch_sync_fold(q.d_desc, nch, max_piece, q.d_part, stream));
+        PSK_HIP(mark("sync_join"));
+        PSK_HIP(psk::launch_sync_join(q.d_desc, nch, q.d_part, h->d_sync, stream));
+        PSK_TRY(h->sync_hist.record(stream));
+        return PSK_SOFT_OK;
+    };
+    return h->ypass.finish(q, stream, enqueue());
+}
+
+uint64_t psk_soft_sync_bytes(void) { return sizeof(psk_soft_sync_t); }
+uint64_t psk_soft_sync_in_bytes(void) { return sizeof(psk_soft_sync_in_t); }
+uint32_t psk_soft_sync_piece(void) { return psk::kSyncPiece; }
+static_assert(sizeof(psk_soft_sync_t) == 456 && sizeof(psk_soft_sync_in_t) == 32 && sizeof(psk_soft_sync_hit_t) == 24, "include/psk_soft_hip.h states the sizes");
+
+psk_soft_status psk_soft_get_sync(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, psk_soft_sync_t *rec)
+{
+    if (!h || !rec || !nch || (uint64_t)ch0 + nch > h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_sync: bad arguments");
+    if (h->dry ? h->sync_dry.empty() : !h->d_sync) {  // (no call yet: the records are zeros)
+        std::memset(rec, 0, sizeof(psk_soft_sync_t) * nch);
+        return PSK_SOFT_OK;
+    }
+    if (h->dry) {
+        std::memcpy(rec, h->sync_dry.data() + ch0, sizeof(psk_soft_sync_t) * nch);
+        return PSK_SOFT_OK;
+    }
+    const psk_soft_status st = psk_soft_synchronize(h);
+    if (st != PSK_SOFT_OK)
+        return st;
+    PSK_TRY(h->ypass.wait());
+    PSK_HIP(hipMemcpy(rec, h->d_sync + ch0, sizeof(psk_soft_sync_t) * nch, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+// the history of a channel: its current slot, behind the last sync launch
+psk_soft_status psk_soft_sync_get_history(psk_soft_handle_t *h, uint32_t ch, float *out)
+{
+    if (!h || !out || ch >= h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_get_history: bad arguments");
+    return history_get(h, h->sync_hist, ch, out);
+}
+
+psk_soft_status psk_soft_sync_set_history(psk_soft_handle_t *h, uint32_t ch, const float *in)
+{
+    if (!h || !in || ch >= h->nch)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_set_history: bad arguments");
+    return history_set(h, h->sync_hist, ch, in);
+}
+
+psk_soft_status psk_soft_sync_host(const float *word, uint32_t L, float threshold, uint32_t flags, const float *hist_in, const float *soft,
+                                   uint64_t n, psk_soft_sync_t *rec, float *hist_out)
+{
+    if (!word || !rec || (n && !soft))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_host: null pointer");
+    if (!L || L > psk::kSyncMaxWord || !sync_threshold_ok(threshold) || (flags & ~(uint32_t)PSK_SOFT_SYNC_RESTART) || n >= psk::kSyncMaxN)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_host: a word length outside 1 .. 128, a threshold that is NaN, <= 0 or > 1, flags, or 2^30 symbols or more");
+    *rec = psk_soft_sync_t{};
+    const bool restart = (flags & PSK_SOFT_SYNC_RESTART) != 0;
+    float hist[2u * psk::kSyncHist] = {};
+    if (hist_in && !(restart && n))  // (a row without symbols is not searched: its history does not move)
+        std::memcpy(hist, hist_in, sizeof hist);
+    if (!n) {
+        if (hist_out)
+            std::memcpy(hist_out, hist, sizeof hist);
+        return PSK_SOFT_OK;
+    }
+    // component c (0 re, 1 im) of x[g], g >= -127
+    auto x = [&](int64_t g, int c) { return g < 0 ? hist[2 * (g + (int64_t)psk::kSyncHist) + c] : soft[2 * g + c]; };
+    const float Ew = psk::sy_word_energy(word, L);
+    int64_t p0;
+    rec->n_symbols = n;
+    rec->n_windows = psk::sync_windows(n, L, restart, &p0);
+    rec->word_len = L, rec->flags = PSK_SOFT_SYNC_DATA;
+    bool has_best = false;
+    for (uint64_t k = 0; k < rec->n_windows; k++) {
+        const int64_t p = p0 + (int64_t)k;
+        float cr = 0.0f, ci = 0.0f, e = 0.0f, m;
+        for (uint32_t j = 0; j < L; j++) {
+            const float xr = x(p + j, 0), xi = x(p + j, 1);
+            psk::sy_step(j == 0, xr, xi, psk::sy_energy(xr, xi), word[2u * j], word[2u * j + 1u], &cr, &ci, &e);
+        }
+        if (!psk::sy_metric(cr, ci, e, Ew, &m))
+            continue;
+        rec->n_valid++;
+        psk_soft_sync_hit_t hit = {};
+        hit.pos = p, hit.cr = cr, hit.ci = ci, hit.e = e, hit.m = m;
+        if (!has_best || m > rec->best.m)
+            rec->best = hit, has_best = true;
+        if (m >= threshold) {
+            if (rec->n_hits < psk::kSyncHits)
+                rec->hits[rec->n_hits] = hit;
+            rec->n_hits++;
+        }
+    }
+    if (hist_out) {
+        float nh[2u * psk::kSyncHist];
+        for (int64_t j = 0; j < (int64_t)psk::kSyncHist; j++)
+            for (int c = 0; c < 2; c++) nh[2 * j + c] = x((int64_t)n - (int64_t)psk::kSyncHist + j, c);
+        std::memcpy(hist_out, nh, sizeof nh);
+    }
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_sync_derive(const psk_soft_sync_hit_t *hit, uint16_t constelationSize, uint32_t word_len, float Ew,
+                                     psk_soft_sync_derived_t *out)
+{
+    const uint32_t M = constelationSize;
+    if (!hit || !out || (M != 2 && M != 4 && M != 8) || !word_len || word_len > psk::kSyncMaxWord)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_sync_derive: null pointer, a constelationSize other than 2, 4, 8 or a word length outside 1 .. 128");
+    const double nan = std::nan(""), two_pi = 2.0 * 3.14159265358979323846;
+    *out = psk_soft_sync_derived_t{};
+    out->angle = out->residual = out->amplitude = out->metric = nan;
+    out->rotation = -1;
+    const psk_soft_sync_hit_t zero = {};
+    if (!std::memcmp(hit, &zero, sizeof zero))
+        return PSK_SOFT_OK;
+    const double cr = hit->cr, ci = hit->ci, e = hit->e;
+    const double angle = std::atan2(ci, cr), turns = std::rint(angle * M / two_pi);
+    out->angle = angle;
+    out->rotation = (int32_t)(((int64_t)turns % (int64_t)M + (int64_t)M) % (int64_t)M);
+    out->residual = angle - turns * two_pi / M;
+    out->amplitude = std::sqrt(e / (double)word_len);
+    out->metric = (cr * cr + ci * ci) / (e * (double)Ew);
     return PSK_SOFT_OK;
 }
 

@@ -230,6 +230,59 @@ class SymrateDerived(ctypes.Structure):
     ]
 
 
+SYNC_RESTART = 1  # SyncIn.flags
+SYNC_DATA, SYNC_PLANNED = 1, 128  # SyncRecord.flags
+SYNC_MAX_WORD, SYNC_SLOTS, SYNC_HITS = 128, 16, 16
+SYNC_HISTORY_FLOATS = 2 * (SYNC_MAX_WORD - 1)
+
+
+class SyncIn(ctypes.Structure):
+    """psk_soft_sync_in_t: one channel of a sync_device call -- a DEVICE pointer to n_symbols (re, im) pairs, word = 1 + the slot
+    of the word (0: not searched), flags (SYNC_RESTART), the threshold of a hit."""
+
+    _fields_ = [
+        ("soft", ctypes.c_void_p),
+        ("n_symbols", ctypes.c_uint64),
+        ("word", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("threshold", ctypes.c_float),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+class SyncHit(ctypes.Structure):
+    """psk_soft_sync_hit_t: a window -- its position relative to the row's symbol 0, its sums and its metric."""
+
+    _fields_ = [("pos", ctypes.c_int64), ("cr", ctypes.c_float), ("ci", ctypes.c_float), ("e", ctypes.c_float), ("m", ctypes.c_float)]
+
+
+class SyncRecord(ctypes.Structure):
+    """psk_soft_sync_t: the record of the last sync_device call that covered a channel."""
+
+    _fields_ = [
+        ("n_symbols", ctypes.c_uint64),
+        ("n_windows", ctypes.c_uint64),
+        ("n_valid", ctypes.c_uint64),
+        ("n_hits", ctypes.c_uint64),
+        ("best", SyncHit),
+        ("hits", SyncHit * SYNC_HITS),
+        ("word_len", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 2),
+    ]
+
+
+class SyncDerived(ctypes.Structure):
+    _fields_ = [
+        ("angle", ctypes.c_double),
+        ("residual", ctypes.c_double),
+        ("amplitude", ctypes.c_double),
+        ("metric", ctypes.c_double),
+        ("rotation", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_hip.h declares
@@ -288,6 +341,16 @@ EXPORTS = (
     "psk_soft_symrate_host",
     "psk_soft_symrate_bytes",
     "psk_soft_symrate_piece",
+    "psk_soft_sync_define",
+    "psk_soft_sync_device",
+    "psk_soft_get_sync",
+    "psk_soft_sync_get_history",
+    "psk_soft_sync_set_history",
+    "psk_soft_sync_derive",
+    "psk_soft_sync_host",
+    "psk_soft_sync_bytes",
+    "psk_soft_sync_in_bytes",
+    "psk_soft_sync_piece",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -413,6 +476,19 @@ def load():
     L.psk_soft_symrate_bytes.restype = u64
     L.psk_soft_symrate_piece.argtypes = []
     L.psk_soft_symrate_piece.restype = u32
+    L.psk_soft_sync_define.argtypes = [vp, u32, vp, u32]
+    L.psk_soft_sync_device.argtypes = [vp, u32, u32, ctypes.POINTER(SyncIn), vp]
+    L.psk_soft_get_sync.argtypes = [vp, u32, u32, ctypes.POINTER(SyncRecord)]
+    L.psk_soft_sync_get_history.argtypes = [vp, u32, vp]
+    L.psk_soft_sync_set_history.argtypes = [vp, u32, vp]
+    L.psk_soft_sync_derive.argtypes = [ctypes.POINTER(SyncHit), ctypes.c_uint16, u32, ctypes.c_float, ctypes.POINTER(SyncDerived)]
+    L.psk_soft_sync_host.argtypes = [vp, u32, ctypes.c_float, u32, vp, vp, u64, ctypes.POINTER(SyncRecord), vp]
+    L.psk_soft_sync_bytes.argtypes = []
+    L.psk_soft_sync_bytes.restype = u64
+    L.psk_soft_sync_in_bytes.argtypes = []
+    L.psk_soft_sync_in_bytes.restype = u64
+    L.psk_soft_sync_piece.argtypes = []
+    L.psk_soft_sync_piece.restype = u32
     _lib = L
     return L
 
@@ -623,6 +699,51 @@ def symrate_host(S, iq, tune=None):
 def symrate_piece():
     """Blocks of one piece of the device's fold (psk_soft_symrate_piece)."""
     return int(load().psk_soft_symrate_piece())
+
+
+def sync_host(word, threshold, soft, flags=0, hist_in=None):
+    """psk_soft_sync_host: the search of one row on the host.  word and soft are interleaved float32 (re, im) (an odd last element
+    is dropped), hist_in None (zeros) or 254 floats.  Returns (SyncRecord, the history behind the row: 254 float32)."""
+    w = np.ascontiguousarray(word, np.float32)
+    x = np.ascontiguousarray(soft, np.float32)
+    hin = None
+    if hist_in is not None:
+        hin = np.ascontiguousarray(hist_in, np.float32)
+        if hin.size != SYNC_HISTORY_FLOATS:
+            raise ValueError("a history is 127 complex symbols: 254 floats")
+    rec = SyncRecord()
+    hout = np.zeros(SYNC_HISTORY_FLOATS, np.float32)
+    _check(load().psk_soft_sync_host(w.ctypes.data if w.size else None, w.size // 2, float(threshold), int(flags),
+                                     hin.ctypes.data if hin is not None else None, x.ctypes.data if x.size else None, x.size // 2,
+                                     ctypes.byref(rec), hout.ctypes.data))
+    return rec, hout
+
+
+def sync_word_energy(word):
+    """Ew of a word: the float32 sum, in index order, of re*re + im*im (what sync_derive takes)."""
+    w = np.ascontiguousarray(word, np.float32).reshape(-1, 2)
+    s = np.float32(0)
+    for j, (a, b) in enumerate(w):
+        t = np.float32(np.float32(a * a) + np.float32(b * b))
+        s = t if j == 0 else np.float32(s + t)
+    return float(s)
+
+
+def sync_derive(hit, M, L, Ew):
+    """psk_soft_sync_derive of one SyncHit: dict of angle, residual, amplitude, metric (NaN for an all-zero hit) and rotation
+    (0 .. M-1; -1 for an all-zero hit)."""
+    d = SyncDerived()
+    _check(load().psk_soft_sync_derive(ctypes.byref(hit), int(M), int(L), float(Ew), ctypes.byref(d)))
+    return {k: getattr(d, k) for k, _ in SyncDerived._fields_ if k != "pad"}
+
+
+def sync_piece():
+    """Windows of one piece of the device's fold (psk_soft_sync_piece)."""
+    return int(load().psk_soft_sync_piece())
+
+
+def _sync_in(s):
+    return s if isinstance(s, SyncIn) else SyncIn(*s)
 
 
 class Handle:
@@ -1013,6 +1134,43 @@ class Handle:
         """symrate_device, then one dict per covered channel: the derived values (symrate_derive) of its record."""
         self.symrate_device(ch0, pkts, strides, tunes, stream)
         return [symrate_derive(r) for r in self.symrate_records(ch0, len(pkts))]
+
+    def sync_define(self, slot, word):
+        """psk_soft_sync_define: the word (1 .. 128 points, interleaved float32 (re, im), copied) of slot `slot` (0 .. 15); a
+        channel names it as SyncIn.word = slot + 1."""
+        w = np.ascontiguousarray(word, np.float32)
+        if w.size % 2:
+            raise ValueError("a word is (re, im) pairs")
+        _check(self._L.psk_soft_sync_define(self._h, int(slot), w.ctypes.data if w.size else None, w.size // 2))
+
+    def sync_device(self, ch0, ins, stream=None):
+        """The search of a known word in the soft rows of [ch0, ch0 + len(ins)) (psk_soft_sync_device): leaves a SyncRecord per
+        covered channel and moves the searched channels' histories; touches no demodulator state.  ins: a ctypes SyncIn array
+        or a sequence of SyncIn / (soft, n_symbols, word, flags, threshold).  The rows are DEVICE memory, complete on `stream`
+        -- the soft rows of a process_device call enqueued there just before are."""
+        if not isinstance(ins, ctypes.Array):
+            ins = (SyncIn * len(ins))(*[_sync_in(s) for s in ins])
+        _check(self._L.psk_soft_sync_device(self._h, ch0, len(ins), ins, ctypes.c_void_p(stream or 0)))
+
+    def sync_records(self, ch0=0, nch=None):
+        """The raw SyncRecord records of [ch0, ch0+nch) (psk_soft_get_sync), a ctypes array."""
+        nch = self.n_channels - ch0 if nch is None else nch
+        arr = (SyncRecord * nch)()
+        _check(self._L.psk_soft_get_sync(self._h, ch0, nch, arr))
+        return arr
+
+    def sync_history(self, ch):
+        """The sync history of channel ch (psk_soft_sync_get_history): 254 float32, 127 (re, im) pairs, oldest first."""
+        out = np.zeros(SYNC_HISTORY_FLOATS, np.float32)
+        _check(self._L.psk_soft_sync_get_history(self._h, int(ch), out.ctypes.data))
+        return out
+
+    def set_sync_history(self, ch, floats):
+        """psk_soft_sync_set_history: replace the sync history of channel ch."""
+        x = np.ascontiguousarray(floats, np.float32)
+        if x.size != SYNC_HISTORY_FLOATS:
+            raise ValueError("a history is 127 complex symbols: 254 floats")
+        _check(self._L.psk_soft_sync_set_history(self._h, int(ch), x.ctypes.data))
 
     def export_state(self, ch):
         n = int(self._L.psk_soft_state_bytes(self._h))
