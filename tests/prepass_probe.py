@@ -17,7 +17,12 @@ The two looks (psk_symrate.hip, psk_acquire.hip; the shim links psk_symrate.o an
 LookCase at the end of this file lays out the sources, a region of partials and a region of records -- memory the handle
 allocates in the product, which tests/row_guards.py cannot fence --, launches fold and join once each, and expects the bytes
 of symrate_model.partials / join_bytes and acquire_model.device_partials / join_bytes: every partial, every record, and poison
-in every partial's pad, in every slot no descriptor owns and in the guards."""
+in every partial's pad, in every slot no descriptor owns and in the guards.
+
+The word search (psk_sync.hip; the shim links psk_sync.o) closes the file: a SyncCase holds the rows, the words, both history
+slots of every searched descriptor, the partials and the records, launches the fold, the join or both, and expects of every
+partial the members sync_model.partial_writes lists -- NaN poison in the others --, sync_model.join_bytes of the partials in the
+record, the model's history in hist_out, poison in its pad, and everything else as it went up."""
 import ctypes
 import math
 import os
@@ -28,6 +33,7 @@ from tests import acquire_model as am
 from tests import fir_model as fm
 from tests import resample_model as rm
 from tests import symrate_model as sm
+from tests import sync_model as ym
 from tests import tune_model as tm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,11 +74,16 @@ SYMRATE_REC = np.dtype([("n_samples", _U8), ("n_used", _U8), ("n_blocks", _U8), 
                         ("sum_im", _F8, (2, 8)), ("sum_pow", _F8, 2), ("sum_lvl", _F8, 2), ("samplesPerBaud", _U2), ("flags", _U1), ("pad", _U1, 5)])
 ACQUIRE_REC = np.dtype([("n_samples", _U8), ("n_valid", _U8), ("n_pairs", _U8, 8), ("sum_re", _F8, 8), ("sum_im", _F8, 8), ("sum_e", _F8),
                         ("constelationSize", _U2), ("flags", _U1), ("pad", _U1, 5)])
+# the word search (psk_sync.h; the partial and the record: tests/sync_model.py)
+SYNC_DESC = np.dtype([("soft", _U8), ("word", _U8), ("hist_in", _U8), ("hist_out", _U8), ("n", _U8), ("p0", "<i8"), ("n_windows", _U4), ("part0", _U4),
+                      ("n_piece", _U4), ("channel", _U4), ("L", _U4), ("flags", _U4), ("threshold", "<f4"), ("Ew", "<f4")])
 # in the order of psk_prepass_probe_sizeof
-MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE, FIR, SYMRATE_DESC, SYMRATE_PART, ACQUIRE_DESC, ACQUIRE_PART, SYMRATE_REC, ACQUIRE_REC)
+MIRRORS = (GROUP, CHAN, SINGLE, TUNE, RESAMPLE, FIR, SYMRATE_DESC, SYMRATE_PART, ACQUIRE_DESC, ACQUIRE_PART, SYMRATE_REC, ACQUIRE_REC,
+           SYNC_DESC, ym.PART_DTYPE, ym.RECORD_DTYPE)
 CONSTANTS = ("resample_piece", "resample_inputs", "gather_tile", "gather_min_group", "tune_table_floats", "fir_window", "fir_max_taps",
              "fir_hist_slot_floats", "symrate_piece", "symrate_halo", "symrate_threads", "symrate_min_s", "symrate_max_s", "symrate_max_blocks",
-             "acquire_piece", "acquire_halo", "acquire_threads")
+             "acquire_piece", "acquire_halo", "acquire_threads", "sync_piece", "sync_threads", "sync_hist", "sync_hist_slot_floats",
+             "sync_max_word", "sync_hits")
 LOOK_DATA, LOOK_TUNED = 1, 2  # PSK_SOFT_SR_DATA / PSK_SOFT_A_DATA, PSK_SOFT_SR_TUNED / PSK_SOFT_A_TUNED
 FIR_HIST_BYTES = 8 * fm.HIST  # the payload of a history slot of the filter: 127 float2
 
@@ -97,7 +108,8 @@ def load():
                            ("psk_prepass_probe_resample", [vp, u64, vp, u32, u64]), ("psk_prepass_probe_fir_piece", [i]),
                            ("psk_prepass_probe_fir", [vp, u64, vp, u32, u64]),
                            ("psk_prepass_probe_symrate", [vp, u64, vp, u32, u32, u64, u64]),
-                           ("psk_prepass_probe_acquire", [vp, u64, vp, u32, u32, u64, u64, i])):
+                           ("psk_prepass_probe_acquire", [vp, u64, vp, u32, u32, u64, u64, i]),
+                           ("psk_prepass_probe_sync", [vp, u64, vp, u32, u32, u64, u64, i])):
             getattr(L, name).argtypes, getattr(L, name).restype = args, i
         _lib = L
     return _lib
@@ -712,3 +724,219 @@ class LookCase(_Case):
         fn = load().psk_prepass_probe_symrate if self.kind == "symrate" else load().psk_prepass_probe_acquire
         extra = () if self.kind == "symrate" else (1 if self.tables else 0,)
         return _launch(self.kind, fn, self.image, self.desc.ctypes.data, len(self.desc), self.max_piece, self.part_off, self.rec_off, *extra)
+
+
+# ---- the word search: fold and join (psk_sync.hip) -----------------------------------------------------------------------------------
+
+SYNC_DATA, SYNC_RESTART = 1, 2  # SyncDesc::flags (psk_sync.h): kSyncData, kSyncRestart
+SYNC_SLOT_BYTES, SYNC_HIST_BYTES = 1024, 8 * ym.HIST  # a history slot, and its payload: 127 float2
+SYNC_WORD_BYTES = 8 * ym.MAX_WORD  # a word slot: 128 float2
+NAN_WORD = 0x7FC00ABC  # a quiet NaN as poison: what must not be read shows in whatever is made of it
+JOIN_CHUNK = 64  # partials the join takes a trip
+
+
+def nan_poison(nbytes):
+    assert nbytes % 4 == 0
+    return np.frombuffer(np.full(nbytes // 4, NAN_WORD, "<u4").tobytes(), np.uint8)
+
+
+def sync_grid(n_desc, max_piece):
+    """Workgroups per channel, as front_grid_y (psk_front_src.h) has it for psk::launch_sync_fold: min(pieces of the channel
+    with the most, ceil(2048 / n_desc)), at least 1, at most 65535.  2048 and the bounds are that function's literals."""
+    per = min(max_piece, -(-2048 // n_desc))
+    return max(1, min(per, 65535))
+
+
+def sync_walk(n_piece, per):
+    """the pieces each of the `per` workgroups of a channel takes (psk_sync_fold_kernel: p = blockIdx.x, p += gridDim.x)"""
+    return [list(range(y, n_piece, per)) for y in range(per)]
+
+
+class SyncCase(_Case):
+    """One launch of the word search's fold, of its join, or of both (which: bit 0 the fold, bit 1 the join).  protos: the
+    distinct rows, modelled once -- dicts of word (2 L floats), thr, x (2 n floats), restart, hist (254 floats in front of a
+    continued row; None: zeros), skew (0 or 8 bytes past a line) --, or SYNTHETIC ones for the join alone: dicts of parts (partials
+    as tests/sync_model.py has them), n, n_windows, L; their partials are in the arena before the launch, NaN poison in every
+    member partial_writes does not list.  uses: one (proto, data) per descriptor; a descriptor without `data` is all zeros except
+    `channel`, as sync_enqueue (psk_capi.cpp) builds it: it owns no partial and no history, its record is 456 zero bytes.
+
+    The arena: the rows; the words, 128 float2 a slot with NaN behind L; a pair of history slots per searched descriptor -- the
+    one read holds the history, NaN poison for a restarted row, which may not read it -- ; the partials, in another order than
+    the descriptors' (i -> i * a % n) with a slot nobody owns behind every `spare_every`-th, NaN poison throughout; the records,
+    `channel` a permutation with slots no descriptor names.  Expected: of a partial the members partial_writes lists and poison in
+    the others, the model's 1016 bytes in hist_out and poison in its 8 pad bytes, join_bytes of the partials in the record, and
+    everything else as it went up."""
+
+    def __init__(self, protos, uses, spare_every=3, which=3):
+        super().__init__()
+        self.protos, self.uses, self.which = protos, uses, which
+        psize, rsize = ym.PART_BYTES, ym.RECORD_BYTES
+        a = self.arena
+        words = {}
+        for k, p in enumerate(protos):
+            p["synthetic"] = "x" not in p
+            if p["synthetic"]:
+                assert which == 2, "synthetic partials are for the join alone"
+            else:
+                w, x = np.ascontiguousarray(p["word"], F32), np.ascontiguousarray(p["x"], F32)
+                p["L"], p["n"] = w.size // 2, x.size // 2
+                flags = ym.RESTART if p["restart"] else 0
+                p["p0"], p["n_windows"] = ym.windows(p["n"], p["L"], p["restart"])
+                p["parts"], p["hist_out"] = ym.partials_and_history(w, p["thr"], x, flags, p.get("hist"))
+                p["Ew"] = ym.word_energy(w)
+                p["src"] = a.source(x, k, 8, skew=p.get("skew", 0))
+                key = w.tobytes()
+                if key not in words:
+                    slot = np.concatenate([np.frombuffer(key, np.uint8), nan_poison(SYNC_WORD_BYTES - len(key))])
+                    words[key] = a.source(slot, "word L%d" % p["L"], 8)
+                p["word_off"] = words[key]
+            p["record"] = ym.join_bytes(p["parts"], p["n"], p["n_windows"], p["L"])
+            p["writes"] = [ym.partial_writes(q) for q in p["parts"]]
+            assert len(p["parts"]) == max(1, -(-p["n_windows"] // ym.PIECE)) and len(p["record"]) == rsize
+        n = len(uses)
+        self.desc = np.zeros(n, SYNC_DESC)
+        searched = [i for i, (_, data) in enumerate(uses) if data]
+        # the partials: searched descriptor order[0] takes the first slots, order[1] the next ..; a spare slot behind every spare_every-th
+        m = len(searched)
+        mul = _coprime(m, int(0.618 * m))
+        order = [searched[(j * mul + m // 2) % m] for j in range(m)]
+        part0, spare, at = [0] * n, [], 0
+        for j, i in enumerate(order):
+            part0[i] = at
+            at += len(protos[uses[i][0]]["parts"])
+            if j % spare_every == spare_every - 1:
+                spare.append(at)
+                at += 1
+        self.n_slots = at
+        self.n_rec = n + max(2, min(n // 16, 512))
+        cmul = _coprime(self.n_rec, int(0.382 * self.n_rec))
+        channel = [(i * cmul + 1) % self.n_rec for i in range(n)]
+        hist_in, hist_out = [0] * n, [0] * n
+        for i in searched:
+            p = protos[uses[i][0]]
+            if p["synthetic"]:
+                continue
+            h = p.get("hist")
+            values = np.frombuffer(nan_poison(SYNC_HIST_BYTES).tobytes(), F32) if p["restart"] else np.zeros(2 * ym.HIST, F32) if h is None else h
+            hist_in[i], hist_out[i] = a.history(i % 2, values, i, SYNC_SLOT_BYTES, SYNC_HIST_BYTES)
+            self._writes.append((hist_out[i], p["hist_out"]))
+        pimg = nan_poison(self.n_slots * psize).copy()
+        for i in searched:
+            p = protos[uses[i][0]]
+            for q, writes in enumerate(p["writes"]):
+                o = (part0[i] + q) * psize
+                for off, b in writes:
+                    if p["synthetic"]:
+                        pimg[o + off: o + off + len(b)] = np.frombuffer(b, np.uint8)
+        self.part_off = a._place(pimg)
+        self.rec_off = a._place(np.full(self.n_rec * rsize, ROW_BYTE, np.uint8))
+        R, zero = a.regions, bytes(rsize)
+        for i, (k, data) in enumerate(uses):
+            p = protos[k]
+            if data:
+                for q, writes in enumerate(p["writes"]):
+                    o = self.part_off + (part0[i] + q) * psize
+                    R.append(Region(o, o + psize, "partial", i, 4))
+                    if which & 1:
+                        self._writes += [(o + off, b) for off, b in writes]
+            o = self.rec_off + channel[i] * rsize
+            R.append(Region(o, o + rsize, "record", i, 8))
+            if which & 2:
+                self._writes.append((o, p["record"] if data else zero))
+        for sl in spare:
+            R.append(Region(self.part_off + sl * psize, self.part_off + (sl + 1) * psize, "spare_partial", None, 4))
+        for ch in sorted(set(range(self.n_rec)) - set(channel)):
+            R.append(Region(self.rec_off + ch * rsize, self.rec_off + (ch + 1) * rsize, "spare_record", None, 8))
+        d = self.desc
+        d["channel"] = channel
+        pk = [protos[uses[i][0]] for i in searched]
+        real = [not p["synthetic"] for p in pk]
+        d["soft"][searched] = [p["src"] if r else 0 for p, r in zip(pk, real)]
+        d["word"][searched] = [p["word_off"] if r else 0 for p, r in zip(pk, real)]
+        d["hist_in"][searched], d["hist_out"][searched] = [hist_in[i] for i in searched], [hist_out[i] for i in searched]
+        d["n"][searched], d["n_windows"][searched], d["L"][searched] = [p["n"] for p in pk], [p["n_windows"] for p in pk], [p["L"] for p in pk]
+        d["p0"][searched] = [p["p0"] if r else 0 for p, r in zip(pk, real)]
+        d["part0"][searched], d["n_piece"][searched] = [part0[i] for i in searched], [len(p["parts"]) for p in pk]
+        d["flags"][searched] = [SYNC_DATA | (SYNC_RESTART if r and p["restart"] else 0) for p, r in zip(pk, real)]
+        d["threshold"][searched] = [p["thr"] if r else 0.5 for p, r in zip(pk, real)]
+        d["Ew"][searched] = [p["Ew"] if r else 1.0 for p, r in zip(pk, real)]
+        self.part0, self.channel, self.spare, self.searched = part0, channel, spare, searched
+        self.spare_channels = sorted(set(range(self.n_rec)) - set(channel))
+        self.max_piece = max(len(p["parts"]) for p in pk)
+        self.per = sync_grid(n, self.max_piece)
+        self._finish()
+        self._check_extents()
+
+    def _check_extents(self):
+        """what the two kernels may touch behind every descriptor lies where the arena has it"""
+        a, d = self.arena, self.desc
+        psize, rsize = ym.PART_BYTES, ym.RECORD_BYTES
+        assert self.part_off % 8 == 0 and self.rec_off % 8 == 0 and a.size < (1 << 31) and self.which in (1, 2, 3)
+        assert len(set(self.channel)) == len(self.channel) and max(self.channel) < self.n_rec
+        assert a.size >= self.rec_off + self.n_rec * rsize + GUARD and self.rec_off >= self.part_off + self.n_slots * psize + GUARD
+        taken = np.zeros(self.n_slots, np.int32)
+        for i, (k, data) in enumerate(self.uses):
+            x = d[i]
+            assert a.inside("record", self.rec_off + int(x["channel"]) * rsize, rsize), i
+            if not data:
+                z = x.copy()
+                z["channel"] = 0
+                assert z.tobytes() == bytes(SYNC_DESC.itemsize), "a descriptor without data is zeros except its channel"
+                continue
+            p = self.protos[k]
+            L, n, nw, np_ = int(x["L"]), int(x["n"]), int(x["n_windows"]), int(x["n_piece"])
+            assert int(x["flags"]) & SYNC_DATA and 1 <= L <= ym.MAX_WORD and 1 <= n < (1 << 30), (i, L, n)
+            assert np_ == max(1, -(-nw // ym.PIECE)) and int(x["part0"]) + np_ <= self.n_slots, (i, nw, np_)
+            taken[int(x["part0"]): int(x["part0"]) + np_] += 1
+            for q in (0, np_ - 1):
+                assert a.inside("partial", self.part_off + (int(x["part0"]) + q) * psize, psize), (i, q)
+            if p["synthetic"]:
+                assert self.which == 2
+                continue
+            restart = bool(int(x["flags"]) & SYNC_RESTART)
+            assert (int(x["p0"]), nw) == ym.windows(n, L, restart) and int(x["p0"]) == (0 if restart else -(L - 1))
+            # the fold reads x[0 .. n-1] (the last window ends at p0 + nw - 1 + L - 1 = n - 1), w[0 .. L-1], the 127 symbols of
+            # hist_in unless restarted, and writes 127 symbols of hist_out
+            assert nw == 0 or int(x["p0"]) + nw - 1 + L - 1 == n - 1
+            assert int(x["soft"]) % 8 == 0 and a.inside("source", int(x["soft"]), 8 * n), (i, n)
+            assert int(x["word"]) % 8 == 0 and a.inside("source", int(x["word"]), 8 * L), (i, L)
+            assert int(x["hist_in"]) % 8 == 0 and a.inside("hist_in", int(x["hist_in"]), SYNC_HIST_BYTES), i
+            assert int(x["hist_out"]) % 8 == 0 and a.inside("hist_out", int(x["hist_out"]), SYNC_HIST_BYTES), i
+        assert taken.max() == 1 and not taken[self.spare].any()
+        for sl in self.spare[:1] + self.spare[-1:]:
+            assert a.inside("spare_partial", self.part_off + sl * psize, psize)
+
+    def partial_bytes(self, image, i, q):
+        o = self.part_off + (self.part0[i] + q) * ym.PART_BYTES
+        return image[o: o + ym.PART_BYTES].tobytes()
+
+    def record_bytes(self, image, i):
+        o = self.rec_off + self.channel[i] * ym.RECORD_BYTES
+        return image[o: o + ym.RECORD_BYTES].tobytes()
+
+    def field(self, f):
+        """the member of the partial or of the record a finding's first byte lies in"""
+        if f["where"] in ("partial", "spare_partial"):
+            dt, at = ym.PART_DTYPE, (f["offset"] - self.part_off) % ym.PART_BYTES
+        elif f["where"] in ("record", "spare_record"):
+            dt, at = ym.RECORD_DTYPE, (f["offset"] - self.rec_off) % ym.RECORD_BYTES
+        else:
+            return None
+        for name in dt.names:
+            sub, off = dt.fields[name][:2]
+            if off <= at < off + sub.itemsize:
+                return "%s[%d]" % (name, (at - off) // sub.base.itemsize) if sub.shape else name
+        return "padding"
+
+    def check(self, after):
+        found = self.arena.compare(self.want, after)
+        for f in found:
+            f["field"] = self.field(f)
+            if f["field"]:
+                f["message"] += " (%s)" % f["field"]
+        return found
+
+    def run(self):
+        self._check_extents()
+        return _launch("sync", load().psk_prepass_probe_sync, self.image, self.desc.ctypes.data, len(self.desc), self.max_piece, self.part_off,
+                       self.rec_off, self.which)

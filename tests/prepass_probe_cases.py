@@ -10,6 +10,7 @@ from tests import fir_model as fm
 from tests import prepass_probe as pp
 from tests import resample_model as rm  # noqa: F401  (the tests reach the model through this module)
 from tests import symrate_model as sm
+from tests import sync_model as ym
 from tests import tune_model as tm
 
 F32 = np.float32
@@ -667,3 +668,287 @@ def acquire_loop():
     for i in range(20):
         add(2 + (i * 7) % 39, (2, 4, 8)[i % 3])
     return pp.LookCase("acquire", protos, loop_uses(20), spare_every=97)
+
+
+# ---- the word search (psk_sync.hip) --------------------------------------------------------------------------------------------------
+#
+# Rows of two kinds.  A COMB row is one repeated symbol under the word of two points a quarter turn apart: the window at a planted
+# word has m = 1, the one in front of it 1/2, the one behind it 0 -- hits exactly where a case puts them, two windows apart if
+# need be, and all of them equal bests.  A WORD row is noisy QPSK with a random QPSK word of length L written at given positions.
+# Places are given as WINDOW INDICES (window k lies at position p0 + k; piece k // 1024) or as positions relative to x[0].
+
+SY_P = ym.PIECE
+SY_SYMBOL = 0.8 - 0.3j
+COMB = np.array([1, 0, 0, 1], F32)
+COMB_THR = 0.999
+
+
+def _iq(z):
+    x = np.empty(2 * len(z), F32)
+    x[0::2], x[1::2] = z.real, z.imag
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def _sync_word_z(L):
+    rng = np.random.default_rng(500 + L)
+    return ym.psk_points(4, rng.integers(0, 4, L))
+
+
+def sync_word(L):
+    """the word of length L: unit QPSK points, interleaved float32"""
+    return _iq(_sync_word_z(L))
+
+
+def comb_proto(n_windows, hits, restart, zero=(), skew=0):
+    """a comb row of n_windows windows with a hit at each window index of `hits` (at least two apart); zero: (lo, hi) ranges of
+    window indices whose symbols are all zeros -- none of those windows is valid"""
+    hits = sorted(hits)
+    assert all(b - a >= 2 for a, b in zip(hits, hits[1:])) and (not hits or 0 <= hits[0] and hits[-1] < n_windows)
+    n, p0 = (n_windows + 1, 0) if restart else (n_windows, -1)
+    z = np.full(ym.HIST + n, SY_SYMBOL)
+    z[ym.HIST + p0 + np.asarray(hits, np.int64) + 1] *= 1j
+    for lo, hi in zero:
+        assert not any(lo - 1 <= h <= hi for h in hits)
+        z[ym.HIST + p0 + lo: ym.HIST + p0 + hi + 1] = 0
+    return dict(word=COMB, thr=COMB_THR, x=_iq(z[ym.HIST:]), restart=restart, hist=None if restart else _iq(z[:ym.HIST]), skew=skew, hits=hits,
+                kind="comb")
+
+
+def word_proto(L, n, restart, at, seed, sigma=0.05, thr=0.9, skew=0, clean=(), nan_at=None):
+    """a noisy QPSK row of n symbols behind 127 symbols of history with the word of length L written at the positions `at`
+    (relative to x[0]; cut at either end) in front of the noise and at the positions `clean` behind it; nan_at: a NaN symbol"""
+    rng = np.random.default_rng(seed)
+    wz = _sync_word_z(L) * SY_SYMBOL
+    z = ym.psk_points(4, rng.integers(0, 4, ym.HIST + n)) * SY_SYMBOL
+    noise = sigma * (rng.standard_normal(len(z)) + 1j * rng.standard_normal(len(z)))
+    for places, late in ((at, False), (clean, True)):
+        if late:
+            z = z + noise
+        for p in places:
+            lo, hi = max(p + ym.HIST, 0), min(p + ym.HIST + L, len(z))
+            if hi > lo:
+                z[lo:hi] = wz[lo - p - ym.HIST: hi - p - ym.HIST]
+    x = _iq(z[ym.HIST:])
+    if nan_at is not None:
+        x[2 * nan_at + 1] = np.nan
+    return dict(word=sync_word(L), thr=thr, x=x, restart=restart, hist=None if restart else _iq(z[:ym.HIST]), skew=skew, kind="word")
+
+
+def windows_proto(L, n_windows, restart, at, seed, **kw):
+    """word_proto by its number of windows"""
+    return word_proto(L, n_windows + (L - 1 if restart else 0), restart, at, seed, **kw)
+
+
+# A. every word length
+
+SYNC_LENGTH_WINDOWS = SY_P + 65  # two pieces, the second with one full turn of wave 0 and one lane of its second
+SYNC_LENGTH_IDLE = 1900
+
+
+@functools.lru_cache(maxsize=None)
+def sync_lengths(spread):
+    """L = 1 .. 128, each with a continued row (a word across the row's start, through hist_in) and a restarted one, P + 65
+    windows each: 256 descriptors.  spread: the same 256 among 1900 descriptors without data -- one workgroup a channel, which
+    walks both pieces."""
+    protos = []
+    for L in range(1, ym.MAX_WORD + 1):
+        for restart in (False, True):
+            n = SYNC_LENGTH_WINDOWS + (L - 1 if restart else 0)
+            at = (3 if restart else -(L // 2), 200, SY_P - L // 2, n - L)
+            protos.append(word_proto(L, n, restart, at, 11000 + 2 * L + restart, skew=8 if L % 2 else 0))
+    if not spread:
+        return pp.SyncCase(protos, [(k, True) for k in range(len(protos))])
+    uses = [(0, False)] * (len(protos) + SYNC_LENGTH_IDLE)
+    for k in range(len(protos)):
+        uses[3 + 8 * k] = (k, True)
+    return pp.SyncCase(protos, uses)
+
+
+# B. workgroups that walk several pieces
+
+SYNC_WALK_SHAPES = (700, 1100, 2100)
+SYNC_WALK_LONG, SYNC_WALK_SHORT = (0, 1, 2, 3, 5, 10, 11), (6, 7, 8, 9, 4)
+SYNC_WALK_CROWD, SYNC_WALK_ZEROS = (3, 400, 20), 2  # (piece, first window, hits) of proto 0's crowd; proto 1's piece without a valid window
+
+
+def sync_walk_protos():
+    P = SY_P
+    pr = []
+    # 0: comb, 7 pieces, restarted: three hits in every piece and 20 more in piece 3
+    cp, c0, cn = SYNC_WALK_CROWD
+    pr.append(comb_proto(6 * P + 950, [p * P + o for p in range(7) for o in (5, 300, 900)] + [cp * P + c0 + 4 * i for i in range(cn)], True))
+    # 1: comb, 5 pieces, continued: a hit at position -1, piece 2 all zeros between pieces with valid windows
+    pr.append(comb_proto(4 * P + 100, [0, 40, P + 7, P + 900, 3 * P + 1, 3 * P + 500, 4 * P + 2, 4 * P + 77], False,
+                         zero=[(SYNC_WALK_ZEROS * P, (SYNC_WALK_ZEROS + 1) * P)], skew=8))
+    # 2: L = 31, restarted, four whole pieces of one period of P symbols: the same best, bit for bit, in every piece
+    seg = word_proto(31, P, True, (4,), 12001, sigma=0.1)["x"]
+    pr.append(dict(word=sync_word(31), thr=0.7, x=np.concatenate([seg] * 4 + [seg[:60]]), restart=True, hist=None, skew=0, kind="periodic"))
+    # 3 .. 5: L = 128 continued (a word across the row's start and one across a piece edge) and restarted, L = 31 continued
+    pr.append(windows_proto(128, 2 * P + 300, False, (-64, 500, P - 64 - 127, 2 * P + 10), 12003, skew=8))
+    pr.append(windows_proto(128, P + 1, True, (30, 700), 12004))
+    pr.append(windows_proto(31, 3 * P + 77, False, (-15, 600, P + 3, 2 * P + 500, 3 * P + 10), 12005))
+    # 6 .. 9: one and two pieces
+    pr.append(comb_proto(39, [3, 20], True, skew=8))
+    pr.append(comb_proto(P + 1, [0, P - 2, P], False))
+    pr.append(windows_proto(31, 170, True, (50,), 12008, skew=8))
+    pr.append(word_proto(128, 100, False, (-100,), 12009))
+    # 10: comb, 3 pieces, restarted: 18 hits in each of pieces 1 and 2
+    pr.append(comb_proto(2 * P + 500, [9, 700] + [P + 100 + 6 * i for i in range(18)] + [2 * P + 11 + 2 * i for i in range(18)], True))
+    # 11: L = 31, 5 pieces, restarted, a NaN symbol at a piece edge
+    pr.append(windows_proto(31, 4 * P + 9, True, (100, P + 100, 2 * P + 200, 3 * P + 5, 4 * P - 20), 12011, nan_at=2 * P))
+    return pr
+
+
+@functools.lru_cache(maxsize=None)
+def sync_walk(n_desc):
+    """700, 1100 and 2100 descriptors -- 3, 2 and 1 workgroups a channel -- over the twelve rows of sync_walk_protos: every 25th
+    a row of 3 .. 7 pieces, every ninth without data, the rest rows of 1 and 2 pieces"""
+    uses = []
+    for i in range(n_desc):
+        if i % 9 == 4:
+            uses.append((6, False))
+        elif i % 25 == 0:
+            uses.append((SYNC_WALK_LONG[(i // 25) % len(SYNC_WALK_LONG)], True))
+        else:
+            uses.append((SYNC_WALK_SHORT[i % len(SYNC_WALK_SHORT)], True))
+    return pp.SyncCase(sync_walk_protos(), uses)
+
+
+# C. the join's chunks of 64 partials
+
+SYNC_CHUNK_PIECES = (1, 63, 64, 65, 127, 128, 129, 130, 66, 66)
+
+
+def _w(piece, k=0):
+    return piece * SY_P + 10 + 4 * k
+
+
+def sync_chunk_protos():
+    """ten rows, comb but one, of SYNC_CHUNK_PIECES pieces.  2: ten hits in pieces 0 .. 54 and ten in piece 63 -- the cap is met in
+    lane 63; 3: ten in pieces 3 .. 57 and ten in piece 64 -- the 16th stored hit lies in chunk 1; 4: hits in chunk 1 only; 5: 20
+    hits in piece 5, then hits in chunk 1 that are counted and not stored; 6: five, five, and ten in piece 128 -- the cap is met
+    in the third chunk; 7: ten either side of piece 64; 8: L = 31 under noise of 0.3 with one noiseless word in piece 64; 9: one
+    hit in piece 10 and one in piece 65 -- equal bests in two chunks"""
+    P = SY_P
+    pr = [comb_proto(P - 7, [3, 500], True),
+          comb_proto(62 * P + 300, [_w(0), _w(30), _w(62)], False, skew=8),
+          comb_proto(63 * P + 1000, [_w(p) for p in range(0, 60, 6)] + [_w(63, k) for k in range(10)], True),
+          comb_proto(64 * P + 65, [_w(p) for p in range(3, 63, 6)] + [_w(64, k) for k in range(10)], False),
+          comb_proto(126 * P + 50, [_w(64), _w(64, 1), _w(90), _w(126)], True, skew=8),
+          comb_proto(128 * P, [_w(5, k) for k in range(20)] + [_w(64), _w(100), _w(127, 3)], False),
+          comb_proto(128 * P + 100, [_w(p) for p in (1, 9, 17, 25, 33, 64, 70, 80, 90, 127)] + [_w(128, k) for k in range(10)], True),
+          comb_proto(129 * P + 50, [_w(p) for p in range(0, 64, 7)] + [_w(p) for p in (64, 65, 70, 77, 90, 100, 111, 127, 128, 129)], False, skew=8),
+          windows_proto(31, 65 * P + 40, True, (1000, 20000), 13008, sigma=0.3, thr=0.7, clean=(64 * P + 300,)),
+          comb_proto(65 * P + 40, [_w(10), _w(65)], True)]
+    return pr
+
+
+@functools.lru_cache(maxsize=None)
+def sync_chunks():
+    """the ten rows of sync_chunk_protos and two descriptors without data, one launch of fold and join"""
+    pr = sync_chunk_protos()
+    uses = [(k, True) for k in range(len(pr))]
+    uses[4:4] = [(0, False)]
+    uses.append((0, False))
+    return pp.SyncCase(pr, uses)
+
+
+SYNC_HIT_COUNTS = (0, 1, 15, 16, 17, 1024)
+
+
+def synthetic_partial(piece, n_valid, n_hits, m_best):
+    """a partial as a fold could have left it for piece `piece`: positions inside the piece, ascending; arbitrary sums"""
+    k = np.arange(min(n_hits, ym.HITS))
+    hits = np.zeros(len(k), ym.HIT_DTYPE)
+    hits["pos"], hits["cr"], hits["ci"], hits["e"], hits["m"] = piece * SY_P + 3 * k, piece + k / 16.0, -1.0 - k, 2.0 + k, 0.9 + k / 256.0
+    best = None
+    if n_valid:
+        best = np.zeros((), ym.HIT_DTYPE)
+        best["pos"], best["cr"], best["ci"], best["e"], best["m"] = piece * SY_P + 517, piece, 0.5, 3.0, m_best
+    return dict(n_valid=n_valid, n_hits=n_hits, best=best, hits=hits)
+
+
+def synthetic_proto(name, counts):
+    """a row of len(counts) pieces by its partials alone: piece p has counts[p] hits; as many valid windows, but at least 7 --
+    and none in every fifth piece without a hit, whose best is poison; the bests are drawn from eleven values, so that equal
+    maxima lie in several pieces and chunks"""
+    parts = []
+    for p, h in enumerate(counts):
+        v = 0 if h == 0 and p % 5 == 2 else max(h, 7)
+        parts.append(synthetic_partial(p, v, h, 0.25 + ((p * 37 + 5) % 11) / 16.0))
+    nw = len(counts) * SY_P
+    return dict(parts=parts, n=nw + 4, n_windows=nw, L=5, name=name, counts=tuple(counts))
+
+
+def _cycle(n, first=0):
+    return [SYNC_HIT_COUNTS[(p + first) % len(SYNC_HIT_COUNTS)] for p in range(n)]
+
+
+@functools.lru_cache(maxsize=None)
+def sync_join_alone():
+    """the join alone on partials written by numpy: 1, 64, 65 and 200 pieces of 1024 hits each; then 130 pieces with 0, 1, 15, 16,
+    17 and 1024 hits mixed: the cap met in lane 0, in lane 63, by the first partial of the second chunk, and in the second chunk
+    alone; one descriptor without data"""
+    pr = [synthetic_proto("full %d" % k, [1024] * k) for k in (1, 64, 65, 200)]
+    pr.append(synthetic_proto("cycle", _cycle(130)))
+    pr.append(synthetic_proto("lane 0", [17] + _cycle(129, 1)))
+    pr.append(synthetic_proto("lane 63", [0] * 63 + [1024] + _cycle(66)))
+    pr.append(synthetic_proto("chunk edge", [0] * 7 + [15] + [0] * 56 + [1, 17] + _cycle(64)))
+    pr.append(synthetic_proto("second chunk", [0] * 64 + [1024] + _cycle(65)))
+    uses = [(k, True) for k in range(len(pr))]
+    uses[2:2] = [(0, False)]
+    return pp.SyncCase(pr, uses, which=2)
+
+
+# D. the channel loop's second trip
+
+SYNC_LOOP_DESCRIPTORS = pp.LOOK_GRID_MAX + 600
+SYNC_LOOP_PAIRS = 40
+SYNC_LOOP_KINDS = ("L 128, one piece, then L 3, five pieces", "L 3, five pieces, then L 128, one piece", "data, then none", "none, then data")
+
+
+def sync_loop_first(k):
+    """the first descriptor of pair k; its partner is 65535 further"""
+    return 7 + 13 * k
+
+
+@functools.lru_cache(maxsize=None)
+def sync_loop():
+    """65535 + 600 descriptors, all without data but 40 pairs (i, i + 65535), which share a workgroup of the fold and one of the
+    join: SYNC_LOOP_KINDS in turn.  Protos 0, 1: L = 128, 300 symbols, continued and restarted; 2, 3: L = 3, five pieces"""
+    P = SY_P
+    pr = [word_proto(128, 300, False, (-64, 100), 14000), word_proto(128, 300, True, (10,), 14001, skew=8),
+          windows_proto(3, 4 * P + 50, False, (-1, 2 * P), 14002, skew=8), windows_proto(3, 4 * P + 50, True, (5,), 14003)]
+    uses = [(0, False)] * SYNC_LOOP_DESCRIPTORS
+    for k in range(SYNC_LOOP_PAIRS):
+        i, alt = sync_loop_first(k), (k // 4) % 2
+        one, five = (alt, True), (2 + alt, True)
+        uses[i], uses[i + pp.LOOK_GRID_MAX] = ((one, five), (five, one), ((one, five)[alt], (0, False)), ((0, False), (five, one)[alt]))[k % 4]
+    return pp.SyncCase(pr, uses, spare_every=7)
+
+
+# E. alignment and the history
+
+SYNC_SHORT_L = (1, 64, 128)
+
+
+def sync_short_lengths(L):
+    return sorted({1, L - 1, 126, 127, 128, 300} - {0})
+
+
+@functools.lru_cache(maxsize=None)
+def sync_short_rows():
+    """rows of 1, L - 1, 126, 127, 128 and 300 symbols at L = 1, 64 and 128, continued (a word across the row's start) and
+    restarted, rows 8 bytes past a line for every second: the history shifts by fewer than 127 symbols, or is the row's end"""
+    pr = []
+    for L in SYNC_SHORT_L:
+        for n in sync_short_lengths(L):
+            for restart in (False, True):
+                pr.append(word_proto(L, n, restart, (-(L // 2), n // 3), 15000 + 1000 * L + 2 * n + restart, skew=8 if len(pr) % 4 < 2 else 0))
+    return pp.SyncCase(pr, [(k, True) for k in range(len(pr))], spare_every=2)
+
+
+SYNC_CASES = {"lengths": lambda: sync_lengths(False), "lengths spread": lambda: sync_lengths(True), "walk 700": lambda: sync_walk(700),
+              "walk 1100": lambda: sync_walk(1100), "walk 2100": lambda: sync_walk(2100), "chunks": sync_chunks, "join alone": sync_join_alone,
+              "loop": sync_loop, "short rows": sync_short_rows}

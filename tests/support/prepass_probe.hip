@@ -1,10 +1,11 @@
-// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip, psk_fir.hip) and the two
-// looks (psk_symrate.hip, psk_acquire.hip: fold and join) launched by themselves, so that tests can hold every byte they write -- each
+// prepass_probe.hip -- TEST SUPPORT: the pre-pass kernels (psk_gather.hip, psk_tune.hip, psk_resample.hip, psk_fir.hip), the two
+// looks (psk_symrate.hip, psk_acquire.hip: fold and join) and the word search (psk_sync.hip: fold and join) launched by themselves,
+// so that tests can hold every byte they write -- each
 // row sample, both history slots, every partial and record -- and every byte they must not write to the models, bit for bit
 // (tests/prepass_probe.py, tests/test_gpu_prepass_probe.py).
 //
 // This file holds no kernel.  It is linked with the product's own objects psk_gather.o, psk_tune.o, psk_resample.o, psk_fir.o,
-// psk_symrate.o and psk_acquire.o as the product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
+// psk_symrate.o, psk_acquire.o and psk_sync.o as the product's build made them (psk_soft_amd/csrc/Makefile, target ../libpsk_prepass_probe.so): the machine code under test is
 // the product's.  Nothing of it is linked into the product library.
 //
 // One C entry per kernel.  The caller passes one host ARENA -- sources, destination rows, histories, poison everywhere else --
@@ -23,6 +24,7 @@
 #include "psk_gather.h"
 #include "psk_resample.h"
 #include "psk_symrate.h"
+#include "psk_sync.h"
 #include "psk_tune.h"
 
 using namespace psk;
@@ -86,7 +88,7 @@ bool point(P &field, const char *d_arena, uint64_t bytes)
 extern "C" {
 
 // 0 GatherGroup, 1 GatherChan, 2 GatherSingle, 3 TuneDesc, 4 ResampleDesc, 5 FirDesc, 6 SymrateDesc, 7 SymratePartial, 8 AcquireDesc,
-// 9 AcquirePartial, 10 psk_soft_symrate_t, 11 psk_soft_acquire_t
+// 9 AcquirePartial, 10 psk_soft_symrate_t, 11 psk_soft_acquire_t, 12 SyncDesc, 13 SyncPartial, 14 psk_soft_sync_t
 int psk_prepass_probe_sizeof(int which)
 {
     switch (which) {
@@ -102,13 +104,17 @@ int psk_prepass_probe_sizeof(int which)
     case 9: return (int)sizeof(AcquirePartial);
     case 10: return (int)sizeof(psk_soft_symrate_t);
     case 11: return (int)sizeof(psk_soft_acquire_t);
+    case 12: return (int)sizeof(SyncDesc);
+    case 13: return (int)sizeof(SyncPartial);
+    case 14: return (int)sizeof(psk_soft_sync_t);
     default: return -1;
     }
 }
 
 // 0 kResamplePiece, 1 kResampleInputs, 2 kGatherTile, 3 kGatherMinGroup, 4 kTuneTableFloats, 5 kFirWindow, 6 kFirMaxTaps,
 // 7 kFirHistSlotFloats, 8 kSymratePiece, 9 kSymrateHalo, 10 kSymrateThreads, 11 kSymrateMinS, 12 kSymrateMaxS, 13 kSymrateMaxBlocks,
-// 14 kAcquirePiece, 15 kAcquireHalo, 16 kAcquireThreads
+// 14 kAcquirePiece, 15 kAcquireHalo, 16 kAcquireThreads, 17 kSyncPiece, 18 kSyncThreads, 19 kSyncHist, 20 kSyncHistSlotFloats,
+// 21 kSyncMaxWord, 22 kSyncHits
 int psk_prepass_probe_constant(int which)
 {
     switch (which) {
@@ -129,6 +135,12 @@ int psk_prepass_probe_constant(int which)
     case 14: return (int)kAcquirePiece;
     case 15: return (int)kAcquireHalo;
     case 16: return (int)kAcquireThreads;
+    case 17: return (int)kSyncPiece;
+    case 18: return (int)kSyncThreads;
+    case 19: return (int)kSyncHist;
+    case 20: return (int)kSyncHistSlotFloats;
+    case 21: return (int)kSyncMaxWord;
+    case 22: return (int)kSyncHits;
     default: return -1;
     }
 }
@@ -271,6 +283,33 @@ int psk_prepass_probe_acquire(void *arena, uint64_t bytes, const void *desc, uin
     hipError_t e = launch_acquire_fold((const AcquireDesc *)r.d_desc[0], n_desc, max_piece, r.d_tab, part, r.stream);
     if (e == hipSuccess)
         e = launch_acquire_join((const AcquireDesc *)r.d_desc[0], n_desc, part, (psk_soft_acquire_t *)(r.d_arena + rec_off), r.stream);
+    return r.end(e, arena, bytes, nullptr);
+}
+
+// The word search: which bit 0 launches the fold, bit 1 the join, on one stream in that order.  soft, word, hist_in and hist_out of
+// a descriptor with kSyncData are arena offsets; a descriptor without it is passed as it is.
+int psk_prepass_probe_sync(void *arena, uint64_t bytes, const void *desc, uint32_t n_desc, uint32_t max_piece, uint64_t part_off,
+                           uint64_t rec_off, int which)
+{
+    if (!arena || !bytes || !desc || !n_desc || part_off >= bytes || rec_off >= bytes || part_off % 8u || rec_off % 8u || !(which & 3) ||
+        (which & ~3))
+        return (int)hipErrorInvalidValue;
+    std::vector<SyncDesc> d((const SyncDesc *)desc, (const SyncDesc *)desc + n_desc);
+    Run r;
+    if (!r.begin(arena, bytes))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    for (SyncDesc &t : d)
+        if ((t.flags & kSyncData) && (!point(t.soft, r.d_arena, bytes) || !point(t.word, r.d_arena, bytes) ||
+                                      !point(t.hist_in, r.d_arena, bytes) || !point(t.hist_out, r.d_arena, bytes)))
+            return r.end(hipErrorInvalidValue, arena, 0, nullptr);
+    if (!r.descriptors(0, d.data(), sizeof(SyncDesc) * d.size()))
+        return r.end(hipSuccess, arena, 0, nullptr);
+    SyncPartial *const part = (SyncPartial *)(r.d_arena + part_off);
+    hipError_t e = hipSuccess;
+    if (which & 1)
+        e = launch_sync_fold((const SyncDesc *)r.d_desc[0], n_desc, max_piece, part, r.stream);
+    if (e == hipSuccess && (which & 2))
+        e = launch_sync_join((const SyncDesc *)r.d_desc[0], n_desc, part, (psk_soft_sync_t *)(r.d_arena + rec_off), r.stream);
     return r.end(e, arena, bytes, nullptr);
 }
 

@@ -2,6 +2,9 @@
 once (numpy rounds each elementwise operation; nothing here can fuse), the loop over j = 0 .. L-1 in that order vectorised over the
 windows, hits and best by the header's rules.  The tests hold psk_soft_sync_host and the device to it byte for byte.
 
+partials / partial_writes / join_bytes state what one piece of the device's fold leaves in its SyncPartial and what the join may
+read of it: the probe (tests/prepass_probe.py) holds the partials, the histories and the records of the kernels alone to them.
+
 Also the stimulus of the issue's three oracle cases (a word written into random PSK data every `period` symbols) and helpers that
 read a record."""
 import math
@@ -98,6 +101,70 @@ def model_record(word, threshold, soft, flags=0, hist_in=None):
     for s, k in enumerate(hi[:HITS]):
         put(rec["hits"][s], k)
     return rec, new_hist
+
+
+# ---- what a piece of the device's fold leaves, and what its join may read (psk_sync.h: SyncPartial) --------------------------------
+
+PART_DTYPE = np.dtype([("n_valid", "<u4"), ("n_hits", "<u4"), ("best", HIT_DTYPE), ("hits", HIT_DTYPE, (HITS,))])
+PART_BYTES = PART_DTYPE.itemsize
+assert PART_BYTES == 8 + HIT_BYTES * (1 + HITS)
+
+
+def partials_and_history(word, threshold, soft, flags=0, hist_in=None):
+    """(one partial per piece of PIECE windows -- one for a row without a window --, the history behind the row).  A partial is a
+    dict: n_valid, n_hits, best (a HIT_DTYPE scalar: the piece's first maximum; None without a valid window), hits (the piece's
+    first min(n_hits, 16) hits, an array of HIT_DTYPE)."""
+    pos, cr, ci, e, m, valid, new_hist = model_windows(word, soft, flags, hist_in)
+    with np.errstate(invalid="ignore"):
+        hit = valid & (m >= F32(threshold))
+    every = np.zeros(len(pos), HIT_DTYPE)
+    every["pos"], every["cr"], every["ci"], every["e"], every["m"] = pos, cr, ci, e, m
+    out = []
+    for lo in range(0, max(len(pos), 1), PIECE):
+        hi = min(lo + PIECE, len(pos))
+        vi = lo + np.flatnonzero(valid[lo:hi])
+        hk = lo + np.flatnonzero(hit[lo:hi])
+        best = every[vi[np.argmax(m[vi])]].copy() if len(vi) else None  # (argmax: the first of equal maxima)
+        out.append(dict(n_valid=len(vi), n_hits=len(hk), best=best, hits=every[hk[:HITS]].copy()))
+    return out, new_hist
+
+
+def partials(word, threshold, soft, flags=0, hist_in=None):
+    return partials_and_history(word, threshold, soft, flags, hist_in)[0]
+
+
+def partial_writes(p):
+    """the (offset, bytes) pairs the owner of a partial stores, and nothing else: the two counts always, `best` only with a valid
+    window, hits[k] only for k < min(n_hits, 16)"""
+    out = [(0, np.array([p["n_valid"], p["n_hits"]], "<u4").tobytes())]
+    if p["n_valid"]:
+        out.append((PART_DTYPE.fields["best"][1], p["best"].tobytes()))
+    k = min(int(p["n_hits"]), HITS)
+    assert len(p["hits"]) >= k
+    if k:
+        out.append((PART_DTYPE.fields["hits"][1], p["hits"][:k].tobytes()))
+    return out
+
+
+def join_bytes(parts, n, n_windows, L):
+    """the 456 bytes of the record from the partials alone, in piece order; it reads of a partial what the join may read: the
+    counts, `best` where n_valid != 0, hits[k] for k < min(n_hits, 16).  A later best must be greater."""
+    rec = np.zeros((), RECORD_DTYPE)
+    rec["n_symbols"], rec["n_windows"], rec["word_len"], rec["flags"] = n, n_windows, L, DATA
+    nv = nh = 0
+    best = None
+    for p in parts:
+        k = min(int(p["n_hits"]), HITS)
+        if k and nh < HITS:
+            take = min(k, HITS - nh)
+            rec["hits"][nh: nh + take] = p["hits"][:take]
+        if p["n_valid"] and (best is None or p["best"]["m"] > best["m"]):
+            best = p["best"]
+        nv, nh = nv + int(p["n_valid"]), nh + int(p["n_hits"])
+    rec["n_valid"], rec["n_hits"] = nv, nh
+    if best is not None:
+        rec["best"] = best
+    return rec.tobytes()
 
 
 def as_np(rec):

@@ -1,4 +1,4 @@
-"""The gather, tune, resample and filter kernels and (at the end of the file) the two looks by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim
+"""The gather, tune, resample and filter kernels and (at the end of the file) the two looks and the word search by themselves on a real MI355X (psk_soft_amd/libpsk_prepass_probe.so: a shim
 linked with the product's own psk_gather.o, psk_tune.o, psk_resample.o and psk_fir.o).  The demodulator behind these kernels shows one row sample
 in eight at samplesPerBaud 8; here every byte of the arena a launch ran in is compared with the arena
 the models expect -- a byte copy for the gathers, tests/tune_model.py for the tune kernel, tests/tune_model.py followed by
@@ -162,3 +162,67 @@ def test_acquire_lengths_formats_and_placements(mixed):
 def test_acquire_more_packets_than_the_grid_has_rows():
     case = pc.acquire_loop()
     _clean(case, case.run(), "%d acquire descriptors, arena %d bytes" % (len(case.desc), case.arena.size))
+
+
+# ---- the word search: fold and join ----------------------------------------------------------------------------------------------------
+#
+# psk_sync.hip through the shim, psk_sync.o as the product's build made it.  The arena holds the rows, the words, both history
+# slots of every searched descriptor, the partials and the records -- the last three are memory the handle owns in the product,
+# which the guards of tests/test_gpu_sync.py cannot fence.  Expected, byte for byte: of every partial the members
+# sync_model.partial_writes lists and NaN poison in the others (an unwritten best, hits[k] from min(n_hits, 16) on), the record
+# sync_model.join_bytes makes of the partials, the model's 1016 bytes of history and poison in the 8 behind them, 456 zero bytes
+# for a descriptor without data, and every spare partial, spare record, row, word, hist_in and guard byte as it went up.
+# tests/test_prepass_probe.py asserts what each case reaches.
+
+def _sync_clean(name):
+    case = pc.SYNC_CASES[name]()
+    after = case.run()
+    _clean(case, after, "sync %s: %d descriptors, arena %d bytes, %d workgroup(s) a channel" % (name, len(case.desc), case.arena.size, case.per))
+    return case, after
+
+
+def test_sync_every_word_length():
+    """L = 1 .. 128, a continued and a restarted row each, P + 65 windows: 256 descriptors, a workgroup a piece.  Then the same
+    256 among 1900 descriptors without data: one workgroup a channel walks both pieces, and leaves the same bytes."""
+    one, a = _sync_clean("lengths")
+    two, b = _sync_clean("lengths spread")
+    assert (one.per, two.per) == (2, 1)
+    for k, i in enumerate(two.searched):
+        assert two.uses[i][0] == one.uses[k][0] == k
+        assert two.record_bytes(b, i) == one.record_bytes(a, k), "L %d" % (k // 2 + 1)
+        for q in range(2):
+            assert two.partial_bytes(b, i, q) == one.partial_bytes(a, k, q), "L %d, piece %d" % (k // 2 + 1, q)
+
+
+@pytest.mark.parametrize("n_desc", pc.SYNC_WALK_SHAPES)
+def test_sync_workgroups_that_walk_several_pieces(n_desc):
+    """700, 1100 and 2100 descriptors: three, two and one workgroup a channel over rows of up to seven pieces -- more than 16
+    hits in a piece that is not its workgroup's first, a piece without a valid window between two with, equal bests in pieces of
+    one workgroup and of two, channels of one piece next to channels of seven"""
+    _sync_clean("walk %d" % n_desc)
+
+
+def test_sync_rows_of_more_than_64_pieces():
+    """rows of 1, 63, 64, 65, 127, 128, 129 and 130 pieces: the join's second and third trip -- the hits of the chunks before
+    carried, the cap of 16 met across a chunk edge, the best across chunks"""
+    _sync_clean("chunks")
+
+
+def test_sync_join_alone_on_written_partials():
+    """the join by itself on partials numpy wrote, NaN poison in every member it may not read: 1, 64, 65 and 200 pieces of 1024
+    hits; 0, 1, 15, 16, 17 and 1024 hits mixed, the cap met in lane 0, in lane 63 and at the chunk edge"""
+    case, after = _sync_clean("join alone")
+    full = case.protos[3]
+    rec = np.frombuffer(case.record_bytes(after, case.searched[3]), pc.ym.RECORD_DTYPE)[0]
+    assert len(full["parts"]) == 200 and int(rec["n_valid"]) == int(rec["n_hits"]) == 204800
+    assert rec["hits"].tobytes() == full["parts"][0]["hits"].tobytes()
+
+
+def test_sync_more_channels_than_the_grid_has_rows():
+    """65535 + 600 descriptors, 40 pairs (i, i + 65535) that differ in L, in their pieces and in having data at all"""
+    _sync_clean("loop")
+
+
+def test_sync_short_rows_and_the_history():
+    """rows of 1, L - 1, 126, 127, 128 and 300 symbols at L = 1, 64, 128: the history shifted by fewer than 127 symbols"""
+    _sync_clean("short rows")

@@ -446,6 +446,108 @@ def test_process_then_sync_on_one_stream_finds_every_frame(oracle_mod, deferred)
             pl.load().hipStreamDestroy(stream)
 
 
+# ---- 5a. workgroups that walk several pieces; rows of more than 64 pieces -----------------------------------------------------------
+
+def _comb_row(n, at):
+    """n copies of one symbol, turned by a quarter from at + 1 on for one symbol: the comb word hits at `at` and nowhere else"""
+    z = np.full(n, 0.8 - 0.3j)
+    z[np.asarray(at) + 1] *= 1j
+    x = np.empty(2 * n, F32)
+    x[0::2], x[1::2] = z.real, z.imag
+    return x
+
+
+def search_shared(h, rows, pick, set_hist=True):
+    """one sync_device call over len(pick) channels that share the device rows of `rows`: channel i searches rows[pick[i]] (None:
+    not searched).  The rows lie between guard bytes in one arena, as in search()."""
+    off, size = [], 0
+    for i, c in enumerate(rows):
+        start = -(-(size + GUARD) // 128) * 128 + (8 if i % 2 else 0)
+        off.append(start)
+        size = start + c.x.nbytes
+    size += GUARD
+    arena = np.full(size, GUARD_BYTE, np.uint8)
+    for o, c in zip(off, rows):
+        arena[o: o + c.x.nbytes] = c.x.view(np.uint8)
+    ins = (pl.SyncIn * len(pick))()
+    d = h.device_alloc(size)
+    try:
+        for i, k in enumerate(pick):
+            if k is None:
+                continue
+            c = rows[k]
+            ins[i] = pl.SyncIn(d + off[k], c.x.size // 2, c.slot + 1, c.flags, c.thr, 0)
+            if set_hist and c.hist is not None:
+                h.set_sync_history(i, c.hist)
+        h.upload(d, arena)
+        h.sync_device(0, ins)
+        recs = sm.as_np(h.sync_records(0, len(pick)))
+        back = h.download(d, (size,), np.uint8)
+        assert back.tobytes() == arena.tobytes(), "the call wrote into a row or a guard"
+    finally:
+        h.device_free(d)
+    return recs
+
+
+def test_two_thousand_channels_share_rows_of_one_to_five_pieces():
+    """700 channels, then 2100 on the same handle -- three workgroups a channel, then one that walks all five pieces; the
+    host's part0 runs over some 5000 partials and the scratch grows between the calls -- over six device rows of 1 .. 5 pieces,
+    continued and restarted; every ninth channel is not searched.  Records and histories are the model's and the host's."""
+    hist = _row(127, 77, WORDS[SLOT_OF[31]], at=(127 - 15,))
+    hits4 = [-1, 5, 900, P + 1] + [2 * P + 40 + 2 * i for i in range(20)] + [3 * P + 3, 3 * P + 9]
+    rows = [Case("shared comb 1", _comb_row(300, [7, 100]), COMB_SLOT, thr=0.999, flags=pl.SYNC_RESTART),
+            Case("shared L31 2", _planted(P + 400, 31, 8101), SLOT_OF[31], hist=hist),
+            Case("shared L128 3", _planted(2 * P + 127 + 60, 128, 8102), SLOT_OF[128], flags=pl.SYNC_RESTART),
+            Case("shared comb 4", _comb_row(3 * P + 500, hits4), COMB_SLOT, thr=0.999, hist=np.tile(np.array([0.8, -0.3], F32), 127)),
+            Case("shared L31 5", _planted(4 * P + 30 + 7, 31, 8104), SLOT_OF[31], flags=pl.SYNC_RESTART),
+            Case("shared L128 2", _planted(P + 9, 128, 8105), SLOT_OF[128], hist=_row(127, 78, WORDS[SLOT_OF[128]], at=(127 - 64,)))]
+    pieces = [len(sm.partials(WORDS[c.slot], c.thr, c.x, c.flags, c.hist)) for c in rows]
+    assert pieces == [1, 2, 3, 4, 5, 2]
+    models = [model_of(c) for c in rows]
+    assert int(models[3][0]["n_hits"]) == 26 and models[3][0]["hits"]["pos"][0] == -1  # (the history's last symbol starts a word)
+    h = _handle(2100, max_window_samples=16, max_phase_avg=1, max_packet_complex=64)
+    try:
+        for n in (700, 2100):
+            pick = [None if i % 9 == 4 else (i * 5 + i // 6) % 6 for i in range(n)]
+            assert {k for k in pick if k is not None} == set(range(6))
+            before = [h.sync_history(i).tobytes() for i in range(n) if pick[i] is None]
+            recs = search_shared(h, rows, pick)
+            for i, k in enumerate(pick):
+                if k is None:
+                    assert recs[i].tobytes() == bytes(sm.RECORD_BYTES), i
+                else:
+                    assert recs[i].tobytes() == models[k][0].tobytes(), (n, i, rows[k].name)
+                    assert h.sync_history(i).tobytes() == models[k][1].tobytes(), (n, i, rows[k].name)
+            assert before == [h.sync_history(i).tobytes() for i in range(n) if pick[i] is None], "a channel that is not searched keeps its history"
+    finally:
+        h.close()
+
+
+def test_a_row_of_131_pieces_alone_and_among_short_rows():
+    """130 P + 5 windows -- the join takes three trips over the partials -- with ten hits in front of piece 64 and ten from it
+    on: the 16th stored hit lies in the second trip.  Alone, then as channel 7 among 20 short rows: the same bytes."""
+    at = [p * P + 33 for p in (0, 5, 11, 20, 31, 40, 47, 55, 60, 63)] + [64 * P + 2 * i for i in range(6)] + [p * P + 1 for p in (65, 100, 128, 130)]
+    big = Case("131 pieces", _comb_row(130 * P + 6, at), COMB_SLOT, thr=0.999, flags=pl.SYNC_RESTART)
+    rec, _ = model_of(big)
+    assert int(rec["n_windows"]) == 130 * P + 5 and int(rec["n_hits"]) == 20 and [int(x) for x in rec["hits"]["pos"]] == at[:16]
+    assert at[9] < 64 * P <= at[10] and int(rec["best"]["pos"]) == at[0]
+    # (channel 0 goes on from the history the first call leaves there; the other channels of the fresh handle from zeros)
+    short = [Case("short beside 131 %d" % k, _planted(40 + 31 * k, WORD_LENGTHS[k % 6], 8200 + k), k % 6, flags=(0, pl.SYNC_RESTART)[k % 2],
+                  hist=model_of(big)[1] if k == 0 else None) for k in range(20)]
+    h = _handle(21)
+    try:
+        alone = search(h, [big])
+        check(h, [big], alone)
+        batch = short[:7] + [big] + short[7:]
+        recs = search(h, batch, set_hist=False)
+        assert bytes(recs[7]) == bytes(alone[0])
+        sm.assert_same(recs[7], rec, big.name)
+        assert h.sync_history(7).tobytes() == model_of(big)[1].tobytes()
+        check(h, batch, recs)
+    finally:
+        h.close()
+
+
 # ---- 6. more channels than a grid dimension holds ---------------------------------------------------------------------------------
 
 def test_sixty_six_thousand_channels_in_one_call():

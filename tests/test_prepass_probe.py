@@ -16,7 +16,13 @@ the whole wave, a tree one level short at four and at 32 lanes a block, a writte
 descriptor's index, n_pairs off by one at lag 128, a halo taken from the partner packet of the second trip, a second-trip packet
 skipped, and an acquire join without the partials 64 and above --; what the width, validity, edge and 70000-descriptor cases
 reach, against restatements of sr_width, the wave / sub walk of stage 1 and the grid rule; and acquire_model.device_record, the
-restated order of additions, held to the exact model_record on every acquire packet of the probe."""
+restated order of additions, held to the exact model_record on every acquire packet of the probe.
+
+The word search (psk_sync.hip) follows in the same order: the mirrors and the constants; sync_model.partials / join_bytes held to
+model_record and model_windows on every row of every case; the comparator on a numpy stand-in for fold and join -- clean on all
+nine cases, and fourteen injected faults (SYNC_FAULTS) each reported by the cases named there --; and what the cases reach: every
+word length on two pieces walked both ways, second and third pieces of a workgroup, the join's second and third trip, the cap of
+16 hits met in lane 0, in lane 63 and at the chunk edge, the channel loop's second trip, the shift of a short row's history."""
 import numpy as np
 import pytest
 
@@ -27,6 +33,7 @@ from tests import prepass_probe as pp
 from tests import prepass_probe_cases as pc
 from tests import resample_model as rm
 from tests import symrate_model as sm
+from tests import sync_model as ym
 from tests import tune_model as tm
 
 F32 = np.float32
@@ -1097,3 +1104,361 @@ def test_the_bound_of_a_long_acquire_packet_is_wider_than_one_float32_rounding()
     p = pc.acquire_lengths_case(False).protos[-1]
     exact, bound = am.model_record(p["iq"], p["M"])["sums"]["sum_re"][0]
     assert bound > 2.0 ** -24 and p["n"] == 65 * am.PIECE + 131
+
+
+# ---- the word search (psk_sync.hip): the mirrors, the models, the comparator on a SyncCase, what the cases reach ----------------------
+
+SP = ym.PIECE
+PART, REC = ym.PART_BYTES, ym.RECORD_BYTES
+
+
+def test_the_sync_mirrors_and_constants_are_the_models():
+    assert [pp.sizeof(k) for k in (12, 13, 14)] == [pp.SYNC_DESC.itemsize, PART, REC] == [80, 416, 456]
+    assert (pp.constant("sync_piece"), pp.constant("sync_threads"), pp.constant("sync_hist")) == (ym.PIECE, ym.THREADS, ym.HIST)
+    assert (pp.constant("sync_hist_slot_floats"), pp.constant("sync_max_word"), pp.constant("sync_hits")) == (256, ym.MAX_WORD, ym.HITS)
+    assert 4 * pp.constant("sync_hist_slot_floats") == pp.SYNC_SLOT_BYTES == pp.SYNC_HIST_BYTES + 8 and pl.sync_piece() == ym.PIECE
+    assert [ym.PART_DTYPE.fields[k][1] for k in ("n_valid", "n_hits", "best", "hits")] == [0, 4, 8, 32]
+    assert [pp.SYNC_DESC.fields[k][1] for k in ("soft", "word", "hist_in", "hist_out", "n", "p0", "n_windows", "part0", "n_piece", "channel",
+                                                "L", "flags", "threshold", "Ew")] == [0, 8, 16, 24, 32, 40, 48, 52, 56, 60, 64, 68, 72, 76]
+    # sync_grid restates front_grid_y: 2048 workgroups spread over the descriptors, no more than the longest row has pieces
+    assert [pp.sync_grid(n, 7) for n in (1, 256, 292, 293, 682, 683, 700, 1024, 1100, 2048, 2049, 2100, 66135)] == [7, 7, 7, 7, 4, 3, 3, 2, 2, 1, 1, 1, 1]
+    assert pp.sync_grid(1, 1 << 20) == 2048 and pp.sync_walk(7, 3) == [[0, 3, 6], [1, 4], [2, 5]] and pp.sync_walk(1, 3) == [[0], [], []]
+
+
+def _flags(p):
+    return ym.RESTART if p["restart"] else 0
+
+
+SYNC_MODELLED = ("lengths", "walk 700", "chunks", "loop", "short rows")  # (the other cases are made of the same rows)
+
+
+@pytest.mark.parametrize("name", SYNC_MODELLED)
+def test_sync_the_partials_of_every_row_join_to_the_models_record(name):
+    """partials is not its own judge: join_bytes of the partials of every row of every case is model_record's record, the
+    history model_windows'; the chunked join below -- the device's trips of 64 -- agrees with both"""
+    case = pc.SYNC_CASES[name]()
+    for k, p in enumerate(case.protos):
+        rec, hist = ym.model_record(p["word"], p["thr"], p["x"], _flags(p), p["hist"])
+        assert p["record"] == rec.tobytes(), (name, k)
+        assert p["hist_out"].tobytes() == hist.tobytes() == ym.model_windows(p["word"], p["x"], _flags(p), p["hist"])[-1].tobytes(), (name, k)
+        assert _sync_join(p["parts"], p["n"], p["n_windows"], p["L"]) == p["record"], (name, k)
+        assert int(rec["n_windows"]) == p["n_windows"] and len(p["parts"]) == max(1, -(-p["n_windows"] // SP))
+        for q in p["parts"]:
+            assert q["n_hits"] <= q["n_valid"] <= SP and len(q["hits"]) == min(q["n_hits"], ym.HITS) and (q["best"] is None) == (q["n_valid"] == 0)
+
+
+# ---- a numpy stand-in for the two kernels, and the faults a wrong kernel would make --------------------------------------------------
+
+def _sync_join(parts, n, n_windows, L, fault=None):
+    """the record as psk_sync_join_kernel makes it: trips of 64 partials, `before` = the hits of the trips before plus a scan
+    of this one, the best of a trip merged into the best so far.  fault: what a wrong join would do."""
+    rec = np.zeros((), ym.RECORD_DTYPE)
+    rec["n_symbols"], rec["n_windows"], rec["word_len"], rec["flags"] = n, n_windows, L, ym.DATA
+    nv = nh = 0
+    best, seventeenth = None, None
+    later = fault == "best_later_pieces"
+    for base in range(0, len(parts), pp.JOIN_CHUNK):
+        chunk = parts[base: base + pp.JOIN_CHUNK]
+        before = 0 if fault == "before_drops_nh" else nh
+        mine = None
+        for q in chunk:
+            ph = int(q["n_hits"])
+            if ph and before < ym.HITS:
+                take = min(ph, ym.HITS - before)
+                rec["hits"][before: before + take] = q["hits"][:take]
+            elif ph and before == ym.HITS and seventeenth is None:
+                seventeenth = q["hits"][0]
+            if ph > ym.HITS - before >= 0 and seventeenth is None and len(q["hits"]) > ym.HITS - before:
+                seventeenth = q["hits"][ym.HITS - before]
+            before += ph
+            if q["n_valid"] and (mine is None or q["best"]["m"] > mine["m"] or (later and q["best"]["m"] == mine["m"])):
+                mine = q["best"]
+            nv, nh = nv + int(q["n_valid"]), nh + ph
+        if mine is not None and (best is None or mine["m"] > best["m"] or (fault in ("best_later_pieces", "best_later_chunks") and mine["m"] == best["m"])):
+            best = mine
+    rec["n_valid"], rec["n_hits"] = nv, nh
+    if best is not None:
+        rec["best"] = best
+    out = bytearray(rec.tobytes())
+    if fault == "hit17_join" and seventeenth is not None:
+        at = ym.RECORD_DTYPE.fields["hits"][1] + ym.HITS * ym.HIT_BYTES
+        out[at:] = seventeenth.tobytes()[: REC - at]  # (hits[16]: it lies on word_len, flags and the pad)
+    return bytes(out)
+
+
+SYNC_FAULTS = {
+    "walk_stops": ("walk 2100", "lengths spread"),     # a walk that stops after gridDim.x pieces
+    "stale_hits": ("walk 700", "walk 2100"),           # a second piece's hits taken from the first piece's list
+    "before_drops_nh": ("chunks", "join alone"),       # nh of the earlier chunks dropped from `before`
+    "hit17_fold": ("walk 1100",),                      # a 17th hit stored by the fold
+    "hit17_join": ("join alone", "chunks"),            # ... and by the join
+    "best_later_pieces": ("walk 700",),                # the later of two equal bests kept, across pieces
+    "best_later_chunks": ("chunks", "join alone"),     # ... and across chunks only
+    "best_no_valid": ("walk 1100", "short rows"),      # best written for a piece with no valid window
+    "hit_past": ("short rows", "lengths"),             # hits[min(n_hits, 16)] written
+    "hist_1024": ("short rows",),                      # 1024 bytes of history written
+    "hist_read_restart": ("short rows",),              # hist_in read under restart
+    "spare_record": ("lengths",),                      # a record written for a spare channel
+    "no_zero_record": ("loop", "lengths spread"),      # no zero record for a descriptor without data
+    "next_part0": ("walk 700", "loop"),                # a partial written through the next descriptor's part0
+}
+
+
+def _sync_written(case, fault=None):
+    """The arena after a stand-in for fold and join that stores what the models say and nothing else -- the partials through
+    partial_writes, piece by piece as the workgroups walk them; the record by _sync_join --, or with one fault."""
+    after = case.image.copy()
+    late = []  # stores that no rightful store may cover: the workgroups run in no order
+
+    def put(off, b):
+        after[off: off + len(b)] = np.frombuffer(bytes(b), np.uint8)
+
+    nxt = dict(zip(case.searched, case.searched[1:]))
+    for i, (k, data) in enumerate(case.uses):
+        p = case.protos[k]
+        rec_at = case.rec_off + case.channel[i] * REC
+        if not data:
+            if case.which & 2 and fault != "no_zero_record":
+                put(rec_at, bytes(REC))
+            continue
+        parts = list(p["parts"])
+        if case.which & 1:
+            owner = [y for y, walk in enumerate(pp.sync_walk(len(parts), case.per)) for _ in walk]
+            assert sorted(q for walk in pp.sync_walk(len(parts), case.per) for q in walk) == list(range(len(parts))) and len(owner) == len(parts)
+            if fault == "walk_stops":
+                parts = [q if j < case.per else None for j, q in enumerate(parts)]
+            if fault == "stale_hits":
+                for j in range(case.per, len(parts)):
+                    prev, own = p["parts"][j - case.per]["hits"], parts[j]["hits"].copy()
+                    own[: min(len(prev), len(own))] = prev[: min(len(prev), len(own))]
+                    parts[j] = dict(parts[j], hits=own)
+            base = case.part0[nxt[i]] if fault == "next_part0" and i in nxt else case.part0[i]
+            for j, q in enumerate(parts):
+                if q is None:
+                    continue
+                o = case.part_off + (base + j) * PART
+                for off, b in ym.partial_writes(q):
+                    put(o + off, b)
+                kept = min(int(q["n_hits"]), ym.HITS)
+                if fault == "best_no_valid" and not q["n_valid"]:
+                    put(o + 8, bytes(ym.HIT_BYTES))
+                if fault == "hit_past" and kept < ym.HITS:
+                    put(o + 32 + ym.HIT_BYTES * kept, bytes(ym.HIT_BYTES))
+                if fault == "hit17_fold" and q["n_hits"] > ym.HITS:
+                    late.append((o + PART, q["hits"][ym.HITS - 1].tobytes()))
+            h = p["hist_out"]
+            if fault == "hist_read_restart" and p["restart"]:
+                h = np.concatenate([np.frombuffer(pp.nan_poison(pp.SYNC_HIST_BYTES).tobytes(), F32), p["x"]])[-2 * ym.HIST:]
+            put(int(case.desc["hist_out"][i]), h.tobytes() + (bytes(8) if fault == "hist_1024" else b""))
+        if case.which & 2:
+            put(rec_at, _sync_join([q for q in parts if q is not None], p["n"], p["n_windows"], p["L"], fault))
+    if fault == "spare_record":
+        put(case.rec_off + case.spare_channels[len(case.spare_channels) // 2] * REC, bytes(REC))
+    for off, b in late:
+        put(off, b)
+    return after
+
+
+@pytest.mark.parametrize("name", sorted(pc.SYNC_CASES))
+def test_sync_a_correct_writer_is_clean_on_every_case(name):
+    case = pc.SYNC_CASES[name]()
+    found = case.check(_sync_written(case))
+    assert found == [], pp.messages(found)
+    nothing = case.check(case.image)
+    assert nothing and {f["where"] for f in nothing} <= {"partial", "record", "hist_out"}, "an arena nothing was written to is not clean"
+    # the layout has what a wrong store would hit
+    assert case.spare and case.spare_channels and list(case.desc["channel"]) != list(range(len(case.desc)))
+    assert [case.part0[i] for i in case.searched] != sorted(case.part0[i] for i in case.searched) or len(case.searched) < 3
+
+
+@pytest.mark.parametrize("fault", sorted(SYNC_FAULTS))
+def test_sync_every_fault_is_reported_by_its_cases(fault):
+    for name in SYNC_FAULTS[fault]:
+        case = pc.SYNC_CASES[name]()
+        found = case.check(_sync_written(case, fault))
+        assert found, "%s goes unseen by %s" % (fault, name)
+        where = {f["where"] for f in found}
+        if fault in ("before_drops_nh", "hit17_join", "best_later_pieces", "best_later_chunks"):
+            assert where == {"record"}, pp.messages(found)
+            want = {"before_drops_nh": ("hits",), "hit17_join": ("word_len",), "best_later_pieces": ("best",), "best_later_chunks": ("best",)}[fault]
+            assert all(f["field"].startswith(want) for f in found), pp.messages(found)
+        elif fault in ("hist_1024",):
+            assert where == {"hist_pad"}, pp.messages(found)
+        elif fault in ("hist_read_restart",):
+            assert where == {"hist_out"}, pp.messages(found)
+        elif fault == "spare_record":
+            assert where == {"spare_record"} and len(found) == 1, pp.messages(found)
+        elif fault == "no_zero_record":
+            assert where == {"record"} and all(f["got"] == "c3" * 8 for f in found), pp.messages(found)
+        elif fault in ("best_no_valid", "hit_past"):
+            assert where == {"partial"} and all(f["field"].startswith(("best", "hits")) for f in found), pp.messages(found)
+
+
+def test_sync_the_faults_across_chunks_need_rows_of_more_than_64_pieces():
+    """what the suite's rows of at most four pieces could not show: each of these goes unseen by the walk cases"""
+    case = pc.SYNC_CASES["walk 700"]()
+    for fault in ("before_drops_nh", "best_later_chunks"):
+        assert case.check(_sync_written(case, fault)) == [], fault
+
+
+# ---- what the sync cases reach -----------------------------------------------------------------------------------------------------------
+
+def _piece_of(p, pos):
+    return (int(pos) - p["p0"]) // SP
+
+
+def test_sync_lengths_reach_every_word_length_on_two_pieces_walked_both_ways():
+    one, two = pc.SYNC_CASES["lengths"](), pc.SYNC_CASES["lengths spread"]()
+    assert (len(one.desc), one.per, one.max_piece) == (256, 2, 2) and (len(two.desc), two.per, two.max_piece) == (256 + 1900, 1, 2)
+    assert pp.sync_walk(2, 2) == [[0], [1]] and pp.sync_walk(2, 1) == [[0, 1]]
+    assert sorted((p["L"], p["restart"]) for p in one.protos) == [(L, r) for L in range(1, 129) for r in (False, True)]
+    for p in one.protos:
+        L = p["L"]
+        assert p["n_windows"] == SP + 65 and len(p["parts"]) == 2 and p["n"] == SP + 65 + (L - 1 if p["restart"] else 0)
+        # the second piece: one full turn of wave 0 and one lane of its second
+        assert p["n_windows"] - SP == 64 + 1 and p["parts"][1]["n_valid"] == 65
+        hits = [int(h) for h in np.frombuffer(p["record"], ym.RECORD_DTYPE)[0]["hits"]["pos"][: min(16, sum(q["n_hits"] for q in p["parts"]))]]
+        if not p["restart"] and L >= 2:
+            assert -(L // 2) in hits, "L %d: the word across the row's start is found through hist_in" % L
+        assert all(q["n_hits"] >= 1 for q in p["parts"]), L
+    # the same rows, the same expected bytes
+    for k, i in enumerate(two.searched):
+        assert two.uses[i] == (k, True) and two.record_bytes(two.want, i) == one.record_bytes(one.want, k)
+        assert [two.partial_bytes(two.want, i, q) for q in (0, 1)] == [one.partial_bytes(one.want, k, q) for q in (0, 1)]
+    assert sum(1 for _, data in two.uses if not data) == 1900
+
+
+def test_sync_walk_cases_reach_second_and_third_pieces_of_a_workgroup():
+    cases = {n: pc.sync_walk(n) for n in pc.SYNC_WALK_SHAPES}
+    assert [cases[n].per for n in pc.SYNC_WALK_SHAPES] == [3, 2, 1] and all(c.max_piece == 7 for c in cases.values())
+    pr = cases[700].protos
+    assert [len(p["parts"]) for p in pr] == [7, 5, 4, 3, 2, 4, 1, 2, 1, 1, 3, 5]
+    assert {(p["L"], p["restart"]) for p in pr} == {(2, True), (2, False), (31, True), (31, False), (128, True), (128, False)}
+    walks = pp.sync_walk(7, 3)
+    assert max(len(w) for w in walks) == 3 and len({len(w) for w in walks}) == 2, "three pieces for one workgroup, and a ragged walk"
+    assert pp.sync_walk(1, 3)[1:] == [[], []] and pp.sync_walk(2, 3)[2] == [], "blockIdx.x >= n_piece beside a channel of seven"
+    for n, c in cases.items():
+        used = {k for k, data in c.uses if data}
+        assert used == set(range(12)) and sum(1 for _, data in c.uses if not data) > n // 10
+        near = [(len(c.protos[c.uses[i][0]]["parts"]), len(c.protos[c.uses[i + 1][0]]["parts"])) for i in range(n - 1) if c.uses[i][1] and c.uses[i + 1][1]]
+        assert {(7, 1), (1, 7)} & set(near) or {(7, 2), (2, 7)} & set(near)
+    # hits in every piece
+    assert all(q["n_hits"] >= 3 for q in pr[0]["parts"]) and all(q["n_hits"] >= 1 for q in pr[5]["parts"])
+    # more than 16 hits in a piece that is not its workgroup's first, at every shape, hits of the piece before under them, and
+    # fewer hits in the piece the workgroup takes next
+    cp, _, cn = pc.SYNC_WALK_CROWD
+    assert pr[0]["parts"][cp]["n_hits"] == cn + 3 > ym.HITS
+    for per in (3, 2, 1):
+        assert cp >= per and pr[0]["parts"][cp - per]["n_hits"] == 3 and pr[0]["parts"][cp + per]["n_hits"] == 3
+    assert [q["n_hits"] for q in pr[10]["parts"]] == [2, 18, 18]
+    # a piece without a valid window between two with
+    z = pr[1]["parts"]
+    assert z[pc.SYNC_WALK_ZEROS]["n_valid"] == 0 and z[pc.SYNC_WALK_ZEROS]["best"] is None and z[1]["n_valid"] == SP and z[3]["n_valid"] == SP
+    assert np.frombuffer(pr[1]["record"], ym.RECORD_DTYPE)[0]["hits"]["pos"][0] == -1
+    # equal bests in the four pieces of the periodic row: pieces 0 and 3 share a workgroup of three, 0 and 1 do not
+    bests = [q["best"] for q in pr[2]["parts"]]
+    assert len({b.tobytes()[8:] for b in bests}) == 1 and [int(b["pos"]) for b in bests] == [int(bests[0]["pos"]) + SP * k for k in range(4)]
+    assert np.frombuffer(pr[2]["record"], ym.RECORD_DTYPE)[0]["best"]["pos"] == bests[0]["pos"]
+    assert 0 in walks[0] and 3 in walks[0] and 1 in walks[1]
+    # the NaN at the piece edge takes the windows that meet it, on both sides
+    assert pr[11]["parts"][1]["n_valid"] == SP - 30 and pr[11]["parts"][2]["n_valid"] == SP - 1
+
+
+def test_sync_chunk_cases_reach_the_joins_second_and_third_trip():
+    case = pc.SYNC_CASES["chunks"]()
+    pr = case.protos
+    assert tuple(len(p["parts"]) for p in pr) == pc.SYNC_CHUNK_PIECES and case.per == 130 and pr[7]["n_windows"] % SP != 0
+    assert [(p["L"], p["restart"]) for p in pr[:8]] == [(2, r) for r in (True, False, True, False, True, False, True, False)]
+    rec = [np.frombuffer(p["record"], ym.RECORD_DTYPE)[0] for p in pr]
+    chunk_hits = lambda p, c: sum(q["n_hits"] for q in p["parts"][64 * c: 64 * c + 64])  # noqa: E731
+    # 2: the cap is met in lane 63 of the first trip; 3: the 16th stored hit lies in the second
+    assert (chunk_hits(pr[2], 0), rec[2]["n_hits"]) == (20, 20) and _piece_of(pr[2], rec[2]["hits"]["pos"][15]) == 63
+    assert (chunk_hits(pr[3], 0), chunk_hits(pr[3], 1), rec[3]["n_hits"]) == (10, 10, 20) and _piece_of(pr[3], rec[3]["hits"]["pos"][15]) == 64
+    assert _piece_of(pr[3], rec[3]["hits"]["pos"][9]) < 64 <= _piece_of(pr[3], rec[3]["hits"]["pos"][10])
+    # 4: hits in the second chunk only
+    assert (chunk_hits(pr[4], 0), chunk_hits(pr[4], 1), rec[4]["n_hits"]) == (0, 4, 4) and _piece_of(pr[4], rec[4]["hits"]["pos"][0]) == 64
+    # 5: 20 hits in one piece of chunk 0, then three in chunk 1: counted, none stored
+    assert pr[5]["parts"][5]["n_hits"] == 20 and chunk_hits(pr[5], 1) == 3 and rec[5]["n_hits"] == 23
+    assert {_piece_of(pr[5], x) for x in rec[5]["hits"]["pos"]} == {5}
+    # 6: the cap met in the third trip; 7: ten either side of piece 64, 130 pieces
+    assert [chunk_hits(pr[6], c) for c in range(3)] == [5, 5, 10] and _piece_of(pr[6], rec[6]["hits"]["pos"][15]) == 128
+    assert [chunk_hits(pr[7], c) for c in range(3)] == [10, 8, 2] and rec[7]["n_hits"] == 20
+    # 8: the best of the second chunk is strictly greater than every best before it
+    b = [q["best"]["m"] for q in pr[8]["parts"]]
+    assert pr[8]["L"] == 31 and _piece_of(pr[8], rec[8]["best"]["pos"]) == 64 and b[64] > max(b[:64]) and b[64] > max(b[65:])
+    assert rec[8]["n_valid"] == pr[8]["n_windows"] == 65 * SP + 40
+    # 9: equal bests in chunk 0 and chunk 1: the first
+    b = pr[9]["parts"]
+    assert b[10]["best"].tobytes()[8:] == b[65]["best"].tobytes()[8:] and _piece_of(pr[9], rec[9]["best"]["pos"]) == 10
+    assert all(q["best"]["m"] < b[10]["best"]["m"] for j, q in enumerate(b) if j not in (10, 65))
+    # the totals of a trip fit 32 bits, the counts are 64-bit sums of them
+    assert all(int(r["n_valid"]) == sum(q["n_valid"] for q in p["parts"]) for r, p in zip(rec, pr)) and int(rec[7]["n_valid"]) > 64 * SP
+
+
+def test_sync_join_alone_reaches_the_cap_in_lane_0_lane_63_and_at_the_chunk_edge():
+    case = pc.SYNC_CASES["join alone"]()
+    assert case.which == 2 and [len(p["parts"]) for p in case.protos[:4]] == [1, 64, 65, 200]
+    by = {p["name"]: p for p in case.protos}
+    rec = {k: np.frombuffer(p["record"], ym.RECORD_DTYPE)[0] for k, p in by.items()}
+    assert int(rec["full 200"]["n_valid"]) == int(rec["full 200"]["n_hits"]) == 204800
+    assert rec["full 200"]["hits"].tobytes() == by["full 200"]["parts"][0]["hits"].tobytes()
+
+    def met(p):
+        """(the piece in which the 16th hit lies, the hits in front of that piece)"""
+        total = 0
+        for j, c in enumerate(p["counts"]):
+            if total + c >= ym.HITS:
+                return j, total
+            total += c
+
+    assert met(by["lane 0"]) == (0, 0) and met(by["lane 63"]) == (63, 0) and met(by["chunk edge"]) == (64, 15) and met(by["second chunk"]) == (64, 0)
+    assert met(by["cycle"]) == (2, 1)
+    for name in ("cycle", "lane 0", "lane 63", "chunk edge", "second chunk"):
+        p = by[name]
+        assert len(p["parts"]) == 130 and set(p["counts"]) == set(pc.SYNC_HIT_COUNTS), name
+        assert any(q["n_valid"] == 0 for q in p["parts"]) and len({float(q["best"]["m"]) for q in p["parts"] if q["n_valid"]}) == 11
+    # the best of several equal maxima, in chunk 0 and in chunk 1, is the first
+    top = [j for j, q in enumerate(by["full 200"]["parts"]) if q["best"]["m"] == rec["full 200"]["best"]["m"]]
+    assert top[0] < 64 <= top[-1] and int(rec["full 200"]["best"]["pos"]) == top[0] * SP + 517
+    # NaN poison in every member partial_writes does not list
+    poison = pp.nan_poison(ym.HIT_BYTES).tobytes()
+    for i in case.searched:
+        for j, q in enumerate(case.protos[case.uses[i][0]]["parts"]):
+            b = case.partial_bytes(case.image, i, j)
+            kept = min(q["n_hits"], ym.HITS)
+            assert b[32 + 24 * kept:] == poison * (ym.HITS - kept) and (b[8:32] == poison) == (q["n_valid"] == 0)
+            assert b[32: 32 + 24 * kept] == q["hits"].tobytes()
+
+
+def test_sync_loop_reaches_the_second_trip_with_partners_that_differ():
+    case = pc.SYNC_CASES["loop"]()
+    n = len(case.desc)
+    assert n == pc.SYNC_LOOP_DESCRIPTORS == 65535 + 600 and pp.look_trips(n) == 2 and case.per == 1 and case.max_piece == 5
+    assert 65535 * REC < case.arena.size <= 32 << 20 and len(case.searched) == 60  # (nearly all of it records)
+    kinds = []
+    for k in range(pc.SYNC_LOOP_PAIRS):
+        i = pc.sync_loop_first(k)
+        (ka, da), (kb, db) = case.uses[i], case.uses[i + pp.LOOK_GRID_MAX]
+        a, b = case.protos[ka], case.protos[kb]
+        shape = lambda p, d: (p["L"], len(p["parts"])) if d else None  # noqa: E731
+        kinds.append({((128, 1), (3, 5)): 0, ((3, 5), (128, 1)): 1}.get((shape(a, da), shape(b, db)), 2 if da and not db else 3 if db and not da else None))
+    assert kinds == [k % 4 for k in range(pc.SYNC_LOOP_PAIRS)]
+    assert {case.uses[i][0] for i in case.searched} == {0, 1, 2, 3}
+    paired = {pc.sync_loop_first(k) + t for k in range(pc.SYNC_LOOP_PAIRS) for t in (0, pp.LOOK_GRID_MAX)}
+    assert all(not data for i, (_, data) in enumerate(case.uses) if i not in paired)
+
+
+def test_sync_short_rows_shift_the_history():
+    case = pc.SYNC_CASES["short rows"]()
+    seen = set()
+    for p in case.protos:
+        L, n = p["L"], p["n"]
+        seen.add((L, n, p["restart"]))
+        front = np.zeros(2 * ym.HIST, F32) if p["restart"] else p["hist"]
+        assert p["hist_out"].tobytes() == np.concatenate([front, p["x"]])[-2 * ym.HIST:].tobytes()
+        if n < ym.HIST:
+            assert p["hist_out"][: 2 * (ym.HIST - n)].tobytes() == front[2 * n:].tobytes()
+        assert p["n_windows"] == (max(0, n - L + 1) if p["restart"] else n) and len(p["parts"]) == 1
+    assert seen == {(L, n, r) for L in pc.SYNC_SHORT_L for n in pc.sync_short_lengths(L) for r in (False, True)}
+    assert any(p["n_windows"] == 0 and p["parts"][0]["best"] is None for p in case.protos), "a restarted row shorter than its word"
+    assert {int(d["soft"]) % 128 for d in case.desc} == {0, 8}

@@ -89,6 +89,18 @@ def test_sync_host_against_the_model(L):
                     assert nw == (max(0, n - L + 1) if flags else n), ctx
 
 
+def test_sync_host_against_the_model_on_rows_of_up_to_130_pieces():
+    """the rows the probe searches for the join's second and third trip (tests/prepass_probe_cases.py): 1 .. 130 pieces of 1024
+    windows -- the first rows beyond four pieces the host definition meets -- with hits either side of piece 64"""
+    from tests import prepass_probe_cases as pc
+
+    rows = pc.sync_chunk_protos()
+    for k, p in enumerate(rows):
+        rec, _ = _check_host(p["word"], p["thr"], p["x"], pl.SYNC_RESTART if p["restart"] else 0, p["hist"], "chunk row %d" % k)
+        assert -(-rec.n_windows // sm.PIECE) == pc.SYNC_CHUNK_PIECES[k], k
+    assert max(pc.SYNC_CHUNK_PIECES) == 130 and sum(1 for n in pc.SYNC_CHUNK_PIECES if n > 64) >= 6
+
+
 def test_a_word_at_every_position_across_the_history_boundary():
     """the stream's word starts k symbols in front of the row, k = 0 .. L: the hit is at -k (none at k = L: that window was the
     call before's), its metric that of the window wholly inside a row"""
