@@ -856,6 +856,129 @@ uint64_t psk_soft_sync_bytes(void);         /* sizeof(psk_soft_sync_t), for bind
 uint64_t psk_soft_sync_in_bytes(void);      /* sizeof(psk_soft_sync_in_t), for bindings */
 uint32_t psk_soft_sync_piece(void);         /* windows of one piece of the device's fold (tests: the counts at its edges) */
 
+/* ---- frames as soft bits: segments of the soft rows as per-bit LLRs (psk_soft_demap_device) -------------------------------------
+ * psk_soft_sync_derive says at which symbol a frame starts and by which multiple of 2 pi / M the constellation is turned.  A
+ * decoder behind the demodulator eats per-bit soft decisions, not complex points.  This call cuts segments out of rows that are
+ * already in device memory, turns each by a complex gain, forms max-log LLRs against a constellation the caller defines and writes
+ * them where the caller wants them, as float32 or as saturated int8; it leaves one small record per segment, from which the
+ * host gets the noise level that scales the next frame's LLRs.  A frame is one segment, or one segment per row it lies across.
+ *
+ * The call touches no demodulator state, statistics, quality, look or sync records and no history: psk_soft_peek, psk_soft_query,
+ * the state blob, the statistics and the results of every later call are what they are without it.  The rows, the sync history and
+ * the maps are read, never written.
+ *
+ * All arithmetic is float32, every operation rounded once, no fused multiply-add, denormals kept, unless doubles are named.
+ * Maps.  The handle keeps PSK_SOFT_DEMAP_SLOTS numbered maps (psk_soft_demap_define): M = 2, 4 or 8 finite complex float32 points
+ *   p[0] .. p[M-1], interleaved (re, im), as the caller expects them in `soft` at rotation 0, and labels[k], the B-bit label of
+ *   point k, B = log2 M; the labels are a permutation of 0 .. M-1, so every bit has points on both sides.  Bit j (j = 0 .. B-1)
+ *   of a symbol is (label >> (B-1-j)) & 1: MSB first.
+ * Segments.  One psk_soft_demap_in_t per segment: symbol i of the segment is symbol pos + i of the row of n_symbols (re, im) pairs
+ *   at `soft`; pos + count <= n_symbols.  Without PSK_SOFT_DEMAP_FRONT pos >= 0.  With it pos >= -127, and the positions -127 .. -1
+ *   are the sync history in front of the row that the LAST psk_soft_sync_device call over `channel` searched -- the history that
+ *   call read (zeros if it had PSK_SOFT_SYNC_RESTART) --, which is what lets a frame be cut whose word that call found at a negative
+ *   position.  The handle remembers per channel whether the last sync call that covered it searched it, and with which flags;
+ *   FRONT on any other channel is refused (a sync call that fails after its launches began leaves its channels not searched).
+ *   The caller enqueues the demap on the stream of that sync call and ahead of the next sync call over the channel: that ordering
+ *   is the caller's and is not checked.
+ * Per symbol x, with g = (gain_re, gain_im):
+ *     y.re = x.re*g.re - x.im*g.im     y.im = x.re*g.im + x.im*g.re     (the two products rounded, then the sum or difference)
+ *     e = y.re*y.re + y.im*y.im
+ *     for k = 0 .. M-1:  dr = y.re - p[k].re,  di = y.im - p[k].im,  d[k] = dr*dr + di*di
+ *   A minimum over a set of k is the FIRST minimum, k ascending from the set's first member: a later one must compare less, so a
+ *   NaN in the first member stays.  dmin is that minimum over all k; for each bit j
+ *     l = min{d[k] : bit j of label k is 1} - min{d[k] : bit j is 0},    v = l * scale
+ *   so a positive v means bit 0 is the nearer.
+ * Output.  Value i*B + j of the segment is v of bit j of symbol i.  float32: ((float *)out)[i*B + j] = v as it is, but a NaN as
+ *   the quiet NaN 0x7fc00000 (sign and payload of a NaN differ between machines; the bytes must not); `out` 4-byte aligned.
+ *   With PSK_SOFT_DEMAP_I8: ((int8_t *)out)[i*B + j] = rintf(v) (ties to even), clamped to -127 .. 127, a NaN written as 0; `out`
+ *   may have any byte alignment, so the segments of one frame abut in the frame's buffer.  Exactly count*B values are written and
+ *   no byte outside them.  The outputs of a call's segments must not overlap: that is the caller's duty and is not checked.
+ * Record.  One psk_soft_demap_t per segment of the LAST call, in the order of `in`.  A symbol is FINITE when y.re, y.im, e and dmin
+ *   are all finite.  sum_e and sum_err add e and dmin of the finite symbols, each term widened exactly to double, in a fixed order
+ *   that depends on the symbol's index in the segment only: pieces of psk_soft_demap_piece() = 1024 symbols; lane t of 256 adds
+ *   its symbols t, t + 256, t + 512, t + 768 of the piece in that order, from 0.0; a xor tree across each wave of 64 lanes, offsets
+ *   32 .. 1 (every lane: s += the s of lane ^ offset); the four waves in order, from wave 0's value; the pieces in ascending
+ *   order, from piece 0's.  No floating-point atomics.  Because the order depends on the segment only, a frame cut into two
+ *   segments gives two records whose counts add, but whose sums need not equal -- to the last bits -- the sums of the frame
+ *   demapped as one segment.  sigma^2 = sum_err / (2 n_finite) is the decision-directed noise power per component. */
+#define PSK_SOFT_DEMAP_SLOTS        16
+#define PSK_SOFT_DEMAP_MAX_SEGMENTS (1u << 20)
+enum { PSK_SOFT_DEMAP_I8 = 1, PSK_SOFT_DEMAP_FRONT = 2 };                           /* psk_soft_demap_in_t.flags */
+/* psk_soft_demap_t.flags: DATA or PLANNED, ORed with REC_I8 -- the segment's PSK_SOFT_DEMAP_I8 bit shifted left by one */
+enum { PSK_SOFT_DEMAP_DATA = 1, PSK_SOFT_DEMAP_REC_I8 = 2, PSK_SOFT_DEMAP_PLANNED = 128 };
+enum { PSK_SOFT_DEMAP_GAIN_RESIDUAL = 1, PSK_SOFT_DEMAP_GAIN_UNIT = 2 };            /* psk_soft_demap_gain flags */
+
+typedef struct psk_soft_demap_in {
+    const float *soft;    /* DEVICE pointer to the row's symbol 0, 8-byte aligned; NULL: the segment is skipped             */
+    uint64_t n_symbols;   /* length of that row; below 2^30                                                                */
+    int64_t pos;          /* first symbol of the segment, relative to the row                                              */
+    void *out;            /* DEVICE pointer to the output: count*B float32 (4-byte aligned) or int8 (any alignment)        */
+    uint32_t count;       /* symbols in the segment; 0: the segment is skipped                                             */
+    uint32_t channel;     /* used only with PSK_SOFT_DEMAP_FRONT: the channel whose sync history lies in front of the row   */
+    uint32_t map;         /* 1 + the slot of the map; 0: the segment is skipped                                            */
+    uint32_t flags;       /* PSK_SOFT_DEMAP_I8, PSK_SOFT_DEMAP_FRONT                                                       */
+    float gain_re, gain_im;   /* the complex gain; finite                                                                  */
+    float scale;          /* the LLR scale; finite                                                                         */
+    uint32_t pad;         /* zero                                                                                          */
+} psk_soft_demap_in_t;    /* 64 bytes */
+
+typedef struct psk_soft_demap {          /* one per segment of the LAST psk_soft_demap_device call */
+    uint64_t n_symbols;                  /* the segment's count                                                            */
+    uint64_t n_finite;                   /* symbols whose y.re, y.im, e and dmin are all finite                            */
+    uint64_t n_clip;                     /* int8 values the clamp changed (+-inf counts); 0 for float32                    */
+    uint64_t n_nan;                      /* output values that were NaN                                                    */
+    double sum_e, sum_err;               /* sums of e and of dmin over the finite symbols, in the order above              */
+    uint32_t bits, flags;                /* B; PSK_SOFT_DEMAP_DATA or _PLANNED, | PSK_SOFT_DEMAP_REC_I8 for an int8 segment */
+    uint32_t pad[2];                     /* zero                                                                           */
+} psk_soft_demap_t;                      /* 64 bytes */
+
+/* The map of slot `slot` (0 .. PSK_SOFT_DEMAP_SLOTS - 1), copied into memory the handle owns; a segment names it as map = slot + 1.
+ * Redefining a slot waits for the handle's last demap launch first.  A control-plane-only handle records M only.
+ * PSK_SOFT_ERR_INVALID_ARG: null pointer, slot out of range, M other than 2, 4, 8, a non-finite point, labels that are not a
+ * permutation of 0 .. M-1. */
+psk_soft_status psk_soft_demap_define(psk_soft_handle_t *h, uint32_t slot, uint32_t M, const float *points /* [2 M] */,
+                                      const uint8_t *labels /* [M] */);
+
+/* The segments in[0 .. nseg-1], nseg = 1 .. PSK_SOFT_DEMAP_MAX_SEGMENTS: the call covers segments, not channels.  The rows must be
+ * complete on `stream` (a process call and a sync call enqueued there just before are); with PSK_SOFT_OPT_DEFERRED_JOIN pending
+ * the call joins the side streams into `stream` first, as the sync entry does.  The call returns without waiting.  The records live
+ * in memory the handle owns, grown on demand; every call replaces them.
+ * A segment with count == 0, map == 0 or soft == NULL is skipped: it gets the all-zero record, nothing is written to its `out`
+ * and nothing else of it is looked at.
+ * Refusals (PSK_SOFT_ERR_INVALID_ARG before anything is enqueued or any record changes): a null pointer, nseg out of range; on a
+ * segment that is not skipped a slot out of range or never defined, unknown flag bits, a non-zero pad, a `soft` that is not
+ * 8-byte aligned, a null `out` or one that is not 4-byte aligned for float32, n_symbols >= 2^30, pos + count > n_symbols,
+ * pos < 0 without PSK_SOFT_DEMAP_FRONT or pos < -127 with it, FRONT on a channel out of range or on one whose last covering sync
+ * call did not search it, a gain or scale that is not finite.
+ * How: two launches on `stream`.  The fold's grid is pieces x segments (more than 65535 segments take further trips of the segment
+ * loop); consecutive lanes take consecutive symbols with one 8-byte load each, the map is wave-uniform, the values are staged in
+ * LDS and stored as full dwords, with byte stores only at the unaligned head and tail of an int8 piece.  The join, one wave per
+ * segment, adds the pieces' partials in order and writes the record.
+ * A control-plane-only handle checks the arguments, then leaves records with n_symbols, bits and flags = PSK_SOFT_DEMAP_PLANNED
+ * (| PSK_SOFT_DEMAP_REC_I8), everything else zero. */
+psk_soft_status psk_soft_demap_device(psk_soft_handle_t *h, uint32_t nseg, const psk_soft_demap_in_t *in /* [nseg] */, void *stream);
+/* waits like psk_soft_get_sync does and copies the records of the segments [first, first + n) of the last call out.
+ * PSK_SOFT_ERR_INVALID_ARG: a null pointer, n == 0, a range beyond the last call's nseg, no call yet. */
+psk_soft_status psk_soft_get_demap(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_demap_t *rec /* [n] */);
+
+/* host only, pure: the definition for one segment on the host.  `in` is read as the entry reads it, with HOST pointers in soft and
+ * out; map and channel are not looked at (the map is points / labels / M); with PSK_SOFT_DEMAP_FRONT the positions in front of the
+ * row come from front[254] (127 (re, im) pairs, oldest first), zeros if it is NULL.  The bytes at out and *rec are byte for byte
+ * what the device writes (flags = PSK_SOFT_DEMAP_DATA | REC_I8).  A skipped segment gives the zero record.  Refuses what the
+ * entry and psk_soft_demap_define refuse of their arguments. */
+psk_soft_status psk_soft_demap_host(const float *points, const uint8_t *labels, uint32_t M, const psk_soft_demap_in_t *in,
+                                    const float *front /* [254] or NULL */, psk_soft_demap_t *rec);
+/* host only, pure, doubles rounded once at the end: the gain that undoes a derived hit, gain = exp(-i theta) / amplitude.
+ * theta = d->rotation * 2 pi / M, its cosine and sine from an exact table (0, +-1, +-(double)M_SQRT1_2), so quadrant turns are exact;
+ * with PSK_SOFT_DEMAP_GAIN_RESIDUAL theta is turned further by d->residual (C cos and sin); PSK_SOFT_DEMAP_GAIN_UNIT leaves the
+ * division by d->amplitude out.  PSK_SOFT_ERR_INVALID_ARG: null pointer, M other than 2, 4, 8, unknown flags, a rotation outside
+ * 0 .. M-1 (the -1 of an all-zero hit), an amplitude that is not finite and positive, with GAIN_RESIDUAL a residual that is
+ * not finite. */
+psk_soft_status psk_soft_demap_gain(const psk_soft_sync_derived_t *d, uint32_t M, uint32_t flags, float gain[2]);
+uint64_t psk_soft_demap_bytes(void);        /* sizeof(psk_soft_demap_t), for bindings */
+uint64_t psk_soft_demap_in_bytes(void);     /* sizeof(psk_soft_demap_in_t), for bindings */
+uint32_t psk_soft_demap_piece(void);        /* symbols of one piece of the device's fold: the summation order's unit */
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

@@ -24,6 +24,7 @@
 #include "psk_acquire.h"
 #include "psk_symrate.h"
 #include "psk_sync.h"
+#include "psk_demap.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -487,6 +488,96 @@ struct PassRing {
     }
 };
 
+// What a pass of psk_soft_demap_device (psk_demap.hip) owns until its event.  The call covers segments, not channels -- up to 2^20
+// of them --, so unlike a PassRing's the descriptors grow on demand with the partials.  The records of the handle are the last
+// call's and every pass rewrites them from segment 0: a pass on another stream waits for the one before.
+struct DemapRing {
+    struct Slot {
+        psk::DemapDesc *h_desc = nullptr, *d_desc = nullptr;
+        size_t desc_cap = 0;  // descriptors
+        psk::DemapPartial *d_part = nullptr;
+        size_t part_cap = 0;  // partials
+        hipEvent_t ev = nullptr;
+        bool used = false;
+        hipStream_t stream = nullptr;
+    } slot[2];
+    int turn = 0;
+
+    Slot &next()
+    {
+        Slot &q = slot[turn];
+        turn = (turn + 1) % 2;
+        return q;
+    }
+    // the slot once its last pass has ended, with room for nseg descriptors and n_part partials
+    static psk_soft_status claim(Slot &q, size_t nseg, size_t n_part)
+    {
+        if (q.used)
+            PSK_HIP(hipEventSynchronize(q.ev));
+        q.used = false;
+        if (!q.ev)
+            PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+        if (nseg > q.desc_cap) {
+            if (q.h_desc) (void)hipHostFree(q.h_desc);
+            if (q.d_desc) (void)hipFree(q.d_desc);
+            q.h_desc = q.d_desc = nullptr;
+            q.desc_cap = 0;
+            const size_t cap = nseg + nseg / 4u + 256u;
+            PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(psk::DemapDesc) * cap));
+            PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(psk::DemapDesc) * cap));
+            q.desc_cap = cap;
+        }
+        if (n_part > q.part_cap) {
+            if (q.d_part) (void)hipFree(q.d_part);
+            q.d_part = nullptr;
+            q.part_cap = 0;
+            const size_t cap = n_part + n_part / 4u + 256u;
+            PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(psk::DemapPartial) * cap));
+            q.part_cap = cap;
+        }
+        return PSK_SOFT_OK;
+    }
+    psk_soft_status upload(Slot &q, size_t nseg, hipStream_t stream)
+    {
+        for (const Slot &k : slot)
+            if (&k != &q && k.used && k.stream != stream)
+                PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
+        PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(psk::DemapDesc) * nseg, hipMemcpyHostToDevice, stream));
+        q.used = true, q.stream = stream;
+        return PSK_SOFT_OK;
+    }
+    // the slot is free again behind whatever the pass has put on the stream; returns `st`, the pass's status so far
+    static psk_soft_status finish(Slot &q, hipStream_t stream, psk_soft_status st)
+    {
+        const std::string keep = g_last_error;
+        if (const hipError_t e = hipEventRecord(q.ev, stream)) {
+            (void)hipStreamSynchronize(stream);
+            q.used = false;
+            if (st == PSK_SOFT_OK)
+                return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+        }
+        g_last_error = keep;
+        return st;
+    }
+    // every pass enqueued so far has ended
+    psk_soft_status wait()
+    {
+        for (Slot &q : slot)
+            if (q.used)
+                PSK_HIP(hipEventSynchronize(q.ev));
+        return PSK_SOFT_OK;
+    }
+    void free()
+    {
+        for (Slot &q : slot) {
+            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
+            if (q.h_desc) (void)hipHostFree(q.h_desc);
+            if (q.d_desc) (void)hipFree(q.d_desc);
+            if (q.d_part) (void)hipFree(q.d_part);
+        }
+    }
+};
+
 // Largest phaseAvg of the wave-scan kernels: their LDS ring of unwrapped phases holds phaseAvg + 128 values in a power
 // of two; 32768 floats (128 KiB) leave room for the energy ring next to it.  Channels with phaseAvg > kDeepFit are
 // launched apart from the others of their window class ("deep" classes, index H + 8): a ring that size allows one wave
@@ -683,6 +774,20 @@ struct psk_soft_handle {
     std::vector<psk_soft_sync_t> sync_dry;
     PassRing<psk::SyncDesc, psk::SyncPartial, kAcquireSlots> ypass;
     HistoryBank sync_hist{"sync history", psk::kSyncHistSlotFloats, 2u * psk::kSyncHistSlotFloats, 2u * psk::kSyncHist};
+    // ... and what PSK_SOFT_DEMAP_FRONT asks of a channel: how the last sync call that covered it left it (empty: no call yet)
+    enum : uint8_t { kSyncNotSearched = 0, kSyncSearched = 1, kSyncSearchedRestart = 2 };
+    std::vector<uint8_t> sync_last;
+    // psk_soft_demap_device: the maps of every slot (kDemapSlots DemapMap, allocated at the first psk_soft_demap_define; M 0: never
+    // defined); one record per segment of the last call, grown on demand -- a control-plane-only handle keeps them on the host --;
+    // the passes' descriptors and partials (DemapRing)
+    psk::DemapMap *d_demap_maps = nullptr;
+    uint32_t demap_M[psk::kDemapSlots] = {};
+    psk_soft_demap_t *d_demap = nullptr;
+    size_t demap_cap = 0;       // records
+    bool demap_called = false;
+    uint32_t demap_nseg = 0;    // of the last call
+    std::vector<psk_soft_demap_t> demap_dry;
+    DemapRing dpass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -2203,6 +2308,9 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_sync) (void)hipFree(h->d_sync);
         if (h->d_sync_words) (void)hipFree(h->d_sync_words);
         h->sync_hist.free();
+        h->dpass.free();
+        if (h->d_demap) (void)hipFree(h->d_demap);
+        if (h->d_demap_maps) (void)hipFree(h->d_demap_maps);
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
         if (h->d_test) (void)hipFree(h->d_test);
@@ -3766,6 +3874,17 @@ static psk_soft_status sync_records_ensure(psk_soft_handle *h)
 
 static psk_soft_status sync_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in, hipStream_t stream);
 
+// how a call that went through leaves its covered channels for PSK_SOFT_DEMAP_FRONT: searched or not, and with which flags
+static void sync_remember(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in)
+{
+    if (h->sync_last.empty())
+        h->sync_last.assign(h->nch, psk_soft_handle::kSyncNotSearched);
+    for (uint32_t i = 0; i < nch; i++)
+        h->sync_last[ch0 + i] = !sync_searched(in[i])                      ? psk_soft_handle::kSyncNotSearched
+                                : (in[i].flags & PSK_SOFT_SYNC_RESTART) ? psk_soft_handle::kSyncSearchedRestart
+                                                                        : psk_soft_handle::kSyncSearched;
+}
+
 psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in, void *stream_v)
 {
     if (!h || !in || !nch || (uint64_t)ch0 + nch > h->nch)
@@ -3807,6 +3926,7 @@ psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_
             }
             h->sync_dry[ch0 + i] = r;
         }
+        sync_remember(h, ch0, nch, in);
         return PSK_SOFT_OK;
     }
     PSK_HIP(hipSetDevice(h->device));
@@ -3815,10 +3935,14 @@ psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_
     PSK_HIP(deferred_join(h, stream));
     PSK_TRY(h->sync_hist.ensure(h->nch));
     const psk_soft_status st = sync_enqueue(h, ch0, nch, in, stream);
-    if (st == PSK_SOFT_OK)  // (the whole call went through: the new histories are the channels')
+    if (st != PSK_SOFT_OK && !h->sync_last.empty())  // (a launch may have written the other slots: nothing for FRONT to read there)
+        for (uint32_t i = 0; i < nch; i++) h->sync_last[ch0 + i] = psk_soft_handle::kSyncNotSearched;
+    if (st == PSK_SOFT_OK) {  // (the whole call went through: the new histories are the channels')
         for (uint32_t i = 0; i < nch; i++)
             if (sync_searched(in[i]))
                 h->sync_hist.flip(ch0 + i);
+        sync_remember(h, ch0, nch, in);
+    }
     return st;
 }
 
@@ -3984,6 +4108,290 @@ psk_soft_status psk_soft_sync_derive(const psk_soft_sync_hit_t *hit, uint16_t co
     out->residual = angle - turns * two_pi / M;
     out->amplitude = std::sqrt(e / (double)word_len);
     out->metric = (cr * cr + ci * ci) / (e * (double)Ew);
+    return PSK_SOFT_OK;
+}
+
+// ---- psk_soft_demap_device: segments of the soft rows as per-bit LLRs (include/psk_soft_hip.h, psk_demap.hip) ----
+// Behind the sync call: a fold over pieces of kDemapPiece symbols and a join per segment on the caller's stream, one record per
+// segment of the call; a ring of its own (DemapRing).  Nothing of the control plane, of the demodulator's state or of any other
+// record is read or written; of the sync pass only the history slot its last call read.
+static bool demap_map_ok(uint32_t M, const float *points, const uint8_t *labels)
+{
+    if (M != 2u && M != 4u && M != 8u)
+        return false;
+    uint32_t seen = 0;
+    for (uint32_t k = 0; k < M; k++) {
+        if (!psk::dm_finite(points[2u * k]) || !psk::dm_finite(points[2u * k + 1u]) || labels[k] >= M)
+            return false;
+        seen |= 1u << labels[k];
+    }
+    return seen == (1u << M) - 1u;
+}
+
+static psk::DemapMap demap_map_make(uint32_t M, const float *points, const uint8_t *labels)
+{
+    psk::DemapMap m = {};
+    m.M = M, m.B = M == 2u ? 1u : M == 4u ? 2u : 3u;
+    for (uint32_t k = 0; k < M; k++) m.p[2u * k] = points[2u * k], m.p[2u * k + 1u] = points[2u * k + 1u], m.label[k] = labels[k];
+    return m;
+}
+
+psk_soft_status psk_soft_demap_define(psk_soft_handle_t *h, uint32_t slot, uint32_t M, const float *points, const uint8_t *labels)
+{
+    if (!h || !points || !labels || slot >= psk::kDemapSlots || !demap_map_ok(M, points, labels))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_demap_define: null pointer, a slot above 15, an M other than 2, 4, 8, a non-finite point or labels that are not a permutation of 0 .. M-1");
+    if (!h->dry) {
+        PSK_HIP(hipSetDevice(h->device));
+        if (!h->d_demap_maps) {
+            psk::DemapMap *p = nullptr;
+            PSK_HIP(hipMalloc((void **)&p, sizeof(psk::DemapMap) * psk::kDemapSlots));
+            if (hipMemset(p, 0, sizeof(psk::DemapMap) * psk::kDemapSlots) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+                (void)hipFree(p);
+                return fail(PSK_SOFT_ERR_HIP, "demap maps: hipMemset failed");
+            }
+            h->d_demap_maps = p;
+        }
+        PSK_TRY(h->dpass.wait());  // (no launch is still reading the slot)
+        const psk::DemapMap m = demap_map_make(M, points, labels);
+        PSK_HIP(hipMemcpy(h->d_demap_maps + slot, &m, sizeof m, hipMemcpyHostToDevice));
+    }
+    h->demap_M[slot] = M;  // (a control-plane-only handle checks and counts: M is all it needs)
+    return PSK_SOFT_OK;
+}
+
+static bool demap_skipped(const psk_soft_demap_in_t &k) { return !k.count || !k.map || !k.soft; }
+
+// what is wrong with a segment that is not skipped, but for its map and its channel; nullptr: nothing
+static const char *demap_segment_fault(const psk_soft_demap_in_t &k)
+{
+    const bool front = (k.flags & PSK_SOFT_DEMAP_FRONT) != 0;
+    if (k.flags & ~(uint32_t)(PSK_SOFT_DEMAP_I8 | PSK_SOFT_DEMAP_FRONT))
+        return "unknown flag bits";
+    if (k.pad)
+        return "pad must be zero";
+    if ((uintptr_t)k.soft & 7u)
+        return "soft must be 8-byte aligned";
+    if (!k.out)
+        return "out is null";
+    if (!(k.flags & PSK_SOFT_DEMAP_I8) && ((uintptr_t)k.out & 3u))
+        return "a float32 out must be 4-byte aligned";
+    if (k.n_symbols >= psk::kDemapMaxN)
+        return "2^30 symbols or more";
+    if (k.pos < (front ? -(int64_t)psk::kDemapFront : (int64_t)0))
+        return "pos below 0 (below -127 with PSK_SOFT_DEMAP_FRONT)";
+    // (no sum of pos and count is formed: pos may be anything up to INT64_MAX; n_symbols < 2^30 and pos >= -127 here)
+    if (k.pos > (int64_t)k.n_symbols || (int64_t)k.count > (int64_t)k.n_symbols - k.pos)
+        return "pos + count beyond n_symbols";
+    if (!psk::dm_finite(k.gain_re) || !psk::dm_finite(k.gain_im) || !psk::dm_finite(k.scale))
+        return "a gain or scale that is not finite";
+    return nullptr;
+}
+
+static psk_soft_status demap_enqueue(psk_soft_handle *h, uint32_t nseg, const psk_soft_demap_in_t *in, hipStream_t stream);
+
+psk_soft_status psk_soft_demap_device(psk_soft_handle_t *h, uint32_t nseg, const psk_soft_demap_in_t *in, void *stream_v)
+{
+    if (!h || !in || !nseg || nseg > psk::kDemapMaxSegments)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_demap_device: null pointer or a number of segments outside 1 .. 2^20");
+    // the refusals, before anything is enqueued or any record changes
+    for (uint32_t i = 0; i < nseg; i++) {
+        const psk_soft_demap_in_t &k = in[i];
+        if (demap_skipped(k))
+            continue;
+        const char *what = nullptr;
+        if (k.map > psk::kDemapSlots || !h->demap_M[k.map - 1u])
+            what = "a map slot above 15 or never defined (psk_soft_demap_define)";
+        else
+            what = demap_segment_fault(k);
+        if (!what && (k.flags & PSK_SOFT_DEMAP_FRONT) &&
+            (k.channel >= h->nch || h->sync_last.empty() || h->sync_last[k.channel] == psk_soft_handle::kSyncNotSearched))
+            what = "PSK_SOFT_DEMAP_FRONT on a channel out of range or one whose last sync call did not search it";
+        if (what) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "psk_soft_demap_device: segment %u: %s", i, what);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+    }
+    if (h->dry) {
+        h->demap_dry.assign(nseg, psk_soft_demap_t{});
+        for (uint32_t i = 0; i < nseg; i++) {
+            if (demap_skipped(in[i]))
+                continue;
+            psk_soft_demap_t &r = h->demap_dry[i];
+            const uint32_t M = h->demap_M[in[i].map - 1u];
+            r.n_symbols = in[i].count;
+            r.bits = M == 2u ? 1u : M == 4u ? 2u : 3u;
+            r.flags = PSK_SOFT_DEMAP_PLANNED | ((in[i].flags & PSK_SOFT_DEMAP_I8) ? PSK_SOFT_DEMAP_REC_I8 : 0u);
+        }
+        h->demap_called = true, h->demap_nseg = nseg;
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: the rows must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    return demap_enqueue(h, nseg, in, stream);
+}
+
+// the fold and the join of a demap call whose arguments have passed
+static psk_soft_status demap_enqueue(psk_soft_handle *h, uint32_t nseg, const psk_soft_demap_in_t *in, hipStream_t stream)
+{
+    uint64_t n_part = 0;
+    for (uint32_t i = 0; i < nseg; i++)
+        if (!demap_skipped(in[i]))
+            n_part += psk::demap_pieces(in[i].count);
+    if (n_part > 0x7fffffffull)
+        return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_demap_device: too many symbols in one call");
+    if (nseg > h->demap_cap) {  // (the records are the last call's: nothing of them is kept)
+        PSK_TRY(h->dpass.wait());
+        if (h->d_demap) (void)hipFree(h->d_demap);
+        h->d_demap = nullptr;
+        h->demap_cap = 0;
+        const size_t cap = (size_t)nseg + nseg / 4u + 256u;
+        PSK_HIP(hipMalloc((void **)&h->d_demap, sizeof(psk_soft_demap_t) * cap));
+        h->demap_cap = cap;
+    }
+    auto &q = h->dpass.next();
+    PSK_TRY(h->dpass.claim(q, nseg, n_part));
+    uint32_t part0 = 0, max_piece = 0;
+    for (uint32_t i = 0; i < nseg; i++) {
+        psk::DemapDesc &d = q.h_desc[i];
+        d = psk::DemapDesc{};
+        const psk_soft_demap_in_t &k = in[i];
+        if (demap_skipped(k))
+            continue;  // (its zero record)
+        d.soft = k.soft, d.out = k.out, d.pos = k.pos, d.count = k.count;
+        // the history the channel's last sync call read: since that call's flip the slot that is not current
+        if (k.pos < 0 && h->sync_last[k.channel] == psk_soft_handle::kSyncSearched)
+            d.front = h->sync_hist.out(k.channel);
+        d.map = k.map - 1u;
+        d.flags = psk::kDemapData | ((k.flags & PSK_SOFT_DEMAP_I8) ? psk::kDemapI8 : 0u);
+        d.part0 = part0, d.n_piece = psk::demap_pieces(k.count);
+        d.gain_re = k.gain_re, d.gain_im = k.gain_im, d.scale = k.scale;
+        part0 += d.n_piece;
+        max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
+    }
+    PSK_TRY(h->dpass.upload(q, nseg, stream));
+    // the records are the new call's from here on, also if a launch below fails
+    h->demap_called = true, h->demap_nseg = nseg;
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = segments, tiles = pieces)
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, 0, nseg, n_part, 0, 0, h->slot, stream); };
+    auto enqueue = [&]() -> psk_soft_status {
+        PSK_HIP(mark("demap_fold"));
+        PSK_HIP(psk::launch_demap_fold(q.d_desc, nseg, max_piece, h->d_demap_maps, q.d_part, stream));
+        PSK_HIP(mark("demap_join"));
+        PSK_HIP(psk::launch_demap_join(q.d_desc, nseg, h->d_demap_maps, q.d_part, h->d_demap, stream));
+        return PSK_SOFT_OK;
+    };
+    return h->dpass.finish(q, stream, enqueue());
+}
+
+uint64_t psk_soft_demap_bytes(void) { return sizeof(psk_soft_demap_t); }
+uint64_t psk_soft_demap_in_bytes(void) { return sizeof(psk_soft_demap_in_t); }
+uint32_t psk_soft_demap_piece(void) { return psk::kDemapPiece; }
+static_assert(sizeof(psk_soft_demap_t) == 64 && sizeof(psk_soft_demap_in_t) == 64, "include/psk_soft_hip.h states the sizes");
+
+psk_soft_status psk_soft_get_demap(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_demap_t *rec)
+{
+    if (!h || !rec || !n || !h->demap_called || (uint64_t)first + n > h->demap_nseg)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_demap: null pointer, no psk_soft_demap_device call yet or a range beyond its segments");
+    if (h->dry) {
+        std::memcpy(rec, h->demap_dry.data() + first, sizeof(psk_soft_demap_t) * n);
+        return PSK_SOFT_OK;
+    }
+    const psk_soft_status st = psk_soft_synchronize(h);
+    if (st != PSK_SOFT_OK)
+        return st;
+    PSK_TRY(h->dpass.wait());
+    PSK_HIP(hipMemcpy(rec, h->d_demap + first, sizeof(psk_soft_demap_t) * n, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_demap_host(const float *points, const uint8_t *labels, uint32_t M, const psk_soft_demap_in_t *in, const float *front,
+                                    psk_soft_demap_t *rec)
+{
+    if (!points || !labels || !in || !rec || !demap_map_ok(M, points, labels))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_demap_host: null pointer, an M other than 2, 4, 8, a non-finite point or labels that are not a permutation");
+    *rec = psk_soft_demap_t{};
+    if (!in->count || !in->soft)
+        return PSK_SOFT_OK;
+    if (const char *what = demap_segment_fault(*in))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_demap_host: ") + what);
+    const psk::DemapMap m = demap_map_make(M, points, labels);
+    const bool i8 = (in->flags & PSK_SOFT_DEMAP_I8) != 0;
+    const uint32_t B = m.B, T = psk::kDemapThreads, P = psk::kDemapPiece;
+    double sum_e = 0.0, sum_err = 0.0;
+    for (uint32_t lo = 0; lo < in->count; lo += P) {
+        const uint32_t cnt = in->count - lo < P ? in->count - lo : P;
+        double le[psk::kDemapThreads] = {}, lr[psk::kDemapThreads] = {};  // the lanes' sums, from 0.0
+        for (uint32_t i = 0; i < cnt; i++) {  // (ascending: lane i % 256 meets its symbols in the order t, t + 256, ...)
+            const int64_t g = in->pos + (int64_t)lo + (int64_t)i;
+            float xr = 0.0f, xi = 0.0f;
+            if (g >= 0)
+                xr = in->soft[2 * g], xi = in->soft[2 * g + 1];
+            else if (front)
+                xr = front[2 * (g + (int64_t)psk::kDemapFront)], xi = front[2 * (g + (int64_t)psk::kDemapFront) + 1];
+            float e, dmin, v[psk::kDemapMaxB];
+            if (psk::dm_symbol(m, xr, xi, in->gain_re, in->gain_im, in->scale, &e, &dmin, v)) {
+                le[i % T] += (double)e, lr[i % T] += (double)dmin;
+                rec->n_finite++;
+            }
+            for (uint32_t j = 0; j < B; j++) {
+                const uint64_t at = (uint64_t)(lo + i) * B + j;
+                rec->n_nan += v[j] != v[j] ? 1u : 0u;
+                if (i8) {
+                    uint32_t clip = 0;
+                    static_cast<int8_t *>(in->out)[at] = (int8_t)psk::dm_i8(v[j], &clip);
+                    rec->n_clip += clip;
+                } else {
+                    static_cast<float *>(in->out)[at] = psk::dm_f32(v[j]);
+                }
+            }
+        }
+        // the xor tree across each wave (every lane: s += the s of lane ^ offset), then the waves in order from wave 0's value
+        double pe = 0.0, pr = 0.0;
+        for (uint32_t w = 0; w < T / 64u; w++) {
+            for (uint32_t off = 32; off >= 1; off >>= 1) {
+                double ne[64], nr[64];
+                for (uint32_t l = 0; l < 64; l++) ne[l] = le[64 * w + l] + le[64 * w + (l ^ off)], nr[l] = lr[64 * w + l] + lr[64 * w + (l ^ off)];
+                std::memcpy(le + 64 * w, ne, sizeof ne), std::memcpy(lr + 64 * w, nr, sizeof nr);
+            }
+            pe = w ? pe + le[64 * w] : le[0];
+            pr = w ? pr + lr[64 * w] : lr[0];
+        }
+        // the pieces in ascending order, from piece 0's
+        sum_e = lo ? sum_e + pe : pe;
+        sum_err = lo ? sum_err + pr : pr;
+    }
+    rec->n_symbols = in->count;
+    rec->sum_e = sum_e, rec->sum_err = sum_err;
+    rec->bits = B;
+    rec->flags = PSK_SOFT_DEMAP_DATA | (i8 ? PSK_SOFT_DEMAP_REC_I8 : 0u);
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_demap_gain(const psk_soft_sync_derived_t *d, uint32_t M, uint32_t flags, float gain[2])
+{
+    if (!d || !gain || (M != 2u && M != 4u && M != 8u) || (flags & ~(uint32_t)(PSK_SOFT_DEMAP_GAIN_RESIDUAL | PSK_SOFT_DEMAP_GAIN_UNIT)))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_demap_gain: null pointer, an M other than 2, 4, 8 or unknown flags");
+    if (d->rotation < 0 || d->rotation >= (int32_t)M || !std::isfinite(d->amplitude) || !(d->amplitude > 0.0) ||
+        ((flags & PSK_SOFT_DEMAP_GAIN_RESIDUAL) && !std::isfinite(d->residual)))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_demap_gain: a rotation outside 0 .. M-1, an amplitude that is not finite and positive or a residual that is not finite");
+    // cos and sin of k * 2 pi / 8, exactly
+    const double s = 0.70710678118654752440;  // M_SQRT1_2
+    const double ct[8] = {1.0, s, 0.0, -s, -1.0, -s, 0.0, s}, st[8] = {0.0, s, 1.0, s, 0.0, -s, -1.0, -s};
+    const uint32_t k = (uint32_t)d->rotation * (8u / M);
+    double c = ct[k], sn = st[k];
+    if (flags & PSK_SOFT_DEMAP_GAIN_RESIDUAL) {
+        const double cr = std::cos(d->residual), sr = std::sin(d->residual);
+        const double c2 = c * cr - sn * sr, s2 = c * sr + sn * cr;
+        c = c2, sn = s2;
+    }
+    // exp(-i theta) / amplitude
+    double gr = c, gi = 0.0 - sn;
+    if (!(flags & PSK_SOFT_DEMAP_GAIN_UNIT))
+        gr /= d->amplitude, gi /= d->amplitude;
+    gain[0] = (float)gr, gain[1] = (float)gi;
     return PSK_SOFT_OK;
 }
 

@@ -283,6 +283,49 @@ class SyncDerived(ctypes.Structure):
     ]
 
 
+DEMAP_I8, DEMAP_FRONT = 1, 2  # DemapIn.flags
+DEMAP_DATA, DEMAP_REC_I8, DEMAP_PLANNED = 1, 2, 128  # DemapRecord.flags (REC_I8: the segment's DEMAP_I8 bit shifted left by one)
+DEMAP_GAIN_RESIDUAL, DEMAP_GAIN_UNIT = 1, 2  # demap_gain flags
+DEMAP_SLOTS, DEMAP_MAX_SEGMENTS, DEMAP_FRONT_SYMBOLS = 16, 1 << 20, 127
+
+
+class DemapIn(ctypes.Structure):
+    """psk_soft_demap_in_t: one segment of a demap_device call -- a DEVICE pointer to the row's symbol 0 and the row's length, the
+    segment's first symbol and count, a DEVICE pointer to its output, the channel (with DEMAP_FRONT only), map = 1 + the slot of
+    the map (0: skipped), flags (DEMAP_I8, DEMAP_FRONT), the complex gain and the LLR scale."""
+
+    _fields_ = [
+        ("soft", ctypes.c_void_p),
+        ("n_symbols", ctypes.c_uint64),
+        ("pos", ctypes.c_int64),
+        ("out", ctypes.c_void_p),
+        ("count", ctypes.c_uint32),
+        ("channel", ctypes.c_uint32),
+        ("map", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("gain_re", ctypes.c_float),
+        ("gain_im", ctypes.c_float),
+        ("scale", ctypes.c_float),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+class DemapRecord(ctypes.Structure):
+    """psk_soft_demap_t: the record of one segment of the last demap_device call."""
+
+    _fields_ = [
+        ("n_symbols", ctypes.c_uint64),
+        ("n_finite", ctypes.c_uint64),
+        ("n_clip", ctypes.c_uint64),
+        ("n_nan", ctypes.c_uint64),
+        ("sum_e", ctypes.c_double),
+        ("sum_err", ctypes.c_double),
+        ("bits", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 2),
+    ]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_hip.h declares
@@ -351,6 +394,14 @@ EXPORTS = (
     "psk_soft_sync_bytes",
     "psk_soft_sync_in_bytes",
     "psk_soft_sync_piece",
+    "psk_soft_demap_define",
+    "psk_soft_demap_device",
+    "psk_soft_get_demap",
+    "psk_soft_demap_host",
+    "psk_soft_demap_gain",
+    "psk_soft_demap_bytes",
+    "psk_soft_demap_in_bytes",
+    "psk_soft_demap_piece",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -489,6 +540,17 @@ def load():
     L.psk_soft_sync_in_bytes.restype = u64
     L.psk_soft_sync_piece.argtypes = []
     L.psk_soft_sync_piece.restype = u32
+    L.psk_soft_demap_define.argtypes = [vp, u32, u32, vp, vp]
+    L.psk_soft_demap_device.argtypes = [vp, u32, ctypes.POINTER(DemapIn), vp]
+    L.psk_soft_get_demap.argtypes = [vp, u32, u32, ctypes.POINTER(DemapRecord)]
+    L.psk_soft_demap_host.argtypes = [vp, vp, u32, ctypes.POINTER(DemapIn), vp, ctypes.POINTER(DemapRecord)]
+    L.psk_soft_demap_gain.argtypes = [ctypes.POINTER(SyncDerived), u32, u32, ctypes.POINTER(ctypes.c_float)]
+    L.psk_soft_demap_bytes.argtypes = []
+    L.psk_soft_demap_bytes.restype = u64
+    L.psk_soft_demap_in_bytes.argtypes = []
+    L.psk_soft_demap_in_bytes.restype = u64
+    L.psk_soft_demap_piece.argtypes = []
+    L.psk_soft_demap_piece.restype = u32
     _lib = L
     return L
 
@@ -744,6 +806,56 @@ def sync_piece():
 
 def _sync_in(s):
     return s if isinstance(s, SyncIn) else SyncIn(*s)
+
+
+def _demap_map(points, labels):
+    p = np.ascontiguousarray(points, np.float32).reshape(-1)
+    lab = np.ascontiguousarray(labels, np.uint8).reshape(-1)
+    if p.size != 2 * lab.size:
+        raise ValueError("a map is M points (2 M floats) and M labels")
+    return p, lab
+
+
+def demap_host(points, labels, soft, pos, count, gain, scale, flags=0, front=None):
+    """psk_soft_demap_host: one segment on the host.  points: M interleaved float32 (re, im); labels: M labels; soft: the row,
+    interleaved float32 (an odd last element is dropped); the segment is its symbols [pos, pos + count); gain: (re, im);
+    flags: DEMAP_I8, DEMAP_FRONT; front: None (zeros) or the 254 floats in front of the row (read with DEMAP_FRONT where pos < 0).
+    Returns (the count * B values: int8 with DEMAP_I8, float32 without, the DemapRecord)."""
+    p, lab = _demap_map(points, labels)
+    x = np.ascontiguousarray(soft, np.float32)
+    fr = None
+    if front is not None:
+        fr = np.ascontiguousarray(front, np.float32)
+        if fr.size != 2 * DEMAP_FRONT_SYMBOLS:
+            raise ValueError("the symbols in front of a row are 127 complex symbols: 254 floats")
+    B = max(int(lab.size).bit_length() - 1, 0)
+    out = np.zeros(max(int(count) * B, 1), np.int8 if flags & DEMAP_I8 else np.float32)
+    k = DemapIn(x.ctypes.data if x.size else None, x.size // 2, int(pos), out.ctypes.data, int(count), 0, 1, int(flags),
+                float(gain[0]), float(gain[1]), float(scale), 0)
+    rec = DemapRecord()
+    _check(load().psk_soft_demap_host(p.ctypes.data if p.size else None, lab.ctypes.data if lab.size else None, lab.size, ctypes.byref(k),
+                                      fr.ctypes.data if fr is not None else None, ctypes.byref(rec)))
+    return out[: int(count) * B], rec
+
+
+def demap_gain(derived, M, flags=0):
+    """psk_soft_demap_gain: the (re, im) gain, two float32, that undoes a derived hit -- a SyncDerived or the dict sync_derive
+    returns -- for constellation size M.  flags: DEMAP_GAIN_RESIDUAL, DEMAP_GAIN_UNIT."""
+    d = derived
+    if not isinstance(d, SyncDerived):
+        d = SyncDerived(derived["angle"], derived["residual"], derived["amplitude"], derived["metric"], derived["rotation"], 0)
+    g = (ctypes.c_float * 2)()
+    _check(load().psk_soft_demap_gain(ctypes.byref(d), int(M), int(flags), g))
+    return np.array([g[0], g[1]], np.float32)
+
+
+def demap_piece():
+    """Symbols of one piece of the device's fold (psk_soft_demap_piece): the unit of the records' summation order."""
+    return int(load().psk_soft_demap_piece())
+
+
+def _demap_in(s):
+    return s if isinstance(s, DemapIn) else DemapIn(*s)
 
 
 class Handle:
@@ -1157,6 +1269,29 @@ class Handle:
         nch = self.n_channels - ch0 if nch is None else nch
         arr = (SyncRecord * nch)()
         _check(self._L.psk_soft_get_sync(self._h, ch0, nch, arr))
+        return arr
+
+    def demap_define(self, slot, points, labels):
+        """psk_soft_demap_define: the map of slot `slot` (0 .. 15) -- M = 2, 4 or 8 points, interleaved float32 (re, im), and their
+        M labels (a permutation of 0 .. M-1), copied; a segment names it as DemapIn.map = slot + 1."""
+        p, lab = _demap_map(points, labels)
+        _check(self._L.psk_soft_demap_define(self._h, int(slot), lab.size, p.ctypes.data if p.size else None,
+                                             lab.ctypes.data if lab.size else None))
+
+    def demap_device(self, ins, stream=None):
+        """Segments of soft rows as per-bit LLRs (psk_soft_demap_device): writes count * B values per segment to its `out` and
+        leaves a DemapRecord per segment; touches no demodulator state.  ins: a ctypes DemapIn array or a sequence of DemapIn /
+        field tuples.  Rows and outputs are DEVICE memory, the rows complete on `stream` (None: the handle's)."""
+        if not isinstance(ins, ctypes.Array):
+            ins = (DemapIn * len(ins))(*[_demap_in(s) for s in ins])
+        _check(self._L.psk_soft_demap_device(self._h, len(ins), ins, ctypes.c_void_p(stream or 0)))
+
+    def demap_records(self, first=0, n=1):
+        """The DemapRecord records of the segments [first, first + n) of the last demap_device call (psk_soft_get_demap), a ctypes
+        array.  The handle does not tell how many segments that call had: a range beyond them is refused."""
+        n = int(n)
+        arr = (DemapRecord * n)()
+        _check(self._L.psk_soft_get_demap(self._h, int(first), n, arr))
         return arr
 
     def sync_history(self, ch):
