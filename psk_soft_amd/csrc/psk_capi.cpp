@@ -107,6 +107,30 @@ psk_soft_status fail(psk_soft_status st, const std::string &msg)
         if (e_ != hipSuccess)                                                                     \
             return fail(PSK_SOFT_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));     \
     } while (0)
+// (a step that fails ends the function with its status, the message as the step left it)
+#define PSK_TRY(call)                       \
+    do {                                    \
+        const psk_soft_status s_ = (call);  \
+        if (s_ != PSK_SOFT_OK)              \
+            return s_;                      \
+    } while (0)
+
+// n and a quarter more: what a buffer that is grown on demand is given when n no longer fit
+inline size_t with_headroom(size_t n) { return n + n / 4u + 256u; }
+// Device memory of `bytes` zeros in *out, `what` in the message of a failure.  The memset is through before a launch on any stream
+// reads or writes the memory.
+template <class T>
+psk_soft_status alloc_zeroed(T **out, size_t bytes, const char *what)
+{
+    void *p = nullptr;
+    PSK_HIP(hipMalloc((void **)&p, bytes));
+    if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(p);
+        return fail(PSK_SOFT_ERR_HIP, std::string(what) + ": hipMemset failed");
+    }
+    *out = static_cast<T *>(p);
+    return PSK_SOFT_OK;
+}
 
 constexpr int kPlanSlots = 4;
 constexpr int kAuxStreams = 3;  // side streams for the launches of a batch that mixes window classes (see psk_soft_process_device)
@@ -337,15 +361,8 @@ struct HistoryBank {
     {
         if (d)
             return PSK_SOFT_OK;
-        float *p = nullptr;
-        const size_t bytes = sizeof(float) * chan_floats * nch;
-        PSK_HIP(hipMalloc((void **)&p, bytes));
-        if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-            (void)hipFree(p);  // (the memset is through before a launch on any stream reads a slot)
-            return fail(PSK_SOFT_ERR_HIP, std::string(name) + ": hipMemset failed");
-        }
+        PSK_TRY(alloc_zeroed(&d, sizeof(float) * chan_floats * nch, name));
         cur.assign(nch, 0);
-        d = p;
         return PSK_SOFT_OK;
     }
     float *slot(uint32_t ch, uint32_t which) const { return d + (size_t)chan_floats * ch + slot_floats * which; }
@@ -394,20 +411,55 @@ struct HistoryBank {
     }
 };
 
-// What a pass of fold + join behind a call owns until its event -- PSK_SOFT_OPT_QUALITY's behind a process call (psk_quality.hip),
-// psk_soft_acquire_device's (psk_acquire.hip): the descriptors (pinned, and their copy in device memory: one per channel of the
-// handle) and the partials of the fold (grown on demand).  The chunks of psk_soft_process_host run on streams of their own and overlap,
-// hence a ring of N of them.  A pass goes through the members in the order they stand in.
+// ---- the reduction-pass layer: what the fold + join passes behind a call share ----
+// A pass is a fold over pieces and a join per record on the caller's stream: PSK_SOFT_OPT_QUALITY's behind a process call
+// (psk_quality.hip), the two looks (psk_acquire.hip, psk_symrate.hip), the word search (psk_sync.hip), the demapper (psk_demap.hip).
+// An entry of the kind has a PassRing and a Records in the handle and goes through them in this order: next + claim a slot of the
+// ring; fill the slot's pinned descriptors, one per record of the call, giving each its partials with a PieceCount (which holds the
+// 2^31 limit; the message is the entry's); then run(): room for the partials, the descriptors up behind the passes of other streams
+// that write the same records, the entry's own launches (its trace lines, its fold, its join, whatever else it puts on the stream),
+// and the slot's event behind them however they ended.  Its psk_soft_get_* is its own argument check and records_read.  A pass
+// over the handle's channels asks claim for the handle's channel count, so that its descriptors are allocated once, and covers
+// the channels of its call; a pass over something else (the demapper's segments) asks for what the call needs and covers
+// kAllRecords.  The chunks of psk_soft_process_host run on streams of their own and overlap, hence a ring of N slots.
+
+// the records a pass writes: [first, first + n) of the entry's
+struct PassCover {
+    uint32_t first, n;
+};
+constexpr PassCover kAllRecords = {0u, UINT32_MAX};
+
+// The partials of a pass, handed out as its descriptors are filled: where a record's start and how many it has; the pass's total
+// and the most any record has.
+struct PieceCount {
+    uint64_t total = 0;
+    uint32_t max_piece = 0;
+    // a record of `pieces` pieces; false, and nothing counted: the pass would have 2^31 partials or more
+    bool add(uint64_t pieces, uint32_t *part0, uint32_t *n_piece)
+    {
+        if (pieces > 0x7fffffffull || total + pieces > 0x7fffffffull)
+            return false;
+        *part0 = (uint32_t)total;
+        *n_piece = (uint32_t)pieces;
+        total += pieces;
+        max_piece = *n_piece > max_piece ? *n_piece : max_piece;
+        return true;
+    }
+};
+
+// What a pass owns until its event: the descriptors (pinned, and their copy in device memory) and the partials of the fold, both
+// grown on demand.  A pass goes through the members in the order they stand in.
 template <class Desc, class Partial, int N>
 struct PassRing {
     struct Slot {
         Desc *h_desc = nullptr, *d_desc = nullptr;
+        size_t desc_cap = 0;  // descriptors
         Partial *d_part = nullptr;
         size_t part_cap = 0;  // partials
         hipEvent_t ev = nullptr;
         bool used = false;
         hipStream_t stream = nullptr;
-        uint32_t ch0 = 0, nch = 0;
+        PassCover cover = {0, 0};
     } slot[N];
     int turn = 0;
 
@@ -418,17 +470,24 @@ struct PassRing {
         turn = (turn + 1) % N;
         return q;
     }
-    // ... once its last pass has ended; event and descriptors (handle_nch of them) are created on first use
-    static psk_soft_status claim(Slot &q, uint32_t handle_nch)
+    // ... once its last pass has ended, with room for n_desc descriptors: a slot that has less gets n_desc + headroom.  The event is
+    // created on first use.
+    static psk_soft_status claim(Slot &q, size_t n_desc, size_t headroom = 0)
     {
         if (q.used)
             PSK_HIP(hipEventSynchronize(q.ev));
+        q.used = false;  // (the event has completed: nothing waits for it again, and upload sets `used` for the next pass)
         if (!q.ev)
             PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-        if (!q.h_desc)
-            PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(Desc) * (size_t)handle_nch));
-        if (!q.d_desc)
-            PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(Desc) * (size_t)handle_nch));
+        if (n_desc <= q.desc_cap)
+            return PSK_SOFT_OK;
+        if (q.h_desc) (void)hipHostFree(q.h_desc);
+        if (q.d_desc) (void)hipFree(q.d_desc);
+        q.h_desc = q.d_desc = nullptr;
+        q.desc_cap = 0;
+        PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(Desc) * (n_desc + headroom)));
+        PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(Desc) * (n_desc + headroom)));
+        q.desc_cap = n_desc + headroom;
         return PSK_SOFT_OK;
     }
     // room for n partials
@@ -439,20 +498,20 @@ struct PassRing {
         if (q.d_part) (void)hipFree(q.d_part);
         q.d_part = nullptr;
         q.part_cap = 0;
-        const size_t cap = (size_t)n + (size_t)n / 4u + 256u;
+        const size_t cap = with_headroom((size_t)n);
         PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(Partial) * cap));
         q.part_cap = cap;
         return PSK_SOFT_OK;
     }
-    // The record of a channel is written by one pass at a time: `stream` waits for the passes of other streams over channels of
-    // [ch0, ch0 + nch); then the descriptors go up and the slot is the pass's.
-    psk_soft_status upload(Slot &q, uint32_t ch0, uint32_t nch, hipStream_t stream)
+    // A record is written by one pass at a time: `stream` waits for the passes of other streams over records of `cover`; then the
+    // n_desc descriptors go up and the slot is the pass's.
+    psk_soft_status upload(Slot &q, uint32_t n_desc, PassCover cover, hipStream_t stream)
     {
         for (const Slot &k : slot)
-            if (&k != &q && k.used && k.stream != stream && k.ch0 < ch0 + nch && ch0 < k.ch0 + k.nch)
+            if (&k != &q && k.used && k.stream != stream && k.cover.first < cover.first + cover.n && cover.first < k.cover.first + k.cover.n)
                 PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
-        PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(Desc) * (size_t)nch, hipMemcpyHostToDevice, stream));
-        q.used = true, q.stream = stream, q.ch0 = ch0, q.nch = nch;
+        PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(Desc) * (size_t)n_desc, hipMemcpyHostToDevice, stream));
+        q.used = true, q.stream = stream, q.cover = cover;
         return PSK_SOFT_OK;
     }
     // The slot is free again behind whatever the pass has put on the stream.  Returns `st`, the pass's status so far (its error text
@@ -468,6 +527,15 @@ struct PassRing {
         }
         g_last_error = keep;
         return st;
+    }
+    // The pass from its filled descriptors on: room for n_part partials, the descriptors up, then enqueue() -- the entry's launches,
+    // a psk_soft_status -- and, on every path behind a successful upload, the slot's event.
+    template <class Enqueue>
+    psk_soft_status run(Slot &q, uint32_t n_desc, PassCover cover, uint64_t n_part, hipStream_t stream, Enqueue enqueue)
+    {
+        PSK_TRY(grow(q, n_part));
+        PSK_TRY(upload(q, n_desc, cover, stream));
+        return finish(q, stream, enqueue());
     }
     // every pass enqueued so far has ended
     psk_soft_status wait()
@@ -488,93 +556,43 @@ struct PassRing {
     }
 };
 
-// What a pass of psk_soft_demap_device (psk_demap.hip) owns until its event.  The call covers segments, not channels -- up to 2^20
-// of them --, so unlike a PassRing's the descriptors grow on demand with the partials.  The records of the handle are the last
-// call's and every pass rewrites them from segment 0: a pass on another stream waits for the one before.
-struct DemapRing {
-    struct Slot {
-        psk::DemapDesc *h_desc = nullptr, *d_desc = nullptr;
-        size_t desc_cap = 0;  // descriptors
-        psk::DemapPartial *d_part = nullptr;
-        size_t part_cap = 0;  // partials
-        hipEvent_t ev = nullptr;
-        bool used = false;
-        hipStream_t stream = nullptr;
-    } slot[2];
-    int turn = 0;
+// The records of an entry, one per channel of the handle or per segment of the last call: an array in device memory, written by
+// the joins; a control-plane-only handle keeps them on the host.
+template <class Rec>
+struct Records {
+    Rec *d = nullptr;
+    size_t cap = 0;  // records of d
+    std::vector<Rec> dry;
 
-    Slot &next()
+    bool exist() const { return d || !dry.empty(); }
+    // n records of zeros, unless they exist (`what`: in the message of a failure)
+    psk_soft_status ensure_zeroed(bool on_host, size_t n, const char *what)
     {
-        Slot &q = slot[turn];
-        turn = (turn + 1) % 2;
-        return q;
-    }
-    // the slot once its last pass has ended, with room for nseg descriptors and n_part partials
-    static psk_soft_status claim(Slot &q, size_t nseg, size_t n_part)
-    {
-        if (q.used)
-            PSK_HIP(hipEventSynchronize(q.ev));
-        q.used = false;
-        if (!q.ev)
-            PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-        if (nseg > q.desc_cap) {
-            if (q.h_desc) (void)hipHostFree(q.h_desc);
-            if (q.d_desc) (void)hipFree(q.d_desc);
-            q.h_desc = q.d_desc = nullptr;
-            q.desc_cap = 0;
-            const size_t cap = nseg + nseg / 4u + 256u;
-            PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(psk::DemapDesc) * cap));
-            PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(psk::DemapDesc) * cap));
-            q.desc_cap = cap;
-        }
-        if (n_part > q.part_cap) {
-            if (q.d_part) (void)hipFree(q.d_part);
-            q.d_part = nullptr;
-            q.part_cap = 0;
-            const size_t cap = n_part + n_part / 4u + 256u;
-            PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(psk::DemapPartial) * cap));
-            q.part_cap = cap;
-        }
+        if (on_host && dry.empty())
+            dry.assign(n, Rec{});
+        if (on_host || d)
+            return PSK_SOFT_OK;
+        PSK_TRY(alloc_zeroed(&d, sizeof(Rec) * n, what));
+        cap = n;
         return PSK_SOFT_OK;
     }
-    psk_soft_status upload(Slot &q, size_t nseg, hipStream_t stream)
+    // room for n records in device memory behind every pass of `ring`; what the records held is not kept
+    template <class Ring>
+    psk_soft_status grow(Ring &ring, size_t n)
     {
-        for (const Slot &k : slot)
-            if (&k != &q && k.used && k.stream != stream)
-                PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
-        PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(psk::DemapDesc) * nseg, hipMemcpyHostToDevice, stream));
-        q.used = true, q.stream = stream;
-        return PSK_SOFT_OK;
-    }
-    // the slot is free again behind whatever the pass has put on the stream; returns `st`, the pass's status so far
-    static psk_soft_status finish(Slot &q, hipStream_t stream, psk_soft_status st)
-    {
-        const std::string keep = g_last_error;
-        if (const hipError_t e = hipEventRecord(q.ev, stream)) {
-            (void)hipStreamSynchronize(stream);
-            q.used = false;
-            if (st == PSK_SOFT_OK)
-                return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
-        }
-        g_last_error = keep;
-        return st;
-    }
-    // every pass enqueued so far has ended
-    psk_soft_status wait()
-    {
-        for (Slot &q : slot)
-            if (q.used)
-                PSK_HIP(hipEventSynchronize(q.ev));
+        if (n <= cap)
+            return PSK_SOFT_OK;
+        PSK_TRY(ring.wait());
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        cap = 0;
+        PSK_HIP(hipMalloc((void **)&d, sizeof(Rec) * with_headroom(n)));
+        cap = with_headroom(n);
         return PSK_SOFT_OK;
     }
     void free()
     {
-        for (Slot &q : slot) {
-            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
-            if (q.h_desc) (void)hipHostFree(q.h_desc);
-            if (q.d_desc) (void)hipFree(q.d_desc);
-            if (q.d_part) (void)hipFree(q.d_part);
-        }
+        if (d) (void)hipFree(d);
     }
 };
 
@@ -747,8 +765,7 @@ struct psk_soft_handle {
     // PSK_SOFT_OPT_QUALITY: one record per channel, written by the pass behind every call (psk_quality.hip); a control-plane-only
     // handle keeps them on the host
     int opt_quality = 0;
-    psk_soft_quality_t *d_quality = nullptr;
-    std::vector<psk_soft_quality_t> quality_dry;
+    Records<psk_soft_quality_t> quality;
     PassRing<psk::QualityDesc, psk::QualityPartial, kQualitySlots> qpass;
     struct QualitySnap {
         uint16_t M, S;
@@ -757,12 +774,10 @@ struct psk_soft_handle {
     std::vector<QualitySnap> q_snap;  // scratch of one call: the properties it ran with
     // psk_soft_acquire_device: one record per channel, written by the join of the last call that covered it (psk_acquire.hip); a
     // control-plane-only handle keeps them on the host
-    psk_soft_acquire_t *d_acquire = nullptr;
-    std::vector<psk_soft_acquire_t> acquire_dry;
+    Records<psk_soft_acquire_t> acquire;
     PassRing<psk::AcquireDesc, psk::AcquirePartial, kAcquireSlots> apass;
     // psk_soft_symrate_device: the same for the symbol-rate look (psk_symrate.hip)
-    psk_soft_symrate_t *d_symrate = nullptr;
-    std::vector<psk_soft_symrate_t> symrate_dry;
+    Records<psk_soft_symrate_t> symrate;
     PassRing<psk::SymrateDesc, psk::SymratePartial, kAcquireSlots> spass;
     // psk_soft_sync_device: the words of every slot (kSyncSlots x kSyncMaxWord float2, allocated at the first psk_soft_sync_define),
     // their lengths (0: never defined) and energies Ew; one record per channel, allocated (zeros) at the first call -- a
@@ -770,8 +785,7 @@ struct psk_soft_handle {
     float *d_sync_words = nullptr;
     uint32_t sync_len[psk::kSyncSlots] = {};
     float sync_ew[psk::kSyncSlots] = {};
-    psk_soft_sync_t *d_sync = nullptr;
-    std::vector<psk_soft_sync_t> sync_dry;
+    Records<psk_soft_sync_t> sync;
     PassRing<psk::SyncDesc, psk::SyncPartial, kAcquireSlots> ypass;
     HistoryBank sync_hist{"sync history", psk::kSyncHistSlotFloats, 2u * psk::kSyncHistSlotFloats, 2u * psk::kSyncHist};
     // ... and what PSK_SOFT_DEMAP_FRONT asks of a channel: how the last sync call that covered it left it (empty: no call yet)
@@ -779,15 +793,13 @@ struct psk_soft_handle {
     std::vector<uint8_t> sync_last;
     // psk_soft_demap_device: the maps of every slot (kDemapSlots DemapMap, allocated at the first psk_soft_demap_define; M 0: never
     // defined); one record per segment of the last call, grown on demand -- a control-plane-only handle keeps them on the host --;
-    // the passes' descriptors and partials (DemapRing)
+    // the passes' descriptors grow on demand too, and every pass covers all the records (kAllRecords)
     psk::DemapMap *d_demap_maps = nullptr;
     uint32_t demap_M[psk::kDemapSlots] = {};
-    psk_soft_demap_t *d_demap = nullptr;
-    size_t demap_cap = 0;       // records
+    Records<psk_soft_demap_t> demap;
     bool demap_called = false;
     uint32_t demap_nseg = 0;    // of the last call
-    std::vector<psk_soft_demap_t> demap_dry;
-    DemapRing dpass;
+    PassRing<psk::DemapDesc, psk::DemapPartial, 2> dpass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     CopyPool *pool = nullptr;
@@ -916,13 +928,7 @@ struct Round {
     bool fork = false, deferred = false;
     uint64_t sig = 0;
 };
-// (a phase that fails ends the round with its status)
-#define PSK_TRY(call)                       \
-    do {                                    \
-        const psk_soft_status s_ = (call);  \
-        if (s_ != PSK_SOFT_OK)              \
-            return s_;                      \
-    } while (0)
+// (a phase that fails ends the round with its status: PSK_TRY)
 
 // CS16, CS8 and CF16 channels of the window classes with in-place instantiations (psk_fast_inst.hip, PSK_INST_PKT): a class of
 // their own per format, no conversion.  (What would go through the time-tiled kernels is moved back: move_in_place_back.)
@@ -2141,6 +2147,21 @@ psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, 
     h->slot_stream[r.slot] = r.stream, h->slot_ch0[r.slot] = ch0, h->slot_nch[r.slot] = nch;
     return PSK_SOFT_OK;
 }
+
+// The tail of every psk_soft_get_* of the reduction-pass layer: records [first, first + n) of an entry whose arguments have passed,
+// once every call and every pass of its ring enqueued so far has ended.
+template <class Rec, class Ring>
+psk_soft_status records_read(psk_soft_handle_t *h, const Records<Rec> &recs, Ring &ring, uint32_t first, uint32_t n, Rec *out)
+{
+    if (h->dry) {
+        std::memcpy(out, recs.dry.data() + first, sizeof(Rec) * n);
+        return PSK_SOFT_OK;
+    }
+    PSK_TRY(psk_soft_synchronize(h));
+    PSK_TRY(ring.wait());
+    PSK_HIP(hipMemcpy(out, recs.d + first, sizeof(Rec) * n, hipMemcpyDeviceToHost));
+    return PSK_SOFT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2177,11 +2198,6 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
     h->last_mode.assign(n_channels, psk::PLAN_SKIP);
     h->device = device;
     h->dry = (device == PSK_SOFT_DEVICE_NONE);
-    if (h->dry) {
-        h->quality_dry.assign(n_channels, psk_soft_quality_t{});
-        h->acquire_dry.assign(n_channels, psk_soft_acquire_t{});
-        h->symrate_dry.assign(n_channels, psk_soft_symrate_t{});
-    }
     if (const char *e = std::getenv("PSK_SOFT_TIME_TILED"))
         h->opt_tiled = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
     if (const char *e = std::getenv("PSK_SOFT_FAR_FIT"))  // (as psk_soft_set_option(PSK_SOFT_OPT_FAR_FIT))
@@ -2247,15 +2263,6 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
             return bail("hipMemcpy state", e2);
         if ((e2 = hipMemset(h->d_ring, 0, ring_b)) != hipSuccess) return bail("hipMemset", e2);
         if ((e2 = hipMemset(h->d_yv, 0, yv_b)) != hipSuccess) return bail("hipMemset", e2);
-        if ((e2 = hipMalloc((void **)&h->d_quality, sizeof(psk_soft_quality_t) * (size_t)n_channels)) != hipSuccess)
-            return bail("hipMalloc quality", e2);
-        if ((e2 = hipMemset(h->d_quality, 0, sizeof(psk_soft_quality_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
-        if ((e2 = hipMalloc((void **)&h->d_acquire, sizeof(psk_soft_acquire_t) * (size_t)n_channels)) != hipSuccess)
-            return bail("hipMalloc acquire", e2);
-        if ((e2 = hipMemset(h->d_acquire, 0, sizeof(psk_soft_acquire_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
-        if ((e2 = hipMalloc((void **)&h->d_symrate, sizeof(psk_soft_symrate_t) * (size_t)n_channels)) != hipSuccess)
-            return bail("hipMalloc symrate", e2);
-        if ((e2 = hipMemset(h->d_symrate, 0, sizeof(psk_soft_symrate_t) * (size_t)n_channels)) != hipSuccess) return bail("hipMemset", e2);
         for (int s = 0; s < kPlanSlots; s++) {
             // (a slot = the plans of a call followed by the compact channel lists of its launches: one upload)
             // (... behind the header the kernels find in front of the plans: psk_plan.h)
@@ -2276,6 +2283,14 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
             return bail("hipStreamCreate", e2);
         if (const char *e = std::getenv("PSK_SOFT_PLAN_STREAM"))
             h->opt_up_stream = std::atoi(e) != 0;
+    }
+    // the records of the quality pass and of the two looks: zeros until a pass writes one (the word search's come with its first call)
+    if (h->quality.ensure_zeroed(h->dry, n_channels, "psk_soft_create: quality records") != PSK_SOFT_OK ||
+        h->acquire.ensure_zeroed(h->dry, n_channels, "psk_soft_create: acquire records") != PSK_SOFT_OK ||
+        h->symrate.ensure_zeroed(h->dry, n_channels, "psk_soft_create: symrate records") != PSK_SOFT_OK) {
+        const std::string msg = g_last_error;
+        psk_soft_destroy(h);
+        return fail(PSK_SOFT_ERR_HIP, msg);
     }
     *out = h;
     return PSK_SOFT_OK;
@@ -2298,18 +2313,13 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
         if (h->d_state) (void)hipFree(h->d_state);
         if (h->d_ring) (void)hipFree(h->d_ring);
         if (h->d_yv) (void)hipFree(h->d_yv);
-        h->qpass.free();
-        if (h->d_quality) (void)hipFree(h->d_quality);
-        h->apass.free();
-        if (h->d_acquire) (void)hipFree(h->d_acquire);
-        h->spass.free();
-        if (h->d_symrate) (void)hipFree(h->d_symrate);
-        h->ypass.free();
-        if (h->d_sync) (void)hipFree(h->d_sync);
+        h->qpass.free(), h->quality.free();
+        h->apass.free(), h->acquire.free();
+        h->spass.free(), h->symrate.free();
+        h->ypass.free(), h->sync.free();
         if (h->d_sync_words) (void)hipFree(h->d_sync_words);
         h->sync_hist.free();
-        h->dpass.free();
-        if (h->d_demap) (void)hipFree(h->d_demap);
+        h->dpass.free(), h->demap.free();
         if (h->d_demap_maps) (void)hipFree(h->d_demap_maps);
         if (h->d_tiles) (void)hipFree(h->d_tiles);
         if (h->d_traw) (void)hipFree(h->d_traw);
@@ -2560,7 +2570,7 @@ static psk_soft_status quality_pass(psk_soft_handle_t *h, uint32_t ch0, uint32_t
             r.n_symbols = outs[i].n_symbols;
             r.constelationSize = snap[i].M, r.samplesPerBaud = snap[i].S, r.differentialDecoding = snap[i].diff;
             r.flags = PSK_SOFT_Q_PLANNED;
-            h->quality_dry[ch0 + i] = r;
+            h->quality.dry[ch0 + i] = r;
         }
         return PSK_SOFT_OK;
     }
@@ -2570,8 +2580,7 @@ static psk_soft_status quality_pass(psk_soft_handle_t *h, uint32_t ch0, uint32_t
     PSK_HIP(deferred_join(h, stream));
     auto &q = h->qpass.next();
     PSK_TRY(h->qpass.claim(q, h->nch));
-    uint64_t n_seg = 0;
-    uint32_t max_seg = 0;
+    PieceCount segs;  // (the pieces of this pass: segments of kQualitySegSymbols symbols)
     for (uint32_t i = 0; i < nch; i++) {
         const psk_soft_output_t &o = outs[i];
         psk::QualityDesc &d = q.h_desc[i];
@@ -2593,28 +2602,19 @@ static psk_soft_status quality_pass(psk_soft_handle_t *h, uint32_t ch0, uint32_t
         d.soft = (f & PSK_SOFT_Q_SOFT) ? o.soft : nullptr;
         d.phase = (f & PSK_SOFT_Q_PHASE) ? o.phase : nullptr;
         d.sidx = (f & PSK_SOFT_Q_INDEX) ? o.sampleIndex : nullptr;
-        if (f & (PSK_SOFT_Q_SOFT | PSK_SOFT_Q_INDEX)) {
-            const uint64_t segs = (o.n_symbols + psk::kQualitySegSymbols - 1u) / psk::kQualitySegSymbols;
-            if (n_seg + segs > 0x7fffffffull)
-                return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_process: too many symbols in one call for the quality pass");
-            d.seg0 = (uint32_t)n_seg;
-            d.n_seg = (uint32_t)segs;
-            n_seg += segs;
-            max_seg = d.n_seg > max_seg ? d.n_seg : max_seg;
-        }
+        if ((f & (PSK_SOFT_Q_SOFT | PSK_SOFT_Q_INDEX)) &&
+            !segs.add((o.n_symbols + psk::kQualitySegSymbols - 1u) / psk::kQualitySegSymbols, &d.seg0, &d.n_seg))
+            return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_process: too many symbols in one call for the quality pass");
     }
-    PSK_TRY(h->qpass.grow(q, n_seg));
-    PSK_TRY(h->qpass.upload(q, ch0, nch, stream));
     // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: tiles = segments; `slot` is the call's last plan slot)
-    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_seg, 0, 0, (h->slot + kPlanSlots - 1) % kPlanSlots, stream); };
-    auto enqueue = [&]() -> psk_soft_status {
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, segs.total, 0, 0, (h->slot + kPlanSlots - 1) % kPlanSlots, stream); };
+    return h->qpass.run(q, nch, {ch0, nch}, segs.total, stream, [&]() -> psk_soft_status {
         PSK_HIP(mark("quality_fold"));
-        PSK_HIP(psk::launch_quality_fold(q.d_desc, nch, max_seg, q.d_part, stream));
+        PSK_HIP(psk::launch_quality_fold(q.d_desc, nch, segs.max_piece, q.d_part, stream));
         PSK_HIP(mark("quality_join"));
-        PSK_HIP(psk::launch_quality_join(q.d_desc, nch, q.d_part, h->d_quality, stream));
+        PSK_HIP(psk::launch_quality_join(q.d_desc, nch, q.d_part, h->quality.d, stream));
         return PSK_SOFT_OK;
-    };
-    return h->qpass.finish(q, stream, enqueue());
+    });
 }
 
 // The public entry: the call, and with PSK_SOFT_OPT_QUALITY the reduction pass behind it.
@@ -3357,7 +3357,7 @@ psk_soft_status psk_soft_fir_set_history(psk_soft_handle_t *h, uint32_t ch, cons
 // One look at a packet per channel: the fold over pieces of kAcquirePiece samples and the join per packet, on the caller's stream,
 // one record per covered channel.  Nothing of the control plane or of the demodulator's state is read but constelationSize, and
 // nothing is written but the records (and, for the columns of a frame group, their rows of the gather scratch: front_layout).
-// The descriptors go up from pinned memory of a slot of their own, as the quality pass's.
+// The entry is look_device with kAcquireLook; the pass goes through the reduction-pass layer (PassRing) as the quality pass's does.
 // (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
 static bool acquire_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t &k)
 {
@@ -3365,57 +3365,79 @@ static bool acquire_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_pac
     return k.present && k.sri_mode == 1 && k.n_floats >= 2 && (M == 2 || M == 4 || M == 8);
 }
 
-static psk_soft_status acquire_enqueue(const FrontCall &c, const FrontPlan &plan);
+// What one look at a packet per channel is made of; look_device is the rest of psk_soft_acquire_device and psk_soft_symrate_device.
+struct LookEntry {
+    const StridedEntry &entry;  // its name and its message about alignment
+    bool (*looks_at)(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t &k);    // a packet the call reads
+    uint64_t (*n_used)(psk_soft_handle *h, uint32_t ch, uint64_t n);                   // ... and how many of its n samples
+    void (*plan_record)(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t *k);  // the record of a control-plane-only handle
+                                                                                       // (k: the packet if it is read, else nullptr)
+    psk_soft_status (*enqueue)(const FrontCall &c, const FrontPlan &plan);             // the fold and the join
+};
 
-psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
-                                        const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
+static psk_soft_status look_device(const LookEntry &e, psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                   const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
 {
     if (!h || !pkts || !nch || (uint64_t)ch0 + nch > h->nch)
-        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_acquire_device: bad arguments");
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string(e.entry.name) + ": bad arguments");
     const FrontCall c = {h, ch0, nch, pkts, sample_stride, tune, nullptr, nullptr, stream_v ? (hipStream_t)stream_v : h->stream};
-    // (a packet the call reads: present, complex data, at least one sample, a constellation the M-th power is defined for)
-    auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, pkts[i]); };
+    auto looked_at = [&](uint32_t i) { return e.looks_at(h, ch0 + i, pkts[i]); };
     // the refusals, before anything is enqueued or any record changes
     for (uint32_t i = 0; i < nch; i++) {
         const psk_soft_packet_t &k = pkts[i];
         if (!k.present)
             continue;
-        PSK_TRY(strided_refusal(kAcquireEntry, ch0 + i, k, c.stride(i), looked_at(i)));
+        PSK_TRY(strided_refusal(e.entry, ch0 + i, k, c.stride(i), looked_at(i)));
         if (!psk::pkt_format_known(k.format)) {
             char buf[160];
-            std::snprintf(buf, sizeof buf, "psk_soft_acquire_device: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
-                          ch0 + i, (unsigned)k.format);
+            std::snprintf(buf, sizeof buf, "%s: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
+                          e.entry.name, ch0 + i, (unsigned)k.format);
             return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
         }
         if (looked_at(i) && !k.data && !h->dry)
-            return fail(PSK_SOFT_ERR_INVALID_ARG, kAcquireEntry.misaligned);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, e.entry.misaligned);
     }
     if (h->dry) {
-        for (uint32_t i = 0; i < nch; i++) {
-            psk_soft_acquire_t r = {};
-            if (looked_at(i)) {
-                r.n_samples = pkts[i].n_floats / 2u;
-                r.constelationSize = ctl_of(h, ch0 + i).props.constelationSize;
-                r.flags = PSK_SOFT_A_PLANNED;
-            }
-            h->acquire_dry[ch0 + i] = r;
-        }
+        for (uint32_t i = 0; i < nch; i++) e.plan_record(h, ch0 + i, looked_at(i) ? &pkts[i] : nullptr);
         return PSK_SOFT_OK;
     }
     PSK_HIP(hipSetDevice(h->device));
     // strided packets: the columns of a frame group of at least kGatherMinGroup go through the tile gather into own-format rows of
-    // the stream's gather scratch, which the fold reads; any other strided packet is read where it lies, at its stride
+    // the stream's gather scratch, which the fold reads; any other strided packet is read where it lies, at its stride.  A row
+    // holds the samples the look uses, no more.
     FrontPlan plan;
     plan.singles_in_place = true;
     plan.pkt.assign(nch, FrontPkt{});
     for (uint32_t i = 0; i < nch; i++) {
         plan.pkt[i].gathered = c.stride(i) != 1 && looked_at(i);
         plan.pkt[i].n_in = pkts[i].n_floats / 2u;
+        if (looked_at(i))
+            plan.pkt[i].n_in = e.n_used(h, ch0 + i, plan.pkt[i].n_in);
     }
     psk_soft_status st = front_enqueue(c, plan);
     if (st == PSK_SOFT_OK)
-        st = acquire_enqueue(c, plan);
+        st = e.enqueue(c, plan);
     return plan.owed ? front_release(c, plan, st) : st;
+}
+
+static psk_soft_status acquire_enqueue(const FrontCall &c, const FrontPlan &plan);
+static const LookEntry kAcquireLook = {
+    kAcquireEntry, acquire_looks_at, [](psk_soft_handle *, uint32_t, uint64_t n) { return n; },
+    [](psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t *k) {
+        psk_soft_acquire_t r = {};
+        if (k) {
+            r.n_samples = k->n_floats / 2u;
+            r.constelationSize = ctl_of(h, ch).props.constelationSize;
+            r.flags = PSK_SOFT_A_PLANNED;
+        }
+        h->acquire.dry[ch] = r;
+    },
+    acquire_enqueue};
+
+psk_soft_status psk_soft_acquire_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
+                                        const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
+{
+    return look_device(kAcquireLook, h, ch0, nch, pkts, sample_stride, tune, stream_v);
 }
 
 // the fold and the join of an acquire call whose arguments have passed (plan: the rows of its gathered packets)
@@ -3427,8 +3449,7 @@ static psk_soft_status acquire_enqueue(const FrontCall &c, const FrontPlan &plan
     auto looked_at = [&](uint32_t i) { return acquire_looks_at(h, ch0 + i, c.pkts[i]); };
     auto &q = h->apass.next();
     PSK_TRY(h->apass.claim(q, h->nch));
-    uint64_t n_part = 0;
-    uint32_t max_piece = 0;
+    PieceCount parts;
     bool any_tuned = false;
     for (uint32_t i = 0; i < nch; i++) {
         psk::AcquireDesc &d = q.h_desc[i];
@@ -3449,28 +3470,20 @@ static psk_soft_status acquire_enqueue(const FrontCall &c, const FrontPlan &plan
             d.flags |= PSK_SOFT_A_TUNED;
             any_tuned = true;
         }
-        const uint64_t pieces = (d.n + psk::kAcquirePiece - 1u) / psk::kAcquirePiece;
-        if (pieces > 0x7fffffffull || n_part + pieces > 0x7fffffffull)
+        if (!parts.add((d.n + psk::kAcquirePiece - 1u) / psk::kAcquirePiece, &d.part0, &d.n_piece))
             return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_acquire_device: too many samples in one call");
-        d.part0 = (uint32_t)n_part;
-        d.n_piece = (uint32_t)pieces;
-        n_part += pieces;
-        max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
     }
-    PSK_TRY(h->apass.grow(q, n_part));
-    if (any_tuned)
-        PSK_TRY(ensure_tune_tab(h));
-    PSK_TRY(h->apass.upload(q, ch0, nch, stream));
     // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = covered channels, tiles = pieces)
-    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_part, 0, 0, h->slot, stream); };
-    auto enqueue = [&]() -> psk_soft_status {
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, parts.total, 0, 0, h->slot, stream); };
+    return h->apass.run(q, nch, {ch0, nch}, parts.total, stream, [&]() -> psk_soft_status {
+        if (any_tuned)
+            PSK_TRY(ensure_tune_tab(h));
         PSK_HIP(mark("acquire_fold"));
-        PSK_HIP(psk::launch_acquire_fold(q.d_desc, nch, max_piece, any_tuned ? h->d_tune_tab : nullptr, q.d_part, stream));
+        PSK_HIP(psk::launch_acquire_fold(q.d_desc, nch, parts.max_piece, any_tuned ? h->d_tune_tab : nullptr, q.d_part, stream));
         PSK_HIP(mark("acquire_join"));
-        PSK_HIP(psk::launch_acquire_join(q.d_desc, nch, q.d_part, h->d_acquire, stream));
+        PSK_HIP(psk::launch_acquire_join(q.d_desc, nch, q.d_part, h->acquire.d, stream));
         return PSK_SOFT_OK;
-    };
-    return h->apass.finish(q, stream, enqueue());
+    });
 }
 
 uint64_t psk_soft_acquire_bytes(void) { return sizeof(psk_soft_acquire_t); }
@@ -3480,16 +3493,7 @@ psk_soft_status psk_soft_get_acquire(psk_soft_handle_t *h, uint32_t ch0, uint32_
 {
     if (!h || !rec || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_acquire: bad arguments");
-    if (h->dry) {
-        std::memcpy(rec, h->acquire_dry.data() + ch0, sizeof(psk_soft_acquire_t) * nch);
-        return PSK_SOFT_OK;
-    }
-    const psk_soft_status st = psk_soft_synchronize(h);
-    if (st != PSK_SOFT_OK)
-        return st;
-    PSK_TRY(h->apass.wait());
-    PSK_HIP(hipMemcpy(rec, h->d_acquire + ch0, sizeof(psk_soft_acquire_t) * nch, hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return records_read(h, h->acquire, h->apass, ch0, nch, rec);
 }
 
 psk_soft_status psk_soft_acquire_host(uint16_t constelationSize, const psk_soft_tune_t *tune, const float *in, uint64_t n_complex,
@@ -3574,8 +3578,8 @@ psk_soft_status psk_soft_acquire_derive(const psk_soft_acquire_t *rec, psk_soft_
 }
 
 // ---- psk_soft_symrate_device: the symbol rate of a packet (include/psk_soft_hip.h, psk_symrate.hip) ----
-// The carrier look's shape, one for one: a fold over pieces of kSymratePiece blocks and a join per packet on the caller's stream,
-// one record per covered channel; its refusals, its gather (of the samples the look uses), a pass ring of its own.  Nothing of the
+// The second look (look_device, kSymrateLook): a fold over pieces of kSymratePiece blocks and a join per packet on the caller's
+// stream, one record per covered channel; the gather takes the samples the look uses, no more; a pass ring of its own.  Nothing of the
 // control plane is read but samplesPerBaud, nothing is written but the records and the rows of the gather scratch.
 // (a packet the call reads: present, complex data, a block length the look is defined for, at least two blocks)
 static bool symrate_looks_at(psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t &k)
@@ -3592,61 +3596,30 @@ static uint32_t symrate_blocks(uint64_t n, uint32_t S)
 
 static const StridedEntry kSymrateEntry = {"psk_soft_symrate_device", "psk_soft_symrate_device: packet data must be 8-byte aligned (CS16: 4) (CS8: 2) (CF16: 4)"};
 static psk_soft_status symrate_enqueue(const FrontCall &c, const FrontPlan &plan);
+static const LookEntry kSymrateLook = {
+    kSymrateEntry, symrate_looks_at,
+    [](psk_soft_handle *h, uint32_t ch, uint64_t n) {
+        const uint32_t S = ctl_of(h, ch).props.samplesPerBaud;
+        return (uint64_t)symrate_blocks(n, S) * S;
+    },
+    [](psk_soft_handle *h, uint32_t ch, const psk_soft_packet_t *k) {
+        psk_soft_symrate_t r = {};
+        if (k) {
+            const uint32_t S = ctl_of(h, ch).props.samplesPerBaud;
+            r.n_samples = k->n_floats / 2u;
+            r.n_blocks = symrate_blocks(r.n_samples, S);
+            r.n_used = r.n_blocks * S;
+            r.samplesPerBaud = (uint16_t)S;
+            r.flags = PSK_SOFT_SR_PLANNED;
+        }
+        h->symrate.dry[ch] = r;
+    },
+    symrate_enqueue};
 
 psk_soft_status psk_soft_symrate_device(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, const psk_soft_packet_t *pkts,
                                         const uint64_t *sample_stride, const psk_soft_tune_t *tune, void *stream_v)
 {
-    if (!h || !pkts || !nch || (uint64_t)ch0 + nch > h->nch)
-        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_symrate_device: bad arguments");
-    const FrontCall c = {h, ch0, nch, pkts, sample_stride, tune, nullptr, nullptr, stream_v ? (hipStream_t)stream_v : h->stream};
-    auto looked_at = [&](uint32_t i) { return symrate_looks_at(h, ch0 + i, pkts[i]); };
-    // the refusals, before anything is enqueued or any record changes
-    for (uint32_t i = 0; i < nch; i++) {
-        const psk_soft_packet_t &k = pkts[i];
-        if (!k.present)
-            continue;
-        PSK_TRY(strided_refusal(kSymrateEntry, ch0 + i, k, c.stride(i), looked_at(i)));
-        if (!psk::pkt_format_known(k.format)) {
-            char buf[160];
-            std::snprintf(buf, sizeof buf, "psk_soft_symrate_device: channel %u: unknown packet format %u (PSK_SOFT_FORMAT_CF32 = 0, CS16 = 1, CS8 = 3, CF16 = 4)",
-                          ch0 + i, (unsigned)k.format);
-            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
-        }
-        if (looked_at(i) && !k.data && !h->dry)
-            return fail(PSK_SOFT_ERR_INVALID_ARG, kSymrateEntry.misaligned);
-    }
-    if (h->dry) {
-        for (uint32_t i = 0; i < nch; i++) {
-            psk_soft_symrate_t r = {};
-            if (looked_at(i)) {
-                const uint32_t S = ctl_of(h, ch0 + i).props.samplesPerBaud;
-                r.n_samples = pkts[i].n_floats / 2u;
-                r.n_blocks = symrate_blocks(r.n_samples, S);
-                r.n_used = r.n_blocks * S;
-                r.samplesPerBaud = (uint16_t)S;
-                r.flags = PSK_SOFT_SR_PLANNED;
-            }
-            h->symrate_dry[ch0 + i] = r;
-        }
-        return PSK_SOFT_OK;
-    }
-    PSK_HIP(hipSetDevice(h->device));
-    // strided packets as in psk_soft_acquire_device; a row holds the samples the look uses, no more
-    FrontPlan plan;
-    plan.singles_in_place = true;
-    plan.pkt.assign(nch, FrontPkt{});
-    for (uint32_t i = 0; i < nch; i++) {
-        plan.pkt[i].gathered = c.stride(i) != 1 && looked_at(i);
-        plan.pkt[i].n_in = pkts[i].n_floats / 2u;
-        if (looked_at(i)) {
-            const uint32_t S = ctl_of(h, ch0 + i).props.samplesPerBaud;
-            plan.pkt[i].n_in = (uint64_t)symrate_blocks(plan.pkt[i].n_in, S) * S;
-        }
-    }
-    psk_soft_status st = front_enqueue(c, plan);
-    if (st == PSK_SOFT_OK)
-        st = symrate_enqueue(c, plan);
-    return plan.owed ? front_release(c, plan, st) : st;
+    return look_device(kSymrateLook, h, ch0, nch, pkts, sample_stride, tune, stream_v);
 }
 
 // the fold and the join of a symbol-rate call whose arguments have passed (plan: the rows of its gathered packets)
@@ -3657,8 +3630,7 @@ static psk_soft_status symrate_enqueue(const FrontCall &c, const FrontPlan &plan
     const hipStream_t stream = c.stream;
     auto &q = h->spass.next();
     PSK_TRY(h->spass.claim(q, h->nch));
-    uint64_t n_part = 0;
-    uint32_t max_piece = 0;
+    PieceCount parts;
     for (uint32_t i = 0; i < nch; i++) {
         psk::SymrateDesc &d = q.h_desc[i];
         d = psk::SymrateDesc{};
@@ -3679,24 +3651,19 @@ static psk_soft_status symrate_enqueue(const FrontCall &c, const FrontPlan &plan
             d.phase = c.tune[i].phase, d.step = c.tune[i].step;
             d.flags |= PSK_SOFT_SR_TUNED;
         }
-        d.part0 = (uint32_t)n_part;
-        d.n_piece = (d.n_blocks + psk::kSymratePiece - 1u) / psk::kSymratePiece;  // (at most 8 a packet: no overflow to refuse)
-        n_part += d.n_piece;
-        max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
+        // (at most 8 pieces a packet: the count cannot refuse)
+        (void)parts.add((d.n_blocks + psk::kSymratePiece - 1u) / psk::kSymratePiece, &d.part0, &d.n_piece);
     }
-    PSK_TRY(h->spass.grow(q, n_part));
-    PSK_TRY(ensure_tune_tab(h));  // (the block phasors come from the tables, tuned or not)
-    PSK_TRY(h->spass.upload(q, ch0, nch, stream));
     // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = covered channels, tiles = pieces)
-    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_part, 0, 0, h->slot, stream); };
-    auto enqueue = [&]() -> psk_soft_status {
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, parts.total, 0, 0, h->slot, stream); };
+    return h->spass.run(q, nch, {ch0, nch}, parts.total, stream, [&]() -> psk_soft_status {
+        PSK_TRY(ensure_tune_tab(h));  // (the block phasors come from the tables, tuned or not)
         PSK_HIP(mark("symrate_fold"));
-        PSK_HIP(psk::launch_symrate_fold(q.d_desc, nch, max_piece, h->d_tune_tab, q.d_part, stream));
+        PSK_HIP(psk::launch_symrate_fold(q.d_desc, nch, parts.max_piece, h->d_tune_tab, q.d_part, stream));
         PSK_HIP(mark("symrate_join"));
-        PSK_HIP(psk::launch_symrate_join(q.d_desc, nch, q.d_part, h->d_symrate, stream));
+        PSK_HIP(psk::launch_symrate_join(q.d_desc, nch, q.d_part, h->symrate.d, stream));
         return PSK_SOFT_OK;
-    };
-    return h->spass.finish(q, stream, enqueue());
+    });
 }
 
 uint64_t psk_soft_symrate_bytes(void) { return sizeof(psk_soft_symrate_t); }
@@ -3706,16 +3673,7 @@ psk_soft_status psk_soft_get_symrate(psk_soft_handle_t *h, uint32_t ch0, uint32_
 {
     if (!h || !rec || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_symrate: bad arguments");
-    if (h->dry) {
-        std::memcpy(rec, h->symrate_dry.data() + ch0, sizeof(psk_soft_symrate_t) * nch);
-        return PSK_SOFT_OK;
-    }
-    const psk_soft_status st = psk_soft_synchronize(h);
-    if (st != PSK_SOFT_OK)
-        return st;
-    PSK_TRY(h->spass.wait());
-    PSK_HIP(hipMemcpy(rec, h->d_symrate + ch0, sizeof(psk_soft_symrate_t) * nch, hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return records_read(h, h->symrate, h->spass, ch0, nch, rec);
 }
 
 psk_soft_status psk_soft_symrate_host(uint16_t samplesPerBaud, const psk_soft_tune_t *tune, const float *in, uint64_t n_complex,
@@ -3851,27 +3809,6 @@ psk_soft_status psk_soft_sync_define(psk_soft_handle_t *h, uint32_t slot, const 
 static bool sync_searched(const psk_soft_sync_in_t &k) { return k.word != 0u && k.soft != nullptr && k.n_symbols != 0u; }
 static bool sync_threshold_ok(float t) { return t > 0.0f && t <= 1.0f; }  // (false for NaN)
 
-// the records of a handle, zeros until a call writes one
-static psk_soft_status sync_records_ensure(psk_soft_handle *h)
-{
-    if (h->dry) {
-        if (h->sync_dry.empty())
-            h->sync_dry.assign(h->nch, psk_soft_sync_t{});
-        return PSK_SOFT_OK;
-    }
-    if (h->d_sync)
-        return PSK_SOFT_OK;
-    psk_soft_sync_t *p = nullptr;
-    const size_t bytes = sizeof(psk_soft_sync_t) * (size_t)h->nch;
-    PSK_HIP(hipMalloc((void **)&p, bytes));
-    if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(p);  // (the memset is through before a launch on any stream writes a record)
-        return fail(PSK_SOFT_ERR_HIP, "sync records: hipMemset failed");
-    }
-    h->d_sync = p;
-    return PSK_SOFT_OK;
-}
-
 static psk_soft_status sync_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t nch, const psk_soft_sync_in_t *in, hipStream_t stream);
 
 // how a call that went through leaves its covered channels for PSK_SOFT_DEMAP_FRONT: searched or not, and with which flags
@@ -3913,7 +3850,7 @@ psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_
             return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
         }
     }
-    PSK_TRY(sync_records_ensure(h));
+    PSK_TRY(h->sync.ensure_zeroed(h->dry, h->nch, "sync records"));  // (zeros until a call writes one)
     if (h->dry) {
         for (uint32_t i = 0; i < nch; i++) {
             psk_soft_sync_t r = {};
@@ -3924,7 +3861,7 @@ psk_soft_status psk_soft_sync_device(psk_soft_handle_t *h, uint32_t ch0, uint32_
                 r.n_windows = psk::sync_windows(in[i].n_symbols, r.word_len, (in[i].flags & PSK_SOFT_SYNC_RESTART) != 0, &p0);
                 r.flags = PSK_SOFT_SYNC_PLANNED;
             }
-            h->sync_dry[ch0 + i] = r;
+            h->sync.dry[ch0 + i] = r;
         }
         sync_remember(h, ch0, nch, in);
         return PSK_SOFT_OK;
@@ -3951,8 +3888,7 @@ static psk_soft_status sync_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t n
 {
     auto &q = h->ypass.next();
     PSK_TRY(h->ypass.claim(q, h->nch));
-    uint64_t n_part = 0;
-    uint32_t max_piece = 0;
+    PieceCount parts;
     for (uint32_t i = 0; i < nch; i++) {
         psk::SyncDesc &d = q.h_desc[i];
         d = psk::SyncDesc{};
@@ -3971,27 +3907,19 @@ static psk_soft_status sync_enqueue(psk_soft_handle *h, uint32_t ch0, uint32_t n
         d.flags = psk::kSyncData | (restart ? psk::kSyncRestart : 0u);
         d.threshold = k.threshold, d.Ew = h->sync_ew[slot];
         // (a row without a window still has a piece: its workgroup writes the history)
-        const uint32_t pieces = d.n_windows ? (d.n_windows + psk::kSyncPiece - 1u) / psk::kSyncPiece : 1u;
-        if (n_part + pieces > 0x7fffffffull)
+        if (!parts.add(d.n_windows ? (d.n_windows + psk::kSyncPiece - 1u) / psk::kSyncPiece : 1u, &d.part0, &d.n_piece))
             return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_sync_device: too many symbols in one call");
-        d.part0 = (uint32_t)n_part;
-        d.n_piece = pieces;
-        n_part += pieces;
-        max_piece = pieces > max_piece ? pieces : max_piece;
     }
-    PSK_TRY(h->ypass.grow(q, n_part));
-    PSK_TRY(h->ypass.upload(q, ch0, nch, stream));
     // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = covered channels, tiles = pieces)
-    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, n_part, 0, 0, h->slot, stream); };
-    auto enqueue = [&]() -> psk_soft_status {
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, ch0, nch, parts.total, 0, 0, h->slot, stream); };
+    return h->ypass.run(q, nch, {ch0, nch}, parts.total, stream, [&]() -> psk_soft_status {
         PSK_HIP(mark("sync_fold"));
-        PSK_HIP(psk::launch_sync_fold(q.d_desc, nch, max_piece, q.d_part, stream));
+        PSK_HIP(psk::launch_sync_fold(q.d_desc, nch, parts.max_piece, q.d_part, stream));
         PSK_HIP(mark("sync_join"));
-        PSK_HIP(psk::launch_sync_join(q.d_desc, nch, q.d_part, h->d_sync, stream));
+        PSK_HIP(psk::launch_sync_join(q.d_desc, nch, q.d_part, h->sync.d, stream));
         PSK_TRY(h->sync_hist.record(stream));
         return PSK_SOFT_OK;
-    };
-    return h->ypass.finish(q, stream, enqueue());
+    });
 }
 
 uint64_t psk_soft_sync_bytes(void) { return sizeof(psk_soft_sync_t); }
@@ -4003,20 +3931,11 @@ psk_soft_status psk_soft_get_sync(psk_soft_handle_t *h, uint32_t ch0, uint32_t n
 {
     if (!h || !rec || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_sync: bad arguments");
-    if (h->dry ? h->sync_dry.empty() : !h->d_sync) {  // (no call yet: the records are zeros)
+    if (!h->sync.exist()) {  // (no call yet: the records are zeros)
         std::memset(rec, 0, sizeof(psk_soft_sync_t) * nch);
         return PSK_SOFT_OK;
     }
-    if (h->dry) {
-        std::memcpy(rec, h->sync_dry.data() + ch0, sizeof(psk_soft_sync_t) * nch);
-        return PSK_SOFT_OK;
-    }
-    const psk_soft_status st = psk_soft_synchronize(h);
-    if (st != PSK_SOFT_OK)
-        return st;
-    PSK_TRY(h->ypass.wait());
-    PSK_HIP(hipMemcpy(rec, h->d_sync + ch0, sizeof(psk_soft_sync_t) * nch, hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return records_read(h, h->sync, h->ypass, ch0, nch, rec);
 }
 
 // the history of a channel: its current slot, behind the last sync launch
@@ -4113,8 +4032,9 @@ psk_soft_status psk_soft_sync_derive(const psk_soft_sync_hit_t *hit, uint16_t co
 
 // ---- psk_soft_demap_device: segments of the soft rows as per-bit LLRs (include/psk_soft_hip.h, psk_demap.hip) ----
 // Behind the sync call: a fold over pieces of kDemapPiece symbols and a join per segment on the caller's stream, one record per
-// segment of the call; a ring of its own (DemapRing).  Nothing of the control plane, of the demodulator's state or of any other
-// record is read or written; of the sync pass only the history slot its last call read.
+// segment of the call; a ring of its own, two slots whose descriptors grow on demand (up to 2^20 segments a call).  Nothing of the
+// control plane, of the demodulator's state or of any other record is read or written; of the sync pass only the history slot its
+// last call read.
 static bool demap_map_ok(uint32_t M, const float *points, const uint8_t *labels)
 {
     if (M != 2u && M != 4u && M != 8u)
@@ -4142,15 +4062,8 @@ psk_soft_status psk_soft_demap_define(psk_soft_handle_t *h, uint32_t slot, uint3
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_demap_define: null pointer, a slot above 15, an M other than 2, 4, 8, a non-finite point or labels that are not a permutation of 0 .. M-1");
     if (!h->dry) {
         PSK_HIP(hipSetDevice(h->device));
-        if (!h->d_demap_maps) {
-            psk::DemapMap *p = nullptr;
-            PSK_HIP(hipMalloc((void **)&p, sizeof(psk::DemapMap) * psk::kDemapSlots));
-            if (hipMemset(p, 0, sizeof(psk::DemapMap) * psk::kDemapSlots) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-                (void)hipFree(p);
-                return fail(PSK_SOFT_ERR_HIP, "demap maps: hipMemset failed");
-            }
-            h->d_demap_maps = p;
-        }
+        if (!h->d_demap_maps)
+            PSK_TRY(alloc_zeroed(&h->d_demap_maps, sizeof(psk::DemapMap) * psk::kDemapSlots, "demap maps"));
         PSK_TRY(h->dpass.wait());  // (no launch is still reading the slot)
         const psk::DemapMap m = demap_map_make(M, points, labels);
         PSK_HIP(hipMemcpy(h->d_demap_maps + slot, &m, sizeof m, hipMemcpyHostToDevice));
@@ -4213,11 +4126,11 @@ psk_soft_status psk_soft_demap_device(psk_soft_handle_t *h, uint32_t nseg, const
         }
     }
     if (h->dry) {
-        h->demap_dry.assign(nseg, psk_soft_demap_t{});
+        h->demap.dry.assign(nseg, psk_soft_demap_t{});
         for (uint32_t i = 0; i < nseg; i++) {
             if (demap_skipped(in[i]))
                 continue;
-            psk_soft_demap_t &r = h->demap_dry[i];
+            psk_soft_demap_t &r = h->demap.dry[i];
             const uint32_t M = h->demap_M[in[i].map - 1u];
             r.n_symbols = in[i].count;
             r.bits = M == 2u ? 1u : M == 4u ? 2u : 3u;
@@ -4236,24 +4149,16 @@ psk_soft_status psk_soft_demap_device(psk_soft_handle_t *h, uint32_t nseg, const
 // the fold and the join of a demap call whose arguments have passed
 static psk_soft_status demap_enqueue(psk_soft_handle *h, uint32_t nseg, const psk_soft_demap_in_t *in, hipStream_t stream)
 {
-    uint64_t n_part = 0;
+    // (counted ahead of the descriptors: a call that is refused for its size leaves the last call's records standing)
+    PieceCount parts;
+    uint32_t ignored;
     for (uint32_t i = 0; i < nseg; i++)
-        if (!demap_skipped(in[i]))
-            n_part += psk::demap_pieces(in[i].count);
-    if (n_part > 0x7fffffffull)
-        return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_demap_device: too many symbols in one call");
-    if (nseg > h->demap_cap) {  // (the records are the last call's: nothing of them is kept)
-        PSK_TRY(h->dpass.wait());
-        if (h->d_demap) (void)hipFree(h->d_demap);
-        h->d_demap = nullptr;
-        h->demap_cap = 0;
-        const size_t cap = (size_t)nseg + nseg / 4u + 256u;
-        PSK_HIP(hipMalloc((void **)&h->d_demap, sizeof(psk_soft_demap_t) * cap));
-        h->demap_cap = cap;
-    }
+        if (!demap_skipped(in[i]) && !parts.add(psk::demap_pieces(in[i].count), &ignored, &ignored))
+            return fail(PSK_SOFT_ERR_LIMIT, "psk_soft_demap_device: too many symbols in one call");
+    PSK_TRY(h->demap.grow(h->dpass, nseg));  // (the records are the last call's: nothing of them is kept)
     auto &q = h->dpass.next();
-    PSK_TRY(h->dpass.claim(q, nseg, n_part));
-    uint32_t part0 = 0, max_piece = 0;
+    PSK_TRY(h->dpass.claim(q, nseg, nseg / 4u + 256u));
+    parts = PieceCount{};
     for (uint32_t i = 0; i < nseg; i++) {
         psk::DemapDesc &d = q.h_desc[i];
         d = psk::DemapDesc{};
@@ -4266,24 +4171,20 @@ static psk_soft_status demap_enqueue(psk_soft_handle *h, uint32_t nseg, const ps
             d.front = h->sync_hist.out(k.channel);
         d.map = k.map - 1u;
         d.flags = psk::kDemapData | ((k.flags & PSK_SOFT_DEMAP_I8) ? psk::kDemapI8 : 0u);
-        d.part0 = part0, d.n_piece = psk::demap_pieces(k.count);
+        (void)parts.add(psk::demap_pieces(k.count), &d.part0, &d.n_piece);  // (counted above: it fits)
         d.gain_re = k.gain_re, d.gain_im = k.gain_im, d.scale = k.scale;
-        part0 += d.n_piece;
-        max_piece = d.n_piece > max_piece ? d.n_piece : max_piece;
     }
-    PSK_TRY(h->dpass.upload(q, nseg, stream));
-    // the records are the new call's from here on, also if a launch below fails
-    h->demap_called = true, h->demap_nseg = nseg;
     // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = segments, tiles = pieces)
-    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, 0, nseg, n_part, 0, 0, h->slot, stream); };
-    auto enqueue = [&]() -> psk_soft_status {
+    auto mark = [&](const char *what) { return trace_launch(h, what, 0, 0, 0, nseg, parts.total, 0, 0, h->slot, stream); };
+    return h->dpass.run(q, nseg, kAllRecords, parts.total, stream, [&]() -> psk_soft_status {
+        // the descriptors are up: the records are the new call's from here on, also if a launch below fails
+        h->demap_called = true, h->demap_nseg = nseg;
         PSK_HIP(mark("demap_fold"));
-        PSK_HIP(psk::launch_demap_fold(q.d_desc, nseg, max_piece, h->d_demap_maps, q.d_part, stream));
+        PSK_HIP(psk::launch_demap_fold(q.d_desc, nseg, parts.max_piece, h->d_demap_maps, q.d_part, stream));
         PSK_HIP(mark("demap_join"));
-        PSK_HIP(psk::launch_demap_join(q.d_desc, nseg, h->d_demap_maps, q.d_part, h->d_demap, stream));
+        PSK_HIP(psk::launch_demap_join(q.d_desc, nseg, h->d_demap_maps, q.d_part, h->demap.d, stream));
         return PSK_SOFT_OK;
-    };
-    return h->dpass.finish(q, stream, enqueue());
+    });
 }
 
 uint64_t psk_soft_demap_bytes(void) { return sizeof(psk_soft_demap_t); }
@@ -4295,16 +4196,7 @@ psk_soft_status psk_soft_get_demap(psk_soft_handle_t *h, uint32_t first, uint32_
 {
     if (!h || !rec || !n || !h->demap_called || (uint64_t)first + n > h->demap_nseg)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_demap: null pointer, no psk_soft_demap_device call yet or a range beyond its segments");
-    if (h->dry) {
-        std::memcpy(rec, h->demap_dry.data() + first, sizeof(psk_soft_demap_t) * n);
-        return PSK_SOFT_OK;
-    }
-    const psk_soft_status st = psk_soft_synchronize(h);
-    if (st != PSK_SOFT_OK)
-        return st;
-    PSK_TRY(h->dpass.wait());
-    PSK_HIP(hipMemcpy(rec, h->d_demap + first, sizeof(psk_soft_demap_t) * n, hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return records_read(h, h->demap, h->dpass, first, n, rec);
 }
 
 psk_soft_status psk_soft_demap_host(const float *points, const uint8_t *labels, uint32_t M, const psk_soft_demap_in_t *in, const float *front,
@@ -4735,15 +4627,7 @@ psk_soft_status psk_soft_get_quality(psk_soft_handle_t *h, uint32_t ch0, uint32_
 {
     if (!h || !q || !nch || (uint64_t)ch0 + nch > h->nch)
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_quality: bad arguments");
-    if (h->dry) {
-        std::memcpy(q, h->quality_dry.data() + ch0, sizeof(psk_soft_quality_t) * nch);
-        return PSK_SOFT_OK;
-    }
-    const psk_soft_status st = quality_wait(h);
-    if (st != PSK_SOFT_OK)
-        return st;
-    PSK_HIP(hipMemcpy(q, h->d_quality + ch0, sizeof(psk_soft_quality_t) * nch, hipMemcpyDeviceToHost));
-    return PSK_SOFT_OK;
+    return records_read(h, h->quality, h->qpass, ch0, nch, q);
 }
 
 psk_soft_status psk_soft_quality_derive(const psk_soft_quality_t *q, psk_soft_quality_derived_t *d)
@@ -4799,12 +4683,12 @@ psk_soft_status psk_soft_set_option(psk_soft_handle_t *h, int option, int value)
             return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_set_option: PSK_SOFT_OPT_QUALITY takes 0 or 1");
         if (value) {  // (all records zeroed)
             if (h->dry) {
-                h->quality_dry.assign(h->nch, psk_soft_quality_t{});
+                h->quality.dry.assign(h->nch, psk_soft_quality_t{});
             } else {
                 const psk_soft_status st = quality_wait(h);
                 if (st != PSK_SOFT_OK)
                     return st;
-                PSK_HIP(hipMemset(h->d_quality, 0, sizeof(psk_soft_quality_t) * (size_t)h->nch));
+                PSK_HIP(hipMemset(h->quality.d, 0, sizeof(psk_soft_quality_t) * (size_t)h->nch));
             }
         }
         h->opt_quality = value;

@@ -445,6 +445,60 @@ def test_two_calls_back_to_back_on_one_stream():
         pl.load().hipStreamDestroy(stream)
 
 
+def test_three_calls_on_two_streams_with_the_descriptors_growing():
+    """3, 700 and 2 segments on stream A, stream B, stream A, no wait between them: the first call's slot holds 3 + 0 + 256
+    descriptors, the second makes a slot and the handle's records grow, the third reuses a grown slot.  Segments of 1 .. 1500
+    symbols (one or two pieces).  All three calls' outputs and guards are whole, the records are the third call's, and outputs and
+    records are those of the same calls with a wait after each."""
+    M = 4
+    row = dm.noisy_row(M, 3000, 96)
+    counts = [1, 1023, 1024, 1025, 1500] + [1 + (37 * k) % 90 for k in range(690)] + [P + 1 + 9 * k for k in range(5)]
+    calls = [[Seg(0, 5 * k, 900 + 300 * k, SLOT[M], pl.DEMAP_I8 * (k % 2), mis=k % 4 if k % 2 else 0) for k in range(3)],
+             [Seg(0, (11 * k) % 1400, n, SLOT[M], pl.DEMAP_I8 * (k % 2), mis=k % 4 if k % 2 else 0, scale=2.0 + k % 3) for k, n in enumerate(counts)],
+             [Seg(0, 3, 1400, SLOT[M], 0, scale=1.5), Seg(0, 2000, 77, SLOT[M], pl.DEMAP_I8, mis=3)]]
+    assert [len(c) for c in calls] == [3, 700, 2] and min(counts) == 1 and max(counts) == 1500
+    every = [s for c in calls for s in c]
+    want = [s.expect([row]) for s in every]
+    a, b = _second_stream(), _second_stream()
+
+    def run(in_flight):
+        h = _handle()
+        rows = outs = None
+        try:
+            rows = Guarded(h, [row.nbytes], fill={0: row})
+            outs = Guarded(h, [s.count * s.B * s.item for s in every], [s.mis for s in every])
+            k0 = 0
+            for segs, stream in zip(calls, (a, b, a)):
+                arr = (pl.DemapIn * len(segs))()
+                for i, s in enumerate(segs):
+                    arr[i] = pl.DemapIn(rows.ptr(0), 3000, s.pos, outs.ptr(k0 + i), s.count, 0, s.slot + 1, s.flags, s.gain[0], s.gain[1], s.scale, 0)
+                h.demap_device(arr, stream.value)
+                if not in_flight:
+                    h.synchronize()
+                    assert pl.load().hipStreamSynchronize(stream) == 0
+                k0 += len(segs)
+            recs = bytes(h.demap_records(0, 2))
+            with pytest.raises(pl.PskSoftError):
+                h.demap_records(0, 3)
+            outs.check({(k, 0): b_ for k, (b_, _) in enumerate(want)}, "the outputs of the three calls and their guards")
+            rows.check({}, "the row and its guards")
+            return recs, h.download(outs.dev, (outs.size,), np.uint8).tobytes()
+        finally:
+            for g in (rows, outs):
+                if g:
+                    g.free()
+            h.close()
+
+    try:
+        flight, waited = run(True), run(False)
+        for i in range(2):
+            dm.assert_same(flight[0][64 * i: 64 * (i + 1)], want[703 + i][1], "third call, segment %d" % i)
+        assert flight == waited
+    finally:
+        for s in (a, b):
+            pl.load().hipStreamDestroy(s)
+
+
 # ---- 5. deferred join; the demodulator is left alone ------------------------------------------------------------------------------
 
 def _process_then_demap(deferred, stream, with_demap=True):

@@ -247,6 +247,65 @@ def test_a_record_does_not_depend_on_the_batch_the_handle_or_the_stream():
         pl.load().hipStreamDestroy(second)
 
 
+def test_slot_ring_wraps_with_sync_calls_in_flight_on_two_streams():
+    """Nine calls back to back -- one more than two turns of the four-slot ring -- over channels [0, 6) and [2, 8) in turn, on the
+    handle's stream and a second one in turn, nothing waited for until the records are read: every channel's record and history
+    are the model's for the whole sequence of calls that covered it, and byte for byte those of the same calls with a wait after
+    each.  Rows of 1100 .. 1200 symbols are two pieces each (a row that continues has as many windows as symbols), so the rows of
+    channels 1 and 6 have 1000 .. 1024 symbols: one piece."""
+    C, K, L, slot = 8, 9, 16, 7
+    word = _word(L, 516)
+    spans = [(0, 6) if k % 2 == 0 else (2, 6) for k in range(K)]
+    n_of = lambda k, c: 1000 + (5 * k + c) % 25 if c in (1, 6) else 1100 + (37 * k + 11 * c) % 101  # noqa: E731
+    rows = [[_row(n_of(k, c), 31000 + 16 * k + c, word, at=(40 + 3 * c, n_of(k, c) - 5 - c)) for c in range(lo, lo + n)]
+            for k, (lo, n) in enumerate(spans)]
+    sizes = sorted({x.size // 2 for r in rows for x in r})
+    assert sizes[0] <= P < 1100 <= sizes[-1] <= 1200
+    off, size = [], 0
+    for r in rows:
+        off.append([])
+        for x in r:
+            off[-1].append(-(-size // 128) * 128)
+            size = off[-1][-1] + x.nbytes
+    arena = np.zeros(size, np.uint8)
+    for r, o in zip(rows, off):
+        for x, at in zip(r, o):
+            arena[at: at + x.nbytes] = x.view(np.uint8)
+    # the model: each channel's calls in order, the history carried from one to the next
+    want, hist = [None] * C, [None] * C
+    for k, (lo, n) in enumerate(spans):
+        for i in range(n):
+            want[lo + i], hist[lo + i] = sm.model_record(word, THR, rows[k][i], 0, hist[lo + i])
+    second = _second_stream()
+
+    def run(in_flight):
+        h = _handle(C)
+        d = h.device_alloc(size)
+        try:
+            h.sync_define(slot, word)
+            h.upload(d, arena)
+            for k, (lo, n) in enumerate(spans):
+                ins = [pl.SyncIn(d + off[k][i], rows[k][i].size // 2, slot + 1, 0, THR, 0) for i in range(n)]
+                h.sync_device(lo, ins, None if k % 2 == 0 else second.value)
+                if not in_flight:
+                    h.synchronize()
+                    assert pl.load().hipStreamSynchronize(second) == 0
+            recs = h.sync_records()
+            return recs, [h.sync_history(c).tobytes() for c in range(C)]
+        finally:
+            h.device_free(d)
+            h.close()
+
+    try:
+        (flight, flight_hist), (waited, waited_hist) = run(True), run(False)
+        for c in range(C):
+            sm.assert_same(flight[c], want[c], "channel %d" % c)
+        assert bytes(flight) == bytes(waited)
+        assert flight_hist == waited_hist and flight_hist == [x.tobytes() for x in hist]
+    finally:
+        pl.load().hipStreamDestroy(second)
+
+
 # ---- 4. the history ---------------------------------------------------------------------------------------------------------------
 
 def _abs_hits(rec, shift):
