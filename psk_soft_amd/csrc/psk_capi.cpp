@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -117,18 +118,127 @@ psk_soft_status fail(psk_soft_status st, const std::string &msg)
 
 // n and a quarter more: what a buffer that is grown on demand is given when n no longer fit
 inline size_t with_headroom(size_t n) { return n + n / 4u + 256u; }
-// Device memory of `bytes` zeros in *out, `what` in the message of a failure.  The memset is through before a launch on any stream
+
+// ---- ownership ("Ownership") ----
+// Whatever the handle holds of the HIP runtime -- device memory, pinned memory, events, streams -- is a member of one of the four
+// types below, in the handle or in a struct the handle contains: the destructor gives it back, and nothing else does.  None can be
+// copied.  An empty owner makes no HIP call, in any method or in its destructor: a control-plane-only handle never touches the runtime.
+struct DeviceMem {
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes); }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+// memory of either kind, in bytes (what grow_scratch sees of a buffer) ...
+template <class Mem>
+class OwnedBytes {
+public:
+    OwnedBytes() = default;
+    OwnedBytes(const OwnedBytes &) = delete;
+    OwnedBytes &operator=(const OwnedBytes &) = delete;
+    ~OwnedBytes() { release(); }
+    void release()
+    {
+        if (p_)
+            Mem::free(p_);
+        p_ = nullptr;
+    }
+    // what is held is released, then `bytes` are allocated; a failure leaves the owner empty
+    hipError_t alloc_bytes(size_t bytes)
+    {
+        release();
+        const hipError_t e = Mem::alloc(&p_, bytes);
+        if (e != hipSuccess)
+            p_ = nullptr;
+        return e;
+    }
+
+protected:
+    void *p_ = nullptr;
+};
+// ... and as n elements of T; reads as the T * it holds
+template <class T, class Mem>
+class OwnedBuf : public OwnedBytes<Mem> {
+public:
+    hipError_t alloc(size_t n) { return this->alloc_bytes(sizeof(T) * n); }
+    T *get() const { return static_cast<T *>(this->p_); }
+    operator T *() const { return get(); }
+};
+template <class T>
+using DeviceBuf = OwnedBuf<T, DeviceMem>;
+template <class T>
+using PinnedBuf = OwnedBuf<T, PinnedMem>;
+
+// An event (no timing, unless asked for) and whether it has been recorded since it was last cleared: both waits do nothing on one
+// that was not.  Created by ensure() where its site creates it, else by its first record.
+class Event {
+public:
+    Event() = default;
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event()
+    {
+        if (ev_)  // (what it stands behind may be on a stream the caller brought, which nobody else waits for)
+            (void)sync(), (void)hipEventDestroy(ev_);
+    }
+    explicit operator bool() const { return ev_ != nullptr; }
+    hipEvent_t get() const { return ev_; }
+    hipError_t ensure(bool timing = false)
+    {
+        if (ev_)
+            return hipSuccess;
+        return timing ? hipEventCreate(&ev_) : hipEventCreateWithFlags(&ev_, hipEventDisableTiming);
+    }
+    hipError_t record(hipStream_t stream)
+    {
+        if (const hipError_t e = ensure())
+            return e;
+        const hipError_t e = hipEventRecord(ev_, stream);
+        recorded_ = recorded_ || e == hipSuccess;
+        return e;
+    }
+    bool recorded() const { return recorded_; }
+    void clear() { recorded_ = false; }  // (it has completed, or what it stood for is void: nothing waits for it again)
+    hipError_t wait(hipStream_t stream) const { return recorded_ ? hipStreamWaitEvent(stream, ev_, 0) : hipSuccess; }  // `stream` waits
+    hipError_t sync() const { return recorded_ ? hipEventSynchronize(ev_) : hipSuccess; }                              // the host waits
+
+private:
+    hipEvent_t ev_ = nullptr;
+    bool recorded_ = false;
+};
+
+// A non-blocking stream, created where its site creates it; the destructor waits for what it carries.
+class Stream {
+public:
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream()
+    {
+        if (s_)
+            (void)hipStreamSynchronize(s_), (void)hipStreamDestroy(s_);
+    }
+    hipError_t create() { return hipStreamCreateWithFlags(&s_, hipStreamNonBlocking); }
+    hipError_t create(int priority) { return hipStreamCreateWithPriority(&s_, hipStreamNonBlocking, priority); }
+    hipError_t sync() const { return s_ ? hipStreamSynchronize(s_) : hipSuccess; }
+    operator hipStream_t() const { return s_; }
+
+private:
+    hipStream_t s_ = nullptr;
+};
+
+// Device memory of n zeroed T in `out`, `what` in the message of a failure.  The memset is through before a launch on any stream
 // reads or writes the memory.
 template <class T>
-psk_soft_status alloc_zeroed(T **out, size_t bytes, const char *what)
+psk_soft_status alloc_zeroed(DeviceBuf<T> &out, size_t n, const char *what)
 {
-    void *p = nullptr;
-    PSK_HIP(hipMalloc((void **)&p, bytes));
-    if (hipMemset(p, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(p);
+    PSK_HIP(out.alloc(n));
+    if (hipMemset(out, 0, sizeof(T) * n) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        out.release();
         return fail(PSK_SOFT_ERR_HIP, std::string(what) + ": hipMemset failed");
     }
-    *out = static_cast<T *>(p);
     return PSK_SOFT_OK;
 }
 
@@ -277,10 +387,10 @@ struct PlanSummary {
 // kernels of another and the download of a third overlap), and an event for "outputs are in host
 // memory".
 struct StageSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    uint8_t *h_buf = nullptr;  // pinned: [in | soft | phase | bits | sidx]
-    uint8_t *d_buf = nullptr;
+    Stream stream;
+    Event done;
+    PinnedBuf<uint8_t> h_buf;  // [in | soft | phase | bits | sidx]
+    DeviceBuf<uint8_t> d_buf;
     size_t in_cap = 0;         // bytes of the input region; the others follow as IN, IN/2, IN, IN/4
     bool busy = false;
     // what the chunk in flight needs for unpacking
@@ -300,49 +410,33 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // own and would otherwise wait for each other --; a buffer taken over from another stream is used behind the event that ends its last call.
 struct StreamScratch {
     hipStream_t stream = nullptr;
-    char *buf = nullptr;
+    DeviceBuf<char> buf;
     size_t cap = 0;  // bytes
-    hipEvent_t ev = nullptr;
-    bool ev_used = false;
+    Event ev;
     uint64_t last_use = 0;
-    void free()
-    {
-        if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
-        if (buf) (void)hipFree(buf);
-    }
 };
 // ... and the descriptors of one strided call (psk_gather.h): written into page-locked memory, uploaded on the caller's stream in
 // front of the gather, reused behind the event that ends the call
 struct GatherDescSlot {
-    char *h_buf = nullptr, *d_buf = nullptr;
+    PinnedBuf<char> h_buf;
+    DeviceBuf<char> d_buf;
     size_t cap = 0;  // bytes
-    hipEvent_t ev = nullptr;
-    bool used = false;
+    Event ev;
     // the slot for a call with `bytes` of descriptors: behind the event of its last call, grown on demand
     psk_soft_status claim(size_t bytes)
     {
-        if (!ev)
-            PSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        if (used)
-            PSK_HIP(hipEventSynchronize(ev));
-        used = false;
+        PSK_HIP(ev.ensure());
+        PSK_HIP(ev.sync());
+        ev.clear();
         if (bytes <= cap)
             return PSK_SOFT_OK;
-        if (h_buf) (void)hipHostFree(h_buf);
-        if (d_buf) (void)hipFree(d_buf);
-        h_buf = d_buf = nullptr;
+        h_buf.release(), d_buf.release();
         cap = 0;
         const size_t grown = align_up(bytes + bytes / 4, 4096);
-        PSK_HIP(hipHostMalloc((void **)&h_buf, grown));
-        PSK_HIP(hipMalloc((void **)&d_buf, grown));
+        PSK_HIP(h_buf.alloc(grown));
+        PSK_HIP(d_buf.alloc(grown));
         cap = grown;
         return PSK_SOFT_OK;
-    }
-    void free()
-    {
-        if (ev) (void)hipEventSynchronize(ev), (void)hipEventDestroy(ev);
-        if (h_buf) (void)hipHostFree(h_buf);
-        if (d_buf) (void)hipFree(d_buf);
     }
 };
 // The history of every channel in front of a pre-pass that needs one (the resampler's, the filter's): two slots a channel in
@@ -352,16 +446,15 @@ struct GatherDescSlot {
 struct HistoryBank {
     const char *name;                                  // in messages
     uint32_t slot_floats, chan_floats, live_floats;    // a slot, a channel's two slots with their padding, what of a slot is history
-    float *d = nullptr;
+    DeviceBuf<float> d;
     std::vector<uint8_t> cur;  // the current slot of each channel
-    hipEvent_t ev = nullptr;
-    bool ev_used = false;
+    Event ev;
 
     psk_soft_status ensure(uint32_t nch)
     {
         if (d)
             return PSK_SOFT_OK;
-        PSK_TRY(alloc_zeroed(&d, sizeof(float) * chan_floats * nch, name));
+        PSK_TRY(alloc_zeroed(d, (size_t)chan_floats * nch, name));
         cur.assign(nch, 0);
         return PSK_SOFT_OK;
     }
@@ -371,17 +464,13 @@ struct HistoryBank {
     void flip(uint32_t ch) { cur[ch] ^= 1u; }
     psk_soft_status record(hipStream_t stream)
     {
-        if (!ev)
-            PSK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        PSK_HIP(hipEventRecord(ev, stream));
-        ev_used = true;
+        PSK_HIP(ev.record(stream));
         return PSK_SOFT_OK;
     }
     // no launch is still reading or writing a slot
     psk_soft_status wait()
     {
-        if (ev_used)
-            PSK_HIP(hipEventSynchronize(ev));
+        PSK_HIP(ev.sync());
         return PSK_SOFT_OK;
     }
     // the current slot of a channel, live_floats floats: zeros while nothing is allocated
@@ -403,11 +492,6 @@ struct HistoryBank {
             return st;
         PSK_HIP(hipMemcpy(slot(ch, cur[ch]), from, sizeof(float) * live_floats, hipMemcpyHostToDevice));
         return PSK_SOFT_OK;
-    }
-    void free()
-    {
-        if (d) (void)hipFree(d);
-        if (ev) (void)hipEventDestroy(ev);
     }
 };
 
@@ -452,12 +536,12 @@ struct PieceCount {
 template <class Desc, class Partial, int N>
 struct PassRing {
     struct Slot {
-        Desc *h_desc = nullptr, *d_desc = nullptr;
+        PinnedBuf<Desc> h_desc;
+        DeviceBuf<Desc> d_desc;
         size_t desc_cap = 0;  // descriptors
-        Partial *d_part = nullptr;
+        DeviceBuf<Partial> d_part;
         size_t part_cap = 0;  // partials
-        hipEvent_t ev = nullptr;
-        bool used = false;
+        Event ev;  // behind the slot's last pass
         hipStream_t stream = nullptr;
         PassCover cover = {0, 0};
     } slot[N];
@@ -474,19 +558,15 @@ struct PassRing {
     // created on first use.
     static psk_soft_status claim(Slot &q, size_t n_desc, size_t headroom = 0)
     {
-        if (q.used)
-            PSK_HIP(hipEventSynchronize(q.ev));
-        q.used = false;  // (the event has completed: nothing waits for it again, and upload sets `used` for the next pass)
-        if (!q.ev)
-            PSK_HIP(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+        PSK_HIP(q.ev.sync());
+        q.ev.clear();  // (the event has completed: nothing waits for it again until finish records it for the next pass)
+        PSK_HIP(q.ev.ensure());
         if (n_desc <= q.desc_cap)
             return PSK_SOFT_OK;
-        if (q.h_desc) (void)hipHostFree(q.h_desc);
-        if (q.d_desc) (void)hipFree(q.d_desc);
-        q.h_desc = q.d_desc = nullptr;
+        q.h_desc.release(), q.d_desc.release();
         q.desc_cap = 0;
-        PSK_HIP(hipHostMalloc((void **)&q.h_desc, sizeof(Desc) * (n_desc + headroom)));
-        PSK_HIP(hipMalloc((void **)&q.d_desc, sizeof(Desc) * (n_desc + headroom)));
+        PSK_HIP(q.h_desc.alloc(n_desc + headroom));
+        PSK_HIP(q.d_desc.alloc(n_desc + headroom));
         q.desc_cap = n_desc + headroom;
         return PSK_SOFT_OK;
     }
@@ -495,11 +575,9 @@ struct PassRing {
     {
         if (n <= q.part_cap)
             return PSK_SOFT_OK;
-        if (q.d_part) (void)hipFree(q.d_part);
-        q.d_part = nullptr;
         q.part_cap = 0;
         const size_t cap = with_headroom((size_t)n);
-        PSK_HIP(hipMalloc((void **)&q.d_part, sizeof(Partial) * cap));
+        PSK_HIP(q.d_part.alloc(cap));
         q.part_cap = cap;
         return PSK_SOFT_OK;
     }
@@ -508,10 +586,10 @@ struct PassRing {
     psk_soft_status upload(Slot &q, uint32_t n_desc, PassCover cover, hipStream_t stream)
     {
         for (const Slot &k : slot)
-            if (&k != &q && k.used && k.stream != stream && k.cover.first < cover.first + cover.n && cover.first < k.cover.first + k.cover.n)
-                PSK_HIP(hipStreamWaitEvent(stream, k.ev, 0));
+            if (&k != &q && k.stream != stream && k.cover.first < cover.first + cover.n && cover.first < k.cover.first + k.cover.n)
+                PSK_HIP(k.ev.wait(stream));  // (a slot whose pass has been waited for, or that never had one: nothing)
         PSK_HIP(hipMemcpyAsync(q.d_desc, q.h_desc, sizeof(Desc) * (size_t)n_desc, hipMemcpyHostToDevice, stream));
-        q.used = true, q.stream = stream, q.cover = cover;
+        q.stream = stream, q.cover = cover;
         return PSK_SOFT_OK;
     }
     // The slot is free again behind whatever the pass has put on the stream.  Returns `st`, the pass's status so far (its error text
@@ -519,9 +597,8 @@ struct PassRing {
     static psk_soft_status finish(Slot &q, hipStream_t stream, psk_soft_status st)
     {
         const std::string keep = g_last_error;
-        if (const hipError_t e = hipEventRecord(q.ev, stream)) {
+        if (const hipError_t e = q.ev.record(stream)) {  // (the slot stays as claim left it: nothing waits for its event)
             (void)hipStreamSynchronize(stream);
-            q.used = false;
             if (st == PSK_SOFT_OK)
                 return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
         }
@@ -540,19 +617,8 @@ struct PassRing {
     // every pass enqueued so far has ended
     psk_soft_status wait()
     {
-        for (Slot &q : slot)
-            if (q.used)
-                PSK_HIP(hipEventSynchronize(q.ev));
+        for (Slot &q : slot) PSK_HIP(q.ev.sync());
         return PSK_SOFT_OK;
-    }
-    void free()
-    {
-        for (Slot &q : slot) {
-            if (q.ev) (void)hipEventSynchronize(q.ev), (void)hipEventDestroy(q.ev);
-            if (q.h_desc) (void)hipHostFree(q.h_desc);
-            if (q.d_desc) (void)hipFree(q.d_desc);
-            if (q.d_part) (void)hipFree(q.d_part);
-        }
     }
 };
 
@@ -560,7 +626,7 @@ struct PassRing {
 // the joins; a control-plane-only handle keeps them on the host.
 template <class Rec>
 struct Records {
-    Rec *d = nullptr;
+    DeviceBuf<Rec> d;
     size_t cap = 0;  // records of d
     std::vector<Rec> dry;
 
@@ -572,7 +638,7 @@ struct Records {
             dry.assign(n, Rec{});
         if (on_host || d)
             return PSK_SOFT_OK;
-        PSK_TRY(alloc_zeroed(&d, sizeof(Rec) * n, what));
+        PSK_TRY(alloc_zeroed(d, n, what));
         cap = n;
         return PSK_SOFT_OK;
     }
@@ -583,16 +649,10 @@ struct Records {
         if (n <= cap)
             return PSK_SOFT_OK;
         PSK_TRY(ring.wait());
-        if (d) (void)hipFree(d);
-        d = nullptr;
         cap = 0;
-        PSK_HIP(hipMalloc((void **)&d, sizeof(Rec) * with_headroom(n)));
+        PSK_HIP(d.alloc(with_headroom(n)));
         cap = with_headroom(n);
         return PSK_SOFT_OK;
-    }
-    void free()
-    {
-        if (d) (void)hipFree(d);
     }
 };
 
@@ -668,24 +728,29 @@ struct psk_soft_handle {
     uint32_t mixed_lo = 0, mixed_hi = 0;  // a range that was compared and found mixed ...
     int mixed_ttl = 0;                    // ... is not compared again for this many calls (or until something is configured)
     int opt_stamp = 1;                    // PSK_SOFT_STAMP=0 (environment): every channel planned on its own (A/B runs, tests)
+    // Every resource below is an owning member (DeviceBuf, PinnedBuf, Event, Stream: see "ownership" above) and goes with the handle.
+    // psk_soft_destroy waits for every stream the handle owns before it deletes the handle, so nothing is in flight when the first
+    // member goes and the order in which the members are destroyed does not matter.
     // device memory
-    psk::ChanState *d_state = nullptr;
-    float2 *d_ring = nullptr;
-    float *d_yv = nullptr;
+    DeviceBuf<psk::ChanState> d_state;
+    DeviceBuf<float2> d_ring;
+    DeviceBuf<float> d_yv;
+    // the plan slots: a pinned block and its copy in device memory; the plans lie kPlanHeaderBytes into each (psk_plan.h)
+    PinnedBuf<char> h_plan_blk[kPlanSlots];
+    DeviceBuf<char> d_plan_blk[kPlanSlots];
     psk::ChanPlan *h_plans[kPlanSlots] = {};
     psk::ChanPlan *d_plans[kPlanSlots] = {};
-    hipEvent_t ev[kPlanSlots] = {};
+    Event ev[kPlanSlots];
     // the plans of a call are uploaded on a stream of their own, so that the copy runs under the kernels of the call before
     // instead of behind them (20 us of a 4096-channel call); the caller's stream waits for ev_up of the slot
-    hipStream_t up_stream = nullptr;
-    hipEvent_t ev_up[kPlanSlots] = {};
+    Stream up_stream;
+    Event ev_up[kPlanSlots];
     int opt_up_stream = 1;  // PSK_SOFT_PLAN_STREAM=0 (environment): upload on the caller's stream (A/B runs)
-    bool ev_used[kPlanSlots] = {};
     int slot = 0;
     bool opt_qpsk_sign_map = false;  // PSK_SOFT_OPT_QPSK_SIGN_BITMAP
-    hipStream_t stream = nullptr;
-    hipStream_t aux[kAuxStreams] = {};     // created on first use
-    hipEvent_t aux_fork = nullptr, aux_join[kAuxStreams] = {};
+    Stream stream;
+    Stream aux[kAuxStreams];     // created on first use
+    Event aux_fork, aux_join[kAuxStreams];
     int opt_fork = 1;                       // PSK_SOFT_OPT_CONCURRENT_CLASSES
     // PSK_SOFT_OPT_DEFERRED_JOIN: the side streams of a batch that mixes window classes are NOT joined into the caller's stream at
     // the end of the call -- every class ends its calls on its own stream (exact tier and reference-order hand-over included) and
@@ -698,20 +763,30 @@ struct psk_soft_handle {
     uint64_t deferred_sig = 0;
     uint32_t deferred_ch0 = 0, deferred_nch = 0;
     hipStream_t deferred_stream = nullptr;
-    hipEvent_t slot_aux_ev[kPlanSlots][kAuxStreams] = {};  // end of a deferred call on each side stream (a plan slot is reused after them too)
-    bool slot_aux_used[kPlanSlots][kAuxStreams] = {};
+    Event slot_aux_ev[kPlanSlots][kAuxStreams];  // end of a deferred call on each side stream (a plan slot is reused after them too)
     // what the call that last used each plan slot worked on, and on which stream (its end is the slot's event)
     hipStream_t slot_stream[kPlanSlots] = {};
     uint32_t slot_ch0[kPlanSlots] = {}, slot_nch[kPlanSlots] = {};
     // time-tiled kernels (psk_tile_kernel.h): scratch of one call -- per-tile reports, and per symbol the raw phase, the
     // picked sample and the phase estimate -- grown on demand; calls that use it on different streams are ordered by tile_ev
     int opt_tiled = 1;  // PSK_SOFT_OPT_TIME_TILED
-    psk::TileInfo *d_tiles = nullptr;
-    float *d_traw = nullptr, *d_test = nullptr;
-    float2 *d_ts = nullptr;
+    DeviceBuf<psk::TileInfo> d_tiles;
+    DeviceBuf<float> d_traw, d_test;
+    DeviceBuf<float2> d_ts;
     size_t tile_cap = 0, tile_sym_cap = 0;
     size_t pf_cap = 0, pf_sym_cap = 0;  // ... of the parallel fit's arrays (the classes that use it come first in the scratch)
     psk::PfScratch pf{};   // ... and of the parallel fit (psk_pfit.h), same capacities; PfChan: one per channel of the handle
+    struct PfMem {         // what pf points at: the owner of its arrays and of its pinned note; scratch_tiles takes pf from view()
+        DeviceBuf<int> k;
+        DeviceBuf<float> y, tt;
+        DeviceBuf<double> S, c, xs;
+        DeviceBuf<psk::PfTile> tile;
+        DeviceBuf<psk::PfBlock> blk;
+        DeviceBuf<psk::PfWalk> walk;
+        DeviceBuf<psk::PfChan> chan;
+        PinnedBuf<uint32_t> hint;
+        psk::PfScratch view() const { return psk::PfScratch{k, y, S, c, tt, xs, tile, blk, walk, chan, hint}; }
+    } pf_mem;
     int opt_pfit = 1;      // PSK_SOFT_PARALLEL_FIT (environment): 0 = time-tiled calls keep the block-by-block fit (A/B runs),
                            // 2 = the second round of the parallel fit is always enqueued (tests), 1 = for a while after
                            // a call reported a first guess that failed (pf.hint, a word the kernels write into page-locked memory)
@@ -721,26 +796,25 @@ struct psk_soft_handle {
     int opt_validate = 0;                   // PSK_SOFT_VALIDATE=1 (environment, tests): see `validate` in process_round
     int opt_split = 2;                      // PSK_SOFT_SPLIT_CLASSES=n (environment): pieces a mixed batch's calls are cut into (0 / 1: never)
     int opt_pipe = 1;                       // PSK_SOFT_PIPELINED=0 (environment): never the pipelined mode (A/B runs)
-    hipStream_t pipe_st[2] = {};            // its fit and back streams (the front stage stays on the class's stream)
-    hipEvent_t pipe_ev[kPipeEvents] = {};
-    void *d_pipe_carry = nullptr;           // per channel of a pipelined launch: the fit state between two ranges (PipeCarry)
-    float *d_pipe_y = nullptr;              // ... and its ring of unwrapped phases
+    Stream pipe_st[2];                      // its fit and back streams (the front stage stays on the class's stream)
+    Event pipe_ev[kPipeEvents];
+    DeviceBuf<char> d_pipe_carry;           // per channel of a pipelined launch: the fit state between two ranges (PipeCarry)
+    DeviceBuf<float> d_pipe_y;              // ... and its ring of unwrapped phases
     size_t pipe_cap = 0;
     // wide symbols (samplesPerBaud > kSeqMaxS): the chunk records of the front stage (psk_wide.hip) and the rows of symbolEnergy[] of the
     // reference-order kernel's wide build, grown on demand like the scratch above and ordered by the same event
-    void *d_wide_rec = nullptr, *d_wide_stat = nullptr;
+    DeviceBuf<char> d_wide_rec, d_wide_stat;
     size_t wide_rec_cap = 0, wide_stat_cap = 0;  // bytes
-    double *d_wide_symE = nullptr;
+    DeviceBuf<double> d_wide_symE;
     size_t wide_symE_cap = 0;  // doubles
-    hipEvent_t tile_ev = nullptr;
+    Event tile_ev;
     hipStream_t tile_stream = nullptr;  // stream of the last call that used the scratch
-    bool tile_ev_used = false;
     // PSK_SOFT_OPT_FAR_FIT: phaseAvg above kFastFitMax on the fast path (psk_farfit.hip).  The rings of that fit stage are rows of
     // d_far_y, one per channel that has ever emitted as a far channel (far_row[channel] = row + 1, 0: none yet) -- by channel, not by
     // position in the call: calls on disjoint channel ranges run side by side on different streams.  Grown on demand, never shrunk;
     // a row holds nothing between calls (the prologue of every call copies the carried values in).
     int opt_far_fit = 0;
-    float *d_far_y = nullptr;
+    DeviceBuf<float> d_far_y;
     uint32_t far_rows_cap = 0, far_rows_used = 0;
     std::vector<uint32_t> far_row;
     bool poisoned = false;  // a HIP call failed after kernels of a call were enqueued: host mirror and device state may disagree
@@ -752,12 +826,12 @@ struct psk_soft_handle {
     GatherDescSlot gdesc[kGatherDescSlots];
     uint64_t gat_calls = 0;
     int gdesc_turn = 0;
-    float *d_tune_tab = nullptr;  // tuned packets: the two phasor tables (psk_tune.h), uploaded when the first tuned packet comes
+    DeviceBuf<float> d_tune_tab;  // tuned packets: the two phasor tables (psk_tune.h), uploaded when the first tuned packet comes
     // resampled packets: the history of every channel, two slots of three float2 in 64 bytes
     HistoryBank rs_hist{"resample history", psk::kResampleHistSlotFloats, psk::kResampleHistFloats, psk::kResampleHistSlotFloats};
     // filtered packets: the taps of every slot (kFirSlots x kFirMaxTaps floats, allocated at the first psk_soft_fir_define) and
     // their counts (0: never defined); the history of every channel, two slots of 127 float2 in 1 KiB each
-    float *d_fir_taps = nullptr;
+    DeviceBuf<float> d_fir_taps;
     uint32_t fir_ntaps[psk::kFirSlots] = {};
     HistoryBank fir_hist{"filter history", psk::kFirHistSlotFloats, 2u * psk::kFirHistSlotFloats, 2u * psk::kFirHist};
     int opt_diag_gather_only = 0;  // PSK_SOFT_DIAG_GATHER_ONLY=1 (environment, timing experiments only -- tools/strided_rates.py): a
@@ -782,7 +856,7 @@ struct psk_soft_handle {
     // psk_soft_sync_device: the words of every slot (kSyncSlots x kSyncMaxWord float2, allocated at the first psk_soft_sync_define),
     // their lengths (0: never defined) and energies Ew; one record per channel, allocated (zeros) at the first call -- a
     // control-plane-only handle keeps them on the host --; the history of every channel, two slots of 127 float2 in 1 KiB each
-    float *d_sync_words = nullptr;
+    DeviceBuf<float> d_sync_words;
     uint32_t sync_len[psk::kSyncSlots] = {};
     float sync_ew[psk::kSyncSlots] = {};
     Records<psk_soft_sync_t> sync;
@@ -794,7 +868,7 @@ struct psk_soft_handle {
     // psk_soft_demap_device: the maps of every slot (kDemapSlots DemapMap, allocated at the first psk_soft_demap_define; M 0: never
     // defined); one record per segment of the last call, grown on demand -- a control-plane-only handle keeps them on the host --;
     // the passes' descriptors grow on demand too, and every pass covers all the records (kAllRecords)
-    psk::DemapMap *d_demap_maps = nullptr;
+    DeviceBuf<psk::DemapMap> d_demap_maps;
     uint32_t demap_M[psk::kDemapSlots] = {};
     Records<psk_soft_demap_t> demap;
     bool demap_called = false;
@@ -802,7 +876,7 @@ struct psk_soft_handle {
     PassRing<psk::DemapDesc, psk::DemapPartial, 2> dpass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
-    CopyPool *pool = nullptr;
+    std::unique_ptr<CopyPool> pool;
     size_t stage_bytes = 32u << 20;  // input bytes per chunk (PSK_SOFT_STAGE_MB)
 };
 
@@ -859,9 +933,9 @@ hipError_t deferred_join(psk_soft_handle *h, hipStream_t stream)
     for (int a = 0; a < kAuxStreams; a++) {
         if (!h->aux[a])
             continue;
-        if (const hipError_t e = hipEventRecord(h->aux_join[a], h->aux[a]))
+        if (const hipError_t e = h->aux_join[a].record(h->aux[a]))
             return e;
-        if (const hipError_t e = hipStreamWaitEvent(stream, h->aux_join[a], 0))
+        if (const hipError_t e = h->aux_join[a].wait(stream))
             return e;
     }
     h->deferred_pending = false;
@@ -1020,13 +1094,11 @@ psk_soft_status take_slot(Round &r)
         return PSK_SOFT_OK;
     }
     PSK_HIP(hipSetDevice(h->device));
-    if (h->ev_used[r.slot])
-        PSK_HIP(hipEventSynchronize(h->ev[r.slot]));
-    for (int a = 0; a < kAuxStreams; a++)
-        if (h->slot_aux_used[r.slot][a]) {  // (a deferred call's classes end on the side streams)
-            PSK_HIP(hipEventSynchronize(h->slot_aux_ev[r.slot][a]));
-            h->slot_aux_used[r.slot][a] = false;
-        }
+    PSK_HIP(h->ev[r.slot].sync());
+    for (Event &e : h->slot_aux_ev[r.slot]) {  // (a deferred call's classes end on the side streams)
+        PSK_HIP(e.sync());
+        e.clear();
+    }
     r.plans = h->h_plans[r.slot];
     r.handed_over = psk::plan_header(h->d_plans[r.slot]);
     return PSK_SOFT_OK;
@@ -1169,12 +1241,10 @@ psk_soft_status wait_for_overlapping_calls(Round &r)
 {
     psk_soft_handle *const h = r.h;
     for (int k = 0; k < kPlanSlots; k++)
-        if (k != r.slot && h->ev_used[k] && h->slot_stream[k] != r.stream && h->slot_ch0[k] < r.ch0 + r.nch &&
+        if (k != r.slot && h->ev[k].recorded() && h->slot_stream[k] != r.stream && h->slot_ch0[k] < r.ch0 + r.nch &&
             r.ch0 < h->slot_ch0[k] + h->slot_nch[k]) {
-            PSK_HIP(hipStreamWaitEvent(r.stream, h->ev[k], 0));
-            for (int a = 0; a < kAuxStreams; a++)
-                if (h->slot_aux_used[k][a])
-                    PSK_HIP(hipStreamWaitEvent(r.stream, h->slot_aux_ev[k][a], 0));
+            PSK_HIP(h->ev[k].wait(r.stream));
+            for (const Event &e : h->slot_aux_ev[k]) PSK_HIP(e.wait(r.stream));
         }
     return PSK_SOFT_OK;
 }
@@ -1340,11 +1410,11 @@ void place_all(Round &r)
 }
 
 struct ScratchBuf {  // one buffer of a scratch that grows on demand, and the bytes it is to have
-    void **buf;
+    OwnedBytes<DeviceMem> *buf;
     size_t bytes;
 };
 template <class T>
-inline ScratchBuf scratch_buf(T **p, size_t n) { return ScratchBuf{reinterpret_cast<void **>(p), sizeof(T) * n}; }
+inline ScratchBuf scratch_buf(DeviceBuf<T> &b, size_t n) { return ScratchBuf{&b, sizeof(T) * n}; }
 inline size_t plus_quarter(size_t need) { return need + need / 4; }  // (a scratch grows to the largest call seen, plus a quarter)
 // A scratch is too small for the call (rare): the device is waited for -- no call is in flight on a buffer that moves --, the buffers
 // are freed and allocated anew.  *got = false: out of device memory, none of them is held; what the call does then is the caller's business.
@@ -1352,12 +1422,12 @@ hipError_t grow_scratch(std::initializer_list<ScratchBuf> bufs, bool *got)
 {
     if (const hipError_t e = hipDeviceSynchronize())
         return e;
-    for (const ScratchBuf &b : bufs) (void)hipFree(*b.buf), *b.buf = nullptr;
+    for (const ScratchBuf &b : bufs) b.buf->release();
     *got = true;
-    for (const ScratchBuf &b : bufs) *got = *got && hipMalloc(b.buf, b.bytes) == hipSuccess;
+    for (const ScratchBuf &b : bufs) *got = *got && b.buf->alloc_bytes(b.bytes) == hipSuccess;
     if (!*got) {
         (void)hipGetLastError();
-        for (const ScratchBuf &b : bufs) (void)hipFree(*b.buf), *b.buf = nullptr;
+        for (const ScratchBuf &b : bufs) b.buf->release();
     }
     return hipSuccess;
 }
@@ -1373,23 +1443,20 @@ psk_soft_status claim_scratch(StreamScratch (&ring)[N], uint64_t *calls, hipStre
         own = !own && c.buf && c.stream == stream ? &c : own;
     }
     *out = sc = own ? own : sc;
-    if (!sc->ev)
-        PSK_HIP(hipEventCreateWithFlags(&sc->ev, hipEventDisableTiming));
-    if (sc->ev_used && sc->stream != stream)
-        PSK_HIP(hipStreamWaitEvent(stream, sc->ev, 0));
+    PSK_HIP(sc->ev.ensure());
+    if (sc->stream != stream)
+        PSK_HIP(sc->ev.wait(stream));
     if (need > sc->cap) {
         sc->cap = 0;
         const size_t cap = align_up(plus_quarter(need), 4096);
         if (oom) {
             bool got = false;
-            PSK_HIP(grow_scratch({ScratchBuf{(void **)&sc->buf, cap}}, &got));
+            PSK_HIP(grow_scratch({scratch_buf(sc->buf, cap)}, &got));
             if (!got)
                 return fail(PSK_SOFT_ERR_HIP, oom);
         } else {
             PSK_HIP(hipDeviceSynchronize());
-            if (sc->buf) (void)hipFree(sc->buf);
-            sc->buf = nullptr;
-            PSK_HIP(hipMalloc((void **)&sc->buf, cap));
+            PSK_HIP(sc->buf.alloc(cap));
         }
         sc->cap = cap;
     }
@@ -1412,19 +1479,20 @@ psk_soft_status scratch_tiles(Round &r)
     h->tile_cap = h->tile_sym_cap = h->pf_cap = h->pf_sym_cap = 0;
     const size_t syms = plus_quarter(r.tile_syms), cnt = plus_quarter(r.tile_count);
     const size_t psyms = plus_quarter(r.pf_syms) + 128u, pcnt = plus_quarter(r.pf_count) + 1u;
-    psk::PfScratch &pf = h->pf;
+    psk_soft_handle::PfMem &pf = h->pf_mem;
     bool got = false;
-    PSK_HIP(grow_scratch({scratch_buf(&h->d_tiles, cnt), scratch_buf(&h->d_traw, syms), scratch_buf(&h->d_test, syms), scratch_buf(&h->d_ts, syms),
-                          scratch_buf(&pf.k, psyms), scratch_buf(&pf.y, psyms), scratch_buf(&pf.S, psyms), scratch_buf(&pf.c, psyms),
-                          scratch_buf(&pf.tt, psyms), scratch_buf(&pf.xs, psyms), scratch_buf(&pf.tile, pcnt),
-                          scratch_buf(&pf.blk, psyms / 128u + 1u), scratch_buf(&pf.walk, psyms / 128u + 1u)},
+    PSK_HIP(grow_scratch({scratch_buf(h->d_tiles, cnt), scratch_buf(h->d_traw, syms), scratch_buf(h->d_test, syms), scratch_buf(h->d_ts, syms),
+                          scratch_buf(pf.k, psyms), scratch_buf(pf.y, psyms), scratch_buf(pf.S, psyms), scratch_buf(pf.c, psyms),
+                          scratch_buf(pf.tt, psyms), scratch_buf(pf.xs, psyms), scratch_buf(pf.tile, pcnt),
+                          scratch_buf(pf.blk, psyms / 128u + 1u), scratch_buf(pf.walk, psyms / 128u + 1u)},
                          &got));
     if (got && !pf.chan) {
-        got = hipMalloc((void **)&pf.chan, sizeof(psk::PfChan) * h->nch) == hipSuccess &&
-              hipMemset(pf.chan, 0, sizeof(psk::PfChan) * h->nch) == hipSuccess && hipHostMalloc((void **)&pf.hint, 64) == hipSuccess;
+        got = pf.chan.alloc(h->nch) == hipSuccess && hipMemset(pf.chan, 0, sizeof(psk::PfChan) * h->nch) == hipSuccess &&
+              pf.hint.alloc(16) == hipSuccess;  // (64 bytes)
         if (got)
             *pf.hint = 0u;
     }
+    h->pf = pf.view();  // (whatever moved or went: the kernels' struct follows its owner)
     if (got) {
         h->tile_cap = cnt, h->tile_sym_cap = syms, h->pf_cap = pcnt, h->pf_sym_cap = psyms;
         return PSK_SOFT_OK;
@@ -1455,7 +1523,7 @@ psk_soft_status scratch_wide(Round &r)
     h->wide_rec_cap = h->wide_stat_cap = 0;
     const size_t rb = plus_quarter(r.wide_rec_need), sb = plus_quarter(r.wide_stat_need);
     bool got = false;
-    PSK_HIP(grow_scratch({ScratchBuf{&h->d_wide_rec, rb}, ScratchBuf{&h->d_wide_stat, sb}}, &got));
+    PSK_HIP(grow_scratch({scratch_buf(h->d_wide_rec, rb), scratch_buf(h->d_wide_stat, sb)}, &got));
     if (got) {
         h->wide_rec_cap = rb, h->wide_stat_cap = sb;
         return PSK_SOFT_OK;
@@ -1487,7 +1555,7 @@ psk_soft_status scratch_far_rows(Round &r)
         // (the one place of this path that waits for the device: a row carries nothing from one call to the next)
         h->far_rows_cap = 0;
         const uint32_t cap = plus_quarter(used) < h->nch ? (uint32_t)plus_quarter(used) : h->nch;
-        PSK_HIP(grow_scratch({ScratchBuf{(void **)&h->d_far_y, psk::far_ring_bytes() * cap}}, &got));
+        PSK_HIP(grow_scratch({ScratchBuf{&h->d_far_y, psk::far_ring_bytes() * cap}}, &got));
         if (got)
             h->far_rows_cap = cap;
     }
@@ -1525,7 +1593,7 @@ psk_soft_status scratch_wide_seq(Round &r)
         return PSK_SOFT_OK;
     h->wide_symE_cap = 0;
     bool got = false;
-    PSK_HIP(grow_scratch({scratch_buf(&h->d_wide_symE, plus_quarter(need))}, &got));
+    PSK_HIP(grow_scratch({scratch_buf(h->d_wide_symE, plus_quarter(need))}, &got));
     if (!got)  // (nothing else carries a wide symbol)
         return fail(PSK_SOFT_ERR_HIP, "psk_soft_process: out of device memory for the symbolEnergy rows of wide symbols");
     h->wide_symE_cap = plus_quarter(need);
@@ -1538,8 +1606,7 @@ psk_soft_status scratch_order(Round &r)
     psk_soft_handle *const h = r.h;
     if (!r.tile_syms && !r.n_wide_seq)
         return PSK_SOFT_OK;
-    if (!h->tile_ev)
-        PSK_HIP(hipEventCreateWithFlags(&h->tile_ev, hipEventDisableTiming));
+    PSK_HIP(h->tile_ev.ensure());
     if (r.tile_syms) {
         // second round of the parallel fit: for the next 16 tiled calls after one whose first guess of the unwrap counts
         // failed somewhere (the kernels leave a note in page-locked memory; a late or lost note costs a call or two)
@@ -1551,8 +1618,8 @@ psk_soft_status scratch_order(Round &r)
         }
         r.pf_second = h->opt_pfit == 2 || h->pf_second_ttl > 0;
     }
-    if (h->tile_ev_used && h->tile_stream != r.stream)
-        PSK_HIP(hipStreamWaitEvent(r.stream, h->tile_ev, 0));
+    if (h->tile_stream != r.stream)
+        PSK_HIP(h->tile_ev.wait(r.stream));
     if (!r.tile_syms || !r.pipe_need)
         return PSK_SOFT_OK;
     // the pipelined mode's own scratch (one PipeCarry and one ring of kPipeMaxYLen floats per channel of a launch) and its
@@ -1561,7 +1628,7 @@ psk_soft_status scratch_order(Round &r)
         h->pipe_cap = 0;
         const size_t cap = plus_quarter(r.pipe_need);
         bool got = false;
-        PSK_HIP(grow_scratch({ScratchBuf{&h->d_pipe_carry, psk::pipe_carry_bytes() * cap}, scratch_buf(&h->d_pipe_y, kPipeMaxYLen * cap)}, &got));
+        PSK_HIP(grow_scratch({scratch_buf(h->d_pipe_carry, psk::pipe_carry_bytes() * cap), scratch_buf(h->d_pipe_y, kPipeMaxYLen * cap)}, &got));
         if (got)
             h->pipe_cap = cap;
         else  // (out of device memory: the one-launch kernels do without)
@@ -1573,8 +1640,8 @@ psk_soft_status scratch_order(Round &r)
         PSK_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
         // (CU-masked streams for the stages -- the serial ones on every n-th CU, the front stage on the others -- were measured:
         // no gain, 2.77 ... 2.84 against 2.75 ms at 512 channels)
-        for (hipStream_t &q : h->pipe_st) PSK_HIP(hipStreamCreateWithPriority(&q, hipStreamNonBlocking, prio_hi));
-        for (hipEvent_t &e : h->pipe_ev) PSK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (Stream &q : h->pipe_st) PSK_HIP(q.create(prio_hi));
+        for (Event &e : h->pipe_ev) PSK_HIP(e.ensure());
     }
     return PSK_SOFT_OK;
 }
@@ -1764,8 +1831,8 @@ psk_soft_status upload(Round &r)
     if (h->opt_up_stream) {
         // (the slot's previous user has finished -- waited for in take_slot --, nothing else reads or writes d_plans[slot])
         PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[r.slot]), hdr, up_bytes, hipMemcpyHostToDevice, h->up_stream));
-        PSK_HIP(hipEventRecord(h->ev_up[r.slot], h->up_stream));
-        PSK_HIP(hipStreamWaitEvent(r.stream, h->ev_up[r.slot], 0));
+        PSK_HIP(h->ev_up[r.slot].record(h->up_stream));
+        PSK_HIP(h->ev_up[r.slot].wait(r.stream));
     } else {
         PSK_HIP(hipMemcpyAsync(psk::plan_header(h->d_plans[r.slot]), hdr, up_bytes, hipMemcpyHostToDevice, r.stream));
     }
@@ -1902,29 +1969,29 @@ psk_soft_status enqueue_piped(const Round &r, const LaunchSet &s, int S, int H, 
     float *const carry_y = h->d_pipe_y + (size_t)kPipeMaxYLen * s.off;
     const uint32_t y_pipe = ring_floats(s.max_n, 512u);
     int e = 0;
-    PSK_HIP(hipEventRecord(h->pipe_ev[e], st));  // (the side streams start behind everything this one carries)
-    PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
-    PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
+    PSK_HIP(h->pipe_ev[e].record(st));  // (the side streams start behind everything this one carries)
+    PSK_HIP(h->pipe_ev[e].wait(h->pipe_st[0]));
+    PSK_HIP(h->pipe_ev[e].wait(h->pipe_st[1]));
     e++;
     for (uint32_t t0 = 0; t0 < T; t0 += tr) {
         const uint32_t nt = T - t0 < tr ? T - t0 : tr;
         PSK_HIP(mark(r, st, "pipe_front", S, H, s.off, cnt, nt, y_len, r_len));
         PSK_HIP(psk::launch_tile_front(S, class_H(H), r.d_plans, l, r.ch0, cnt, nt, h->d_state, h->d_ring, h->lim.ring_cap, r_len, h->d_tiles,
                                        h->d_traw, h->d_ts, h->pf.chan, t0, st));
-        PSK_HIP(hipEventRecord(h->pipe_ev[e], st));
-        PSK_HIP(hipStreamWaitEvent(h->pipe_st[0], h->pipe_ev[e], 0));
+        PSK_HIP(h->pipe_ev[e].record(st));
+        PSK_HIP(h->pipe_ev[e].wait(h->pipe_st[0]));
         e++;
         PSK_HIP(mark(r, h->pipe_st[0], "pipe_fit", S, H, s.off, cnt, nt, y_pipe, 0));
         PSK_HIP(psk::launch_tile_fit_range(r.d_plans, l, r.ch0, cnt, h->d_state, h->d_ring, h->lim.ring_cap, h->d_yv, h->lim.fit_cap, y_pipe,
                                            h->d_tiles, h->d_traw, h->d_ts, h->d_test, carry, carry_y, t0, nt, h->pipe_st[0]));
-        PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[0]));
-        PSK_HIP(hipStreamWaitEvent(h->pipe_st[1], h->pipe_ev[e], 0));
+        PSK_HIP(h->pipe_ev[e].record(h->pipe_st[0]));
+        PSK_HIP(h->pipe_ev[e].wait(h->pipe_st[1]));
         e++;
         PSK_HIP(mark(r, h->pipe_st[1], "pipe_back", S, H, s.off, cnt, nt, y_pipe, 0));
         PSK_HIP(psk::launch_tile_back(r.d_plans, l, r.ch0, cnt, nt, h->d_state, h->d_tiles, h->d_ts, h->d_test, t0, 1u, h->pipe_st[1]));
     }
-    PSK_HIP(hipEventRecord(h->pipe_ev[e], h->pipe_st[1]));  // (behind the last fit too: the last back waited for it)
-    PSK_HIP(hipStreamWaitEvent(st, h->pipe_ev[e], 0));
+    PSK_HIP(h->pipe_ev[e].record(h->pipe_st[1]));  // (behind the last fit too: the last back waited for it)
+    PSK_HIP(h->pipe_ev[e].wait(st));
     return PSK_SOFT_OK;
 }
 // One window class (samplesPerBaud, history depth) on its stream: the time-tiled kernels first where it has its tiles; then screened
@@ -1967,18 +2034,13 @@ psk_soft_status enqueue_join_and_tail(Round &r, int used_aux)
     psk_soft_handle *const h = r.h;
     const hipStream_t st = r.stream;
     if (r.deferred) {
-        for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
-            if (!h->slot_aux_ev[r.slot][a])
-                PSK_HIP(hipEventCreateWithFlags(&h->slot_aux_ev[r.slot][a], hipEventDisableTiming));
-            PSK_HIP(hipEventRecord(h->slot_aux_ev[r.slot][a], h->aux[a]));
-            h->slot_aux_used[r.slot][a] = true;
-        }
+        for (int a = 0; a < used_aux && a < kAuxStreams; a++) PSK_HIP(h->slot_aux_ev[r.slot][a].record(h->aux[a]));  // (created here)
         h->deferred_pending = true, h->deferred_sig = r.sig, h->deferred_stream = st;
         return PSK_SOFT_OK;
     }
     for (int a = 0; a < used_aux && a < kAuxStreams; a++) {
-        PSK_HIP(hipEventRecord(h->aux_join[a], h->aux[a]));
-        PSK_HIP(hipStreamWaitEvent(st, h->aux_join[a], 0));
+        PSK_HIP(h->aux_join[a].record(h->aux[a]));
+        PSK_HIP(h->aux_join[a].wait(st));
     }
     if (!r.res.any_seq && !r.res.any_emit)  // (any_emit: the exactness guard may hand calls over at run time)
         return PSK_SOFT_OK;
@@ -2030,7 +2092,7 @@ psk_soft_status enqueue(Round &r)
                                 h->lim.fit_cap, stream));
     if (r.fork) {
         if (!h->aux_fork) {  // (the side streams, created at the first call that mixes window classes)
-            PSK_HIP(hipEventCreateWithFlags(&h->aux_fork, hipEventDisableTiming));
+            PSK_HIP(h->aux_fork.ensure());
             // (streams of one priority share a few hardware queues, and two streams that land on the same one run their kernels one
             // after the other: a stream of another priority gets a queue of its own -- DESIGN.md 3.5)
             int prio_lo = 0, prio_hi = 0;
@@ -2039,13 +2101,13 @@ psk_soft_status enqueue(Round &r)
                 const char *pe = getenv("PSK_SOFT_AUX_PRIO");
                 const int mode = pe ? atoi(pe) : 1;
                 if (mode == 0 || prio_lo == prio_hi)
-                    PSK_HIP(hipStreamCreateWithFlags(&h->aux[k], hipStreamNonBlocking));
+                    PSK_HIP(h->aux[k].create());
                 else
-                    PSK_HIP(hipStreamCreateWithPriority(&h->aux[k], hipStreamNonBlocking, mode == 1 ? prio_hi : prio_lo));
-                PSK_HIP(hipEventCreateWithFlags(&h->aux_join[k], hipEventDisableTiming));
+                    PSK_HIP(h->aux[k].create(mode == 1 ? prio_hi : prio_lo));
+                PSK_HIP(h->aux_join[k].ensure());
             }
         }
-        PSK_HIP(hipEventRecord(h->aux_fork, stream));
+        PSK_HIP(h->aux_fork.record(stream));
     }
     int used_aux = 0;
     for (int i = 0; i < r.n_cls; i++) {
@@ -2055,7 +2117,7 @@ psk_soft_status enqueue(Round &r)
             const int a = (i - 1) % kAuxStreams;
             st = h->aux[a];
             if (i - 1 < kAuxStreams) {
-                PSK_HIP(hipStreamWaitEvent(st, h->aux_fork, 0));
+                PSK_HIP(h->aux_fork.wait(st));
                 used_aux = i;
             }
         }
@@ -2063,12 +2125,10 @@ psk_soft_status enqueue(Round &r)
     }
     PSK_TRY(enqueue_join_and_tail(r, used_aux));
     if (r.tile_syms || r.n_wide_seq)
-        PSK_HIP(hipEventRecord(h->tile_ev, stream));
-    if (r.n_cvt) {
-        PSK_HIP(hipEventRecord(r.cv->ev, stream));
-        r.cv->ev_used = true;
-    }
-    PSK_HIP(hipEventRecord(h->ev[r.slot], stream));
+        PSK_HIP(h->tile_ev.record(stream));
+    if (r.n_cvt)
+        PSK_HIP(r.cv->ev.record(stream));
+    PSK_HIP(h->ev[r.slot].record(stream));
     return PSK_SOFT_OK;
 }
 // What a round is of: the whole call (cont == nullptr), or a piece of a call the library has cut (process_device_call) -- cont[i]: bit 0 =
@@ -2138,12 +2198,9 @@ psk_soft_status process_round(psk_soft_handle_t *h, uint32_t ch0, uint32_t nch, 
         return est;
     }
     commit(r);
-    if (r.tile_syms || r.n_wide_seq) {
-        h->tile_ev_used = true;
+    if (r.tile_syms || r.n_wide_seq)
         h->tile_stream = r.stream;
-    }
     h->slot = (h->slot + 1) % kPlanSlots;
-    h->ev_used[r.slot] = true;
     h->slot_stream[r.slot] = r.stream, h->slot_ch0[r.slot] = ch0, h->slot_nch[r.slot] = nch;
     return PSK_SOFT_OK;
 }
@@ -2196,8 +2253,7 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
     h->ctl.resize(n_channels);
     h->ctl_next.resize(n_channels);
     h->last_mode.assign(n_channels, psk::PLAN_SKIP);
-    h->device = device;
-    h->dry = (device == PSK_SOFT_DEVICE_NONE);
+    h->dry = (device == PSK_SOFT_DEVICE_NONE);  // (h->device: set below, once the device has been found usable)
     if (const char *e = std::getenv("PSK_SOFT_TIME_TILED"))
         h->opt_tiled = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
     if (const char *e = std::getenv("PSK_SOFT_FAR_FIT"))  // (as psk_soft_set_option(PSK_SOFT_OPT_FAR_FIT))
@@ -2221,77 +2277,70 @@ psk_soft_status psk_soft_create(int device, uint32_t n_channels, const psk_soft_
         h->opt_stamp = std::atoi(e) != 0;
     if (const char *e = std::getenv("PSK_SOFT_PARALLEL_FIT"))
         h->opt_pfit = std::atoi(e) < 0 ? 0 : std::atoi(e) > 2 ? 2 : std::atoi(e);
+    // the one way out of a create that fails: the handle goes the way every handle goes, whatever it holds by then
+    auto bail = [&](psk_soft_status st, const std::string &msg) {
+        const std::string keep = msg;
+        psk_soft_destroy(h);
+        return fail(st, keep);
+    };
+    auto bail_hip = [&](const char *what, hipError_t e2) {
+        return bail(PSK_SOFT_ERR_HIP, std::string("psk_soft_create: ") + what + ": " + hipGetErrorString(e2));
+    };
     if (!h->dry) {
         int ndev = 0;
         hipError_t e = hipGetDeviceCount(&ndev);
-        if (e != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-            delete h;
-            return fail(PSK_SOFT_ERR_NO_DEVICE,
-                        std::string("psk_soft_create: no usable HIP device (") +
-                            (e != hipSuccess ? hipGetErrorString(e) : "device index out of range") + ")");
-        }
+        if (e != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+            return bail(PSK_SOFT_ERR_NO_DEVICE, std::string("psk_soft_create: no usable HIP device (") +
+                                                    (e != hipSuccess ? hipGetErrorString(e) : "device index out of range") + ")");
         hipDeviceProp_t prop;
-        if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) {
-            delete h;
-            return fail(PSK_SOFT_ERR_NO_DEVICE, "psk_soft_create: hipSetDevice failed");
-        }
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-            delete h;
-            return fail(PSK_SOFT_ERR_NO_DEVICE,
-                        std::string("psk_soft_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
-        }
-        auto bail = [&](const char *what, hipError_t e2) {
-            std::string msg = std::string("psk_soft_create: ") + what + ": " + hipGetErrorString(e2);
-            psk_soft_destroy(h);
-            return fail(PSK_SOFT_ERR_HIP, msg);
-        };
+        if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess)
+            return bail(PSK_SOFT_ERR_NO_DEVICE, "psk_soft_create: hipSetDevice failed");
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return bail(PSK_SOFT_ERR_NO_DEVICE, std::string("psk_soft_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+        h->device = device;
         hipError_t e2;
-        if ((e2 = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)) != hipSuccess)
-            return bail("hipStreamCreate", e2);
+        if ((e2 = h->stream.create()) != hipSuccess)
+            return bail_hip("hipStreamCreate", e2);
         size_t state_b = sizeof(psk::ChanState) * (size_t)n_channels;
         size_t ring_b = sizeof(float2) * 2u * (size_t)h->lim.ring_cap * n_channels;
         size_t yv_b = sizeof(float) * (size_t)h->lim.fit_cap * n_channels;
-        if ((e2 = hipMalloc((void **)&h->d_state, state_b)) != hipSuccess) return bail("hipMalloc state", e2);
-        if ((e2 = hipMalloc((void **)&h->d_ring, ring_b)) != hipSuccess) return bail("hipMalloc ring", e2);
-        if ((e2 = hipMalloc((void **)&h->d_yv, yv_b)) != hipSuccess) return bail("hipMalloc yvals", e2);
+        if ((e2 = h->d_state.alloc_bytes(state_b)) != hipSuccess) return bail_hip("hipMalloc state", e2);
+        if ((e2 = h->d_ring.alloc_bytes(ring_b)) != hipSuccess) return bail_hip("hipMalloc ring", e2);
+        if ((e2 = h->d_yv.alloc_bytes(yv_b)) != hipSuccess) return bail_hip("hipMalloc yvals", e2);
         // psk_soft_i constructor state: phaseEstimate 0, last (0,0), LinearFit denominator 1, xAvg 0
         // (cpp/psk_soft.cpp:35-46, 187-199)
         std::vector<psk::ChanState> init(n_channels);
         std::memset(init.data(), 0, state_b);
         for (auto &s : init) s.lf_den = 1.0f;
         if ((e2 = hipMemcpy(h->d_state, init.data(), state_b, hipMemcpyHostToDevice)) != hipSuccess)
-            return bail("hipMemcpy state", e2);
-        if ((e2 = hipMemset(h->d_ring, 0, ring_b)) != hipSuccess) return bail("hipMemset", e2);
-        if ((e2 = hipMemset(h->d_yv, 0, yv_b)) != hipSuccess) return bail("hipMemset", e2);
+            return bail_hip("hipMemcpy state", e2);
+        if ((e2 = hipMemset(h->d_ring, 0, ring_b)) != hipSuccess) return bail_hip("hipMemset", e2);
+        if ((e2 = hipMemset(h->d_yv, 0, yv_b)) != hipSuccess) return bail_hip("hipMemset", e2);
         for (int s = 0; s < kPlanSlots; s++) {
             // (a slot = the plans of a call followed by the compact channel lists of its launches: one upload)
             // (... behind the header the kernels find in front of the plans: psk_plan.h)
-            char *hb = nullptr, *db = nullptr;
-            if ((e2 = hipHostMalloc((void **)&hb, slot_bytes(n_channels))) != hipSuccess)
-                return bail("hipHostMalloc plans", e2);
-            std::memset(hb, 0, psk::kPlanHeaderBytes);
-            h->h_plans[s] = reinterpret_cast<psk::ChanPlan *>(hb + psk::kPlanHeaderBytes);
-            if ((e2 = hipMalloc((void **)&db, slot_bytes(n_channels))) != hipSuccess)
-                return bail("hipMalloc plans", e2);
-            h->d_plans[s] = reinterpret_cast<psk::ChanPlan *>(db + psk::kPlanHeaderBytes);
-            if ((e2 = hipEventCreateWithFlags(&h->ev[s], hipEventDisableTiming)) != hipSuccess)
-                return bail("hipEventCreate", e2);
-            if ((e2 = hipEventCreateWithFlags(&h->ev_up[s], hipEventDisableTiming)) != hipSuccess)
-                return bail("hipEventCreate", e2);
+            if ((e2 = h->h_plan_blk[s].alloc(slot_bytes(n_channels))) != hipSuccess)
+                return bail_hip("hipHostMalloc plans", e2);
+            std::memset(h->h_plan_blk[s], 0, psk::kPlanHeaderBytes);
+            h->h_plans[s] = reinterpret_cast<psk::ChanPlan *>(h->h_plan_blk[s] + psk::kPlanHeaderBytes);
+            if ((e2 = h->d_plan_blk[s].alloc(slot_bytes(n_channels))) != hipSuccess)
+                return bail_hip("hipMalloc plans", e2);
+            h->d_plans[s] = reinterpret_cast<psk::ChanPlan *>(h->d_plan_blk[s] + psk::kPlanHeaderBytes);
+            if ((e2 = h->ev[s].ensure()) != hipSuccess)
+                return bail_hip("hipEventCreate", e2);
+            if ((e2 = h->ev_up[s].ensure()) != hipSuccess)
+                return bail_hip("hipEventCreate", e2);
         }
-        if ((e2 = hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking)) != hipSuccess)
-            return bail("hipStreamCreate", e2);
+        if ((e2 = h->up_stream.create()) != hipSuccess)
+            return bail_hip("hipStreamCreate", e2);
         if (const char *e = std::getenv("PSK_SOFT_PLAN_STREAM"))
             h->opt_up_stream = std::atoi(e) != 0;
     }
     // the records of the quality pass and of the two looks: zeros until a pass writes one (the word search's come with its first call)
     if (h->quality.ensure_zeroed(h->dry, n_channels, "psk_soft_create: quality records") != PSK_SOFT_OK ||
         h->acquire.ensure_zeroed(h->dry, n_channels, "psk_soft_create: acquire records") != PSK_SOFT_OK ||
-        h->symrate.ensure_zeroed(h->dry, n_channels, "psk_soft_create: symrate records") != PSK_SOFT_OK) {
-        const std::string msg = g_last_error;
-        psk_soft_destroy(h);
-        return fail(PSK_SOFT_ERR_HIP, msg);
-    }
+        h->symrate.ensure_zeroed(h->dry, n_channels, "psk_soft_create: symrate records") != PSK_SOFT_OK)
+        return bail(PSK_SOFT_ERR_HIP, g_last_error);
     *out = h;
     return PSK_SOFT_OK;
 }
@@ -2300,79 +2349,14 @@ psk_soft_status psk_soft_destroy(psk_soft_handle_t *h)
 {
     if (!h)
         return PSK_SOFT_OK;
-    if (!h->dry) {
+    // Every stream the handle owns is idle before anything is released (an absent stream: no HIP call); the members' destructors do
+    // the rest, in whatever order.
+    if (h->device != PSK_SOFT_DEVICE_NONE)
         (void)hipSetDevice(h->device);
-        if (h->stream)
-            (void)hipStreamSynchronize(h->stream);
-        for (int s = 0; s < kPlanSlots; s++) {
-            if (h->h_plans[s]) (void)hipHostFree(psk::plan_header(h->h_plans[s]));
-            if (h->d_plans[s]) (void)hipFree(psk::plan_header(h->d_plans[s]));
-            if (h->ev[s]) (void)hipEventDestroy(h->ev[s]);
-            if (h->ev_up[s]) (void)hipEventDestroy(h->ev_up[s]);
-        }
-        if (h->d_state) (void)hipFree(h->d_state);
-        if (h->d_ring) (void)hipFree(h->d_ring);
-        if (h->d_yv) (void)hipFree(h->d_yv);
-        h->qpass.free(), h->quality.free();
-        h->apass.free(), h->acquire.free();
-        h->spass.free(), h->symrate.free();
-        h->ypass.free(), h->sync.free();
-        if (h->d_sync_words) (void)hipFree(h->d_sync_words);
-        h->sync_hist.free();
-        h->dpass.free(), h->demap.free();
-        if (h->d_demap_maps) (void)hipFree(h->d_demap_maps);
-        if (h->d_tiles) (void)hipFree(h->d_tiles);
-        if (h->d_traw) (void)hipFree(h->d_traw);
-        if (h->d_test) (void)hipFree(h->d_test);
-        if (h->d_ts) (void)hipFree(h->d_ts);
-        for (void *q : {(void *)h->pf.k, (void *)h->pf.y, (void *)h->pf.S, (void *)h->pf.c, (void *)h->pf.tt, (void *)h->pf.xs,
-                        (void *)h->pf.tile, (void *)h->pf.blk, (void *)h->pf.walk, (void *)h->pf.chan})
-            if (q) (void)hipFree(q);
-        if (h->pf.hint) (void)hipHostFree(h->pf.hint);
-        if (h->tile_ev) (void)hipEventDestroy(h->tile_ev);
-        for (auto &cv : h->cvt) cv.free();
-        for (auto &g : h->gat) g.free();
-        for (auto &g : h->gdesc) g.free();
-        if (h->d_tune_tab) (void)hipFree(h->d_tune_tab);
-        h->rs_hist.free();
-        if (h->d_fir_taps) (void)hipFree(h->d_fir_taps);
-        h->fir_hist.free();
-        for (auto &sl : h->stage) {
-            if (sl.stream) (void)hipStreamSynchronize(sl.stream);
-            if (sl.h_buf) (void)hipHostFree(sl.h_buf);
-            if (sl.d_buf) (void)hipFree(sl.d_buf);
-            if (sl.done) (void)hipEventDestroy(sl.done);
-            if (sl.stream) (void)hipStreamDestroy(sl.stream);
-        }
-        delete h->pool;
-        for (int k = 0; k < kAuxStreams; k++) {
-            if (h->aux[k]) (void)hipStreamSynchronize(h->aux[k]);
-            if (h->aux_join[k]) (void)hipEventDestroy(h->aux_join[k]);
-            if (h->aux[k]) (void)hipStreamDestroy(h->aux[k]);
-        }
-        for (hipStream_t &q : h->pipe_st)
-            if (q) {
-                (void)hipStreamSynchronize(q);
-                (void)hipStreamDestroy(q);
-            }
-        for (hipEvent_t &e : h->pipe_ev)
-            if (e) (void)hipEventDestroy(e);
-        if (h->d_pipe_carry) (void)hipFree(h->d_pipe_carry);
-        if (h->d_pipe_y) (void)hipFree(h->d_pipe_y);
-        if (h->d_wide_rec) (void)hipFree(h->d_wide_rec);
-        if (h->d_wide_stat) (void)hipFree(h->d_wide_stat);
-        if (h->d_wide_symE) (void)hipFree(h->d_wide_symE);
-        if (h->d_far_y) (void)hipFree(h->d_far_y);
-        if (h->aux_fork) (void)hipEventDestroy(h->aux_fork);
-        for (auto &row : h->slot_aux_ev)
-            for (hipEvent_t &e : row)
-                if (e) (void)hipEventDestroy(e);
-        if (h->up_stream) {
-            (void)hipStreamSynchronize(h->up_stream);
-            (void)hipStreamDestroy(h->up_stream);
-        }
-        if (h->stream) (void)hipStreamDestroy(h->stream);
-    }
+    (void)h->stream.sync(), (void)h->up_stream.sync();
+    for (const Stream &s : h->aux) (void)s.sync();
+    for (const Stream &s : h->pipe_st) (void)s.sync();
+    for (const StageSlot &sl : h->stage) (void)sl.stream.sync();
     delete h;
     return PSK_SOFT_OK;
 }
@@ -2670,7 +2654,7 @@ static psk_soft_status ensure_tune_tab(psk_soft_handle *h)
 {
     if (h->d_tune_tab)
         return PSK_SOFT_OK;
-    PSK_HIP(hipMalloc((void **)&h->d_tune_tab, sizeof(float) * psk::kTuneTableFloats));
+    PSK_HIP(h->d_tune_tab.alloc(psk::kTuneTableFloats));
     PSK_HIP(hipMemcpy(h->d_tune_tab, psk::tune_tables(), sizeof(float) * psk::kTuneTableFloats, hipMemcpyHostToDevice));
     return PSK_SOFT_OK;
 }
@@ -2913,7 +2897,7 @@ static psk_soft_status front_describe(const FrontCall &c, FrontPlan &plan)
     PSK_TRY(ds.claim(plan.desc_bytes));
     plan.ds = &ds;
     char *const buf = plan.sc->buf;
-    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf);
+    psk::GatherGroup *const hg = reinterpret_cast<psk::GatherGroup *>(ds.h_buf.get());
     psk::GatherChan *const hc = reinterpret_cast<psk::GatherChan *>(ds.h_buf + plan.off_cols);
     psk::GatherSingle *const hs = reinterpret_cast<psk::GatherSingle *>(ds.h_buf + plan.off_singles);
     psk::TuneDesc *ht = reinterpret_cast<psk::TuneDesc *>(ds.h_buf + plan.off_tune);
@@ -3011,13 +2995,12 @@ static psk_soft_status front_launch(const FrontCall &c, FrontPlan &plan)
     psk_soft_handle *h = c.h;
     GatherDescSlot &ds = *plan.ds;
     PSK_HIP(hipMemcpyAsync(ds.d_buf, ds.h_buf, plan.desc_bytes, hipMemcpyHostToDevice, c.stream));
-    ds.used = true;  // (from here on the slot waits for its event, which front_release records whatever happens)
-    plan.owed = true;
+    plan.owed = true;  // (from here on the slot waits for its event, which front_release records whatever happens)
     // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: S = bytes of a complex sample, cnt = groups / singles / packets covered)
     auto mark = [&](const char *what, int bytes, uint32_t cnt, uint64_t tiles) {
         return trace_launch(h, what, bytes, 0, c.ch0, cnt, tiles, 0, 0, h->slot, c.stream);
     };
-    const psk::GatherGroup *dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf);
+    const psk::GatherGroup *dg = reinterpret_cast<const psk::GatherGroup *>(ds.d_buf.get());
     const psk::GatherChan *dc = reinterpret_cast<const psk::GatherChan *>(ds.d_buf + plan.off_cols);
     const psk::GatherSingle *dsg = reinterpret_cast<const psk::GatherSingle *>(ds.d_buf + plan.off_singles);
     for (int b = 0; b < 3; b++) {
@@ -3065,11 +3048,10 @@ static psk_soft_status front_enqueue(const FrontCall &c, FrontPlan &plan)
 static psk_soft_status front_release(const FrontCall &c, FrontPlan &plan, psk_soft_status st)
 {
     const std::string keep = g_last_error;
-    const hipError_t e1 = hipEventRecord(plan.sc->ev, c.stream), e2 = hipEventRecord(plan.ds->ev, c.stream);
-    plan.sc->ev_used = true;
+    const hipError_t e1 = plan.sc->ev.record(c.stream), e2 = plan.ds->ev.record(c.stream);
     if (e1 != hipSuccess || e2 != hipSuccess) {
         (void)hipStreamSynchronize(c.stream);
-        plan.ds->used = false;
+        plan.ds->ev.clear();
         if (st == PSK_SOFT_OK)
             return fail(PSK_SOFT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
     }
@@ -3279,7 +3261,7 @@ psk_soft_status psk_soft_fir_define(psk_soft_handle_t *h, uint32_t slot, const f
     }
     PSK_HIP(hipSetDevice(h->device));
     if (!h->d_fir_taps)
-        PSK_HIP(hipMalloc((void **)&h->d_fir_taps, sizeof(float) * psk::kFirSlots * psk::kFirMaxTaps));
+        PSK_HIP(h->d_fir_taps.alloc((size_t)psk::kFirSlots * psk::kFirMaxTaps));
     PSK_TRY(h->fir_hist.wait());  // (no launch is still reading the slot)
     PSK_HIP(hipMemcpy(h->d_fir_taps + (size_t)psk::kFirMaxTaps * slot, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice));
     h->fir_ntaps[slot] = n_taps;
@@ -3796,7 +3778,7 @@ psk_soft_status psk_soft_sync_define(psk_soft_handle_t *h, uint32_t slot, const 
     if (!h->dry) {
         PSK_HIP(hipSetDevice(h->device));
         if (!h->d_sync_words)
-            PSK_HIP(hipMalloc((void **)&h->d_sync_words, sizeof(float) * 2u * psk::kSyncSlots * psk::kSyncMaxWord));
+            PSK_HIP(h->d_sync_words.alloc((size_t)2u * psk::kSyncSlots * psk::kSyncMaxWord));
         PSK_TRY(h->sync_hist.wait());  // (no launch is still reading the slot)
         PSK_HIP(hipMemcpy(h->d_sync_words + (size_t)2u * psk::kSyncMaxWord * slot, word, sizeof(float) * 2u * n, hipMemcpyHostToDevice));
         h->sync_ew[slot] = psk::sy_word_energy(word, n);
@@ -4063,7 +4045,7 @@ psk_soft_status psk_soft_demap_define(psk_soft_handle_t *h, uint32_t slot, uint3
     if (!h->dry) {
         PSK_HIP(hipSetDevice(h->device));
         if (!h->d_demap_maps)
-            PSK_TRY(alloc_zeroed(&h->d_demap_maps, sizeof(psk::DemapMap) * psk::kDemapSlots, "demap maps"));
+            PSK_TRY(alloc_zeroed(h->d_demap_maps, psk::kDemapSlots, "demap maps"));
         PSK_TRY(h->dpass.wait());  // (no launch is still reading the slot)
         const psk::DemapMap m = demap_map_make(M, points, labels);
         PSK_HIP(hipMemcpy(h->d_demap_maps + slot, &m, sizeof m, hipMemcpyHostToDevice));
@@ -4296,19 +4278,16 @@ psk_soft_status psk_soft_demap_gain(const psk_soft_sync_derived_t *d, uint32_t M
 static psk_soft_status stage_ensure(psk_soft_handle *h, StageSlot &sl, size_t in_bytes)
 {
     if (!sl.stream) {
-        PSK_HIP(hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
-        PSK_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+        PSK_HIP(sl.stream.create());
+        PSK_HIP(sl.done.ensure());
     }
     if (sl.in_cap >= in_bytes)
         return PSK_SOFT_OK;
     size_t cap = align_up(in_bytes > h->stage_bytes ? in_bytes : h->stage_bytes, 4096);
-    if (sl.h_buf) (void)hipHostFree(sl.h_buf);
-    if (sl.d_buf) (void)hipFree(sl.d_buf);
-    sl.h_buf = nullptr;
-    sl.d_buf = nullptr;
+    sl.h_buf.release(), sl.d_buf.release();
     sl.in_cap = 0;
-    PSK_HIP(hipHostMalloc((void **)&sl.h_buf, region_total(cap)));
-    PSK_HIP(hipMalloc((void **)&sl.d_buf, region_total(cap)));
+    PSK_HIP(sl.h_buf.alloc(region_total(cap)));
+    PSK_HIP(sl.d_buf.alloc(region_total(cap)));
     sl.in_cap = cap;
     return PSK_SOFT_OK;
 }
@@ -4318,7 +4297,7 @@ static psk_soft_status stage_retire(psk_soft_handle *h, StageSlot &sl, psk_soft_
 {
     if (!sl.busy)
         return PSK_SOFT_OK;
-    PSK_HIP(hipEventSynchronize(sl.done));
+    PSK_HIP(sl.done.sync());
     const uint8_t *hs = sl.h_buf + region_soft(sl.in_cap), *hp = sl.h_buf + region_phase(sl.in_cap);
     const uint8_t *hb = sl.h_buf + region_bits(sl.in_cap), *hx = sl.h_buf + region_sidx(sl.in_cap);
     psk_soft_output_t *o0 = outs + (sl.ch0 - batch_ch0);
@@ -4350,7 +4329,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
         if (const char *e = std::getenv("PSK_SOFT_HOST_THREADS")) nt = std::atoi(e);
         unsigned hw = std::thread::hardware_concurrency();
         if (hw && (unsigned)nt > hw) nt = (int)hw;
-        h->pool = new CopyPool(nt > 1 ? nt - 1 : 0);  // the calling thread works too
+        h->pool.reset(new CopyPool(nt > 1 ? nt - 1 : 0));  // the calling thread works too
         if (const char *e = std::getenv("PSK_SOFT_STAGE_MB")) {
             long mb = std::atol(e);
             if (mb >= 1 && mb <= 4096) h->stage_bytes = (size_t)mb << 20;
@@ -4488,7 +4467,7 @@ psk_soft_status psk_soft_process_host(psk_soft_handle_t *h, uint32_t ch0, uint32
         if (op) PSK_HIP(hipMemcpyAsync(sl.h_buf + region_phase(sl.in_cap), d_phase, op, hipMemcpyDeviceToHost, sl.stream));
         if (ob) PSK_HIP(hipMemcpyAsync(sl.h_buf + region_bits(sl.in_cap), d_bits, ob, hipMemcpyDeviceToHost, sl.stream));
         if (ox) PSK_HIP(hipMemcpyAsync(sl.h_buf + region_sidx(sl.in_cap), d_sidx, ox, hipMemcpyDeviceToHost, sl.stream));
-        PSK_HIP(hipEventRecord(sl.done, sl.stream));
+        PSK_HIP(sl.done.record(sl.stream));
         sl.busy = true;
         first = last;
     }
@@ -4508,21 +4487,15 @@ psk_soft_status psk_soft_synchronize(psk_soft_handle_t *h)
     if (h->dry)
         return PSK_SOFT_OK;
     PSK_HIP(hipSetDevice(h->device));
-    for (int s = 0; s < kPlanSlots; s++)
-        if (h->ev_used[s])
-            PSK_HIP(hipEventSynchronize(h->ev[s]));
-    PSK_HIP(hipStreamSynchronize(h->stream));
-    for (int a = 0; a < kAuxStreams; a++)
-        if (h->aux[a])
-            PSK_HIP(hipStreamSynchronize(h->aux[a]));
+    for (const Event &e : h->ev) PSK_HIP(e.sync());
+    PSK_HIP(h->stream.sync());
+    for (const Stream &s : h->aux) PSK_HIP(s.sync());
     if (h->deferred_pending && h->deferred_stream)
         PSK_HIP(hipStreamSynchronize(h->deferred_stream));
     h->deferred_pending = false;
-    for (auto &row : h->slot_aux_used)
-        for (bool &u : row) u = false;
-    for (auto &sl : h->stage)
-        if (sl.stream)
-            PSK_HIP(hipStreamSynchronize(sl.stream));
+    for (auto &row : h->slot_aux_ev)
+        for (Event &e : row) e.clear();
+    for (const StageSlot &sl : h->stage) PSK_HIP(sl.stream.sync());
     return PSK_SOFT_OK;
 }
 
@@ -4538,8 +4511,8 @@ psk_soft_status psk_soft_join(psk_soft_handle_t *h, void *stream_v)
     if (h->deferred_stream && h->deferred_stream != stream) {
         if (!h->aux_fork)
             return PSK_SOFT_OK;
-        PSK_HIP(hipEventRecord(h->aux_fork, h->deferred_stream));
-        PSK_HIP(hipStreamWaitEvent(stream, h->aux_fork, 0));
+        PSK_HIP(h->aux_fork.record(h->deferred_stream));
+        PSK_HIP(h->aux_fork.wait(stream));
     }
     h->deferred_pending = true;  // (deferred_join() clears it)
     PSK_HIP(deferred_join(h, stream));
@@ -4799,19 +4772,17 @@ psk_soft_status psk_soft_probe_read_ms(psk_soft_handle_t *h, const void *dev_ptr
         return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_probe_read_ms: needs a device handle, a 16-byte aligned device "
                                               "pointer, at least 16 bytes and one repetition");
     PSK_HIP(hipSetDevice(h->device));
-    hipEvent_t e0, e1;
-    PSK_HIP(hipEventCreate(&e0));
-    PSK_HIP(hipEventCreate(&e1));
-    float *sink = reinterpret_cast<float *>(h->d_state);  // (never written: see the kernel)
+    Event e0, e1;  // (with timing; they go on every way out)
+    PSK_HIP(e0.ensure(true));
+    PSK_HIP(e1.ensure(true));
+    float *sink = reinterpret_cast<float *>(h->d_state.get());  // (never written: see the kernel)
     PSK_HIP(psk::launch_read_probe(dev_ptr, bytes, sink, h->stream));  // untimed first pass
-    PSK_HIP(hipEventRecord(e0, h->stream));
+    PSK_HIP(e0.record(h->stream));
     for (int r = 0; r < reps; r++) PSK_HIP(psk::launch_read_probe(dev_ptr, bytes, sink, h->stream));
-    PSK_HIP(hipEventRecord(e1, h->stream));
-    PSK_HIP(hipEventSynchronize(e1));
+    PSK_HIP(e1.record(h->stream));
+    PSK_HIP(e1.sync());
     float ms = 0.0f;
-    PSK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    PSK_HIP(hipEventElapsedTime(&ms, e0.get(), e1.get()));
     *ms_per_pass = (double)ms / reps;
     return PSK_SOFT_OK;
 }
