@@ -979,6 +979,119 @@ uint64_t psk_soft_demap_bytes(void);        /* sizeof(psk_soft_demap_t), for bin
 uint64_t psk_soft_demap_in_bytes(void);     /* sizeof(psk_soft_demap_in_t), for bindings */
 uint32_t psk_soft_demap_piece(void);        /* symbols of one piece of the device's fold: the summation order's unit */
 
+/* ---- frames as payload bits: Viterbi decoding of int8 LLR frames (psk_soft_viterbi_device) ---------------------------------------
+ * What stands behind the demapper is an FEC decoder.  This call decodes frames of int8 LLRs that are already in device memory --
+ * as psk_soft_demap_device writes them with PSK_SOFT_DEMAP_I8 -- with a binary convolutional code the caller defines, and writes
+ * the payload bits where the caller wants them; it leaves one small record per frame.  Everything is integer arithmetic, so the
+ * host definition (psk_soft_viterbi_host) and the device agree to the byte without any care about rounding.
+ *
+ * The call touches no demodulator state, statistics or history, and no quality, look, sync or demap record.  The LLRs and the
+ * codes are read, never written.
+ *
+ * Code.  Constraint length K = 3 .. 7; n = 2 .. 4 generator polynomials g[j], each a K-bit integer whose bit K-1 taps the current
+ *   input bit (the usual octal notation: 0171, 0133 for K = 7).  A state is K-1 bits, s = (u_t, u_{t-1}, ...) with the newest
+ *   input at bit K-2.  At step t from state s_{t-1} with input u the register is r = (u << (K-1)) | s_{t-1}; code bit j is
+ *   c_j = parity(r & g[j]); the new state is s_t = r >> 1.  Refused: a polynomial that is 0 or has bits at or above K, and a set
+ *   of polynomials that, taken over all j, taps neither bit K-1 nor bit 0.
+ * Puncturing.  A period P (1 .. 16 steps, n*P <= 32) and a `keep` mask of n*P bits: bit p*n + j set means code bit j of a step
+ *   with t mod P == p was transmitted.  The frame's LLRs are the kept code bits in order of (t, j); a bit that was not kept
+ *   contributes 0 and is not read.  `keep` has at least one bit set and none at or above n*P.  P = 1, keep = 2^n - 1 is the
+ *   unpunctured code.  psk_soft_viterbi_count gives the number of LLRs a frame of n_steps steps holds.
+ * Input.  int8 LLRs; a positive value means bit 0 is the nearer.  The pointer may have any byte alignment (the segments of a
+ *   frame abut).  The value -128 is taken as it is.  float32 LLRs are not accepted by this entry.
+ * Path metrics are int32 and are MAXIMISED.  The branch metric of a branch with code bits c is bm = sum_j (c_j ? -l_j : +l_j)
+ *   over the kept bits.  At the start pm[0] = 0 and pm[s] = -2^30 for every other s; with PSK_SOFT_VITERBI_ANY_START every
+ *   pm[s] = 0 (a frame cut out of a running stream).  n_steps <= PSK_SOFT_VITERBI_MAX_STEPS = 65536, so |pm| <= 4*128*65536 = 2^25
+ *   < 2^26 on reachable states; an unreachable state stays below -2^30 + 2^26 and above -2^31.  No normalisation exists and none
+ *   is needed.
+ * Add-compare-select.  State s has the two predecessors p_b = ((s << 1) & (2^(K-1) - 1)) | b, b = 0, 1; its input bit is
+ *   u = s >> (K-2).  pm'[s] = max_b (pm[p_b] + bm_b); b = 1 wins only if strictly greater.  The decision d_t[s] is the winning b.
+ * End and traceback.  With PSK_SOFT_VITERBI_TERMINATED the end state is 0 and the last K-1 steps are the tail: n_bits =
+ *   n_steps - (K-1); n_steps < K-1 is refused.  Without it the end state is the FIRST maximum of the final metrics, s ascending,
+ *   and n_bits = n_steps.  Going back from t = n_steps - 1: u_t = s_t >> (K-2), s_{t-1} = ((s_t << 1) & mask) | d_t[s_t].  The
+ *   state reached in front of step 0 is the record's start_state; it is 0 unless ANY_START.
+ * Output.  The bits u_0 .. u_{n_bits-1}, one a byte (uint8 0 / 1).  With PSK_SOFT_VITERBI_PACKED eight a byte: bit i goes to byte
+ *   i >> 3 at bit 7 - (i & 7); the unused low bits of the last byte are zero.  `out` may have any byte alignment.  Exactly n_bits,
+ *   or ceil(n_bits / 8), bytes are written and no byte outside them.  The outputs of a call's frames must not overlap: that is
+ *   the caller's duty and is not checked.
+ * Record.  One psk_soft_viterbi_t per frame of the LAST call, in the order of `in`.  Everything in it is an integer and therefore
+ *   independent of any summation order.  With start state 0 (no ANY_START) metric <= sum_abs, with equality exactly when
+ *   n_flip == 0.
+ * Cost.  One frame never uses more than one wave of 64 lanes, a state a lane: a call with few frames is slow, and only a call
+ *   of thousands of frames fills the machine.  The decisions of a frame in flight live in scratch the handle owns, 8 bytes a
+ *   step, grown on demand; a call keeps at most PSK_SOFT_VITERBI_SCRATCH_BYTES of them in flight (the allocation itself has a
+ *   quarter of headroom, and each of the two calls that may be in flight has its own); frames beyond that take further trips
+ *   of the same workgroups. */
+#define PSK_SOFT_VITERBI_SLOTS         16
+#define PSK_SOFT_VITERBI_MAX_FRAMES    (1u << 20)
+#define PSK_SOFT_VITERBI_MAX_STEPS     65536u
+#define PSK_SOFT_VITERBI_SCRATCH_BYTES (256ull << 20)
+enum { PSK_SOFT_VITERBI_PACKED = 1, PSK_SOFT_VITERBI_TERMINATED = 2, PSK_SOFT_VITERBI_ANY_START = 4 };  /* psk_soft_viterbi_in_t.flags */
+/* psk_soft_viterbi_t.flags: DATA or PLANNED, ORed with the frame's flags shifted left by one */
+enum { PSK_SOFT_VITERBI_DATA = 1, PSK_SOFT_VITERBI_REC_PACKED = 2, PSK_SOFT_VITERBI_REC_TERMINATED = 4,
+       PSK_SOFT_VITERBI_REC_ANY_START = 8, PSK_SOFT_VITERBI_PLANNED = 128 };
+
+typedef struct psk_soft_viterbi_in {
+    const int8_t *llr;    /* DEVICE pointer to the frame's first LLR, any alignment; NULL: the frame is skipped              */
+    void *out;            /* DEVICE pointer to the output: n_bits bytes, or ceil(n_bits / 8) with PACKED; any alignment     */
+    uint32_t n_steps;     /* trellis steps (input bits including the tail); 0: the frame is skipped                         */
+    uint32_t code;        /* 1 + the slot of the code; 0: the frame is skipped                                              */
+    uint32_t flags;       /* PSK_SOFT_VITERBI_PACKED, _TERMINATED, _ANY_START                                               */
+    uint32_t pad;         /* zero                                                                                           */
+} psk_soft_viterbi_in_t;  /* 32 bytes */
+
+typedef struct psk_soft_viterbi {        /* one per frame of the LAST psk_soft_viterbi_device call */
+    uint64_t n_steps;
+    uint64_t n_llr;                      /* the LLRs read                                                                   */
+    int64_t metric;                      /* the end state's path metric, minus nothing                                     */
+    int64_t sum_abs;                     /* sum |l| over the LLRs read, with |-128| = 128                                   */
+    uint32_t n_flip;                     /* LLRs l != 0 whose sign disagrees with the decoded path's code bit: the channel-
+                                            error count a caller uses as a lock indicator                                  */
+    uint32_t n_zero;                     /* LLRs equal to 0                                                                 */
+    uint32_t end_state, start_state;
+    uint32_t n_bits;
+    uint32_t flags;                      /* PSK_SOFT_VITERBI_DATA or _PLANNED, | the frame's flags shifted left by one      */
+    uint32_t pad[2];                     /* zero                                                                            */
+} psk_soft_viterbi_t;                    /* 64 bytes */
+
+/* The code of slot `slot` (0 .. PSK_SOFT_VITERBI_SLOTS - 1), copied into memory the handle owns; a frame names it as code =
+ * slot + 1.  Redefining a slot waits for the handle's last viterbi launch first.  A control-plane-only handle records the code.
+ * PSK_SOFT_ERR_INVALID_ARG: a null pointer, a slot out of range, K outside 3 .. 7, n outside 2 .. 4, a polynomial the text above
+ * refuses, P outside 1 .. 16 or n*P > 32, a keep of 0 or with bits at or above n*P. */
+psk_soft_status psk_soft_viterbi_define(psk_soft_handle_t *h, uint32_t slot, uint32_t K, uint32_t n, const uint32_t *g /* [n] */,
+                                        uint32_t P, uint32_t keep);
+/* The frames in[0 .. nframe-1], nframe = 1 .. PSK_SOFT_VITERBI_MAX_FRAMES.  The LLRs must be complete on `stream` (a demap call
+ * enqueued there just before is); with PSK_SOFT_OPT_DEFERRED_JOIN pending the call joins the side streams into `stream` first,
+ * as the sync and demap entries do.  The call returns without waiting.  Every call replaces the records.
+ * A frame with n_steps == 0, code == 0 or llr == NULL is skipped: it gets the all-zero record and nothing is written.
+ * Refusals (PSK_SOFT_ERR_INVALID_ARG before anything is enqueued or any record changes): a null pointer, nframe out of range; on
+ * a frame that is not skipped a slot out of range or never defined, unknown flag bits, a non-zero pad, a null `out`, n_steps
+ * above PSK_SOFT_VITERBI_MAX_STEPS, TERMINATED with n_steps < K-1.
+ * How: one launch on `stream`, one wave per frame (see Cost above); frames beyond 65535 workgroups or beyond the scratch bound
+ * take further trips of the same workgroups.
+ * A control-plane-only handle checks the arguments, then leaves records with n_steps, n_llr, n_bits and flags =
+ * PSK_SOFT_VITERBI_PLANNED | the frame's flags shifted left by one, everything else zero. */
+psk_soft_status psk_soft_viterbi_device(psk_soft_handle_t *h, uint32_t nframe, const psk_soft_viterbi_in_t *in /* [nframe] */,
+                                        void *stream);
+/* waits like psk_soft_get_demap does and copies the records of the frames [first, first + n) of the last call out.
+ * PSK_SOFT_ERR_INVALID_ARG: a null pointer, n == 0, a range beyond the last call's nframe, no call yet. */
+psk_soft_status psk_soft_get_viterbi(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_viterbi_t *rec /* [n] */);
+/* host only, pure: the definition for one frame on the host.  `in` is read as the entry reads it, with HOST pointers in llr and
+ * out; `code` is not looked at beyond being non-zero (the code is K, n, g, P, keep).  The bytes at out and *rec are byte for byte
+ * what the device writes (flags = PSK_SOFT_VITERBI_DATA | ...).  A skipped frame gives the zero record.  Refuses what the entry
+ * and psk_soft_viterbi_define refuse of their arguments. */
+psk_soft_status psk_soft_viterbi_host(uint32_t K, uint32_t n, const uint32_t *g, uint32_t P, uint32_t keep,
+                                      const psk_soft_viterbi_in_t *in, psk_soft_viterbi_t *rec);
+/* host only, pure: the encoder with puncturing applied, from state 0: bits[0 .. n_steps-1] (uint8, the low bit counts; a caller
+ * that terminates appends its K-1 zeros itself) to psk_soft_viterbi_count(...) code bits, one a byte (0 / 1), in order of (t, j). */
+psk_soft_status psk_soft_viterbi_encode_host(uint32_t K, uint32_t n, const uint32_t *g, uint32_t P, uint32_t keep, const uint8_t *bits,
+                                             uint32_t n_steps, uint8_t *code_bits_out);
+/* host only, pure: the number of LLRs a frame of n_steps steps holds; 0 for arguments psk_soft_viterbi_define refuses of n, P, keep
+ * (K is not looked at) */
+uint64_t psk_soft_viterbi_count(uint32_t K, uint32_t n, uint32_t P, uint32_t keep, uint64_t n_steps);
+uint64_t psk_soft_viterbi_bytes(void);      /* sizeof(psk_soft_viterbi_t), for bindings */
+uint64_t psk_soft_viterbi_in_bytes(void);   /* sizeof(psk_soft_viterbi_in_t), for bindings */
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

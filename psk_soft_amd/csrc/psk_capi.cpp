@@ -26,6 +26,7 @@
 #include "psk_symrate.h"
 #include "psk_sync.h"
 #include "psk_demap.h"
+#include "psk_viterbi.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -874,6 +875,16 @@ struct psk_soft_handle {
     bool demap_called = false;
     uint32_t demap_nseg = 0;    // of the last call
     PassRing<psk::DemapDesc, psk::DemapPartial, 2> dpass;
+    // psk_soft_viterbi_device: the codes of every slot (kViterbiSlots ViterbiCode, allocated at the first psk_soft_viterbi_define;
+    // K 0: never defined) and their copy on the host; one record per frame of the last call, grown on demand -- a
+    // control-plane-only handle keeps them on the host --; the "partials" of its pass are the decision words of the frames in
+    // flight (psk_viterbi.hip), at most kViterbiScratchWords a call
+    DeviceBuf<psk::ViterbiCode> d_viterbi_codes;
+    psk::ViterbiCode viterbi_code[psk::kViterbiSlots] = {};
+    Records<psk_soft_viterbi_t> viterbi;
+    bool viterbi_called = false;
+    uint32_t viterbi_nframe = 0;  // of the last call
+    PassRing<psk::ViterbiDesc, uint64_t, 2> vpass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     std::unique_ptr<CopyPool> pool;
@@ -4266,6 +4277,243 @@ psk_soft_status psk_soft_demap_gain(const psk_soft_sync_derived_t *d, uint32_t M
     if (!(flags & PSK_SOFT_DEMAP_GAIN_UNIT))
         gr /= d->amplitude, gi /= d->amplitude;
     gain[0] = (float)gr, gain[1] = (float)gi;
+    return PSK_SOFT_OK;
+}
+
+// ---- psk_soft_viterbi_device: frames of int8 LLRs as payload bits (include/psk_soft_hip.h, psk_viterbi.hip) ----
+// Behind the demap call: one launch on the caller's stream, one wave per frame, one record per frame of the call; a ring of its
+// own like the demapper's, whose "partials" are the decision words of the frames in flight.  Nothing of the control plane, of the
+// demodulator's state or of any other record is read or written.
+static psk::ViterbiCode viterbi_code_make(uint32_t K, uint32_t n, const uint32_t *g, uint32_t P, uint32_t keep)
+{
+    psk::ViterbiCode c = {};
+    c.K = K, c.n = n, c.P = P, c.keep = keep;
+    for (uint32_t j = 0; j < n; j++) c.g[j] = g[j];
+    return c;
+}
+
+psk_soft_status psk_soft_viterbi_define(psk_soft_handle_t *h, uint32_t slot, uint32_t K, uint32_t n, const uint32_t *g, uint32_t P, uint32_t keep)
+{
+    if (!h || !g || slot >= psk::kViterbiSlots || !psk::vt_code_ok(K, n, g, P, keep))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_viterbi_define: null pointer, a slot above 15, K outside 3 .. 7, n outside 2 .. 4, a polynomial that is 0 or has bits at or above K, polynomials that tap neither bit K-1 nor bit 0, P outside 1 .. 16, n P above 32 or a keep that is 0 or has bits at or above n P");
+    const psk::ViterbiCode c = viterbi_code_make(K, n, g, P, keep);
+    if (!h->dry) {
+        PSK_HIP(hipSetDevice(h->device));
+        if (!h->d_viterbi_codes)
+            PSK_TRY(alloc_zeroed(h->d_viterbi_codes, psk::kViterbiSlots, "viterbi codes"));
+        PSK_TRY(h->vpass.wait());  // (no launch is still reading the slot)
+        PSK_HIP(hipMemcpy(h->d_viterbi_codes + slot, &c, sizeof c, hipMemcpyHostToDevice));
+    }
+    h->viterbi_code[slot] = c;
+    return PSK_SOFT_OK;
+}
+
+static bool viterbi_skipped(const psk_soft_viterbi_in_t &k) { return !k.n_steps || !k.code || !k.llr; }
+
+// what is wrong with a frame that is not skipped, given the K of its code; nullptr: nothing
+static const char *viterbi_frame_fault(const psk_soft_viterbi_in_t &k, uint32_t K)
+{
+    if (k.flags & ~psk::kViterbiFlagMask)
+        return "unknown flag bits";
+    if (k.pad)
+        return "pad must be zero";
+    if (!k.out)
+        return "out is null";
+    if (k.n_steps > psk::kViterbiMaxSteps)
+        return "more than 65536 steps";
+    if ((k.flags & PSK_SOFT_VITERBI_TERMINATED) && k.n_steps < K - 1u)
+        return "PSK_SOFT_VITERBI_TERMINATED with fewer than K-1 steps";
+    return nullptr;
+}
+
+psk_soft_status psk_soft_viterbi_device(psk_soft_handle_t *h, uint32_t nframe, const psk_soft_viterbi_in_t *in, void *stream_v)
+{
+    if (!h || !in || !nframe || nframe > psk::kViterbiMaxFrames)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_viterbi_device: null pointer or a number of frames outside 1 .. 2^20");
+    // the refusals, before anything is enqueued or any record changes
+    uint32_t max_steps = 0;
+    for (uint32_t i = 0; i < nframe; i++) {
+        const psk_soft_viterbi_in_t &k = in[i];
+        if (viterbi_skipped(k))
+            continue;
+        const char *what = nullptr;
+        if (k.code > psk::kViterbiSlots || !h->viterbi_code[k.code - 1u].K)
+            what = "a code slot above 15 or never defined (psk_soft_viterbi_define)";
+        else
+            what = viterbi_frame_fault(k, h->viterbi_code[k.code - 1u].K);
+        if (what) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "psk_soft_viterbi_device: frame %u: %s", i, what);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+        max_steps = k.n_steps > max_steps ? k.n_steps : max_steps;
+    }
+    auto n_llr_of = [&](const psk_soft_viterbi_in_t &k) {
+        const psk::ViterbiCode &c = h->viterbi_code[k.code - 1u];
+        return (uint32_t)psk::vt_count(c.n, c.P, c.keep, k.n_steps);
+    };
+    if (h->dry) {
+        h->viterbi.dry.assign(nframe, psk_soft_viterbi_t{});
+        for (uint32_t i = 0; i < nframe; i++) {
+            if (viterbi_skipped(in[i]))
+                continue;
+            psk_soft_viterbi_t &r = h->viterbi.dry[i];
+            r.n_steps = in[i].n_steps;
+            r.n_llr = n_llr_of(in[i]);
+            r.n_bits = psk::viterbi_bits(h->viterbi_code[in[i].code - 1u].K, in[i].n_steps, in[i].flags);
+            r.flags = PSK_SOFT_VITERBI_PLANNED | (in[i].flags << 1);
+        }
+        h->viterbi_called = true, h->viterbi_nframe = nframe;
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: whatever made the LLRs must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    // the frames in flight: one per workgroup, each with room for the longest frame's decisions, within the scratch bound
+    const uint32_t steps_cap = max_steps ? (max_steps + psk::kViterbiChunk - 1u) / psk::kViterbiChunk * psk::kViterbiChunk : psk::kViterbiChunk;
+    uint64_t grid = psk::kViterbiScratchWords / steps_cap;  // (steps_cap <= 65536: at least 512)
+    grid = grid < nframe ? grid : nframe;
+    grid = grid < 65535u ? grid : 65535u;
+    PSK_TRY(h->viterbi.grow(h->vpass, nframe));  // (the records are the last call's: nothing of them is kept)
+    auto &q = h->vpass.next();
+    PSK_TRY(h->vpass.claim(q, nframe, nframe / 4u + 256u));
+    for (uint32_t i = 0; i < nframe; i++) {
+        psk::ViterbiDesc &d = q.h_desc[i];
+        d = psk::ViterbiDesc{};
+        const psk_soft_viterbi_in_t &k = in[i];
+        if (viterbi_skipped(k))
+            continue;  // (its zero record)
+        d.llr = k.llr, d.out = k.out, d.n_steps = k.n_steps, d.code = k.code - 1u;
+        d.flags = psk::kViterbiData | (k.flags << 1);
+        d.n_llr = n_llr_of(k);
+    }
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = frames, tiles = workgroups)
+    return h->vpass.run(q, nframe, kAllRecords, grid * steps_cap, stream, [&]() -> psk_soft_status {
+        // the descriptors are up: the records are the new call's from here on, also if the launch below fails
+        h->viterbi_called = true, h->viterbi_nframe = nframe;
+        PSK_HIP(trace_launch(h, "viterbi", 0, 0, 0, nframe, grid, 0, 0, h->slot, stream));
+        PSK_HIP(psk::launch_viterbi(q.d_desc, nframe, (uint32_t)grid, steps_cap, h->d_viterbi_codes, q.d_part, h->viterbi.d, stream));
+        return PSK_SOFT_OK;
+    });
+}
+
+uint64_t psk_soft_viterbi_bytes(void) { return sizeof(psk_soft_viterbi_t); }
+uint64_t psk_soft_viterbi_in_bytes(void) { return sizeof(psk_soft_viterbi_in_t); }
+static_assert(sizeof(psk_soft_viterbi_t) == 64 && sizeof(psk_soft_viterbi_in_t) == 32, "include/psk_soft_hip.h states the sizes");
+static_assert(PSK_SOFT_VITERBI_DATA == psk::kViterbiData && PSK_SOFT_VITERBI_REC_PACKED == PSK_SOFT_VITERBI_PACKED << 1 &&
+                  PSK_SOFT_VITERBI_REC_TERMINATED == PSK_SOFT_VITERBI_TERMINATED << 1 &&
+                  PSK_SOFT_VITERBI_REC_ANY_START == PSK_SOFT_VITERBI_ANY_START << 1,
+              "the record's flags are the frame's shifted left by one");
+
+psk_soft_status psk_soft_get_viterbi(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_viterbi_t *rec)
+{
+    if (!h || !rec || !n || !h->viterbi_called || (uint64_t)first + n > h->viterbi_nframe)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_viterbi: null pointer, no psk_soft_viterbi_device call yet or a range beyond its frames");
+    return records_read(h, h->viterbi, h->vpass, first, n, rec);
+}
+
+uint64_t psk_soft_viterbi_count(uint32_t K, uint32_t n, uint32_t P, uint32_t keep, uint64_t n_steps)
+{
+    (void)K;
+    if (n < 2u || n > psk::kViterbiMaxN || !P || P > psk::kViterbiMaxP || n * P > 32u || !keep || (n * P < 32u && (keep >> (n * P))))
+        return 0;
+    return (n_steps / P) * psk::vt_popc(keep) + psk::vt_count(n, P, keep, (uint32_t)(n_steps % P));
+}
+
+psk_soft_status psk_soft_viterbi_encode_host(uint32_t K, uint32_t n, const uint32_t *g, uint32_t P, uint32_t keep, const uint8_t *bits,
+                                             uint32_t n_steps, uint8_t *code_bits_out)
+{
+    if (!g || !psk::vt_code_ok(K, n, g, P, keep) || (n_steps && (!bits || !code_bits_out)))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_viterbi_encode_host: null pointer or a code psk_soft_viterbi_define refuses");
+    const psk::ViterbiCode c = viterbi_code_make(K, n, g, P, keep);
+    uint32_t s = 0, phase = 0;
+    for (uint32_t t = 0; t < n_steps; t++) {
+        const uint32_t r = ((uint32_t)(bits[t] & 1u) << (K - 1u)) | s;
+        const uint32_t cb = psk::vt_code_bits(c, r), km = psk::vt_keep_of(n, keep, phase);
+        phase = psk::vt_next_phase(P, phase);
+        for (uint32_t j = 0; j < n; j++)
+            if ((km >> j) & 1u)
+                *code_bits_out++ = (uint8_t)((cb >> j) & 1u);
+        s = r >> 1;
+    }
+    return PSK_SOFT_OK;
+}
+
+psk_soft_status psk_soft_viterbi_host(uint32_t K, uint32_t n, const uint32_t *g, uint32_t P, uint32_t keep, const psk_soft_viterbi_in_t *in,
+                                      psk_soft_viterbi_t *rec)
+{
+    if (!g || !in || !rec || !psk::vt_code_ok(K, n, g, P, keep))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_viterbi_host: null pointer or a code psk_soft_viterbi_define refuses");
+    *rec = psk_soft_viterbi_t{};
+    if (viterbi_skipped(*in))
+        return PSK_SOFT_OK;
+    if (const char *what = viterbi_frame_fault(*in, K))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_viterbi_host: ") + what);
+    const psk::ViterbiCode c = viterbi_code_make(K, n, g, P, keep);
+    const uint32_t T = in->n_steps, NS = 1u << (K - 1u), mask = NS - 1u;
+    uint32_t bits0[64], bits1[64];
+    int32_t pm[64], nw[64];
+    for (uint32_t s = 0; s < NS; s++) {
+        bits0[s] = psk::vt_branch_bits(c, s, 0u), bits1[s] = psk::vt_branch_bits(c, s, 1u);
+        pm[s] = ((in->flags & PSK_SOFT_VITERBI_ANY_START) || s == 0u) ? 0 : psk::kViterbiUnreached;
+    }
+    // forward: the decisions of a step are one word, bit s the decision of state s
+    std::vector<uint64_t> dec(T);
+    const int8_t *q = in->llr;
+    uint32_t phase = 0;
+    for (uint32_t t = 0; t < T; t++) {
+        const uint32_t km = psk::vt_keep_of(n, keep, phase);
+        phase = psk::vt_next_phase(P, phase);
+        int32_t l[psk::kViterbiMaxN] = {};
+        for (uint32_t j = 0; j < n; j++)
+            if ((km >> j) & 1u)
+                l[j] = *q++;
+        uint64_t w = 0;
+        for (uint32_t s = 0; s < NS; s++) {
+            const uint32_t p0 = (s << 1) & mask;
+            uint32_t d;
+            nw[s] = psk::vt_acs(pm[p0], psk::vt_bm<psk::kViterbiMaxN>(bits0[s], l), pm[p0 | 1u], psk::vt_bm<psk::kViterbiMaxN>(bits1[s], l), &d);
+            w |= (uint64_t)d << s;
+        }
+        for (uint32_t s = 0; s < NS; s++) pm[s] = nw[s];
+        dec[t] = w;
+    }
+    const uint64_t n_llr = (uint64_t)(q - in->llr);
+    // the end state: 0, or the first maximum
+    uint32_t s = 0;
+    if (!(in->flags & PSK_SOFT_VITERBI_TERMINATED))
+        for (uint32_t k = 1; k < NS; k++)
+            if (pm[k] > pm[s])
+                s = k;
+    rec->end_state = s, rec->metric = pm[s];
+    // traceback; the path's code bits against the LLRs, walked from the back
+    const uint32_t n_bits = psk::viterbi_bits(K, T, in->flags);
+    const bool packed = (in->flags & PSK_SOFT_VITERBI_PACKED) != 0;
+    uint8_t *const out = (uint8_t *)in->out;
+    if (packed)
+        std::memset(out, 0, (n_bits + 7u) / 8u);
+    uint32_t sum_abs = 0, n_flip = 0, n_zero = 0;
+    for (uint32_t t = T; t-- > 0u;) {
+        const uint32_t u = s >> (K - 2u);
+        const uint32_t prev = ((s << 1) & mask) | (uint32_t)((dec[t] >> s) & 1u);
+        const uint32_t cb = psk::vt_code_bits(c, (u << (K - 1u)) | prev), km = psk::vt_keep_of(n, keep, t % P);
+        const int8_t *const lt = in->llr + psk::vt_count(n, P, keep, t);
+        for (uint32_t j = 0, k = 0; j < n; j++)
+            if ((km >> j) & 1u)
+                psk::vt_tally((int32_t)lt[k++], (cb >> j) & 1u, &sum_abs, &n_flip, &n_zero);
+        if (t < n_bits) {
+            if (packed)
+                out[t >> 3] |= (uint8_t)(u << (7u - (t & 7u)));
+            else
+                out[t] = (uint8_t)u;
+        }
+        s = prev;
+    }
+    rec->n_steps = T, rec->n_llr = n_llr;
+    rec->sum_abs = sum_abs, rec->n_flip = n_flip, rec->n_zero = n_zero;
+    rec->start_state = s, rec->n_bits = n_bits;
+    rec->flags = PSK_SOFT_VITERBI_DATA | (in->flags << 1);
     return PSK_SOFT_OK;
 }
 

@@ -326,6 +326,45 @@ class DemapRecord(ctypes.Structure):
     ]
 
 
+VITERBI_PACKED, VITERBI_TERMINATED, VITERBI_ANY_START = 1, 2, 4  # ViterbiIn.flags
+# ViterbiRecord.flags: DATA or PLANNED, ORed with the frame's flags shifted left by one
+VITERBI_DATA, VITERBI_REC_PACKED, VITERBI_REC_TERMINATED, VITERBI_REC_ANY_START, VITERBI_PLANNED = 1, 2, 4, 8, 128
+VITERBI_SLOTS, VITERBI_MAX_FRAMES, VITERBI_MAX_STEPS, VITERBI_SCRATCH_BYTES = 16, 1 << 20, 65536, 256 << 20
+
+
+class ViterbiIn(ctypes.Structure):
+    """psk_soft_viterbi_in_t: one frame of a viterbi_device call -- a DEVICE pointer to its int8 LLRs (any alignment), a DEVICE
+    pointer to its output, the trellis steps, code = 1 + the slot of the code (0: skipped) and flags (VITERBI_PACKED,
+    VITERBI_TERMINATED, VITERBI_ANY_START)."""
+
+    _fields_ = [
+        ("llr", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("n_steps", ctypes.c_uint32),
+        ("code", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32),
+    ]
+
+
+class ViterbiRecord(ctypes.Structure):
+    """psk_soft_viterbi_t: the record of one frame of the last viterbi_device call."""
+
+    _fields_ = [
+        ("n_steps", ctypes.c_uint64),
+        ("n_llr", ctypes.c_uint64),
+        ("metric", ctypes.c_int64),
+        ("sum_abs", ctypes.c_int64),
+        ("n_flip", ctypes.c_uint32),
+        ("n_zero", ctypes.c_uint32),
+        ("end_state", ctypes.c_uint32),
+        ("start_state", ctypes.c_uint32),
+        ("n_bits", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 2),
+    ]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_hip.h declares
@@ -402,6 +441,14 @@ EXPORTS = (
     "psk_soft_demap_bytes",
     "psk_soft_demap_in_bytes",
     "psk_soft_demap_piece",
+    "psk_soft_viterbi_define",
+    "psk_soft_viterbi_device",
+    "psk_soft_get_viterbi",
+    "psk_soft_viterbi_host",
+    "psk_soft_viterbi_encode_host",
+    "psk_soft_viterbi_count",
+    "psk_soft_viterbi_bytes",
+    "psk_soft_viterbi_in_bytes",
     "psk_soft_process_host",
     "psk_soft_synchronize",
     "psk_soft_join",
@@ -551,6 +598,17 @@ def load():
     L.psk_soft_demap_in_bytes.restype = u64
     L.psk_soft_demap_piece.argtypes = []
     L.psk_soft_demap_piece.restype = u32
+    L.psk_soft_viterbi_define.argtypes = [vp, u32, u32, u32, vp, u32, u32]
+    L.psk_soft_viterbi_device.argtypes = [vp, u32, ctypes.POINTER(ViterbiIn), vp]
+    L.psk_soft_get_viterbi.argtypes = [vp, u32, u32, ctypes.POINTER(ViterbiRecord)]
+    L.psk_soft_viterbi_host.argtypes = [u32, u32, vp, u32, u32, ctypes.POINTER(ViterbiIn), ctypes.POINTER(ViterbiRecord)]
+    L.psk_soft_viterbi_encode_host.argtypes = [u32, u32, vp, u32, u32, vp, u32, vp]
+    L.psk_soft_viterbi_count.argtypes = [u32, u32, u32, u32, u64]
+    L.psk_soft_viterbi_count.restype = u64
+    L.psk_soft_viterbi_bytes.argtypes = []
+    L.psk_soft_viterbi_bytes.restype = u64
+    L.psk_soft_viterbi_in_bytes.argtypes = []
+    L.psk_soft_viterbi_in_bytes.restype = u64
     _lib = L
     return L
 
@@ -856,6 +914,47 @@ def demap_piece():
 
 def _demap_in(s):
     return s if isinstance(s, DemapIn) else DemapIn(*s)
+
+
+def _viterbi_polys(g):
+    return np.ascontiguousarray(g, np.uint32).reshape(-1)
+
+
+def viterbi_count(K, g, P, keep, n_steps):
+    """psk_soft_viterbi_count: the LLRs (kept code bits) of a frame of n_steps steps of the code (K, polynomials g, puncture
+    period P, keep mask); 0 for a puncture pattern psk_soft_viterbi_define refuses."""
+    return int(load().psk_soft_viterbi_count(int(K), int(_viterbi_polys(g).size), int(P), int(keep), int(n_steps)))
+
+
+def viterbi_encode(K, g, P, keep, bits):
+    """psk_soft_viterbi_encode_host: the code bits (uint8 0 / 1, punctured, in order of (t, j)) of the input bits, from state 0;
+    a terminated frame's K-1 zeros are the caller's to append."""
+    pol = _viterbi_polys(g)
+    u = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+    out = np.zeros(max(viterbi_count(K, pol, P, keep, u.size), 1), np.uint8)
+    _check(load().psk_soft_viterbi_encode_host(int(K), int(pol.size), pol.ctypes.data if pol.size else None, int(P), int(keep),
+                                               u.ctypes.data if u.size else None, int(u.size), out.ctypes.data))
+    return out[: viterbi_count(K, pol, P, keep, u.size)]
+
+
+def viterbi_host(K, g, P, keep, llr, n_steps, flags=0):
+    """psk_soft_viterbi_host: one frame on the host.  llr: the frame's int8 LLRs (at least viterbi_count of them).  Returns (the
+    output bytes: n_bits uint8, or ceil(n_bits / 8) with VITERBI_PACKED, the ViterbiRecord)."""
+    pol = _viterbi_polys(g)
+    x = np.ascontiguousarray(llr, np.int8).reshape(-1)
+    if x.size < viterbi_count(K, pol, P, keep, n_steps):
+        raise ValueError("fewer LLRs than the frame's steps hold")
+    out = np.zeros(int(n_steps) + 8, np.uint8)
+    k = ViterbiIn(x.ctypes.data if x.size else out.ctypes.data, out.ctypes.data, int(n_steps), 1, int(flags), 0)
+    rec = ViterbiRecord()
+    _check(load().psk_soft_viterbi_host(int(K), int(pol.size), pol.ctypes.data if pol.size else None, int(P), int(keep), ctypes.byref(k),
+                                        ctypes.byref(rec)))
+    n = int(rec.n_bits)
+    return out[: (n + 7) // 8 if flags & VITERBI_PACKED else n].copy(), rec
+
+
+def _viterbi_in(s):
+    return s if isinstance(s, ViterbiIn) else ViterbiIn(*s)
 
 
 class Handle:
@@ -1292,6 +1391,30 @@ class Handle:
         n = int(n)
         arr = (DemapRecord * n)()
         _check(self._L.psk_soft_get_demap(self._h, int(first), n, arr))
+        return arr
+
+    def viterbi_define(self, slot, K, g, P=1, keep=None):
+        """psk_soft_viterbi_define: the code of slot `slot` (0 .. 15) -- constraint length K, the polynomials g, the puncture period
+        P and keep mask (None: every bit kept), copied; a frame names it as ViterbiIn.code = slot + 1."""
+        pol = _viterbi_polys(g)
+        if keep is None:
+            keep = (1 << (int(pol.size) * int(P))) - 1
+        _check(self._L.psk_soft_viterbi_define(self._h, int(slot), int(K), int(pol.size), pol.ctypes.data if pol.size else None, int(P),
+                                               int(keep) & 0xFFFFFFFF))
+
+    def viterbi_device(self, ins, stream=None):
+        """Frames of int8 LLRs as payload bits (psk_soft_viterbi_device): writes n_bits bytes (or ceil(n_bits / 8) with
+        VITERBI_PACKED) per frame to its `out` and leaves a ViterbiRecord per frame; touches no demodulator state.  ins: a ctypes
+        ViterbiIn array or a sequence of ViterbiIn / tuples in field order."""
+        if not isinstance(ins, ctypes.Array):
+            ins = (ViterbiIn * len(ins))(*[_viterbi_in(s) for s in ins])
+        _check(self._L.psk_soft_viterbi_device(self._h, len(ins), ins, ctypes.c_void_p(stream or 0)))
+
+    def viterbi_records(self, first=0, n=1):
+        """The ViterbiRecord records of the frames [first, first + n) of the last viterbi_device call (psk_soft_get_viterbi), a
+        ctypes array; waits for that call."""
+        arr = (ViterbiRecord * n)()
+        _check(self._L.psk_soft_get_viterbi(self._h, int(first), n, arr))
         return arr
 
     def sync_history(self, ch):
