@@ -1092,6 +1092,11 @@ uint64_t psk_soft_viterbi_count(uint32_t K, uint32_t n, uint32_t P, uint32_t kee
 uint64_t psk_soft_viterbi_bytes(void);      /* sizeof(psk_soft_viterbi_t), for bindings */
 uint64_t psk_soft_viterbi_in_bytes(void);   /* sizeof(psk_soft_viterbi_in_t), for bindings */
 
+/* ---- frames as corrected bytes: Reed-Solomon decoding of byte frames ----------------------------------------------------------------
+ * The outer code behind the decoder above: the psk_soft_rs_ family -- its definition, structs and seven entries -- is declared in
+ * psk_soft_rs.h, which this header includes here, so that one include still declares the whole interface. */
+#include "psk_soft_rs.h"
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

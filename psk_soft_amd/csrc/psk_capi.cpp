@@ -27,6 +27,7 @@
 #include "psk_sync.h"
 #include "psk_demap.h"
 #include "psk_viterbi.h"
+#include "psk_rs.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -885,6 +886,16 @@ struct psk_soft_handle {
     bool viterbi_called = false;
     uint32_t viterbi_nframe = 0;  // of the last call
     PassRing<psk::ViterbiDesc, uint64_t, 2> vpass;
+    // psk_soft_rs_device: the codes of every slot (kRsSlots RsCode, allocated at the first psk_soft_rs_define; gfpoly 0: never
+    // defined), their masks (kRsMaskStride bytes a slot) and the codes' copy on the host; one record per frame of the last call,
+    // grown on demand -- a control-plane-only handle keeps them on the host --; its pass has no partials
+    DeviceBuf<psk::RsCode> d_rs_codes;
+    DeviceBuf<uint8_t> d_rs_masks;
+    psk::RsCode rs_code[psk::kRsSlots] = {};
+    Records<psk_soft_rs_t> rs;
+    bool rs_called = false;
+    uint32_t rs_nframe = 0;  // of the last call
+    PassRing<psk::RsDesc, uint32_t, 2> rpass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     std::unique_ptr<CopyPool> pool;
@@ -4514,6 +4525,272 @@ psk_soft_status psk_soft_viterbi_host(uint32_t K, uint32_t n, const uint32_t *g,
     rec->sum_abs = sum_abs, rec->n_flip = n_flip, rec->n_zero = n_zero;
     rec->start_state = s, rec->n_bits = n_bits;
     rec->flags = PSK_SOFT_VITERBI_DATA | (in->flags << 1);
+    return PSK_SOFT_OK;
+}
+
+// ---- psk_soft_rs_device: frames of bytes as corrected bytes (include/psk_soft_rs.h, psk_rs.hip) ----
+// Behind the viterbi call: one launch on the caller's stream, one wave per frame, one record per frame of the call; a ring of its
+// own like the decoder's, without partials.  Nothing of the control plane, of the demodulator's state or of any other record is
+// read or written.
+static psk::RsCode rs_code_make(uint32_t gfpoly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n, uint32_t depth, uint32_t mask_len)
+{
+    psk::RsCode c = {};
+    c.gfpoly = gfpoly, c.fcr = fcr, c.prim = prim, c.nroots = nroots, c.n = n, c.depth = depth, c.mask_len = mask_len;
+    return c;
+}
+
+static const char *const kRsCodeFault =
+    "null pointer, a slot above 15, gfpoly outside 0x100 .. 0x1ff or not primitive, fcr above 254, prim outside 1 .. 254 or not coprime to "
+    "255, nroots outside 2 .. 64, n outside nroots + 1 .. 255, depth outside 1 .. 8, mask_len above n depth or a null mask with mask_len > 0";
+
+psk_soft_status psk_soft_rs_define(psk_soft_handle_t *h, uint32_t slot, uint32_t gfpoly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n,
+                                   uint32_t depth, const uint8_t *mask, uint32_t mask_len)
+{
+    if (!h || slot >= psk::kRsSlots || !psk::rs_code_ok(gfpoly, fcr, prim, nroots, n, depth, mask_len) || (mask_len && !mask))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_rs_define: ") + kRsCodeFault);
+    const psk::RsCode c = rs_code_make(gfpoly, fcr, prim, nroots, n, depth, mask_len);
+    if (!h->dry) {
+        PSK_HIP(hipSetDevice(h->device));
+        if (!h->d_rs_codes)
+            PSK_TRY(alloc_zeroed(h->d_rs_codes, psk::kRsSlots, "rs codes"));
+        if (!h->d_rs_masks)
+            PSK_TRY(alloc_zeroed(h->d_rs_masks, (size_t)psk::kRsSlots * psk::kRsMaskStride, "rs masks"));
+        PSK_TRY(h->rpass.wait());  // (no launch is still reading the slot)
+        if (mask_len)
+            PSK_HIP(hipMemcpy(h->d_rs_masks + (size_t)slot * psk::kRsMaskStride, mask, mask_len, hipMemcpyHostToDevice));
+        PSK_HIP(hipMemcpy(h->d_rs_codes + slot, &c, sizeof c, hipMemcpyHostToDevice));
+    }
+    h->rs_code[slot] = c;
+    return PSK_SOFT_OK;
+}
+
+static bool rs_skipped(const psk_soft_rs_in_t &k) { return !k.code || !k.in; }
+
+// what is wrong with a frame that is not skipped; nullptr: nothing
+static const char *rs_frame_fault(const psk_soft_rs_in_t &k)
+{
+    if (k.flags & ~psk::kRsFlagMask)
+        return "unknown flag bits";
+    if (k.pad[0] || k.pad[1])
+        return "pad must be zero";
+    if (!k.out)
+        return "out is null";
+    return nullptr;
+}
+
+psk_soft_status psk_soft_rs_device(psk_soft_handle_t *h, uint32_t nframe, const psk_soft_rs_in_t *in, void *stream_v)
+{
+    if (!h || !in || !nframe || nframe > psk::kRsMaxFrames)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_rs_device: null pointer or a number of frames outside 1 .. 2^20");
+    // the refusals, before anything is enqueued or any record changes
+    for (uint32_t i = 0; i < nframe; i++) {
+        const psk_soft_rs_in_t &k = in[i];
+        if (rs_skipped(k))
+            continue;
+        const char *what = nullptr;
+        if (k.code > psk::kRsSlots || !h->rs_code[k.code - 1u].gfpoly)
+            what = "a code slot above 15 or never defined (psk_soft_rs_define)";
+        else
+            what = rs_frame_fault(k);
+        if (what) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "psk_soft_rs_device: frame %u: %s", i, what);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+    }
+    if (h->dry) {
+        h->rs.dry.assign(nframe, psk_soft_rs_t{});
+        for (uint32_t i = 0; i < nframe; i++) {
+            if (rs_skipped(in[i]))
+                continue;
+            const psk::RsCode &c = h->rs_code[in[i].code - 1u];
+            psk_soft_rs_t &r = h->rs.dry[i];
+            r.n = (uint16_t)c.n, r.k = (uint16_t)(c.n - c.nroots), r.depth = (uint8_t)c.depth, r.nroots = (uint8_t)c.nroots;
+            r.flags = PSK_SOFT_RS_PLANNED | (in[i].flags << 1);
+        }
+        h->rs_called = true, h->rs_nframe = nframe;
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: whatever made the bytes must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    const uint32_t grid = nframe < psk::kRsMaxGrid ? nframe : psk::kRsMaxGrid;
+    PSK_TRY(h->rs.grow(h->rpass, nframe));  // (the records are the last call's: nothing of them is kept)
+    auto &q = h->rpass.next();
+    PSK_TRY(h->rpass.claim(q, nframe, nframe / 4u + 256u));
+    for (uint32_t i = 0; i < nframe; i++) {
+        psk::RsDesc &d = q.h_desc[i];
+        d = psk::RsDesc{};
+        const psk_soft_rs_in_t &k = in[i];
+        if (rs_skipped(k))
+            continue;  // (its zero record)
+        d.in = k.in, d.out = k.out, d.code = k.code - 1u;
+        d.flags = psk::kRsData | (k.flags << 1);
+    }
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = frames, tiles = workgroups)
+    return h->rpass.run(q, nframe, kAllRecords, 0, stream, [&]() -> psk_soft_status {
+        // the descriptors are up: the records are the new call's from here on, also if the launch below fails
+        h->rs_called = true, h->rs_nframe = nframe;
+        PSK_HIP(trace_launch(h, "rs", 0, 0, 0, nframe, grid, 0, 0, h->slot, stream));
+        PSK_HIP(psk::launch_rs(q.d_desc, nframe, grid, h->d_rs_codes, h->d_rs_masks, h->rs.d, stream));
+        return PSK_SOFT_OK;
+    });
+}
+
+uint64_t psk_soft_rs_bytes(void) { return sizeof(psk_soft_rs_t); }
+uint64_t psk_soft_rs_in_bytes(void) { return sizeof(psk_soft_rs_in_t); }
+static_assert(sizeof(psk_soft_rs_t) == 64 && sizeof(psk_soft_rs_in_t) == 32, "include/psk_soft_rs.h states the sizes");
+static_assert(offsetof(psk_soft_rs_t, n_err) == 16 && offsetof(psk_soft_rs_t, n_bit) == 24 && offsetof(psk_soft_rs_t, depth) == 8,
+              "psk_rs.hip stores the record as eight words");
+static_assert(PSK_SOFT_RS_DATA == psk::kRsData && PSK_SOFT_RS_REC_WITH_PARITY == PSK_SOFT_RS_WITH_PARITY << 1,
+              "the record's flags are the frame's shifted left by one");
+
+psk_soft_status psk_soft_get_rs(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_rs_t *rec)
+{
+    if (!h || !rec || !n || !h->rs_called || (uint64_t)first + n > h->rs_nframe)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_get_rs: null pointer, no psk_soft_rs_device call yet or a range beyond its frames");
+    return records_read(h, h->rs, h->rpass, first, n, rec);
+}
+
+// the generator g(x) = prod (x - root m), g[d] the coefficient of x^d, d = 0 .. nroots
+static void rs_generator(const psk::RsCode &c, uint8_t *g)
+{
+    g[0] = 1;
+    for (uint32_t m = 0; m < c.nroots; m++) {
+        const uint32_t root = psk::rs_root(c, m);
+        g[m + 1u] = 0;
+        for (uint32_t d = m + 1u; d > 0u; d--) g[d] = (uint8_t)(g[d - 1u] ^ psk::gf_mul(c.gfpoly, g[d], root));
+        g[0] = (uint8_t)psk::gf_mul(c.gfpoly, g[0], root);
+    }
+}
+
+psk_soft_status psk_soft_rs_encode_host(uint32_t gfpoly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n, uint32_t depth,
+                                        const uint8_t *mask, uint32_t mask_len, const uint8_t *data, uint8_t *frame_out)
+{
+    if (!data || !frame_out || !psk::rs_code_ok(gfpoly, fcr, prim, nroots, n, depth, mask_len) || (mask_len && !mask))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_rs_encode_host: ") + kRsCodeFault);
+    const psk::RsCode c = rs_code_make(gfpoly, fcr, prim, nroots, n, depth, mask_len);
+    const uint32_t k = n - nroots;
+    uint8_t g[psk::kRsMaxRoots + 1u];
+    rs_generator(c, g);
+    for (uint32_t j = 0; j < depth; j++) {
+        uint8_t par[psk::kRsMaxRoots] = {};  // par[d]: the coefficient of x^d of the remainder so far
+        for (uint32_t i = 0; i < k; i++) {
+            const uint8_t b = data[i * depth + j];
+            frame_out[i * depth + j] = b;
+            const uint32_t fb = b ^ par[nroots - 1u];
+            for (uint32_t d = nroots - 1u; d > 0u; d--) par[d] = (uint8_t)(par[d - 1u] ^ psk::gf_mul(gfpoly, fb, g[d]));
+            par[0] = (uint8_t)psk::gf_mul(gfpoly, fb, g[0]);
+        }
+        for (uint32_t i = 0; i < nroots; i++) frame_out[(k + i) * depth + j] = par[nroots - 1u - i];
+    }
+    for (uint32_t q = 0; q < mask_len; q++) frame_out[q] ^= mask[q];
+    return PSK_SOFT_OK;
+}
+
+// One received word w[0 .. n-1] corrected in place, the definition on the host: syndromes, Berlekamp-Massey, a search of the n
+// positions, Forney, and the outcome held to the definition.  Returns the number of bytes changed, or kRsFailed with w unchanged.
+static uint32_t rs_decode_word(const psk::RsCode &c, uint8_t *w, uint32_t *n_bit)
+{
+    const uint32_t gp = c.gfpoly, nroots = c.nroots, n = c.n, t = nroots / 2u;
+    *n_bit = 0;
+    uint8_t S[psk::kRsMaxRoots], root[psk::kRsMaxRoots];
+    uint32_t any = 0;
+    for (uint32_t m = 0; m < nroots; m++) {
+        root[m] = (uint8_t)psk::rs_root(c, m);
+        uint32_t s = 0;
+        for (uint32_t i = 0; i < n; i++) s = psk::gf_mul(gp, s, root[m]) ^ w[i];
+        S[m] = (uint8_t)s, any |= s;
+    }
+    if (!any)
+        return 0;
+    uint8_t lam[psk::kRsMaxRoots + 2u] = {1}, B[psk::kRsMaxRoots + 2u] = {1}, T[psk::kRsMaxRoots + 2u];
+    uint32_t len = 0;
+    for (uint32_t r = 0; r < nroots; r++) {
+        uint32_t delta = 0;
+        for (uint32_t i = 0; i <= r; i++) delta ^= psk::gf_mul(gp, lam[i], S[r - i]);
+        for (uint32_t d = nroots + 1u; d > 0u; d--) B[d] = B[d - 1u];  // x B
+        B[0] = 0;
+        if (!delta)
+            continue;
+        for (uint32_t d = 0; d <= nroots + 1u; d++) T[d] = (uint8_t)(lam[d] ^ psk::gf_mul(gp, delta, B[d]));
+        if (2u * len <= r) {
+            const uint32_t inv = psk::gf_inv(gp, delta);
+            for (uint32_t d = 0; d <= nroots + 1u; d++) B[d] = (uint8_t)psk::gf_mul(gp, lam[d], inv);
+            len = r + 1u - len;
+        }
+        std::memcpy(lam, T, sizeof T);
+    }
+    uint32_t deg = 0;
+    for (uint32_t d = 0; d <= nroots + 1u; d++)
+        if (lam[d])
+            deg = d;
+    if (len > t || deg != len)
+        return psk::kRsFailed;
+    uint8_t om[psk::kRsMaxRoots] = {};
+    for (uint32_t L = 0; L < deg; L++)
+        for (uint32_t i = 0; i <= L; i++) om[L] ^= (uint8_t)psk::gf_mul(gp, lam[i], S[L - i]);
+    uint8_t e[255] = {};
+    uint32_t nroot = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t p = n - 1u - i, xinv = psk::rs_locator_inv(c, p);
+        uint32_t lamv = 0, omv = 0, der = 0, xp = 1u, xprev = 0u;
+        for (uint32_t d = 0; d <= deg; d++) {
+            lamv ^= psk::gf_mul(gp, lam[d], xp);
+            omv ^= d < deg ? psk::gf_mul(gp, om[d], xp) : 0u;
+            der ^= (d & 1u) ? psk::gf_mul(gp, lam[d], xprev) : 0u;
+            xprev = xp;
+            xp = psk::gf_mul(gp, xp, xinv);
+        }
+        if (lamv)
+            continue;
+        nroot++;
+        const uint32_t v = der ? psk::rs_magnitude(c, p, omv, der) : 0u;
+        if (!v)
+            return psk::kRsFailed;
+        e[i] = (uint8_t)v;
+    }
+    if (nroot != deg)
+        return psk::kRsFailed;
+    for (uint32_t m = 0; m < nroots; m++) {  // the pattern's syndromes are the word's
+        uint32_t s = 0;
+        for (uint32_t i = 0; i < n; i++) s = psk::gf_mul(gp, s, root[m]) ^ e[i];
+        if (s != S[m])
+            return psk::kRsFailed;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        w[i] ^= e[i];
+        *n_bit += (uint32_t)__builtin_popcount(e[i]);
+    }
+    return deg;
+}
+
+psk_soft_status psk_soft_rs_host(uint32_t gfpoly, uint32_t fcr, uint32_t prim, uint32_t nroots, uint32_t n, uint32_t depth, const uint8_t *mask,
+                                 uint32_t mask_len, const psk_soft_rs_in_t *in, psk_soft_rs_t *rec)
+{
+    if (!in || !rec || !psk::rs_code_ok(gfpoly, fcr, prim, nroots, n, depth, mask_len) || (mask_len && !mask))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_rs_host: ") + kRsCodeFault);
+    *rec = psk_soft_rs_t{};
+    if (rs_skipped(*in))
+        return PSK_SOFT_OK;
+    if (const char *what = rs_frame_fault(*in))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_rs_host: ") + what);
+    const psk::RsCode c = rs_code_make(gfpoly, fcr, prim, nroots, n, depth, mask_len);
+    const uint32_t k = n - nroots, n_out = (in->flags & PSK_SOFT_RS_WITH_PARITY) ? n : k;
+    for (uint32_t j = 0; j < depth; j++) {
+        uint8_t w[255];
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t off = i * depth + j;
+            w[i] = (uint8_t)(in->in[off] ^ (off < mask_len ? mask[off] : 0u));
+        }
+        uint32_t n_bit = 0;
+        rec->n_err[j] = (uint8_t)rs_decode_word(c, w, &n_bit);
+        rec->n_bit[j] = (uint16_t)n_bit;
+        for (uint32_t i = 0; i < n_out; i++) in->out[i * depth + j] = w[i];
+    }
+    rec->n = (uint16_t)n, rec->k = (uint16_t)k, rec->depth = (uint8_t)depth, rec->nroots = (uint8_t)nroots;
+    rec->flags = PSK_SOFT_RS_DATA | (in->flags << 1);
     return PSK_SOFT_OK;
 }
 

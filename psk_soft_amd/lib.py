@@ -365,7 +365,72 @@ class ViterbiRecord(ctypes.Structure):
     ]
 
 
+RS_WITH_PARITY = 1  # RsIn.flags
+# RsRecord.flags: DATA or PLANNED, ORed with the frame's flags shifted left by one
+RS_DATA, RS_REC_WITH_PARITY, RS_PLANNED = 1, 2, 128
+RS_SLOTS, RS_MAX_FRAMES, RS_MAX_DEPTH, RS_MAX_ROOTS, RS_FAILED = 16, 1 << 20, 8, 64, 255
+# the usual parameter sets: (gfpoly, fcr, prim, nroots, n)
+RS_CCSDS = (0x187, 112, 11, 32, 255)
+RS_DVB = (0x11D, 0, 1, 16, 204)
+
+
+class RsIn(ctypes.Structure):
+    """psk_soft_rs_in_t: one frame of an rs_device call -- a DEVICE pointer to its n * depth bytes (any alignment), a DEVICE
+    pointer to its output, code = 1 + the slot of the code (0: skipped) and flags (RS_WITH_PARITY)."""
+
+    _fields_ = [
+        ("in_", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("code", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 2),
+    ]
+
+
+class RsRecord(ctypes.Structure):
+    """psk_soft_rs_t: the record of one frame of the last rs_device call.  The C record has no per-frame totals; the properties
+    here sum over the frame's codewords."""
+
+    _fields_ = [
+        ("flags", ctypes.c_uint32),
+        ("n", ctypes.c_uint16),
+        ("k", ctypes.c_uint16),
+        ("depth", ctypes.c_uint8),
+        ("nroots", ctypes.c_uint8),
+        ("pad0", ctypes.c_uint8 * 6),
+        ("n_err", ctypes.c_uint8 * 8),
+        ("n_bit", ctypes.c_uint16 * 8),
+        ("pad1", ctypes.c_uint8 * 24),
+    ]
+
+    @property
+    def failed(self):
+        """codewords of the frame that could not be corrected"""
+        return sum(1 for j in range(self.depth) if self.n_err[j] == RS_FAILED)
+
+    @property
+    def corrected_bytes(self):
+        """bytes corrected over the frame's codewords that decoded"""
+        return sum(self.n_err[j] for j in range(self.depth) if self.n_err[j] != RS_FAILED)
+
+    @property
+    def corrected_bits(self):
+        """bits corrected over the frame's codewords that decoded"""
+        return sum(self.n_bit[j] for j in range(self.depth))
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
+
+# every symbol include/psk_soft_rs.h declares (the psk_soft_rs_ family; psk_soft_hip.h includes that header)
+RS_EXPORTS = (
+    "psk_soft_rs_define",
+    "psk_soft_rs_device",
+    "psk_soft_get_rs",
+    "psk_soft_rs_host",
+    "psk_soft_rs_encode_host",
+    "psk_soft_rs_bytes",
+    "psk_soft_rs_in_bytes",
+)
 
 # every symbol include/psk_soft_hip.h declares
 EXPORTS = (
@@ -609,6 +674,15 @@ def load():
     L.psk_soft_viterbi_bytes.restype = u64
     L.psk_soft_viterbi_in_bytes.argtypes = []
     L.psk_soft_viterbi_in_bytes.restype = u64
+    L.psk_soft_rs_define.argtypes = [vp, u32, u32, u32, u32, u32, u32, u32, vp, u32]
+    L.psk_soft_rs_device.argtypes = [vp, u32, ctypes.POINTER(RsIn), vp]
+    L.psk_soft_get_rs.argtypes = [vp, u32, u32, ctypes.POINTER(RsRecord)]
+    L.psk_soft_rs_host.argtypes = [u32, u32, u32, u32, u32, u32, vp, u32, ctypes.POINTER(RsIn), ctypes.POINTER(RsRecord)]
+    L.psk_soft_rs_encode_host.argtypes = [u32, u32, u32, u32, u32, u32, vp, u32, vp, vp]
+    L.psk_soft_rs_bytes.argtypes = []
+    L.psk_soft_rs_bytes.restype = u64
+    L.psk_soft_rs_in_bytes.argtypes = []
+    L.psk_soft_rs_in_bytes.restype = u64
     _lib = L
     return L
 
@@ -955,6 +1029,48 @@ def viterbi_host(K, g, P, keep, llr, n_steps, flags=0):
 
 def _viterbi_in(s):
     return s if isinstance(s, ViterbiIn) else ViterbiIn(*s)
+
+
+def _rs_mask(mask):
+    m = np.zeros(0, np.uint8) if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+    return m, (m.ctypes.data if m.size else None)
+
+
+def rs_encode_host(gfpoly, fcr, prim, nroots, n, depth, data, mask=None):
+    """psk_soft_rs_encode_host: the frame (n * depth uint8) of the (n - nroots) * depth data bytes -- data[i * depth + j] is byte i
+    of codeword j --, systematic, interleaved, the mask (None: none) applied."""
+    m, mp = _rs_mask(mask)
+    k = int(n) - int(nroots)
+    d = np.ascontiguousarray(data, np.uint8).reshape(-1)
+    if k > 0 and 1 <= int(depth) <= RS_MAX_DEPTH and d.size != k * int(depth):
+        raise ValueError("data must hold (n - nroots) * depth bytes")
+    out = np.zeros(255 * RS_MAX_DEPTH, np.uint8)
+    _check(load().psk_soft_rs_encode_host(int(gfpoly), int(fcr), int(prim), int(nroots), int(n), int(depth), mp, int(m.size),
+                                          d.ctypes.data if d.size else None, out.ctypes.data))
+    return out[: int(n) * int(depth)].copy()
+
+
+def rs_host(gfpoly, fcr, prim, nroots, n, depth, frame, mask=None, flags=0):
+    """psk_soft_rs_host: one frame on the host.  frame: its n * depth bytes.  Returns (the output bytes: (n - nroots) * depth
+    uint8, or n * depth with RS_WITH_PARITY, the RsRecord)."""
+    m, mp = _rs_mask(mask)
+    x = np.ascontiguousarray(frame, np.uint8).reshape(-1)
+    if 1 <= int(n) <= 255 and 1 <= int(depth) <= RS_MAX_DEPTH and x.size < int(n) * int(depth):
+        raise ValueError("fewer bytes than the frame holds")
+    out = np.zeros(255 * RS_MAX_DEPTH, np.uint8)
+    k = RsIn(x.ctypes.data if x.size else out.ctypes.data, out.ctypes.data, 1, int(flags), (ctypes.c_uint32 * 2)(0, 0))
+    rec = RsRecord()
+    _check(load().psk_soft_rs_host(int(gfpoly), int(fcr), int(prim), int(nroots), int(n), int(depth), mp, int(m.size), ctypes.byref(k),
+                                   ctypes.byref(rec)))
+    nb = int(rec.n if flags & RS_WITH_PARITY else rec.k) * int(rec.depth)
+    return out[:nb].copy(), rec
+
+
+def _rs_in(s):
+    if isinstance(s, RsIn):
+        return s
+    s = tuple(s)
+    return RsIn(s[0], s[1], s[2], s[3] if len(s) > 3 else 0, (ctypes.c_uint32 * 2)(0, 0))
 
 
 class Handle:
@@ -1415,6 +1531,29 @@ class Handle:
         ctypes array; waits for that call."""
         arr = (ViterbiRecord * n)()
         _check(self._L.psk_soft_get_viterbi(self._h, int(first), n, arr))
+        return arr
+
+    def rs_define(self, slot, gfpoly, fcr, prim, nroots, n=255, depth=1, mask=None):
+        """psk_soft_rs_define: the Reed-Solomon code of slot `slot` (0 .. 15) -- the field polynomial, first consecutive root, the
+        primitive element's power, the number of roots, the codeword length n (below 255: shortened), the interleave depth and
+        the derandomiser mask (None: none), copied; a frame names it as RsIn.code = slot + 1."""
+        m, mp = _rs_mask(mask)
+        _check(self._L.psk_soft_rs_define(self._h, int(slot), int(gfpoly), int(fcr), int(prim), int(nroots), int(n), int(depth), mp,
+                                          int(m.size)))
+
+    def rs_device(self, ins, stream=None):
+        """Frames of bytes as corrected bytes (psk_soft_rs_device): writes (n - nroots) * depth bytes (or n * depth with
+        RS_WITH_PARITY) per frame to its `out` and leaves an RsRecord per frame; touches no demodulator state.  ins: a ctypes
+        RsIn array or a sequence of RsIn / tuples (in, out, code[, flags])."""
+        if not isinstance(ins, ctypes.Array):
+            ins = (RsIn * len(ins))(*[_rs_in(s) for s in ins])
+        _check(self._L.psk_soft_rs_device(self._h, len(ins), ins, ctypes.c_void_p(stream or 0)))
+
+    def get_rs(self, first=0, n=1):
+        """The RsRecord records of the frames [first, first + n) of the last rs_device call (psk_soft_get_rs), a ctypes array;
+        waits for that call."""
+        arr = (RsRecord * n)()
+        _check(self._L.psk_soft_get_rs(self._h, int(first), n, arr))
         return arr
 
     def sync_history(self, ch):
