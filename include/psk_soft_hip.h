@@ -1097,6 +1097,11 @@ uint64_t psk_soft_viterbi_in_bytes(void);   /* sizeof(psk_soft_viterbi_in_t), fo
  * psk_soft_rs.h, which this header includes here, so that one include still declares the whole interface. */
 #include "psk_soft_rs.h"
 
+/* ---- frames as aligned bytes: between the decoder and the outer code ----------------------------------------------------------------
+ * The psk_soft_frame_ family -- the word search in the decoded bits and the cut of aligned, deinterleaved byte frames -- is declared
+ * in psk_soft_frame.h, included here in the same way. */
+#include "psk_soft_frame.h"
+
 /* Force every channel through the reference-order (sequential) kernel: 1 on, 0 off. */
 psk_soft_status psk_soft_set_force_sequential(psk_soft_handle_t *h, int on);
 

@@ -28,6 +28,7 @@
 #include "psk_demap.h"
 #include "psk_viterbi.h"
 #include "psk_rs.h"
+#include "psk_frame.h"
 #include "psk_ctl.h"
 #include "psk_gather.h"
 #include "psk_plan.h"
@@ -896,6 +897,22 @@ struct psk_soft_handle {
     bool rs_called = false;
     uint32_t rs_nframe = 0;  // of the last call
     PassRing<psk::RsDesc, uint32_t, 2> rpass;
+    // psk_soft_frame_search_device: the words of every slot (on the host: a stream's descriptor carries its word; length 0: never
+    // defined); one record per stream of the last call; a ring of two passes with the fold's partials.
+    psk::FrameWord frame_word[psk::kFrameSlots] = {};
+    Records<psk_soft_frame_search_t> fsearch;
+    bool fsearch_called = false;
+    uint32_t fsearch_n = 0;  // streams of the last call
+    PassRing<psk::FrameSearchDesc, psk::FrameSearchPartial, 2> fpass;
+    // psk_soft_frame_cut_device: the formats of every slot (branches 0: never defined), their tables (256 bytes a slot, allocated
+    // with the first table; a control-plane-only handle keeps none); one record per frame of the last call; a ring of its own
+    // without partials.
+    psk::FrameFormat frame_format[psk::kFrameSlots] = {};
+    DeviceBuf<uint8_t> d_frame_tables;
+    Records<psk_soft_frame_cut_t> fcut;
+    bool fcut_called = false;
+    uint32_t fcut_n = 0;  // frames of the last call
+    PassRing<psk::FrameCutDesc, uint32_t, 2> cpass;
     // ingest pipeline of the host-buffer entry point (psk_soft_process_host)
     StageSlot stage[kStageSlots];
     std::unique_ptr<CopyPool> pool;
@@ -4793,6 +4810,338 @@ psk_soft_status psk_soft_rs_host(uint32_t gfpoly, uint32_t fcr, uint32_t prim, u
     rec->flags = PSK_SOFT_RS_DATA | (in->flags << 1);
     return PSK_SOFT_OK;
 }
+
+// ---- psk_soft_frame_search_device, psk_soft_frame_cut_device: frames as aligned bytes (include/psk_soft_frame.h, psk_frame.hip) ----
+// Between the viterbi call and the rs call, on the caller's stream.  The search is a pass of the reduction-pass layer with
+// partials (a fold over tiles of phases or windows, a join per stream); the cut is one launch with a ring of its own like the rs
+// entry's.  Nothing of the control plane, of the demodulator's state or of any other record is read or written.
+static const char *const kFrameWordFault = "null pointer, a slot above 15, length outside 1 .. 64, bits of word or care at length and above, or care == 0";
+static const char *const kFrameFormatFault =
+    "null pointer, a slot above 15, branches outside 1 .. 255, cell above 255 or branches (branches - 1) cell above 2^24";
+
+psk_soft_status psk_soft_frame_word_define(psk_soft_handle_t *h, uint32_t slot, uint32_t length, uint64_t word, uint64_t care)
+{
+    if (!h || slot >= psk::kFrameSlots || !psk::frame_word_ok(length, word, care))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_frame_word_define: ") + kFrameWordFault);
+    if (!h->dry)
+        PSK_TRY(h->fpass.wait());  // (the handle's last search launch is behind us)
+    h->frame_word[slot] = psk::FrameWord{word, care, length, psk::frame_popcount(care)};
+    return PSK_SOFT_OK;
+}
+
+static bool frame_search_skipped(const psk_soft_frame_search_in_t &k) { return !k.word || !k.bits; }
+
+// what is wrong with a stream that is not skipped, searched for a word of `ncare` care bits; nullptr: nothing
+static const char *frame_search_fault(const psk_soft_frame_search_in_t &k, uint32_t ncare)
+{
+    if (2ull * k.max_diff >= ncare)
+        return "2 max_diff must be below the number of care bits";
+    if (k.period > psk::kFrameMaxPeriod)
+        return "a period above 2^20";
+    if (k.n_bits < 1u || k.n_bits > psk::kFrameMaxBits)
+        return "n_bits outside 1 .. 2^31";
+    if (k.flags)
+        return "unknown flag bits";
+    if (k.pad[0] || k.pad[1] || k.pad[2])
+        return "pad must be zero";
+    return nullptr;
+}
+
+static uint32_t frame_windows(uint32_t n_bits, uint32_t length) { return n_bits >= length ? n_bits - length + 1u : 0u; }
+
+psk_soft_status psk_soft_frame_search_device(psk_soft_handle_t *h, uint32_t nstream, const psk_soft_frame_search_in_t *in, void *stream_v)
+{
+    if (!h || !in || !nstream || nstream > psk::kFrameMaxStreams)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_frame_search_device: null pointer or a number of streams outside 1 .. 2^20");
+    // the refusals, before anything is enqueued or any record changes
+    PieceCount parts;
+    for (uint32_t i = 0; i < nstream; i++) {
+        const psk_soft_frame_search_in_t &k = in[i];
+        if (frame_search_skipped(k))
+            continue;
+        const char *what = nullptr;
+        if (k.word > psk::kFrameSlots || !h->frame_word[k.word - 1u].length)
+            what = "a word slot above 15 or never defined (psk_soft_frame_word_define)";
+        else
+            what = frame_search_fault(k, h->frame_word[k.word - 1u].ncare);
+        uint32_t part0, n_tile;
+        if (!what && !parts.add(psk::frame_tiles(frame_windows(k.n_bits, h->frame_word[k.word - 1u].length), k.period), &part0, &n_tile))
+            what = "the call would have 2^31 tiles or more";
+        if (what) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "psk_soft_frame_search_device: stream %u: %s", i, what);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+    }
+    if (h->dry) {
+        h->fsearch.dry.assign(nstream, psk_soft_frame_search_t{});
+        for (uint32_t i = 0; i < nstream; i++) {
+            if (frame_search_skipped(in[i]))
+                continue;
+            const psk::FrameWord &w = h->frame_word[in[i].word - 1u];
+            psk_soft_frame_search_t &r = h->fsearch.dry[i];
+            r.flags = PSK_SOFT_FRAME_PLANNED, r.length = w.length, r.n_windows = frame_windows(in[i].n_bits, w.length);
+        }
+        h->fsearch_called = true, h->fsearch_n = nstream;
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: whatever made the bits must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    PSK_TRY(h->fsearch.grow(h->fpass, nstream));  // (the records are the last call's: nothing of them is kept)
+    auto &q = h->fpass.next();
+    PSK_TRY(h->fpass.claim(q, nstream, nstream / 4u + 256u));
+    parts = PieceCount{};
+    for (uint32_t i = 0; i < nstream; i++) {
+        psk::FrameSearchDesc &d = q.h_desc[i];
+        d = psk::FrameSearchDesc{};
+        d.part0 = (uint32_t)parts.total;  // (a stream without tiles shares its first partial with the next: the fold's search)
+        const psk_soft_frame_search_in_t &k = in[i];
+        if (frame_search_skipped(k))
+            continue;  // (its zero record)
+        const psk::FrameWord &w = h->frame_word[k.word - 1u];
+        // whole bytes of bit0 go into the pointer: the kernels count bits in 32
+        d.bits = k.bits + (k.bit0 >> 3), d.bit0 = k.bit0 & 7u;
+        d.word = w.word, d.care = w.care, d.length = w.length, d.ncare = w.ncare;
+        d.n_windows = frame_windows(k.n_bits, w.length), d.max_diff = k.max_diff, d.period = k.period;
+        d.flags = psk::kFrameData;
+        (void)parts.add(psk::frame_tiles(d.n_windows, d.period), &d.part0, &d.n_tile);
+    }
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = streams, tiles = workgroups of the fold)
+    return h->fpass.run(q, nstream, kAllRecords, parts.total, stream, [&]() -> psk_soft_status {
+        // the descriptors are up: the records are the new call's from here on, also if a launch below fails
+        h->fsearch_called = true, h->fsearch_n = nstream;
+        PSK_HIP(trace_launch(h, "frame_search", 0, 0, 0, nstream, parts.total, 0, 0, h->slot, stream));
+        PSK_HIP(psk::launch_frame_search(q.d_desc, nstream, (uint32_t)parts.total, q.d_part, h->fsearch.d, stream));
+        return PSK_SOFT_OK;
+    });
+}
+
+psk_soft_status psk_soft_get_frame_search(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_frame_search_t *rec)
+{
+    if (!h || !rec || !n || !h->fsearch_called || (uint64_t)first + n > h->fsearch_n)
+        return fail(PSK_SOFT_ERR_INVALID_ARG,
+                    "psk_soft_get_frame_search: null pointer, no psk_soft_frame_search_device call yet or a range beyond its streams");
+    return records_read(h, h->fsearch, h->fpass, first, n, rec);
+}
+
+// stream bit i of (bits, bit0)
+static inline uint32_t frame_bit(const uint8_t *bits, uint64_t bit0, uint64_t i)
+{
+    const uint64_t g = bit0 + i;
+    return (bits[g >> 3] >> (7u - (uint32_t)(g & 7u))) & 1u;
+}
+
+psk_soft_status psk_soft_frame_search_host(uint32_t length, uint64_t word, uint64_t care, const psk_soft_frame_search_in_t *in,
+                                           psk_soft_frame_search_t *rec)
+{
+    if (!in || !rec || !psk::frame_word_ok(length, word, care))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_frame_search_host: ") + kFrameWordFault);
+    *rec = psk_soft_frame_search_t{};
+    if (frame_search_skipped(*in))
+        return PSK_SOFT_OK;
+    const uint32_t ncare = psk::frame_popcount(care);
+    if (const char *what = frame_search_fault(*in, ncare))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_frame_search_host: ") + what);
+    const uint32_t n_windows = frame_windows(in->n_bits, length), P = in->period;
+    rec->flags = PSK_SOFT_FRAME_DATA, rec->length = length, rec->n_windows = n_windows;
+    if (!n_windows)
+        return PSK_SOFT_OK;
+    const uint64_t keep = length == 64u ? ~0ull : (1ull << length) - 1ull;
+    // one walk over the windows: the counts, the minimum, the score and the inverted hits of every phase; a second one lists
+    uint64_t win = 0, min_key = ~0ull;
+    for (uint32_t i = 0; i + 1u < length; i++) win = (win << 1) | frame_bit(in->bits, in->bit0, i);
+    std::vector<uint32_t> score(P), inverted(P);
+    for (uint32_t p = 0; p < n_windows; p++) {
+        win = ((win << 1) | frame_bit(in->bits, in->bit0, (uint64_t)p + length - 1u)) & keep;
+        const psk::FrameVerdict v = psk::frame_verdict(psk::frame_popcount((win ^ word) & care), ncare, in->max_diff);
+        const uint64_t key = psk::frame_min_key(v.diff, p, v.pol);
+        min_key = key < min_key ? key : min_key;
+        if (!v.hit)
+            continue;
+        rec->n_hit[v.pol]++;
+        if (P)
+            score[p % P]++, inverted[p % P] += v.pol;
+        else if (rec->n_listed < psk::kFrameHits)
+            rec->hits[rec->n_listed++] = psk_soft_frame_hit_t{p, (uint16_t)v.diff, (uint8_t)v.pol, 0};
+    }
+    rec->min_diff = (uint32_t)(min_key >> 40), rec->min_pos = (uint32_t)(min_key >> 1) & 0x7fffffffu, rec->min_pol = (uint32_t)min_key & 1u;
+    if (!P)
+        return PSK_SOFT_OK;
+    uint32_t best = 0;
+    for (uint32_t f = 1; f < P; f++) best = score[f] > score[best] ? f : best;
+    rec->best_phase = best, rec->best_score = score[best], rec->best_inv = inverted[best];
+    for (uint64_t p = best; p < n_windows && rec->n_listed < psk::kFrameHits && score[best]; p += P) {
+        uint64_t w = 0;
+        for (uint32_t i = 0; i < length; i++) w = (w << 1) | frame_bit(in->bits, in->bit0, p + i);
+        const psk::FrameVerdict v = psk::frame_verdict(psk::frame_popcount((w ^ word) & care), ncare, in->max_diff);
+        if (v.hit)
+            rec->hits[rec->n_listed++] = psk_soft_frame_hit_t{(uint32_t)p, (uint16_t)v.diff, (uint8_t)v.pol, 0};
+    }
+    return PSK_SOFT_OK;
+}
+
+uint32_t psk_soft_frame_tile(void) { return psk::kFrameTile; }
+
+psk_soft_status psk_soft_frame_format_define(psk_soft_handle_t *h, uint32_t slot, uint32_t branches, uint32_t cell, const uint8_t *table)
+{
+    if (!h || slot >= psk::kFrameSlots || !psk::frame_format_ok(branches, cell))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_frame_format_define: ") + kFrameFormatFault);
+    if (!h->dry) {
+        PSK_HIP(hipSetDevice(h->device));
+        PSK_TRY(h->cpass.wait());  // (no launch is still reading the slot)
+        if (table) {
+            if (!h->d_frame_tables)
+                PSK_TRY(alloc_zeroed(h->d_frame_tables, (size_t)psk::kFrameSlots * 256u, "frame tables"));
+            PSK_HIP(hipMemcpy(h->d_frame_tables + (size_t)slot * 256u, table, 256u, hipMemcpyHostToDevice));
+        }
+    }
+    h->frame_format[slot] = psk::FrameFormat{branches, cell, table != nullptr};
+    return PSK_SOFT_OK;
+}
+
+// what is wrong with a frame that is not skipped, cut with a format of `branches` branches; nullptr: nothing
+static const char *frame_cut_fault(const psk_soft_frame_cut_in_t &k, uint32_t branches)
+{
+    if (k.branch0 >= branches)
+        return "branch0 at or above the format's branches";
+    if (k.n_bytes < 1u || k.n_bytes > psk::kFrameMaxBytes)
+        return "n_bytes outside 1 .. 2^20";
+    if (k.flags & ~psk::kFrameCutFlagMask)
+        return "unknown flag bits";
+    if (k.pad[0] || k.pad[1])
+        return "pad must be zero";
+    if (!k.out)
+        return "out is null";
+    return nullptr;
+}
+
+static const psk::FrameFormat kFramePlain = {1u, 0u, false};
+
+psk_soft_status psk_soft_frame_cut_device(psk_soft_handle_t *h, uint32_t nframe, const psk_soft_frame_cut_in_t *in, void *stream_v)
+{
+    if (!h || !in || !nframe || nframe > psk::kFrameMaxFrames)
+        return fail(PSK_SOFT_ERR_INVALID_ARG, "psk_soft_frame_cut_device: null pointer or a number of frames outside 1 .. 2^20");
+    // the refusals, before anything is enqueued or any record changes
+    for (uint32_t i = 0; i < nframe; i++) {
+        const psk_soft_frame_cut_in_t &k = in[i];
+        if (!k.bits)
+            continue;
+        const char *what = nullptr;
+        if (k.format > psk::kFrameSlots || (k.format && !h->frame_format[k.format - 1u].branches))
+            what = "a format slot above 15 or never defined (psk_soft_frame_format_define)";
+        else
+            what = frame_cut_fault(k, k.format ? h->frame_format[k.format - 1u].branches : 1u);
+        if (what) {
+            char buf[200];
+            std::snprintf(buf, sizeof buf, "psk_soft_frame_cut_device: frame %u: %s", i, what);
+            return fail(PSK_SOFT_ERR_INVALID_ARG, buf);
+        }
+    }
+    if (h->dry) {
+        h->fcut.dry.assign(nframe, psk_soft_frame_cut_t{});
+        for (uint32_t i = 0; i < nframe; i++) {
+            if (!in[i].bits)
+                continue;
+            const psk::FrameFormat &f = in[i].format ? h->frame_format[in[i].format - 1u] : kFramePlain;
+            psk_soft_frame_cut_t &r = h->fcut.dry[i];
+            r.n_bytes = in[i].n_bytes, r.span = psk::frame_span(f.branches, f.cell, in[i].branch0, in[i].n_bytes);
+            r.flags = PSK_SOFT_FRAME_PLANNED | (in[i].flags << 1);
+        }
+        h->fcut_called = true, h->fcut_n = nframe;
+        return PSK_SOFT_OK;
+    }
+    PSK_HIP(hipSetDevice(h->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : h->stream;
+    // (a deferred call's classes end on the side streams: whatever made the bits must be complete)
+    PSK_HIP(deferred_join(h, stream));
+    const uint32_t grid = nframe < psk::kFrameCutGrid ? nframe : psk::kFrameCutGrid;
+    PSK_TRY(h->fcut.grow(h->cpass, nframe));  // (the records are the last call's: nothing of them is kept)
+    auto &q = h->cpass.next();
+    PSK_TRY(h->cpass.claim(q, nframe, nframe / 4u + 256u));
+    for (uint32_t i = 0; i < nframe; i++) {
+        psk::FrameCutDesc &d = q.h_desc[i];
+        d = psk::FrameCutDesc{};
+        const psk_soft_frame_cut_in_t &k = in[i];
+        if (!k.bits)
+            continue;  // (its zero record)
+        const psk::FrameFormat &f = k.format ? h->frame_format[k.format - 1u] : kFramePlain;
+        // whole bytes of bit go into the pointer: the kernel counts bits in 32
+        d.bits = k.bits + (k.bit >> 3), d.bit = k.bit & 7u, d.out = k.out;
+        d.n_bytes = k.n_bytes, d.branches = f.branches, d.stride = psk::frame_stride(f.branches, f.cell), d.branch0 = k.branch0;
+        d.flags = psk::kFrameData | (k.flags << 1);
+        d.table = f.table ? k.format : 0u;
+        d.span = psk::frame_span(f.branches, f.cell, k.branch0, k.n_bytes);
+    }
+    // (PSK_SOFT_TRACE_LAUNCHES, trace_launch: cnt = frames, tiles = workgroups)
+    return h->cpass.run(q, nframe, kAllRecords, 0, stream, [&]() -> psk_soft_status {
+        // the descriptors are up: the records are the new call's from here on, also if the launch below fails
+        h->fcut_called = true, h->fcut_n = nframe;
+        PSK_HIP(trace_launch(h, "frame_cut", 0, 0, 0, nframe, grid, 0, 0, h->slot, stream));
+        PSK_HIP(psk::launch_frame_cut(q.d_desc, nframe, grid, h->d_frame_tables, h->fcut.d, stream));
+        return PSK_SOFT_OK;
+    });
+}
+
+psk_soft_status psk_soft_get_frame_cut(psk_soft_handle_t *h, uint32_t first, uint32_t n, psk_soft_frame_cut_t *rec)
+{
+    if (!h || !rec || !n || !h->fcut_called || (uint64_t)first + n > h->fcut_n)
+        return fail(PSK_SOFT_ERR_INVALID_ARG,
+                    "psk_soft_get_frame_cut: null pointer, no psk_soft_frame_cut_device call yet or a range beyond its frames");
+    return records_read(h, h->fcut, h->cpass, first, n, rec);
+}
+
+psk_soft_status psk_soft_frame_cut_host(uint32_t branches, uint32_t cell, const uint8_t *table, const psk_soft_frame_cut_in_t *in,
+                                        psk_soft_frame_cut_t *rec)
+{
+    if (!in || !rec || !psk::frame_format_ok(branches, cell))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_frame_cut_host: ") + kFrameFormatFault);
+    *rec = psk_soft_frame_cut_t{};
+    if (!in->bits)
+        return PSK_SOFT_OK;
+    if (const char *what = frame_cut_fault(*in, branches))
+        return fail(PSK_SOFT_ERR_INVALID_ARG, std::string("psk_soft_frame_cut_host: ") + what);
+    const uint32_t stride = psk::frame_stride(branches, cell);
+    const uint32_t inv = (in->flags & PSK_SOFT_FRAME_INVERT) ? 0xffu : 0u;
+    uint32_t ones = 0;
+    for (uint32_t i = 0; i < in->n_bytes; i++) {
+        const uint64_t q = psk::frame_source(i, in->branch0, branches, stride);
+        uint32_t b = 0;
+        for (uint32_t j = 0; j < 8u; j++) b = (b << 1) | frame_bit(in->bits, in->bit, 8u * q + j);
+        b ^= inv;
+        b = table ? table[b] : b;
+        in->out[i] = (uint8_t)b;
+        ones += psk::frame_popcount(b);
+    }
+    rec->flags = PSK_SOFT_FRAME_DATA | (in->flags << 1);
+    rec->n_bytes = in->n_bytes, rec->span = psk::frame_span(branches, cell, in->branch0, in->n_bytes), rec->n_ones = ones;
+    return PSK_SOFT_OK;
+}
+
+uint64_t psk_soft_frame_span(uint32_t branches, uint32_t cell, uint32_t branch0, uint32_t n_bytes)
+{
+    if (!psk::frame_format_ok(branches, cell) || branch0 >= branches || n_bytes < 1u || n_bytes > psk::kFrameMaxBytes)
+        return 0;
+    return psk::frame_span(branches, cell, branch0, n_bytes);
+}
+
+uint64_t psk_soft_frame_search_bytes(void) { return sizeof(psk_soft_frame_search_t); }
+uint64_t psk_soft_frame_search_in_bytes(void) { return sizeof(psk_soft_frame_search_in_t); }
+uint64_t psk_soft_frame_cut_bytes(void) { return sizeof(psk_soft_frame_cut_t); }
+uint64_t psk_soft_frame_cut_in_bytes(void) { return sizeof(psk_soft_frame_cut_in_t); }
+static_assert(sizeof(psk_soft_frame_search_t) == 192 && sizeof(psk_soft_frame_search_in_t) == 48 && sizeof(psk_soft_frame_cut_t) == 32 &&
+                  sizeof(psk_soft_frame_cut_in_t) == 48 && sizeof(psk_soft_frame_hit_t) == 8,
+              "include/psk_soft_frame.h states the sizes");
+static_assert(offsetof(psk_soft_frame_search_t, n_hit) == 12 && offsetof(psk_soft_frame_search_t, min_diff) == 20 &&
+                  offsetof(psk_soft_frame_search_t, best_phase) == 32 && offsetof(psk_soft_frame_search_t, n_listed) == 44 &&
+                  offsetof(psk_soft_frame_search_t, hits) == 64 && offsetof(psk_soft_frame_hit_t, diff) == 4 &&
+                  offsetof(psk_soft_frame_hit_t, pol) == 6,
+              "psk_frame.hip stores the search record as sixteen words and sixteen hits");
+static_assert(offsetof(psk_soft_frame_cut_t, span) == 8 && offsetof(psk_soft_frame_cut_t, n_ones) == 12,
+              "psk_frame.hip stores the cut record as eight words");
+static_assert(PSK_SOFT_FRAME_DATA == psk::kFrameData && PSK_SOFT_FRAME_REC_INVERT == PSK_SOFT_FRAME_INVERT << 1,
+              "the cut record's flags are the frame's shifted left by one");
 
 // ---- host-buffer path: the ingest pipeline --------------------------
 // The batch is cut into chunks of channels of about `stage_bytes` of input each.  Per chunk: the

@@ -419,6 +419,95 @@ class RsRecord(ctypes.Structure):
         return sum(self.n_bit[j] for j in range(self.depth))
 
 
+FRAME_INVERT = 1  # FrameCutIn.flags
+# the frame records' flags: DATA or PLANNED; in the cut's ORed with the frame's flags shifted left by one
+FRAME_DATA, FRAME_REC_INVERT, FRAME_PLANNED = 1, 2, 128
+FRAME_SLOTS, FRAME_MAX_STREAMS, FRAME_MAX_FRAMES, FRAME_MAX_PERIOD, FRAME_MAX_BITS, FRAME_MAX_BYTES = 16, 1 << 20, 1 << 20, 1 << 20, 1 << 31, 1 << 20
+FRAME_MAX_DELAY, FRAME_HITS = 1 << 24, 16
+# the usual words and formats: (length, word, care) and (branches, cell)
+FRAME_CCSDS_ASM = (32, 0x1ACFFC1D, 0xFFFFFFFF)
+FRAME_DVB_SYNC = (8, 0x47, 0xFF)
+FRAME_DVB_PERIOD = 1632
+FRAME_DVB_INTERLEAVER = (12, 17)
+
+
+class FrameSearchIn(ctypes.Structure):
+    """psk_soft_frame_search_in_t: one stream of a frame_search_device call -- a DEVICE pointer to its packed bits (any alignment),
+    the bit at which it starts, its length in bits, word = 1 + the slot of the word (0: skipped), max_diff and the period (0: no
+    fold)."""
+
+    _fields_ = [
+        ("bits", ctypes.c_void_p),
+        ("bit0", ctypes.c_uint64),
+        ("n_bits", ctypes.c_uint32),
+        ("word", ctypes.c_uint32),
+        ("max_diff", ctypes.c_uint32),
+        ("period", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 3),
+    ]
+
+
+class FrameHit(ctypes.Structure):
+    """psk_soft_frame_hit_t: a listed hit -- the window's first stream bit, its diff and its polarity (1: inverted)."""
+
+    _fields_ = [("pos", ctypes.c_uint32), ("diff", ctypes.c_uint16), ("pol", ctypes.c_uint8), ("zero", ctypes.c_uint8)]
+
+
+class FrameSearchRecord(ctypes.Structure):
+    """psk_soft_frame_search_t: the record of one stream of the last frame_search_device call."""
+
+    _fields_ = [
+        ("flags", ctypes.c_uint32),
+        ("length", ctypes.c_uint32),
+        ("n_windows", ctypes.c_uint32),
+        ("n_hit", ctypes.c_uint32 * 2),
+        ("min_diff", ctypes.c_uint32),
+        ("min_pos", ctypes.c_uint32),
+        ("min_pol", ctypes.c_uint32),
+        ("best_phase", ctypes.c_uint32),
+        ("best_score", ctypes.c_uint32),
+        ("best_inv", ctypes.c_uint32),
+        ("n_listed", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 4),
+        ("hits", FrameHit * 16),
+    ]
+
+    @property
+    def listed(self):
+        """the listed hits as (pos, diff, pol) tuples"""
+        return [(int(k.pos), int(k.diff), int(k.pol)) for k in self.hits[: self.n_listed]]
+
+
+class FrameCutIn(ctypes.Structure):
+    """psk_soft_frame_cut_in_t: one frame of a frame_cut_device call -- a DEVICE pointer to the stream's packed bits, the bit at
+    which the frame starts, a DEVICE pointer to its n_bytes output bytes, format = 1 + the slot of the format (0: plain), the
+    branch of its first byte and flags (FRAME_INVERT)."""
+
+    _fields_ = [
+        ("bits", ctypes.c_void_p),
+        ("bit", ctypes.c_uint64),
+        ("out", ctypes.c_void_p),
+        ("n_bytes", ctypes.c_uint32),
+        ("format", ctypes.c_uint32),
+        ("branch0", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 2),
+    ]
+
+
+class FrameCutRecord(ctypes.Structure):
+    """psk_soft_frame_cut_t: the record of one frame of the last frame_cut_device call."""
+
+    _fields_ = [
+        ("flags", ctypes.c_uint32),
+        ("n_bytes", ctypes.c_uint32),
+        ("span", ctypes.c_uint32),
+        ("n_ones", ctypes.c_uint32),
+        ("pad", ctypes.c_uint32 * 4),
+    ]
+
+
 QUALITY_FIELDS = tuple(k for k, _ in Quality._fields_ if k != "pad")
 
 # every symbol include/psk_soft_rs.h declares (the psk_soft_rs_ family; psk_soft_hip.h includes that header)
@@ -430,6 +519,24 @@ RS_EXPORTS = (
     "psk_soft_rs_encode_host",
     "psk_soft_rs_bytes",
     "psk_soft_rs_in_bytes",
+)
+
+# every symbol include/psk_soft_frame.h declares (the psk_soft_frame_ family; psk_soft_hip.h includes that header)
+FRAME_EXPORTS = (
+    "psk_soft_frame_word_define",
+    "psk_soft_frame_search_device",
+    "psk_soft_get_frame_search",
+    "psk_soft_frame_search_host",
+    "psk_soft_frame_tile",
+    "psk_soft_frame_format_define",
+    "psk_soft_frame_cut_device",
+    "psk_soft_get_frame_cut",
+    "psk_soft_frame_cut_host",
+    "psk_soft_frame_span",
+    "psk_soft_frame_search_bytes",
+    "psk_soft_frame_search_in_bytes",
+    "psk_soft_frame_cut_bytes",
+    "psk_soft_frame_cut_in_bytes",
 )
 
 # every symbol include/psk_soft_hip.h declares
@@ -683,6 +790,22 @@ def load():
     L.psk_soft_rs_bytes.restype = u64
     L.psk_soft_rs_in_bytes.argtypes = []
     L.psk_soft_rs_in_bytes.restype = u64
+    L.psk_soft_frame_word_define.argtypes = [vp, u32, u32, u64, u64]
+    L.psk_soft_frame_search_device.argtypes = [vp, u32, ctypes.POINTER(FrameSearchIn), vp]
+    L.psk_soft_get_frame_search.argtypes = [vp, u32, u32, ctypes.POINTER(FrameSearchRecord)]
+    L.psk_soft_frame_search_host.argtypes = [u32, u64, u64, ctypes.POINTER(FrameSearchIn), ctypes.POINTER(FrameSearchRecord)]
+    L.psk_soft_frame_tile.argtypes = []
+    L.psk_soft_frame_tile.restype = u32
+    L.psk_soft_frame_format_define.argtypes = [vp, u32, u32, u32, vp]
+    L.psk_soft_frame_cut_device.argtypes = [vp, u32, ctypes.POINTER(FrameCutIn), vp]
+    L.psk_soft_get_frame_cut.argtypes = [vp, u32, u32, ctypes.POINTER(FrameCutRecord)]
+    L.psk_soft_frame_cut_host.argtypes = [u32, u32, vp, ctypes.POINTER(FrameCutIn), ctypes.POINTER(FrameCutRecord)]
+    L.psk_soft_frame_span.argtypes = [u32, u32, u32, u32]
+    L.psk_soft_frame_span.restype = u64
+    for _n in ("search", "search_in", "cut", "cut_in"):
+        _f = getattr(L, "psk_soft_frame_%s_bytes" % _n)
+        _f.argtypes = []
+        _f.restype = u64
     _lib = L
     return L
 
@@ -1071,6 +1194,65 @@ def _rs_in(s):
         return s
     s = tuple(s)
     return RsIn(s[0], s[1], s[2], s[3] if len(s) > 3 else 0, (ctypes.c_uint32 * 2)(0, 0))
+
+
+def _frame_table(table):
+    if table is None:
+        return None, None
+    t = np.ascontiguousarray(table, np.uint8).reshape(-1)
+    if t.size != 256:
+        raise ValueError("a table is 256 bytes")
+    return t, t.ctypes.data
+
+
+def _u32x(n):
+    return (ctypes.c_uint32 * n)(*([0] * n))
+
+
+def frame_search_host(length, word, care, bits, n_bits, bit0=0, max_diff=0, period=0):
+    """psk_soft_frame_search_host: one stream on the host.  bits: the packed bytes that hold the stream bits bit0 .. bit0 + n_bits - 1.
+    Returns the FrameSearchRecord."""
+    x = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+    if 8 * x.size < int(bit0) + int(n_bits):
+        raise ValueError("fewer bytes than the stream's bits")
+    k = FrameSearchIn(x.ctypes.data if x.size else None, int(bit0), int(n_bits), 1, int(max_diff), int(period), 0, _u32x(3))
+    rec = FrameSearchRecord()
+    _check(load().psk_soft_frame_search_host(int(length), int(word), int(care), ctypes.byref(k), ctypes.byref(rec)))
+    return rec
+
+
+def frame_span(branches, cell, branch0, n_bytes):
+    """psk_soft_frame_span: the stream bytes from `bit` that a frame of n_bytes bytes touches (0: refused arguments)."""
+    return int(load().psk_soft_frame_span(int(branches), int(cell), int(branch0), int(n_bytes)))
+
+
+def frame_cut_host(branches, cell, bits, bit, n_bytes, branch0=0, table=None, flags=0):
+    """psk_soft_frame_cut_host: one frame on the host.  bits: the packed bytes of the stream, which must hold frame_span(...) bytes
+    from `bit`.  Returns (the n_bytes output bytes, the FrameCutRecord)."""
+    x = np.ascontiguousarray(bits, np.uint8).reshape(-1)
+    span = frame_span(branches, cell, branch0, n_bytes)
+    if span and 8 * x.size < int(bit) + 8 * span:
+        raise ValueError("fewer bytes than the frame's span")
+    t, tp = _frame_table(table)
+    out = np.zeros(max(int(n_bytes), 1) if span else 1, np.uint8)
+    k = FrameCutIn(x.ctypes.data if x.size else None, int(bit), out.ctypes.data, int(n_bytes), 0, int(branch0), int(flags), _u32x(2))
+    rec = FrameCutRecord()
+    _check(load().psk_soft_frame_cut_host(int(branches), int(cell), tp, ctypes.byref(k), ctypes.byref(rec)))
+    return out[: int(rec.n_bytes)].copy(), rec
+
+
+def _frame_search_in(s):
+    if isinstance(s, FrameSearchIn):
+        return s
+    s = tuple(s) + (0, 0)
+    return FrameSearchIn(s[0], s[1], s[2], s[3], s[4], s[5], 0, _u32x(3))
+
+
+def _frame_cut_in(s):
+    if isinstance(s, FrameCutIn):
+        return s
+    s = tuple(s) + (0, 0, 0)
+    return FrameCutIn(s[0], s[1], s[2], s[3], s[4], s[5], s[6], _u32x(2))
 
 
 class Handle:
@@ -1554,6 +1736,51 @@ class Handle:
         waits for that call."""
         arr = (RsRecord * n)()
         _check(self._L.psk_soft_get_rs(self._h, int(first), n, arr))
+        return arr
+
+    def frame_word_define(self, slot, length, word, care=None):
+        """psk_soft_frame_word_define: the word of slot `slot` (0 .. 15) -- its length in bits (1 .. 64), the word (its first bit in
+        stream order the most significant of the `length`) and the care mask (None: every bit); a stream names it as
+        FrameSearchIn.word = slot + 1."""
+        if care is None:
+            care = (1 << int(length)) - 1 if 1 <= int(length) <= 64 else 0
+        _check(self._L.psk_soft_frame_word_define(self._h, int(slot), int(length), int(word), int(care)))
+
+    def frame_search_device(self, ins, stream=None):
+        """A known word searched in streams of packed bits (psk_soft_frame_search_device): leaves a FrameSearchRecord per stream;
+        touches no demodulator state.  ins: a ctypes FrameSearchIn array or a sequence of FrameSearchIn / tuples (bits, bit0,
+        n_bits, word[, max_diff[, period]])."""
+        if not isinstance(ins, ctypes.Array):
+            ins = (FrameSearchIn * len(ins))(*[_frame_search_in(s) for s in ins])
+        _check(self._L.psk_soft_frame_search_device(self._h, len(ins), ins, ctypes.c_void_p(stream or 0)))
+
+    def frame_search_records(self, first=0, n=1):
+        """The FrameSearchRecord records of the streams [first, first + n) of the last frame_search_device call
+        (psk_soft_get_frame_search), a ctypes array; waits for that call."""
+        arr = (FrameSearchRecord * n)()
+        _check(self._L.psk_soft_get_frame_search(self._h, int(first), n, arr))
+        return arr
+
+    def frame_format_define(self, slot, branches=1, cell=0, table=None):
+        """psk_soft_frame_format_define: the format of slot `slot` (0 .. 15) -- the branches and the cell of the convolutional byte
+        deinterleaver (1 or 0: none) and the 256-byte table every byte goes through (None: the identity), copied; a frame names
+        it as FrameCutIn.format = slot + 1."""
+        t, tp = _frame_table(table)
+        _check(self._L.psk_soft_frame_format_define(self._h, int(slot), int(branches), int(cell), tp))
+
+    def frame_cut_device(self, ins, stream=None):
+        """Byte frames cut from streams of packed bits (psk_soft_frame_cut_device): writes n_bytes bytes per frame to its `out` and
+        leaves a FrameCutRecord per frame; touches no demodulator state.  ins: a ctypes FrameCutIn array or a sequence of
+        FrameCutIn / tuples (bits, bit, out, n_bytes[, format[, branch0[, flags]]])."""
+        if not isinstance(ins, ctypes.Array):
+            ins = (FrameCutIn * len(ins))(*[_frame_cut_in(s) for s in ins])
+        _check(self._L.psk_soft_frame_cut_device(self._h, len(ins), ins, ctypes.c_void_p(stream or 0)))
+
+    def frame_cut_records(self, first=0, n=1):
+        """The FrameCutRecord records of the frames [first, first + n) of the last frame_cut_device call (psk_soft_get_frame_cut),
+        a ctypes array; waits for that call."""
+        arr = (FrameCutRecord * n)()
+        _check(self._L.psk_soft_get_frame_cut(self._h, int(first), n, arr))
         return arr
 
     def sync_history(self, ch):
